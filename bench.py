@@ -28,11 +28,20 @@ import numpy as np
 import torch
 
 
+def _count(least):
+    def conv(s):
+        v = int(s)
+        if v < least:
+            raise argparse.ArgumentTypeError("must be >= %d, got %d" % (least, v))
+        return v
+    return conv
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=30)
-    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--steps", type=_count(1), default=30, help="timed steps")
+    ap.add_argument("--warmup", type=_count(0), default=10, help="untimed steps before them")
     ap.add_argument("--workload", default=None, help="config2 | config3 | config4 (default: config3, config4 when --gpus > 1)")
     ap.add_argument("--features", default=None, help="orb | sift (default: orb; sift for config5, BASELINE.json configs[4])")
     ap.add_argument("--pipeline", default="hot_path", choices=["hot_path", "hot_path_plus_seams", "reference"],
@@ -46,6 +55,9 @@ def parse():
     ap.add_argument("--roofline-launches", type=int, default=200)
     ap.add_argument("--roofline-only", action="store_true",
                     help="run only the roofline leg (for a rocprofv3 --stats pass in which no other kernel overlaps the warp kernel)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32 / float64, at most 64 MB in all; larger "
+                         "outputs as a fixed, seeded sample of their rows); N > 1: rank 0's")
     return ap.parse_args()
 
 
@@ -187,6 +199,10 @@ def main():
         dt = float(tt.item())
     ms_per_step = dt / args.steps * 1e3
     value = n * args.steps / dt
+    if args.dump_outputs and rank == 0:
+        # at once: the legs below run the job's blender and feature finder again, whose buffers the last step's results may share
+        nbytes = dump_outputs(args.dump_outputs, job_outputs(out))
+        log("bench.py: the last timed step's outputs, %.1f MB, written to %s" % (nbytes / 1e6, args.dump_outputs))
 
     # N > 1: rank 0 also runs the SAME job alone (no sharding) so that the strong-scaling base of this workload
     # is on the same line; the other ranks wait at the barrier below.  Outside the timed region.
@@ -603,6 +619,101 @@ def cpu_baseline(cams, workload, frames_dev):
                          sp["compositing"], total),
             "single_thread": {"value": round(len(sub) / t1, 4), "unit": "frames/s", "cores": 1,
                               "sample": "frames %d..%d of the same job as a %d-frame job (6 pairs) on one thread: %.2fs" % (sub[0], sub[-1], len(sub), t1)}}
+
+
+DUMP_BUDGET = 64 * 10 ** 6
+# bytes per group of --dump-outputs, its sample index included; the remaining 4 MB hold the small arrays (n x n tables)
+DUMP_GROUP_BUDGET = {"pano": 36 * 10 ** 6, "keypoint": 16 * 10 ** 6, "match": 8 * 10 ** 6}
+DUMP_SEED = {"pano": 0, "keypoint": 1, "match": 2}
+# arrays whose rows are sampled together (rows are pixels, keypoints, matches)
+DUMP_GROUPS = {"pano": ("pano", "mask"), "keypoint": ("keypoints", "descriptors"), "match": ("matches",)}
+
+
+def job_outputs(out):
+    """What StitchJob.run returned, as host arrays: float32 (values a float32 holds exactly), float64, and the panorama in its own
+    integer types (dump_outputs casts it to float32 after sampling).
+      pano [H*W, 3] (16SC3), mask [H*W], pano_size [W, H], num_bands, indices (the kept frames), confidence [n, n];
+      feature_counts [n]; keypoints [sum, 7]: frame, x, y, size, angle, response, octave; descriptors [sum, 32 (ORB) | 128 (SIFT)];
+      match_counts, num_inliers [n, n]; homographies [n, n, 3, 3] (zeros where
+      has_homography [n, n] is 0); matches [sum, 6]: src, dst, query_idx, train_idx,
+      distance, inlier -- entry (i, j) of the pairwise table for every i != j, in that order."""
+    pano = out["pano"].cpu().numpy()
+    mask = out["mask"].cpu().numpy()
+    h, w = mask.shape[:2]
+    res = {"pano": pano.reshape(h * w, 3), "mask": mask.reshape(h * w),
+           "pano_size": np.array([w, h], np.float64), "num_bands": np.array([out["num_bands"]], np.float64),
+           "indices": np.array(out["indices"], np.float64),
+           "confidence": np.asarray(out["confidence"].cpu().numpy() if torch.is_tensor(out["confidence"]) else out["confidence"], np.float64)}
+    counts, kps, desc = [], [], []
+    for i, f in enumerate(out["features"]):       # (SIFT's packed octave stays below 2^24: exact in float32)
+        k, d = f.download()
+        counts.append(len(k))
+        kps.append(np.stack([np.full(len(k), i, np.float32)] + [k[c].astype(np.float32) for c in k.dtype.names], axis=1))
+        desc.append(d.astype(np.float32))
+    res["feature_counts"] = np.array(counts, np.float64)
+    res["keypoints"] = np.concatenate(kps)
+    res["descriptors"] = np.concatenate(desc)
+    pm = out["matches"]
+    n = pm.n
+    res["match_counts"] = np.zeros((n, n), np.float64)
+    res["num_inliers"] = np.zeros((n, n), np.float64)
+    res["homographies"] = np.zeros((n, n, 3, 3), np.float64)
+    res["has_homography"] = np.zeros((n, n), np.float64)
+    rows = [np.zeros((0, 6), np.float32)]
+    for i in range(n):
+        for j in range(n):
+            m = pm[i * n + j]
+            if i == j or m.src_img_idx < 0:
+                continue                    # the diagonal, or a pair another rank matched
+            res["match_counts"][i, j] = len(m.matches)
+            res["num_inliers"][i, j] = m.num_inliers
+            if m.H is not None:
+                res["homographies"][i, j] = m.H
+                res["has_homography"][i, j] = 1
+            # a pair the matcher did not run RANSAC on carries no inlier mask
+            inl = m.inliers_mask if len(m.inliers_mask) == len(m.matches) else np.zeros(len(m.matches), np.uint8)
+            rows.append(np.stack([np.full(len(m.matches), i), np.full(len(m.matches), j), m.matches["query_idx"], m.matches["train_idx"],
+                                  m.matches["distance"], inl], axis=1).astype(np.float32))
+    res["matches"] = np.concatenate(rows)
+    return res
+
+
+def dump_outputs(dirname, arrays, budget=DUMP_BUDGET, group_budget=None):
+    """Write `arrays` as dirname/<name>.npy; returns the bytes written.  The arrays of each DUMP_GROUPS group share their rows:
+    when the group exceeds its budget, the same fixed, seeded sample of rows is kept of each (sorted, drawn with replacement
+    and deduplicated: a function of the row count alone), and <group>_sample.npy holds the indices of the rows kept -- all of
+    them when the group fits.  Every value written is finite.  The same arrays give the same files."""
+    def float_type(dt):        # integers of up to 16 bits are exact in float32
+        if dt in (np.float32, np.float64):
+            return dt
+        if dt.kind in "iub" and dt.itemsize <= 2:
+            return np.dtype(np.float32)
+        raise TypeError("%s cannot be written as float32 / float64 exactly" % dt)
+    group_budget = group_budget or DUMP_GROUP_BUDGET
+    out = dict(arrays)
+    for g, names in DUMP_GROUPS.items():
+        nrows = len(out[names[0]])
+        row_bytes = 8 + sum(float_type(out[nm].dtype).itemsize * int(np.prod(out[nm].shape[1:])) for nm in names)
+        if nrows * row_bytes > group_budget[g]:
+            rng = np.random.default_rng(DUMP_SEED[g])
+            idx = np.unique(rng.integers(0, nrows, group_budget[g] // row_bytes))
+            for nm in names:
+                out[nm] = out[nm][idx]
+        else:
+            idx = np.arange(nrows)
+        out[g + "_sample"] = idx.astype(np.float64)
+    total = 0
+    for nm, a in out.items():
+        out[nm] = a = np.ascontiguousarray(a, float_type(a.dtype))
+        if not np.isfinite(a).all():
+            raise ValueError("%s holds values that are not finite" % nm)
+        total += a.nbytes + 128                 # + the .npy header
+    if total > budget:
+        raise ValueError("the outputs take %d bytes, more than %d" % (total, budget))
+    os.makedirs(dirname, exist_ok=True)
+    for nm, a in out.items():
+        np.save(os.path.join(dirname, nm + ".npy"), a)
+    return total
 
 
 def _result_roi(rois):
