@@ -44,13 +44,7 @@ int mis_host_stage(MisContext* ctx, size_t bytes, void** out) {
 
 int mis_aux_stream(MisContext* ctx, int k, hipStream_t* out) {
     MIS_CHECK(ctx, k == 0 || k == 1, MIS_E_INVALID, "auxiliary stream index %d", k);
-    if (!ctx->aux[k]) {
-        // MIS_AUX_PRIO=1: the auxiliary streams (the matcher's side chains) at the device's most urgent priority
-        static const bool urgent = getenv("MIS_AUX_PRIO") && atoi(getenv("MIS_AUX_PRIO")) > 0;
-        int least = 0, greatest = 0;
-        if (urgent && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess) MIS_HIP(ctx, hipStreamCreateWithPriority(&ctx->aux[k], hipStreamNonBlocking, greatest));
-        else MIS_HIP(ctx, hipStreamCreateWithFlags(&ctx->aux[k], hipStreamNonBlocking));
-    }
+    if (!ctx->aux[k]) MIS_HIP(ctx, hipStreamCreateWithFlags(&ctx->aux[k], hipStreamNonBlocking));
     *out = ctx->aux[k];
     return MIS_OK;
 }

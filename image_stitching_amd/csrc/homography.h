@@ -45,13 +45,19 @@ struct HomoBatch {
 int homo_batch_reserve(MisContext* ctx, HomoBatch* b, int count, long long points, int max_iters);
 int homo_batch_debug_states(MisContext* ctx, const HomoBatch* b, int* out, int cap);
 void homo_batch_release(HomoBatch* b);
-// `calls` (device array of b->count entries) must be filled before this is enqueued on ctx->stream.
-// phases: 0 = hypotheses [0, PHASE0) + replay + tails of the problems that finish there; 1 = the rest; 2 = both;
-// 3 / 6 = like 0 / 1 without the tails (left pending), 4 = the pending tails of phase 0 (any stream, concurrently with a phases = 1 run);
-// 10 + 2 w / 11 + 2 w = the pending tails of phase w in two steps: mask + inlier compaction / DLT + LM refinement.
-// `stream` = nullptr: the context's stream.
-// Optional ordering hooks of a run: rec is recorded behind the second phase's draw_kernel (rec_pos 0), its 4-point solves (1) or the
-// FIRST phase's draw (2); rec_hyp0 behind the first phase's solves; the second phase's solves wait for wait_hyp1.
-struct HomoSync { hipEvent_t rec = nullptr; int rec_pos = 0; hipEvent_t rec_hyp0 = nullptr; hipEvent_t wait_hyp1 = nullptr; };
-int homo_batch_run(MisContext* ctx, HomoBatch* b, double thresh, int max_iters, double confidence, int phases = 2, hipStream_t stream = nullptr,
-                   const HomoSync* sync = nullptr);
+// What one homo_batch_run call enqueues.  The matcher splits a batch into chains on several streams: a replay-only run of a RANSAC
+// phase leaves the tails of the problems that end there pending, and the mask / refinement runs finish those of one phase.
+enum HomoRun {
+    HOMO_BOTH_PHASES = 2,     // hypotheses [0, PHASE0), replay and tails of the problems that finish there, then the same for the rest
+    HOMO_PHASE0_REPLAY = 3,   // hypotheses [0, PHASE0) and replay; the finishers' tails are left pending
+    HOMO_PHASE1_REPLAY = 6,   // hypotheses [PHASE0, max_iters) and replay; the finishers' tails are left pending
+    HOMO_TAIL0_MASK = 10,     // the pending tails of phase w: 10 + 2 w = inlier mask + compaction, 11 + 2 w = DLT + LM refinement
+    HOMO_TAIL0_REFINE = 11,
+    HOMO_TAIL1_MASK = 12,
+    HOMO_TAIL1_REFINE = 13,
+};
+// `calls` (device array of b->count entries) must be filled before this is enqueued on `stream` (nullptr: the context's stream).
+// Optional ordering hook of a run: rec is recorded behind the draw_kernel of the second phase (rec_pos 0) or of the first (2).
+struct HomoSync { hipEvent_t rec = nullptr; int rec_pos = 0; };
+int homo_batch_run(MisContext* ctx, HomoBatch* b, double thresh, int max_iters, double confidence, HomoRun run = HOMO_BOTH_PHASES,
+                   hipStream_t stream = nullptr, const HomoSync* sync = nullptr);

@@ -36,7 +36,7 @@ struct RansacState {
     int mode;      // 0 skip, 1 exactly 4 points, 2 RANSAC
     int n_sub;     // subsets drawn so far (the sequential getSubset sequence)
     int iter, niters, max_good, done, best_k, result;
-    int tail_pending;   // the loop ended in a scan-only launch: mask / DLT / LM refinement still to run (scan_tail_kernel part 2)
+    int tail_pending;   // the loop ended in a scan-only launch: mask / DLT / LM refinement still to run (scan_tail_kernel parts 3 / 4)
     int draw_k, draw_fail;   // next iteration to draw; getSubset exhausted its 10000 attempts
     long long draw_pos;      // RNG stream position after the last drawn subset
 };
@@ -1494,9 +1494,9 @@ __device__ void lm_refine_coop(TailShared& S, const float* s1, const float* d1, 
 }
 
 // part 0: replay + tail (the finished problems' mask, DLT on the inliers, LM refinement) in one launch;
-// part 1: replay only -- a problem that ends here is marked tail_pending; part 2: the tail of the pending problems whose
-// fin equals `want`.  The split lets the tails of the problems that end in RANSAC phase 0 (latency bound, ~2 ms) run on
-// another stream while phase 1 of the others -- which only needs the replay's verdict -- goes on.
+// part 1: replay only -- a problem that ends here is marked tail_pending; parts 3 / 4: the tail of the pending problems whose
+// fin equals `want`, mask + inlier compaction / DLT + LM.  The split lets the tails of the problems that end in RANSAC phase 0
+// (latency bound, ~2 ms) run on another stream while phase 1 of the others -- which only needs the replay's verdict -- goes on.
 #ifndef MIS_TAIL_WAVES
 #define MIS_TAIL_WAVES 3      // <= 168 registers: a 200-register workgroup waits longer for room beside the composition's grids (6.65 vs 6.9 ms per step; 4 waves = 128 registers spill into the Jacobi loop)
 #endif
@@ -1526,11 +1526,10 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(MIS_TAIL_WAV
     float* s1 = scr_all + 4 * c.pt_off;
     float* d1 = s1 + 2 * (size_t)(n > 0 ? n : 0);
     double* rec = rec_all + 10 * c.pt_off;
-    if (part >= 2) {
-        // part 2 runs the whole tail of a pending problem (flag 1 -> 0); parts 3 / 4 split it: mask + compaction (1 -> 2), DLT + LM (2 -> 0)
+    if (part >= 3) {
+        // the tail of a pending problem: mask + compaction (flag 1 -> 2), then DLT + LM (2 -> 0)
         if (st->tail_pending != (part == 4 ? 2 : 1) || fin[b] != want) return;   // uniform
         __syncthreads();                                    // every thread has read the flag before it changes
-        if (part == 2 && t == 0) st->tail_pending = 0;
     } else {
     if (st->done) return;  // finished in an earlier phase (uniform)
     const int mode = st->mode;
@@ -1607,7 +1606,7 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(MIS_TAIL_WAV
         if (t == 0) st->tail_pending = 1;
         return;
     }
-    }   // part != 2
+    }   // part < 3
     const int result = st->max_good > 0;
     if (part != 4 && t == 0) { res->iters = st->iter; res->ok = result; res->ninl = 0; }
     if (!result) {
@@ -1776,7 +1775,7 @@ void homo_batch_release(HomoBatch* b) {
     b->mem = nullptr; b->bytes = 0;
 }
 
-int homo_batch_run(MisContext* ctx, HomoBatch* b, double thresh, int max_iters, double confidence, int phases, hipStream_t stream, const HomoSync* sync) {
+int homo_batch_run(MisContext* ctx, HomoBatch* b, double thresh, int max_iters, double confidence, HomoRun run, hipStream_t stream, const HomoSync* sync) {
     const HomoSync none;
     const HomoSync& sy = sync ? *sync : none;
     MIS_CHECK(ctx, max_iters >= 1 && max_iters <= b->max_iters, MIS_E_INVALID, "max_iters %d outside the reserved range", max_iters);
@@ -1795,39 +1794,34 @@ int homo_batch_run(MisContext* ctx, HomoBatch* b, double thresh, int max_iters, 
     }
     RansacState* states = (RansacState*)b->state;
     const int p0 = std::min(PHASE0, max_iters);
-    // the launches that run a DLT / LM refinement (parts 0, 2, 4) carry the term stages of ordered_sums in dynamic LDS; replay-only and mask-only ones do not
+    // the launches that run a DLT / LM refinement (parts 0, 4) carry the term stages of ordered_sums in dynamic LDS; replay-only and mask-only ones do not
     // (MIS_TAIL_PLAIN=1: none anywhere -- every ordered sum takes round 3's plain loop; the parity tests run both)
     static const bool plain = getenv("MIS_TAIL_PLAIN") != nullptr && atoi(getenv("MIS_TAIL_PLAIN")) != 0;
     auto tail_staged = [&](int part) { return (part == 1 || part == 3 || plain) ? 0 : 1; };
     auto tail_lds = [&](int part) { return tail_staged(part) ? TAIL_DYN_LDS : (size_t)0; };
-    if (phases == 0 || phases == 2 || phases == 3) {
+    const int replay_part = run == HOMO_BOTH_PHASES ? 0 : 1;      // 1: replay only, the finishers' tails are left pending
+    if (run == HOMO_BOTH_PHASES || run == HOMO_PHASE0_REPLAY) {
         MIS_HIP(ctx, hipMemsetAsync(b->fin, 0xff, sizeof(int) * (size_t)b->count, st));
         hipLaunchKernelGGL(draw_kernel, dim3(b->count), dim3(DRAW_TB), 0, st, b->calls, states, b->sub_idx, b->draw_idx, rt.U, rt.state_T, max_iters, 0, p0);
         if (sy.rec && sy.rec_pos == 2) MIS_HIP(ctx, hipEventRecord(sy.rec, st));
         hipLaunchKernelGGL(hyp_quad_kernel, dim3((p0 + HQ_HYPS - 1) / HQ_HYPS, b->count), dim3(4 * HQ_HYPS), hq_lds, st, b->calls, states, b->sub_idx, b->Hc, b->valid, 0, max_iters);
-        if (sy.rec_hyp0) MIS_HIP(ctx, hipEventRecord(sy.rec_hyp0, st));
         hipLaunchKernelGGL(hyp_count_kernel, dim3((p0 + 3) / 4, b->count), dim3(256), 0, st, b->calls, states, (const double*)b->Hc, (const int*)b->valid, b->good, 0, max_iters, thr);
-        hipLaunchKernelGGL(scan_tail_kernel, dim3(b->count), dim3(TB), tail_lds(phases == 3 ? 1 : 0), st, b->calls, states, b->Hc, b->valid, b->good, b->scr, b->rec, b->results, 0, p0,
-                           max_iters, confidence, thr, b->fin, phases == 3 ? 1 : 0, 0, tail_staged(phases == 3 ? 1 : 0));
+        hipLaunchKernelGGL(scan_tail_kernel, dim3(b->count), dim3(TB), tail_lds(replay_part), st, b->calls, states, b->Hc, b->valid, b->good, b->scr, b->rec, b->results, 0, p0,
+                           max_iters, confidence, thr, b->fin, replay_part, 0, tail_staged(replay_part));
     }
-    if (phases == 4)   // the tails a phases == 3 run left pending (fin == 0)
-        hipLaunchKernelGGL(scan_tail_kernel, dim3(b->count), dim3(TB), tail_lds(2), st, b->calls, states, b->Hc, b->valid, b->good, b->scr, b->rec, b->results, 0, p0,
-                           max_iters, confidence, thr, b->fin, 2, 0, tail_staged(2));
-    if (phases >= 10) {   // 10 + 2 w: mask + compaction, 11 + 2 w: DLT + LM, of the problems a replay-only run left pending with fin == w
-        const int want = (phases - 10) >> 1, part = 3 + ((phases - 10) & 1);
+    if (run >= HOMO_TAIL0_MASK) {   // the problems a replay-only run left pending with fin == w
+        const int want = (run - HOMO_TAIL0_MASK) >> 1, part = 3 + ((run - HOMO_TAIL0_MASK) & 1);
         hipLaunchKernelGGL(scan_tail_kernel, dim3(b->count), dim3(TB), tail_lds(part), st, b->calls, states, b->Hc, b->valid, b->good, b->scr, b->rec, b->results, 0, p0,
                            max_iters, confidence, thr, b->fin, part, want, tail_staged(part));
     }
-    if ((phases == 1 || phases == 2 || phases == 6) && max_iters > p0) {
+    if ((run == HOMO_BOTH_PHASES || run == HOMO_PHASE1_REPLAY) && max_iters > p0) {
         hipLaunchKernelGGL(draw_kernel, dim3(b->count), dim3(DRAW_TB), 0, st, b->calls, states, b->sub_idx, b->draw_idx, rt.U, rt.state_T, max_iters, 1, max_iters);
         if (sy.rec && sy.rec_pos == 0) MIS_HIP(ctx, hipEventRecord(sy.rec, st));
-        if (sy.wait_hyp1) MIS_HIP(ctx, hipStreamWaitEvent(st, sy.wait_hyp1, 0));
         hipLaunchKernelGGL(hyp_quad_kernel, dim3((max_iters - p0 + HQ_HYPS - 1) / HQ_HYPS, b->count), dim3(4 * HQ_HYPS), hq_lds, st, b->calls, states, b->sub_idx, b->Hc, b->valid, p0, max_iters);
-        if (sy.rec && sy.rec_pos == 1) MIS_HIP(ctx, hipEventRecord(sy.rec, st));
         hipLaunchKernelGGL(hyp_count_kernel, dim3((max_iters - p0 + 3) / 4, b->count), dim3(256), 0, st, b->calls, states, (const double*)b->Hc, (const int*)b->valid, b->good, p0,
                            max_iters, thr);
-        hipLaunchKernelGGL(scan_tail_kernel, dim3(b->count), dim3(TB), tail_lds(phases == 6 ? 1 : 0), st, b->calls, states, b->Hc, b->valid, b->good, b->scr, b->rec, b->results, p0,
-                           max_iters, max_iters, confidence, thr, b->fin, phases == 6 ? 1 : 0, 0, tail_staged(phases == 6 ? 1 : 0));
+        hipLaunchKernelGGL(scan_tail_kernel, dim3(b->count), dim3(TB), tail_lds(replay_part), st, b->calls, states, b->Hc, b->valid, b->good, b->scr, b->rec, b->results, p0,
+                           max_iters, max_iters, confidence, thr, b->fin, replay_part, 0, tail_staged(replay_part));
     }
     MIS_HIP(ctx, hipGetLastError());
     return MIS_OK;

@@ -680,15 +680,15 @@ __global__ __launch_bounds__(256) void copy_segments_kernel(CopySegs c) {
 }
 
 __global__ void second_calls_kernel(int np, const HomoCall* calls1, const HomoResult* res1, const float* scr1, const int* fin1, int want, int thresh2,
-                                    HomoCall* calls2, PairOut* outs, int check_det) {
+                                    HomoCall* calls2, PairOut* outs) {
     int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= np) return;
     const HomoCall c1 = calls1[k];
     HomoCall c;
     c.src = nullptr; c.dst = nullptr; c.mask = nullptr; c.pt_off = c1.pt_off; c.n = 0; c.active = 0;
-    // check_det == 0: the refined first H is still being computed on another stream; the host applies the reference's
-    // |det H| >= eps test when it assembles the results and drops a second estimation that was run in vain
-    if (fin1[k] == want && c1.active && res1[k].ok && (!check_det || !(fabs(det3(res1[k].H)) < DBL_EPSILON))) {
+    // the refined first H is still being computed on another stream: the host applies the reference's |det H| >= eps test when
+    // it assembles the results and drops a second estimation that was run in vain
+    if (fin1[k] == want && c1.active && res1[k].ok) {
         outs[k].passed = 1;
         const int ninl = res1[k].ninl;
         if (ninl >= thresh2) {
@@ -732,9 +732,9 @@ struct MatchWorkspace : MisWorkspace {
     hipEvent_t ev_phase0 = nullptr, ev_side_done = nullptr, ev_phase1 = nullptr, ev_third_done = nullptr, ev_matches = nullptr;
     // "the 2-NN pass of matcher call number knn_seq has been enqueued, ev_knn marks its end" (mis_match_knn_fence)
     hipEvent_t ev_knn = nullptr;
-    hipEvent_t ev_draw1 = nullptr, ev_side_hyp0 = nullptr, ev_b2_replay = nullptr;
-    hipEvent_t tev[8] = {nullptr};   // MIS_MATCH_TRACE: timing events (2-NN end, phase 0 end, main chain's second RANSAC phase end, main chain end, side end, third end, tails of phase 0 end, side chain's first RANSAC phase end)
-    hipEvent_t ev_gate = nullptr;    // what mis_match_knn_fence queues a stream behind: ev_knn, or the end of the first RANSAC phase (MIS_COMPOSE_GATE)
+    hipEvent_t ev_draw1 = nullptr;   // the side chain's first draw_kernel has run
+    hipEvent_t tev[8] = {nullptr};   // MIS_MATCH_TRACE: timing events (2-NN end, phase 0 end, main chain's second RANSAC phase end, main chain end, side end, third end, tails of phase 0 end, main chain's second draw end)
+    hipEvent_t ev_gate = nullptr;    // what mis_match_knn_fence queues a stream behind: ev_knn, then ev_draw1 once the chains are enqueued
     std::atomic<long long> seq{0}, knn_seq{0};
     hipEvent_t ev_lists = nullptr;                       // the early download of the match lists has landed
     void (*enqueued_cb)(void*) = nullptr;                // mis_match_on_enqueued: one-shot hook of the next call
@@ -752,8 +752,6 @@ struct MatchWorkspace : MisWorkspace {
         if (ev_side_done) hipEventDestroy(ev_side_done);
         if (ev_knn) hipEventDestroy(ev_knn);
         if (ev_draw1) hipEventDestroy(ev_draw1);
-        if (ev_side_hyp0) hipEventDestroy(ev_side_hyp0);
-        if (ev_b2_replay) hipEventDestroy(ev_b2_replay);
     }
 };
 
@@ -924,13 +922,8 @@ int match_impl(MisContext* ctx, const MisFeatures* feats, int n, const MisMatchP
         MIS_HIP(ctx, hipEventCreateWithFlags(&ws->ev_side_done, hipEventDisableTiming));
     }
     const double rt = p->ransac_thresh, cf = p->confidence;
-    bool early_lists = false, packed_lists = false;     // packed: pair k's matches sit at the sum of the counts before it (pack_lists_kernel)
     // everything between the forks to the auxiliary streams and their joins runs inside one scope: an error in there must not
     // leave those streams with work pending (they are the context's, shared with the feature finders) or a copy in flight
-    // MIS_COMPOSE_GATE: 0 = a stream fenced by mis_match_knn_fence (the job's speculative composition) starts behind the 2-NN pass,
-    // 1 = behind the first RANSAC phase of the first estimation (draw, 4-point solves, replay, masks: 0.7 ms of large workgroups
-    // that wait for room once the composition's grids fill the device)
-    static const int compose_gate = getenv("MIS_COMPOSE_GATE") ? atoi(getenv("MIS_COMPOSE_GATE")) : 4;
     static const bool trace_ev = getenv("MIS_MATCH_TRACE") != nullptr;
     auto mark = [&](int i, hipStream_t s_) {      // diagnostics: device time stamps of the chains (printed with the host's when MIS_MATCH_TRACE is set)
         if (!trace_ev) return;
@@ -938,123 +931,75 @@ int match_impl(MisContext* ctx, const MisFeatures* feats, int n, const MisMatchP
         hipEventRecord(ws->tev[i], s_);
     };
     mark(0, st);
+    // Three chains: findHomography returns the RANSAC mask, not one recomputed after its refinement, so the second estimation
+    // starts from the mask while the DLT + LM refinement of the first H runs on a third stream; the |det H| test of the reference
+    // moves to the host assembly below.  Side and third are the context's two auxiliary streams -- the streams the ORB batch's
+    // helper lanes ran on a moment ago -- so that the job keeps to four streams (an earlier version created two more here, one in
+    // a priority class of its own to dodge a shared hardware queue: the step then moved by 25 % with GPU_MAX_HW_QUEUES).
     auto enqueue_chains = [&]() -> int {
-    static const int chains = getenv("MIS_MATCH_CHAINS") ? atoi(getenv("MIS_MATCH_CHAINS")) : 3;   // 2: the two-chain flow below
-    if (chains != 3) {
-    // first estimation, phase 0 up to the replay's verdict (pairs with a clear overlap finish here)
-    if ((rc = homo_batch_run(ctx, &ws->b1, rt, p->max_iters, cf, 3, st)) != MIS_OK) return rc;
-    MIS_HIP(ctx, hipEventRecord(ws->ev_phase0, st));
-    if (compose_gate == 1) ws->ev_gate = ws->ev_phase0;
-    // side stream: the tails of those pairs (mask, DLT on the inliers, LM: ~2 ms of latency) and their inlier-only estimation ...
-    MIS_HIP(ctx, hipStreamWaitEvent(ws->side, ws->ev_phase0, 0));
-    if ((rc = homo_batch_run(ctx, &ws->b1, rt, p->max_iters, cf, 4, ws->side)) != MIS_OK) return rc;
-    hipLaunchKernelGGL(second_calls_kernel, dim3((np + 127) / 128), dim3(128), 0, ws->side, np, (const HomoCall*)ws->b1.calls, (const HomoResult*)ws->b1.results,
-                       (const float*)ws->b1.scr, (const int*)ws->b1.fin, 0, p->num_matches_thresh2, ws->b2.calls, d_out, 1);
-    if ((rc = homo_batch_run(ctx, &ws->b2, rt, p->max_iters, cf, 2, ws->side)) != MIS_OK) return rc;
-    MIS_HIP(ctx, hipEventRecord(ws->ev_side_done, ws->side));
-    // ... while the main stream finishes the first estimation of the others (which only needs the verdict) and runs their second one
-    if ((rc = homo_batch_run(ctx, &ws->b1, rt, p->max_iters, cf, 1, st)) != MIS_OK) return rc;
-    hipLaunchKernelGGL(second_calls_kernel, dim3((np + 127) / 128), dim3(128), 0, st, np, (const HomoCall*)ws->b1.calls, (const HomoResult*)ws->b1.results,
-                       (const float*)ws->b1.scr, (const int*)ws->b1.fin, 1, p->num_matches_thresh2, ws->b3.calls, d_out, 1);
-    if ((rc = homo_batch_run(ctx, &ws->b3, rt, p->max_iters, cf, 2, st)) != MIS_OK) return rc;
-    } else {
-    // Three chains (the default; MIS_MATCH_CHAINS=2 selects the flow above): findHomography returns the RANSAC mask, not one
-    // recomputed after its refinement, so the second estimation starts from the mask while the DLT + LM refinement of the first H
-    // runs on a third stream; the |det H| test of the reference moves to the host assembly below.  Side and third are the
-    // context's two auxiliary streams -- the streams the ORB batch's helper lanes ran on a moment ago -- so that the job keeps to
-    // four streams (an earlier version created two more here, one in a priority class of its own to dodge a shared hardware
-    // queue: the step then moved by 25 % with GPU_MAX_HW_QUEUES).
-    if (!ws->third) {
-        if ((rc = mis_aux_stream(ctx, 1, &ws->third)) != MIS_OK) return rc;
-        MIS_HIP(ctx, hipEventCreateWithFlags(&ws->ev_phase1, hipEventDisableTiming));
-        MIS_HIP(ctx, hipEventCreateWithFlags(&ws->ev_third_done, hipEventDisableTiming));
-        MIS_HIP(ctx, hipEventCreateWithFlags(&ws->ev_matches, hipEventDisableTiming));
-        MIS_HIP(ctx, hipEventCreateWithFlags(&ws->ev_lists, hipEventDisableTiming));
-    }
-    // the match lists are final once the ratio test has run: their download (megabytes) goes to the third stream now, under the
-    // RANSAC chains, instead of behind them (0.3 ms at the end of the call)
-    MIS_HIP(ctx, hipEventRecord(ws->ev_matches, st));
-    MIS_HIP(ctx, hipStreamWaitEvent(ws->third, ws->ev_matches, 0));
-    hipLaunchKernelGGL(pack_lists_kernel, dim3(np), dim3(256), 0, ws->third, (const PairDesc*)d_pairs, np, (const int*)d_nm, (const MisDMatch*)d_matches,
-                       (MisDMatch*)(Hh + h_m), (int*)(Hh + h_nm));
-    MIS_HIP(ctx, hipEventRecord(ws->ev_lists, ws->third));
-    early_lists = true; packed_lists = true;
-    if ((rc = homo_batch_run(ctx, &ws->b1, rt, p->max_iters, cf, 3, st)) != MIS_OK) return rc;
-    if ((rc = homo_batch_run(ctx, &ws->b1, rt, p->max_iters, cf, 10, st)) != MIS_OK) return rc;
-    MIS_HIP(ctx, hipEventRecord(ws->ev_phase0, st));
-    mark(1, st);
-    if (compose_gate == 1) ws->ev_gate = ws->ev_phase0;
-    MIS_HIP(ctx, hipStreamWaitEvent(ws->side, ws->ev_phase0, 0));
-    hipLaunchKernelGGL(second_calls_kernel, dim3((np + 127) / 128), dim3(128), 0, ws->side, np, (const HomoCall*)ws->b1.calls, (const HomoResult*)ws->b1.results,
-                       (const float*)ws->b1.scr, (const int*)ws->b1.fin, 0, p->num_matches_thresh2, ws->b2.calls, d_out, 0);
-    // MIS_HYP_ORDER=1 (experiment): the main chain's second-phase solves wait for the side chain's first solves.  Measured: the side
-    // chain ends where it did (+ 2.65 ms behind the 2-NN pass: its solves are not slowed by the others'), the main chain 0.55 ms later.
-    static const int hyp_order = getenv("MIS_HYP_ORDER") ? atoi(getenv("MIS_HYP_ORDER")) : 0;
-    // MIS_B2_SPLIT (experiment, default 0): the side chain's second phase -- a handful of problems with few points that run all 2000
-    // iterations, 0.5 ms -- taken off it (the replay alone first) and run behind the main chain (1) or behind the first estimation's
-    // tails on the third stream (2).  Measured: the side chain then ends at + 2.27 ms instead of + 2.66, and the chain that took the
-    // second phase at + 2.65: the matcher ends where it did.
-    static const int b2_split = getenv("MIS_B2_SPLIT") ? atoi(getenv("MIS_B2_SPLIT")) : 0;
-    if (!ws->ev_draw1) MIS_HIP(ctx, hipEventCreateWithFlags(&ws->ev_draw1, hipEventDisableTiming));
-    if (!ws->ev_side_hyp0) MIS_HIP(ctx, hipEventCreateWithFlags(&ws->ev_side_hyp0, hipEventDisableTiming));
-    {
-        HomoSync sy;
-        if (compose_gate == 4) { sy.rec = ws->ev_draw1; sy.rec_pos = 2; ws->ev_gate = ws->ev_draw1; }      // gate 4 (the default): behind the side chain's first draw, 0.05 - 0.1 ms behind the first phase -- the tails and that draw hold their compute units by then
-        if (hyp_order) sy.rec_hyp0 = ws->ev_side_hyp0;
-        if (b2_split) {
-            // the side chain was the longest (+ 2.66 ms behind the 2-NN pass): its second phase -- a handful of problems with few
-            // points that run all 2000 iterations -- waited behind the 1.3 ms tails of the finishers although it only needs the
-            // replay's verdict.  The replay alone first; the second phase goes behind the main chain, which ends first
-            if ((rc = homo_batch_run(ctx, &ws->b2, rt, p->max_iters, cf, 3, ws->side, &sy)) != MIS_OK) return rc;
-            if (!ws->ev_b2_replay) MIS_HIP(ctx, hipEventCreateWithFlags(&ws->ev_b2_replay, hipEventDisableTiming));
-            MIS_HIP(ctx, hipEventRecord(ws->ev_b2_replay, ws->side));
-            if ((rc = homo_batch_run(ctx, &ws->b2, rt, p->max_iters, cf, 4, ws->side)) != MIS_OK) return rc;
-        } else
-        if ((rc = homo_batch_run(ctx, &ws->b2, rt, p->max_iters, cf, 2, ws->side, &sy)) != MIS_OK) return rc;
-    }
-    MIS_HIP(ctx, hipEventRecord(ws->ev_side_done, ws->side));
-    mark(4, ws->side);
-    MIS_HIP(ctx, hipStreamWaitEvent(ws->third, ws->ev_phase0, 0));
-    if ((rc = homo_batch_run(ctx, &ws->b1, rt, p->max_iters, cf, 11, ws->third)) != MIS_OK) return rc;
-    mark(6, ws->third);
-    if (b2_split == 2) {      // (experiment: behind the first estimation's tails on the third stream -- that chain then ends at + 2.65 ms)
-        MIS_HIP(ctx, hipStreamWaitEvent(ws->third, ws->ev_b2_replay, 0));
-        if ((rc = homo_batch_run(ctx, &ws->b2, rt, p->max_iters, cf, 1, ws->third)) != MIS_OK) return rc;
-    }
-    {
-        // gate 2: behind the second phase's draw of the main chain -- by then the tails (third stream) and the second estimations
-        // (side stream), released together with it, hold their compute units
-        HomoSync sy;
-        if (compose_gate == 2 || compose_gate == 3) { sy.rec = ws->ev_draw1; sy.rec_pos = compose_gate - 2; ws->ev_gate = ws->ev_draw1; }
-        if (hyp_order) sy.wait_hyp1 = ws->ev_side_hyp0;
-        if (trace_ev && !sy.rec) {      // diagnostics: the end of the main chain's second draw
-            if (!ws->tev[7]) hipEventCreate(&ws->tev[7]);
-            sy.rec = ws->tev[7]; sy.rec_pos = 0;
+        if (!ws->third) {
+            if ((rc = mis_aux_stream(ctx, 1, &ws->third)) != MIS_OK) return rc;
+            MIS_HIP(ctx, hipEventCreateWithFlags(&ws->ev_phase1, hipEventDisableTiming));
+            MIS_HIP(ctx, hipEventCreateWithFlags(&ws->ev_third_done, hipEventDisableTiming));
+            MIS_HIP(ctx, hipEventCreateWithFlags(&ws->ev_matches, hipEventDisableTiming));
+            MIS_HIP(ctx, hipEventCreateWithFlags(&ws->ev_lists, hipEventDisableTiming));
         }
-        if ((rc = homo_batch_run(ctx, &ws->b1, rt, p->max_iters, cf, 6, st, &sy)) != MIS_OK) return rc;
-    }
-    if ((rc = homo_batch_run(ctx, &ws->b1, rt, p->max_iters, cf, 12, st)) != MIS_OK) return rc;
-    MIS_HIP(ctx, hipEventRecord(ws->ev_phase1, st));
-    mark(2, st);
-    // the refinement of the phase-1 finishers' first H stays on this stream (1.7 ms of latency-bound work: behind the 2 ms
-    // refinement of the phase-0 finishers on the third stream it ended the matcher 0.6 ms later); their inlier-only second
-    // estimation goes to the third stream instead
-    if ((rc = homo_batch_run(ctx, &ws->b1, rt, p->max_iters, cf, 13, st)) != MIS_OK) return rc;
-    if (b2_split == 1) {      // the side chain's second phase, behind the main chain (which ends first: + 2.17 ms)
-        MIS_HIP(ctx, hipStreamWaitEvent(st, ws->ev_b2_replay, 0));
-        if ((rc = homo_batch_run(ctx, &ws->b2, rt, p->max_iters, cf, 1, st)) != MIS_OK) return rc;
-    }
-    mark(3, st);
-    MIS_HIP(ctx, hipStreamWaitEvent(ws->third, ws->ev_phase1, 0));
-    hipLaunchKernelGGL(second_calls_kernel, dim3((np + 127) / 128), dim3(128), 0, ws->third, np, (const HomoCall*)ws->b1.calls, (const HomoResult*)ws->b1.results,
-                       (const float*)ws->b1.scr, (const int*)ws->b1.fin, 1, p->num_matches_thresh2, ws->b3.calls, d_out, 0);
-    if ((rc = homo_batch_run(ctx, &ws->b3, rt, p->max_iters, cf, 2, ws->third)) != MIS_OK) return rc;
-    MIS_HIP(ctx, hipEventRecord(ws->ev_third_done, ws->third));
-    mark(5, ws->third);
-    MIS_HIP(ctx, hipStreamWaitEvent(st, ws->ev_third_done, 0));
-    }
-    MIS_HIP(ctx, hipStreamWaitEvent(st, ws->ev_side_done, 0));
-    return MIS_OK;
+        // the match lists are final once the ratio test has run: their download (megabytes) goes to the third stream now, under the
+        // RANSAC chains, instead of behind them (0.3 ms at the end of the call); pair k's matches land at the sum of the counts before it
+        MIS_HIP(ctx, hipEventRecord(ws->ev_matches, st));
+        MIS_HIP(ctx, hipStreamWaitEvent(ws->third, ws->ev_matches, 0));
+        hipLaunchKernelGGL(pack_lists_kernel, dim3(np), dim3(256), 0, ws->third, (const PairDesc*)d_pairs, np, (const int*)d_nm, (const MisDMatch*)d_matches,
+                           (MisDMatch*)(Hh + h_m), (int*)(Hh + h_nm));
+        MIS_HIP(ctx, hipEventRecord(ws->ev_lists, ws->third));
+        // main chain: first estimation of every pair, RANSAC phase 0 and the inlier masks of the pairs that finish there
+        if ((rc = homo_batch_run(ctx, &ws->b1, rt, p->max_iters, cf, HOMO_PHASE0_REPLAY, st)) != MIS_OK) return rc;
+        if ((rc = homo_batch_run(ctx, &ws->b1, rt, p->max_iters, cf, HOMO_TAIL0_MASK, st)) != MIS_OK) return rc;
+        MIS_HIP(ctx, hipEventRecord(ws->ev_phase0, st));
+        mark(1, st);
+        // side chain: the inlier-only estimation of those pairs
+        MIS_HIP(ctx, hipStreamWaitEvent(ws->side, ws->ev_phase0, 0));
+        hipLaunchKernelGGL(second_calls_kernel, dim3((np + 127) / 128), dim3(128), 0, ws->side, np, (const HomoCall*)ws->b1.calls, (const HomoResult*)ws->b1.results,
+                           (const float*)ws->b1.scr, (const int*)ws->b1.fin, 0, p->num_matches_thresh2, ws->b2.calls, d_out);
+        if (!ws->ev_draw1) MIS_HIP(ctx, hipEventCreateWithFlags(&ws->ev_draw1, hipEventDisableTiming));
+        {
+            // the compose gate: behind the side chain's first draw, 0.05 - 0.1 ms behind the first phase -- the tails and that draw
+            // hold their compute units by then
+            HomoSync sy;
+            sy.rec = ws->ev_draw1; sy.rec_pos = 2; ws->ev_gate = ws->ev_draw1;
+            if ((rc = homo_batch_run(ctx, &ws->b2, rt, p->max_iters, cf, HOMO_BOTH_PHASES, ws->side, &sy)) != MIS_OK) return rc;
+        }
+        MIS_HIP(ctx, hipEventRecord(ws->ev_side_done, ws->side));
+        mark(4, ws->side);
+        // third chain: DLT + LM refinement of the first H of the pairs that finished in phase 0
+        MIS_HIP(ctx, hipStreamWaitEvent(ws->third, ws->ev_phase0, 0));
+        if ((rc = homo_batch_run(ctx, &ws->b1, rt, p->max_iters, cf, HOMO_TAIL0_REFINE, ws->third)) != MIS_OK) return rc;
+        mark(6, ws->third);
+        // main chain: RANSAC phase 1 of the others
+        {
+            HomoSync sy;
+            if (trace_ev) {      // diagnostics: the end of the main chain's second draw
+                if (!ws->tev[7]) hipEventCreate(&ws->tev[7]);
+                sy.rec = ws->tev[7]; sy.rec_pos = 0;
+            }
+            if ((rc = homo_batch_run(ctx, &ws->b1, rt, p->max_iters, cf, HOMO_PHASE1_REPLAY, st, &sy)) != MIS_OK) return rc;
+        }
+        if ((rc = homo_batch_run(ctx, &ws->b1, rt, p->max_iters, cf, HOMO_TAIL1_MASK, st)) != MIS_OK) return rc;
+        MIS_HIP(ctx, hipEventRecord(ws->ev_phase1, st));
+        mark(2, st);
+        // the refinement of the phase-1 finishers' first H stays on this stream (1.7 ms of latency-bound work: behind the 2 ms
+        // refinement of the phase-0 finishers on the third stream it ended the matcher 0.6 ms later); their inlier-only second
+        // estimation goes to the third stream instead
+        if ((rc = homo_batch_run(ctx, &ws->b1, rt, p->max_iters, cf, HOMO_TAIL1_REFINE, st)) != MIS_OK) return rc;
+        mark(3, st);
+        MIS_HIP(ctx, hipStreamWaitEvent(ws->third, ws->ev_phase1, 0));
+        hipLaunchKernelGGL(second_calls_kernel, dim3((np + 127) / 128), dim3(128), 0, ws->third, np, (const HomoCall*)ws->b1.calls, (const HomoResult*)ws->b1.results,
+                           (const float*)ws->b1.scr, (const int*)ws->b1.fin, 1, p->num_matches_thresh2, ws->b3.calls, d_out);
+        if ((rc = homo_batch_run(ctx, &ws->b3, rt, p->max_iters, cf, HOMO_BOTH_PHASES, ws->third)) != MIS_OK) return rc;
+        MIS_HIP(ctx, hipEventRecord(ws->ev_third_done, ws->third));
+        mark(5, ws->third);
+        MIS_HIP(ctx, hipStreamWaitEvent(st, ws->ev_third_done, 0));
+        MIS_HIP(ctx, hipStreamWaitEvent(st, ws->ev_side_done, 0));
+        return MIS_OK;
     };
     if ((rc = enqueue_chains()) != MIS_OK) {
         if (ws->side) hipStreamSynchronize(ws->side);
@@ -1071,10 +1016,6 @@ int match_impl(MisContext* ctx, const MisFeatures* feats, int n, const MisMatchP
     int* fin = (int*)(Hh + h_fin);
     MisDMatch* hm = (MisDMatch*)(Hh + h_m);
     uint8_t* hmask = Hh + h_mask;
-    if (!early_lists) {
-        MIS_HIP(ctx, hipMemcpyAsync(nm, d_nm, sizeof(int) * np, hipMemcpyDeviceToHost, st));
-        MIS_HIP(ctx, hipMemcpyAsync(hm, d_matches, sizeof(MisDMatch) * m_total, hipMemcpyDeviceToHost, st));
-    }
     {
         CopySegs cs;
         const void* srcs[6] = {d_out, ws->b1.results, ws->b2.results, ws->b3.results, ws->b1.fin, d_mask};
@@ -1099,26 +1040,6 @@ int match_impl(MisContext* ctx, const MisFeatures* feats, int n, const MisMatchP
     }
     const bool trace = getenv("MIS_MATCH_TRACE") != nullptr;
     const auto tq = std::chrono::steady_clock::now();
-    // MatchesInfo (host), part 1 under the RANSAC chains: the match lists and their mirrors
-    auto lists = [&]() {
-        size_t packed_off = 0;
-        for (int k = 0; k < np; k++) {
-            const PairDesc& pd = pairs[k];
-            MisMatchesInfo* a = &out[pd.i * n + pd.j];
-            MisMatchesInfo* b = &out[pd.j * n + pd.i];
-            a->src_img_idx = pd.i; a->dst_img_idx = pd.j;
-            a->n_matches = nm[k];
-            a->matches = (MisDMatch*)malloc(sizeof(MisDMatch) * (size_t)(nm[k] + 1));
-            memcpy(a->matches, hm + (packed_lists ? packed_off : pd.m_off), sizeof(MisDMatch) * (size_t)nm[k]);
-            packed_off += (size_t)nm[k];
-            b->matches = (MisDMatch*)malloc(sizeof(MisDMatch) * (size_t)(nm[k] + 1));
-            for (int q = 0; q < nm[k]; q++) {
-                b->matches[q] = a->matches[q];
-                b->matches[q].query_idx = a->matches[q].train_idx;
-                b->matches[q].train_idx = a->matches[q].query_idx;
-            }
-        }
-    };
     // an error from here on must not leave half-built entries behind: the lists are released and `out` is back to its zeroed state
     auto drop_lists = [&]() {
         for (int k = 0; k < np; k++) {
@@ -1127,25 +1048,39 @@ int match_impl(MisContext* ctx, const MisFeatures* feats, int n, const MisMatchP
             for (MisMatchesInfo* m : e) { free(m->matches); free(m->inliers_mask); init_info(m); }
         }
     };
-    bool have_lists = false;
-    if (early_lists) {
-        MIS_HIP(ctx, hipEventSynchronize(ws->ev_lists));
-        lists();
-        have_lists = true;
+    // MatchesInfo (host), part 1 under the RANSAC chains: the match lists (packed by pack_lists_kernel) and their mirrors
+    MIS_HIP(ctx, hipEventSynchronize(ws->ev_lists));
+    {
+        size_t packed_off = 0;
+        for (int k = 0; k < np; k++) {
+            const PairDesc& pd = pairs[k];
+            MisMatchesInfo* a = &out[pd.i * n + pd.j];
+            MisMatchesInfo* b = &out[pd.j * n + pd.i];
+            a->src_img_idx = pd.i; a->dst_img_idx = pd.j;
+            a->n_matches = nm[k];
+            a->matches = (MisDMatch*)malloc(sizeof(MisDMatch) * (size_t)(nm[k] + 1));
+            memcpy(a->matches, hm + packed_off, sizeof(MisDMatch) * (size_t)nm[k]);
+            packed_off += (size_t)nm[k];
+            b->matches = (MisDMatch*)malloc(sizeof(MisDMatch) * (size_t)(nm[k] + 1));
+            for (int q = 0; q < nm[k]; q++) {
+                b->matches[q] = a->matches[q];
+                b->matches[q].query_idx = a->matches[q].train_idx;
+                b->matches[q].train_idx = a->matches[q].query_idx;
+            }
+        }
     }
     {
         const hipError_t e = hipStreamSynchronize(st);
         if (e != hipSuccess) {
-            if (have_lists) drop_lists();
+            drop_lists();
             return mis_set_error(ctx, MIS_E_HIP, "hipStreamSynchronize failed: %s (%s:%d)", hipGetErrorString(e), __FILE__, __LINE__);
         }
     }
     const auto ts = std::chrono::steady_clock::now();
     if (l2_bad) {
-        if (have_lists) drop_lists();
+        drop_lists();
         return mis_set_error(ctx, MIS_E_UNSUPPORTED, "L2 matching needs integer-valued descriptors in 0..255 (SIFT style)");
     }
-    if (!early_lists) lists();
     // part 2: masks, H, confidence; the mirror entry gets H^-1 and swapped indices
     for (int k = 0; k < np; k++) {
         const PairDesc& pd = pairs[k];
@@ -1156,9 +1091,8 @@ int match_impl(MisContext* ctx, const MisFeatures* feats, int n, const MisMatchP
             a->inliers_mask = (uint8_t*)malloc((size_t)nm[k] + 1);
             memcpy(a->inliers_mask, hmask + pd.m_off, (size_t)nm[k]);
         }
-        // matchers.cpp: "if (H.empty() || |det H| < eps) return" after the first estimation.  The two-chain flow tests it on
-        // the device before the second estimation; the three-chain flow runs that estimation without waiting for the
-        // refined H, and a degenerate first H drops it here (same expression, same rounding: no FMA contraction)
+        // matchers.cpp: "if (H.empty() || |det H| < eps) return" after the first estimation.  The second estimation runs
+        // without waiting for the refined H, and a degenerate first H drops it here (same expression, same rounding: no FMA contraction)
         const bool det_ok = !(fabs(det3(r1[k].H)) < DBL_EPSILON);
         const bool passed = po[k].passed && det_ok, second = po[k].second && det_ok;
         // H of the inlier-only estimation when it ran (it may come back empty), else of the first one

@@ -310,9 +310,6 @@ __device__ __forceinline__ int fast_score_px(const uint8_t* p, int pp, int t) { 
 // The gray tile (+4 halo) is staged with coalesced dword loads issued up front, the scores of the tile
 // (+1 halo) are computed from LDS, and the survivors go to a per-level list (x | y << 16, score) and a
 // per-level histogram: the score map never exists in HBM.
-#ifndef FN_ABL
-#define FN_ABL 0
-#endif
 #ifndef MIS_FT_ROWS
 #define MIS_FT_ROWS 64
 #endif
@@ -354,9 +351,6 @@ __global__ __launch_bounds__(256) void fast_nms_kernel(Levels L, const uint8_t* 
         }
     }
     __syncthreads();
-#if FN_ABL == 1
-    if (lcount >= 0) return;      // ablation: stop behind the staging of the gray tile
-#endif
     const int SP = FT_COLS + 4;
     // Stage A, every pixel of the scored region (34 rows x 66 columns): a 9-arc of the 16-pixel circle holds one of the positions
     // {0, 8} (three rows below / above) and one of {4, 12} (three columns right / left), so a corner needs
@@ -423,9 +417,6 @@ __global__ __launch_bounds__(256) void fast_nms_kernel(Levels L, const uint8_t* 
         }
     }
     __syncthreads();
-#if FN_ABL == 2
-    if (qcount >= 0) return;      // ablation: stop behind stage A
-#endif
     for (int q = t; q < qcount; q += 256) {
         const int i = queue[q], r = i / (FT_COLS + 2), c = i - r * (FT_COLS + 2);
         const int fsv = fast_score_full(g + (r + 3) * FG_PITCH + (c + FG_COL0), FG_PITCH, L.fast_t);
@@ -435,9 +426,6 @@ __global__ __launch_bounds__(256) void fast_nms_kernel(Levels L, const uint8_t* 
 #endif
     }
     __syncthreads();
-#if FN_ABL == 3
-    if (qcount >= 0) return;      // ablation (tools): stop behind the arc evaluation
-#endif
     {
         // 3 x 3 strict non-max suppression of the corners, from the queue (1.4 % of the pixels have a score at all: a raster pass
         // over the tile read 9 scores per pixel for nothing).  Every lane takes part in every ballot: survivors are appended with
@@ -1344,7 +1332,7 @@ extern "C" int mis_orb_create(MisContext* ctx, const MisOrbParams* p, int max_w,
         // |round(x cos - y sin)| <= round(|(x, y)|); the patch must also stay inside the padded level (border ring of ORB_BORDER)
         const int reach = (int)floor(sqrt((double)max_sq) + 0.5);
         // FAST keypoints keep 3 pixels from the edge, the level carries a border ring of ORB_BORDER: the patch stays inside the padded level
-        o->direct_describe = reach <= DD_R && 3 + ORB_BORDER >= DD_P && getenv("MIS_ORB_FULL_BLUR") == nullptr;
+        o->direct_describe = reach <= DD_R && 3 + ORB_BORDER >= DD_P;
     }
     int rc0 = orb_alloc_workspace(o, 1);      // (after direct_describe is known: it decides whether a frame's block carries a blurred pyramid)
     if (rc0 != MIS_OK) { delete o; return rc0; }

@@ -967,10 +967,9 @@ static void blur(MisSift* s, const float* src, float* dst, int w, int h, double 
     // the tap counts of SIFT::create()'s sigmas run fused (one read, two writes per layer); `prev` is always the source there.
     // Segments: long enough that the N - 1 extra input rows stay a small share, short enough that a layer is >= ~1500 workgroups
     const int nsx = (w + FB_TW - 1) / FB_TW;
-    // (small layers are bound by the serial walk of a segment, not by its N - 1 extra rows: short segments there)
-    static const int seg_min = getenv("MIS_SIFT_SEG_MIN") ? atoi(getenv("MIS_SIFT_SEG_MIN")) : 16;
+    // (small layers are bound by the serial walk of a segment, not by its N - 1 extra rows: short segments there, down to 16 rows)
     int seg = (h * nsx + 1499) / 1500;
-    seg = std::min(256, std::max(seg_min, (seg + 7) & ~7));
+    seg = std::min(256, std::max(16, (seg + 7) & ~7));
     const dim3 gfused(nsx, (h + seg - 1) / seg);
     const bool fused_ok = (prev == nullptr || prev == src) && (dog != nullptr) == (prev != nullptr);
 #define MIS_BLUR_CASE(NN)                                                                                                                        \

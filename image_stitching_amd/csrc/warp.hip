@@ -230,12 +230,6 @@ __device__ __forceinline__ void tile_trig(const WarpArgs& a, int tx0, int ty0, f
 #ifndef WV_LROWS
 #define WV_LROWS 4
 #endif
-#ifndef WV_V3
-#define WV_V3 1      // 1: the pipelined strip kernels of round 3; 0: round 2's one-tile-per-wave kernels (kept for A/B runs)
-#endif
-#ifndef WV_ABL
-#define WV_ABL 0     // diagnostics builds only (tools/warp_variants.sh): phases switched off one at a time
-#endif
 constexpr int LROWS = WV_LROWS;          // rows per lane (4 lane rows per tile)
 constexpr int LPX = 2 * LROWS;            // pixels per lane
 constexpr int FT_W = 32, FT_H = 4 * LROWS;
@@ -416,13 +410,7 @@ __device__ __forceinline__ void tile_map(const WarpArgs& a, const TileTrig& g, i
     for (int i = 0; i < LROWS; i++) {
         v2f xx, yy, zz, qx, qy;
         map_terms(a.m, su, cu, g.rt[i], &xx, &yy, &zz);
-#if WV_ABL == 4   // diagnostics: no division (approximate coordinates)
-        { const v2f r0 = {__builtin_amdgcn_rcpf(zz.x), __builtin_amdgcn_rcpf(zz.y)}; qx = xx * r0; qy = yy * r0; }
-#elif WV_ABL == 5  // diagnostics: no map at all
-        qx = v2f{(float)gx + 100.25f, (float)gx + 101.25f} + 0.f * su; qy = v2f{(float)(gy0 + i) + 100.5f, (float)(gy0 + i) + 100.5f} + 0.f * g.rt[i].x; zz = v2f{1.f, 1.f};
-#else
         div2_shared(xx, yy, zz, &qx, &qy);
-#endif
         zlo = fminf(fminf(zlo, zz.x), zz.y);
         // cvRound(32 x) for |32 x| < 2^22; anything larger lands outside +-2^22 as well and is caught by the box check
         const v2f tx = qx * k32 + magic, ty = qy * k32 + magic;
@@ -516,29 +504,17 @@ __device__ __forceinline__ void tile_map(const WarpArgs& a, const TileTrig& g, i
 // Phase 2: issue the global -> LDS copies of the tile's source box (asynchronous; completion = vmcnt)
 __device__ __forceinline__ void tile_stage(const WarpArgs& a, const TileState& t, uint8_t* stage, int lane) {
     if (!t.staged) return;
-#if WV_ABL == 3   // diagnostics: no global -> LDS copies
-    return;
-#endif
     if (t.wide) stage_box<16>(a.src + t.gbase, a.sstride, stage, t.pitch, t.nrows, lane);
     else stage_box<4>(a.src + t.gbase, a.sstride, stage, t.pitch, t.nrows, lane);
 }
 
 // Phase 3: bilinear gather from the staged box and the 16SC3 / mask stores
-#ifndef WV_TILE_LDS_STORE
-#define WV_TILE_LDS_STORE 0     // 1: whole tiles leave through an LDS transpose as 16-byte pieces. Measured SLOWER here (25.6 vs 24.4 us per launch,
-                                // gpurun_out/r3_v3_var12.txt): this kernel is bound by its LDS (2.1-fold bank conflicts of the 2 x 4 lane blocks); the strip kernel is the form where it pays
-#endif
 __device__ __forceinline__ void tile_sample_store(const WarpArgs& a, const TileState& t, uint8_t* stage, int tx0, int ty0, int lane) {
     uint3 w[LROWS];
     unsigned mm[LROWS];
 #pragma unroll
     for (int i = 0; i < LROWS; i++) {
         int p0[3], p1[3];
-#if WV_ABL == 2   // diagnostics: no LDS gather, no bilinear arithmetic
-        if (true) {
-            p0[0] = t.xq[2 * i] & 255; p0[1] = t.yq[2 * i] & 255; p0[2] = 7; p1[0] = t.xq[2 * i + 1] & 255; p1[1] = t.yq[2 * i + 1] & 255; p1[2] = 9;
-        } else
-#endif
         if (t.staged && t.interior) {
             sample1<false>(stage, t.lbase, t.pitch, a.sw, a.sh, t.xq[2 * i], t.yq[2 * i], p0);
             sample1<false>(stage, t.lbase, t.pitch, a.sw, a.sh, t.xq[2 * i + 1], t.yq[2 * i + 1], p1);
@@ -555,34 +531,6 @@ __device__ __forceinline__ void tile_sample_store(const WarpArgs& a, const TileS
         w[i].z = (unsigned)p1[1] | ((unsigned)p1[2] << 16);
         mm[i] = ((t.msk >> (2 * i) & 1) ? 255u : 0u) | ((t.msk >> (2 * i + 1) & 1) ? 0xff00u : 0u);
     }
-#if WV_TILE_LDS_STORE && WV_LROWS == 4 && WV_ABL != 1
-    // whole tile inside the roi, 16-byte aligned outputs (wave-uniform): the 16 rows of 192 bytes are written to the stage (the
-    // box is spent: every tap of this wave has been read), read back as 192 pieces of 16 bytes -- piece p = row * 12 + column
-    // piece, lane l takes p = l, l + 64, l + 128 -- and stored with global_store_dwordx4: 12 lanes cover a row's 192 bytes
-    const bool full = tx0 + FT_W <= a.dw && ty0 + FT_H <= a.dh && ((((size_t)a.dst | a.dstride) & 15) == 0) && ((((size_t)a.mask | a.mstride) & 7) == 0);
-    if (full) {
-        const int lx = lane & 15, ly = lane >> 4;
-        volatile unsigned* so = reinterpret_cast<volatile unsigned*>(stage + (LROWS * ly) * (FT_W * 6) + lx * 12);
-        volatile unsigned short* sm = reinterpret_cast<volatile unsigned short*>(stage + FT_W * FT_H * 6 + (LROWS * ly) * FT_W + lx * 2);
-#pragma unroll
-        for (int i = 0; i < LROWS; i++) {
-            so[i * (FT_W * 6 / 4)] = w[i].x; so[i * (FT_W * 6 / 4) + 1] = w[i].y; so[i * (FT_W * 6 / 4) + 2] = w[i].z;
-            sm[i * (FT_W / 2)] = (unsigned short)mm[i];
-        }
-        uint8_t* dbase = (uint8_t*)a.dst + (size_t)ty0 * a.dstride + (size_t)tx0 * 6;
-#pragma unroll
-        for (int kk = 0; kk < 3; kk++) {
-            const int p = kk * 64 + lane, row = p / 12, cb = (p - row * 12) * 16;
-            typedef unsigned u4 __attribute__((ext_vector_type(4)));
-            const u4 v = *reinterpret_cast<const u4*>(stage + p * 16);
-            *reinterpret_cast<u4*>(dbase + (size_t)row * a.dstride + cb) = v;
-        }
-        typedef unsigned u2 __attribute__((ext_vector_type(2)));
-        const u2 mv = *reinterpret_cast<const u2*>(stage + FT_W * FT_H * 6 + lane * 8);
-        *reinterpret_cast<u2*>(a.mask + (size_t)(ty0 + (lane >> 2)) * a.mstride + tx0 + (lane & 3) * 8) = mv;
-        return;
-    }
-#endif
     if (!t.col_ok) return;
     uint8_t* drow = (uint8_t*)a.dst + (size_t)t.gy0 * a.dstride + (size_t)t.gx * 6;
     uint8_t* mrow = a.mask + (size_t)t.gy0 * a.mstride + t.gx;
@@ -590,12 +538,8 @@ __device__ __forceinline__ void tile_sample_store(const WarpArgs& a, const TileS
     for (int i = 0; i < LROWS; i++, drow += a.dstride, mrow += a.mstride) {
         if (t.gy0 + i >= a.dh) break;
         if (t.two) {
-#if WV_ABL == 1   // diagnostics: everything but the global stores
-            asm volatile("" :: "v"(w[i].x), "v"(w[i].y), "v"(w[i].z), "v"(mm[i]), "v"(drow), "v"(mrow));
-#else
             *reinterpret_cast<uint3*>(drow) = w[i];
             *reinterpret_cast<unsigned short*>(mrow) = (unsigned short)mm[i];
-#endif
         } else {
             int16_t* d = reinterpret_cast<int16_t*>(drow);
             d[0] = (int16_t)(w[i].x & 0xffff); d[1] = (int16_t)(w[i].x >> 16); d[2] = (int16_t)(w[i].y & 0xffff);
@@ -612,9 +556,6 @@ constexpr int TILE_WAVES = WV_TILE_WAVES;
 #ifndef WV_WAVES_MIN
 #define WV_WAVES_MIN 4     // occupancy floor the register allocator works to (6 and 8 measured in the batched grid: no gain)
 #endif
-#ifndef WV_ORDER
-#define WV_ORDER 2
-#endif
 #ifndef WV_CH_W
 #define WV_CH_W 4
 #endif
@@ -623,8 +564,8 @@ constexpr int TILE_WAVES = WV_TILE_WAVES;
 #endif
 constexpr int CH_W = WV_CH_W, CH_H = WV_CH_H;   // chunk of tiles owned by one XCD (CH_W a multiple of TILE_WAVES)
 static_assert(CH_W % TILE_WAVES == 0, "chunk width must be a whole number of workgroups");
-// bid / nwg: the workgroup's index in its frame's grid and the size of that grid
-__device__ __forceinline__ void warp_fused_body(const WarpArgs& a, const float* __restrict__ tab, int ntiles, int bid, int nwg_frame, uint8_t (*stage_all)[STAGE_BYTES]) {
+// bid: the workgroup's index in the frame's grid
+__device__ __forceinline__ void warp_fused_body(const WarpArgs& a, const float* __restrict__ tab, int bid, uint8_t (*stage_all)[STAGE_BYTES]) {
     const int ntx = (a.dw + FT_W - 1) / FT_W, lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     uint8_t* stage = stage_all[wave];
     // Tile order.  Workgroup b runs on XCD b % 8 (round-robin dispatch) and every XCD has its own L2.  The tile grid is cut into
@@ -633,28 +574,13 @@ __device__ __forceinline__ void warp_fused_body(const WarpArgs& a, const float* 
     // every XCD gets the same mix of cheap interior tiles and expensive border tiles (a contiguous eighth per XCD left the two
     // XCDs that own the top and bottom bands 7 % more work: they finished 2.7 us after the others, tools/warp_stamps.py).
     const int nty = (a.dh + FT_H - 1) / FT_H;
-#if WV_ORDER == 0
-    const int nwg = nwg_frame, xcd = bid & 7;
-    const int wg = xcd * (nwg >> 3) + min(xcd, nwg & 7) + (bid >> 3);
-    const int tile = wg * TILE_WAVES + wave;
-    if (tile >= ntiles) return;
-    const int tx = tile % ntx, ty = tile / ntx;
-#elif WV_ORDER == 1
-    const int tile = bid * TILE_WAVES + wave;
-    if (tile >= ntiles) return;
-    const int tx = tile % ntx, ty = tile / ntx;
-    (void)nwg_frame;
-#else
     constexpr int WG_X = CH_W / TILE_WAVES, WG_PER_CHUNK = WG_X * CH_H;
     const int nchx = (ntx + CH_W - 1) / CH_W;
     const int i = bid >> 3;
     const int chunk = (i / WG_PER_CHUNK) * 8 + (bid & 7), within = i % WG_PER_CHUNK;
-    (void)nwg_frame;
     const int chy = chunk / nchx, chx = chunk - chy * nchx;
     const int tx = chx * CH_W + (within % WG_X) * TILE_WAVES + wave, ty = chy * CH_H + within / WG_X;
     if (tx >= ntx || ty >= nty) return;
-    (void)ntiles;
-#endif
     const int tx0 = tx * FT_W, ty0 = ty * FT_H;
     TileState cur;
     TileTrig trig;
@@ -685,28 +611,19 @@ __device__ __forceinline__ void warp_fused_body(const WarpArgs& a, const float* 
     tile_sample_store(a, cur, stage, tx0, ty0, lane);
 #endif
 }
-__global__ __launch_bounds__(64 * TILE_WAVES) __attribute__((amdgpu_waves_per_eu(WV_WAVES_MIN, 8))) void warp_fused_kernel(WarpArgs a, const float* __restrict__ tab, int ntiles) {
+__global__ __launch_bounds__(64 * TILE_WAVES) __attribute__((amdgpu_waves_per_eu(WV_WAVES_MIN, 8))) void warp_fused_kernel(WarpArgs a, const float* __restrict__ tab) {
     __shared__ __attribute__((aligned(16))) uint8_t stage_all[TILE_WAVES][STAGE_BYTES];
-    warp_fused_body(a, tab, ntiles, (int)blockIdx.x, (int)gridDim.x, stage_all);
+    warp_fused_body(a, tab, (int)blockIdx.x, stage_all);
 }
-// The frames of a compositing loop in ONE grid (y = frame): a 4K frame is 2.8 generations of resident workgroups, so a launch of
-// its own spends a quarter of its time filling and draining the device (tools/warp_stamps.py: the last workgroups start at 19 us of
-// 24); in a common grid the next frame's tiles take the slots the previous frame's stragglers free.
+// The frames of a compositing loop go out in ONE grid (warp_strip_batch_kernel below): a 4K frame is 2.8 generations of resident
+// workgroups, so a launch of its own spends a quarter of its time filling and draining the device (tools/warp_stamps.py: the last
+// workgroups start at 19 us of 24); in a common grid the next frame's tiles take the slots the previous frame's stragglers free.
+// Their trig tables are filled by one launch as well.
 constexpr int WB_MAX = 16;
 struct WarpBatch {
     WarpArgs a[WB_MAX];
     const float* tab[WB_MAX];
-    int ntiles[WB_MAX], nwg[WB_MAX];
 };
-#if !WV_V3      // round 2's batched tile kernel: only in the A / B build without the strip kernels
-__global__ __launch_bounds__(64 * TILE_WAVES) __attribute__((amdgpu_waves_per_eu(WV_WAVES_MIN, 8))) void warp_fused_batch_kernel(WarpBatch b) {
-    __shared__ __attribute__((aligned(16))) uint8_t stage_all[TILE_WAVES][STAGE_BYTES];
-    const int f = blockIdx.y;
-    if ((int)blockIdx.x >= b.nwg[f]) return;      // the grid covers the largest frame of the batch
-    const WarpArgs a = b.a[f];
-    warp_fused_body(a, b.tab[f], b.ntiles[f], (int)blockIdx.x, b.nwg[f], stage_all);
-}
-#endif
 __global__ __launch_bounds__(256) void warp_trig_batch_kernel(WarpBatch b) {
     const int f = blockIdx.y;
     const WarpArgs& a = b.a[f];
@@ -775,9 +692,6 @@ __global__ __launch_bounds__(256) void warp_trig_batch_kernel(WarpBatch b) {
 #endif
 #ifndef WV3_MG
 #define WV3_MG 8
-#endif
-#ifndef WV3_PRIO
-#define WV3_PRIO 0      // diagnostics: 1 = raised priority during the gather, 2 = during map + copies
 #endif
 #ifndef WV3_PITCH_ALIGN
 #define WV3_PITCH_ALIGN 128
@@ -866,16 +780,12 @@ __device__ __forceinline__ int v3_stage_box(const uint8_t* src, unsigned gbase, 
     const int lstep = k * pitch;
     int left = (lr < k && lc * PIECE < rowb) ? nrows - lr : 0;      // this lane copies a row while left > 0
     int n = 0;
-#if WV_ABL == 3
-    return 0;
-#else
 #pragma unroll 1
     for (int r0 = 0; r0 < nrows; r0 += k, n++) {
         if (left > 0) dma_piece<PIECE>(src, voff, lds_off);
         voff += vstep; lds_off += lstep; left -= k;
     }
     return n;
-#endif
 }
 
 // four wave-wide integer reductions at once: min(a), max(b), min(c), max(d) -> uniform values.  The chains are interleaved, so
@@ -939,15 +849,8 @@ __device__ __forceinline__ void v3_map(const V3Frame& f, cf4p rowtab, float su, 
 #pragma unroll
     for (int i = 0; i < V3_TH; i++) {
         float xx, yy, zz, qx, qy;
-#if WV_ABL == 5
-        qx = su * 0.f + 100.25f + (float)(threadIdx.x & 63); qy = (float)(ty0 + i) + 100.5f; zz = 1.f;
-#elif WV_ABL == 4
-        terms(i, &xx, &yy, &zz);
-        { const float r0 = __builtin_amdgcn_rcpf(zz); qx = xx * r0; qy = yy * r0; }
-#else
         terms(i, &xx, &yy, &zz);
         div1_shared(xx, yy, zz, &qx, &qy);
-#endif
         zlo = fminf(zlo, zz);
         // cvRound(32 x) by the 1.5 * 2^23 magic add; one fma: 32 x is exact, so fma(x, 32, magic) rounds once, like (32 x) + magic.
         // xq, yq keep the float's bits: 0x4B400000 + q with q the rounded coordinate (|q| < 2^22); the bias is a multiple of 2^22,
@@ -1135,9 +1038,6 @@ __device__ __forceinline__ void warp_strip_body(const V3Frame& f, int tx0, int t
         const int ty0 = (ty_first + k) * V3_TH, parity = PIPE ? (k & 1) : 0;
         bool deferred = false;
         V3_STAMP(0);
-#if WV3_PRIO == 2
-        __builtin_amdgcn_s_setprio(1);
-#endif
         if (!PIPE) {        // tile k itself: map, copies, (wait for everything)
             v3_map<RING>(f, rowtab, cs.x, cs.y, ty0, ring_lds, 0, cw, cmsk, cu_);
             V3_STAMP(1);
@@ -1153,9 +1053,6 @@ __device__ __forceinline__ void warp_strip_body(const V3Frame& f, int tx0, int t
             }
         }
         V3_STAMP(2);
-#if WV3_PRIO == 2
-        __builtin_amdgcn_s_setprio(0);
-#endif
         if (k >= 0) {
             WSTAT(cu_.fast ? (cu_.interior ? 0 : 1) : 2);
             if (deferred) WSTAT(4);
@@ -1164,9 +1061,6 @@ __device__ __forceinline__ void warp_strip_body(const V3Frame& f, int tx0, int t
                 unsigned p[V3_TH][3];     // a channel in the upper 16 bits
                 wait_vm_dyn(pend);
                 V3_STAMP(3);
-#if WV3_PRIO == 1
-                __builtin_amdgcn_s_setprio(2);      // the gather's LDS reads go out ahead of other waves' arithmetic
-#endif
                 // (the empty asm makes a pixel's word opaque per branch: otherwise the common decode of all pixels is hoisted above
                 // the branch and lives in 5 VGPRs per pixel)
                 if (cu_.interior) {
@@ -1174,11 +1068,7 @@ __device__ __forceinline__ void warp_strip_body(const V3Frame& f, int tx0, int t
                     for (int i = 0; i < V3_TH; i++) {
                         unsigned w = cw[i];
                         asm volatile("" : "+v"(w));
-#if WV_ABL == 2
-                        p[i][0] = w << 16; p[i][1] = w << 8; p[i][2] = w;
-#else
                         v3_sample<true>(cu_.pitch, w, p[i]);
-#endif
                         if (i % V3_GG == V3_GG - 1) __builtin_amdgcn_sched_barrier(0);
                     }
                 } else {
@@ -1190,9 +1080,6 @@ __device__ __forceinline__ void warp_strip_body(const V3Frame& f, int tx0, int t
                         if (i % V3_GG == V3_GG - 1) __builtin_amdgcn_sched_barrier(0);
                     }
                 }
-#if WV3_PRIO == 1
-                __builtin_amdgcn_s_setprio(0);
-#endif
                 const bool ones = cu_.interior != 0;     // (uniform) all taps inside the frame: every lane's mask bits are set
                 int nst = 0;
                 asm volatile("" ::"v"(p[V3_TH - 1][2]));
@@ -1220,9 +1107,6 @@ __device__ __forceinline__ void warp_strip_body(const V3Frame& f, int tx0, int t
                         u4v v[3];
 #pragma unroll
                         for (int kk = 0; kk < 3; kk++) v[kk] = *(const __attribute__((address_space(3))) u4v*)(uintptr_t)(reg + loff + kk * 128);
-#if WV_ABL == 1
-                        asm volatile("" ::"v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(dg + poff));
-#else
                         if (wide_out) {
                             // scalar base + 32-bit lane offset + immediate: no 64-bit address pair per lane (three of them cost the
                             // kernel its fifth wave per SIMD)
@@ -1234,14 +1118,9 @@ __device__ __forceinline__ void warp_strip_body(const V3Frame& f, int tx0, int t
 #pragma unroll
                             for (int kk = 0; kk < 3; kk++) v3_store_piece(dg + poff + kk * 128, v[kk], false);
                         }
-#endif
                         const u2v mv = ones ? u2v{0xffffffffu, 0xffffffffu} : *(const __attribute__((address_space(3))) u2v*)(uintptr_t)(reg + V3_OUT_IMG + lane * 8);
-#if WV_ABL == 1
-                        asm volatile("" ::"v"(mv), "v"(mg + moff));
-#else
                         if (wide_mask) asm volatile("global_store_dwordx2 %0, %1, %2" ::"v"(moff), "v"(mv), "s"(mg) : "memory");
                         else { volatile uint16_t* q = reinterpret_cast<volatile uint16_t*>(mg + moff); q[0] = (uint16_t)mv.x; q[1] = (uint16_t)(mv.x >> 16); q[2] = (uint16_t)mv.y; q[3] = (uint16_t)(mv.y >> 16); }
-#endif
                         nst += (wide_out ? 3 : 0) + (wide_mask ? 1 : 0);     // (narrow stores: not counted -- a lower bound keeps the wait safe)
                     } else if (gy0 < f.dh) {
                         // edge groups (the roi's last columns / rows): whole pieces where they fit, single shorts / bytes for the rest
@@ -1377,7 +1256,6 @@ struct V3Batch {
 static void v3_plan_strips(const MisContext* ctx, const WarpArgs* args, int ng, int base, int* nt_out) {
     const long long slots = (long long)std::max(ctx->num_cu, 1) * 4 * WV3_WAVES_MIN;
     long long after = 0;        // tiles of the frames behind frame k in the grid
-    static const char* plan_env = getenv("MIS_WARP_NT_PLAN");      // experiments: "8,8,...,4,2" (per frame of a launch, the last entry repeats)
     for (int k = ng - 1; k >= 0; k--) {
         const long long tiles = (long long)((args[k].dw + V3_TW - 1) / V3_TW) * ((args[k].dh + V3_TH - 1) / V3_TH);
         int nt = base;
@@ -1385,14 +1263,6 @@ static void v3_plan_strips(const MisContext* ctx, const WarpArgs* args, int ng, 
         else if (after + tiles <= slots * WV3_TAIL4) nt = std::min(nt, 4);
         nt_out[k] = nt;
         after += tiles;
-    }
-    if (plan_env) {
-        int v = base, k = 0;
-        const char* p = plan_env;
-        while (k < ng) {
-            if (*p) { v = atoi(p); while (*p && *p != ',') p++; if (*p == ',') p++; }
-            nt_out[k++] = std::max(1, std::min(v, WV3_NT_MAX));
-        }
     }
 }
 
@@ -1526,7 +1396,7 @@ extern "C" int mis_warp_spherical(MisContext* ctx, const MisImage* src, float sc
     return MIS_OK;
 }
 
-static int grid_of(const WarpArgs& a, int* ntiles);
+static int grid_of(const WarpArgs& a);
 static int warp_fused_impl(MisContext* ctx, const MisImage* src, float scale, const float K[9], const float R[9],
                            MisImage* dst, MisImage* dmask, MisPoint* tl, int repeats, float* avg_us, const MisRect* known_roi = nullptr) {
     if (!ctx) return MIS_E_INVALID;
@@ -1552,8 +1422,7 @@ static int warp_fused_impl(MisContext* ctx, const MisImage* src, float scale, co
     }
     float* tab = (float*)ctx->stage;
     hipLaunchKernelGGL(warp_trig_kernel, dim3((trig_cols(a.dw) + a.dh + 255) / 256), dim3(256), 0, ctx->stream, a, tab);
-    int ntiles;
-    const int nwg = grid_of(a, &ntiles);
+    const int nwg = grid_of(a);
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (avg_us) {
         MIS_HIP(ctx, hipEventCreate(&e0));
@@ -1563,7 +1432,7 @@ static int warp_fused_impl(MisContext* ctx, const MisImage* src, float scale, co
     // one frame per launch: round 2's tile kernel (measured faster there than the strip forms: 23.2 us against 29.3 for one-tile
     // strips and more for longer ones -- a frame alone is 3.5 tiles per wave slot, gpurun_out/r4_plan_ab3.txt)
     for (int rep = 0; rep < repeats; rep++)
-        hipLaunchKernelGGL(warp_fused_kernel, dim3(nwg), dim3(64 * TILE_WAVES), 0, ctx->stream, a, (const float*)tab, ntiles);
+        hipLaunchKernelGGL(warp_fused_kernel, dim3(nwg), dim3(64 * TILE_WAVES), 0, ctx->stream, a, (const float*)tab);
     if (avg_us) {
         float ms = 0.f;
         MIS_HIP(ctx, hipEventRecord(e1, ctx->stream));
@@ -1593,15 +1462,10 @@ extern "C" int mis_warp_spherical_fused_roi(MisContext* ctx, const MisImage* src
     return warp_fused_impl(ctx, src, scale, K, R, dst, dmask, tl, 1, nullptr, roi);
 }
 
-static int grid_of(const WarpArgs& a, int* ntiles) {
-    *ntiles = ((a.dw + FT_W - 1) / FT_W) * ((a.dh + FT_H - 1) / FT_H);
-#if WV_ORDER == 2
-    // whole chunks, a multiple of 8 of them (workgroups past the tile grid return at once)
+// workgroups of warp_fused_kernel: whole chunks, a multiple of 8 of them (workgroups past the tile grid return at once)
+static int grid_of(const WarpArgs& a) {
     const int nchunks = (((a.dw + FT_W - 1) / FT_W + CH_W - 1) / CH_W) * (((a.dh + FT_H - 1) / FT_H + CH_H - 1) / CH_H);
     return ((nchunks + 7) / 8) * 8 * (CH_W / TILE_WAVES) * CH_H;
-#else
-    return (*ntiles + TILE_WAVES - 1) / TILE_WAVES;
-#endif
 }
 
 // n fused warps (the loop of image_stitching.cpp:1154-1164 for all frames) in one grid per WB_MAX frames; the results are those of
@@ -1655,25 +1519,19 @@ static int warp_fused_batch_impl(MisContext* ctx, const MisImage* srcs, int n, f
         ctx->stage_bytes = tab_total * 2 + 4096;
     }
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    std::vector<WarpBatch> batches;
-    std::vector<dim3> grids;
-#if WV_V3
     std::vector<V3Batch> v3batches;
     int nt3 = 1 << 30;      // tiles per strip: one value for the grid (the smallest any frame asks for)
     for (int i = 0; i < n; i++) nt3 = std::min(nt3, v3_strip_tiles(ctx, args[i], n));
-#endif
     for (int g0 = 0; g0 < n; g0 += WB_MAX) {
         const int ng = std::min(WB_MAX, n - g0);
         WarpBatch b;
-        int max_wg = 0, max_trig = 0;
+        int max_trig = 0;
         for (int k = 0; k < WB_MAX; k++) {
             const int i = g0 + (k < ng ? k : 0);
             b.a[k] = args[i]; b.tab[k] = (const float*)((uint8_t*)ctx->stage + tab_off[i]);
-            b.nwg[k] = grid_of(args[i], &b.ntiles[k]);
-            if (k < ng) { max_wg = std::max(max_wg, b.nwg[k]); max_trig = std::max(max_trig, (trig_cols(args[i].dw) + args[i].dh + 255) / 256); }
+            if (k < ng) max_trig = std::max(max_trig, (trig_cols(args[i].dw) + args[i].dh + 255) / 256);
         }
         hipLaunchKernelGGL(warp_trig_batch_kernel, dim3(max_trig, ng), dim3(256), 0, ctx->stream, b);
-#if WV_V3
         // one-dimensional grid: frame after frame, per-frame strip lengths (short strips for the frames at the launch's end)
         V3Batch vb;
         int nts[WB_MAX];
@@ -1690,11 +1548,6 @@ static int warp_fused_batch_impl(MisContext* ctx, const MisImage* srcs, int n, f
         }
         vb.wg_base[WB_MAX] = wg;
         v3batches.push_back(vb);
-        max_wg = wg; 
-        batches.push_back(b); grids.push_back(dim3(max_wg));
-#else
-        batches.push_back(b); grids.push_back(dim3(max_wg, ng));
-#endif
     }
     if (avg_us) {
         MIS_HIP(ctx, hipEventCreate(&e0));
@@ -1702,12 +1555,8 @@ static int warp_fused_batch_impl(MisContext* ctx, const MisImage* srcs, int n, f
         MIS_HIP(ctx, hipEventRecord(e0, ctx->stream));
     }
     for (int rep = 0; rep < repeats; rep++)
-        for (size_t g = 0; g < batches.size(); g++)
-#if WV_V3
-            hipLaunchKernelGGL(warp_strip_batch_kernel, grids[g], dim3(64 * V3_WAVES), 0, ctx->stream, v3batches[g]);
-#else
-            hipLaunchKernelGGL(warp_fused_batch_kernel, grids[g], dim3(64 * TILE_WAVES), 0, ctx->stream, batches[g]);
-#endif
+        for (const V3Batch& vb : v3batches)
+            hipLaunchKernelGGL(warp_strip_batch_kernel, dim3(vb.wg_base[WB_MAX]), dim3(64 * V3_WAVES), 0, ctx->stream, vb);
     if (avg_us) {
         float ms = 0.f;
         MIS_HIP(ctx, hipEventRecord(e1, ctx->stream));

@@ -160,9 +160,10 @@ class HipEngine:
         self._keep = []
         # warp + blend run in a context of their own (second stream): StitchJob composes speculatively while the
         # latency-bound RANSAC chains of the matcher leave most of the device idle
-        # (normal priority: a low-priority stream was measured -- the compose work then finishes after the matcher, 20.1 ms)
+        # (normal priority: a low-priority stream was measured -- the compose work then finishes after the matcher, 20.1 ms;
+        # in round 4, eight runs of 150 steps: no difference)
         h = C.c_void_p()
-        ctx.check(ctx.lib.mis_stream_create(ctx.device.index, int(os.environ.get('MIS_COMPOSE_PRIO', '0')), C.byref(h)))      # (MIS_COMPOSE_PRIO > 0: the least urgent priority -- measured in round 4, eight runs of 150 steps: no difference)
+        ctx.check(ctx.lib.mis_stream_create(ctx.device.index, 0, C.byref(h)))
         self._compose_stream_handle = h
         self.compose_stream = torch.cuda.ExternalStream(h.value, device=ctx.device)
         self.cctx = st.Context(ctx.device.index, stream=h.value)
@@ -340,8 +341,7 @@ class HipEngine:
         """Queue the compose stream behind the 2-NN pass of matcher call `target_seq` (made by another thread): that
         pass fills the device, the RANSAC chains after it do not -- composing from there on costs the matcher nothing
         (measured: 0.5 ms per 16 x 4K step against starting at once)."""
-        import os
-        rc = self.ctx.lib.mis_match_knn_fence(self.ctx.h, None if os.environ.get('MIS_COMPOSE_GPU_FENCE') == '0' else self._compose_stream_handle, target_seq, 50)
+        rc = self.ctx.lib.mis_match_knn_fence(self.ctx.h, self._compose_stream_handle, target_seq, 50)
         if rc == 1:      # MIS_FENCE_TIMEOUT: the matcher call did not show up (a first call that allocates its arenas can take longer)
             # no fence, only less overlap control: the frames' producer was ordered before the compose stream at run() entry
             self.fence_timeouts = getattr(self, "fence_timeouts", 0) + 1

@@ -167,8 +167,7 @@ int mis_matches_free(MisMatchesInfo* m, int count);
  * mis_match_knn_fence(ctx, stream, mis_match_sequence(ctx) + 1 taken BEFORE the other thread calls the matcher, ms)
  * makes `stream` wait for the point of that call behind which other work shares the device well: by default the first draw of
  * the side RANSAC chain, 0.55 ms behind the 2-NN pass (the chains' kernels are few large workgroups that wait for room once another
- * stream's grids fill the compute units; from that point on they hold theirs).  MIS_COMPOSE_GATE in the environment moves it:
- * 1 = the end of the first RANSAC phase, 0 = the end of the 2-NN pass. */
+ * stream's grids fill the compute units; from that point on they hold theirs). */
 long long mis_match_sequence(MisContext* ctx);
 int mis_match_knn_fence(MisContext* ctx, void* stream, long long target_seq, int timeout_ms);
 /* The same without a second host thread: a one-shot hook of this context's NEXT matcher call.  fn(user) runs on the thread that

@@ -275,27 +275,22 @@ np.savez(sys.argv[2], **out)
 '''
 
 
-def test_three_chain_matcher_flow_gives_identical_results(tmp_path):
-    """MIS_MATCH_CHAINS=3 (second estimation from the RANSAC mask while the first H is still being refined, the |det H| test
-    on the host) against the default flow: six 4K frames, every pair's confidence, inlier count, mask and H bit for bit.
-    The switch is read once per process, hence two child processes (one after the other)."""
-    import os
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    outs = []
-    for chains in ("2", "3"):
-        path = str(tmp_path / ("chains%s.npz" % chains))
-        env = dict(os.environ, MIS_MATCH_CHAINS=chains)
-        r = subprocess.run([sys.executable, "-c", _CHAINS3_SCRIPT, root, path], env=env, capture_output=True, text=True, timeout=300)
-        assert r.returncode == 0, r.stdout + r.stderr
-        outs.append(np.load(path))
-    a, b = outs
-    assert sorted(a.files) == sorted(b.files) and len(a.files) == 4 * 36
+def test_three_chain_matcher_flow_gives_identical_results(ctx, oracle_mod):
+    """The matcher's three-chain flow (second estimation from the RANSAC mask while the first H is still being refined, the
+    |det H| test on the host) against the oracle: six 4K frames of config 3, every MatchesInfo field of every pair bit for bit."""
+    import synth
+    import image_stitching_amd as isa
+    size = (3840, 2160)
+    cams = synth.workload("config3")[4:10]
+    frames = [synth.render_frame_gpu(c) for c in cams]
+    feats = isa.OrbFeatureFinder(ctx, size).detect_batch(frames)
+    pm = isa.BestOf2NearestMatcher(ctx, 0.32)(feats)
+    ref = oracle_mod.match_all_pairs([_feat_dict(*f.download(), size) for f in feats])
+    assert len(pm) == len(ref) == 36
     ran = 0
-    for k in a.files:
-        assert a[k].shape == b[k].shape and a[k].tobytes() == b[k].tobytes(), k
-        ran += k.startswith("n") and int(a[k]) > 0
+    for g, o in zip(pm, ref):
+        _compare_matches_info(g, o)
+        ran += g.num_inliers > 0
     assert ran >= 10      # adjacent frames do have inliers: the second estimation was exercised
 
 

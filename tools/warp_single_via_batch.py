@@ -1,5 +1,5 @@
 """One 4K frame through the batched strip grid (mis_warp_spherical_fused_batch with n = 1) against the one-frame launch
-(mis_warp_spherical_fused): which kernel should a single launch run?  MIS_WARP_NT_PLAN sets the strip length."""
+(mis_warp_spherical_fused): which kernel should a single launch run?"""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
