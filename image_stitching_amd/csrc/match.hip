@@ -809,6 +809,13 @@ int match_impl(MisContext* ctx, const MisFeatures* feats, int n, const MisMatchP
             pairs.push_back(pd);
         }
     MIS_CHECK(ctx, !(use_l2 && use_bin), MIS_E_INVALID, "binary and float descriptors cannot be mixed in one matcher call");
+    // l2_prep_kernel zero-pads every frame to 128 columns: frames of different widths would be compared silently
+    // (cv::BFMatcher asserts on it, and mis_knn2 refuses it)
+    for (int i = 0, cols = 0; use_l2 && i < n; i++)
+        if (feats[i].n > 0) {
+            MIS_CHECK(ctx, cols == 0 || feats[i].desc_cols == cols, MIS_E_INVALID, "float descriptors of different widths in one matcher call");
+            cols = feats[i].desc_cols;
+        }
     const int np = (int)pairs.size();
     if (np == 0) return MIS_OK;
     int maxq = 0;

@@ -76,8 +76,9 @@ def _empty_image(ctx, h, w, c, tdtype):
     row = w * c * es
     pitch = (row + 255) // 256 * 256
     buf = torch.empty((h, pitch // es), dtype=tdtype, device=ctx.device)
-    v = buf[:, : w * c]
-    return v.view(h, w, c) if c > 1 else v
+    # as_strided, not view: a view of a single row reports a dense row stride (w * c), which the library refuses for the
+    # fused warp's 16SC3 output when w is odd (rows must be 4-byte aligned)
+    return buf.as_strided((h, w, c), (pitch // es, c, 1)) if c > 1 else buf[:, : w * c]
 
 
 class Context:

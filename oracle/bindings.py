@@ -329,7 +329,8 @@ def match_pair(f1, f2, params=None):
     F1, k1 = _mk_features(f1)
     F2, k2 = _mk_features(f2)
     mi = MatchesInfo()
-    lib().mo_match_pair(C.byref(F1), C.byref(F2), C.byref(params), C.byref(mi))
+    if lib().mo_match_pair(C.byref(F1), C.byref(F2), C.byref(params), C.byref(mi)):
+        raise ValueError("mo_match_pair: descriptors of different types or widths")
     out = _unpack_matches(mi)
     lib().mo_matches_free(C.byref(mi), 1)
     return out
@@ -345,7 +346,8 @@ def match_all_pairs(feats, params=None):
         arr[i] = F
         keep.append(k)
     mis = (MatchesInfo * (n * n))()
-    lib().mo_match_all_pairs(arr, n, C.byref(params), mis)
+    if lib().mo_match_all_pairs(arr, n, C.byref(params), mis):
+        raise ValueError("mo_match_all_pairs: descriptors of different types or widths")
     out = [_unpack_matches(mis[i]) for i in range(n * n)]
     lib().mo_matches_free(mis, n * n)
     return out

@@ -471,6 +471,8 @@ int mo_match_pair(const MoFeatures* f1, const MoFeatures* f2, const MoMatchParam
     memset(out, 0, sizeof(*out));
     out->src_img_idx = -1; out->dst_img_idx = -1;
     int n1 = f1->n, n2 = f2->n;
+    /* cv::BFMatcher asserts on descriptors of different types or widths: refuse them before any read */
+    if (n1 > 0 && n2 > 0 && (!f1->desc_u8 != !f2->desc_u8 || f1->dim != f2->dim)) return -1;
     int* i12 = (int*)malloc(sizeof(int) * 2 * (size_t)(n1 + 1)); float* d12 = (float*)malloc(sizeof(float) * 2 * (size_t)(n1 + 1));
     int* i21 = (int*)malloc(sizeof(int) * 2 * (size_t)(n2 + 1)); float* d21 = (float*)malloc(sizeof(float) * 2 * (size_t)(n2 + 1));
     uint8_t* acc12 = (uint8_t*)calloc((size_t)(n1 + 1), 1);
@@ -540,6 +542,11 @@ static void invert3(const double* H, double* I) {
 
 int mo_match_all_pairs(const MoFeatures* feats, int n, const MoMatchParams* p, MoMatchesInfo* out) {
     for (int i = 0; i < n * n; i++) { memset(&out[i], 0, sizeof(out[i])); out[i].src_img_idx = out[i].dst_img_idx = -1; }
+    for (int i = 0, first = -1; i < n; i++)
+        if (feats[i].n > 0) {
+            if (first >= 0 && (!feats[i].desc_u8 != !feats[first].desc_u8 || feats[i].dim != feats[first].dim)) return -1;
+            if (first < 0) first = i;
+        }
     /* pairs are independent: they run under one parallel loop, as FeaturesMatcher::operator() runs them under
      * parallel_for_ (matchers.cpp MatchPairsBody); the 2-NN loops inside a pair then run serially (no nested teams) */
     int npairs = 0;

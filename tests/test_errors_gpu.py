@@ -101,6 +101,27 @@ def test_matcher_refuses_mixed_descriptors_and_recovers(ctx):
         assert np.array_equal(x.matches, y.matches) and x.confidence == y.confidence
 
 
+def test_matcher_refuses_mixed_float_widths_and_recovers(ctx):
+    """Float descriptors of different widths in one all-pairs call (the L2 path pads every frame to 128 columns, so they would
+    be compared silently): refused before any launch, plain and sharded; the same matcher then still gives the exact lists."""
+    import refimpl as ri
+    import image_stitching_amd as isa
+    from image_stitching_amd.stitching import KP_DTYPE
+    rng = np.random.default_rng(8)
+    d64 = rng.integers(0, 256, (40, 64)).astype(np.float32)
+    d128 = rng.integers(0, 256, (50, 128)).astype(np.float32)
+    mk = lambda d, i: isa.ImageFeatures.upload(ctx, (320, 180), np.zeros(len(d), KP_DTYPE), d, i)
+    m = isa.BestOf2NearestMatcher(ctx, 0.32)
+    for world in (1, 2):
+        with pytest.raises(isa.MisError) as e:
+            m([mk(d64, 0), mk(d128, 1)], rank=0, world_size=world)
+        assert e.value.code == E_INVALID
+    other = np.clip(d128 + rng.integers(-3, 4, d128.shape), 0, 255).astype(np.float32)
+    pm = m([mk(d128, 0), mk(np.zeros((0, 64), np.float32), 1), mk(other, 2)])      # an empty frame's width does not count
+    ref = ri.best_of_2_nearest_matches(d128, other, 0.32)
+    assert len(ref) > 10 and np.array_equal(pm[2].matches, ref.astype(pm[2].matches.dtype))
+
+
 def test_batched_warp_error_hands_back_what_it_allocated(ctx):
     """mis_warp_spherical_fused_batch with library-allocated outputs (data == NULL) and a bad second frame: the call fails with a
     code, frame 0's freshly allocated outputs are released and the caller's structs are back to data == NULL; the same call with

@@ -1,0 +1,186 @@
+"""The 2-NN matchers (HIP) against the exact numpy references of tests/refimpl.py: mis_knn2 bit for bit, and every
+BestOf2NearestMatcher list element for element, at the sizes and distance regimes where the kernels go wrong."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import refimpl as ri
+
+pytestmark = pytest.mark.gpu
+
+HM_TRAINS = [1, 2, 3, 31, 32, 33, 255, 256, 257, 8191, 8192, 8193, 9000]   # > 8192: the vector fallback inside match_impl
+QUERIES = [1, 255, 256, 257]
+
+
+def _flip(rng, d, nbits):
+    """Flip `nbits` distinct random bits of each 32-byte row of d (in place)."""
+    for r in range(d.shape[0]):
+        for b in rng.choice(256, nbits, replace=False):
+            d[r, b >> 3] ^= np.uint8(1 << (b & 7))
+    return d
+
+
+def _bits(nbits_idx):
+    m = np.zeros(32, np.uint8)
+    for b in nbits_idx:
+        m[b >> 3] |= np.uint8(1 << (b & 7))
+    return m
+
+
+def hamming_far_sets(rng, nq, nt):
+    """Trains clustered around one descriptor B (<= 3 bits flipped) plus one train B ^ H (H: 128 random bit positions);
+    queries near B's complement, ~B ^ G with G a 4..20-bit subset of H.  Every query-train distance exceeds 128 (a zero
+    padding row of the fp4 kernel scores 128), and each query's best is the special train at 132..148 with the cluster at
+    >= 233: the ratio test accepts it."""
+    B = rng.integers(0, 256, 32, dtype=np.uint8)
+    t = np.repeat(B[None], nt, 0)
+    for r in range(nt):
+        _flip(rng, t[r:r + 1], int(rng.integers(0, 4)))
+    hpos = rng.choice(256, 128, replace=False)
+    s = nt // 2
+    t[s] = B ^ _bits(hpos)
+    q = np.empty((nq, 32), np.uint8)
+    for r in range(nq):
+        q[r] = ~B ^ _bits(rng.choice(hpos, int(rng.integers(4, 21)), replace=False))
+    if nq > 1 and nt > 1:
+        q[1] = ~t[0]                     # distance 256
+    return q, t
+
+
+def hamming_edge_sets(rng, nq, nt):
+    """Random descriptors with exact duplicates (distance 0, ties across tiles), an all-equal block (ties) and queries
+    exactly on the float32 ratio boundary at conf 0.32: best 17, second 25 (17 < 0.68f * 25 is false)."""
+    q = rng.integers(0, 256, (nq, 32), dtype=np.uint8)
+    t = rng.integers(0, 256, (nt, 32), dtype=np.uint8)
+    if nt >= 3:
+        t[-1] = t[0]
+        t[nt // 2] = t[0]
+        q[0] = t[0]                      # distance 0, three-way tie
+    if nt >= 40:
+        t[5:37] = t[4]                   # an all-equal block spanning a tile edge
+    if nt >= 2 and nq >= 3:
+        a = 1 if nt > 1 else 0
+        pos = rng.permutation(256)
+        q[2] = t[a] ^ _bits(pos[:17])                  # d(q, a) = 17
+        b = nt - 2 if nt > 2 else 0
+        if b != a:
+            t[b] = t[a] ^ _bits(pos[17:25])            # d(q, b) = 25
+    if nq >= 4 and nt >= 3:
+        q[3] = ~q[0]                     # distance 256 to the duplicates
+    return q, t
+
+
+def _upload(ctx, d, i=0, size=(640, 480)):
+    import image_stitching_amd as isa
+    from image_stitching_amd.stitching import KP_DTYPE
+    rng = np.random.default_rng(len(d) + 7 * i)
+    k = np.zeros(len(d), KP_DTYPE)
+    k["x"] = rng.uniform(0, size[0], len(d))
+    k["y"] = rng.uniform(0, size[1], len(d))
+    return isa.ImageFeatures.upload(ctx, size, k, d, i)
+
+
+def _knn2(ctx, q, t):
+    fq, ft = _upload(ctx, q), _upload(ctx, t)
+    idx = np.zeros((len(q), 2), np.int32)
+    dist = np.zeros((len(q), 2), np.float32)
+    ctx.check(ctx.lib.mis_knn2(ctx.h, C.byref(fq.raw), C.byref(ft.raw), idx.ctypes.data_as(C.c_void_p), dist.ctypes.data_as(C.c_void_p)))
+    return idx, dist
+
+
+def _assert_knn2_equal(idx, dist, ridx, rdist):
+    assert np.array_equal(idx, ridx), np.argwhere(idx != ridx)[:5]
+    have = ridx >= 0                     # no second neighbour in a train set of one: only the index (-1) is defined
+    assert np.array_equal(dist[have].view(np.uint32), np.asarray(rdist, np.float32)[have].view(np.uint32))
+
+
+@pytest.mark.parametrize("nt", HM_TRAINS)
+def test_knn2_hamming_vs_exact(ctx, nt):
+    rng = np.random.default_rng(nt)
+    for nq in QUERIES:
+        for gen in (hamming_far_sets, hamming_edge_sets):
+            q, t = gen(rng, nq, nt)
+            idx, dist = _knn2(ctx, q, t)
+            ridx, rdist = ri.knn2_hamming_exact(q, t)
+            _assert_knn2_equal(idx, dist, ridx, rdist)
+
+
+def _check_all_pairs(ctx, sets, conf):
+    import image_stitching_amd as isa
+    feats = [_upload(ctx, d, i) for i, d in enumerate(sets)]
+    pm = isa.BestOf2NearestMatcher(ctx, conf)(feats)
+    n = len(sets)
+    accepted = 0
+    for i in range(n):
+        for j in range(i + 1, n):
+            ref = ri.best_of_2_nearest_matches(sets[i], sets[j], conf)
+            g = pm[i * n + j].matches
+            assert np.array_equal(g, ref.astype(g.dtype)), (i, j, len(g), len(ref))
+            tr = pm[j * n + i].matches
+            assert np.array_equal(tr["query_idx"], g["train_idx"]) and np.array_equal(tr["train_idx"], g["query_idx"])
+            assert np.array_equal(tr["distance"], g["distance"])
+            accepted += len(ref)
+    return accepted
+
+
+@pytest.mark.parametrize("nt", HM_TRAINS)
+def test_match_all_pairs_hamming_vs_reference(ctx, nt):
+    """Three frames: the train set of nt descriptors between two query sets.  max n <= 8192 takes the fp4 matrix kernel,
+    larger sets the vector kernel inside match_impl."""
+    rng = np.random.default_rng(1000 + nt)
+    for gen in (hamming_far_sets, hamming_edge_sets):
+        q, t = gen(rng, 257 + 255, nt)
+        qa, qb = q[:257], q[257:]
+        accepted = _check_all_pairs(ctx, [qa, t, qb], 0.32)
+        if gen is hamming_far_sets and nt >= 2:
+            assert accepted > 0                  # the far regime must exercise accepted matches above distance 128
+    for nq in (1, 256):
+        q, t = hamming_edge_sets(rng, nq, nt)
+        _check_all_pairs(ctx, [q, t], 0.32)
+
+
+L2_COLS = [1, 2, 64, 100, 127, 128]
+
+
+def l2_sets(rng, nq, nt, cols):
+    """Integer descriptors 0..255 (SIFT style) with duplicates (ties), all-0 against all-255 (the largest norm) and a query on
+    the float32 ratio boundary: best 17, second 25."""
+    q = np.clip(np.rint(rng.gamma(0.6, 30.0, (nq, cols))), 0, 255).astype(np.float32)
+    t = np.clip(np.rint(rng.gamma(0.6, 30.0, (nt, cols))), 0, 255).astype(np.float32)
+    t[nt - 1] = t[3]
+    t[nt // 2] = t[3]
+    q[0] = t[3]
+    q[1] = 0.0
+    t[7] = 255.0
+    q[2] = 255.0
+    t[9] = 0.0
+    q[4] = 100.0                          # best 17 (t[11]), second 25 (t[12]) along the first column
+    t[11] = 100.0
+    t[11, 0] = 83.0
+    t[12] = 100.0
+    t[12, 0] = 125.0
+    return q, t
+
+
+@pytest.mark.parametrize("cols", L2_COLS)
+def test_knn2_l2_vs_exact(ctx, cols):
+    rng = np.random.default_rng(cols)
+    for nq, nt in ((64, 40), (300, 1025)):
+        q, t = l2_sets(rng, nq, nt, cols)
+        idx, dist = _knn2(ctx, q, t)
+        ridx, rdist = ri.knn2_l2_exact(q, t)
+        _assert_knn2_equal(idx, dist, ridx, rdist)
+    q, t = np.zeros((3, cols), np.float32), np.full((2, cols), 255.0, np.float32)
+    idx, dist = _knn2(ctx, q, t)
+    assert dist[0, 0] == np.float32(np.sqrt(cols * 255.0 ** 2))
+    _assert_knn2_equal(idx, dist, *ri.knn2_l2_exact(q, t))
+
+
+@pytest.mark.parametrize("cols", L2_COLS)
+def test_match_all_pairs_l2_vs_reference(ctx, cols):
+    rng = np.random.default_rng(100 + cols)
+    qa, t = l2_sets(rng, 120, 300, cols)
+    qb, _ = l2_sets(rng, 50, 300, cols)
+    _check_all_pairs(ctx, [qa, t, qb], 0.32)
+    _check_all_pairs(ctx, [qa, t], 0.65)
