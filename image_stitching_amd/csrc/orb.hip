@@ -1056,29 +1056,53 @@ void linear_exact_coeffs(int dlen, int slen, int* ofs, int* m1) {
     }
 }
 
-// level geometry + budgets for an image size (orb.cpp: layer sizes, nfeaturesPerLevel)
+// a level keeps at most this many keypoints: the final segment of a level holds min(N_l + 128, 2048) (128 for ties at the cut)
+constexpr int ORB_MAX_LEVEL_FEATURES = 2048 - 128;
+
+// orb.cpp layer size: cvRound(image.cols / scale), the division in float
+inline float level_scale(const MisOrbParams& p, int l) { return (float)pow((double)p.scale_factor, (double)l); }
+inline int level_dim(int len, float sc) { return (int)lrint((double)((float)len / sc)); }
+
+// orb.cpp nfeaturesPerLevel
+void level_budgets(const MisOrbParams& p, int* nfeat) {
+    float factor = (float)(1.0 / (double)p.scale_factor);
+    float nd = (float)p.nfeatures * (1 - factor) / (1 - (float)pow((double)factor, (double)p.nlevels));
+    int sum = 0;
+    for (int l = 0; l < p.nlevels - 1; l++) { nfeat[l] = (int)lrintf(nd); sum += nfeat[l]; nd *= factor; }
+    nfeat[p.nlevels - 1] = std::max(p.nfeatures - sum, 0);
+}
+
+// every level of a w x h frame must be non-empty (cv::resize refuses an empty size); checked before a plan is made, so that no
+// table, tile grid or launch ever sees a zero-size level
+int check_level_sizes(MisContext* ctx, const MisOrbParams& p, int w, int h) {
+    for (int l = 0; l < p.nlevels; l++) {
+        const float sc = level_scale(p, l);
+        MIS_CHECK(ctx, level_dim(w, sc) >= 1 && level_dim(h, sc) >= 1, MIS_E_UNSUPPORTED,
+                  "ORB level %d of a %dx%d frame is empty (scale_factor %g, nlevels %d)", l, w, h, (double)p.scale_factor, p.nlevels);
+    }
+    return MIS_OK;
+}
+
+// level geometry + budgets for an image size (orb.cpp: layer sizes, nfeaturesPerLevel); check_level_sizes has passed
 void plan_levels(MisOrb* o, int w, int h) {
     Levels& L = o->L;
     const MisOrbParams& p = o->p;
     L.n = p.nlevels; L.fast_t = p.fast_threshold; L.patch = p.patch_size; L.half_patch = p.patch_size / 2; L.edge = p.edge_threshold;
-    double sf = (double)p.scale_factor;
     size_t pad_off = 0, map_off = 0;
     int cand_off = 0, fin_off = 0, tab_off = 0, surv_off = 0;
-    float factor = (float)(1.0 / sf);
-    float nd = (float)p.nfeatures * (1 - factor) / (1 - (float)pow((double)factor, (double)p.nlevels));
-    int sum = 0;
+    int nfeat[ORB_MAX_LEVELS];
+    level_budgets(p, nfeat);
     for (int l = 0; l < L.n; l++) {
         LevelDesc& d = L.d[l];
-        float sc = (float)pow(sf, (double)l);
+        float sc = level_scale(p, l);
         d.scale = sc;
-        d.w = (int)lrint((double)((float)w / sc));
-        d.h = (int)lrint((double)((float)h / sc));
+        d.w = level_dim(w, sc);
+        d.h = level_dim(h, sc);
         d.pp = (int)mis_align_up((size_t)d.w + 2 * ORB_BORDER, 64);
         d.sp = (int)mis_align_up((size_t)d.w, 64);
         d.pad_off = pad_off; pad_off += (size_t)d.pp * (d.h + 2 * ORB_BORDER);
         d.map_off = map_off; map_off += (size_t)d.sp * d.h;
-        if (l < L.n - 1) { d.nfeat = (int)lrintf(nd); sum += d.nfeat; nd *= factor; }
-        else d.nfeat = std::max(p.nfeatures - sum, 0);
+        d.nfeat = nfeat[l];
         d.n2 = p.score_type == 0 ? 2 * d.nfeat : d.nfeat;
         d.tiles_x = (d.w + FT_COLS - 1) / FT_COLS; d.tiles_y = (d.h + FT_ROWS - 1) / FT_ROWS;
         d.tile_off = surv_off; surv_off += d.tiles_x * d.tiles_y;
@@ -1204,6 +1228,8 @@ int check_image(MisOrb* o, const MisImage* bgr) {
 
 int replan_if_needed(MisOrb* o, int w, int h) {
     if (w == o->cur_w && h == o->cur_h) return MIS_OK;
+    const int rc = check_level_sizes(o->ctx, o->p, w, h);     // (the current plan stays as it is)
+    if (rc != MIS_OK) return rc;
     MIS_HIP(o->ctx, hipStreamSynchronize(o->ctx->stream));
     plan_levels(o, w, h);
     o->cur_w = w; o->cur_h = h;
@@ -1300,7 +1326,17 @@ extern "C" int mis_orb_create(MisContext* ctx, const MisOrbParams* p, int max_w,
                        p->patch_size <= 40 && p->nfeatures >= 1 && p->scale_factor > 1.f && (p->score_type == 0 || p->score_type == 1) &&
                        p->edge_threshold >= 0 && p->fast_threshold >= 1 && p->fast_threshold < 255,
               MIS_E_UNSUPPORTED, "unsupported ORB parameters (need first_level 0, wta_k 2, patch <= 40, nlevels <= 16)");
+    // patchSize 31 takes OpenCV's fixed bit_pattern_31_ table, not the random pattern this library generates
+    MIS_CHECK(ctx, p->patch_size != 31, MIS_E_UNSUPPORTED, "ORB patch_size 31 (OpenCV's fixed bit_pattern_31_) is not supported");
+    {
+        int nfeat[ORB_MAX_LEVELS];
+        level_budgets(*p, nfeat);
+        for (int l = 0; l < p->nlevels; l++)
+            MIS_CHECK(ctx, nfeat[l] <= ORB_MAX_LEVEL_FEATURES, MIS_E_UNSUPPORTED,
+                      "ORB nfeatures %d gives level %d a budget of %d keypoints (at most %d per level)", p->nfeatures, l, nfeat[l], ORB_MAX_LEVEL_FEATURES);
+    }
     MIS_CHECK(ctx, max_w >= 64 && max_h >= 64 && max_w <= 32767 && max_h <= 32767, MIS_E_INVALID, "bad maximum size");
+    if (int rc = check_level_sizes(ctx, *p, max_w, max_h)) return rc;
     MIS_HIP(ctx, hipSetDevice(ctx->device));
     MisOrb* o = new MisOrb();
     o->ctx = ctx; o->p = *p; o->max_w = max_w; o->max_h = max_h;

@@ -85,7 +85,10 @@ typedef struct {
 
 /* ORB::create(nfeatures, scaleFactor, nlevels, edgeThreshold, firstLevel, WTA_K, scoreType,
  * patchSize, fastThreshold) -- replaces image_stitching/image_stitching.cpp:545.  Supported:
- * first_level 0, wta_k 2, score_type 0 (HARRIS_SCORE), patch_size <= 40, nlevels <= 16. */
+ * first_level 0, wta_k 2, score_type 0 (HARRIS_SCORE) or 1 (FAST_SCORE), patch_size 2 .. 40 except 31 (OpenCV's fixed
+ * bit_pattern_31_), nlevels <= 16, at most 1920 keypoints in any level's budget (4000 at 1.2 x 8 levels gives level 0 869), and no
+ * pyramid level of size zero: mis_orb_create (for the maximum size) and mis_orb_detect* (for the frame's) refuse the others with
+ * MIS_E_UNSUPPORTED. */
 typedef struct {
     int nfeatures;
     float scale_factor;

@@ -165,6 +165,8 @@ MoOrb* mo_orb_create(const MoOrbParams* p, int width, int height) {
     if (p->nlevels < 1 || p->nlevels > MO_ORB_MAX_LEVELS || p->first_level != 0 || p->wta_k != 2 ||
         p->patch_size < 2 || p->patch_size > 40 || width < 8 || height < 8)
         return NULL;
+    /* patchSize 31 takes OpenCV's fixed bit_pattern_31_ table (not restated here), every other size the random pattern */
+    if (p->patch_size == 31) return NULL;
     MoOrb* o = (MoOrb*)calloc(1, sizeof(MoOrb));
     const int B = MO_ORB_BORDER;
     o->p = *p; o->w = width; o->h = height; o->nlevels = p->nlevels;
@@ -174,6 +176,10 @@ MoOrb* mo_orb_create(const MoOrbParams* p, int width, int height) {
         o->lscale[l] = sc;
         o->lw[l] = mo_round_d((double)((float)width / sc));
         o->lh[l] = mo_round_d((double)((float)height / sc));
+        /* resize refuses an empty size: a pyramid with an empty level is refused as a whole */
+        if (o->lw[l] < 1 || o->lh[l] < 1) { mo_orb_destroy(o); return NULL; }
+    }
+    for (int l = 0; l < o->nlevels; l++) {
         size_t n = (size_t)o->lw[l] * o->lh[l], np = (size_t)(o->lw[l] + 2 * B) * (o->lh[l] + 2 * B);
         o->gray[l] = (uint8_t*)malloc(n);
         o->score[l] = (uint8_t*)malloc(n);
@@ -192,6 +198,9 @@ MoOrb* mo_orb_create(const MoOrbParams* p, int width, int height) {
             nd *= factor;
         }
         o->nfeat[o->nlevels - 1] = p->nfeatures - sum > 0 ? p->nfeatures - sum : 0;
+        /* the library's per-level limit (orb.hip ORB_MAX_LEVEL_FEATURES): the same parameters are refused here */
+        for (int l = 0; l < o->nlevels; l++)
+            if (o->nfeat[l] > MO_ORB_MAX_LEVEL_FEATURES) { mo_orb_destroy(o); return NULL; }
     }
     /* umax (orb.cpp): quarter-disc extents of the intensity-centroid patch */
     {

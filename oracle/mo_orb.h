@@ -12,6 +12,7 @@ extern "C" {
 #endif
 
 #define MO_ORB_MAX_LEVELS 16
+#define MO_ORB_MAX_LEVEL_FEATURES 1920 /* per-level keypoint budget limit of the library (orb.hip) */
 #define MO_ORB_BORDER 32 /* >= max(edgeThreshold, ceil(halfPatch*sqrt2), 3)+1 = 30 for patch 40 */
 
 typedef struct {

@@ -152,3 +152,53 @@ def test_batched_warp_error_hands_back_what_it_allocated(ctx):
     assert rc == 0 and ds[0].data and ms[1].data
     for k in range(2):
         ctx.lib.mis_image_free(ctx.h, C.byref(ds[k])); ctx.lib.mis_image_free(ctx.h, C.byref(ms[k]))
+
+
+def _detect_matches_reference(finder, frame, kw):
+    import torch
+    import refimpl_orb as ro
+    kps, desc = finder.detect(torch.from_numpy(frame).cuda()).download()
+    c = ro.compare_features(kps, desc, ro.orb(frame, ro.params(**kw), stages=False))
+    assert not c["errors"], c["errors"]
+
+
+def test_orb_refuses_patch_31_and_oversized_level_budgets(ctx):
+    """patch_size 31 (OpenCV's fixed bit_pattern_31_, not generated here) and an nfeatures whose level budget exceeds the 1920 a
+    level holds: MIS_E_UNSUPPORTED from mis_orb_create; the context then creates and runs a finder at the largest accepted value."""
+    import synth
+    import image_stitching_amd as isa
+    from test_refimpl_orb_cpu import MAX_NFEATURES, REFUSED, uniform_noise
+    for kw, size, why in REFUSED:
+        if why == "empty level":
+            continue
+        with pytest.raises(isa.MisError) as e:
+            isa.OrbFeatureFinder(ctx, size, isa.stitching.orb_params(**kw))
+        assert e.value.code == E_UNSUPPORTED, (kw, why)
+    for kw in (dict(patch_size=30), dict(patch_size=32), dict(nfeatures=MAX_NFEATURES)):
+        _detect_matches_reference(isa.OrbFeatureFinder(ctx, (640, 480), isa.stitching.orb_params(**kw)), uniform_noise(640, 480, 7), kw)
+    _detect_matches_reference(isa.OrbFeatureFinder(ctx, (320, 180)), synth.render_frame(synth.make_camera(320, 180, 60.0, 5.0)), {})
+
+
+def test_orb_refuses_zero_size_levels_before_any_launch(ctx):
+    """A pyramid level of size zero is refused on the host: at create time for the maximum size, at detect time for a smaller
+    frame (the plan of the last good size stays); the same finder then detects a frame whose levels are all non-empty."""
+    import torch
+    import image_stitching_amd as isa
+    from test_refimpl_orb_cpu import synth_frame
+    kw = dict(scale_factor=2.0, nlevels=8, nfeatures=1000)
+    with pytest.raises(isa.MisError) as e:                        # 64 / 2^7 = 0.5 -> 0
+        isa.OrbFeatureFinder(ctx, (64, 64), isa.stitching.orb_params(**kw))
+    assert e.value.code == E_UNSUPPORTED
+    kw = dict(scale_factor=2.0, nlevels=11, nfeatures=1000)      # level 10: 1024 x 576 -> 1 x 1 at the maximum size
+    finder = isa.OrbFeatureFinder(ctx, (1024, 576), isa.stitching.orb_params(**kw))
+    good = synth_frame(640, 520)                                  # 520 / 1024 = 0.51 -> 1
+    _detect_matches_reference(finder, good, kw)
+    for w, h in ((640, 480), (64, 64)):                            # 480 / 1024 = 0.47 -> 0
+        with pytest.raises(isa.MisError) as e:
+            finder.detect(torch.zeros((h, w, 3), dtype=torch.uint8, device="cuda"))
+        assert e.value.code == E_UNSUPPORTED
+        with pytest.raises(isa.MisError) as e:
+            finder.detect_batch([torch.zeros((h, w, 3), dtype=torch.uint8, device="cuda")] * 2)
+        assert e.value.code == E_UNSUPPORTED
+    _detect_matches_reference(finder, good, kw)
+    _detect_matches_reference(finder, synth_frame(1024, 576), kw)
