@@ -40,6 +40,8 @@ struct HomoBatch {
     unsigned* draw_next = nullptr;  // per problem: stream-position tables of the subset drawing
     int* draw_idx = nullptr;
     int* fin = nullptr;       // per problem: RANSAC phase in which it finished (0 / 1), -1 while unfinished
+    int2* work = nullptr;     // work list of a RANSAC phase: (problem, first hypothesis) of every block of hypotheses to solve and count
+    unsigned* work_ctr = nullptr;  // at offset 0 of mem: list length, tickets taken by the solve / count launches (zero between phases)
 };
 
 int homo_batch_reserve(MisContext* ctx, HomoBatch* b, int count, long long points, int max_iters);

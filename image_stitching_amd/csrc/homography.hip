@@ -10,13 +10,17 @@
 //                     consumes (duplicate redraws) and whether it passes checkSubset.  Every stream
 //                     position is simulated as the start of ONE attempt in parallel, then one thread
 //                     chases start -> end -> ... through the table: the exact sequential sequence.
+//                     When a phase's drawing ends, the problem appends its hypotheses [lo, min(n_sub, niters)) to the batch's
+//                     work list in blocks of HQ_HYPS (one atomic per problem).
 //   hyp_quad_kernel   four lanes per hypothesis: 4-point normalised DLT, 9x9 Jacobi on the upper triangle;
-//   hyp_count_kernel  one wave per hypothesis: its inlier count.
+//   hyp_count_kernel  one wave per HC_HYPS hypotheses: their inlier counts.  Both are persistent (grids sized by the number of
+//                     compute units, not by max_iters or the problem count) and work through the list's tickets.
 //   scan_tail_kernel  sequential replay of the adaptive loop (niters update) over the scored
 //                     hypotheses; when the loop ends: inlier mask, ordered compaction, DLT on all
 //                     inliers, 10-iteration LM.  f64 sums keep the CPU's order: per-point terms in
 //                     parallel, then ONE thread per accumulator; Jacobi rotations spread over n threads.
-// Phase 0 covers hypotheses [0,128) (overlapping pairs converge there), phase 1 the rest.
+// Phase 0 covers hypotheses [0,128) (overlapping pairs converge there), phase 1 the rest.  The replay launch of a phase empties the
+// work list again for the next phase or call.
 #include "homography.h"
 #include "dev_math.h"
 #include <algorithm>
@@ -30,6 +34,10 @@ namespace {
 #endif
 constexpr int PHASE0 = MIS_PHASE0;       // hypotheses evaluated before the first replay (a single phase over all 2000 was measured: 26 ms instead of 15 ms per step)
 constexpr int RNG_TABLE = 1 << 17;
+#ifndef MIS_HQ_HYPS
+#define MIS_HQ_HYPS 64
+#endif
+constexpr int HQ_HYPS = MIS_HQ_HYPS;  // solves per workgroup of hyp_quad_kernel (4 lanes each) = hypotheses per work-list entry
 constexpr int TB = 256;           // threads of draw / scan_tail workgroups
 
 struct RansacState {
@@ -261,7 +269,7 @@ constexpr int DRAW_CHUNK = 4096;
 constexpr int DRAW_TB = MIS_DRAW_TB;   // threads of a problem's workgroup: a chunk's positions are simulated DRAW_CHUNK / DRAW_TB per thread (256 threads: 0.54 + 1.08 ms for the two draw launches on the matcher's critical path)
 constexpr int DRAW_PTS = 2048;
 __global__ __launch_bounds__(DRAW_TB) void draw_kernel(const HomoCall* calls, RansacState* states, int* sub_idx, int* draw_idx, const unsigned* U,
-                                                  unsigned long long state_T, int max_iters, int phase, int k_hi_arg) {
+                                                  unsigned long long state_T, int max_iters, int phase, int k_hi_arg, int2* work, unsigned* work_ctr) {
 #if MIS_CHAIN_PRIO
     __builtin_amdgcn_s_setprio(MIS_CHAIN_PRIO);      // a latency-bound chain beside the composition's bandwidth-bound kernels: its few waves issue first
 #endif
@@ -510,6 +518,17 @@ __global__ __launch_bounds__(DRAW_TB) void draw_kernel(const HomoCall* calls, Ra
         atomicMax(&g_draw_prof[ph + 2], wall_clock64() - dp0); atomicAdd(&g_draw_prof[ph + 3], 1ull);
     }
 #endif
+    // the phase's hypotheses [lo, min(n_sub, niters)) -- at or beyond niters they can never be replayed -- go to the work list in
+    // blocks of HQ_HYPS, with ONE atomic per problem.  Every return above leaves an empty range: mode 0 / 1, n_sub = 0 (no feasible
+    // subset), or in phase 1 a problem that is done or whose drawing failed in phase 0 (n_sub < PHASE0 then)
+    if (t == 0) {
+        const int lo = phase == 0 ? 0 : min(PHASE0, max_iters), hi = min(st->n_sub, st->niters);
+        if (st->mode == 2 && !st->done && hi > lo) {
+            const int nb = (hi - lo + HQ_HYPS - 1) / HQ_HYPS;
+            const unsigned at = atomicAdd(work_ctr, (unsigned)nb);
+            for (int i = 0; i < nb; i++) work[at + i] = make_int2(b, lo + i * HQ_HYPS);
+        }
+    }
 }
 
 #ifdef MIS_TAIL_PROF
@@ -525,10 +544,6 @@ __device__ unsigned long long g_hyp_prof[8];    // [6], [7]: summed / longest re
 // lane computes c, s, t), the lane's share of the rotation, four quad arg-max re-scans over the rotated values in registers.
 // A wave holds 16 solves and a workgroup 64 (66 KB of LDS: the same 128 solves per compute unit, on eight waves instead of
 // two).  Arithmetic per element and visiting order of every scan are those of the serial loops.
-#ifndef MIS_HQ_HYPS
-#define MIS_HQ_HYPS 64
-#endif
-constexpr int HQ_HYPS = MIS_HQ_HYPS;  // solves per workgroup (4 lanes each)
 constexpr int HQ_STRIDE = HQ_HYPS + 1;         // doubles between consecutive elements of a solve (solve h at + h): the quad's lanes, same h, different elements, fall in different banks
 constexpr int HQ_ELEMS = 127;         // 36 (strict upper triangle) + 9 (W) + 81 (V) + 1 (a dummy element: the target of the pairs that do not exist)
 struct QSlot {
@@ -730,64 +745,117 @@ __device__ int dlt4_quad(const float* M, const float* m, const QSlot s, const in
     return 1;
 }
 
-__global__ __launch_bounds__(4 * HQ_HYPS) void hyp_quad_kernel(const HomoCall* calls, const RansacState* states, const int* sub_idx, double* Hc, int* valid, int lo,
-                                                               int max_iters) {
+// Both hypothesis kernels are persistent: their grids depend on the device alone, and their waves work through the tickets of the
+// phase's work list (draw_kernel) until the list is exhausted.  Wave w's first ticket is w itself; in hyp_quad_kernel a list longer
+// than the grid has waves is dealt further from an atomic counter (the solves' durations vary), hyp_count_kernel deals by stride.
+// (Every wave taking its first ticket from the counter too made 2 000 - 4 000 atomics on one address per launch: 60 - 100 us for an
+// EMPTY list, against 5 - 15 us for the old grids' early exits.)  No wave waits on another; the ticket order only decides who
+// solves / counts what -- every result lands at its (problem, hypothesis) index as before.  The replay launch behind the counts
+// (scan_tail_kernel) zeroes the list for the next phase or call.
+constexpr int HQ_WG_PER_CU = 2;     // hyp_quad_kernel: 66 KB of LDS per workgroup, two fit a compute unit
+constexpr int HC_WG_PER_CU = 4;     // hyp_count_kernel: 256 threads, few registers
+constexpr int HC_HYPS = 4;          // hypotheses per count ticket: one wave, every point loaded once for all four
+enum { WL_N = 0, WL_SOLVE = 1, WL_CTRS = 2 };   // work_ctr: list length, tickets taken from the counter by the solve launch
+static_assert(HQ_HYPS % 16 == 0 && HQ_HYPS % HC_HYPS == 0, "a work-list entry splits into whole solve and count tickets");
+// the wave's first ticket, and its next one: past the grid's own, from the counter.  Every lane takes part in the atomic (lane 0
+// adds 1, the others 0) so that no branch on the lane sits in a ticket loop -- with `if (lane == 0)` around it and around the
+// counts' stores the compiler peeled lane 0 off the loop, and the other lanes went on with a ticket that no lane had drawn.
+__device__ __forceinline__ unsigned first_ticket() { return __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)); }
+__device__ __forceinline__ unsigned next_ticket(unsigned* ctr, unsigned tickets) {
+    const unsigned waves = gridDim.x * (blockDim.x >> 6);
+    if (tickets <= waves) return tickets;        // the grid's own tickets covered the list (uniform: no atomic at all)
+    return waves + __builtin_amdgcn_readfirstlane(atomicAdd(ctr, (threadIdx.x & 63) == 0 ? 1u : 0u));
+}
+
+__global__ __launch_bounds__(4 * HQ_HYPS) void hyp_quad_kernel(const HomoCall* calls, const RansacState* states, const int* sub_idx, double* Hc, int* valid,
+                                                               int max_iters, const int2* work, unsigned* work_ctr) {
 #if MIS_CHAIN_PRIO
     __builtin_amdgcn_s_setprio(MIS_CHAIN_PRIO);
 #endif
     extern __shared__ double sl[];
-    const int b = blockIdx.y, t = threadIdx.x, h = t >> 2, q = t & 3;
-    const RansacState st = states[b];
-    if (st.mode != 2 || st.done) return;
-    const int limit = min(st.n_sub, st.niters);  // hypotheses at or beyond niters can never be replayed
-    const int k = lo + blockIdx.x * HQ_HYPS + h;
-    if (k >= limit) return;                      // whole quads leave together
-    const HomoCall c = calls[b];
-    const int* id = sub_idx + ((size_t)b * max_iters + k) * 4;
-    float ms1[8], ms2[8];
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        int qq = id[i];
-        ms1[2 * i] = c.src[2 * qq]; ms1[2 * i + 1] = c.src[2 * qq + 1];
-        ms2[2 * i] = c.dst[2 * qq]; ms2[2 * i + 1] = c.dst[2 * qq + 1];
-    }
-    double H[9];
+    const int lane = threadIdx.x & 63, q = lane & 3;
+    const int h = threadIdx.x >> 2;            // the quad's slot: each wave has 16 of its own, so waves take tickets independently
+    const unsigned tickets = work_ctr[WL_N] * (HQ_HYPS / 16);     // a ticket: 16 solves, one per quad of the wave
     const QSlot s{sl + h};
-    const int ok = dlt4_quad(ms1, ms2, s, q, H);
-    if (q == 0) {
-        if (ok) {
-            double* o = Hc + ((size_t)b * max_iters + k) * 9;
+    for (unsigned tk = first_ticket(); tk < tickets; tk = next_ticket(work_ctr + WL_SOLVE, tickets)) {
+        const int2 w = work[tk / (HQ_HYPS / 16)];
+        const int b = w.x;
+        const RansacState& st = states[b];
+        const int limit = min(st.n_sub, st.niters);
+        const int k = w.y + (int)(tk % (HQ_HYPS / 16)) * 16 + (lane >> 2);
+        if (k < limit) {                 // whole quads take part or not
+            const HomoCall c = calls[b];
+            const int* id = sub_idx + ((size_t)b * max_iters + k) * 4;
+            float ms1[8], ms2[8];
 #pragma unroll
-            for (int i = 0; i < 9; i++) o[i] = H[i];
+            for (int i = 0; i < 4; i++) {
+                int qq = id[i];
+                ms1[2 * i] = c.src[2 * qq]; ms1[2 * i + 1] = c.src[2 * qq + 1];
+                ms2[2 * i] = c.dst[2 * qq]; ms2[2 * i + 1] = c.dst[2 * qq + 1];
+            }
+            double H[9];
+            const int ok = dlt4_quad(ms1, ms2, s, q, H);
+            // the quad's four lanes hold the same H and ok: all of them store (no branch on the lane in the ticket loop)
+            if (ok) {
+                double* o = Hc + ((size_t)b * max_iters + k) * 9;
+#pragma unroll
+                for (int i = 0; i < 9; i++) o[i] = H[i];
+            }
+            valid[(size_t)b * max_iters + k] = ok;
         }
-        valid[(size_t)b * max_iters + k] = ok;
     }
 }
 
-// findInliers of every hypothesis of hyp_kernel: one wave per hypothesis, lanes over the points (the per-thread loop over all
-// matches was a third of hyp_kernel's latency for a well-matched pair: 1500 points x 30 instructions behind the Jacobi solve)
-__global__ __launch_bounds__(256) void hyp_count_kernel(const HomoCall* calls, const RansacState* states, const double* Hc, const int* valid, int* good, int lo,
-                                                        int max_iters, float thr) {
-    const int b = blockIdx.y, lane = threadIdx.x & 63;
-    const RansacState st = states[b];
-    if (st.mode != 2 || st.done) return;
-    const int limit = min(st.n_sub, st.niters);
-    const int k = lo + blockIdx.x * 4 + (int)(threadIdx.x >> 6);
-    if (k >= limit) return;      // wave-uniform
-    const size_t e = (size_t)b * max_iters + k;
-    int cnt = 0;
-    if (valid[e]) {
-        const HomoCall c = calls[b];
-        float Hf[9];
+// findInliers of every solved hypothesis: a wave per ticket of HC_HYPS consecutive hypotheses of one problem, lanes over the points
+// (the per-thread loop over all matches was a third of hyp_kernel's latency for a well-matched pair: 1500 points x 30 instructions
+// behind the Jacobi solve); each point is loaded once and tested against the ticket's models, HC_UNROLL chunks of 64 points in
+// flight.  A ticket is a few microseconds of work at most, so the tickets are dealt by stride instead of from the counter (taken
+// from it, a list of 300 entries -- 4 800 tickets for 4 096 waves -- cost 4 096 atomics on one address, 48 us against 14 for the old grid).
+constexpr int HC_UNROLL = 4;
+__global__ __launch_bounds__(256) void hyp_count_kernel(const HomoCall* calls, const RansacState* states, const double* Hc, const int* valid, int* good,
+                                                        int max_iters, float thr, const int2* work, const unsigned* work_ctr) {
+    const int lane = threadIdx.x & 63;
+    const unsigned tickets = work_ctr[WL_N] * (HQ_HYPS / HC_HYPS), waves = gridDim.x * (blockDim.x >> 6);
+    for (unsigned tk = first_ticket(); tk < tickets; tk += waves) {
+        const int2 w = work[tk / (HQ_HYPS / HC_HYPS)];
+        const int b = w.x;
+        const RansacState& st = states[b];
+        const int limit = min(st.n_sub, st.niters);
+        const int k0 = w.y + (int)(tk % (HQ_HYPS / HC_HYPS)) * HC_HYPS;
+        if (k0 >= limit) continue;       // wave-uniform
+        const size_t e0 = (size_t)b * max_iters + k0;
+        float Hf[HC_HYPS][9];
+        bool use[HC_HYPS];
+        int cnt[HC_HYPS];
 #pragma unroll
-        for (int i = 0; i < 9; i++) Hf[i] = (float)Hc[e * 9 + i];
-        for (int i0 = 0; i0 < c.n; i0 += 64) {
-            const int i = i0 + lane;
-            const int f = i < c.n ? is_inlier(Hf, c.src[2 * i], c.src[2 * i + 1], c.dst[2 * i], c.dst[2 * i + 1], thr) : 0;
-            cnt += __popcll(__ballot(f));
+        for (int j = 0; j < HC_HYPS; j++) {
+            use[j] = k0 + j < limit && valid[e0 + j];
+            cnt[j] = 0;
+#pragma unroll
+            for (int i = 0; i < 9; i++) Hf[j][i] = use[j] ? (float)Hc[(e0 + j) * 9 + i] : 0.f;
         }
+        const HomoCall c = calls[b];
+        const float2* src = reinterpret_cast<const float2*>(c.src);
+        const float2* dst = reinterpret_cast<const float2*>(c.dst);
+        for (int i0 = 0; i0 < c.n; i0 += 64 * HC_UNROLL) {
+            float2 M[HC_UNROLL], m[HC_UNROLL];
+            bool in[HC_UNROLL];
+#pragma unroll
+            for (int u = 0; u < HC_UNROLL; u++) {
+                const int i = i0 + 64 * u + lane;
+                in[u] = i < c.n;
+                M[u] = src[min(i, c.n - 1)]; m[u] = dst[min(i, c.n - 1)];     // unconditional: all the chunks' loads in flight together
+            }
+#pragma unroll
+            for (int u = 0; u < HC_UNROLL; u++)
+#pragma unroll
+                for (int j = 0; j < HC_HYPS; j++)
+                    if (use[j]) cnt[j] += __popcll(__ballot(in[u] && is_inlier(Hf[j], M[u].x, M[u].y, m[u].x, m[u].y, thr)));
+        }
+        // the counts are wave-uniform: every lane stores them (no branch on the lane in the ticket loop, as above)
+#pragma unroll
+        for (int j = 0; j < HC_HYPS; j++) if (k0 + j < limit) good[e0 + j] = cnt[j];
     }
-    if (lane == 0) good[e] = cnt;
 }
 
 // ---------------------------------------------------------------- scan_tail_kernel -------------
@@ -1502,7 +1570,9 @@ __device__ void lm_refine_coop(TailShared& S, const float* s1, const float* d1, 
 #endif
 __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(MIS_TAIL_WAVES, 8))) void scan_tail_kernel(const HomoCall* calls, RansacState* states, const double* Hc, const int* valid, const int* good,
                                                        float* scr_all, double* rec_all, HomoResult* results, int lo, int hi, int max_iters,
-                                                       double confidence, float thr, int* fin, int part, int want, int staged) {
+                                                       double confidence, float thr, int* fin, int part, int want, int staged, unsigned* work_ctr) {
+    // a replay launch runs behind the phase's last reader of the hypothesis work list: empty it for the next phase or call
+    if (work_ctr && blockIdx.x == 0 && threadIdx.x < WL_CTRS) work_ctr[threadIdx.x] = 0;
 #if MIS_CHAIN_PRIO
     __builtin_amdgcn_s_setprio(MIS_CHAIN_PRIO);      // a latency-bound chain beside the composition's bandwidth-bound kernels: its few waves issue first
 #endif
@@ -1701,20 +1771,26 @@ int homo_batch_reserve(MisContext* ctx, HomoBatch* b, int count, long long point
     count = std::max(count, 1); points = std::max(points, 1ll); max_iters = std::max(max_iters, 1);
     size_t off = 0;
     auto carve = [&](size_t bytes) { size_t o = off; off += mis_align_up(bytes, 256); return o; };
+    const size_t o_wctr = carve(sizeof(unsigned) * WL_CTRS);      // first, at a fixed place: it must survive a reserve that does not reallocate
     size_t o_calls = carve(sizeof(HomoCall) * count), o_res = carve(sizeof(HomoResult) * count), o_state = carve(sizeof(RansacState) * count);
     size_t o_sub = carve(sizeof(int) * 4 * (size_t)count * max_iters), o_hc = carve(sizeof(double) * 9 * (size_t)count * max_iters);
     size_t o_valid = carve(sizeof(int) * (size_t)count * max_iters), o_good = carve(sizeof(int) * (size_t)count * max_iters);
     size_t o_scr = carve(sizeof(float) * 4 * (size_t)points), o_rec = carve(sizeof(double) * 10 * (size_t)points);
     size_t o_dn = carve(256), o_di = carve(sizeof(int) * 4 * (size_t)count * DRAW_CHUNK), o_fin = carve(sizeof(int) * (size_t)count);
+    const size_t o_work = carve(sizeof(int2) * (size_t)count * ((max_iters + HQ_HYPS - 1) / HQ_HYPS));   // one phase's blocks at most
     if (off > b->bytes) {
         if (b->mem) { MIS_HIP(ctx, hipStreamSynchronize(ctx->stream)); MIS_HIP(ctx, hipFree(b->mem)); b->mem = nullptr; b->bytes = 0; }
         MIS_HIP(ctx, hipMalloc(&b->mem, off));
         b->bytes = off;
+        // the work list's counters start at zero; from then on every replay launch leaves them so
+        MIS_HIP(ctx, hipMemsetAsync((uint8_t*)b->mem + o_wctr, 0, sizeof(unsigned) * WL_CTRS, ctx->stream));
+        MIS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
     uint8_t* m = (uint8_t*)b->mem;
     b->calls = (HomoCall*)(m + o_calls); b->results = (HomoResult*)(m + o_res); b->state = m + o_state;
     b->sub_idx = (int*)(m + o_sub); b->Hc = (double*)(m + o_hc); b->valid = (int*)(m + o_valid); b->good = (int*)(m + o_good);
     b->scr = (float*)(m + o_scr); b->rec = (double*)(m + o_rec); b->draw_next = (unsigned*)(m + o_dn); b->draw_idx = (int*)(m + o_di); b->fin = (int*)(m + o_fin);
+    b->work = (int2*)(m + o_work); b->work_ctr = (unsigned*)(m + o_wctr);
     b->count = count; b->points = points; b->max_iters = max_iters;
     return MIS_OK;
 }
@@ -1800,28 +1876,35 @@ int homo_batch_run(MisContext* ctx, HomoBatch* b, double thresh, int max_iters, 
     auto tail_staged = [&](int part) { return (part == 1 || part == 3 || plain) ? 0 : 1; };
     auto tail_lds = [&](int part) { return tail_staged(part) ? TAIL_DYN_LDS : (size_t)0; };
     const int replay_part = run == HOMO_BOTH_PHASES ? 0 : 1;      // 1: replay only, the finishers' tails are left pending
+    // the solves and counts of the work list draw_kernel has just written (the replay launch behind them empties it again)
+    const int ncu = std::max(ctx->num_cu, 1);
+    auto hypotheses = [&]() {
+        hipLaunchKernelGGL(hyp_quad_kernel, dim3(HQ_WG_PER_CU * ncu), dim3(4 * HQ_HYPS), hq_lds, st, b->calls, states, b->sub_idx, b->Hc, b->valid, max_iters,
+                           (const int2*)b->work, b->work_ctr);
+        hipLaunchKernelGGL(hyp_count_kernel, dim3(HC_WG_PER_CU * ncu), dim3(256), 0, st, b->calls, states, (const double*)b->Hc, (const int*)b->valid, b->good,
+                           max_iters, thr, (const int2*)b->work, b->work_ctr);
+    };
     if (run == HOMO_BOTH_PHASES || run == HOMO_PHASE0_REPLAY) {
         MIS_HIP(ctx, hipMemsetAsync(b->fin, 0xff, sizeof(int) * (size_t)b->count, st));
-        hipLaunchKernelGGL(draw_kernel, dim3(b->count), dim3(DRAW_TB), 0, st, b->calls, states, b->sub_idx, b->draw_idx, rt.U, rt.state_T, max_iters, 0, p0);
+        hipLaunchKernelGGL(draw_kernel, dim3(b->count), dim3(DRAW_TB), 0, st, b->calls, states, b->sub_idx, b->draw_idx, rt.U, rt.state_T, max_iters, 0, p0, b->work,
+                           b->work_ctr);
         if (sy.rec && sy.rec_pos == 2) MIS_HIP(ctx, hipEventRecord(sy.rec, st));
-        hipLaunchKernelGGL(hyp_quad_kernel, dim3((p0 + HQ_HYPS - 1) / HQ_HYPS, b->count), dim3(4 * HQ_HYPS), hq_lds, st, b->calls, states, b->sub_idx, b->Hc, b->valid, 0, max_iters);
-        hipLaunchKernelGGL(hyp_count_kernel, dim3((p0 + 3) / 4, b->count), dim3(256), 0, st, b->calls, states, (const double*)b->Hc, (const int*)b->valid, b->good, 0, max_iters, thr);
+        hypotheses();
         hipLaunchKernelGGL(scan_tail_kernel, dim3(b->count), dim3(TB), tail_lds(replay_part), st, b->calls, states, b->Hc, b->valid, b->good, b->scr, b->rec, b->results, 0, p0,
-                           max_iters, confidence, thr, b->fin, replay_part, 0, tail_staged(replay_part));
+                           max_iters, confidence, thr, b->fin, replay_part, 0, tail_staged(replay_part), b->work_ctr);
     }
     if (run >= HOMO_TAIL0_MASK) {   // the problems a replay-only run left pending with fin == w
         const int want = (run - HOMO_TAIL0_MASK) >> 1, part = 3 + ((run - HOMO_TAIL0_MASK) & 1);
         hipLaunchKernelGGL(scan_tail_kernel, dim3(b->count), dim3(TB), tail_lds(part), st, b->calls, states, b->Hc, b->valid, b->good, b->scr, b->rec, b->results, 0, p0,
-                           max_iters, confidence, thr, b->fin, part, want, tail_staged(part));
+                           max_iters, confidence, thr, b->fin, part, want, tail_staged(part), nullptr);
     }
     if ((run == HOMO_BOTH_PHASES || run == HOMO_PHASE1_REPLAY) && max_iters > p0) {
-        hipLaunchKernelGGL(draw_kernel, dim3(b->count), dim3(DRAW_TB), 0, st, b->calls, states, b->sub_idx, b->draw_idx, rt.U, rt.state_T, max_iters, 1, max_iters);
+        hipLaunchKernelGGL(draw_kernel, dim3(b->count), dim3(DRAW_TB), 0, st, b->calls, states, b->sub_idx, b->draw_idx, rt.U, rt.state_T, max_iters, 1, max_iters,
+                           b->work, b->work_ctr);
         if (sy.rec && sy.rec_pos == 0) MIS_HIP(ctx, hipEventRecord(sy.rec, st));
-        hipLaunchKernelGGL(hyp_quad_kernel, dim3((max_iters - p0 + HQ_HYPS - 1) / HQ_HYPS, b->count), dim3(4 * HQ_HYPS), hq_lds, st, b->calls, states, b->sub_idx, b->Hc, b->valid, p0, max_iters);
-        hipLaunchKernelGGL(hyp_count_kernel, dim3((max_iters - p0 + 3) / 4, b->count), dim3(256), 0, st, b->calls, states, (const double*)b->Hc, (const int*)b->valid, b->good, p0,
-                           max_iters, thr);
+        hypotheses();
         hipLaunchKernelGGL(scan_tail_kernel, dim3(b->count), dim3(TB), tail_lds(replay_part), st, b->calls, states, b->Hc, b->valid, b->good, b->scr, b->rec, b->results, p0,
-                           max_iters, max_iters, confidence, thr, b->fin, replay_part, 0, tail_staged(replay_part));
+                           max_iters, max_iters, confidence, thr, b->fin, replay_part, 0, tail_staged(replay_part), b->work_ctr);
     }
     MIS_HIP(ctx, hipGetLastError());
     return MIS_OK;
