@@ -723,20 +723,28 @@ struct Arena {
     void release() { if (p) { if (host) hipHostFree(p); else hipFree(p); } p = nullptr; bytes = 0; }
 };
 
+// an event of the workspace: created on first use, destroyed with the workspace
+struct OwnedEvent {
+    hipEvent_t ev = nullptr;
+    OwnedEvent() = default; OwnedEvent(const OwnedEvent&) = delete;
+    ~OwnedEvent() { if (ev) hipEventDestroy(ev); }
+    hipError_t ready(unsigned flags = hipEventDisableTiming) { return ev ? hipSuccess : hipEventCreateWithFlags(&ev, flags); }
+};
+
 struct MatchWorkspace : MisWorkspace {
     Arena dev, pinned, l2;
     // b1: first estimation of every pair; b2 / b3: the inlier-only estimation of the pairs whose first one finished in
     // RANSAC phase 0 / phase 1.  b2 runs on `side` concurrently with phase 1 of b1 (the chains are latency bound).
     HomoBatch b1, b2, b3;
     hipStream_t side = nullptr, third = nullptr;
-    hipEvent_t ev_phase0 = nullptr, ev_side_done = nullptr, ev_phase1 = nullptr, ev_third_done = nullptr, ev_matches = nullptr;
+    OwnedEvent ev_phase0, ev_side_done, ev_phase1, ev_third_done, ev_matches;
     // "the 2-NN pass of matcher call number knn_seq has been enqueued, ev_knn marks its end" (mis_match_knn_fence)
-    hipEvent_t ev_knn = nullptr;
-    hipEvent_t ev_draw1 = nullptr;   // the side chain's first draw_kernel has run
-    hipEvent_t tev[8] = {nullptr};   // MIS_MATCH_TRACE: timing events (2-NN end, phase 0 end, main chain's second RANSAC phase end, main chain end, side end, third end, tails of phase 0 end, main chain's second draw end)
+    OwnedEvent ev_knn;
+    OwnedEvent ev_draw1;   // the side chain's first draw_kernel has run
+    OwnedEvent tev[8];     // MIS_MATCH_TRACE (trace_mark creates them): timing events (2-NN end, phase 0 end, main chain's second RANSAC phase end, main chain end, side end, third end, tails of phase 0 end, main chain's second draw end)
     hipEvent_t ev_gate = nullptr;    // what mis_match_knn_fence queues a stream behind: ev_knn, then ev_draw1 once the chains are enqueued
     std::atomic<long long> seq{0}, knn_seq{0};
-    hipEvent_t ev_lists = nullptr;                       // the early download of the match lists has landed
+    OwnedEvent ev_lists;                                 // the early download of the match lists has landed
     void (*enqueued_cb)(void*) = nullptr;                // mis_match_on_enqueued: one-shot hook of the next call
     void* enqueued_user = nullptr;
     MatchWorkspace() { pinned.host = true; }
@@ -744,14 +752,11 @@ struct MatchWorkspace : MisWorkspace {
         dev.release(); pinned.release(); l2.release();
         homo_batch_release(&b1); homo_batch_release(&b2); homo_batch_release(&b3);
         // side / third are the context's auxiliary streams: not owned here
-        if (ev_phase1) hipEventDestroy(ev_phase1);
-        if (ev_third_done) hipEventDestroy(ev_third_done);
-        if (ev_matches) hipEventDestroy(ev_matches);
-        if (ev_lists) hipEventDestroy(ev_lists);
-        if (ev_phase0) hipEventDestroy(ev_phase0);
-        if (ev_side_done) hipEventDestroy(ev_side_done);
-        if (ev_knn) hipEventDestroy(ev_knn);
-        if (ev_draw1) hipEventDestroy(ev_draw1);
+    }
+    hipError_t events_ready() {
+        for (OwnedEvent* e : {&ev_knn, &ev_matches, &ev_lists, &ev_phase0, &ev_draw1, &ev_side_done, &ev_phase1, &ev_third_done})
+            if (const hipError_t r = e->ready()) return r;
+        return hipSuccess;
     }
 };
 
@@ -761,13 +766,329 @@ MatchWorkspace* workspace(MisContext* ctx) {
 }
 
 struct Carver {
+    uintptr_t base = 0;   // at(): addresses in an arena at `base` (0: only the size is wanted)
     size_t off = 0;
     size_t take(size_t bytes) { size_t o = off; off += mis_align_up(bytes ? bytes : 1, 256); return o; }
+    void* at(size_t bytes) { return (void*)(base + take(bytes)); }
 };
 
-void init_info(MisMatchesInfo* m) {
-    memset(m, 0, sizeof(*m));
-    m->src_img_idx = -1; m->dst_img_idx = -1;
+void init_info(MisMatchesInfo* m) { memset(m, 0, sizeof(*m)); m->src_img_idx = -1; m->dst_img_idx = -1; }
+
+// MIS_MATCH_TRACE (read once): host time stamps of every matcher call, with device time stamps of its chains (trace_mark)
+bool match_trace() { static const bool on = getenv("MIS_MATCH_TRACE") != nullptr; return on; }
+void trace_mark(MatchWorkspace* ws, int i, hipStream_t s) {
+    if (match_trace() && ws->tev[i].ready(hipEventDefault) == hipSuccess) hipEventRecord(ws->tev[i].ev, s);
+}
+
+// K8 over directed pairs of the sets f[0 .. nsets): fp16 copies + squared norms of every set once (a device flag, copied to *bad_host,
+// marks values that are not SIFT-style integers), then one MFMA distance pass per pair i -> j (and j -> i when both_ways)
+int l2_knn2_pairs(MisContext* ctx, Arena& arena, const MisFeatures* f, int nsets, const PairDesc* pairs, int np, bool both_ways, int* idx2,
+                  float* dist2, int* bad_host) {
+    hipStream_t st = ctx->stream;
+    std::vector<size_t> off(nsets);
+    Carver lc;
+    int maxq = 0;
+    for (int s = 0; s < nsets; s++) {
+        off[s] = lc.take((size_t)std::max(f[s].n, 1) * (256 + 4));   // the rows (a multiple of 256 bytes), then the norms
+        maxq = std::max(maxq, f[s].n);
+    }
+    // o_part: the slice results of one directed pair (stream ordered reuse)
+    const size_t o_bad = lc.take(4), o_part = lc.take((size_t)16 * L2_MAX_SLICES * std::max(maxq, 1));
+    MIS_HIP(ctx, arena.reserve(lc.off));
+    uint8_t* L = (uint8_t*)arena.p;
+    auto set = [&](int s) { return L2Set{(const _Float16*)(L + off[s]), (const float*)(L + off[s] + (size_t)std::max(f[s].n, 1) * 256), std::max(f[s].n, 0)}; };
+    MIS_HIP(ctx, hipMemsetAsync(L + o_bad, 0, 4, st));
+    for (int s = 0; s < nsets; s++)
+        if (f[s].n > 0)
+            hipLaunchKernelGGL(l2_prep_kernel, dim3((f[s].n + 3) / 4), dim3(256), 0, st, (const float*)f[s].descriptors, f[s].n, f[s].desc_cols,
+                               (_Float16*)set(s).h, (float*)set(s).nrm, (int*)(L + o_bad));
+    for (const PairDesc* pd = pairs; pd < pairs + np; pd++) {
+        l2_knn2_launch(st, ctx->num_cu, set(pd->i), set(pd->j), L + o_part, idx2 + 2 * pd->knn_off12, dist2 + 2 * pd->knn_off12);
+        if (both_ways) l2_knn2_launch(st, ctx->num_cu, set(pd->j), set(pd->i), L + o_part, idx2 + 2 * pd->knn_off21, dist2 + 2 * pd->knn_off21);
+    }
+    MIS_HIP(ctx, hipMemcpyAsync(bad_host, L + o_bad, 4, hipMemcpyDeviceToHost, st));
+    return MIS_OK;
+}
+
+enum DescKind { DESC_NONE, DESC_BINARY, DESC_L2 };
+// What a matcher call does, decided on the host before anything is enqueued.  FeaturesMatcher::operator(): all i < j with
+// non-empty keypoint lists, dealt round-robin over ranks.
+struct MatchPlan {
+    std::vector<PairDesc> pairs;
+    std::vector<FeatDev> fd;               // one per frame
+    size_t knn_total = 0, m_total = 0;     // 2-NN queries of both directions of every pair; match capacity of every pair
+    int maxq = 0;                          // the largest keypoint count of a frame
+    DescKind kind = DESC_NONE;
+    std::vector<HmJob> hm_jobs;            // workgroup table of the Hamming pass on the matrix cores (binary, <= HM_MAX_TRAINS)
+};
+int plan_match(MisContext* ctx, const MisFeatures* feats, int n, int rank, int world, MatchPlan* pl) {
+    std::vector<PairDesc>& pairs = pl->pairs;
+    pl->fd.resize(n);
+    bool use_l2 = false, use_bin = false;
+    for (int i = 0; i < n; i++) {
+        const bool bin_i = feats[i].desc_dtype == MIS_U8 && feats[i].desc_cols == 32;
+        const bool l2_i = feats[i].desc_dtype == MIS_F32 && feats[i].desc_cols >= 1 && feats[i].desc_cols <= 128;
+        MIS_CHECK(ctx, feats[i].n == 0 || bin_i || l2_i, MIS_E_UNSUPPORTED,
+                  "all-pairs matching supports 32-byte binary descriptors (Hamming) or f32 descriptors of <= 128 columns (L2)");
+        MIS_CHECK(ctx, feats[i].n < (1 << 22), MIS_E_UNSUPPORTED, "more than 4 M keypoints in one image");   // index bits of the 2-NN keys
+        if (feats[i].n > 0) { if (l2_i) use_l2 = true; else use_bin = true; }
+        pl->fd[i] = FeatDev{(const uint8_t*)feats[i].descriptors, feats[i].keypoints, feats[i].n, feats[i].img_w, feats[i].img_h};
+        pl->maxq = std::max(pl->maxq, feats[i].n);
+    }
+    int pair_index = 0;
+    for (int i = 0; i < n; i++)
+        for (int j = i + 1; j < n; j++) {
+            if (feats[i].n <= 0 || feats[j].n <= 0) continue;
+            if ((pair_index++ % world) != rank) continue;
+            const int cap = feats[i].n + feats[j].n;
+            pairs.push_back(PairDesc{i, j, pl->knn_total, pl->knn_total + feats[i].n, pl->m_total, cap});
+            pl->knn_total += cap; pl->m_total += cap;
+        }
+    MIS_CHECK(ctx, !(use_l2 && use_bin), MIS_E_INVALID, "binary and float descriptors cannot be mixed in one matcher call");
+    // l2_prep_kernel zero-pads every frame to 128 columns: frames of different widths would be compared silently
+    // (cv::BFMatcher asserts on it, and mis_knn2 refuses it)
+    for (int i = 0, cols = 0; use_l2 && i < n; i++)
+        if (feats[i].n > 0) {
+            MIS_CHECK(ctx, cols == 0 || feats[i].desc_cols == cols, MIS_E_INVALID, "float descriptors of different widths in one matcher call");
+            cols = feats[i].desc_cols;
+        }
+    pl->kind = use_l2 ? DESC_L2 : (use_bin ? DESC_BINARY : DESC_NONE);
+    const int np = (int)pairs.size();
+    if (np == 0) return MIS_OK;
+    // workgroup table of the Hamming pass on the matrix cores (HmJob): eight lists by train frame mod 8, interleaved
+    if (pl->kind == DESC_BINARY && pl->maxq <= HM_MAX_TRAINS) {
+        std::vector<HmJob> lists[8];
+        for (int t = 0; t < n; t++)
+            for (int k = 0; k < np; k++) {
+                const int dir = pairs[k].j == t ? 0 : (pairs[k].i == t ? 1 : -1);      // direction 0: queries of i against the trains of j
+                if (dir < 0) continue;
+                const int nqf = feats[dir == 0 ? pairs[k].i : pairs[k].j].n;
+                for (int q0 = 0; q0 < nqf; q0 += 256) lists[t & 7].push_back(HmJob{k, dir, q0, 0});
+            }
+        size_t longest = 0;
+        for (auto& l : lists) longest = std::max(longest, l.size());
+        pl->hm_jobs.assign(longest * 8, HmJob{-1, 0, 0, 0});
+        for (int c = 0; c < 8; c++)
+            for (size_t sl = 0; sl < lists[c].size(); sl++) pl->hm_jobs[sl * 8 + c] = lists[c][sl];
+    }
+    return MIS_OK;
+}
+
+// The device arena of a matcher call: the inputs, the 2-NN of every query of both directions of every pair, the ratio test's
+// match lists and their centre-shifted points (pair k at m_off), the match counts, the inlier masks (at m_off), the PairOuts
+struct MatchDev { FeatDev* feats; PairDesc* pairs; int* idx; float* dist; MisDMatch* matches; float* src; float* dst; int* nm; uint8_t* mask; PairOut* out; };
+int carve_dev(MisContext* ctx, Arena& arena, const MatchPlan& pl, MatchDev* d) {
+    const size_t n = pl.fd.size(), np = pl.pairs.size(), kt = pl.knn_total, mt = pl.m_total;
+    auto lay = [&](Carver c) {      // once to size the arena, once more to place the regions in it
+        d->feats = (FeatDev*)c.at(sizeof(FeatDev) * n); d->pairs = (PairDesc*)c.at(sizeof(PairDesc) * np);
+        d->idx = (int*)c.at(sizeof(int) * 2 * kt); d->dist = (float*)c.at(sizeof(float) * 2 * kt);
+        d->matches = (MisDMatch*)c.at(sizeof(MisDMatch) * mt); d->src = (float*)c.at(sizeof(float) * 2 * mt); d->dst = (float*)c.at(sizeof(float) * 2 * mt);
+        d->nm = (int*)c.at(sizeof(int) * np); d->mask = (uint8_t*)c.at(mt); d->out = (PairOut*)c.at(sizeof(PairOut) * np);
+        return c.off;
+    };
+    MIS_HIP(ctx, arena.reserve(lay(Carver{})));
+    lay(Carver{(uintptr_t)arena.p});
+    return MIS_OK;
+}
+
+// The pinned host arena of a matcher call: the inputs of the 2-NN pass on their way to the device (frames, jobs: the Hamming
+// pass on the matrix cores), everything that comes back (r1 / r2 / r3: b1 / b2 / b3; m: the packed match lists), and the flag of
+// the L2 path (non-integer descriptors: here, an early return never leaves a copy aimed at a stack frame)
+struct MatchPinned {
+    FeatDev* feats; PairDesc* pairs; HmFrame* frames; HmJob* jobs;
+    int* nm; PairOut* out; HomoResult *r1, *r2, *r3; int* fin; MisDMatch* m; uint8_t* mask; volatile int* l2_bad;
+};
+int carve_pinned(MisContext* ctx, Arena& arena, const MatchPlan& pl, MatchPinned* h) {
+    const size_t n = pl.fd.size(), np = pl.pairs.size(), mt = pl.m_total;
+    auto lay = [&](Carver c) {
+        h->feats = (FeatDev*)c.at(sizeof(FeatDev) * n); h->pairs = (PairDesc*)c.at(sizeof(PairDesc) * np); h->frames = (HmFrame*)c.at(sizeof(HmFrame) * n);
+        h->jobs = (HmJob*)c.at(sizeof(HmJob) * pl.hm_jobs.size()); h->nm = (int*)c.at(sizeof(int) * np); h->out = (PairOut*)c.at(sizeof(PairOut) * np);
+        h->r1 = (HomoResult*)c.at(sizeof(HomoResult) * np); h->r2 = (HomoResult*)c.at(sizeof(HomoResult) * np); h->r3 = (HomoResult*)c.at(sizeof(HomoResult) * np);
+        h->fin = (int*)c.at(sizeof(int) * np); h->m = (MisDMatch*)c.at(sizeof(MisDMatch) * mt); h->mask = (uint8_t*)c.at(mt); h->l2_bad = (volatile int*)c.at(sizeof(int));
+        return c.off;
+    };
+    MIS_HIP(ctx, arena.reserve(lay(Carver{})));
+    lay(Carver{(uintptr_t)arena.p});
+    return MIS_OK;
+}
+
+// The 2-NN pass of every directed pair: K8 for float descriptors; for binary ones the vector-pipe kernel when a train set is
+// beyond the key's 13 index bits (also what mis_knn2 runs), else every frame's descriptors once as fp4 nibbles (train form and
+// query form), then all directed pairs in one MFMA launch
+int enqueue_knn(MisContext* ctx, MatchWorkspace* ws, const MatchPlan& pl, const MisFeatures* feats, const MatchDev& d, const MatchPinned& h) {
+    hipStream_t st = ctx->stream;
+    const int n = (int)pl.fd.size(), np = (int)pl.pairs.size();
+    if (pl.kind == DESC_L2) return l2_knn2_pairs(ctx, ws->l2, feats, n, pl.pairs.data(), np, true, d.idx, d.dist, (int*)h.l2_bad);
+    if (pl.maxq > HM_MAX_TRAINS) {
+        hipLaunchKernelGGL(knn2_hamming_kernel, dim3((pl.maxq + 255) / 256, 2 * np), dim3(256), 0, st, (const FeatDev*)d.feats, (const PairDesc*)d.pairs, d.idx, d.dist);
+        return MIS_OK;
+    }
+    Carver lc;
+    const size_t o_fr = lc.take(sizeof(HmFrame) * n), o_jobs = lc.take(sizeof(HmJob) * pl.hm_jobs.size());
+    for (int i = 0; i < n; i++) {
+        const size_t rows = (size_t)(std::max(feats[i].n, 1) + HM_ROWPAD - 1) / HM_ROWPAD * HM_ROWPAD;
+        h.frames[i].train_off = lc.take(rows * 128); h.frames[i].query_off = lc.take(rows * 128);
+    }
+    MIS_HIP(ctx, ws->l2.reserve(lc.off));
+    uint8_t* L = (uint8_t*)ws->l2.p;
+    MIS_HIP(ctx, hipMemcpyAsync(L + o_fr, h.frames, sizeof(HmFrame) * n, hipMemcpyHostToDevice, st));
+    const int maxpad = (pl.maxq + HM_ROWPAD - 1) / HM_ROWPAD * HM_ROWPAD;
+    hipLaunchKernelGGL(hamming_expand4_kernel, dim3(maxpad * 8 / 256, n), dim3(256), 0, st, (const FeatDev*)d.feats, (const HmFrame*)(L + o_fr), (int8_t*)L);
+    memcpy(h.jobs, pl.hm_jobs.data(), sizeof(HmJob) * pl.hm_jobs.size());
+    MIS_HIP(ctx, hipMemcpyAsync(L + o_jobs, h.jobs, sizeof(HmJob) * pl.hm_jobs.size(), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(knn2_hamming_fp4_kernel, dim3((unsigned)pl.hm_jobs.size()), dim3(256), 0, st, (const FeatDev*)d.feats, (const PairDesc*)d.pairs,
+                       (const HmFrame*)(L + o_fr), (const int8_t*)L, d.idx, d.dist, (const HmJob*)(L + o_jobs));
+    return MIS_OK;
+}
+
+// Three chains behind the ratio test: findHomography returns the RANSAC mask, not one recomputed after its refinement, so the
+// second estimation starts from the mask while the DLT + LM refinement of the first H runs on a third stream; the |det H| test of
+// the reference moves to the host assembly.  Side and third are the context's two auxiliary streams -- the streams the ORB batch's
+// helper lanes ran on a moment ago -- so that the job keeps to four streams (an earlier version created two more here, one in
+// a priority class of its own to dodge a shared hardware queue: the step then moved by 25 % with GPU_MAX_HW_QUEUES).
+int enqueue_chains(MisContext* ctx, MatchWorkspace* ws, int np, const MisMatchParams* p, const MatchDev& d, const MatchPinned& h) {
+    hipStream_t st = ctx->stream;
+    int rc;
+    if (!ws->side && (rc = mis_aux_stream(ctx, 0, &ws->side)) != MIS_OK) return rc;
+    trace_mark(ws, 0, st);
+    if (!ws->third && (rc = mis_aux_stream(ctx, 1, &ws->third)) != MIS_OK) return rc;
+    auto run = [&](HomoBatch* b, HomoRun what, hipStream_t s, const HomoSync* sy = nullptr) { return homo_batch_run(ctx, b, p->ransac_thresh, p->max_iters, p->confidence, what, s, sy); };
+    // the match lists are final once the ratio test has run: their download (megabytes) goes to the third stream now, under the
+    // RANSAC chains, instead of behind them (0.3 ms at the end of the call); pair k's matches land at the sum of the counts before it
+    MIS_HIP(ctx, hipEventRecord(ws->ev_matches.ev, st));
+    MIS_HIP(ctx, hipStreamWaitEvent(ws->third, ws->ev_matches.ev, 0));
+    hipLaunchKernelGGL(pack_lists_kernel, dim3(np), dim3(256), 0, ws->third, (const PairDesc*)d.pairs, np, (const int*)d.nm, (const MisDMatch*)d.matches, h.m, h.nm);
+    MIS_HIP(ctx, hipEventRecord(ws->ev_lists.ev, ws->third));
+    // main chain: first estimation of every pair, RANSAC phase 0 and the inlier masks of the pairs that finish there
+    if ((rc = run(&ws->b1, HOMO_PHASE0_REPLAY, st)) != MIS_OK || (rc = run(&ws->b1, HOMO_TAIL0_MASK, st)) != MIS_OK) return rc;
+    MIS_HIP(ctx, hipEventRecord(ws->ev_phase0.ev, st));
+    trace_mark(ws, 1, st);
+    // side chain: the inlier-only estimation of those pairs
+    MIS_HIP(ctx, hipStreamWaitEvent(ws->side, ws->ev_phase0.ev, 0));
+    hipLaunchKernelGGL(second_calls_kernel, dim3((np + 127) / 128), dim3(128), 0, ws->side, np, (const HomoCall*)ws->b1.calls, (const HomoResult*)ws->b1.results,
+                       (const float*)ws->b1.scr, (const int*)ws->b1.fin, 0, p->num_matches_thresh2, ws->b2.calls, d.out);
+    // the compose gate: behind the side chain's first draw, 0.05 - 0.1 ms behind the first phase -- the tails and that draw
+    // hold their compute units by then
+    HomoSync gate;
+    gate.rec = ws->ev_draw1.ev; gate.rec_pos = 2; ws->ev_gate = ws->ev_draw1.ev;
+    if ((rc = run(&ws->b2, HOMO_BOTH_PHASES, ws->side, &gate)) != MIS_OK) return rc;
+    MIS_HIP(ctx, hipEventRecord(ws->ev_side_done.ev, ws->side));
+    trace_mark(ws, 4, ws->side);
+    // third chain: DLT + LM refinement of the first H of the pairs that finished in phase 0
+    MIS_HIP(ctx, hipStreamWaitEvent(ws->third, ws->ev_phase0.ev, 0));
+    if ((rc = run(&ws->b1, HOMO_TAIL0_REFINE, ws->third)) != MIS_OK) return rc;
+    trace_mark(ws, 6, ws->third);
+    // main chain: RANSAC phase 1 of the others
+    HomoSync draw2;      // diagnostics: the end of the main chain's second draw
+    if (match_trace() && ws->tev[7].ready(hipEventDefault) == hipSuccess) draw2.rec = ws->tev[7].ev;
+    if ((rc = run(&ws->b1, HOMO_PHASE1_REPLAY, st, &draw2)) != MIS_OK || (rc = run(&ws->b1, HOMO_TAIL1_MASK, st)) != MIS_OK) return rc;
+    MIS_HIP(ctx, hipEventRecord(ws->ev_phase1.ev, st));
+    trace_mark(ws, 2, st);
+    // the refinement of the phase-1 finishers' first H stays on this stream (1.7 ms of latency-bound work: behind the 2 ms
+    // refinement of the phase-0 finishers on the third stream it ended the matcher 0.6 ms later); their inlier-only second
+    // estimation goes to the third stream instead
+    if ((rc = run(&ws->b1, HOMO_TAIL1_REFINE, st)) != MIS_OK) return rc;
+    trace_mark(ws, 3, st);
+    MIS_HIP(ctx, hipStreamWaitEvent(ws->third, ws->ev_phase1.ev, 0));
+    hipLaunchKernelGGL(second_calls_kernel, dim3((np + 127) / 128), dim3(128), 0, ws->third, np, (const HomoCall*)ws->b1.calls, (const HomoResult*)ws->b1.results,
+                       (const float*)ws->b1.scr, (const int*)ws->b1.fin, 1, p->num_matches_thresh2, ws->b3.calls, d.out);
+    if ((rc = run(&ws->b3, HOMO_BOTH_PHASES, ws->third)) != MIS_OK) return rc;
+    MIS_HIP(ctx, hipEventRecord(ws->ev_third_done.ev, ws->third));
+    trace_mark(ws, 5, ws->third);
+    MIS_HIP(ctx, hipStreamWaitEvent(st, ws->ev_third_done.ev, 0));
+    MIS_HIP(ctx, hipStreamWaitEvent(st, ws->ev_side_done.ev, 0));
+    return MIS_OK;
+}
+
+// the small per-pair results into the pinned staging, behind the chains
+void enqueue_results(MatchWorkspace* ws, int np, size_t m_total, const MatchDev& d, const MatchPinned& h, hipStream_t st) {
+    CopySegs cs{};
+    const void* srcs[6] = {d.out, ws->b1.results, ws->b2.results, ws->b3.results, ws->b1.fin, d.mask};
+    void* dsts[6] = {h.out, h.r1, h.r2, h.r3, h.fin, h.mask};
+    const size_t sizes[6] = {sizeof(PairOut) * np, sizeof(HomoResult) * np, sizeof(HomoResult) * np, sizeof(HomoResult) * np, sizeof(int) * np, m_total};
+    cs.n = 6;
+    for (int k = 0; k < 6; k++) { cs.src[k] = (const uint8_t*)srcs[k]; cs.dst[k] = (uint8_t*)dsts[k]; cs.bytes[k] = (unsigned)sizes[k]; }
+    hipLaunchKernelGGL(copy_segments_kernel, dim3(64), dim3(256), 0, st, cs);
+}
+
+// MatchesInfo (host), part 1 under the RANSAC chains: the match lists (packed by pack_lists_kernel) and their mirrors; part 2
+// once the device is done (*ts: then): masks, H, confidence, the mirror entry with H^-1 and swapped indices
+int assemble_matches(MisContext* ctx, MatchWorkspace* ws, const MatchPlan& pl, const MatchPinned& h, int n, MisMatchesInfo* out,
+                     std::chrono::steady_clock::time_point* ts) {
+    const int np = (int)pl.pairs.size();
+    // an error after the lists exist must not leave half-built entries behind: `out` goes back to its zeroed state
+    auto drop_lists = [&]() {
+        for (const PairDesc& pd : pl.pairs)
+            for (MisMatchesInfo* m : {&out[pd.i * n + pd.j], &out[pd.j * n + pd.i]}) { free(m->matches); free(m->inliers_mask); init_info(m); }
+    };
+    MIS_HIP(ctx, hipEventSynchronize(ws->ev_lists.ev));
+    size_t packed_off = 0;
+    for (int k = 0; k < np; k++) {
+        const PairDesc& pd = pl.pairs[k];
+        MisMatchesInfo *a = &out[pd.i * n + pd.j], *b = &out[pd.j * n + pd.i];
+        const int nm = h.nm[k];
+        a->src_img_idx = pd.i; a->dst_img_idx = pd.j;
+        a->n_matches = nm;
+        a->matches = (MisDMatch*)malloc(sizeof(MisDMatch) * (size_t)(nm + 1));
+        memcpy(a->matches, h.m + packed_off, sizeof(MisDMatch) * (size_t)nm);
+        packed_off += (size_t)nm;
+        b->matches = (MisDMatch*)malloc(sizeof(MisDMatch) * (size_t)(nm + 1));
+        for (int q = 0; q < nm; q++) { b->matches[q] = a->matches[q]; std::swap(b->matches[q].query_idx, b->matches[q].train_idx); }
+    }
+    const hipError_t e = hipStreamSynchronize(ctx->stream);
+    *ts = std::chrono::steady_clock::now();
+    if (e != hipSuccess || *h.l2_bad) {
+        drop_lists();
+        if (e != hipSuccess) return mis_set_error(ctx, MIS_E_HIP, "hipStreamSynchronize failed: %s (%s:%d)", hipGetErrorString(e), __FILE__, __LINE__);
+        return mis_set_error(ctx, MIS_E_UNSUPPORTED, "L2 matching needs integer-valued descriptors in 0..255 (SIFT style)");
+    }
+    for (int k = 0; k < np; k++) {
+        const PairDesc& pd = pl.pairs[k];
+        const PairOut& po = h.out[k];
+        const int nm = h.nm[k];
+        MisMatchesInfo *a = &out[pd.i * n + pd.j], *b = &out[pd.j * n + pd.i];
+        MisDMatch* bm = b->matches;
+        if (po.ran_ransac) {
+            a->inliers_mask = (uint8_t*)malloc((size_t)nm + 1);
+            memcpy(a->inliers_mask, h.mask + pd.m_off, (size_t)nm);
+        }
+        // matchers.cpp: "if (H.empty() || |det H| < eps) return" after the first estimation.  The second estimation runs
+        // without waiting for the refined H, and a degenerate first H drops it here (same expression, same rounding: no FMA contraction)
+        const bool det_ok = !(fabs(det3(h.r1[k].H)) < DBL_EPSILON);
+        const bool passed = po.passed && det_ok, second = po.second && det_ok;
+        // H of the inlier-only estimation when it ran (it may come back empty), else of the first one
+        const HomoResult& hr = second ? (h.fin[k] == 0 ? h.r2[k] : h.r3[k]) : h.r1[k];
+        a->has_H = po.ran_ransac ? hr.ok : 0;
+        if (a->has_H) memcpy(a->H, hr.H, sizeof(a->H));
+        a->num_inliers = passed ? h.r1[k].ninl : 0;
+        if (passed) {
+            // Brown & Lowe confidence; > 3 means near-duplicate images and is zeroed (matchers.cpp)
+            double c = a->num_inliers / (8 + 0.3 * nm);
+            a->confidence = c > 3. ? 0. : c;
+        }
+        *b = *a;
+        b->src_img_idx = pd.j; b->dst_img_idx = pd.i;
+        b->matches = bm;
+        if (a->inliers_mask) {
+            b->inliers_mask = (uint8_t*)malloc((size_t)nm + 1);
+            memcpy(b->inliers_mask, a->inliers_mask, (size_t)nm);
+        }
+        if (a->has_H) invert3(a->H, b->H);
+    }
+    return MIS_OK;
+}
+
+void trace_report(MatchWorkspace* ws, std::chrono::steady_clock::time_point t_begin, std::chrono::steady_clock::time_point tq,
+                  std::chrono::steady_clock::time_point ts) {
+    const auto te = std::chrono::steady_clock::now();
+    auto us = [](auto a, auto b) { return (double)std::chrono::duration_cast<std::chrono::microseconds>(b - a).count(); };
+    fprintf(stderr, "match: enqueue %.0f us, device wait %.0f us, host assembly %.0f us\n", us(t_begin, tq), us(tq, ts), us(ts, te));
+    const OwnedEvent* t = ws->tev;
+    auto ms = [&](int i) { float e = 0; if (t[i].ev) hipEventElapsedTime(&e, t[0].ev, t[i].ev); return e; };
+    if (!(t[0].ev && t[1].ev && t[3].ev && t[4].ev && t[5].ev && t[6].ev)) return;
+    if (t[7].ev) fprintf(stderr, "match chains: main chain's second draw done %.2f\n", ms(7));
+    fprintf(stderr, "match chains, ms after the 2-NN pass was enqueued-behind (device events): first phase done %.2f | tails of its finishers done %.2f | main chain: second RANSAC phase done %.2f, done %.2f | side chain done %.2f | third chain done %.2f\n",
+            ms(1), ms(6), ms(2), ms(3), ms(4), ms(5));
 }
 
 int match_impl(MisContext* ctx, const MisFeatures* feats, int n, const MisMatchParams* p, int rank, int world, MisMatchesInfo* out) {
@@ -782,257 +1103,44 @@ int match_impl(MisContext* ctx, const MisFeatures* feats, int n, const MisMatchP
     } seq_guard{workspace(ctx), 0};
     seq_guard.seq = ++seq_guard.ws->seq;
     for (int i = 0; i < n * n; i++) init_info(&out[i]);
-    // FeaturesMatcher::operator(): all i < j with non-empty keypoint lists, dealt round-robin over ranks
-    std::vector<PairDesc> pairs;
-    std::vector<FeatDev> fd(n);
-    size_t knn_total = 0, m_total = 0;
-    bool use_l2 = false, use_bin = false;
-    for (int i = 0; i < n; i++) {
-        const bool bin_i = feats[i].desc_dtype == MIS_U8 && feats[i].desc_cols == 32;
-        const bool l2_i = feats[i].desc_dtype == MIS_F32 && feats[i].desc_cols >= 1 && feats[i].desc_cols <= 128;
-        MIS_CHECK(ctx, feats[i].n == 0 || bin_i || l2_i, MIS_E_UNSUPPORTED,
-                  "all-pairs matching supports 32-byte binary descriptors (Hamming) or f32 descriptors of <= 128 columns (L2)");
-        MIS_CHECK(ctx, feats[i].n < (1 << 22), MIS_E_UNSUPPORTED, "more than 4 M keypoints in one image");   // index bits of the 2-NN keys
-        if (feats[i].n > 0) { if (l2_i) use_l2 = true; else use_bin = true; }
-        fd[i] = FeatDev{(const uint8_t*)feats[i].descriptors, feats[i].keypoints, feats[i].n, feats[i].img_w, feats[i].img_h};
-    }
-    int pair_index = 0;
-    for (int i = 0; i < n; i++)
-        for (int j = i + 1; j < n; j++) {
-            if (feats[i].n <= 0 || feats[j].n <= 0) continue;
-            if ((pair_index++ % world) != rank) continue;
-            PairDesc pd;
-            pd.i = i; pd.j = j;
-            pd.knn_off12 = knn_total; knn_total += feats[i].n;
-            pd.knn_off21 = knn_total; knn_total += feats[j].n;
-            pd.m_off = m_total; pd.cap = feats[i].n + feats[j].n; m_total += pd.cap;
-            pairs.push_back(pd);
-        }
-    MIS_CHECK(ctx, !(use_l2 && use_bin), MIS_E_INVALID, "binary and float descriptors cannot be mixed in one matcher call");
-    // l2_prep_kernel zero-pads every frame to 128 columns: frames of different widths would be compared silently
-    // (cv::BFMatcher asserts on it, and mis_knn2 refuses it)
-    for (int i = 0, cols = 0; use_l2 && i < n; i++)
-        if (feats[i].n > 0) {
-            MIS_CHECK(ctx, cols == 0 || feats[i].desc_cols == cols, MIS_E_INVALID, "float descriptors of different widths in one matcher call");
-            cols = feats[i].desc_cols;
-        }
-    const int np = (int)pairs.size();
+    MatchPlan pl;
+    int rc;
+    if ((rc = plan_match(ctx, feats, n, rank, world, &pl)) != MIS_OK) return rc;
+    const int np = (int)pl.pairs.size();
     if (np == 0) return MIS_OK;
-    int maxq = 0;
-    for (int i = 0; i < n; i++) maxq = std::max(maxq, feats[i].n);
-    // workgroup table of the Hamming pass on the matrix cores (HmJob): eight lists by train frame mod 8, interleaved
-    std::vector<HmJob> hm_jobs;
-    if (!use_l2 && maxq <= HM_MAX_TRAINS) {
-        std::vector<HmJob> lists[8];
-        for (int t = 0; t < n; t++)
-            for (int k = 0; k < np; k++) {
-                const int dir = pairs[k].j == t ? 0 : (pairs[k].i == t ? 1 : -1);      // direction 0: queries of i against the trains of j
-                if (dir < 0) continue;
-                const int nqf = feats[dir == 0 ? pairs[k].i : pairs[k].j].n;
-                for (int q0 = 0; q0 < nqf; q0 += 256) lists[t & 7].push_back(HmJob{k, dir, q0, 0});
-            }
-        size_t longest = 0;
-        for (auto& l : lists) longest = std::max(longest, l.size());
-        hm_jobs.assign(longest * 8, HmJob{-1, 0, 0, 0});
-        for (int c = 0; c < 8; c++)
-            for (size_t sl = 0; sl < lists[c].size(); sl++) hm_jobs[sl * 8 + c] = lists[c][sl];
-    }
     MatchWorkspace* ws = workspace(ctx);
     hipStream_t st = ctx->stream;
     MIS_HIP(ctx, hipStreamSynchronize(st));  // the arenas may still be read by a previous call's copies
-    Carver dc;
-    const size_t o_feats = dc.take(sizeof(FeatDev) * n), o_pairs = dc.take(sizeof(PairDesc) * np), o_idx = dc.take(sizeof(int) * 2 * knn_total),
-                 o_dist = dc.take(sizeof(int) * 2 * knn_total), o_matches = dc.take(sizeof(MisDMatch) * m_total), o_src = dc.take(sizeof(float) * 2 * m_total),
-                 o_dst = dc.take(sizeof(float) * 2 * m_total), o_nm = dc.take(sizeof(int) * np), o_mask = dc.take(m_total), o_out = dc.take(sizeof(PairOut) * np);
-    MIS_HIP(ctx, ws->dev.reserve(dc.off));
-    uint8_t* D = (uint8_t*)ws->dev.p;
-    FeatDev* d_feats = (FeatDev*)(D + o_feats); PairDesc* d_pairs = (PairDesc*)(D + o_pairs);
-    int* d_idx = (int*)(D + o_idx); float* d_dist = (float*)(D + o_dist);
-    MisDMatch* d_matches = (MisDMatch*)(D + o_matches); float* d_src = (float*)(D + o_src); float* d_dst = (float*)(D + o_dst);
-    int* d_nm = (int*)(D + o_nm); uint8_t* d_mask = D + o_mask; PairOut* d_out = (PairOut*)(D + o_out);
-    int rc;
-    if ((rc = homo_batch_reserve(ctx, &ws->b1, np, (long long)m_total, p->max_iters)) != MIS_OK) return rc;
-    if ((rc = homo_batch_reserve(ctx, &ws->b2, np, (long long)m_total, p->max_iters)) != MIS_OK) return rc;
-    if ((rc = homo_batch_reserve(ctx, &ws->b3, np, (long long)m_total, p->max_iters)) != MIS_OK) return rc;
-    // pinned host mirror of everything that comes back
-    Carver hc;
-    const size_t h_in = hc.take(sizeof(FeatDev) * n + sizeof(PairDesc) * np + sizeof(HmFrame) * n + 1024), h_nm = hc.take(sizeof(int) * np), h_out = hc.take(sizeof(PairOut) * np),
-                 h_r1 = hc.take(sizeof(HomoResult) * np), h_r2 = hc.take(sizeof(HomoResult) * np), h_r3 = hc.take(sizeof(HomoResult) * np), h_fin = hc.take(sizeof(int) * np), h_m = hc.take(sizeof(MisDMatch) * m_total), h_mask = hc.take(m_total), h_bad = hc.take(256), h_jobs = hc.take(sizeof(HmJob) * std::max<size_t>(hm_jobs.size(), 1));
-    MIS_HIP(ctx, ws->pinned.reserve(hc.off));
-    uint8_t* Hh = (uint8_t*)ws->pinned.p;
-    memcpy(Hh + h_in, fd.data(), sizeof(FeatDev) * n);
-    PairDesc* h_pairs = (PairDesc*)(Hh + h_in + mis_align_up(sizeof(FeatDev) * n, 256));
-    memcpy(h_pairs, pairs.data(), sizeof(PairDesc) * np);
-    MIS_HIP(ctx, hipMemcpyAsync(d_feats, Hh + h_in, sizeof(FeatDev) * n, hipMemcpyHostToDevice, st));
-    MIS_HIP(ctx, hipMemcpyAsync(d_pairs, h_pairs, sizeof(PairDesc) * np, hipMemcpyHostToDevice, st));
-    // flag of the L2 path (non-integer descriptors), copied into the pinned arena: an early return never leaves a copy aimed at this frame
-    volatile int& l2_bad = *reinterpret_cast<volatile int*>(Hh + h_bad);
-    l2_bad = 0;
-    if (!use_l2 && maxq > HM_MAX_TRAINS) {
-        // train sets beyond the key's 13 index bits: the vector-pipe kernel (also what mis_knn2 runs)
-        hipLaunchKernelGGL(knn2_hamming_kernel, dim3((maxq + 255) / 256, 2 * np), dim3(256), 0, st, (const FeatDev*)d_feats, (const PairDesc*)d_pairs, d_idx, d_dist);
-    } else if (!use_l2 && !hm_jobs.empty()) {
-        // every frame's descriptors once as fp4 nibbles (train form and query form), then all directed pairs in one MFMA launch
-        std::vector<HmFrame> hf(n);
-        Carver lc;
-        const size_t o_fr = lc.take(sizeof(HmFrame) * n), o_jobs = lc.take(sizeof(HmJob) * hm_jobs.size());
-        for (int i = 0; i < n; i++) {
-            const size_t rows = (size_t)(std::max(feats[i].n, 1) + HM_ROWPAD - 1) / HM_ROWPAD * HM_ROWPAD;
-            hf[i].train_off = lc.take(rows * 128); hf[i].query_off = lc.take(rows * 128);
-        }
-        MIS_HIP(ctx, ws->l2.reserve(lc.off));
-        uint8_t* L = (uint8_t*)ws->l2.p;
-        HmFrame* h_fr = (HmFrame*)(Hh + h_in + mis_align_up(sizeof(FeatDev) * n, 256) + mis_align_up(sizeof(PairDesc) * np, 256));
-        memcpy(h_fr, hf.data(), sizeof(HmFrame) * n);
-        MIS_HIP(ctx, hipMemcpyAsync(L + o_fr, h_fr, sizeof(HmFrame) * n, hipMemcpyHostToDevice, st));
-        const int maxpad = (maxq + HM_ROWPAD - 1) / HM_ROWPAD * HM_ROWPAD;
-        hipLaunchKernelGGL(hamming_expand4_kernel, dim3(maxpad * 8 / 256, n), dim3(256), 0, st, (const FeatDev*)d_feats, (const HmFrame*)(L + o_fr), (int8_t*)L);
-        memcpy(Hh + h_jobs, hm_jobs.data(), sizeof(HmJob) * hm_jobs.size());
-        MIS_HIP(ctx, hipMemcpyAsync(L + o_jobs, Hh + h_jobs, sizeof(HmJob) * hm_jobs.size(), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(knn2_hamming_fp4_kernel, dim3((unsigned)hm_jobs.size()), dim3(256), 0, st, (const FeatDev*)d_feats, (const PairDesc*)d_pairs,
-                           (const HmFrame*)(L + o_fr), (const int8_t*)L, d_idx, d_dist, (const HmJob*)(L + o_jobs));
-    } else if (!use_l2) {
-        // no query anywhere (every frame without features): nothing to search, the lists stay empty
-    } else {
-        // fp16 copies + squared norms of every image once, then one MFMA distance pass per directed pair
-        std::vector<size_t> hoff(n), noff(n);
-        Carver lc;
-        for (int i = 0; i < n; i++) { hoff[i] = lc.take((size_t)std::max(feats[i].n, 1) * 256); noff[i] = lc.take((size_t)std::max(feats[i].n, 1) * 4); }
-        const size_t o_bad = lc.take(4);
-        const size_t o_part = lc.take((size_t)16 * L2_MAX_SLICES * std::max(maxq, 1));   // slice results of one directed pair (stream ordered reuse)
-        MIS_HIP(ctx, ws->l2.reserve(lc.off));
-        uint8_t* L = (uint8_t*)ws->l2.p;
-        MIS_HIP(ctx, hipMemsetAsync(L + o_bad, 0, 4, st));
-        for (int i = 0; i < n; i++)
-            if (feats[i].n > 0)
-                hipLaunchKernelGGL(l2_prep_kernel, dim3((feats[i].n + 3) / 4), dim3(256), 0, st, (const float*)feats[i].descriptors, feats[i].n,
-                                   feats[i].desc_cols, (_Float16*)(L + hoff[i]), (float*)(L + noff[i]), (int*)(L + o_bad));
-        for (const PairDesc& pd : pairs) {
-            L2Set A{(const _Float16*)(L + hoff[pd.i]), (const float*)(L + noff[pd.i]), feats[pd.i].n}, B{(const _Float16*)(L + hoff[pd.j]), (const float*)(L + noff[pd.j]), feats[pd.j].n};
-            l2_knn2_launch(st, ctx->num_cu, A, B, L + o_part, d_idx + 2 * pd.knn_off12, d_dist + 2 * pd.knn_off12);
-            l2_knn2_launch(st, ctx->num_cu, B, A, L + o_part, d_idx + 2 * pd.knn_off21, d_dist + 2 * pd.knn_off21);
-        }
-        MIS_HIP(ctx, hipMemcpyAsync(Hh + h_bad, L + o_bad, 4, hipMemcpyDeviceToHost, st));
-    }
+    MatchDev d; MatchPinned h;
+    if ((rc = carve_dev(ctx, ws->dev, pl, &d)) != MIS_OK) return rc;
+    for (HomoBatch* b : {&ws->b1, &ws->b2, &ws->b3})
+        if ((rc = homo_batch_reserve(ctx, b, np, (long long)pl.m_total, p->max_iters)) != MIS_OK) return rc;
+    if ((rc = carve_pinned(ctx, ws->pinned, pl, &h)) != MIS_OK) return rc;
+    memcpy(h.feats, pl.fd.data(), sizeof(FeatDev) * n);
+    memcpy(h.pairs, pl.pairs.data(), sizeof(PairDesc) * np);
+    MIS_HIP(ctx, hipMemcpyAsync(d.feats, h.feats, sizeof(FeatDev) * n, hipMemcpyHostToDevice, st));
+    MIS_HIP(ctx, hipMemcpyAsync(d.pairs, h.pairs, sizeof(PairDesc) * np, hipMemcpyHostToDevice, st));
+    *h.l2_bad = 0;
+    if ((rc = enqueue_knn(ctx, ws, pl, feats, d, h)) != MIS_OK) return rc;
+    MIS_HIP(ctx, ws->events_ready());
     // the 2-NN pass fills the device on its own; what follows are latency-bound chains.  Work that wants to share the
     // device with the matcher (the job's speculative composition) can queue behind this event: mis_match_knn_fence
-    if (!ws->ev_knn) MIS_HIP(ctx, hipEventCreateWithFlags(&ws->ev_knn, hipEventDisableTiming));
-    MIS_HIP(ctx, hipEventRecord(ws->ev_knn, st));
-    ws->ev_gate = ws->ev_knn;
-    hipLaunchKernelGGL(ratio_union_kernel, dim3(np), dim3(1024), 0, st, (const FeatDev*)d_feats, (const PairDesc*)d_pairs, (const int*)d_idx,
-                       (const float*)d_dist, 1.f - p->match_conf, d_matches, d_src, d_dst, d_nm);
-    hipLaunchKernelGGL(first_calls_kernel, dim3((np + 127) / 128), dim3(128), 0, st, (const PairDesc*)d_pairs, np, (const int*)d_nm, (const float*)d_src,
-                       (const float*)d_dst, d_mask, p->num_matches_thresh1, ws->b1.calls, d_out);
-    if (!ws->side) {
-        if ((rc = mis_aux_stream(ctx, 0, &ws->side)) != MIS_OK) return rc;
-        MIS_HIP(ctx, hipEventCreateWithFlags(&ws->ev_phase0, hipEventDisableTiming));
-        MIS_HIP(ctx, hipEventCreateWithFlags(&ws->ev_side_done, hipEventDisableTiming));
-    }
-    const double rt = p->ransac_thresh, cf = p->confidence;
-    // everything between the forks to the auxiliary streams and their joins runs inside one scope: an error in there must not
-    // leave those streams with work pending (they are the context's, shared with the feature finders) or a copy in flight
-    static const bool trace_ev = getenv("MIS_MATCH_TRACE") != nullptr;
-    auto mark = [&](int i, hipStream_t s_) {      // diagnostics: device time stamps of the chains (printed with the host's when MIS_MATCH_TRACE is set)
-        if (!trace_ev) return;
-        if (!ws->tev[i]) hipEventCreate(&ws->tev[i]);
-        hipEventRecord(ws->tev[i], s_);
-    };
-    mark(0, st);
-    // Three chains: findHomography returns the RANSAC mask, not one recomputed after its refinement, so the second estimation
-    // starts from the mask while the DLT + LM refinement of the first H runs on a third stream; the |det H| test of the reference
-    // moves to the host assembly below.  Side and third are the context's two auxiliary streams -- the streams the ORB batch's
-    // helper lanes ran on a moment ago -- so that the job keeps to four streams (an earlier version created two more here, one in
-    // a priority class of its own to dodge a shared hardware queue: the step then moved by 25 % with GPU_MAX_HW_QUEUES).
-    auto enqueue_chains = [&]() -> int {
-        if (!ws->third) {
-            if ((rc = mis_aux_stream(ctx, 1, &ws->third)) != MIS_OK) return rc;
-            MIS_HIP(ctx, hipEventCreateWithFlags(&ws->ev_phase1, hipEventDisableTiming));
-            MIS_HIP(ctx, hipEventCreateWithFlags(&ws->ev_third_done, hipEventDisableTiming));
-            MIS_HIP(ctx, hipEventCreateWithFlags(&ws->ev_matches, hipEventDisableTiming));
-            MIS_HIP(ctx, hipEventCreateWithFlags(&ws->ev_lists, hipEventDisableTiming));
-        }
-        // the match lists are final once the ratio test has run: their download (megabytes) goes to the third stream now, under the
-        // RANSAC chains, instead of behind them (0.3 ms at the end of the call); pair k's matches land at the sum of the counts before it
-        MIS_HIP(ctx, hipEventRecord(ws->ev_matches, st));
-        MIS_HIP(ctx, hipStreamWaitEvent(ws->third, ws->ev_matches, 0));
-        hipLaunchKernelGGL(pack_lists_kernel, dim3(np), dim3(256), 0, ws->third, (const PairDesc*)d_pairs, np, (const int*)d_nm, (const MisDMatch*)d_matches,
-                           (MisDMatch*)(Hh + h_m), (int*)(Hh + h_nm));
-        MIS_HIP(ctx, hipEventRecord(ws->ev_lists, ws->third));
-        // main chain: first estimation of every pair, RANSAC phase 0 and the inlier masks of the pairs that finish there
-        if ((rc = homo_batch_run(ctx, &ws->b1, rt, p->max_iters, cf, HOMO_PHASE0_REPLAY, st)) != MIS_OK) return rc;
-        if ((rc = homo_batch_run(ctx, &ws->b1, rt, p->max_iters, cf, HOMO_TAIL0_MASK, st)) != MIS_OK) return rc;
-        MIS_HIP(ctx, hipEventRecord(ws->ev_phase0, st));
-        mark(1, st);
-        // side chain: the inlier-only estimation of those pairs
-        MIS_HIP(ctx, hipStreamWaitEvent(ws->side, ws->ev_phase0, 0));
-        hipLaunchKernelGGL(second_calls_kernel, dim3((np + 127) / 128), dim3(128), 0, ws->side, np, (const HomoCall*)ws->b1.calls, (const HomoResult*)ws->b1.results,
-                           (const float*)ws->b1.scr, (const int*)ws->b1.fin, 0, p->num_matches_thresh2, ws->b2.calls, d_out);
-        if (!ws->ev_draw1) MIS_HIP(ctx, hipEventCreateWithFlags(&ws->ev_draw1, hipEventDisableTiming));
-        {
-            // the compose gate: behind the side chain's first draw, 0.05 - 0.1 ms behind the first phase -- the tails and that draw
-            // hold their compute units by then
-            HomoSync sy;
-            sy.rec = ws->ev_draw1; sy.rec_pos = 2; ws->ev_gate = ws->ev_draw1;
-            if ((rc = homo_batch_run(ctx, &ws->b2, rt, p->max_iters, cf, HOMO_BOTH_PHASES, ws->side, &sy)) != MIS_OK) return rc;
-        }
-        MIS_HIP(ctx, hipEventRecord(ws->ev_side_done, ws->side));
-        mark(4, ws->side);
-        // third chain: DLT + LM refinement of the first H of the pairs that finished in phase 0
-        MIS_HIP(ctx, hipStreamWaitEvent(ws->third, ws->ev_phase0, 0));
-        if ((rc = homo_batch_run(ctx, &ws->b1, rt, p->max_iters, cf, HOMO_TAIL0_REFINE, ws->third)) != MIS_OK) return rc;
-        mark(6, ws->third);
-        // main chain: RANSAC phase 1 of the others
-        {
-            HomoSync sy;
-            if (trace_ev) {      // diagnostics: the end of the main chain's second draw
-                if (!ws->tev[7]) hipEventCreate(&ws->tev[7]);
-                sy.rec = ws->tev[7]; sy.rec_pos = 0;
-            }
-            if ((rc = homo_batch_run(ctx, &ws->b1, rt, p->max_iters, cf, HOMO_PHASE1_REPLAY, st, &sy)) != MIS_OK) return rc;
-        }
-        if ((rc = homo_batch_run(ctx, &ws->b1, rt, p->max_iters, cf, HOMO_TAIL1_MASK, st)) != MIS_OK) return rc;
-        MIS_HIP(ctx, hipEventRecord(ws->ev_phase1, st));
-        mark(2, st);
-        // the refinement of the phase-1 finishers' first H stays on this stream (1.7 ms of latency-bound work: behind the 2 ms
-        // refinement of the phase-0 finishers on the third stream it ended the matcher 0.6 ms later); their inlier-only second
-        // estimation goes to the third stream instead
-        if ((rc = homo_batch_run(ctx, &ws->b1, rt, p->max_iters, cf, HOMO_TAIL1_REFINE, st)) != MIS_OK) return rc;
-        mark(3, st);
-        MIS_HIP(ctx, hipStreamWaitEvent(ws->third, ws->ev_phase1, 0));
-        hipLaunchKernelGGL(second_calls_kernel, dim3((np + 127) / 128), dim3(128), 0, ws->third, np, (const HomoCall*)ws->b1.calls, (const HomoResult*)ws->b1.results,
-                           (const float*)ws->b1.scr, (const int*)ws->b1.fin, 1, p->num_matches_thresh2, ws->b3.calls, d_out);
-        if ((rc = homo_batch_run(ctx, &ws->b3, rt, p->max_iters, cf, HOMO_BOTH_PHASES, ws->third)) != MIS_OK) return rc;
-        MIS_HIP(ctx, hipEventRecord(ws->ev_third_done, ws->third));
-        mark(5, ws->third);
-        MIS_HIP(ctx, hipStreamWaitEvent(st, ws->ev_third_done, 0));
-        MIS_HIP(ctx, hipStreamWaitEvent(st, ws->ev_side_done, 0));
-        return MIS_OK;
-    };
-    if ((rc = enqueue_chains()) != MIS_OK) {
+    MIS_HIP(ctx, hipEventRecord(ws->ev_knn.ev, st));
+    ws->ev_gate = ws->ev_knn.ev;
+    hipLaunchKernelGGL(ratio_union_kernel, dim3(np), dim3(1024), 0, st, (const FeatDev*)d.feats, (const PairDesc*)d.pairs, (const int*)d.idx,
+                       (const float*)d.dist, 1.f - p->match_conf, d.matches, d.src, d.dst, d.nm);
+    hipLaunchKernelGGL(first_calls_kernel, dim3((np + 127) / 128), dim3(128), 0, st, (const PairDesc*)d.pairs, np, (const int*)d.nm, (const float*)d.src,
+                       (const float*)d.dst, d.mask, p->num_matches_thresh1, ws->b1.calls, d.out);
+    // the chains fork to the context's auxiliary streams, shared with the feature finders: an error in there must not leave them
+    // with work pending or a copy in flight
+    if ((rc = enqueue_chains(ctx, ws, np, p, d, h)) != MIS_OK) {
         if (ws->side) hipStreamSynchronize(ws->side);
         if (ws->third) hipStreamSynchronize(ws->third);
         hipStreamSynchronize(st);
         return rc;
     }
     MIS_HIP(ctx, hipGetLastError());
-    int* nm = (int*)(Hh + h_nm);
-    PairOut* po = (PairOut*)(Hh + h_out);
-    HomoResult* r1 = (HomoResult*)(Hh + h_r1);
-    HomoResult* r2 = (HomoResult*)(Hh + h_r2);
-    HomoResult* r3 = (HomoResult*)(Hh + h_r3);
-    int* fin = (int*)(Hh + h_fin);
-    MisDMatch* hm = (MisDMatch*)(Hh + h_m);
-    uint8_t* hmask = Hh + h_mask;
-    {
-        CopySegs cs;
-        const void* srcs[6] = {d_out, ws->b1.results, ws->b2.results, ws->b3.results, ws->b1.fin, d_mask};
-        void* dsts[6] = {po, r1, r2, r3, fin, hmask};
-        const size_t sizes[6] = {sizeof(PairOut) * np, sizeof(HomoResult) * np, sizeof(HomoResult) * np, sizeof(HomoResult) * np, sizeof(int) * np, m_total};
-        cs.n = 6;
-        for (int k = 0; k < 6; k++) { cs.src[k] = (const uint8_t*)srcs[k]; cs.dst[k] = (uint8_t*)dsts[k]; cs.bytes[k] = (unsigned)sizes[k]; }
-        for (int k = 6; k < 8; k++) { cs.src[k] = nullptr; cs.dst[k] = nullptr; cs.bytes[k] = 0; }
-        hipLaunchKernelGGL(copy_segments_kernel, dim3(64), dim3(256), 0, st, cs);
-    }
+    enqueue_results(ws, np, pl.m_total, d, h, st);
     // everything of this call is enqueued: a thread waiting in mis_match_knn_fence may start launching now without
     // competing with this one for the runtime's launch path
     ws->knn_seq.store(seq_guard.seq);
@@ -1045,96 +1153,10 @@ int match_impl(MisContext* ctx, const MisFeatures* feats, int n, const MisMatchP
         cb(user);
         MIS_HIP(ctx, hipSetDevice(ctx->device));
     }
-    const bool trace = getenv("MIS_MATCH_TRACE") != nullptr;
     const auto tq = std::chrono::steady_clock::now();
-    // an error from here on must not leave half-built entries behind: the lists are released and `out` is back to its zeroed state
-    auto drop_lists = [&]() {
-        for (int k = 0; k < np; k++) {
-            const PairDesc& pd = pairs[k];
-            MisMatchesInfo* e[2] = {&out[pd.i * n + pd.j], &out[pd.j * n + pd.i]};
-            for (MisMatchesInfo* m : e) { free(m->matches); free(m->inliers_mask); init_info(m); }
-        }
-    };
-    // MatchesInfo (host), part 1 under the RANSAC chains: the match lists (packed by pack_lists_kernel) and their mirrors
-    MIS_HIP(ctx, hipEventSynchronize(ws->ev_lists));
-    {
-        size_t packed_off = 0;
-        for (int k = 0; k < np; k++) {
-            const PairDesc& pd = pairs[k];
-            MisMatchesInfo* a = &out[pd.i * n + pd.j];
-            MisMatchesInfo* b = &out[pd.j * n + pd.i];
-            a->src_img_idx = pd.i; a->dst_img_idx = pd.j;
-            a->n_matches = nm[k];
-            a->matches = (MisDMatch*)malloc(sizeof(MisDMatch) * (size_t)(nm[k] + 1));
-            memcpy(a->matches, hm + packed_off, sizeof(MisDMatch) * (size_t)nm[k]);
-            packed_off += (size_t)nm[k];
-            b->matches = (MisDMatch*)malloc(sizeof(MisDMatch) * (size_t)(nm[k] + 1));
-            for (int q = 0; q < nm[k]; q++) {
-                b->matches[q] = a->matches[q];
-                b->matches[q].query_idx = a->matches[q].train_idx;
-                b->matches[q].train_idx = a->matches[q].query_idx;
-            }
-        }
-    }
-    {
-        const hipError_t e = hipStreamSynchronize(st);
-        if (e != hipSuccess) {
-            drop_lists();
-            return mis_set_error(ctx, MIS_E_HIP, "hipStreamSynchronize failed: %s (%s:%d)", hipGetErrorString(e), __FILE__, __LINE__);
-        }
-    }
-    const auto ts = std::chrono::steady_clock::now();
-    if (l2_bad) {
-        drop_lists();
-        return mis_set_error(ctx, MIS_E_UNSUPPORTED, "L2 matching needs integer-valued descriptors in 0..255 (SIFT style)");
-    }
-    // part 2: masks, H, confidence; the mirror entry gets H^-1 and swapped indices
-    for (int k = 0; k < np; k++) {
-        const PairDesc& pd = pairs[k];
-        MisMatchesInfo* a = &out[pd.i * n + pd.j];
-        MisMatchesInfo* b = &out[pd.j * n + pd.i];
-        MisDMatch* bm = b->matches;
-        if (po[k].ran_ransac) {
-            a->inliers_mask = (uint8_t*)malloc((size_t)nm[k] + 1);
-            memcpy(a->inliers_mask, hmask + pd.m_off, (size_t)nm[k]);
-        }
-        // matchers.cpp: "if (H.empty() || |det H| < eps) return" after the first estimation.  The second estimation runs
-        // without waiting for the refined H, and a degenerate first H drops it here (same expression, same rounding: no FMA contraction)
-        const bool det_ok = !(fabs(det3(r1[k].H)) < DBL_EPSILON);
-        const bool passed = po[k].passed && det_ok, second = po[k].second && det_ok;
-        // H of the inlier-only estimation when it ran (it may come back empty), else of the first one
-        const HomoResult& hr = second ? (fin[k] == 0 ? r2[k] : r3[k]) : r1[k];
-        a->has_H = po[k].ran_ransac ? hr.ok : 0;
-        if (a->has_H) memcpy(a->H, hr.H, sizeof(a->H));
-        a->num_inliers = passed ? r1[k].ninl : 0;
-        if (passed) {
-            // Brown & Lowe confidence; > 3 means near-duplicate images and is zeroed (matchers.cpp)
-            double c = a->num_inliers / (8 + 0.3 * nm[k]);
-            a->confidence = c > 3. ? 0. : c;
-        }
-        *b = *a;
-        b->src_img_idx = pd.j; b->dst_img_idx = pd.i;
-        b->matches = bm;
-        if (a->inliers_mask) {
-            b->inliers_mask = (uint8_t*)malloc((size_t)nm[k] + 1);
-            memcpy(b->inliers_mask, a->inliers_mask, (size_t)nm[k]);
-        }
-        if (a->has_H) invert3(a->H, b->H);
-    }
-    if (trace) {
-        const auto te = std::chrono::steady_clock::now();
-        auto us = [](auto a, auto b) { return (double)std::chrono::duration_cast<std::chrono::microseconds>(b - a).count(); };
-        fprintf(stderr, "match: enqueue %.0f us, device wait %.0f us, host assembly %.0f us\n", us(t_begin, tq), us(tq, ts), us(ts, te));
-        if (ws->tev[0] && ws->tev[1] && ws->tev[3] && ws->tev[4] && ws->tev[5] && ws->tev[6]) {
-            float e1 = 0, e3 = 0, e4 = 0, e5 = 0, e6 = 0;
-            hipEventElapsedTime(&e1, ws->tev[0], ws->tev[1]); hipEventElapsedTime(&e3, ws->tev[0], ws->tev[3]); hipEventElapsedTime(&e4, ws->tev[0], ws->tev[4]);
-            hipEventElapsedTime(&e5, ws->tev[0], ws->tev[5]); hipEventElapsedTime(&e6, ws->tev[0], ws->tev[6]);
-            float e2 = 0, e7 = 0;
-            if (ws->tev[2]) hipEventElapsedTime(&e2, ws->tev[0], ws->tev[2]);
-            if (ws->tev[7]) { hipEventElapsedTime(&e7, ws->tev[0], ws->tev[7]); fprintf(stderr, "match chains: main chain's second draw done %.2f\n", e7); }
-            fprintf(stderr, "match chains, ms after the 2-NN pass was enqueued-behind (device events): first phase done %.2f | tails of its finishers done %.2f | main chain: second RANSAC phase done %.2f, done %.2f | side chain done %.2f | third chain done %.2f\n", e1, e6, e2, e3, e4, e5);
-        }
-    }
+    std::chrono::steady_clock::time_point ts;
+    if ((rc = assemble_matches(ctx, ws, pl, h, n, out, &ts)) != MIS_OK) return rc;
+    if (match_trace()) trace_report(ws, t_begin, tq, ts);
     return MIS_OK;
 }
 
@@ -1215,34 +1237,24 @@ extern "C" int mis_knn2(MisContext* ctx, const MisFeatures* q, const MisFeatures
     MatchWorkspace* ws = workspace(ctx);
     hipStream_t st = ctx->stream;
     MIS_HIP(ctx, hipStreamSynchronize(st));
-    const size_t nq = (size_t)q->n, nt = (size_t)std::max(t->n, 0);
+    const size_t nq = (size_t)q->n;
     Carver dc;
     const size_t o_feats = dc.take(2 * sizeof(FeatDev)), o_pairs = dc.take(sizeof(PairDesc)), o_idx = dc.take(sizeof(int) * 2 * nq), o_dist = dc.take(sizeof(float) * 2 * nq);
-    const size_t o_qh = dc.take(nq * 256), o_th = dc.take(nt * 256), o_qn = dc.take(nq * 4), o_tn = dc.take(nt * 4), o_bad = dc.take(4);
-    const size_t o_part = dc.take((size_t)16 * L2_MAX_SLICES * nq);
     MIS_HIP(ctx, ws->dev.reserve(dc.off));
     uint8_t* D = (uint8_t*)ws->dev.p;
+    const PairDesc pd{0, 1, 0, nq, 0, q->n + t->n};
     int bad = 0;
     if (binary) {
         FeatDev fd[2] = {{(const uint8_t*)q->descriptors, q->keypoints, q->n, q->img_w, q->img_h},
                          {(const uint8_t*)t->descriptors, t->keypoints, t->n, t->img_w, t->img_h}};
-        PairDesc pd;
-        pd.i = 0; pd.j = 1; pd.knn_off12 = 0; pd.knn_off21 = q->n; pd.m_off = 0; pd.cap = q->n + t->n;
         MIS_HIP(ctx, hipMemcpyAsync(D + o_feats, fd, sizeof(fd), hipMemcpyHostToDevice, st));
         MIS_HIP(ctx, hipMemcpyAsync(D + o_pairs, &pd, sizeof(pd), hipMemcpyHostToDevice, st));
         MIS_HIP(ctx, hipStreamSynchronize(st));  // fd / pd live on this stack frame
         hipLaunchKernelGGL(knn2_hamming_kernel, dim3((q->n + 255) / 256, 1), dim3(256), 0, st, (const FeatDev*)(D + o_feats), (const PairDesc*)(D + o_pairs),
                            (int*)(D + o_idx), (float*)(D + o_dist));
     } else {
-        MIS_HIP(ctx, hipMemsetAsync(D + o_bad, 0, 4, st));
-        hipLaunchKernelGGL(l2_prep_kernel, dim3((q->n + 3) / 4), dim3(256), 0, st, (const float*)q->descriptors, q->n, q->desc_cols, (_Float16*)(D + o_qh),
-                           (float*)(D + o_qn), (int*)(D + o_bad));
-        if (t->n > 0)
-            hipLaunchKernelGGL(l2_prep_kernel, dim3((t->n + 3) / 4), dim3(256), 0, st, (const float*)t->descriptors, t->n, t->desc_cols, (_Float16*)(D + o_th),
-                               (float*)(D + o_tn), (int*)(D + o_bad));
-        L2Set Q{(const _Float16*)(D + o_qh), (const float*)(D + o_qn), q->n}, T{(const _Float16*)(D + o_th), (const float*)(D + o_tn), std::max(t->n, 0)};
-        l2_knn2_launch(st, ctx->num_cu, Q, T, D + o_part, (int*)(D + o_idx), (float*)(D + o_dist));
-        MIS_HIP(ctx, hipMemcpyAsync(&bad, D + o_bad, 4, hipMemcpyDeviceToHost, st));
+        const MisFeatures qt[2] = {*q, *t};
+        if (int rc = l2_knn2_pairs(ctx, ws->l2, qt, 2, &pd, 1, false, (int*)(D + o_idx), (float*)(D + o_dist), &bad); rc != MIS_OK) return rc;
     }
     MIS_HIP(ctx, hipGetLastError());
     MIS_HIP(ctx, hipMemcpyAsync(idx2, D + o_idx, sizeof(int) * 2 * nq, hipMemcpyDeviceToHost, st));

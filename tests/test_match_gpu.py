@@ -228,6 +228,47 @@ def test_match_all_pairs_float_descriptors(ctx, oracle_mod):
     assert pm[1].num_inliers >= 400 and pm[1].confidence == 0.0 and pm[2].num_inliers < 20
 
 
+def test_match_all_pairs_refuses_non_integer_float_descriptors(ctx, oracle_mod):
+    """The matcher refuses float descriptors that are not integers (the fp16 MFMA distances would not be exact) only once the
+    device is done, after it has built the match lists: the failed call leaves every MatchesInfo empty, and the next call on
+    the same matcher still equals the oracle."""
+    import ctypes as C
+    import image_stitching_amd as isa
+    from image_stitching_amd import _capi as capi
+    from image_stitching_amd.stitching import KP_DTYPE
+    rng = np.random.default_rng(53)
+    H = np.array([[0.99, 0.01, 30.0], [-0.02, 1.0, -12.0], [1e-5, 0.0, 1.0]])
+    n = 400
+    base = _sift_like(rng, n)
+    k1 = np.zeros(n, KP_DTYPE); k1["x"] = rng.uniform(0, 640, n); k1["y"] = rng.uniform(0, 480, n)
+    p = np.c_[k1["x"] - 320, k1["y"] - 240, np.ones(n)] @ H.T
+    k2 = np.zeros(n, KP_DTYPE); k2["x"] = p[:, 0] / p[:, 2] + 320; k2["y"] = p[:, 1] / p[:, 2] + 240
+    d2 = np.clip(base + rng.integers(-2, 3, base.shape), 0, 255).astype(np.float32)
+    d2[:60] = _sift_like(rng, 60)       # outliers
+    k3, d3 = np.zeros(250, KP_DTYPE), _sift_like(rng, 250)
+    k3["x"] = rng.uniform(0, 640, 250); k3["y"] = rng.uniform(0, 480, 250)
+    sets = [(k1, base), (k2, d2), (k3, d3)]
+    matcher = isa.BestOf2NearestMatcher(ctx, 0.65)
+    bad = [isa.ImageFeatures.upload(ctx, (640, 480), k, d + np.float32(0.25), i) for i, (k, d) in enumerate(sets)]
+    arr = (capi.MisFeatures * 3)()
+    for i, f in enumerate(bad):
+        C.memmove(C.byref(arr[i]), C.byref(f.raw), C.sizeof(capi.MisFeatures))
+    mis = (capi.MisMatchesInfo * 9)()
+    for m in mis:
+        m.src_img_idx, m.dst_img_idx, m.n_matches, m.num_inliers, m.has_H, m.confidence = 1, 2, 3, 4, 1, 0.5
+    with pytest.raises(isa.MisError):
+        ctx.check(ctx.lib.mis_match_all_pairs(ctx.h, arr, 3, C.byref(matcher.params), mis))
+    for m in mis:
+        assert (m.src_img_idx, m.dst_img_idx, m.n_matches, m.num_inliers, m.has_H, m.confidence) == (-1, -1, 0, 0, 0, 0.0)
+        assert not m.matches and not m.inliers_mask and not any(m.H)
+    feats = [isa.ImageFeatures.upload(ctx, (640, 480), k, d, i) for i, (k, d) in enumerate(sets)]
+    pm = matcher(feats)
+    ref = oracle_mod.match_all_pairs([_feat_dict(k, d, (640, 480)) for k, d in sets], oracle_mod.match_default_params(match_conf=0.65))
+    for g, o in zip(pm, ref):
+        _compare_matches_info(g, o)
+    assert pm[1].num_inliers >= 300
+
+
 @pytest.mark.parametrize("n", [5, 6, 8, 10])
 def test_find_homography_tiny_problems_incl_infeasible(ctx, oracle_mod, n):
     """Tiny correspondence sets: (a) every 4-subset fails checkSubset (collinear source points) -> getSubset gives up,
