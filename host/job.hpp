@@ -8,63 +8,29 @@
 //     the composition of ALL frames is enqueued on the compose stream behind the 2-NN pass (mis_match_knn_fence):
 //     batched fused warp + feed (mis_compose_frames) and the collapse (mis_blender_blend)       :647-653, :1086-1228
 //   pruning (myLeaveBiggestComponent); when a frame was dropped the composition is redone for the kept set      :215-278
-// The result stays in HBM (MisImage with mem = MIS_MEM_DEVICE).
+// The result stays in HBM (MisImage with mem = MIS_MEM_DEVICE).  The main context runs on the null stream.  Contexts, finder,
+// blender sizing and the warp + feed are mis::JobCore's (job_core.hpp), shared with mis::ShardedJob; this file is the flow.
 #pragma once
 #include <vector>
-#include "stitcher.hpp"
+#include "job_core.hpp"
 
 namespace mis {
 
-struct JobOutput {
-    std::vector<int> indices;         // frames kept by the pruning
-    std::vector<double> confidence;   // n x n
-    std::vector<int> num_features;
-    MisImage pano{}, mask{};          // device: 16SC3 panorama and 8U mask, owned by the job (valid until its next run)
-    int num_bands = 0, pano_width = 0, pano_height = 0;
-    bool speculation_kept = false;    // the composition enqueued under the matcher was the final one
-    std::vector<MisMatchesInfo> matches;   // n x n (host arrays owned by the library; released by the job's next run)
-};
-
-class StitchJob {
+class StitchJob : private JobCore {
 public:
     StitchJob(int device, int width, int height, const std::vector<CameraParams>& cameras, const StitchConfig& cfg = StitchConfig());
     ~StitchJob();
-    StitchJob(const StitchJob&) = delete;
-    StitchJob& operator=(const StitchJob&) = delete;
     // frames: n device-resident 8UC3 images of the job's size, complete on the main context's stream (or synchronised)
     JobOutput run(const std::vector<MisImage>& frames);
-    void synchronize();
+    using JobCore::synchronize;
     MisContext* context() const { return ctx_; }           // features + matcher
     MisContext* compose_context() const { return cctx_; }  // warp + blend (own stream)
 
 private:
-    struct Compose { int type = 0, bands = 0; float sharp = 0; MisRect pano{}; };
-    void check(MisContext* c, int rc, const char* what) const;
-    Compose prepare(const std::vector<int>& idx);
-    void compose(const std::vector<MisImage>& frames, const std::vector<int>& idx);
     void finalize();
-    static void hook(void* self);
-    static void prep_hook(void* self);      // the finder's hook (mis_orb_on_enqueued): prepare() under the feature stage
 
-    int w_, h_, n_;
-    std::vector<CameraParams> cams_;
-    StitchConfig cfg_;
-    MisContext* ctx_ = nullptr;
-    MisContext* cctx_ = nullptr;
-    void* cstream_ = nullptr;
-    MisOrb* orb_ = nullptr;
-    MisBlender* blender_ = nullptr;
-    Compose key_{};
-    std::vector<float> Ks_, Rs_;      // n x 9 each (float, as main() hands them to the warper)
-    std::vector<MisRect> rois_;       // of the frames of the current composition
     MisImage pano_{}, mask_{};
-    std::vector<MisMatchesInfo> pairwise_;
-    // state of the hook
-    const std::vector<MisImage>* hook_frames_ = nullptr;
-    bool hook_ran_ = false;
-    std::string hook_error_;
-    bool prep_ran_ = false;
-    std::string prep_error_;
+    Hook prep_, match_;     // the finder's hook (mis_orb_on_enqueued): prepare() under the feature stage; the matcher's: the composition
 };
 
 }  // namespace mis

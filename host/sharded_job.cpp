@@ -15,18 +15,6 @@ std::vector<int> frame_block(int n, int rank, int world) {
     return out;
 }
 
-static float median_focal(const std::vector<CameraParams>& cams, const std::vector<int>& idx) {
-    // image_stitching.cpp:884-895: median of the kept cameras' focals (mean of the middle two for an even count), as float
-    std::vector<double> f;
-    for (int i : idx) f.push_back(cams[i].focal);
-    std::sort(f.begin(), f.end());
-    return f.size() % 2 == 1 ? static_cast<float>(f[f.size() / 2]) : static_cast<float>(f[f.size() / 2 - 1] + f[f.size() / 2]) * 0.5f;
-}
-
-void ShardedJob::check(MisContext* c, int rc, const char* what) const {
-    if (rc != MIS_OK) throw std::runtime_error(std::string(what) + " failed on rank " + std::to_string(comm_.rank()) + ": " + mis_last_error(c));
-}
-
 void* ShardedJob::reserve(DevBuf& b, size_t bytes) {
     bytes = std::max<size_t>(bytes, 256);
     if (b.bytes < bytes) {
@@ -38,91 +26,28 @@ void* ShardedJob::reserve(DevBuf& b, size_t bytes) {
     return b.p;
 }
 
+static void* new_stream(int device) {
+    void* s = nullptr;
+    if (mis_stream_create(device, 0, &s) != MIS_OK) throw std::runtime_error("mis_stream_create failed: no HIP device (there is no CPU fallback)");
+    return s;
+}
+
 ShardedJob::ShardedJob(int device, int width, int height, const std::vector<CameraParams>& cameras, Communicator& comm, const StitchConfig& cfg)
-    : device_(device), w_(width), h_(height), n_((int)cameras.size()), cams_(cameras), cfg_(cfg), comm_(comm) {
-    if (cfg_.features_type != "orb" || cfg_.ba_cost_func != "no" || cfg_.expos_comp_type != "no" || cfg_.seam_find_type != "no")
-        throw std::runtime_error("mis::ShardedJob runs the hot path (ORB, supplied cameras, no seam-scale step)");
+    : JobCore("mis::ShardedJob", " on rank " + std::to_string(comm.rank()), device, new_stream(device), width, height, cameras, cfg), comm_(comm) {
     if (n_ % comm_.world() != 0) throw std::runtime_error("the frame count must divide evenly over the ranks");
     mine_ = frame_block(n_, comm_.rank(), comm_.world());
-    if (mis_stream_create(device, 0, &mstream_) != MIS_OK || mis_stream_create(device, 0, &cstream_) != MIS_OK)
-        throw std::runtime_error("mis_stream_create failed: no HIP device (there is no CPU fallback)");
-    if (mis_context_create(device, mstream_, &ctx_) != MIS_OK || mis_context_create(device, cstream_, &cctx_) != MIS_OK)
-        throw std::runtime_error("mis_context_create failed");
-    MisOrbParams op;
-    mis_orb_default_params(&op);
-    check(ctx_, mis_orb_create(ctx_, &op, w_, h_, &orb_), "mis_orb_create");
-    Ks_.resize((size_t)n_ * 9); Rs_.resize((size_t)n_ * 9);
-    for (int i = 0; i < n_; i++) {
-        const Mat3<float> K = cams_[i].K().cast<float>(), R = cams_[i].R.cast<float>();
-        std::copy(K.m.begin(), K.m.end(), Ks_.begin() + 9 * i);
-        std::copy(R.m.begin(), R.m.end(), Rs_.begin() + 9 * i);
-    }
     send_.resize(comm_.world()); recv_.resize(comm_.world());
 }
 
-ShardedJob::~ShardedJob() {
-    if (cctx_) mis_context_synchronize(cctx_);
-    if (ctx_) mis_context_synchronize(ctx_);
-    if (!pairwise_.empty()) mis_matches_free(pairwise_.data(), (int)pairwise_.size());
-    if (blender_) mis_blender_destroy(blender_);
-    if (orb_) mis_orb_destroy(orb_);
+ShardedJob::~ShardedJob() {      // (hipFree synchronises the device)
     for (DevBuf* b : {&kps_send_, &desc_send_, &kps_all_, &desc_all_, &strip_mine_, &strips_all_, &pano_buf_, &mask_buf_}) if (b->p) (void)hipFree(b->p);
     for (auto& b : send_) if (b.p) (void)hipFree(b.p);
     for (auto& b : recv_) if (b.p) (void)hipFree(b.p);
-    if (cctx_) mis_context_destroy(cctx_);
-    if (ctx_) mis_context_destroy(ctx_);
-    if (cstream_) mis_stream_destroy(cstream_);
-    if (mstream_) mis_stream_destroy(mstream_);
 }
 
-void ShardedJob::synchronize() {
-    check(ctx_, mis_context_synchronize(ctx_), "mis_context_synchronize");
-    check(cctx_, mis_context_synchronize(cctx_), "mis_context_synchronize (compose)");
-}
-
-// warpRoi of the kept frames at the scale of that set, panorama roi, blender sizing + prepare (every rank, all kept frames)
-ShardedJob::Compose ShardedJob::prepare(const std::vector<int>& idx) {
-    const int m = (int)idx.size();
-    const float scale = median_focal(cams_, idx);
-    std::vector<float> Ks((size_t)m * 9), Rs((size_t)m * 9);
-    for (int k = 0; k < m; k++) {
-        std::copy(Ks_.begin() + 9 * idx[k], Ks_.begin() + 9 * idx[k] + 9, Ks.begin() + 9 * k);
-        std::copy(Rs_.begin() + 9 * idx[k], Rs_.begin() + 9 * idx[k] + 9, Rs.begin() + 9 * k);
-    }
-    rois_.assign(m, MisRect{});
-    check(cctx_, mis_warp_roi_batch(cctx_, scale, w_, h_, m, Ks.data(), Rs.data(), rois_.data()), "mis_warp_roi_batch");
-    std::vector<MisPoint> corners(m);
-    std::vector<MisSize> sizes(m);
-    for (int k = 0; k < m; k++) { corners[k] = {rois_[k].x, rois_[k].y}; sizes[k] = {rois_[k].width, rois_[k].height}; }
-    Compose c;
-    check(cctx_, mis_result_roi(corners.data(), sizes.data(), m, &c.pano), "mis_result_roi");
-    check(cctx_, mis_blend_config(cfg_.blend_type, cfg_.blend_strength, c.pano.width, c.pano.height, &c.type, &c.bands, &c.sharp), "mis_blend_config");
-    if (c.type != MIS_BLEND_MULTI_BAND) throw std::runtime_error("mis::ShardedJob exchanges the multi-band blender's pyramids");
-    if (!blender_ || c.type != key_.type || c.bands != key_.bands || c.sharp != key_.sharp) {
-        if (blender_) { mis_blender_destroy(blender_); blender_ = nullptr; }
-        check(cctx_, mis_blender_create(cctx_, c.type, c.bands, c.sharp, &blender_), "mis_blender_create");
-    }
-    key_ = c;
-    check(cctx_, mis_blender_prepare(blender_, corners.data(), sizes.data(), m), "mis_blender_prepare");
-    return c;
-}
-
-// batched fused warp + feed of this rank's frames among the kept ones (rois_ from prepare(idx))
-void ShardedJob::compose_mine(const std::vector<MisImage>& frames, const std::vector<int>& idx) {
-    std::vector<MisImage> fr;
-    std::vector<float> Ks, Rs;
-    std::vector<MisRect> rois;
-    for (size_t q = 0; q < mine_.size(); q++) {
-        const auto it = std::find(idx.begin(), idx.end(), mine_[q]);
-        if (it == idx.end()) continue;
-        const int k = (int)(it - idx.begin());
-        fr.push_back(frames[q]);
-        Ks.insert(Ks.end(), Ks_.begin() + 9 * mine_[q], Ks_.begin() + 9 * mine_[q] + 9);
-        Rs.insert(Rs.end(), Rs_.begin() + 9 * mine_[q], Rs_.begin() + 9 * mine_[q] + 9);
-        rois.push_back(rois_[k]);
-    }
-    if (fr.empty()) return;     // every frame of this rank was pruned: nothing to warp or feed (the exchanges around still run)
-    check(cctx_, mis_compose_frames(blender_, fr.data(), (int)fr.size(), median_focal(cams_, idx), Ks.data(), Rs.data(), rois.data()), "mis_compose_frames");
+// the blend exchange moves the multi-band blender's pyramids: any other blend is refused here, before anything is composed
+void ShardedJob::prepare_multi_band(const std::vector<int>& idx) {
+    if (prepare(idx).type != MIS_BLEND_MULTI_BAND) throw std::runtime_error("mis::ShardedJob exchanges the multi-band blender's pyramids");
 }
 
 // Strip exchange + per-strip finalise + assembly (distributed.py: stage_reduce_finalize): every rank ends with the panorama.
@@ -229,45 +154,20 @@ void ShardedJob::exchange_finalize(const std::vector<int>& idx) {
     mask_ = MisImage{mask, pw, ph, 1, (size_t)pw, MIS_U8, MIS_MEM_DEVICE};
 }
 
-void ShardedJob::hook(void* self_) {      // inside the matcher call, once its device work is enqueued: this rank's composition
-    ShardedJob* self = static_cast<ShardedJob*>(self_);
-    self->hook_ran_ = true;
-    try {
-        const int rc = mis_match_knn_fence(self->ctx_, self->cstream_, mis_match_sequence(self->ctx_), 0);
-        if (rc < 0) self->check(self->ctx_, rc, "mis_match_knn_fence");
-        std::vector<int> everyone(self->n_);
-        std::iota(everyone.begin(), everyone.end(), 0);
-        self->compose_mine(*self->hook_frames_, everyone);
-    } catch (const std::exception& e) { self->hook_error_ = e.what(); }
-}
-
-void ShardedJob::prep_hook(void* self_) {
-    ShardedJob* self = static_cast<ShardedJob*>(self_);
-    self->prep_ran_ = true;
-    try {
-        std::vector<int> everyone(self->n_);
-        std::iota(everyone.begin(), everyone.end(), 0);
-        self->prepare(everyone);
-    } catch (const std::exception& e) { self->prep_error_ = e.what(); }
-}
-
-ShardedOutput ShardedJob::run(const std::vector<MisImage>& frames) {
+JobOutput ShardedJob::run(const std::vector<MisImage>& frames) {
     const int m = (int)mine_.size(), world = comm_.world();
     if ((int)frames.size() != m) throw std::runtime_error("ShardedJob::run: one frame per camera of this rank's block");
-    ShardedOutput out;
-    std::vector<int> everyone(n_);
-    std::iota(everyone.begin(), everyone.end(), 0);
+    JobOutput out;
     check(cctx_, mis_context_wait(cctx_, ctx_), "mis_context_wait");
     // ---- features of this rank's block (:567-622); the blender is sized from the finder's hook (cameras only) ----
-    prep_ran_ = false; prep_error_.clear();
-    check(ctx_, mis_orb_on_enqueued(orb_, &ShardedJob::prep_hook, this), "mis_orb_on_enqueued");
+    prep_.arm([this] { prepare_multi_band(everyone_); });
+    check(ctx_, mis_orb_on_enqueued(orb_, &Hook::fire, &prep_), "mis_orb_on_enqueued");
     std::vector<MisFeatures> local(m);
     std::memset(local.data(), 0, sizeof(MisFeatures) * m);
     const int rc_f = m > 0 ? mis_orb_detect_batch(orb_, frames.data(), m, local.data()) : MIS_OK;
     mis_orb_on_enqueued(orb_, nullptr, nullptr);
     check(ctx_, rc_f, "mis_orb_detect_batch");
-    if (!prep_ran_) prep_hook(this);
-    if (!prep_error_.empty()) throw std::runtime_error(prep_error_);
+    prep_.finish();
     // ---- feature all-gather: counts (host), then keypoints and descriptors packed to the job's largest count ----
     std::vector<int> cnt_mine(m), cnt_all(n_);
     for (int k = 0; k < m; k++) cnt_mine[k] = local[k].n;
@@ -288,19 +188,17 @@ ShardedOutput ShardedJob::run(const std::vector<MisImage>& frames) {
     }
     out.num_features = cnt_all;
     // ---- this rank's pairs (:647-653), its composition speculated from the matcher's hook ----
-    if (!pairwise_.empty()) { mis_matches_free(pairwise_.data(), (int)pairwise_.size()); pairwise_.clear(); }
-    pairwise_.assign((size_t)n_ * n_, MisMatchesInfo{});
-    MisMatchParams mp;
-    mis_match_default_params(&mp);
-    mp.match_conf = cfg_.match_conf;
-    hook_frames_ = &frames; hook_ran_ = false; hook_error_.clear();
-    check(ctx_, mis_match_on_enqueued(ctx_, &ShardedJob::hook, this), "mis_match_on_enqueued");
+    const MisMatchParams mp = reset_matches();
+    match_.arm([this, &frames] {
+        fence_knn();
+        compose(frames, mine_, everyone_);
+    });
+    check(ctx_, mis_match_on_enqueued(ctx_, &Hook::fire, &match_), "mis_match_on_enqueued");
     const int rc = mis_match_pairs_sharded(ctx_, feats.data(), n_, &mp, comm_.rank(), world, pairwise_.data());
     mis_match_on_enqueued(ctx_, nullptr, nullptr);
     for (auto& f : local) mis_features_free(ctx_, &f);
     check(ctx_, rc, "mis_match_pairs_sharded");
-    if (!hook_ran_) hook(this);
-    if (!hook_error_.empty()) throw std::runtime_error(hook_error_);
+    match_.finish();
     // ---- the n x n confidences: every pair has exactly one owner, the sum is a gather ----
     out.confidence.resize((size_t)n_ * n_);
     for (int k = 0; k < n_ * n_; k++) out.confidence[k] = pairwise_[k].confidence;
@@ -313,8 +211,8 @@ ShardedOutput ShardedJob::run(const std::vector<MisImage>& frames) {
     out.indices = idx;
     out.speculation_kept = kept == n_;
     if (!out.speculation_kept) {       // a frame was dropped: the kept set's own scale, roi and band count
-        prepare(idx);
-        compose_mine(frames, idx);
+        prepare_multi_band(idx);
+        compose(frames, mine_, idx);
     }
     exchange_finalize(idx);
     check(cctx_, mis_context_synchronize(cctx_), "mis_context_synchronize (compose)");

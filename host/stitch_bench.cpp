@@ -15,6 +15,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <functional>
 #include <iostream>
 #include <string>
 #include <vector>
@@ -62,23 +63,51 @@ static bool read_cams(const std::string& path, int* n, int* W, int* H, std::vect
     return true;
 }
 
-static int write_dump(const std::string& dump, const MisImage& pano_d, const MisImage& mask_d, int pw, int ph, int bands, const std::vector<int>& indices,
-                      const std::vector<int>& nfeat, const std::vector<double>& conf) {
+static int write_dump(const std::string& dump, const mis::JobOutput& out) {
+    const int pw = out.pano_width, ph = out.pano_height;
     std::vector<int16_t> pano((size_t)pw * ph * 3);
     std::vector<uint8_t> mask((size_t)pw * ph);
-    HIPCHK(hipMemcpy2D(pano.data(), (size_t)pw * 6, pano_d.data, pano_d.stride, (size_t)pw * 6, ph, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy2D(mask.data(), (size_t)pw, mask_d.data, mask_d.stride, (size_t)pw, ph, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy2D(pano.data(), (size_t)pw * 6, out.pano.data, out.pano.stride, (size_t)pw * 6, ph, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy2D(mask.data(), (size_t)pw, out.mask.data, out.mask.stride, (size_t)pw, ph, hipMemcpyDeviceToHost));
     std::ofstream(dump + ".pano.s16", std::ios::binary).write((const char*)pano.data(), pano.size() * 2);
     std::ofstream(dump + ".mask.u8", std::ios::binary).write((const char*)mask.data(), mask.size());
     std::ofstream t(dump + ".txt");
-    t << pw << " " << ph << " " << bands << "\n";
-    for (int i : indices) t << i << " ";
+    t << pw << " " << ph << " " << out.num_bands << "\n";
+    for (int i : out.indices) t << i << " ";
     t << "\n";
-    for (int v : nfeat) t << v << " ";
+    for (int v : out.num_features) t << v << " ";
     t << "\n";
     t.precision(17);
-    for (double c : conf) t << c << " ";
+    for (double c : out.confidence) t << c << " ";
     t << "\n";
+    return 0;
+}
+
+// synthetic frames `ids` straight into HBM (rows of 3 W bytes, as bench.py's torch tensors)
+static int render_frames(const std::vector<SyCamera>& sy, const std::vector<int>& ids, int W, int H, std::vector<MisImage>* frames) {
+    for (int i : ids) {
+        void* p = nullptr;
+        HIPCHK(hipMalloc(&p, (size_t)W * H * 3));
+        if (synth_render_frame_gpu(&sy[i], p, (size_t)W * 3, nullptr) != 0) { std::fprintf(stderr, "render failed\n"); return 1; }
+        frames->push_back(MisImage{p, W, H, 3, (size_t)W * 3, MIS_U8, MIS_MEM_DEVICE});
+    }
+    HIPCHK(hipDeviceSynchronize());
+    return 0;
+}
+
+// the warm-up steps, then the timed ones (*dt: their wall time); `settle` runs once the job and the device are idle after each loop
+template <class Job>
+static int run_steps(const Args& a, Job& job, const std::vector<MisImage>& frames, const std::function<void()>& settle, mis::JobOutput* out, double* dt) {
+    for (int i = 0; i < a.warmup; i++) *out = job.run(frames);
+    job.synchronize();
+    HIPCHK(hipDeviceSynchronize());
+    settle();
+    const double t0 = now();
+    for (int i = 0; i < a.steps; i++) *out = job.run(frames);
+    job.synchronize();
+    HIPCHK(hipDeviceSynchronize());
+    settle();
+    *dt = now() - t0;
     return 0;
 }
 
@@ -90,25 +119,14 @@ static int run_single(const Args& a) {
     if (!read_cams(a.cams_path, &n, &W, &H, &sy, &cams)) return 2;
     try {
         mis::StitchJob job(0, W, H, cams);
-        // synthetic frames straight into HBM (rows of 3 W bytes, as bench.py's torch tensors)
-        std::vector<MisImage> frames(n);
-        for (int i = 0; i < n; i++) {
-            void* p = nullptr;
-            HIPCHK(hipMalloc(&p, (size_t)W * H * 3));
-            if (synth_render_frame_gpu(&sy[i], p, (size_t)W * 3, nullptr) != 0) { std::fprintf(stderr, "render failed\n"); return 1; }
-            frames[i] = MisImage{p, W, H, 3, (size_t)W * 3, MIS_U8, MIS_MEM_DEVICE};
-        }
-        HIPCHK(hipDeviceSynchronize());
+        std::vector<int> everyone(n);
+        for (int i = 0; i < n; i++) everyone[i] = i;
+        std::vector<MisImage> frames;
+        if (render_frames(sy, everyone, W, H, &frames)) return 1;
         mis::JobOutput out;
-        for (int i = 0; i < a.warmup; i++) out = job.run(frames);
-        job.synchronize();
-        HIPCHK(hipDeviceSynchronize());
-        const double t0 = now();
-        for (int i = 0; i < a.steps; i++) out = job.run(frames);
-        job.synchronize();
-        HIPCHK(hipDeviceSynchronize());
-        const double dt = now() - t0;
-        if (!a.dump.empty() && write_dump(a.dump, out.pano, out.mask, out.pano_width, out.pano_height, out.num_bands, out.indices, out.num_features, out.confidence)) return 1;
+        double dt = 0;
+        if (run_steps(a, job, frames, [] {}, &out, &dt)) return 1;
+        if (!a.dump.empty() && write_dump(a.dump, out)) return 1;
         std::printf("{\"host\": \"c++ (host/stitch_bench: mis::StitchJob over the C ABI)\", \"metric\": \"4K frames stitched/sec\", \"value\": %.3f, \"unit\": \"frames/s\", "
                     "\"n_gpus\": 1, \"steps\": %d, \"warmup\": %d, \"ms_per_step\": %.3f, \"frames\": %d, \"frame_size\": [%d, %d], \"pano_size\": [%d, %d], "
                     "\"num_bands\": %d, \"kept\": %d, \"speculation_kept\": %s}\n",
@@ -134,29 +152,15 @@ static int run_rank(const Args& a, int rank) {
         std::unique_ptr<mis::Communicator> comm = a.comm == "host" ? mis::make_host_comm(a.session, rank, a.ranks) : mis::make_rccl_comm(a.session, rank, a.ranks);
         mis::ShardedJob job(device, W, H, cams, *comm);
         std::vector<MisImage> frames;
-        for (int i : job.my_frames()) {
-            void* p = nullptr;
-            HIPCHK(hipMalloc(&p, (size_t)W * H * 3));
-            if (synth_render_frame_gpu(&sy[i], p, (size_t)W * 3, nullptr) != 0) { std::fprintf(stderr, "render failed\n"); return 1; }
-            frames.push_back(MisImage{p, W, H, 3, (size_t)W * 3, MIS_U8, MIS_MEM_DEVICE});
-        }
-        HIPCHK(hipDeviceSynchronize());
-        mis::ShardedOutput out;
-        for (int i = 0; i < a.warmup; i++) out = job.run(frames);
-        job.synchronize();
-        HIPCHK(hipDeviceSynchronize());
-        comm->barrier();
-        const double t0 = now();
-        for (int i = 0; i < a.steps; i++) out = job.run(frames);
-        job.synchronize();
-        HIPCHK(hipDeviceSynchronize());
-        comm->barrier();
-        double dt = now() - t0;
+        if (render_frames(sy, job.my_frames(), W, H, &frames)) return 1;
+        mis::JobOutput out;
+        double dt = 0;
+        if (run_steps(a, job, frames, [&] { comm->barrier(); }, &out, &dt)) return 1;
         std::vector<double> all(a.ranks);
         comm->all_gather_host(&dt, all.data(), sizeof(double));
         for (double v : all) dt = std::max(dt, v);      // the slowest rank's clock
         if (rank == 0) {
-            if (!a.dump.empty() && write_dump(a.dump, out.pano, out.mask, out.pano_width, out.pano_height, out.num_bands, out.indices, out.num_features, out.confidence)) return 1;
+            if (!a.dump.empty() && write_dump(a.dump, out)) return 1;
             std::printf("{\"host\": \"c++ (host/stitch_bench: mis::ShardedJob, %d rank%s, %s)\", \"metric\": \"4K frames stitched/sec\", \"value\": %.3f, \"unit\": \"frames/s\", "
                         "\"n_gpus\": %d, \"one_gpu_rehearsal\": %s, \"steps\": %d, \"warmup\": %d, \"ms_per_step\": %.3f, \"frames\": %d, \"frame_size\": [%d, %d], \"pano_size\": [%d, %d], "
                         "\"num_bands\": %d, \"kept\": %d, \"speculation_kept\": %s}\n",
@@ -189,6 +193,8 @@ static int launch(const Args& a, int argc, char** argv) {
         cav.push_back(nullptr);
         if (posix_spawn(&pids[r], "/proc/self/exe", nullptr, nullptr, cav.data(), environ) != 0) { std::fprintf(stderr, "cannot start rank %d\n", r); pids[r] = -1; rc = 1; }
     }
+    // a rank that could not start: the ones already started would wait at the rendezvous until their own limit (reaped below)
+    if (rc != 0) for (pid_t q : pids) if (q > 0) kill(q, SIGKILL);
     int left = 0;
     for (pid_t p : pids) left += p > 0;
     while (left > 0) {
