@@ -1252,7 +1252,8 @@ extern "C" int mis_blend_config(int blend_type, float blend_strength, int pano_w
     float blend_width = sqrtf((float)(pano_w * pano_h)) * blend_strength / 100.f;
     *num_bands = 0; *sharpness = 0.f; *type_out = blend_type;
     if (blend_width < 1.f) *type_out = MIS_BLEND_NO;
-    else if (blend_type == MIS_BLEND_MULTI_BAND) *num_bands = (int)(ceil(log((double)blend_width) / log(2.)) - 1.);
+    // log() of the float blend_width is the float overload (logf); only the division is in double
+    else if (blend_type == MIS_BLEND_MULTI_BAND) *num_bands = (int)(ceil(logf(blend_width) / log(2.)) - 1.);
     else if (blend_type == MIS_BLEND_FEATHER) *sharpness = 1.f / blend_width;
     return MIS_OK;
 }

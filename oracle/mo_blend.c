@@ -28,7 +28,8 @@ int mo_blend_config(int blend_type, float blend_strength, int pano_w, int pano_h
     float blend_width = sqrtf((float)(pano_w * pano_h)) * blend_strength / 100.f;
     *num_bands = 0; *sharpness = 0.f;
     if (blend_width < 1.f) return MO_BLEND_NO;
-    if (blend_type == MO_BLEND_MULTI_BAND) *num_bands = (int)(ceil(log((double)blend_width) / log(2.)) - 1.);
+    /* log() of the float blend_width is the float overload (logf); only the division is in double */
+    if (blend_type == MO_BLEND_MULTI_BAND) *num_bands = (int)(ceil(logf(blend_width) / log(2.)) - 1.);
     else if (blend_type == MO_BLEND_FEATHER) *sharpness = 1.f / blend_width;
     return blend_type;
 }
