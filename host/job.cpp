@@ -26,7 +26,7 @@ JobOutput StitchJob::run(const std::vector<MisImage>& frames) {
     check(cctx_, mis_context_wait(cctx_, ctx_), "mis_context_wait");
     // sizing + zeroing of the panorama pyramids depends on the cameras only: it runs from the finder's hook, once the feature batch is
     // enqueued (warpRoi ends in a synchronisation of the compose stream: in front of the features it kept the main stream idle)
-    prep_.arm([this] { prepare(everyone_); });
+    prep_.arm([this] { if (spec_ok_) prepare(everyone_); });
     check(ctx_, mis_orb_on_enqueued(orb_, &Hook::fire, &prep_), "mis_orb_on_enqueued");
     // ---- features (:567-622) ----
     std::vector<MisFeatures> feats(n_);
@@ -39,6 +39,7 @@ JobOutput StitchJob::run(const std::vector<MisImage>& frames) {
     // ---- matching (:647-653) with the speculative composition (all frames) enqueued from its hook ----
     const MisMatchParams mp = reset_matches();
     match_.arm([this, &frames] {
+        if (!spec_ok_) return;      // a refused all-frames roi: the kept set is composed after the pruning
         fence_knn();
         compose(frames, everyone_, everyone_);
         finalize();
@@ -58,9 +59,9 @@ JobOutput StitchJob::run(const std::vector<MisImage>& frames) {
     idx.resize(kept);
     if (kept < 2) throw std::runtime_error("Need more images");
     out.indices = idx;
-    out.speculation_kept = kept == n_;
+    out.speculation_kept = spec_ok_ && kept == n_;
     if (!out.speculation_kept) {
-        // a frame was dropped: the panorama of the kept set (its own scale, roi and band count) replaces the speculated one
+        // a frame was dropped (or nothing was speculated): the panorama of the kept set (its own scale, roi and band count) replaces the speculated one
         prepare(idx);
         compose(frames, everyone_, idx);
         finalize();

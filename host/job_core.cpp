@@ -41,6 +41,7 @@ JobCore::JobCore(const char* who, std::string where, int device, void* main_stre
     try {
         if (cfg_.features_type != "orb" || cfg_.ba_cost_func != "no" || cfg_.expos_comp_type != "no" || cfg_.seam_find_type != "no")
             throw std::runtime_error(std::string(who) + " runs the hot path (ORB, supplied cameras, no seam-scale step); use mis::Stitcher for the other options");
+        kind_ = warp_kind(cfg_.warp_type);
         if (mis_context_create(device, mstream_, &ctx_) != MIS_OK) throw std::runtime_error("mis_context_create failed: no HIP device (there is no CPU fallback)");
         check(ctx_, mis_stream_create(device, 0, &cstream_), "mis_stream_create");
         if (mis_context_create(device, cstream_, &cctx_) != MIS_OK) throw std::runtime_error("mis_context_create (compose stream) failed");
@@ -56,6 +57,14 @@ JobCore::JobCore(const char* who, std::string where, int device, void* main_stre
         const Mat3<float> K = cams_[i].K().cast<float>(), R = cams_[i].R.cast<float>();
         std::copy(K.m.begin(), K.m.end(), Ks_.begin() + 9 * i);
         std::copy(R.m.begin(), R.m.end(), Rs_.begin() + 9 * i);
+    }
+    // A plane warp refuses the roi of a frame turned behind the panorama plane, even one the pruning will drop: when the all-frames
+    // rois fail, the jobs compose the kept set after pruning instead of speculating (only a refused roi among the kept frames is an
+    // error).  Cameras only, so it is decided here; the spherical roi is never refused.
+    if (kind_ != MIS_WARP_SPHERICAL) {
+        const float scale = median_focal(cams_, everyone_);
+        MisRect r;
+        for (int i = 0; i < n_ && spec_ok_; i++) spec_ok_ = mis_warper_roi(kind_, scale, w_, h_, &Ks_[9 * i], &Rs_[9 * i], &r) == MIS_OK;
     }
 }
 
@@ -88,7 +97,7 @@ JobCore::Compose JobCore::prepare(const std::vector<int>& idx) {
         std::copy(Rs_.begin() + 9 * idx[k], Rs_.begin() + 9 * idx[k] + 9, Rs.begin() + 9 * k);
     }
     rois_.assign(m, MisRect{});
-    check(cctx_, mis_warp_roi_batch(cctx_, scale, w_, h_, m, Ks.data(), Rs.data(), rois_.data()), "mis_warp_roi_batch");
+    check(cctx_, mis_warper_roi_batch(cctx_, kind_, scale, w_, h_, m, Ks.data(), Rs.data(), rois_.data()), "mis_warper_roi_batch");
     std::vector<MisPoint> corners(m);
     std::vector<MisSize> sizes(m);
     for (int k = 0; k < m; k++) { corners[k] = {rois_[k].x, rois_[k].y}; sizes[k] = {rois_[k].width, rois_[k].height}; }
@@ -122,7 +131,8 @@ void JobCore::compose(const std::vector<MisImage>& frames, const std::vector<int
         rois.push_back(rois_[it - idx.begin()]);
     }
     if (fr.empty()) return;     // every frame of a rank was pruned: nothing to warp or feed (the exchanges around still run)
-    check(cctx_, mis_compose_frames(blender_, fr.data(), (int)fr.size(), median_focal(cams_, idx), Ks.data(), Rs.data(), rois.data()), "mis_compose_frames");
+    check(cctx_, mis_compose_frames_kind(blender_, kind_, fr.data(), (int)fr.size(), median_focal(cams_, idx), Ks.data(), Rs.data(), rois.data()),
+          "mis_compose_frames_kind");
 }
 
 MisMatchParams JobCore::reset_matches() {

@@ -66,6 +66,8 @@ protected:
     std::vector<CameraParams> cams_;
     StitchConfig cfg_;
     std::vector<int> everyone_;       // 0 .. n-1
+    int kind_ = MIS_WARP_SPHERICAL;   // the warper (cfg_.warp_type)
+    bool spec_ok_ = true;             // warpRoi of ALL frames succeeds: the composition may be speculated (see JobCore::JobCore)
     void* mstream_ = nullptr;         // main stream (nullptr: the null stream): features, matcher, the feature all-gather
     void* cstream_ = nullptr;         // compose stream: warp, feed, blend (and the sharded job's blend exchange)
     MisContext* ctx_ = nullptr;

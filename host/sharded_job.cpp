@@ -160,7 +160,7 @@ JobOutput ShardedJob::run(const std::vector<MisImage>& frames) {
     JobOutput out;
     check(cctx_, mis_context_wait(cctx_, ctx_), "mis_context_wait");
     // ---- features of this rank's block (:567-622); the blender is sized from the finder's hook (cameras only) ----
-    prep_.arm([this] { prepare_multi_band(everyone_); });
+    prep_.arm([this] { if (spec_ok_) prepare_multi_band(everyone_); });
     check(ctx_, mis_orb_on_enqueued(orb_, &Hook::fire, &prep_), "mis_orb_on_enqueued");
     std::vector<MisFeatures> local(m);
     std::memset(local.data(), 0, sizeof(MisFeatures) * m);
@@ -190,6 +190,7 @@ JobOutput ShardedJob::run(const std::vector<MisImage>& frames) {
     // ---- this rank's pairs (:647-653), its composition speculated from the matcher's hook ----
     const MisMatchParams mp = reset_matches();
     match_.arm([this, &frames] {
+        if (!spec_ok_) return;      // a refused all-frames roi: the kept set is composed after the pruning
         fence_knn();
         compose(frames, mine_, everyone_);
     });
@@ -209,8 +210,8 @@ JobOutput ShardedJob::run(const std::vector<MisImage>& frames) {
     idx.resize(kept);
     if (kept < 2) throw std::runtime_error("Need more images");
     out.indices = idx;
-    out.speculation_kept = kept == n_;
-    if (!out.speculation_kept) {       // a frame was dropped: the kept set's own scale, roi and band count
+    out.speculation_kept = spec_ok_ && kept == n_;
+    if (!out.speculation_kept) {       // a frame was dropped (or nothing was speculated): the kept set's own scale, roi and band count
         prepare_multi_band(idx);
         compose(frames, mine_, idx);
     }

@@ -84,6 +84,7 @@ StitchResult Stitcher::stitch(const std::vector<HostImage>& frames, const std::v
         throw std::runtime_error("exposure compensation '" + cfg_.expos_comp_type + "' is not implemented (only 'no' and 'gain_blocks')");
     if (cfg_.seam_find_type != "no" && cfg_.seam_find_type != "voronoi" && cfg_.seam_find_type != "dp_color")
         throw std::runtime_error("seam finder '" + cfg_.seam_find_type + "' is not implemented ('no', 'voronoi' and 'dp_color' are)");
+    const int kind = warp_kind(cfg_.warp_type);
     MisOrb* orb = nullptr;
     MisSift* sift = nullptr;
     std::vector<MisFeatures> features(n);
@@ -187,7 +188,8 @@ StitchResult Stitcher::stitch(const std::vector<HostImage>& frames, const std::v
         std::copy(R.m.begin(), R.m.end(), Rs[k].begin());
         std::copy(cK.m.begin(), cK.m.end(), cKs[k].begin());
         MisRect roi;
-        mis_warp_roi(compose_warp_scale, cW, cH, cKs[k].data(), Rs[k].data(), &roi);
+        if (mis_warper_roi(kind, compose_warp_scale, cW, cH, cKs[k].data(), Rs[k].data(), &roi) != MIS_OK)
+            throw std::runtime_error("mis_warper_roi failed: frame " + std::to_string(out.indices[k]) + " has no " + cfg_.warp_type + " warp roi");
         corners[k] = {roi.x, roi.y};
         sizes[k] = {roi.width, roi.height};
     }
@@ -217,13 +219,13 @@ StitchResult Stitcher::stitch(const std::vector<HostImage>& frames, const std::v
             else img = full;
             std::array<float, 9> Ks_ = Ks[k];
             Ks_[0] *= swa; Ks_[2] *= swa; Ks_[4] *= swa; Ks_[5] *= swa;
-            check(mis_warp_spherical(ctx_, &img, seam_warp_scale, Ks_.data(), Rs[k].data(), MIS_INTER_LINEAR, MIS_BORDER_REFLECT, &images_warped[k], &seam_corners[k]),
-                  "mis_warp_spherical (seam scale)");
+            check(mis_warper_warp(ctx_, kind, &img, seam_warp_scale, Ks_.data(), Rs[k].data(), MIS_INTER_LINEAR, MIS_BORDER_REFLECT, &images_warped[k], &seam_corners[k]),
+                  "mis_warper_warp (seam scale)");
             std::vector<uint8_t> ones((size_t)img.width * img.height, 255);
             MisImage m{ones.data(), img.width, img.height, 1, (size_t)img.width, MIS_U8, MIS_MEM_HOST};
             MisPoint tl;
-            check(mis_warp_spherical(ctx_, &m, seam_warp_scale, Ks_.data(), Rs[k].data(), MIS_INTER_NEAREST, MIS_BORDER_CONSTANT, &masks_warped[k], &tl),
-                  "mis_warp_spherical (seam-scale mask)");
+            check(mis_warper_warp(ctx_, kind, &m, seam_warp_scale, Ks_.data(), Rs[k].data(), MIS_INTER_NEAREST, MIS_BORDER_CONSTANT, &masks_warped[k], &tl),
+                  "mis_warper_warp (seam-scale mask)");
             if (seam_scale < 1.0) mis_image_free(ctx_, &img);
         }
         if (cfg_.expos_comp_type == "gain_blocks") {
@@ -241,7 +243,7 @@ StitchResult Stitcher::stitch(const std::vector<HostImage>& frames, const std::v
         if (compose_resized) check(mis_resize_linear_exact(ctx_, &full, 0, 0, compose_scale, compose_scale, &src), "mis_resize_linear_exact (compose scale)");
         else src = full;
         MisPoint tl;
-        check(mis_warp_spherical_fused(ctx_, &src, compose_warp_scale, cKs[k].data(), Rs[k].data(), &img_warped_s, &mask_warped, &tl), "mis_warp_spherical_fused");
+        check(mis_warper_warp_fused(ctx_, kind, &src, compose_warp_scale, cKs[k].data(), Rs[k].data(), &img_warped_s, &mask_warped, &tl), "mis_warper_warp_fused");
         if (compose_resized) mis_image_free(ctx_, &src);
         if (compensator) check(mis_compensator_apply(compensator, k, &img_warped_s), "mis_compensator_apply");   // :1162
         if (seam_step) {

@@ -30,7 +30,22 @@ struct StitchConfig {
     // image_stitching_amd.StitchConfig.hot_path() -- pass "gain_blocks" / "dp_color" for the reference's configuration.
     std::string expos_comp_type = "no";    // "no" | "gain_blocks" (64 x 64 blocks, 1 feed, 2 filtering passes)
     std::string seam_find_type = "no";     // "no" | "voronoi" | "dp_color" (the reference's default; this driver's default is the hot path)
+    // warper (:917-969): the three of the reference's GPU branch are built; its other names throw by name (warp_kind)
+    std::string warp_type = "spherical";   // "spherical" | "cylindrical" | "plane"
 };
+
+// warp_type -> MIS_WARP_*; the reference's other warpers (:933-964) are not implemented, anything else is not a warper at all
+inline int warp_kind(const std::string& t) {
+    if (t == "spherical") return MIS_WARP_SPHERICAL;
+    if (t == "cylindrical") return MIS_WARP_CYLINDRICAL;
+    if (t == "plane") return MIS_WARP_PLANE;
+    static const char* unbuilt[] = {"affine", "fisheye", "stereographic", "compressedPlaneA2B1", "compressedPlaneA1.5B1", "compressedPlanePortraitA2B1",
+                                    "compressedPlanePortraitA1.5B1", "paniniA2B1", "paniniA1.5B1", "paniniPortraitA2B1", "paniniPortraitA1.5B1",
+                                    "mercator", "transverseMercator"};
+    for (const char* u : unbuilt)
+        if (t == u) throw std::runtime_error("warper '" + t + "' is not implemented ('spherical', 'cylindrical' and 'plane' are)");
+    throw std::runtime_error("Can't create the following warper '" + t + "'");
+}
 
 // cv::detail::CameraParams as main() fills it (focal, aspect, ppx, ppy, R, t)
 struct CameraParams {

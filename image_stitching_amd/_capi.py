@@ -19,6 +19,7 @@ U8, S16, F32 = 0, 1, 2
 INTER_NEAREST, INTER_LINEAR = 0, 1
 BORDER_CONSTANT, BORDER_REFLECT = 0, 2
 BLEND_NO, BLEND_FEATHER, BLEND_MULTI_BAND = 0, 1, 2
+WARP_SPHERICAL, WARP_CYLINDRICAL, WARP_PLANE = 0, 1, 2
 
 
 class MisPoint(C.Structure):
@@ -134,6 +135,12 @@ PROTOTYPES = {
     "mis_warp_spherical_fused_batch": (_i, [_vp, _P(MisImage), _i, C.c_float, _P(C.c_float), _P(C.c_float), _P(MisRect), _P(MisImage), _P(MisImage), _P(MisPoint)]),
     "mis_warp_spherical_fused_batch_timed": (_i, [_vp, _P(MisImage), _i, C.c_float, _P(C.c_float), _P(C.c_float), _P(MisRect), _P(MisImage), _P(MisImage), _P(MisPoint), _i,
                                                _P(C.c_float)]),
+    "mis_warper_roi": (_i, [_i, _f, _i, _i, _vp, _vp, _P(MisRect)]),
+    "mis_warper_roi_batch": (_i, [_vp, _i, _f, _i, _i, _i, _vp, _vp, _P(MisRect)]),
+    "mis_warper_warp": (_i, [_vp, _i, _P(MisImage), _f, _vp, _vp, _i, _i, _P(MisImage), _P(MisPoint)]),
+    "mis_warper_warp_fused": (_i, [_vp, _i, _P(MisImage), _f, _vp, _vp, _P(MisImage), _P(MisImage), _P(MisPoint)]),
+    "mis_warper_warp_fused_roi": (_i, [_vp, _i, _P(MisImage), _f, _vp, _vp, _P(MisRect), _P(MisImage), _P(MisImage), _P(MisPoint)]),
+    "mis_warper_warp_fused_batch": (_i, [_vp, _i, _P(MisImage), _i, C.c_float, _P(C.c_float), _P(C.c_float), _P(MisRect), _P(MisImage), _P(MisImage), _P(MisPoint)]),
     "mis_warp_spherical_fused": (_i, [_vp, _P(MisImage), _f, _vp, _vp, _P(MisImage), _P(MisImage), _P(MisPoint)]),
     "mis_resize_linear_exact": (_i, [_vp, _P(MisImage), _i, _i, C.c_double, C.c_double, _P(MisImage)]),
     "mis_rotate": (_i, [_vp, _P(MisImage), _i, _P(MisImage)]),
@@ -156,6 +163,7 @@ PROTOTYPES = {
     "mis_blender_feed_batch": (_i, [_vp, _P(MisImage), _P(MisImage), _P(MisPoint), _i]),
     "mis_blender_blend": (_i, [_vp, _P(MisImage), _P(MisImage)]),
     "mis_compose_frames": (_i, [_vp, _P(MisImage), _i, _f, _vp, _vp, _P(MisRect)]),
+    "mis_compose_frames_kind": (_i, [_vp, _i, _P(MisImage), _i, _f, _vp, _vp, _P(MisRect)]),
     "mis_blender_blend_columns": (_i, [_vp, _i, _i, _P(MisImage), _P(MisImage)]),
     "mis_blender_pack_rects": (_i, [_vp, _P(MisLevelRect), _i, _vp, C.c_size_t]),
     "mis_blender_add_rects": (_i, [_vp, _P(MisLevelRect), _i, _vp, C.c_size_t]),

@@ -1401,9 +1401,11 @@ extern "C" int mis_blender_feed_batch(MisBlender* b, const MisImage* imgs, const
 // The compositing loop of main() for n frames in one call (image_stitching.cpp:1154-1164 + :1218 per frame): fused warp
 // into recycled device blocks, feed, next frame.  One library call instead of 2 n keeps a host thread that drives the
 // composition (e.g. concurrently with the matcher) out of the interpreter between launches.
-extern "C" int mis_compose_frames(MisBlender* b, const MisImage* frames, int n, float scale, const float* Ks, const float* Rs, const MisRect* rois) {
+extern "C" int mis_compose_frames_kind(MisBlender* b, int kind, const MisImage* frames, int n, float scale, const float* Ks, const float* Rs,
+                                       const MisRect* rois) {
     if (!b) return MIS_E_INVALID;
     MisContext* ctx = b->ctx;
+    MIS_CHECK(ctx, kind == MIS_WARP_SPHERICAL || kind == MIS_WARP_CYLINDRICAL || kind == MIS_WARP_PLANE, MIS_E_UNSUPPORTED, "unknown warp kind %d", kind);
     MIS_CHECK(ctx, b->prepared, MIS_E_STATE, "compose before prepare");
     MIS_CHECK(ctx, frames && Ks && Rs && rois && n >= 0, MIS_E_INVALID, "null argument");
     MIS_HIP(ctx, hipSetDevice(ctx->device));
@@ -1423,10 +1425,14 @@ extern "C" int mis_compose_frames(MisBlender* b, const MisImage* frames, int n, 
         imgs[i] = MisImage{blk, r.width, r.height, 3, ipitch, MIS_S16, MIS_MEM_DEVICE};
         msks[i] = MisImage{(uint8_t*)blk + ibytes, r.width, r.height, 1, mpitch, MIS_U8, MIS_MEM_DEVICE};
     }
-    if (rc == MIS_OK && n > 0) rc = mis_warp_spherical_fused_batch(ctx, frames, n, scale, Ks, Rs, rois, imgs.data(), msks.data(), tls.data());
+    if (rc == MIS_OK && n > 0) rc = mis_warper_warp_fused_batch(ctx, kind, frames, n, scale, Ks, Rs, rois, imgs.data(), msks.data(), tls.data());
     if (rc == MIS_OK) rc = mis_blender_feed_batch(b, imgs.data(), msks.data(), tls.data(), n);
     for (auto& bl : blocks) mis_pool_free(ctx, bl.first, bl.second);   // stream-ordered reuse
     return rc;
+}
+
+extern "C" int mis_compose_frames(MisBlender* b, const MisImage* frames, int n, float scale, const float* Ks, const float* Rs, const MisRect* rois) {
+    return mis_compose_frames_kind(b, MIS_WARP_SPHERICAL, frames, n, scale, Ks, Rs, rois);
 }
 
 // blend() restricted to the panorama columns x0 .. x1 - 1 (level 0, relative to the padded roi): normalise + collapse run on

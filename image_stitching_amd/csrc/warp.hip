@@ -1,6 +1,10 @@
-// warp.hip -- spherical rotation warp, replaces the reference's
-// cv::detail::SphericalWarper calls: image_stitching/image_stitching.cpp:973/:1117 (create(scale)),
+// warp.hip -- rotation warps, replaces the reference's cv::detail::{Spherical,Cylindrical,Plane}Warper calls
+// (the warp_type switch of image_stitching/image_stitching.cpp:917-969): :973/:1117 (create(scale)),
 // :985/:988/:1154/:1159 (warp), :1138 (warpRoi), :1164 (convertTo CV_16S, fused here).
+// The three kinds share one per-pixel form: x_ = su * s, z_ = cu * s, y_ = c with a column table {su, cu} and a row table
+// {s, m1 c, m4 c, m7 c} (spherical: sin u', cos u' | sin(pi - v'), cos(pi - v'); cylindrical: sin u', cos u' | 1, v';
+// plane: u', 1 | 1, v').  The products by 1 are exact, so the float operations per pixel are OpenCV's for every kind; the
+// plane projector divides by z whatever its sign (a compile-time switch of the fused kernels).
 //
 // One pass per frame: the inverse map (mapBackward) is evaluated in registers -- OpenCV's xmap/ymap
 // (8 B per output pixel written and read back) never exist -- and the bilinear gather (INTER_BITS = 5
@@ -10,6 +14,7 @@
 #include "common.h"
 #include "dev_math.h"
 #include <algorithm>
+#include <climits>
 #include <vector>
 
 namespace {
@@ -17,12 +22,16 @@ namespace {
 struct Projector {
     float scale;
     float k[9], rinv[9], r_kinv[9], k_rinv[9];
+    int kind;   // MIS_WARP_*
 };
 
+static bool kind_ok(int kind) { return kind == MIS_WARP_SPHERICAL || kind == MIS_WARP_CYLINDRICAL || kind == MIS_WARP_PLANE; }
+
 // ProjectorBase::setCameraParams (stitching/src/warpers.cpp): float matrices, double intermediates
-void projector_set(Projector* p, float scale, const float K[9], const float R[9]) {
+void projector_set(Projector* p, int kind, float scale, const float K[9], const float R[9]) {
     double kinv[9], d;
     float kinv_f[9];
+    p->kind = kind;
     p->scale = scale;
     for (int i = 0; i < 9; i++) p->k[i] = K[i];
     for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) p->rinv[i * 3 + j] = R[j * 3 + i];
@@ -52,18 +61,36 @@ void projector_set(Projector* p, float scale, const float K[9], const float R[9]
         }
 }
 
-// SphericalProjector::mapForward (warpers_inl.hpp); the same float operations on the host and on the device
-MIS_HD void map_forward(const float* m, float scale, float x, float y, float* u, float* v) {
+// {Spherical,Cylindrical,Plane}Projector::mapForward (warpers_inl.hpp); the same float operations on the host and on the
+// device.  Returns z_ > 0 (the plane's corners must lie in front of the panorama plane).
+MIS_HD bool map_forward(int kind, const float* m, float scale, float x, float y, float* u, float* v) {
     float x_ = (m[0] * x + m[1] * y) + m[2];
     float y_ = (m[3] * x + m[4] * y) + m[5];
     float z_ = (m[6] * x + m[7] * y) + m[8];
-    *u = scale * mis_atan2f(x_, z_);
-    float w = y_ / sqrtf((x_ * x_ + y_ * y_) + z_ * z_);
-    *v = scale * (MIS_PI_F - mis_acosf(w == w ? w : 0));
+    if (kind == MIS_WARP_PLANE) {
+        *u = scale * (x_ / z_ * 1.f);
+        *v = scale * (y_ / z_ * 1.f);
+    } else if (kind == MIS_WARP_CYLINDRICAL) {
+        *u = scale * mis_atan2f(x_, z_);
+        *v = scale * y_ / sqrtf(x_ * x_ + z_ * z_);
+    } else {
+        *u = scale * mis_atan2f(x_, z_);
+        float w = y_ / sqrtf((x_ * x_ + y_ * y_) + z_ * z_);
+        *v = scale * (MIS_PI_F - mis_acosf(w == w ? w : 0));
+    }
+    return z_ > 0.f;
 }
 
-// SphericalWarper::detectResultRoi, second half: the float extremes of the border projection -> integer roi with the pole tests
-void roi_from_extremes(const Projector* p, int sw, int sh, float tl_uf, float tl_vf, float br_uf, float br_vf, int* tlx, int* tly, int* brx, int* bry) {
+// {Spherical,RotationWarperBase}::detectResultRoi, second half: the float extremes of the border projection -> integer roi, with
+// the pole tests for the spherical kind.  The other kinds refuse extremes that static_cast<int> cannot take (infinite or NaN:
+// OpenCV would return a meaningless rectangle) -> MIS_E_INVALID.
+int roi_from_extremes(const Projector* p, int sw, int sh, float tl_uf, float tl_vf, float br_uf, float br_vf, int* tlx, int* tly, int* brx, int* bry) {
+    if (p->kind != MIS_WARP_SPHERICAL) {
+        auto fits = [](float f) { return f > -2147483520.f && f < 2147483520.f; };      // false for NaN and +-inf
+        if (!(fits(tl_uf) && fits(tl_vf) && fits(br_uf) && fits(br_vf))) return MIS_E_INVALID;
+        *tlx = (int)tl_uf; *tly = (int)tl_vf; *brx = (int)br_uf; *bry = (int)br_vf;
+        return MIS_OK;
+    }
     tl_uf = (float)(int)tl_uf; tl_vf = (float)(int)tl_vf; br_uf = (float)(int)br_uf; br_vf = (float)(int)br_vf;
     for (int pass = 0; pass < 2; pass++) {
         float x = p->rinv[1], y = pass == 0 ? p->rinv[4] : -p->rinv[4], z = p->rinv[7];
@@ -80,11 +107,15 @@ void roi_from_extremes(const Projector* p, int sw, int sh, float tl_uf, float tl
         }
     }
     *tlx = (int)tl_uf; *tly = (int)tl_vf; *brx = (int)br_uf; *bry = (int)br_vf;
+    return MIS_OK;
 }
 
-// SphericalWarper::detectResultRoi: border projection + pole tests; 2(W+H) points on the host (single-call entry points;
-// a job's frames go through mis_warp_roi_batch: one small kernel for all of them).  Nothing is cached: every call pays it.
-void detect_result_roi(const Projector* p, int sw, int sh, int* tlx, int* tly, int* brx, int* bry) {
+// detectResultRoi on the host (single-call entry points; a job's frames go through mis_warper_roi_batch: one small kernel for all
+// of them).  Nothing is cached: every call pays it.
+//  * spherical (SphericalWarper::detectResultRoi) and cylindrical (detectResultRoiByBorder): the 2(W+H) border pixels;
+//  * plane (PlaneWarper::detectResultRoi): the four corners (0,0), (0,h-1), (w-1,0), (w-1,h-1).  A corner with z_ <= 0 lies behind
+//    the panorama plane and OpenCV's rectangle means nothing: MIS_E_INVALID.
+int detect_result_roi(const Projector* p, int sw, int sh, int* tlx, int* tly, int* brx, int* bry) {
     float tl_uf = FLT_MAX, tl_vf = FLT_MAX, br_uf = -FLT_MAX, br_vf = -FLT_MAX, u, v;
     auto upd = [&]() {
         if (u < tl_uf) tl_uf = u;
@@ -92,43 +123,67 @@ void detect_result_roi(const Projector* p, int sw, int sh, int* tlx, int* tly, i
         if (u > br_uf) br_uf = u;
         if (v > br_vf) br_vf = v;
     };
-    for (int x = 0; x < sw; ++x) {
-        map_forward(p->r_kinv, p->scale, (float)x, 0, &u, &v); upd();
-        map_forward(p->r_kinv, p->scale, (float)x, (float)(sh - 1), &u, &v); upd();
+    const int kind = p->kind;
+    if (kind == MIS_WARP_PLANE) {
+        const float cx[4] = {0.f, 0.f, (float)(sw - 1), (float)(sw - 1)}, cy[4] = {0.f, (float)(sh - 1), 0.f, (float)(sh - 1)};
+        bool front = true;
+        for (int c = 0; c < 4; c++) { front &= map_forward(kind, p->r_kinv, p->scale, cx[c], cy[c], &u, &v); upd(); }
+        if (!front) return MIS_E_INVALID;
+    } else {
+        for (int x = 0; x < sw; ++x) {
+            map_forward(kind, p->r_kinv, p->scale, (float)x, 0, &u, &v); upd();
+            map_forward(kind, p->r_kinv, p->scale, (float)x, (float)(sh - 1), &u, &v); upd();
+        }
+        for (int y = 0; y < sh; ++y) {
+            map_forward(kind, p->r_kinv, p->scale, 0, (float)y, &u, &v); upd();
+            map_forward(kind, p->r_kinv, p->scale, (float)(sw - 1), (float)y, &u, &v); upd();
+        }
     }
-    for (int y = 0; y < sh; ++y) {
-        map_forward(p->r_kinv, p->scale, 0, (float)y, &u, &v); upd();
-        map_forward(p->r_kinv, p->scale, (float)(sw - 1), (float)y, &u, &v); upd();
-    }
-    roi_from_extremes(p, sw, sh, tl_uf, tl_vf, br_uf, br_vf, tlx, tly, brx, bry);
+    return roi_from_extremes(p, sw, sh, tl_uf, tl_vf, br_uf, br_vf, tlx, tly, brx, bry);
 }
 
-void projector_and_roi(float scale, const float K[9], const float R[9], int w, int h, Projector* p, int* tlx, int* tly, int* brx, int* bry) {
-    projector_set(p, scale, K, R);
-    detect_result_roi(p, w, h, tlx, tly, brx, bry);
+// the (x, y, width, height) rectangle of an inclusive roi; its size in 64 bits: a width or height past INT_MAX (extremes on either
+// side of +-2^30, e.g. a plane corner just in front of the panorama plane) is refused rather than wrapped -> MIS_E_INVALID
+int roi_rect(int tlx, int tly, int brx, int bry, MisRect* r) {
+    const long long w = (long long)brx + 1 - tlx, h = (long long)bry + 1 - tly;
+    if (w < 1 || h < 1 || w > INT_MAX || h > INT_MAX) return MIS_E_INVALID;
+    r->x = tlx; r->y = tly; r->width = (int)w; r->height = (int)h;
+    return MIS_OK;
+}
+
+int projector_and_roi(int kind, float scale, const float K[9], const float R[9], int w, int h, Projector* p, int* tlx, int* tly, int* brx, int* bry) {
+    projector_set(p, kind, scale, K, R);
+    return detect_result_roi(p, w, h, tlx, tly, brx, bry);
 }
 
 // The border walk of detectResultRoi for a whole job: workgroup f projects the 2(W+H) border pixels of frame f and reduces
 // the four extremes (min / max of finite floats: any order gives the host loop's result).  Jobs and results live in pinned,
 // device-visible host memory: one launch + one stream synchronisation for all frames of a panorama.
+// (The plane kind: threads 0..3 project the four corners, and `behind` reports a corner with z_ <= 0.)
 struct RoiJob {
     float r_kinv[9], scale;
-    int sw, sh;
+    int sw, sh, kind;
+    int behind;     // out (plane): some corner lies behind the panorama plane
     float ext[4];   // out: min u, min v, max u, max v
 };
 __global__ __launch_bounds__(256) void warp_roi_kernel(RoiJob* jobs) {
     RoiJob* j = jobs + blockIdx.x;
     __shared__ float red[4][4];
+    __shared__ int behind;
     float m[9];
     for (int i = 0; i < 9; i++) m[i] = j->r_kinv[i];
     const float scale = j->scale;
-    const int sw = j->sw, sh = j->sh;
+    const int sw = j->sw, sh = j->sh, kind = j->kind;
+    if (threadIdx.x == 0) behind = 0;
+    __syncthreads();
     float lo_u = FLT_MAX, lo_v = FLT_MAX, hi_u = -FLT_MAX, hi_v = -FLT_MAX;
-    for (int i = threadIdx.x; i < 2 * (sw + sh); i += 256) {
+    const int npts = kind == MIS_WARP_PLANE ? 4 : 2 * (sw + sh);
+    for (int i = threadIdx.x; i < npts; i += 256) {
         float x, y, u, v;
-        if (i < 2 * sw) { x = (float)(i >> 1); y = (i & 1) ? (float)(sh - 1) : 0.f; }
+        if (kind == MIS_WARP_PLANE) { x = i < 2 ? 0.f : (float)(sw - 1); y = (i & 1) ? (float)(sh - 1) : 0.f; }
+        else if (i < 2 * sw) { x = (float)(i >> 1); y = (i & 1) ? (float)(sh - 1) : 0.f; }
         else { const int k = i - 2 * sw; y = (float)(k >> 1); x = (k & 1) ? (float)(sw - 1) : 0.f; }
-        map_forward(m, scale, x, y, &u, &v);
+        if (!map_forward(kind, m, scale, x, y, &u, &v) && kind == MIS_WARP_PLANE) behind = 1;
         lo_u = fminf(lo_u, u); lo_v = fminf(lo_v, v); hi_u = fmaxf(hi_u, u); hi_v = fmaxf(hi_v, v);
     }
     for (int o = 32; o > 0; o >>= 1) {
@@ -139,6 +194,7 @@ __global__ __launch_bounds__(256) void warp_roi_kernel(RoiJob* jobs) {
     if ((threadIdx.x & 63) == 0) { red[wave][0] = lo_u; red[wave][1] = lo_v; red[wave][2] = hi_u; red[wave][3] = hi_v; }
     __syncthreads();
     if (threadIdx.x == 0) {
+        j->behind = behind;
         j->ext[0] = fminf(fminf(red[0][0], red[1][0]), fminf(red[2][0], red[3][0]));
         j->ext[1] = fminf(fminf(red[0][1], red[1][1]), fminf(red[2][1], red[3][1]));
         j->ext[2] = fmaxf(fmaxf(red[0][2], red[1][2]), fmaxf(red[2][2], red[3][2]));
@@ -150,6 +206,7 @@ struct WarpArgs {
     float m[9];  // k_rinv
     float scale;
     int tlx, tly, dw, dh, sw, sh, cn;
+    int kind;        // MIS_WARP_* (read by the table fills and the u8 warp; in the padding before `src`: the layout is unchanged)
     const uint8_t* src;
     size_t sstride;
     void* dst;       // s16x3 (fused) or u8 x cn
@@ -160,14 +217,28 @@ struct WarpArgs {
 
 constexpr int TILE_W = 128, TILE_H = 16;
 
-// SphericalProjector::mapBackward with the separable trig pre-evaluated
-__device__ __forceinline__ void map_backward(const float* m, float sinu, float cosu, float sinv, float cosv, float* x, float* y) {
+// {Spherical,Cylindrical,Plane}Projector::mapBackward with the separable terms pre-evaluated (table_terms); the plane divides
+// by z whatever its sign
+__device__ __forceinline__ void map_backward(int kind, const float* m, float sinu, float cosu, float sinv, float cosv, float* x, float* y) {
     float x_ = sinv * sinu, y_ = cosv, z_ = sinv * cosu;
     float xx = (m[0] * x_ + m[1] * y_) + m[2] * z_;
     float yy = (m[3] * x_ + m[4] * y_) + m[5] * z_;
     float z = (m[6] * x_ + m[7] * y_) + m[8] * z_;
-    if (z > 0) { *x = xx / z; *y = yy / z; }
+    if (kind == MIS_WARP_PLANE || z > 0) { *x = xx / z; *y = yy / z; }
     else { *x = -1.f; *y = -1.f; }
+}
+
+// the separable terms of output column `col` ({su, cu}) and row `row` ({s, c}) of a warp kind (u' = u / scale, v' = v / scale):
+// spherical {sin u', cos u'} {sin(pi - v'), cos(pi - v')}; cylindrical {sin u', cos u'} {1, v'}; plane {u', 1} {1, v'}
+__device__ __forceinline__ void col_terms(int kind, float scale, int col, float* su, float* cu) {
+    const float u = (float)col / scale;
+    if (kind == MIS_WARP_PLANE) { *su = u; *cu = 1.f; }
+    else mis_sincosf(u, su, cu);
+}
+__device__ __forceinline__ void row_terms(int kind, float scale, int row, float* s, float* c) {
+    const float v = (float)row / scale;
+    if (kind == MIS_WARP_SPHERICAL) mis_sincosf(MIS_PI_F - v, s, c);
+    else { *s = 1.f; *c = v; }
 }
 
 // remap INTER_LINEAR, BORDER_REFLECT on u8: INTER_BITS = 5, Q15 weights, round at bit 14
@@ -198,13 +269,10 @@ __device__ __forceinline__ bool nearest_inside(int sw, int sh, float x, float y,
 
 __device__ __forceinline__ void tile_trig(const WarpArgs& a, int tx0, int ty0, float* su, float* cu, float* sv, float* cv) {
     int t = threadIdx.x;
-    if (t < TILE_W) {
-        float u = (float)(a.tlx + tx0 + t) / a.scale;
-        mis_sincosf(u, &su[t], &cu[t]);
-    } else if (t < TILE_W + TILE_H) {
+    if (t < TILE_W) col_terms(a.kind, a.scale, a.tlx + tx0 + t, &su[t], &cu[t]);
+    else if (t < TILE_W + TILE_H) {
         int r = t - TILE_W;
-        float v = (float)(a.tly + ty0 + r) / a.scale;
-        mis_sincosf(MIS_PI_F - v, &sv[r], &cv[r]);
+        row_terms(a.kind, a.scale, a.tly + ty0 + r, &sv[r], &cv[r]);
     }
     __syncthreads();
 }
@@ -239,18 +307,21 @@ typedef float v2f __attribute__((ext_vector_type(2)));
 __host__ __device__ __forceinline__ int trig_cols(int dw) { return (dw + 3) & ~1; }  // >= dw + 2, even: 16-byte aligned row table
 static size_t trig_table_floats(int dw, int dh) { return 2 * (size_t)trig_cols(dw) + 4 * (size_t)dh; }
 
-__global__ __launch_bounds__(256) void warp_trig_kernel(WarpArgs a, float* tab) {
-    const int i = blockIdx.x * 256 + threadIdx.x, ncol = trig_cols(a.dw);
-    if (i < ncol) {
-        float u = (float)(a.tlx + i) / a.scale;
-        mis_sincosf(u, &tab[2 * i], &tab[2 * i + 1]);
-    } else if (i < ncol + a.dh) {
+// entry i of a frame's tables: column i ({su, cu}) for i < ncol, else row i - ncol ({s, m1 c, m4 c, m7 c})
+__device__ __forceinline__ void trig_fill(const WarpArgs& a, float* tab, int i, int ncol) {
+    if (i < ncol) col_terms(a.kind, a.scale, a.tlx + i, &tab[2 * i], &tab[2 * i + 1]);
+    else if (i < ncol + a.dh) {
         const int r = i - ncol;
-        float v = (float)(a.tly + r) / a.scale, s, c;
-        mis_sincosf(MIS_PI_F - v, &s, &c);
+        float s, c;
+        row_terms(a.kind, a.scale, a.tly + r, &s, &c);
         float* t = tab + 2 * ncol + 4 * r;
         t[0] = s; t[1] = a.m[1] * c; t[2] = a.m[4] * c; t[3] = a.m[7] * c;
     }
+}
+
+__global__ __launch_bounds__(256) void warp_trig_kernel(WarpArgs a, float* tab) {
+    const int i = blockIdx.x * 256 + threadIdx.x, ncol = trig_cols(a.dw);
+    trig_fill(a, tab, i, ncol);
 }
 
 // cvRound(v) in [0, len): round-half-even maps [-0.5, len - 0.5) into range, and the upper end point
@@ -390,6 +461,8 @@ __device__ __forceinline__ void tile_trig(const WarpArgs& a, const float* __rest
     for (int i = 0; i < LROWS; i++) g.rt[i] = rowtab[min(gy0 + i, a.dh - 1)];  // rows past the roi shadow the last one
 }
 
+// ZTEST: the generic branch maps z <= 0 to (-1, -1) (spherical, cylindrical); without it every pixel divides (plane)
+template <bool ZTEST>
 __device__ __forceinline__ void tile_map(const WarpArgs& a, const TileTrig& g, int tx0, int ty0, int lane, TileState& t) {
     const int lx = lane & 15, ly = lane >> 4;
     const int gxr = tx0 + 2 * lx, gy0 = ty0 + LROWS * ly;
@@ -444,7 +517,7 @@ __device__ __forceinline__ void tile_map(const WarpArgs& a, const TileTrig& g, i
             map_terms(a.m, su, cu, g.rt[i], &xx, &yy, &zz);
 #pragma unroll
             for (int k = 0; k < 2; k++) {
-                const bool front = zz[k] > 0;
+                const bool front = !ZTEST || zz[k] > 0;
                 const float x = front ? xx[k] / zz[k] : -1.f, y = front ? yy[k] / zz[k] : -1.f;
                 const int xr = mis_round_sat_f(x * 32.f), yr = mis_round_sat_f(y * 32.f);
                 xq[2 * i + k] = (mis_sat_short(xr >> 5) << 5) | (xr & 31);
@@ -565,6 +638,7 @@ constexpr int TILE_WAVES = WV_TILE_WAVES;
 constexpr int CH_W = WV_CH_W, CH_H = WV_CH_H;   // chunk of tiles owned by one XCD (CH_W a multiple of TILE_WAVES)
 static_assert(CH_W % TILE_WAVES == 0, "chunk width must be a whole number of workgroups");
 // bid: the workgroup's index in the frame's grid
+template <bool ZTEST>
 __device__ __forceinline__ void warp_fused_body(const WarpArgs& a, const float* __restrict__ tab, int bid, uint8_t (*stage_all)[STAGE_BYTES]) {
     const int ntx = (a.dw + FT_W - 1) / FT_W, lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     uint8_t* stage = stage_all[wave];
@@ -589,7 +663,7 @@ __device__ __forceinline__ void warp_fused_body(const WarpArgs& a, const float* 
     tile_trig(a, tab, tx0, ty0, lane, trig);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     const unsigned long long s1 = __builtin_readcyclecounter();
-    tile_map(a, trig, tx0, ty0, lane, cur);
+    tile_map<ZTEST>(a, trig, tx0, ty0, lane, cur);
     const unsigned long long s2 = __builtin_readcyclecounter();
     tile_stage(a, cur, stage, lane);
     const unsigned long long s3 = __builtin_readcyclecounter();
@@ -604,16 +678,17 @@ __device__ __forceinline__ void warp_fused_body(const WarpArgs& a, const float* 
     }
 #else
     tile_trig(a, tab, tx0, ty0, lane, trig);
-    tile_map(a, trig, tx0, ty0, lane, cur);
+    tile_map<ZTEST>(a, trig, tx0, ty0, lane, cur);
     tile_stage(a, cur, stage, lane);                       // asynchronous global -> LDS copies ...
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // ... have landed
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     tile_sample_store(a, cur, stage, tx0, ty0, lane);
 #endif
 }
+template <bool ZTEST>
 __global__ __launch_bounds__(64 * TILE_WAVES) __attribute__((amdgpu_waves_per_eu(WV_WAVES_MIN, 8))) void warp_fused_kernel(WarpArgs a, const float* __restrict__ tab) {
     __shared__ __attribute__((aligned(16))) uint8_t stage_all[TILE_WAVES][STAGE_BYTES];
-    warp_fused_body(a, tab, (int)blockIdx.x, stage_all);
+    warp_fused_body<ZTEST>(a, tab, (int)blockIdx.x, stage_all);
 }
 // The frames of a compositing loop go out in ONE grid (warp_strip_batch_kernel below): a 4K frame is 2.8 generations of resident
 // workgroups, so a launch of its own spends a quarter of its time filling and draining the device (tools/warp_stamps.py: the last
@@ -629,16 +704,7 @@ __global__ __launch_bounds__(256) void warp_trig_batch_kernel(WarpBatch b) {
     const WarpArgs& a = b.a[f];
     float* tab = const_cast<float*>(b.tab[f]);
     const int i = blockIdx.x * 256 + threadIdx.x, ncol = trig_cols(a.dw);
-    if (i < ncol) {
-        float u = (float)(a.tlx + i) / a.scale;
-        mis_sincosf(u, &tab[2 * i], &tab[2 * i + 1]);
-    } else if (i < ncol + a.dh) {
-        const int r = i - ncol;
-        float v = (float)(a.tly + r) / a.scale, s, c;
-        mis_sincosf(MIS_PI_F - v, &s, &c);
-        float* t = tab + 2 * ncol + 4 * r;
-        t[0] = s; t[1] = a.m[1] * c; t[2] = a.m[4] * c; t[3] = a.m[7] * c;
-    }
+    trig_fill(a, tab, i, ncol);
 }
 
 
@@ -959,7 +1025,8 @@ __device__ __forceinline__ void v3_sample_global(const V3Frame& f, int xq, int y
 }
 
 // A tile outside the fast path, pixel by pixel (cold): generic map (IEEE division, x86 cvRound overflow, saturate_cast<short>
-// of the integer part), taps from global memory, 2-byte stores.
+// of the integer part), taps from global memory, 2-byte stores.  ZTEST as tile_map's.
+template <bool ZTEST>
 __device__ __noinline__ void v3_cold_tile(const V3Frame& f, float su, float cu, int gx, int ty0) {
     if (gx >= f.dw) return;
     const float xhi = (float)f.sw - 0.5f, yhi = (float)f.sh - 0.5f;
@@ -974,7 +1041,7 @@ __device__ __noinline__ void v3_cold_tile(const V3Frame& f, float su, float cu, 
         const float xx = (x_ * f.m[0] + rt.y) + z_ * f.m[2];
         const float yy = (x_ * f.m[3] + rt.z) + z_ * f.m[5];
         const float zz = (x_ * f.m[6] + rt.w) + z_ * f.m[8];
-        const bool front = zz > 0;
+        const bool front = !ZTEST || zz > 0;
         const float x = front ? xx / zz : -1.f, y = front ? yy / zz : -1.f;
         const int xr = mis_round_sat_f(x * 32.f), yr = mis_round_sat_f(y * 32.f);
         int p[3];
@@ -993,7 +1060,7 @@ __device__ __forceinline__ void v3_store_piece(uint8_t* p, u4v v, bool wide_out)
 // The strip a wave owns: columns tx0 .. tx0 + 63, tiles ty_first .. ty_first + nt - 1 (V3_TH rows each).
 // PIPE = false: the same stages one tile after the other (map, copies, wait, gather, stores) -- no second tile in flight, fewer
 // registers, more waves per SIMD: the form for a launch of ONE frame, whose strips are too short to fill a pipeline.
-template <bool PIPE, int RING>
+template <bool PIPE, int RING, bool ZTEST>
 __device__ __forceinline__ void warp_strip_body(const V3Frame& f, int tx0, int ty_first, int nt, lds_p ring) {
     const int lane = threadIdx.x & 63;
     const int nty = (f.dh + V3_TH - 1) / V3_TH;
@@ -1181,7 +1248,7 @@ __device__ __forceinline__ void warp_strip_body(const V3Frame& f, int tx0, int t
         const V3Frame fc = f;       // a copy for the call: the kernel's own arguments stay in registers
 #pragma unroll 1
         for (int k = 0; k < nt; k++)
-            if (cold >> k & 1) v3_cold_tile(fc, cs.x, cs.y, tx0 + lane, (ty_first + k) * V3_TH);
+            if (cold >> k & 1) v3_cold_tile<ZTEST>(fc, cs.x, cs.y, tx0 + lane, (ty_first + k) * V3_TH);
     }
 }
 
@@ -1217,6 +1284,16 @@ static int v3_strip_tiles(const MisContext* ctx, const WarpArgs& a, int frames) 
     const long long nt = tiles / ((long long)std::max(ctx->num_cu, 1) * WV3_SLOTS);
     return (int)std::min<long long>(WV3_NT_MAX, std::max<long long>(1, nt));
 }
+// The fast paths' upper bound on z: |z| <= (|m6| + |m7| + |m8|) max(|x_|, |y_|, |z_|).  Spherical terms are at most 1 (the kernels'
+// own guard); the cylinder's y_ = v' and the plane's x_ = u', y_ = v' grow with the roi, so those kinds scale the bound by the
+// largest |u'|, |v'| of the roi (a frame that fails it takes the generic map everywhere).
+static bool fast_z_bound_ok(const WarpArgs& a) {
+    const float msum = fabsf(a.m[6]) + fabsf(a.m[7]) + fabsf(a.m[8]);
+    if (a.kind == MIS_WARP_SPHERICAL) return msum <= 1048576.f;
+    const double uv = std::max({1.0, std::fabs((double)a.tlx), std::fabs((double)a.tlx + a.dw), std::fabs((double)a.tly),
+                                std::fabs((double)a.tly + a.dh)}) / (double)a.scale;
+    return (double)msum * std::max(1.0, uv) <= 1048576.0;
+}
 static V3Frame v3_frame_of(const WarpArgs& a, const float* tab) {
     V3Frame f;
     for (int i = 0; i < 9; i++) f.m[i] = a.m[i];
@@ -1231,7 +1308,7 @@ static V3Frame v3_frame_of(const WarpArgs& a, const float* tab) {
     f.flags = 0;
     if ((((size_t)a.src | a.sstride) & 15) == 0) f.flags |= V3F_WIDE_SRC;
     // |z| <= |m6| + |m7| + |m8| bounds z from above; dword-aligned frames below 4 GB only
-    if (small && (((size_t)a.src | a.sstride) & 3) == 0 && fabsf(a.m[6]) + fabsf(a.m[7]) + fabsf(a.m[8]) <= 1048576.f) f.flags |= V3F_FAST_OK;
+    if (small && (((size_t)a.src | a.sstride) & 3) == 0 && fast_z_bound_ok(a)) f.flags |= V3F_FAST_OK;
     if ((((size_t)a.dst | a.dstride) & 15) == 0) f.flags |= V3F_WIDE_OUT;
     if ((((size_t)a.mask | a.mstride) & 7) == 0) f.flags |= V3F_WIDE_MASK;
     f.src = a.src; f.dst = (uint8_t*)a.dst; f.mask = a.mask; f.tab = tab;
@@ -1270,6 +1347,7 @@ static void v3_plan_strips(const MisContext* ctx, const WarpArgs* args, int ng, 
 // hands out workgroups in index order as slots free up, so the strips of the LAST frames are the launch's tail: the host plans
 // them shorter (v3_plan_strips) -- with 8-tile strips everywhere a 16-frame launch is 7.25 generations of ~37 us waves and a
 // quarter of the slots run an eighth wave while the others idle.
+template <bool ZTEST>
 __global__ __launch_bounds__(64 * V3_WAVES) __attribute__((amdgpu_waves_per_eu(WV3_WAVES_MIN, 8))) void warp_strip_batch_kernel(V3Batch b) {
     __shared__ __attribute__((aligned(16))) uint8_t ring_all[V3_WAVES][V3_RING];
     const int bid = (int)blockIdx.x;
@@ -1281,7 +1359,7 @@ __global__ __launch_bounds__(64 * V3_WAVES) __attribute__((amdgpu_waves_per_eu(W
     const int nt = b.nt[fi];
     int tx0, ty_first;
     if (!v3_strip_of(bid - b.wg_base[fi], wave, f.dw, f.dh, nt, &tx0, &ty_first)) return;
-    warp_strip_body<true, V3_RING>(f, tx0, ty_first, nt, (lds_p)ring_all[wave]);
+    warp_strip_body<true, V3_RING, ZTEST>(f, tx0, ty_first, nt, (lds_p)ring_all[wave]);
 }
 
 // General warp (seam-scale path and plain masks): u8 with CN channels, one column per lane.
@@ -1298,7 +1376,7 @@ __global__ __launch_bounds__(256) void warp_u8_kernel(WarpArgs a) {
             const int r = wave * 4 + i, gy = ty0 + r;
             if (gy >= a.dh) break;
             float x, y;
-            map_backward(a.m, su[cx], cu[cx], sv[r], cv[r], &x, &y);
+            map_backward(a.kind, a.m, su[cx], cu[cx], sv[r], cv[r], &x, &y);
             uint8_t* d = (uint8_t*)a.dst + (size_t)gy * a.dstride + (size_t)gx * CN;
             if (LINEAR) {
                 int p[CN];
@@ -1316,7 +1394,8 @@ __global__ __launch_bounds__(256) void warp_u8_kernel(WarpArgs a) {
 }
 
 // `known`: the roi warpRoi / mis_warp_roi_batch returned for exactly these (scale, K, R, size) -- skips the border walk
-int setup(MisContext* ctx, const MisImage* src, float scale, const float K[9], const float R[9], WarpArgs* a, int* brx, int* bry, const MisRect* known = nullptr) {
+int setup(MisContext* ctx, int kind, const MisImage* src, float scale, const float K[9], const float R[9], WarpArgs* a, int* brx, int* bry, const MisRect* known = nullptr) {
+    MIS_CHECK(ctx, kind_ok(kind), MIS_E_UNSUPPORTED, "unknown warp kind %d", kind);
     MIS_CHECK(ctx, src && K && R, MIS_E_INVALID, "null argument");
     MIS_CHECK(ctx, src->dtype == MIS_U8 && (src->channels == 1 || src->channels == 3), MIS_E_UNSUPPORTED,
               "warp source must be 8UC1 or 8UC3");
@@ -1326,13 +1405,18 @@ int setup(MisContext* ctx, const MisImage* src, float scale, const float K[9], c
     Projector p;
     int tlx, tly;
     if (known) {
-        projector_set(&p, scale, K, R);
+        projector_set(&p, kind, scale, K, R);
         tlx = known->x; tly = known->y; *brx = known->x + known->width - 1; *bry = known->y + known->height - 1;
     } else {
-        projector_and_roi(scale, K, R, src->width, src->height, &p, &tlx, &tly, brx, bry);
+        MIS_CHECK(ctx, projector_and_roi(kind, scale, K, R, src->width, src->height, &p, &tlx, &tly, brx, bry) == MIS_OK, MIS_E_INVALID, "%s",
+                  kind == MIS_WARP_PLANE ? "warp roi refused: a corner of the frame lies behind the panorama plane"
+                                         : "warp roi refused: the border projects to a non-finite extreme");
     }
     for (int i = 0; i < 9; i++) a->m[i] = p.k_rinv[i];
+    a->kind = kind;
     a->scale = scale; a->tlx = tlx; a->tly = tly;
+    MIS_CHECK(ctx, (long long)*brx - tlx + 1 <= INT_MAX && (long long)*bry - tly + 1 <= INT_MAX, MIS_E_INVALID,
+              "warp roi %d..%d x %d..%d does not fit an int size", tlx, *brx, tly, *bry);
     a->dw = *brx - tlx + 1; a->dh = *bry - tly + 1;
     a->sw = src->width; a->sh = src->height; a->cn = src->channels;
     MIS_CHECK(ctx, a->dw > 0 && a->dh > 0 && (long long)a->dw * a->dh < (1ll << 31), MIS_E_INVALID, "degenerate warp roi %dx%d", a->dw, a->dh);
@@ -1358,23 +1442,27 @@ extern "C" int mis_debug_warp_stamps(unsigned long long* out, int n) {
 }
 #endif
 
-extern "C" int mis_warp_roi(float scale, int w, int h, const float K[9], const float R[9], MisRect* roi) {
+extern "C" int mis_warper_roi(int kind, float scale, int w, int h, const float K[9], const float R[9], MisRect* roi) {
+    if (!kind_ok(kind)) return MIS_E_UNSUPPORTED;
     if (!K || !R || !roi || w < 1 || h < 1 || !(scale > 0.f)) return MIS_E_INVALID;
     Projector p;
-    int tlx, tly, brx, bry;
-    projector_and_roi(scale, K, R, w, h, &p, &tlx, &tly, &brx, &bry);
-    roi->x = tlx; roi->y = tly; roi->width = brx + 1 - tlx; roi->height = bry + 1 - tly;
-    return MIS_OK;
+    int tlx, tly, brx, bry, rc;
+    if ((rc = projector_and_roi(kind, scale, K, R, w, h, &p, &tlx, &tly, &brx, &bry)) != MIS_OK) return rc;
+    return roi_rect(tlx, tly, brx, bry, roi);
 }
 
-extern "C" int mis_warp_spherical(MisContext* ctx, const MisImage* src, float scale, const float K[9], const float R[9],
-                                  int interp, int border, MisImage* dst, MisPoint* tl) {
+extern "C" int mis_warp_roi(float scale, int w, int h, const float K[9], const float R[9], MisRect* roi) {
+    return mis_warper_roi(MIS_WARP_SPHERICAL, scale, w, h, K, R, roi);
+}
+
+extern "C" int mis_warper_warp(MisContext* ctx, int kind, const MisImage* src, float scale, const float K[9], const float R[9],
+                               int interp, int border, MisImage* dst, MisPoint* tl) {
     if (!ctx) return MIS_E_INVALID;
     MIS_CHECK(ctx, (interp == MIS_INTER_LINEAR && border == MIS_BORDER_REFLECT) || (interp == MIS_INTER_NEAREST && border == MIS_BORDER_CONSTANT),
               MIS_E_UNSUPPORTED, "supported: (LINEAR, REFLECT) and (NEAREST, CONSTANT)");
     WarpArgs a;
     int brx, bry, rc;
-    if ((rc = setup(ctx, src, scale, K, R, &a, &brx, &bry)) != MIS_OK) return rc;
+    if ((rc = setup(ctx, kind, src, scale, K, R, &a, &brx, &bry)) != MIS_OK) return rc;
     MIS_HIP(ctx, hipSetDevice(ctx->device));
     DevImage din, dout;
     if ((rc = mis_dev_image_in(ctx, src, &din)) != MIS_OK) return rc;
@@ -1396,14 +1484,26 @@ extern "C" int mis_warp_spherical(MisContext* ctx, const MisImage* src, float sc
     return MIS_OK;
 }
 
+extern "C" int mis_warp_spherical(MisContext* ctx, const MisImage* src, float scale, const float K[9], const float R[9],
+                                  int interp, int border, MisImage* dst, MisPoint* tl) {
+    return mis_warper_warp(ctx, MIS_WARP_SPHERICAL, src, scale, K, R, interp, border, dst, tl);
+}
+
 static int grid_of(const WarpArgs& a);
-static int warp_fused_impl(MisContext* ctx, const MisImage* src, float scale, const float K[9], const float R[9],
+static int warp_fused_batch_impl(MisContext* ctx, int kind, const MisImage* srcs, int n, float scale, const float* Ks, const float* Rs, const MisRect* rois,
+                                 MisImage* dsts, MisImage* dmasks, MisPoint* tls, int repeats, float* avg_us);
+static int warp_fused_impl(MisContext* ctx, int kind, const MisImage* src, float scale, const float K[9], const float R[9],
                            MisImage* dst, MisImage* dmask, MisPoint* tl, int repeats, float* avg_us, const MisRect* known_roi = nullptr) {
     if (!ctx) return MIS_E_INVALID;
     WarpArgs a;
     int brx, bry, rc;
-    if ((rc = setup(ctx, src, scale, K, R, &a, &brx, &bry, known_roi)) != MIS_OK) return rc;
+    if ((rc = setup(ctx, kind, src, scale, K, R, &a, &brx, &bry, known_roi)) != MIS_OK) return rc;
     MIS_CHECK(ctx, src->channels == 3, MIS_E_UNSUPPORTED, "fused warp needs an 8UC3 source");
+    if (kind != MIS_WARP_SPHERICAL && !fast_z_bound_ok(a) && repeats == 1 && !avg_us) {
+        // the one-frame kernel's z guard is the spherical one: a roi this far out goes through the batch form (same results)
+        const MisRect r{a.tlx, a.tly, a.dw, a.dh};
+        return warp_fused_batch_impl(ctx, kind, src, 1, scale, K, R, &r, dst, dmask, tl, 1, nullptr);
+    }
     MIS_HIP(ctx, hipSetDevice(ctx->device));
     DevImage din, dout, dm;
     if ((rc = mis_dev_image_in(ctx, src, &din)) != MIS_OK) return rc;
@@ -1432,7 +1532,8 @@ static int warp_fused_impl(MisContext* ctx, const MisImage* src, float scale, co
     // one frame per launch: round 2's tile kernel (measured faster there than the strip forms: 23.2 us against 29.3 for one-tile
     // strips and more for longer ones -- a frame alone is 3.5 tiles per wave slot, gpurun_out/r4_plan_ab3.txt)
     for (int rep = 0; rep < repeats; rep++)
-        hipLaunchKernelGGL(warp_fused_kernel, dim3(nwg), dim3(64 * TILE_WAVES), 0, ctx->stream, a, (const float*)tab);
+        if (kind == MIS_WARP_PLANE) hipLaunchKernelGGL(warp_fused_kernel<false>, dim3(nwg), dim3(64 * TILE_WAVES), 0, ctx->stream, a, (const float*)tab);
+        else hipLaunchKernelGGL(warp_fused_kernel<true>, dim3(nwg), dim3(64 * TILE_WAVES), 0, ctx->stream, a, (const float*)tab);
     if (avg_us) {
         float ms = 0.f;
         MIS_HIP(ctx, hipEventRecord(e1, ctx->stream));
@@ -1449,17 +1550,27 @@ static int warp_fused_impl(MisContext* ctx, const MisImage* src, float scale, co
     return MIS_OK;
 }
 
-extern "C" int mis_warp_spherical_fused(MisContext* ctx, const MisImage* src, float scale, const float K[9], const float R[9],
-                                        MisImage* dst, MisImage* dmask, MisPoint* tl) {
-    return warp_fused_impl(ctx, src, scale, K, R, dst, dmask, tl, 1, nullptr);
+extern "C" int mis_warper_warp_fused(MisContext* ctx, int kind, const MisImage* src, float scale, const float K[9], const float R[9],
+                                     MisImage* dst, MisImage* dmask, MisPoint* tl) {
+    return warp_fused_impl(ctx, kind, src, scale, K, R, dst, dmask, tl, 1, nullptr);
 }
 
-// the compose loop's form: the roi is the one mis_warp_roi / mis_warp_roi_batch gave for these parameters
-extern "C" int mis_warp_spherical_fused_roi(MisContext* ctx, const MisImage* src, float scale, const float K[9], const float R[9], const MisRect* roi,
-                                            MisImage* dst, MisImage* dmask, MisPoint* tl) {
+extern "C" int mis_warp_spherical_fused(MisContext* ctx, const MisImage* src, float scale, const float K[9], const float R[9],
+                                        MisImage* dst, MisImage* dmask, MisPoint* tl) {
+    return mis_warper_warp_fused(ctx, MIS_WARP_SPHERICAL, src, scale, K, R, dst, dmask, tl);
+}
+
+// the compose loop's form: the roi is the one mis_warper_roi / mis_warper_roi_batch gave for these parameters
+extern "C" int mis_warper_warp_fused_roi(MisContext* ctx, int kind, const MisImage* src, float scale, const float K[9], const float R[9], const MisRect* roi,
+                                         MisImage* dst, MisImage* dmask, MisPoint* tl) {
     if (!ctx) return MIS_E_INVALID;
     MIS_CHECK(ctx, roi && roi->width > 0 && roi->height > 0, MIS_E_INVALID, "empty roi");
-    return warp_fused_impl(ctx, src, scale, K, R, dst, dmask, tl, 1, nullptr, roi);
+    return warp_fused_impl(ctx, kind, src, scale, K, R, dst, dmask, tl, 1, nullptr, roi);
+}
+
+extern "C" int mis_warp_spherical_fused_roi(MisContext* ctx, const MisImage* src, float scale, const float K[9], const float R[9], const MisRect* roi,
+                                            MisImage* dst, MisImage* dmask, MisPoint* tl) {
+    return mis_warper_warp_fused_roi(ctx, MIS_WARP_SPHERICAL, src, scale, K, R, roi, dst, dmask, tl);
 }
 
 // workgroups of warp_fused_kernel: whole chunks, a multiple of 8 of them (workgroups past the tile grid return at once)
@@ -1471,8 +1582,9 @@ static int grid_of(const WarpArgs& a) {
 // n fused warps (the loop of image_stitching.cpp:1154-1164 for all frames) in one grid per WB_MAX frames; the results are those of
 // n mis_warp_spherical_fused_roi calls.  repeats / avg_us: the batch launched `repeats` times back to back between two HIP events
 // (avg_us = the average duration of one pass over all n frames), for the roofline measurement.
-static int warp_fused_batch_impl(MisContext* ctx, const MisImage* srcs, int n, float scale, const float* Ks, const float* Rs, const MisRect* rois,
+static int warp_fused_batch_impl(MisContext* ctx, int kind, const MisImage* srcs, int n, float scale, const float* Ks, const float* Rs, const MisRect* rois,
                                  MisImage* dsts, MisImage* dmasks, MisPoint* tls, int repeats, float* avg_us) {
+    MIS_CHECK(ctx, kind_ok(kind), MIS_E_UNSUPPORTED, "unknown warp kind %d", kind);
     MIS_CHECK(ctx, srcs && Ks && Rs && rois && dsts && dmasks && n >= 1, MIS_E_INVALID, "null argument");
     MIS_HIP(ctx, hipSetDevice(ctx->device));
     std::vector<WarpArgs> args((size_t)n);
@@ -1499,7 +1611,7 @@ static int warp_fused_batch_impl(MisContext* ctx, const MisImage* srcs, int n, f
         WarpArgs& a = args[i];
         int brx, bry;
         if (!(rois[i].width > 0 && rois[i].height > 0)) { rc = mis_set_error(ctx, MIS_E_INVALID, "frame %d: empty roi", i); break; }
-        if ((rc = setup(ctx, &srcs[i], scale, Ks + 9 * i, Rs + 9 * i, &a, &brx, &bry, &rois[i])) != MIS_OK) break;
+        if ((rc = setup(ctx, kind, &srcs[i], scale, Ks + 9 * i, Rs + 9 * i, &a, &brx, &bry, &rois[i])) != MIS_OK) break;
         if (srcs[i].channels != 3) { rc = mis_set_error(ctx, MIS_E_UNSUPPORTED, "fused warp needs an 8UC3 source"); break; }
         if ((rc = mis_dev_image_in(ctx, &srcs[i], &din[i])) != MIS_OK) break;
         if ((rc = mis_dev_image_out(ctx, &dsts[i], a.dw, a.dh, 3, MIS_S16, &dout[i])) != MIS_OK) break;
@@ -1556,7 +1668,8 @@ static int warp_fused_batch_impl(MisContext* ctx, const MisImage* srcs, int n, f
     }
     for (int rep = 0; rep < repeats; rep++)
         for (const V3Batch& vb : v3batches)
-            hipLaunchKernelGGL(warp_strip_batch_kernel, dim3(vb.wg_base[WB_MAX]), dim3(64 * V3_WAVES), 0, ctx->stream, vb);
+            if (kind == MIS_WARP_PLANE) hipLaunchKernelGGL(warp_strip_batch_kernel<false>, dim3(vb.wg_base[WB_MAX]), dim3(64 * V3_WAVES), 0, ctx->stream, vb);
+            else hipLaunchKernelGGL(warp_strip_batch_kernel<true>, dim3(vb.wg_base[WB_MAX]), dim3(64 * V3_WAVES), 0, ctx->stream, vb);
     if (avg_us) {
         float ms = 0.f;
         MIS_HIP(ctx, hipEventRecord(e1, ctx->stream));
@@ -1574,22 +1687,29 @@ static int warp_fused_batch_impl(MisContext* ctx, const MisImage* srcs, int n, f
     return rc;
 }
 
+extern "C" int mis_warper_warp_fused_batch(MisContext* ctx, int kind, const MisImage* srcs, int n, float scale, const float* Ks, const float* Rs,
+                                           const MisRect* rois, MisImage* dsts, MisImage* dmasks, MisPoint* tls) {
+    if (!ctx) return MIS_E_INVALID;
+    MIS_CHECK(ctx, kind_ok(kind), MIS_E_UNSUPPORTED, "unknown warp kind %d", kind);
+    if (n == 0) return MIS_OK;
+    return warp_fused_batch_impl(ctx, kind, srcs, n, scale, Ks, Rs, rois, dsts, dmasks, tls, 1, nullptr);
+}
+
 extern "C" int mis_warp_spherical_fused_batch(MisContext* ctx, const MisImage* srcs, int n, float scale, const float* Ks, const float* Rs, const MisRect* rois,
                                               MisImage* dsts, MisImage* dmasks, MisPoint* tls) {
-    if (!ctx) return MIS_E_INVALID;
-    if (n == 0) return MIS_OK;
-    return warp_fused_batch_impl(ctx, srcs, n, scale, Ks, Rs, rois, dsts, dmasks, tls, 1, nullptr);
+    return mis_warper_warp_fused_batch(ctx, MIS_WARP_SPHERICAL, srcs, n, scale, Ks, Rs, rois, dsts, dmasks, tls);
 }
 
 extern "C" int mis_warp_spherical_fused_batch_timed(MisContext* ctx, const MisImage* srcs, int n, float scale, const float* Ks, const float* Rs, const MisRect* rois,
                                                     MisImage* dsts, MisImage* dmasks, MisPoint* tls, int repeats, float* avg_us) {
     if (!ctx) return MIS_E_INVALID;
     MIS_CHECK(ctx, repeats >= 1 && avg_us && n >= 1, MIS_E_INVALID, "repeats must be >= 1, n >= 1 and avg_us non-null");
-    return warp_fused_batch_impl(ctx, srcs, n, scale, Ks, Rs, rois, dsts, dmasks, tls, repeats, avg_us);
+    return warp_fused_batch_impl(ctx, MIS_WARP_SPHERICAL, srcs, n, scale, Ks, Rs, rois, dsts, dmasks, tls, repeats, avg_us);
 }
 
-extern "C" int mis_warp_roi_batch(MisContext* ctx, float scale, int w, int h, int n, const float* Ks, const float* Rs, MisRect* rois) {
+extern "C" int mis_warper_roi_batch(MisContext* ctx, int kind, float scale, int w, int h, int n, const float* Ks, const float* Rs, MisRect* rois) {
     if (!ctx) return MIS_E_INVALID;
+    MIS_CHECK(ctx, kind_ok(kind), MIS_E_UNSUPPORTED, "unknown warp kind %d", kind);
     MIS_CHECK(ctx, Ks && Rs && rois && n >= 1 && w >= 1 && h >= 1 && scale > 0.f, MIS_E_INVALID, "invalid argument");
     MIS_HIP(ctx, hipSetDevice(ctx->device));
     const size_t need = sizeof(RoiJob) * (size_t)n;
@@ -1601,24 +1721,31 @@ extern "C" int mis_warp_roi_batch(MisContext* ctx, float scale, int w, int h, in
     RoiJob* jobs = (RoiJob*)ctx->roi_pinned;
     std::vector<Projector> proj((size_t)n);
     for (int i = 0; i < n; i++) {
-        projector_set(&proj[i], scale, Ks + 9 * i, Rs + 9 * i);
+        projector_set(&proj[i], kind, scale, Ks + 9 * i, Rs + 9 * i);
         memcpy(jobs[i].r_kinv, proj[i].r_kinv, sizeof(jobs[i].r_kinv));
-        jobs[i].scale = scale; jobs[i].sw = w; jobs[i].sh = h;
+        jobs[i].scale = scale; jobs[i].sw = w; jobs[i].sh = h; jobs[i].kind = kind; jobs[i].behind = 0;
     }
     hipLaunchKernelGGL(warp_roi_kernel, dim3(n), dim3(256), 0, ctx->stream, jobs);
     MIS_HIP(ctx, hipGetLastError());
     MIS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     for (int i = 0; i < n; i++) {
         int tlx, tly, brx, bry;
-        roi_from_extremes(&proj[i], w, h, jobs[i].ext[0], jobs[i].ext[1], jobs[i].ext[2], jobs[i].ext[3], &tlx, &tly, &brx, &bry);
-        rois[i].x = tlx; rois[i].y = tly; rois[i].width = brx + 1 - tlx; rois[i].height = bry + 1 - tly;
+        MIS_CHECK(ctx, !jobs[i].behind, MIS_E_INVALID, "frame %d: warp roi refused: a corner of the frame lies behind the panorama plane", i);
+        MIS_CHECK(ctx, roi_from_extremes(&proj[i], w, h, jobs[i].ext[0], jobs[i].ext[1], jobs[i].ext[2], jobs[i].ext[3], &tlx, &tly, &brx, &bry) == MIS_OK,
+                  MIS_E_INVALID, "frame %d: warp roi refused: the border projects to a non-finite extreme", i);
+        MIS_CHECK(ctx, roi_rect(tlx, tly, brx, bry, &rois[i]) == MIS_OK, MIS_E_INVALID, "frame %d: warp roi %d..%d x %d..%d does not fit an int size",
+                  i, tlx, brx, tly, bry);
     }
     return MIS_OK;
+}
+
+extern "C" int mis_warp_roi_batch(MisContext* ctx, float scale, int w, int h, int n, const float* Ks, const float* Rs, MisRect* rois) {
+    return mis_warper_roi_batch(ctx, MIS_WARP_SPHERICAL, scale, w, h, n, Ks, Rs, rois);
 }
 
 extern "C" int mis_warp_spherical_fused_timed(MisContext* ctx, const MisImage* src, float scale, const float K[9], const float R[9],
                                               MisImage* dst, MisImage* dmask, MisPoint* tl, int repeats, float* avg_us) {
     if (!ctx) return MIS_E_INVALID;
     MIS_CHECK(ctx, repeats >= 1 && avg_us, MIS_E_INVALID, "repeats must be >= 1 and avg_us non-null");
-    return warp_fused_impl(ctx, src, scale, K, R, dst, dmask, tl, repeats, avg_us);
+    return warp_fused_impl(ctx, MIS_WARP_SPHERICAL, src, scale, K, R, dst, dmask, tl, repeats, avg_us);
 }

@@ -152,6 +152,8 @@ class HipEngine:
     def __init__(self, ctx, frame_size, config=None):
         self.ctx = ctx
         self.cfg = config or st.StitchConfig.hot_path()
+        self.warp_type = self.cfg.warp_type            # the warper this engine runs (StitchJob checks it against the job's)
+        self.kind = st.check_warp_config(self.cfg)
         self.frame_size = frame_size
         # finder per features_type (image_stitching.cpp:543-563): ORB, or SIFT (float descriptors -> the L2 matcher)
         self.finder = st.SiftFeatureFinder(ctx, frame_size) if self.cfg.features_type == "sift" else st.OrbFeatureFinder(ctx, frame_size)
@@ -286,11 +288,11 @@ class HipEngine:
 
     # ---- compose ----
     def warp_roi(self, scale, cam, size=None):
-        return st.warp_roi(scale, size or self.frame_size, cam["K"], cam["R"])
+        return st.warp_roi(scale, size or self.frame_size, cam["K"], cam["R"], self.kind)
 
     def warp_rois(self, scale, cams, size=None):
         """warpRoi of every camera (image_stitching.cpp:1119-1140): one kernel on the compose stream, nothing cached."""
-        return st.warp_rois(self.cctx, scale, size or self.frame_size, cams)
+        return st.warp_rois(self.cctx, scale, size or self.frame_size, cams, self.kind)
 
     def resize_frame(self, frame, f):
         """cv::resize(full_img, img, Size(), f, f, INTER_LINEAR_EXACT) (image_stitching.cpp:1143-1146) on the compose stream."""
@@ -305,7 +307,7 @@ class HipEngine:
             self.blender = {capi.BLEND_MULTI_BAND: lambda: st.MultiBandBlender(self.cctx, bands),
                             capi.BLEND_FEATHER: lambda: st.FeatherBlender(self.cctx, sharp), capi.BLEND_NO: lambda: st.Blender(self.cctx)}[btype]()
         self.blender.prepare(corners, sizes)
-        self.warper = st.SphericalWarper(self.cctx, scale)
+        self.warper = st.RotationWarper(self.cctx, scale, self.kind)
         self.pano_size = (pw, ph)
         return btype, bands
 
@@ -351,7 +353,7 @@ class HipEngine:
     def warp_feed_many(self, frames, cams, rois):
         """warp_feed for a list of frames in one library call (no interpreter work between the launches: the thread that
         composes speculatively does not compete for the GIL with the thread that drives the matcher)."""
-        self.blender.compose_frames(frames, self.warper.scale, cams, rois)
+        self.blender.compose_frames(frames, self.warper.scale, cams, rois, self.kind)
 
     def accumulators(self):
         """[(lap int16 [h, w*3], weight f32 [h, w])] tensor views of the blender's panorama pyramids."""
@@ -441,7 +443,12 @@ class StitchJob:
     def __init__(self, ctx, frame_size, cameras, rank=0, world_size=1, group=None, engine=None, config=None, force_collectives=False, always_collective=False):
         self.cfg = config or st.StitchConfig.hot_path()
         st.check_seam_config(self.cfg)
+        self.kind = st.check_warp_config(self.cfg)
         self.engine = engine or HipEngine(ctx, frame_size, self.cfg)
+        # an engine warps one kind (its own config's; spherical when it does not say): never another than the job's
+        engine_warp = getattr(self.engine, "warp_type", "spherical")
+        if engine_warp != self.cfg.warp_type:
+            raise NotImplementedError("warp_type %r: the engine %s warps %r only" % (self.cfg.warp_type, type(self.engine).__name__, engine_warp))
         self.cams = cameras
         self.cams0 = cameras          # the caller's cameras; self.cams holds the refined ones after a run with bundle adjustment
         self.n = len(cameras)
@@ -660,6 +667,22 @@ class StitchJob:
             return self.stage_reduce_finalize()
 
     # -- whole job ---------------------------------------------------------------------------
+    def speculation_roi_ok(self):
+        """Whether warpRoi of ALL frames succeeds at the all-frames compose scale, as the speculative composition needs it.  A
+        plane warp refuses a frame turned behind the panorama plane, even one the pruning will drop: then the job composes the
+        kept set after pruning instead (only a refused roi among the kept frames is an error).  Cameras only: decided before
+        matching starts.  The spherical roi is never refused."""
+        if self.kind == capi.WARP_SPHERICAL:
+            return True
+        g = st.compose_geometry(self.cfg, self.frame_size, st.Stitcher.warped_image_scale(self.cams))
+        try:
+            for c in self.cams:
+                c = st.scaled_camera(c, g.aspect) if g.aspect != 1.0 else c
+                st.warp_roi(g.warp_scale, g.size, c["K"], c["R"], self.kind)
+        except st.MisError:
+            return False
+        return True
+
     def _compose_on_side_stream(self, frames, indices, prepared=None):
         """stage_compose with the engine's compose stream current (allocations and launches belong to it)."""
         eng = self.engine
@@ -680,6 +703,7 @@ class StitchJob:
         # host work (DP seams) and small kernels then run under the matcher's 5 ms instead of behind them
         solo_rank = self.world == 1 and not self.force_collectives
         spec = getattr(self.engine, "speculative_compose", False) and not refine and (not self.seam_needed or solo_rank)
+        spec = spec and self.speculation_roi_ok()
         prepared = None
         side = getattr(self.engine, "compose_stream", None)
         if side is not None:

@@ -119,51 +119,75 @@ class Context:
 
 
 # ------------------------------------------------------------------------------------------------
-# warp: cv::detail::SphericalWarper (image_stitching.cpp:973, :985, :988, :1117, :1138, :1154, :1159)
-def warp_roi(scale, src_size, K, R):
+# warp: cv::detail::{Spherical,Cylindrical,Plane}Warper, chosen by warp_type (image_stitching.cpp:917-969; :973, :985, :988,
+# :1117, :1138, :1154, :1159)
+WARP_KINDS = {"spherical": capi.WARP_SPHERICAL, "cylindrical": capi.WARP_CYLINDRICAL, "plane": capi.WARP_PLANE}
+# the reference's other warp_type names (image_stitching.cpp:933-964): known there, not built here
+UNBUILT_WARP_TYPES = ("affine", "fisheye", "stereographic", "compressedPlaneA2B1", "compressedPlaneA1.5B1", "compressedPlanePortraitA2B1",
+                      "compressedPlanePortraitA1.5B1", "paniniA2B1", "paniniA1.5B1", "paniniPortraitA2B1", "paniniPortraitA1.5B1",
+                      "mercator", "transverseMercator")
+
+
+def warp_kind(warp_type):
+    """warp_type -> MIS_WARP_* kind; the reference's unbuilt warpers raise NotImplementedError by name, other names ValueError
+    (the reference's "Can't create the following warper", image_stitching.cpp:966-970)."""
+    if warp_type in WARP_KINDS:
+        return WARP_KINDS[warp_type]
+    if warp_type in UNBUILT_WARP_TYPES:
+        raise NotImplementedError("warp_type %r: only 'spherical', 'cylindrical' and 'plane' are implemented (the warpers of the "
+                                  "reference's GPU branch, image_stitching.cpp:921-931; DESIGN.md section 8)" % (warp_type,))
+    raise ValueError("warp_type %r: not a warper the reference knows (image_stitching.cpp:917-969)" % (warp_type,))
+
+
+def warp_roi(scale, src_size, K, R, kind=capi.WARP_SPHERICAL):
     """RotationWarper::warpRoi(src_size, K, R) -> (x, y, width, height)."""
     lib = capi.load()
     _, kp = _mat9(K)
     _, rp = _mat9(R)
     r = capi.MisRect()
-    rc = lib.mis_warp_roi(float(scale), int(src_size[0]), int(src_size[1]), kp, rp, C.byref(r))
+    rc = lib.mis_warper_roi(int(kind), float(scale), int(src_size[0]), int(src_size[1]), kp, rp, C.byref(r))
     if rc != capi.MIS_OK:
-        raise MisError(rc, "mis_warp_roi: invalid arguments")
+        raise MisError(rc, "mis_warper_roi: invalid arguments or a refused roi (kind %d)" % kind)
     return r.x, r.y, r.width, r.height
 
 
-def warp_rois(ctx, scale, src_size, cameras):
+def warp_rois(ctx, scale, src_size, cameras, kind=capi.WARP_SPHERICAL):
     """The warpRoi loop of main() (image_stitching.cpp:1119-1140) for all cameras in one library call: the border walks run
     in one small kernel on the context's stream -> [(x, y, width, height)]."""
     n = len(cameras)
     Ks = np.ascontiguousarray(np.stack([np.asarray(c["K"], np.float32).reshape(9) for c in cameras]))
     Rs = np.ascontiguousarray(np.stack([np.asarray(c["R"], np.float32).reshape(9) for c in cameras]))
     rr = (capi.MisRect * n)()
-    ctx.check(ctx.lib.mis_warp_roi_batch(ctx.h, float(scale), int(src_size[0]), int(src_size[1]), n,
-                                         Ks.ctypes.data_as(C.c_void_p), Rs.ctypes.data_as(C.c_void_p), rr))
+    ctx.check(ctx.lib.mis_warper_roi_batch(ctx.h, int(kind), float(scale), int(src_size[0]), int(src_size[1]), n,
+                                           Ks.ctypes.data_as(C.c_void_p), Rs.ctypes.data_as(C.c_void_p), rr))
     return [(r.x, r.y, r.width, r.height) for r in rr]
 
 
-class SphericalWarper:
-    """warper_creator->create(scale) (image_stitching.cpp:973, :1117)."""
+class RotationWarper:
+    """warper_creator->create(scale) (image_stitching.cpp:973, :1117) for a warper kind (MIS_WARP_*)."""
+    kind = None
 
-    def __init__(self, ctx, scale):
+    def __init__(self, ctx, scale, kind=None):
         self.ctx, self.scale = ctx, float(scale)
+        if kind is not None:
+            self.kind = int(kind)
+        if self.kind not in WARP_KINDS.values():
+            raise NotImplementedError("warper kind %r" % (self.kind,))
 
     def warpRoi(self, src_size, K, R):
-        return warp_roi(self.scale, src_size, K, R)
+        return warp_roi(self.scale, src_size, K, R, self.kind)
 
     def warp(self, src, K, R, interp=capi.INTER_LINEAR, border=capi.BORDER_REFLECT):
         """Point warp(src, K, R, interp, border, dst) -> (tl, dst)."""
         simg = as_image(src)
-        x, y, w, h = warp_roi(self.scale, (simg.width, simg.height), K, R)
+        x, y, w, h = warp_roi(self.scale, (simg.width, simg.height), K, R, self.kind)
         dst = _empty_image(self.ctx, h, w, simg.channels, torch.uint8)
         dimg = as_image(dst)
         ka, kp = _mat9(K)
         ra, rp = _mat9(R)
         tl = capi.MisPoint()
-        self.ctx.check(self.ctx.lib.mis_warp_spherical(self.ctx.h, C.byref(simg), self.scale, kp, rp, interp, border,
-                                                       C.byref(dimg), C.byref(tl)))
+        self.ctx.check(self.ctx.lib.mis_warper_warp(self.ctx.h, self.kind, C.byref(simg), self.scale, kp, rp, interp, border,
+                                                    C.byref(dimg), C.byref(tl)))
         return (tl.x, tl.y), dst
 
     def alloc_fused(self, roi):
@@ -178,15 +202,15 @@ class SphericalWarper:
         tl = capi.MisPoint()
         if roi is not None:      # the roi warpRoi gave for these parameters: the warp does not walk the border again
             rr = capi.MisRect(int(roi[0]), int(roi[1]), int(roi[2]), int(roi[3]))
-            self.ctx.check(self.ctx.lib.mis_warp_spherical_fused_roi(self.ctx.h, C.byref(simg), self.scale, kp, rp, C.byref(rr),
-                                                                     C.byref(dimg), C.byref(mimg), C.byref(tl)))
+            self.ctx.check(self.ctx.lib.mis_warper_warp_fused_roi(self.ctx.h, self.kind, C.byref(simg), self.scale, kp, rp, C.byref(rr),
+                                                                  C.byref(dimg), C.byref(mimg), C.byref(tl)))
         else:
-            self.ctx.check(self.ctx.lib.mis_warp_spherical_fused(self.ctx.h, C.byref(simg), self.scale, kp, rp, C.byref(dimg),
-                                                                 C.byref(mimg), C.byref(tl)))
+            self.ctx.check(self.ctx.lib.mis_warper_warp_fused(self.ctx.h, self.kind, C.byref(simg), self.scale, kp, rp, C.byref(dimg),
+                                                              C.byref(mimg), C.byref(tl)))
         return (tl.x, tl.y)
 
     def warp_fused_batch(self, imgs, cameras, rois):
-        """mis_warp_spherical_fused_batch: the compose-scale step of main() for all frames (one grid per 16 frames)
+        """mis_warper_warp_fused_batch: the compose-scale step of main() for all frames (one grid per 16 frames)
         -> [(tl, img_warped_s, mask_warped)], the results of warp_fused per frame."""
         n = len(imgs)
         if n == 0:
@@ -200,12 +224,15 @@ class SphericalWarper:
         rs = (capi.MisRect * n)(*[capi.MisRect(int(r[0]), int(r[1]), int(r[2]), int(r[3])) for r in rois])
         tls = (capi.MisPoint * n)()
         fp = C.POINTER(C.c_float)
-        self.ctx.check(self.ctx.lib.mis_warp_spherical_fused_batch(self.ctx.h, im, n, float(self.scale), Ks.ctypes.data_as(fp), Rs.ctypes.data_as(fp), rs, ds, ms, tls))
+        self.ctx.check(self.ctx.lib.mis_warper_warp_fused_batch(self.ctx.h, self.kind, im, n, float(self.scale), Ks.ctypes.data_as(fp), Rs.ctypes.data_as(fp), rs, ds, ms, tls))
         return [((t.x, t.y), o[0], o[1]) for t, o in zip(tls, outs)]
 
     def warp_fused_batch_timed(self, imgs, cameras, rois, dsts, masks, repeats):
         """mis_warp_spherical_fused_batch_timed: the fused warps of all frames in one grid per 16 frames, launched `repeats` times
-        back to back between two HIP events on the context's stream -> average microseconds of one pass over all frames."""
+        back to back between two HIP events on the context's stream -> average microseconds of one pass over all frames
+        (a measurement aid of the spherical warper)."""
+        if self.kind != capi.WARP_SPHERICAL:
+            raise NotImplementedError("the timed warps measure the spherical kind only")
         n = len(imgs)
         im = (capi.MisImage * n)(*[as_image(i) for i in imgs])
         ds = (capi.MisImage * n)(*[as_image(d) for d in dsts])
@@ -221,7 +248,9 @@ class SphericalWarper:
         return us.value
 
     def warp_fused_timed(self, src_bgr, K, R, roi, dst, msk, repeats):
-        """Average duration (us) of the fused warp kernel over `repeats` back-to-back launches (HIP events)."""
+        """Average duration (us) of the fused warp kernel over `repeats` back-to-back launches (HIP events; spherical only)."""
+        if self.kind != capi.WARP_SPHERICAL:
+            raise NotImplementedError("the timed warps measure the spherical kind only")
         simg, dimg, mimg = as_image(src_bgr), as_image(dst), as_image(msk)
         ka, kp = _mat9(K)
         ra, rp = _mat9(R)
@@ -235,10 +264,30 @@ class SphericalWarper:
         convertTo(CV_16S) (image_stitching.cpp:1154-1164) -> (tl, img_warped_s, mask_warped)."""
         if roi is None:
             simg = as_image(src_bgr)
-            roi = warp_roi(self.scale, (simg.width, simg.height), K, R)
+            roi = warp_roi(self.scale, (simg.width, simg.height), K, R, self.kind)
         dst, msk = self.alloc_fused(roi)
         tl = self.warp_fused_into(src_bgr, K, R, roi, dst, msk)
         return tl, dst, msk
+
+
+class SphericalWarper(RotationWarper):
+    """SphericalWarper::create(scale) (image_stitching.cpp:927, :939)."""
+    kind = capi.WARP_SPHERICAL
+
+
+class CylindricalWarper(RotationWarper):
+    """CylindricalWarper::create(scale) (image_stitching.cpp:925, :937)."""
+    kind = capi.WARP_CYLINDRICAL
+
+
+class PlaneWarper(RotationWarper):
+    """PlaneWarper::create(scale) with T = 0 (image_stitching.cpp:923, :933)."""
+    kind = capi.WARP_PLANE
+
+
+def make_warper(ctx, scale, warp_type="spherical"):
+    """warper_creator (image_stitching.cpp:917-969) -> create(scale)."""
+    return RotationWarper(ctx, scale, warp_kind(warp_type))
 
 
 # ------------------------------------------------------------------------------------------------
@@ -404,7 +453,7 @@ class Blender:
         x, y, w, h = result_roi(corners, sizes)
         self._size = (w, h)
 
-    def compose_frames(self, frames, scale, cameras, rois):
+    def compose_frames(self, frames, scale, cameras, rois, kind=capi.WARP_SPHERICAL):
         """The compositing loop's per-frame body for all frames in one library call (fused warp + feed each;
         image_stitching.cpp:1154-1164, :1218): the calling thread stays out of the interpreter between launches."""
         n = len(frames)
@@ -414,7 +463,8 @@ class Blender:
         Ks = np.ascontiguousarray(np.stack([np.asarray(c["K"], np.float32).reshape(9) for c in cameras]))
         Rs = np.ascontiguousarray(np.stack([np.asarray(c["R"], np.float32).reshape(9) for c in cameras]))
         rr = (capi.MisRect * n)(*[capi.MisRect(int(r[0]), int(r[1]), int(r[2]), int(r[3])) for r in rois])
-        self.ctx.check(self.ctx.lib.mis_compose_frames(self.h, arr, n, float(scale), Ks.ctypes.data_as(C.c_void_p), Rs.ctypes.data_as(C.c_void_p), rr))
+        self.ctx.check(self.ctx.lib.mis_compose_frames_kind(self.h, int(kind), arr, n, float(scale), Ks.ctypes.data_as(C.c_void_p),
+                                                            Rs.ctypes.data_as(C.c_void_p), rr))
 
     def feed(self, img, mask, tl):
         i, m = as_image(img), as_image(mask)
@@ -924,6 +974,11 @@ def find_homography(ctx, src, dst, thresh=3.0, max_iters=2000, confidence=0.995)
 
 
 # ------------------------------------------------------------------------------------------------
+def check_warp_config(cfg):
+    """warp_type of the config -> MIS_WARP_* kind, or NotImplementedError / ValueError by name before any device work."""
+    return warp_kind(cfg.warp_type)
+
+
 def check_seam_config(cfg):
     if cfg.seam_find_type not in ("no", "voronoi", "dp_color"):
         raise NotImplementedError("seam_find_type %r: 'no', 'voronoi' and 'dp_color' are implemented (dp_colorgrad and the "
@@ -938,7 +993,7 @@ def seam_scale_warp(ctx, cfg, frame_size, frame, camera, warped_image_scale, wor
     w, h = frame_size
     seam_scale = min(1.0, float(np.sqrt(cfg.seam_megapix * 1e6 / (w * h))))
     swa = np.float32(seam_scale / work_scale)
-    warper = SphericalWarper(ctx, np.float32(np.float32(warped_image_scale) * swa))
+    warper = make_warper(ctx, np.float32(np.float32(warped_image_scale) * swa), cfg.warp_type)
     img = resize(ctx, frame, fx=seam_scale, fy=seam_scale) if seam_scale < 1.0 else frame
     K = np.array(camera["K"], np.float32).copy()
     K[0, 0] *= swa; K[0, 2] *= swa; K[1, 1] *= swa; K[1, 2] *= swa
@@ -1051,6 +1106,7 @@ class Stitcher:
     def __init__(self, ctx, frame_size, config=None):
         self.ctx = ctx
         self.cfg = config or StitchConfig()
+        self.kind = check_warp_config(self.cfg)
         self.frame_size = frame_size
         self.finder = OrbFeatureFinder(ctx, frame_size)
         self.matcher = BestOf2NearestMatcher(ctx, self.cfg.match_conf)
@@ -1082,9 +1138,9 @@ class Stitcher:
         if g.size != tuple(self.frame_size):
             frames = {i: resize(self.ctx, frames[i], fx=g.compose_scale, fy=g.compose_scale) for i in indices}
         scale = g.warp_scale
-        warper = SphericalWarper(self.ctx, scale)
+        warper = RotationWarper(self.ctx, scale, self.kind)
         w, h = g.size
-        rois = warp_rois(self.ctx, scale, (w, h), [cameras[i] for i in indices])
+        rois = warp_rois(self.ctx, scale, (w, h), [cameras[i] for i in indices], self.kind)
         corners = [(r[0], r[1]) for r in rois]
         sizes = [(r[2], r[3]) for r in rois]
         if blender is None:
