@@ -26,12 +26,13 @@ JobOutput StitchJob::run(const std::vector<MisImage>& frames) {
     check(cctx_, mis_context_wait(cctx_, ctx_), "mis_context_wait");
     // sizing + zeroing of the panorama pyramids depends on the cameras only: it runs from the finder's hook, once the feature batch is
     // enqueued (warpRoi ends in a synchronisation of the compose stream: in front of the features it kept the main stream idle)
+    const MisImage* work = work_frames(frames);       // (:602, one launch on the main stream)
     prep_.arm([this] { if (spec_ok_) prepare(everyone_); });
     check(ctx_, mis_orb_on_enqueued(orb_, &Hook::fire, &prep_), "mis_orb_on_enqueued");
     // ---- features (:567-622) ----
     std::vector<MisFeatures> feats(n_);
     std::memset(feats.data(), 0, sizeof(MisFeatures) * n_);
-    const int rc_f = mis_orb_detect_batch(orb_, frames.data(), n_, feats.data());
+    const int rc_f = mis_orb_detect_batch(orb_, work, n_, feats.data());
     mis_orb_on_enqueued(orb_, nullptr, nullptr);
     check(ctx_, rc_f, "mis_orb_detect_batch");
     prep_.finish();

@@ -36,8 +36,13 @@ void JobCore::check(MisContext* c, int rc, const char* what) const {
 
 JobCore::JobCore(const char* who, std::string where, int device, void* main_stream, int width, int height, const std::vector<CameraParams>& cameras,
                  const StitchConfig& cfg)
-    : w_(width), h_(height), n_((int)cameras.size()), cams_(cameras), cfg_(cfg), everyone_(n_), mstream_(main_stream), where_(std::move(where)) {
+    : w_(width), h_(height), n_((int)cameras.size()), wg_(work_geometry(cfg, width, height)), cams_(cameras), cfg_(cfg), everyone_(n_), mstream_(main_stream),
+      where_(std::move(where)) {
     std::iota(everyone_.begin(), everyone_.end(), 0);
+    if (wg_.scale != 1.0) {
+        for (auto& c : cams_) { c.focal *= wg_.scale; c.ppx *= wg_.scale; c.ppy *= wg_.scale; }
+        compose_work_aspect_ = 1.0 / wg_.scale;
+    }
     try {
         if (cfg_.features_type != "orb" || cfg_.ba_cost_func != "no" || cfg_.expos_comp_type != "no" || cfg_.seam_find_type != "no")
             throw std::runtime_error(std::string(who) + " runs the hot path (ORB, supplied cameras, no seam-scale step); use mis::Stitcher for the other options");
@@ -47,14 +52,16 @@ JobCore::JobCore(const char* who, std::string where, int device, void* main_stre
         if (mis_context_create(device, cstream_, &cctx_) != MIS_OK) throw std::runtime_error("mis_context_create (compose stream) failed");
         MisOrbParams op;
         mis_orb_default_params(&op);
-        check(ctx_, mis_orb_create(ctx_, &op, w_, h_, &orb_), "mis_orb_create");
+        check(ctx_, mis_orb_create(ctx_, &op, wg_.width, wg_.height, &orb_), "mis_orb_create");
     } catch (...) {
         release();
         throw;
     }
     Ks_.resize((size_t)n_ * 9); Rs_.resize((size_t)n_ * 9);
     for (int i = 0; i < n_; i++) {
-        const Mat3<float> K = cams_[i].K().cast<float>(), R = cams_[i].R.cast<float>();
+        CameraParams cc = cams_[i];
+        if (compose_work_aspect_ != 1.0) { cc.focal *= compose_work_aspect_; cc.ppx *= compose_work_aspect_; cc.ppy *= compose_work_aspect_; }
+        const Mat3<float> K = cc.K().cast<float>(), R = cams_[i].R.cast<float>();
         std::copy(K.m.begin(), K.m.end(), Ks_.begin() + 9 * i);
         std::copy(R.m.begin(), R.m.end(), Rs_.begin() + 9 * i);
     }
@@ -62,7 +69,7 @@ JobCore::JobCore(const char* who, std::string where, int device, void* main_stre
     // rois fail, the jobs compose the kept set after pruning instead of speculating (only a refused roi among the kept frames is an
     // error).  Cameras only, so it is decided here; the spherical roi is never refused.
     if (kind_ != MIS_WARP_SPHERICAL) {
-        const float scale = median_focal(cams_, everyone_);
+        const float scale = warp_scale(everyone_);
         MisRect r;
         for (int i = 0; i < n_ && spec_ok_; i++) spec_ok_ = mis_warper_roi(kind_, scale, w_, h_, &Ks_[9 * i], &Rs_[9 * i], &r) == MIS_OK;
     }
@@ -70,11 +77,24 @@ JobCore::JobCore(const char* who, std::string where, int device, void* main_stre
 
 JobCore::~JobCore() { release(); }
 
+float JobCore::warp_scale(const std::vector<int>& idx) const {
+    const float scale = median_focal(cams_, idx);
+    return compose_work_aspect_ != 1.0 ? scale * static_cast<float>(compose_work_aspect_) : scale;
+}
+
+const MisImage* JobCore::work_frames(const std::vector<MisImage>& frames) {
+    if (wg_.scale == 1.0 || frames.empty()) return frames.data();
+    if (work_.size() < frames.size()) work_.resize(frames.size(), MisImage{});
+    check(ctx_, mis_resize_linear_exact_batch(ctx_, frames.data(), (int)frames.size(), 0, 0, wg_.scale, wg_.scale, work_.data()), "mis_resize_linear_exact_batch");
+    return work_.data();
+}
+
 // a context is destroyed before its stream (its destruction synchronises that stream)
 void JobCore::release() {
     if (cctx_) mis_context_synchronize(cctx_);
     if (ctx_) mis_context_synchronize(ctx_);
     if (!pairwise_.empty()) mis_matches_free(pairwise_.data(), (int)pairwise_.size());
+    if (ctx_) for (auto& im : work_) mis_image_free(ctx_, &im);
     if (blender_) mis_blender_destroy(blender_);
     if (orb_) mis_orb_destroy(orb_);
     if (cctx_) mis_context_destroy(cctx_);
@@ -90,7 +110,7 @@ void JobCore::synchronize() {
 
 JobCore::Compose JobCore::prepare(const std::vector<int>& idx) {
     const int m = (int)idx.size();
-    const float scale = median_focal(cams_, idx);
+    const float scale = warp_scale(idx);
     std::vector<float> Ks((size_t)m * 9), Rs((size_t)m * 9);
     for (int k = 0; k < m; k++) {
         std::copy(Ks_.begin() + 9 * idx[k], Ks_.begin() + 9 * idx[k] + 9, Ks.begin() + 9 * k);
@@ -131,7 +151,7 @@ void JobCore::compose(const std::vector<MisImage>& frames, const std::vector<int
         rois.push_back(rois_[it - idx.begin()]);
     }
     if (fr.empty()) return;     // every frame of a rank was pruned: nothing to warp or feed (the exchanges around still run)
-    check(cctx_, mis_compose_frames_kind(blender_, kind_, fr.data(), (int)fr.size(), median_focal(cams_, idx), Ks.data(), Rs.data(), rois.data()),
+    check(cctx_, mis_compose_frames_kind(blender_, kind_, fr.data(), (int)fr.size(), warp_scale(idx), Ks.data(), Rs.data(), rois.data()),
           "mis_compose_frames_kind");
 }
 

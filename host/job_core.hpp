@@ -56,6 +56,11 @@ protected:
     Compose prepare(const std::vector<int>& idx);
     // the compose stream queued behind the 2-NN pass of the matcher call in flight (from the matcher's hook)
     void fence_knn();
+    // the frames at work scale (:589-603): resized in one launch into images the core keeps from its first run on (allocated by the
+    // library then; an allocation per run would synchronise the device); the frames themselves when the work scale is 1
+    const MisImage* work_frames(const std::vector<MisImage>& frames);
+    // the warper's scale for the frames `idx`: median focal of their work-unit cameras times (float)compose_work_aspect (:884-895, :1116)
+    float warp_scale(const std::vector<int>& idx) const;
     // batched fused warp + feed (rois_ from prepare(idx)) of the frames among `frame_ids` that are in `idx`; frames[q] is frame
     // frame_ids[q].  Both lists ascend, so the frames go in `idx` order.
     void compose(const std::vector<MisImage>& frames, const std::vector<int>& frame_ids, const std::vector<int>& idx);
@@ -63,7 +68,10 @@ protected:
     MisMatchParams reset_matches();
 
     int w_, h_, n_;
-    std::vector<CameraParams> cams_;
+    WorkGeometry wg_;                 // work scale and work image size (features_[i].img_size, the finder's size)
+    double compose_work_aspect_ = 1;  // compose_scale / work_scale with compose_scale = 1 (:1113)
+    std::vector<CameraParams> cams_;  // in work units: focal, ppx, ppy times work_scale (:635-637)
+    std::vector<MisImage> work_;      // work frames (device), kept between runs
     StitchConfig cfg_;
     std::vector<int> everyone_;       // 0 .. n-1
     int kind_ = MIS_WARP_SPHERICAL;   // the warper (cfg_.warp_type)
@@ -75,7 +83,7 @@ protected:
     MisOrb* orb_ = nullptr;
     MisBlender* blender_ = nullptr;
     Compose key_{};
-    std::vector<float> Ks_, Rs_;      // n x 9 each (float, as main() hands them to the warper)
+    std::vector<float> Ks_, Rs_;      // n x 9 each (float, as main() hands them to the warper): the compositing loop's, intrinsics times compose_work_aspect (:1122-1125)
     std::vector<MisRect> rois_;       // of the frames of the current composition (position in idx)
     std::vector<MisMatchesInfo> pairwise_;
 

@@ -160,11 +160,12 @@ JobOutput ShardedJob::run(const std::vector<MisImage>& frames) {
     JobOutput out;
     check(cctx_, mis_context_wait(cctx_, ctx_), "mis_context_wait");
     // ---- features of this rank's block (:567-622); the blender is sized from the finder's hook (cameras only) ----
+    const MisImage* work = work_frames(frames);       // (:602, one launch on the main stream)
     prep_.arm([this] { if (spec_ok_) prepare_multi_band(everyone_); });
     check(ctx_, mis_orb_on_enqueued(orb_, &Hook::fire, &prep_), "mis_orb_on_enqueued");
     std::vector<MisFeatures> local(m);
     std::memset(local.data(), 0, sizeof(MisFeatures) * m);
-    const int rc_f = m > 0 ? mis_orb_detect_batch(orb_, frames.data(), m, local.data()) : MIS_OK;
+    const int rc_f = m > 0 ? mis_orb_detect_batch(orb_, work, m, local.data()) : MIS_OK;
     mis_orb_on_enqueued(orb_, nullptr, nullptr);
     check(ctx_, rc_f, "mis_orb_detect_batch");
     prep_.finish();
@@ -181,7 +182,7 @@ JobOutput ShardedJob::run(const std::vector<MisImage>& frames) {
     std::vector<MisFeatures> feats(n_);
     for (int i = 0; i < n_; i++) {
         MisFeatures& f = feats[i];
-        f.img_idx = i; f.img_w = w_; f.img_h = h_; f.n = cnt_all[i];
+        f.img_idx = i; f.img_w = wg_.width; f.img_h = wg_.height; f.n = cnt_all[i];      // the work image's size (:613)
         f.keypoints = reinterpret_cast<MisKeyPoint*>((uint8_t*)kps_all_.p + kb * i);
         f.descriptors = (uint8_t*)desc_all_.p + db * i;
         f.desc_cols = 32; f.desc_dtype = MIS_U8; f.owner_ = nullptr;

@@ -1,6 +1,6 @@
 // stitch_bench.cpp -- the job of bench.py (4K frames stitched per second, frames resident in HBM) driven from C++:
 // mis::StitchJob over the C ABI, synthetic frames rendered into HBM by synth/libmissynth_gpu.so.
-//   stitch_bench <cams.txt> [--steps K] [--warmup W] [--dump prefix] [--ranks N] [--comm host|rccl] [--one-gpu] [--warp kind]
+//   stitch_bench <cams.txt> [--steps K] [--warmup W] [--dump prefix] [--ranks N] [--comm host|rccl] [--one-gpu] [--warp kind] [--work_megapix f]
 // --ranks N > 1: the SHARDED job (mis::ShardedJob, host/sharded_job.hpp): this process never touches the GPU -- it creates the ranks'
 // rendezvous file, starts N child processes of itself (rank r on GPU r; --one-gpu: all on GPU 0, a rehearsal), relays rank 0's line,
 // and when a rank fails it ends the others and exits non-zero.  --comm rccl (default for N > 1): RCCL called directly; --comm host:
@@ -40,6 +40,7 @@ struct Args {
     std::string cams_path, dump, comm, session, warp = "spherical";
     int steps = 20, warmup = 5, ranks = 1, child_rank = -1;
     bool one_gpu = false;
+    double work_megapix = -1;      // features at work scale (image_stitching.cpp:589-603); -1: full resolution
 };
 
 static bool read_cams(const std::string& path, int* n, int* W, int* H, std::vector<SyCamera>* sy, std::vector<mis::CameraParams>* cams) {
@@ -120,6 +121,7 @@ static int run_single(const Args& a) {
     try {
         mis::StitchConfig cfg;
         cfg.warp_type = a.warp;
+        cfg.work_megapix = a.work_megapix;
         mis::StitchJob job(0, W, H, cams, cfg);
         std::vector<int> everyone(n);
         for (int i = 0; i < n; i++) everyone[i] = i;
@@ -154,6 +156,7 @@ static int run_rank(const Args& a, int rank) {
         std::unique_ptr<mis::Communicator> comm = a.comm == "host" ? mis::make_host_comm(a.session, rank, a.ranks) : mis::make_rccl_comm(a.session, rank, a.ranks);
         mis::StitchConfig cfg;
         cfg.warp_type = a.warp;
+        cfg.work_megapix = a.work_megapix;
         mis::ShardedJob job(device, W, H, cams, *comm, cfg);
         std::vector<MisImage> frames;
         if (render_frames(sy, job.my_frames(), W, H, &frames)) return 1;
@@ -218,7 +221,7 @@ static int launch(const Args& a, int argc, char** argv) {
 }
 
 int main(int argc, char** argv) {
-    if (argc < 2) { std::fprintf(stderr, "usage: stitch_bench cams.txt [--steps K] [--warmup W] [--dump prefix] [--ranks N] [--comm host|rccl] [--one-gpu] [--warp spherical|cylindrical|plane]\n"); return 2; }
+    if (argc < 2) { std::fprintf(stderr, "usage: stitch_bench cams.txt [--steps K] [--warmup W] [--dump prefix] [--ranks N] [--comm host|rccl] [--one-gpu] [--warp spherical|cylindrical|plane] [--work_megapix f]\n"); return 2; }
     Args a;
     a.cams_path = argv[1];
     for (int i = 2; i < argc; i++) {
@@ -229,6 +232,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--comm") && i + 1 < argc) a.comm = argv[++i];
         else if (!std::strcmp(argv[i], "--one-gpu")) a.one_gpu = true;
         else if (!std::strcmp(argv[i], "--warp") && i + 1 < argc) a.warp = argv[++i];
+        else if (!std::strcmp(argv[i], "--work_megapix") && i + 1 < argc) a.work_megapix = std::strtod(argv[++i], nullptr);
         else if (!std::strcmp(argv[i], "--rank-child") && i + 1 < argc) a.child_rank = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--session") && i + 1 < argc) a.session = argv[++i];
     }

@@ -17,7 +17,7 @@
 int main(int argc, char** argv) {
     if (argc < 2) {
         std::cout << "usage: " << argv[0] << " <image directory> [--features orb|sift] [--ba no|reproj] [--ba_refine_mask xxxxx] [--wave_correct horiz|vert|no]\n"
-                     "       [--expos_comp no|gain_blocks] [--seam no|voronoi|dp_color] [--warp spherical|cylindrical|plane] [--blend no|feather|multiband] [--conf_thresh f] [--match_conf f] [--compose_megapix f] [--seam_megapix f]\n"
+                     "       [--expos_comp no|gain_blocks] [--seam no|voronoi|dp_color] [--warp spherical|cylindrical|plane] [--blend no|feather|multiband] [--conf_thresh f] [--match_conf f] [--compose_megapix f] [--seam_megapix f] [--work_megapix f]\n"
                      "(the reference sets these as globals, image_stitching.cpp:49-85)\n";
         return -1;
     }
@@ -34,6 +34,7 @@ int main(int argc, char** argv) {
         else if (k == "--blend") cfg.blend_type = v == "no" ? MIS_BLEND_NO : (v == "feather" ? MIS_BLEND_FEATHER : MIS_BLEND_MULTI_BAND);
         else if (k == "--compose_megapix") cfg.compose_megapix = std::strtod(v.c_str(), nullptr);
         else if (k == "--seam_megapix") cfg.seam_megapix = std::strtod(v.c_str(), nullptr);
+        else if (k == "--work_megapix") cfg.work_megapix = std::strtod(v.c_str(), nullptr);
         else if (k == "--conf_thresh") cfg.conf_thresh = std::strtof(v.c_str(), nullptr);
         else if (k == "--match_conf") cfg.match_conf = std::strtof(v.c_str(), nullptr);
         else { std::cout << "unknown option " << k << "\n"; return -1; }
@@ -74,7 +75,8 @@ int main(int argc, char** argv) {
         }
         mis::Stitcher st(0, cfg);
         mis::StitchResult r = st.stitch(frames, cams);
-        // the reference checkpoints the refined cameras and the kept indices (image_stitching.cpp:707-708)
+        // the reference checkpoints the refined cameras and the kept indices (image_stitching.cpp:707-708); with --work_megapix the
+        // cameras are in work units, as the reference's are at that point
         mis::serializeCameraParams(r.cameras, (fs::path(argv[1]) / "cams.data").string());
         mis::serializeIndices(r.indices, (fs::path(argv[1]) / "indices.data").string());
         mis::writePPM((fs::path(argv[1]) / "result.ppm").string(), r.pano);

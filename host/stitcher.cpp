@@ -75,7 +75,9 @@ StitchResult Stitcher::stitch(const std::vector<HostImage>& frames, const std::v
     std::vector<CameraParams> cameras = cams_in;
     const int W = frames[0].width, H = frames[0].height;
 
-    // ---- features (image_stitching.cpp:545, :567-622; work_megapix = -1: full resolution) ----
+    // ---- features (image_stitching.cpp:545, :567-622) on the work images (:589-603: every frame resized by work_scale, one launch) ----
+    const WorkGeometry wg = work_geometry(cfg_, W, H);
+    const double work_scale = wg.scale;
     double t = now();
     if (cfg_.features_type != "orb" && cfg_.features_type != "sift") throw std::runtime_error("Unknown 2D features type: '" + cfg_.features_type + "'.");
     if (cfg_.ba_cost_func != "no" && cfg_.ba_cost_func != "reproj")
@@ -90,15 +92,22 @@ StitchResult Stitcher::stitch(const std::vector<HostImage>& frames, const std::v
     std::vector<MisFeatures> features(n);
     std::vector<MisImage> views(n);
     for (int i = 0; i < n; i++) views[i] = view(frames[i]);
+    std::vector<MisImage> work(work_scale < 1.0 ? n : 0, MisImage{});       // allocated by the library, in HBM
+    if (work_scale < 1.0) check(mis_resize_linear_exact_batch(ctx_, views.data(), n, 0, 0, work_scale, work_scale, work.data()), "mis_resize_linear_exact_batch");
+    const MisImage* imgs = work_scale < 1.0 ? work.data() : views.data();
     if (cfg_.features_type == "sift") {
-        check(mis_sift_create(ctx_, nullptr, W, H, &sift), "mis_sift_create");
-        check(mis_sift_detect_batch(sift, views.data(), n, features.data()), "mis_sift_detect_batch");
+        check(mis_sift_create(ctx_, nullptr, wg.width, wg.height, &sift), "mis_sift_create");
+        check(mis_sift_detect_batch(sift, imgs, n, features.data()), "mis_sift_detect_batch");
     } else {
         MisOrbParams op;
         mis_orb_default_params(&op);
-        check(mis_orb_create(ctx_, &op, W, H, &orb), "mis_orb_create");
-        check(mis_orb_detect_batch(orb, views.data(), n, features.data()), "mis_orb_detect_batch");
+        check(mis_orb_create(ctx_, &op, wg.width, wg.height, &orb), "mis_orb_create");
+        check(mis_orb_detect_batch(orb, imgs, n, features.data()), "mis_orb_detect_batch");
     }
+    for (auto& im : work) mis_image_free(ctx_, &im);
+    // cam.focal, ppx, ppy *= work_scale (:635-637): matching, bundle adjustment and the median focal are in work units
+    if (work_scale != 1.0)
+        for (auto& c : cameras) { c.focal *= work_scale; c.ppx *= work_scale; c.ppy *= work_scale; }
     for (int i = 0; i < n; i++) {
         features[i].img_idx = i;
         std::cout << "Features in image #" << i + 1 << ": " << features[i].n << std::endl;
@@ -172,7 +181,7 @@ StitchResult Stitcher::stitch(const std::vector<HostImage>& frames, const std::v
     t = now();
     double compose_scale = 1.0;
     if (cfg_.compose_megapix > 0) compose_scale = std::min(1.0, std::sqrt(cfg_.compose_megapix * 1e6 / ((double)W * H)));
-    const double compose_work_aspect = compose_scale / 1.0;     // work_scale = 1: features at full resolution
+    const double compose_work_aspect = compose_scale / work_scale;     // :1113
     const bool compose_resized = std::abs(compose_scale - 1) > 1e-1;
     const int cW = compose_resized ? (int)std::nearbyint(W * compose_scale) : W, cH = compose_resized ? (int)std::nearbyint(H * compose_scale) : H;
     const float compose_warp_scale = warped_image_scale * static_cast<float>(compose_work_aspect);
@@ -209,7 +218,7 @@ StitchResult Stitcher::stitch(const std::vector<HostImage>& frames, const std::v
     std::vector<MisImage> masks_warped(kept);
     if (seam_step) {
         const double seam_scale = std::min(1.0, std::sqrt(cfg_.seam_megapix * 1e6 / ((double)W * H)));
-        const float swa = (float)seam_scale;   // seam_work_aspect with work_scale = 1
+        const float swa = (float)(seam_scale / work_scale);   // seam_work_aspect (:607)
         const float seam_warp_scale = warped_image_scale * swa;
         std::vector<MisImage> images_warped(kept);
         std::vector<MisPoint> seam_corners(kept);

@@ -2,6 +2,7 @@
 // main() (image_stitching/image_stitching.cpp:281-1232) re-authored over the C ABI of libmistitch
 // (include/mistitch.h).  No OpenCV: plain PODs, std::vector, and the library's opaque handles.
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <stdexcept>
@@ -15,6 +16,7 @@ namespace mis {
 
 // The reference's globals-as-config (image_stitching.cpp:49-85), same defaults.
 struct StitchConfig {
+    // work_megapix >= 0: features, matching and bundle adjustment on frames resized by work_scale (:589-603, work_geometry below)
     double work_megapix = -1, seam_megapix = 0.1, compose_megapix = -1;  // compose -1: full-resolution warp + blend
     float conf_thresh = 0.95f;
     float match_conf = 0.32f;
@@ -47,6 +49,17 @@ inline int warp_kind(const std::string& t) {
     throw std::runtime_error("Can't create the following warper '" + t + "'");
 }
 
+// work scale of main() (:589-603): 1 when work_megapix < 0, else min(1, sqrt(work_megapix * 1e6 / area)) from the first frame; the
+// work image has the size cv::resize gives for that factor (cvRound).  No |scale - 1| > 0.1 test here, unlike the compose loop.
+struct WorkGeometry { double scale = 1; int width = 0, height = 0; };
+inline WorkGeometry work_geometry(const StitchConfig& cfg, int width, int height) {
+    WorkGeometry g{1.0, width, height};
+    if (cfg.work_megapix < 0) return g;
+    g.scale = std::min(1.0, std::sqrt(cfg.work_megapix * 1e6 / ((double)width * height)));
+    if (g.scale < 1.0) { g.width = (int)std::nearbyint(width * g.scale); g.height = (int)std::nearbyint(height * g.scale); }
+    return g;
+}
+
 // cv::detail::CameraParams as main() fills it (focal, aspect, ppx, ppy, R, t)
 struct CameraParams {
     double focal = 1, aspect = 1, ppx = 0, ppy = 0;
@@ -75,7 +88,7 @@ struct StitchResult {
     HostImage pano;      // 8UC3 (saturate_cast<uchar> of the 16SC3 result, as imwrite does)
     HostImage mask;      // 8UC1
     std::vector<int> indices;          // images kept by the biggest-component pruning
-    std::vector<CameraParams> cameras; // of the kept images, after the optional refinement
+    std::vector<CameraParams> cameras; // of the kept images, after the optional refinement; in work units (focal, ppx, ppy times work_scale, :635-637)
     std::vector<int> num_features;
     std::vector<double> confidence;    // n x n
     double t_features = 0, t_matching = 0, t_compositing = 0;

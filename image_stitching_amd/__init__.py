@@ -13,8 +13,8 @@ from ._capi import (BLEND_FEATHER, BLEND_MULTI_BAND, BLEND_NO, BORDER_CONSTANT, 
 from .stitching import (BestOf2NearestMatcher, Blender, BlocksGainCompensator, NoSeamFinder, VoronoiSeamFinder, DpSeamFinder, Context, FeatherBlender, ImageFeatures, MatchesInfo,
                         MisError, MultiBandBlender, OrbFeatureFinder, SiftFeatureFinder, SphericalWarper, CylindricalWarper, PlaneWarper,
                         RotationWarper, StitchConfig, Stitcher,
-                        blend_config, bundle_adjust_reproj, computeImageFeatures, find_homography, leaveBiggestComponent, resize, result_roi,
-                        rotate, seam_mask_apply, warp_roi, wave_correct)
+                        blend_config, bundle_adjust_reproj, computeImageFeatures, find_homography, leaveBiggestComponent, resize, resize_batch, result_roi,
+                        rotate, seam_mask_apply, warp_roi, wave_correct, work_geometry)
 
 __all__ = [
     "Context", "MisError", "SphericalWarper", "Blender", "MultiBandBlender", "FeatherBlender", "OrbFeatureFinder", "SiftFeatureFinder",
@@ -22,5 +22,5 @@ __all__ = [
     "find_homography", "warp_roi", "result_roi", "blend_config", "StitchConfig", "Stitcher", "resize", "rotate",
     "seam_mask_apply", "bundle_adjust_reproj", "wave_correct", "BlocksGainCompensator", "NoSeamFinder", "VoronoiSeamFinder", "DpSeamFinder",
     "INTER_NEAREST", "INTER_LINEAR", "BORDER_CONSTANT", "BORDER_REFLECT", "BLEND_NO", "BLEND_FEATHER",
-    "BLEND_MULTI_BAND", "CylindricalWarper", "PlaneWarper", "RotationWarper", "WARP_SPHERICAL", "WARP_CYLINDRICAL", "WARP_PLANE",
+    "BLEND_MULTI_BAND", "resize_batch", "work_geometry", "CylindricalWarper", "PlaneWarper", "RotationWarper", "WARP_SPHERICAL", "WARP_CYLINDRICAL", "WARP_PLANE",
 ]

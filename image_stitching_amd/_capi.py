@@ -143,6 +143,7 @@ PROTOTYPES = {
     "mis_warper_warp_fused_batch": (_i, [_vp, _i, _P(MisImage), _i, C.c_float, _P(C.c_float), _P(C.c_float), _P(MisRect), _P(MisImage), _P(MisImage), _P(MisPoint)]),
     "mis_warp_spherical_fused": (_i, [_vp, _P(MisImage), _f, _vp, _vp, _P(MisImage), _P(MisImage), _P(MisPoint)]),
     "mis_resize_linear_exact": (_i, [_vp, _P(MisImage), _i, _i, C.c_double, C.c_double, _P(MisImage)]),
+    "mis_resize_linear_exact_batch": (_i, [_vp, _P(MisImage), _i, _i, _i, C.c_double, C.c_double, _P(MisImage)]),
     "mis_rotate": (_i, [_vp, _P(MisImage), _i, _P(MisImage)]),
     "mis_seam_mask_apply": (_i, [_vp, _P(MisImage), _P(MisImage)]),
     "mis_compensator_create": (_i, [_vp, _i, _i, _i, _P(_vp)]),

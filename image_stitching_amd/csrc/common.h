@@ -17,6 +17,7 @@ struct MisContext {
     int device = 0;
     int num_cu = 256;   // compute units of the device (persistent kernels size their grids from it)
     MisWorkspace* match_ws = nullptr;
+    MisWorkspace* resize_ws = nullptr;    // device coefficient tables of mis_resize_linear_exact_batch, one per geometry (imgops.hip)
     // recycled device blocks (size, pointer): feature sets are allocated and released every frame, and a
     // hipFree would synchronise the whole device each time
     std::vector<std::pair<size_t, void*>> pool;

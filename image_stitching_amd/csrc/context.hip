@@ -82,6 +82,7 @@ extern "C" int mis_context_destroy(MisContext* ctx) {
     hipSetDevice(ctx->device);
     hipStreamSynchronize(ctx->stream);
     delete ctx->match_ws;
+    delete ctx->resize_ws;
     for (auto& b : ctx->pool) hipFree(b.second);
     if (ctx->stage) hipFree(ctx->stage);
     if (ctx->roi_pinned) hipHostFree(ctx->roi_pinned);

@@ -155,8 +155,12 @@ class HipEngine:
         self.warp_type = self.cfg.warp_type            # the warper this engine runs (StitchJob checks it against the job's)
         self.kind = st.check_warp_config(self.cfg)
         self.frame_size = frame_size
+        # features come from the work image (image_stitching.cpp:589-603, :613): the finder is sized for it, and the work frames
+        # live in buffers allocated on first use and kept (an allocation per run would synchronise the device)
+        self.work_scale, self.work_size = st.work_geometry(self.cfg, frame_size)
+        self._work_frames = []
         # finder per features_type (image_stitching.cpp:543-563): ORB, or SIFT (float descriptors -> the L2 matcher)
-        self.finder = st.SiftFeatureFinder(ctx, frame_size) if self.cfg.features_type == "sift" else st.OrbFeatureFinder(ctx, frame_size)
+        self.finder = st.SiftFeatureFinder(ctx, self.work_size) if self.cfg.features_type == "sift" else st.OrbFeatureFinder(ctx, self.work_size)
         self.matcher = st.BestOf2NearestMatcher(ctx, self.cfg.match_conf)
         self.blender = None
         self._keep = []
@@ -173,8 +177,17 @@ class HipEngine:
         self.speculative_compose = True
 
     # ---- features ----
+    def work_frames(self, frames):
+        """cv::resize(full_img, img, Size(), work_scale, work_scale, INTER_LINEAR_EXACT) (image_stitching.cpp:602) of these frames
+        in one launch, into the engine's buffers; the frames themselves when the work scale is 1."""
+        if self.work_scale == 1.0 or not frames:
+            return frames
+        while len(self._work_frames) < len(frames):       # 8UC3, as the finders take them
+            self._work_frames.append(st._empty_image(self.ctx, self.work_size[1], self.work_size[0], 3, torch.uint8))
+        return st.resize_batch(self.ctx, frames, self.work_scale, self.work_scale, out=self._work_frames[:len(frames)])
+
     def detect(self, frames):
-        return self.finder.detect_batch(frames)
+        return self.finder.detect_batch(self.work_frames(frames))
 
     def feature_counts(self, feats):
         return torch.tensor([len(f) for f in feats], dtype=torch.int32, device=self.ctx.device)
@@ -202,7 +215,7 @@ class HipEngine:
         """Gathered tensors [n, ...] -> ImageFeatures views (no copies; tensors kept alive)."""
         self._keep = [kps_all, desc_all, counts_all]
         counts = counts_all.cpu().tolist()
-        w, h = self.frame_size
+        w, h = self.work_size          # features[i].img_size is the work image's (image_stitching.cpp:613)
         sift = self.cfg.features_type == "sift"
         out = []
         for i, n in enumerate(counts):
@@ -246,7 +259,7 @@ class HipEngine:
     # ---- seam-scale step (exposure compensation + seam finder) ----
     def seam_local(self, frames, cams, scale):
         """This rank's frames at seam scale -> [(corner, image 8UC3 tensor, mask 8U tensor)] (compose stream)."""
-        return [st.seam_scale_warp(self.cctx, self.cfg, self.frame_size, f, c, scale) for f, c in zip(frames, cams)]
+        return [st.seam_scale_warp(self.cctx, self.cfg, self.frame_size, f, c, scale, self.work_scale) for f, c in zip(frames, cams)]
 
     def seam_pack(self, item, cap):
         """(corner, image, mask) -> one uint8 tensor of cap * 4 bytes (image, then mask) for the all-gather."""
@@ -449,14 +462,22 @@ class StitchJob:
         engine_warp = getattr(self.engine, "warp_type", "spherical")
         if engine_warp != self.cfg.warp_type:
             raise NotImplementedError("warp_type %r: the engine %s warps %r only" % (self.cfg.warp_type, type(self.engine).__name__, engine_warp))
-        self.cams = cameras
-        self.cams0 = cameras          # the caller's cameras; self.cams holds the refined ones after a run with bundle adjustment
+        # work scale (image_stitching.cpp:589-603): the engine detects on resized frames and everything between features and
+        # composition is in work units; an engine that does not resize is refused, not run at full resolution
+        self.work_scale, self.work_size = st.work_geometry(self.cfg, frame_size)
+        if self.work_scale != 1.0 and getattr(self.engine, "work_scale", 1.0) != self.work_scale:
+            raise NotImplementedError("work_megapix %r (work scale %.6f): the engine %s does not resize frames to work scale"
+                                      % (self.cfg.work_megapix, self.work_scale, type(self.engine).__name__))
+        self.cams0 = cameras          # the caller's cameras, in full-resolution pixels
+        # cam.focal, ppx, ppy *= work_scale before matching (:635-637): what every run starts from
+        self.work_cams0 = cameras if self.work_scale == 1.0 else [st.scaled_camera(c, self.work_scale) for c in cameras]
+        self.cams = self.work_cams0   # work units; holds the refined cameras after a run with bundle adjustment
         self.n = len(cameras)
         self.rank, self.world = rank, world_size
         self.comm = Comm(rank, world_size, group, always_collective)
         self.my_frames = frame_block(self.n, rank, world_size)
         self.frame_size = frame_size
-        self.scale = st.Stitcher.warped_image_scale(cameras)
+        self.scale = st.Stitcher.warped_image_scale(self.cams)
         self.force_collectives = force_collectives   # run the pack / gather / reduce code even at world size 1 (tests)
         self.seam_needed = self.cfg.expos_comp_type != "no" or self.cfg.seam_find_type != "no"
         counts = {len(frame_block(self.n, r, world_size)) for r in range(world_size)}
@@ -494,7 +515,7 @@ class StitchJob:
         # the reference takes the median focal of the KEPT cameras (image_stitching.cpp:746-748, :884-895)
         self.scale = st.Stitcher.warped_image_scale([self.cams[i] for i in indices])
         # compose scale (:1105-1140): warper scale, intrinsics and frame size of the compositing loop
-        g = st.compose_geometry(self.cfg, self.frame_size, self.scale)
+        g = st.compose_geometry(self.cfg, self.frame_size, self.scale, self.work_scale)
         self._geom = g
         ccams = {i: st.scaled_camera(self.cams[i], g.aspect) for i in indices} if g.aspect != 1.0 else {i: self.cams[i] for i in indices}
         if g.size != tuple(self.frame_size) and not hasattr(eng, "resize_frame"):
@@ -674,7 +695,7 @@ class StitchJob:
         matching starts.  The spherical roi is never refused."""
         if self.kind == capi.WARP_SPHERICAL:
             return True
-        g = st.compose_geometry(self.cfg, self.frame_size, st.Stitcher.warped_image_scale(self.cams))
+        g = st.compose_geometry(self.cfg, self.frame_size, st.Stitcher.warped_image_scale(self.cams), self.work_scale)
         try:
             for c in self.cams:
                 c = st.scaled_camera(c, g.aspect) if g.aspect != 1.0 else c
@@ -807,8 +828,8 @@ class StitchJob:
                     # the adjuster needs every connected pair's inlier matches, and the pairs were dealt over the ranks: every
                     # rank contributes the entries it owns, all ranks assemble the same table and run the same (host) solver
                     pm = self.engine.matches_from_entries(self.comm.all_gather_objects(self.engine.match_entries(pm, self.cfg.conf_thresh)), self.n)
-                refined = self.engine.refine_cameras(feats, pm, indices, self.cams0)     # every run starts from the cameras the job was given
-                self.cams = list(self.cams0)
+                refined = self.engine.refine_cameras(feats, pm, indices, self.work_cams0)     # every run starts from the cameras the job was given
+                self.cams = list(self.work_cams0)
                 for i, c in zip(indices, refined):
                     self.cams[i] = c
                 self.scale = st.Stitcher.warped_image_scale([self.cams[i] for i in indices])

@@ -308,6 +308,25 @@ def resize(ctx, src, dsize=None, fx=0.0, fy=0.0):
     return dst
 
 
+def resize_batch(ctx, frames, fx, fy, out=None):
+    """cv::resize(frame, dst, Size(), fx, fy, INTER_LINEAR_EXACT) for n device frames of one size and type in one launch
+    (mis_resize_linear_exact_batch; the work-scale resize of image_stitching.cpp:602) -> list of device images.  `out`: images
+    of the destination size to write into (a job allocates them once); allocated here when None."""
+    frames = list(frames)
+    n = len(frames)
+    if n == 0:
+        return []
+    simgs = [as_image(f) for f in frames]
+    if out is None:
+        dw, dh = int(np.rint(simgs[0].width * fx)), int(np.rint(simgs[0].height * fy))   # cvRound: half to even
+        out = [_empty_image(ctx, dh, dw, simgs[0].channels, torch.uint8) for _ in range(n)]
+    out = list(out)[:n]
+    sa = (capi.MisImage * n)(*simgs)
+    da = (capi.MisImage * n)(*[as_image(o) for o in out])
+    ctx.check(ctx.lib.mis_resize_linear_exact_batch(ctx.h, sa, n, 0, 0, float(fx), float(fy), da))
+    return out
+
+
 def rotate(ctx, src, code):
     """cv::rotate(src, dst, code) on the device (8UC1 / 8UC3)."""
     simg = as_image(src)
@@ -1021,27 +1040,42 @@ def seam_solve(ctx, cfg, corners, images_warped, masks_warped):
 @dataclass
 class ComposeGeometry:
     compose_scale: float      # min(1, sqrt(compose_megapix * 1e6 / area)); 1 when compose_megapix <= 0
-    aspect: float             # compose_work_aspect = compose_scale / work_scale (work_scale = 1: features at full resolution)
+    aspect: float             # compose_work_aspect = compose_scale / work_scale
     warp_scale: float         # warped_image_scale * (float)compose_work_aspect
     size: tuple               # frame size inside the compositing loop
 
 
-def compose_geometry(cfg, frame_size, warped_image_scale):
+def work_geometry(cfg, frame_size):
+    """The work scale of main() (image_stitching.cpp:589-603) -> (work_scale, (work_w, work_h)): 1 and the frame as it is when
+    work_megapix < 0, otherwise min(1, sqrt(work_megapix * 1e6 / area)) and the size cv::resize gives for that factor (cvRound);
+    there is no |scale - 1| > 0.1 test here, unlike the compose loop.  A scale of exactly 1 is the identity."""
+    w, h = int(frame_size[0]), int(frame_size[1])
+    if cfg.work_megapix < 0:
+        return 1.0, (w, h)
+    ws = min(1.0, float(np.sqrt(cfg.work_megapix * 1e6 / (w * h))))
+    if ws == 1.0:
+        return 1.0, (w, h)
+    return ws, (int(round(w * ws)), int(round(h * ws)))      # cvRound: half to even, as Python's round
+
+
+def compose_geometry(cfg, frame_size, warped_image_scale, work_scale=1.0):
     """The scales of the compositing loop (image_stitching.cpp:1105-1146): compose_scale from compose_megapix, the warper's scale
-    and the intrinsics multiplied by compose_work_aspect, and -- only when |compose_scale - 1| > 0.1, as the reference tests it --
-    frames and their sizes resized (cvRound)."""
+    and the intrinsics multiplied by compose_work_aspect = compose_scale / work_scale, and -- only when |compose_scale - 1| > 0.1,
+    as the reference tests it -- frames and their sizes resized (cvRound).  warped_image_scale and the cameras it is applied to are
+    in work units (:635-637)."""
     w, h = frame_size
     cs = 1.0
     if cfg.compose_megapix > 0:
         cs = min(1.0, float(np.sqrt(cfg.compose_megapix * 1e6 / (w * h))))
-    aspect = cs / 1.0
+    aspect = cs / work_scale
     warp_scale = float(np.float32(warped_image_scale) * np.float32(aspect))
     size = (int(round(w * cs)), int(round(h * cs))) if abs(cs - 1) > 1e-1 else (int(w), int(h))      # cvRound: half to even, as Python's round
     return ComposeGeometry(cs, aspect, warp_scale, size)
 
 
 def scaled_camera(cam, aspect):
-    """cameras[i].focal *= a; ppx *= a; ppy *= a (image_stitching.cpp:1122-1125), in double like CameraParams; K() = [f 0 ppx; 0 f*aspect ppy]"""
+    """cameras[i].focal *= a; ppx *= a; ppy *= a (image_stitching.cpp:635-637 with the work scale, :1122-1125 with
+    compose_work_aspect), in double like CameraParams; K() = [f 0 ppx; 0 f*aspect ppy]"""
     K = np.array(cam["K"], np.float64)
     f = K[0, 0] * aspect
     K2 = K.copy()
@@ -1058,7 +1092,8 @@ def scaled_camera(cam, aspect):
 @dataclass
 class StitchConfig:
     """The reference's globals-as-config (image_stitching.cpp:49-85), same defaults; compose_megapix
-    <= 0 keeps frames at full resolution through warp + blend (the throughput configuration)."""
+    <= 0 keeps frames at full resolution through warp + blend (the throughput configuration).  work_megapix >= 0: features,
+    matching and bundle adjustment at work scale (:589-603); the cameras a caller passes are always in full-resolution pixels."""
     work_megapix: float = -1
     seam_megapix: float = 0.1
     compose_megapix: float = 0.4
@@ -1108,10 +1143,23 @@ class Stitcher:
         self.cfg = config or StitchConfig()
         self.kind = check_warp_config(self.cfg)
         self.frame_size = frame_size
-        self.finder = OrbFeatureFinder(ctx, frame_size)
+        # features come from the work image (image_stitching.cpp:602, :613): the finder is sized for it
+        self.work_scale, self.work_size = work_geometry(self.cfg, frame_size)
+        self.finder = OrbFeatureFinder(ctx, self.work_size)
         self.matcher = BestOf2NearestMatcher(ctx, self.cfg.match_conf)
 
+    def work_cameras(self, cameras):
+        """The caller's full-resolution cameras in work units (cam.focal, ppx, ppy *= work_scale, image_stitching.cpp:635-637);
+        list or dict, as given."""
+        if self.work_scale == 1.0:
+            return cameras
+        if isinstance(cameras, dict):
+            return {i: scaled_camera(c, self.work_scale) for i, c in cameras.items()}
+        return [scaled_camera(c, self.work_scale) for c in cameras]
+
     def features(self, frames):
+        if self.work_scale < 1.0:
+            frames = resize_batch(self.ctx, frames, self.work_scale, self.work_scale)
         return self.finder.detect_batch(frames)
 
     def match(self, feats, rank=0, world_size=1):
@@ -1127,12 +1175,13 @@ class Stitcher:
         return float(np.float32(focals[n // 2 - 1] + focals[n // 2]) * np.float32(0.5))
 
     def compose(self, frames, cameras, indices=None, blender=None):
-        """Compositing loop (image_stitching.cpp:1086-1225), frames and intrinsics at compose scale (compose_megapix)."""
+        """Compositing loop (image_stitching.cpp:1086-1225), frames and intrinsics at compose scale (compose_megapix).  `cameras`
+        are in work units (work_cameras of the caller's, or what refine_cameras returned)."""
         indices = list(range(len(frames)) if indices is None else indices)
         # the reference replaces `cameras` by the kept subset (image_stitching.cpp:746-748) before the median focal (:884-895)
         scale = self.warped_image_scale([cameras[i] for i in indices])
-        g = compose_geometry(self.cfg, self.frame_size, scale)
-        seam = self.seam_step(frames, cameras, indices, scale)      # at seam scale, with the un-scaled intrinsics (:973-1065)
+        g = compose_geometry(self.cfg, self.frame_size, scale, self.work_scale)
+        seam = self.seam_step(frames, cameras, indices, scale, self.work_scale)      # at seam scale, with the work-unit intrinsics (:973-1065)
         if g.aspect != 1.0:
             cameras = {i: scaled_camera(cameras[i], g.aspect) for i in indices}
         if g.size != tuple(self.frame_size):
@@ -1163,12 +1212,13 @@ class Stitcher:
             blender.feed(img_s, mask, tl)
         return blender.blend()
 
-    def seam_step(self, frames, cameras, indices, warped_image_scale, work_scale=1.0):
+    def seam_step(self, frames, cameras, indices, warped_image_scale, work_scale=None):
         """The seam-scale pass of main() (image_stitching.cpp:604-622 resize, :973-990 warp, :1002-1023 exposure
         compensator feed, :1029-1065 seam finder) -> (compensator | None, masks_warped) or None when both are off."""
         check_seam_config(self.cfg)
         if self.cfg.expos_comp_type == "no" and self.cfg.seam_find_type == "no":
             return None
+        work_scale = self.work_scale if work_scale is None else work_scale
         items = [seam_scale_warp(self.ctx, self.cfg, self.frame_size, frames[i], cameras[i], warped_image_scale, work_scale) for i in indices]
         return seam_solve(self.ctx, self.cfg, [it[0] for it in items], [it[1] for it in items], [it[2] for it in items])
 
@@ -1176,5 +1226,5 @@ class Stitcher:
         feats = self.features(frames)
         pm = self.match(feats)
         idx = leaveBiggestComponent(pm, len(frames), self.cfg.conf_thresh)
-        result, mask = self.compose(frames, cameras, list(idx))
+        result, mask = self.compose(frames, self.work_cameras(cameras), list(idx))
         return result, mask, feats, pm, idx

@@ -286,6 +286,20 @@ int mis_sift_debug_level(MisSift* sift, const MisImage* bgr, int octave, int lay
  * scale), :1144 (compose scale).  8UC1 / 8UC3.  dst_w, dst_h > 0: that size (scale = dsize / ssize); otherwise
  * dsize = (cvRound(w * fx), cvRound(h * fy)) and the coordinate scale is exactly 1/fx, 1/fy, as in resize(). */
 int mis_resize_linear_exact(MisContext* ctx, const MisImage* src, int dst_w, int dst_h, double fx, double fy, MisImage* dst);
+/* The work-scale resize of every frame of a job in one launch -- replaces the loop body image_stitching.cpp:589-603
+ * (work_megapix < 0: work_scale = 1, the frame is used as it is; otherwise work_scale = min(1, sqrt(work_megapix * 1e6 / area))
+ * from the first frame and cv::resize(full_img, img, Size(), work_scale, work_scale, INTER_LINEAR_EXACT) for every frame, with no
+ * |scale - 1| > 0.1 test).  What follows from the work scale is the caller's: features carry the work size (:613), seam_work_aspect =
+ * seam_scale / work_scale (:607), cameras *= work_scale before matching (:635-637), compose_work_aspect = compose_scale /
+ * work_scale (:1113-1125).
+ * n images of one size and type (8UC1 / 8UC3) -> n images; the size / factor rules and the 8.8 fixed-point arithmetic of
+ * mis_resize_linear_exact, bit for bit.  Outputs follow the library's convention (data == NULL: allocated in HBM, kept by the
+ * caller for the next call; otherwise exactly the destination size).  The coefficient tables are cached on the device per
+ * geometry (grow-only, released with the context): with device images a call that finds its geometry uploads nothing and never
+ * waits for the stream; the first call of a geometry uploads through the context's pinned staging and waits for that copy.
+ * Host images are accepted as the single entry accepts them (staged through HBM, a copy and a wait per image).
+ * Images of different size or type, n <= 0, null pointers: MIS_E_INVALID; other types than 8UC1 / 8UC3: MIS_E_UNSUPPORTED. */
+int mis_resize_linear_exact_batch(MisContext* ctx, const MisImage* srcs, int n, int dst_w, int dst_h, double fx, double fy, MisImage* dsts);
 /* cv::rotate(src, dst, code) -- replaces image_stitching.cpp:571 (ROTATE_90_CLOCKWISE = 0), :576 (ROTATE_180 = 1);
  * 2 = ROTATE_90_COUNTERCLOCKWISE.  8UC1 / 8UC3. */
 int mis_rotate(MisContext* ctx, const MisImage* src, int rotate_code, MisImage* dst);
