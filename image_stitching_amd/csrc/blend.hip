@@ -1118,7 +1118,7 @@ void feed_tile_rect(const MisBlender* b, int w, int h, MisPoint tl, int* otnx, i
 // n frames into the multi-band pyramids, bit-identical to n single feeds in the same order: the Gaussian pyramids of all
 // frames are built first (batched launches, see FeedBatch), then the Laplacians are accumulated frame by frame (the f32 weight
 // sums keep the feed order).
-int feed_multiband_batch(MisBlender* b, const MisImage* imgs, const DevImage* dimg, const DevImage* dmask, const MisPoint* tls, int n) {
+int feed_multiband_batch(MisBlender* b, const MisImage* imgs, const DevView* dimg, const DevView* dmask, const MisPoint* tls, int n) {
     MisContext* ctx = b->ctx;
     const int nb = b->num_bands;
     const MisRect& R = b->roi;
@@ -1224,7 +1224,7 @@ int feed_multiband_batch(MisBlender* b, const MisImage* imgs, const DevImage* di
     return MIS_OK;
 }
 
-int feed_feather(MisBlender* b, const DevImage& dimg, const DevImage& dmask, int w, int h, MisPoint tl) {
+int feed_feather(MisBlender* b, const DevView& dimg, const DevView& dmask, int w, int h, MisPoint tl) {
     MisContext* ctx = b->ctx;
     MIS_CHECK(ctx, w <= FT_MAXCHUNK * FT_TB * FT_PX, MIS_E_UNSUPPORTED, "feather blender: frames wider than %d pixels", FT_MAXCHUNK * FT_TB * FT_PX);
     const int gp = (w + 7) & ~7;                                   // u16 row pitch of g: rows start on 16 bytes
@@ -1353,9 +1353,8 @@ extern "C" int mis_blender_feed(MisBlender* b, const MisImage* img, const MisIma
     int rc = feed_check(b, img, mask, tl);
     if (rc != MIS_OK) return rc;
     MIS_HIP(ctx, hipSetDevice(ctx->device));
-    DevImage di, dm;
-    if ((rc = mis_dev_image_in(ctx, img, &di)) != MIS_OK) return rc;
-    if ((rc = mis_dev_image_in(ctx, mask, &dm)) != MIS_OK) { mis_dev_image_release(ctx, &di); return rc; }
+    DevView di, dm;
+    if ((rc = di.read(ctx, img)) != MIS_OK || (rc = dm.read(ctx, mask)) != MIS_OK) return rc;
     const int w = img->width, h = img->height;
     if (b->type != MIS_BLEND_MULTI_BAND) b->fresh = false;
     if (b->type == MIS_BLEND_MULTI_BAND) rc = feed_multiband_batch(b, img, &di, &dm, &tl, 1);
@@ -1365,8 +1364,7 @@ extern "C" int mis_blender_feed(MisBlender* b, const MisImage* img, const MisIma
                            (const uint8_t*)dm.data, dm.stride, w, h, b->lap[0], b->dst_mask, b->lw[0], tl.x - b->roi.x, tl.y - b->roi.y);
         rc = hipGetLastError() == hipSuccess ? MIS_OK : mis_set_error(ctx, MIS_E_HIP, "feed_plain launch failed");
     }
-    int r1 = mis_dev_image_release(ctx, &di), r2 = mis_dev_image_release(ctx, &dm);
-    return rc != MIS_OK ? rc : (r1 != MIS_OK ? r1 : r2);
+    return rc;
 }
 
 // n feeds in one call: same result as mis_blender_feed(imgs[0]) ... mis_blender_feed(imgs[n - 1]) in that order.  The multi-band
@@ -1384,18 +1382,10 @@ extern "C" int mis_blender_feed_batch(MisBlender* b, const MisImage* imgs, const
     int rc = MIS_OK;
     for (int k = 0; k < n; k++) if ((rc = feed_check(b, &imgs[k], &masks[k], tls[k])) != MIS_OK) return rc;
     MIS_HIP(ctx, hipSetDevice(ctx->device));
-    std::vector<DevImage> di(n), dm(n);
-    int got = 0;
-    for (; got < n && rc == MIS_OK; got++) {
-        if ((rc = mis_dev_image_in(ctx, &imgs[got], &di[got])) != MIS_OK) break;
-        if ((rc = mis_dev_image_in(ctx, &masks[got], &dm[got])) != MIS_OK) { mis_dev_image_release(ctx, &di[got]); break; }
-    }
-    if (rc == MIS_OK) rc = feed_multiband_batch(b, imgs, di.data(), dm.data(), tls, n);
-    for (int k = 0; k < got; k++) {
-        const int r1 = mis_dev_image_release(ctx, &di[k]), r2 = mis_dev_image_release(ctx, &dm[k]);
-        if (rc == MIS_OK) rc = r1 != MIS_OK ? r1 : r2;
-    }
-    return rc;
+    std::vector<DevView> di(n), dm(n);
+    for (int k = 0; k < n; k++)
+        if ((rc = di[k].read(ctx, &imgs[k])) != MIS_OK || (rc = dm[k].read(ctx, &masks[k])) != MIS_OK) return rc;
+    return feed_multiband_batch(b, imgs, di.data(), dm.data(), tls, n);
 }
 
 // The compositing loop of main() for n frames in one call (image_stitching.cpp:1154-1164 + :1218 per frame): fused warp
@@ -1444,10 +1434,10 @@ static int blend_columns(MisBlender* b, int x0, int x1, MisImage* dst, MisImage*
     x1 = std::min(x1, b->fw);
     MIS_CHECK(ctx, x0 >= 0 && x0 < x1, MIS_E_INVALID, "empty column range %d..%d (panorama width %d)", x0, x1, b->fw);
     MIS_HIP(ctx, hipSetDevice(ctx->device));
-    DevImage dd, dm;
+    DevView dd, dm;
     int rc;
-    if ((rc = mis_dev_image_out(ctx, dst, x1 - x0, b->fh, 3, MIS_S16, &dd)) != MIS_OK) return rc;
-    if ((rc = mis_dev_image_out(ctx, dmask, x1 - x0, b->fh, 1, MIS_U8, &dm)) != MIS_OK) return rc;
+    if ((rc = dd.write(ctx, dst, x1 - x0, b->fh, 3, MIS_S16)) != MIS_OK) return rc;
+    if ((rc = dm.write(ctx, dmask, x1 - x0, b->fh, 1, MIS_U8)) != MIS_OK) return rc;
     MIS_CHECK(ctx, dd.stride % 2 == 0, MIS_E_INVALID, "16SC3 stride must be even");
     const int nb = b->num_bands;
     if (b->type != MIS_BLEND_NO) {
@@ -1477,8 +1467,7 @@ static int blend_columns(MisBlender* b, int x0, int x1, MisImage* dst, MisImage*
     hipLaunchKernelGGL(finalize_kernel, grid2d(x1 - x0, b->fh), dim3(256), 0, ctx->stream, b->lap[0], b->wgt[0], b->dst_mask, b->lw[0], x1 - x0,
                        b->fh, (int16_t*)dd.data, dd.stride, (uint8_t*)dm.data, dm.stride, x0);
     MIS_HIP(ctx, hipGetLastError());
-    if ((rc = mis_dev_image_commit(ctx, dst, &dd)) != MIS_OK) return rc;
-    if ((rc = mis_dev_image_commit(ctx, dmask, &dm)) != MIS_OK) return rc;
+    if ((rc = dd.commit()) != MIS_OK || (rc = dm.commit()) != MIS_OK) return rc;
     b->prepared = false;  // the accumulators are consumed (the reference releases them in blend())
     return MIS_OK;
 }

@@ -41,11 +41,13 @@ struct MisContext {
 
 int mis_set_error(MisContext* ctx, int code, const char* fmt, ...);
 int mis_host_stage(MisContext* ctx, size_t bytes, void** out);   // pinned scratch of at least `bytes` (valid until the next call)
-int mis_pool_alloc(MisContext* ctx, size_t bytes, void** out, size_t* got);
+int mis_dev_stage(MisContext* ctx, size_t bytes, void** out);    // the same in device memory
+// (errs: the context that gets the error text when it is not ctx -- a block taken from another context's pool on a thread of its own)
+int mis_pool_alloc(MisContext* ctx, size_t bytes, void** out, size_t* got, MisContext* errs = nullptr);
 int mis_aux_stream(MisContext* ctx, int k, hipStream_t* out);   // k = 0, 1
 void mis_pool_free(MisContext* ctx, void* p, size_t bytes);
 // a device block for a feature set from ctx's pool of recycled blocks, registered so that mis_features_free recycles it (orb.hip)
-int mis_feat_block_alloc(MisContext* ctx, size_t bytes, void** out);
+int mis_feat_block_alloc(MisContext* ctx, size_t bytes, void** out, MisContext* errs = nullptr);
 
 #define MIS_HIP(ctx, call)                                                                             \
     do {                                                                                               \
@@ -63,15 +65,34 @@ int mis_feat_block_alloc(MisContext* ctx, size_t bytes, void** out);
 static inline size_t mis_dtype_size(int dtype) { return dtype == MIS_U8 ? 1 : (dtype == MIS_S16 ? 2 : 4); }
 static inline size_t mis_align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
-// Device view of an image: either the caller's device pointer or a staged copy of a host buffer.
-struct DevImage {
+// Device view of a caller's image for the length of a scope: the caller's device pointer, or a staged device copy of a host
+// buffer.  Whatever the view allocated and did not hand over in commit() is freed when it goes out of scope, after a wait for
+// the context's stream, so an early return drops nothing.
+struct DevView {
     void* data = nullptr;
     size_t stride = 0;
-    bool owned = false;
+    DevView() = default;
+    DevView(const DevView&) = delete;
+    DevView& operator=(const DevView&) = delete;
+    ~DevView();
+    int read(MisContext* ctx, const MisImage* img);     // host images are uploaded
+    // Output of the given geometry: the caller's device buffer, a device twin of a host buffer, or (data == NULL) a device
+    // allocation entered into *img, which is the caller's only after commit(): without it *img goes back to what it was.
+    int write(MisContext* ctx, MisImage* img, int width, int height, int channels, int dtype);
+    int read_write(MisContext* ctx, MisImage* img);     // read(), and commit() copies a host image back
+    int commit();                                       // copy a host output back and free its twin; hand a fresh allocation over
+private:
+    MisContext* ctx_ = nullptr;
+    MisImage* out_ = nullptr;       // what commit() copies back to
+    MisImage entry_{};              // *out_ before a fresh allocation was entered into it
+    bool staged_ = false, fresh_ = false;
 };
-int mis_dev_image_in(MisContext* ctx, const MisImage* img, DevImage* out);   // read access
-int mis_dev_image_release(MisContext* ctx, DevImage* d);
-// Prepare an output image (allocate when data == NULL) and, for host outputs, a device twin.
-int mis_dev_image_out(MisContext* ctx, MisImage* img, int width, int height, int channels, int dtype, DevImage* out);
-int mis_dev_image_commit(MisContext* ctx, const MisImage* img, DevImage* d);  // copy back for host outputs, release
+
+// a HIP event that is destroyed with its scope
+struct OwnedEvent {
+    hipEvent_t ev = nullptr;
+    OwnedEvent() = default; OwnedEvent(const OwnedEvent&) = delete;
+    ~OwnedEvent() { if (ev) hipEventDestroy(ev); }
+    hipError_t ready(unsigned flags = hipEventDisableTiming) { return ev ? hipSuccess : hipEventCreateWithFlags(&ev, flags); }
+};
 

@@ -14,7 +14,7 @@ int mis_set_error(MisContext* ctx, int code, const char* fmt, ...) {
 }
 
 static std::mutex g_pool_mutex;      // (the SIFT batch's lanes allocate their output blocks from the caller's context on several host threads)
-int mis_pool_alloc(MisContext* ctx, size_t bytes, void** out, size_t* got) {
+int mis_pool_alloc(MisContext* ctx, size_t bytes, void** out, size_t* got, MisContext* errs) {
     // best fit among the recycled blocks (at most 2x the request), else a fresh allocation
     std::lock_guard<std::mutex> lock(g_pool_mutex);
     int best = -1;
@@ -25,7 +25,7 @@ int mis_pool_alloc(MisContext* ctx, size_t bytes, void** out, size_t* got) {
         ctx->pool.erase(ctx->pool.begin() + best);
         return MIS_OK;
     }
-    MIS_HIP(ctx, hipMalloc(out, bytes));
+    MIS_HIP(errs ? errs : ctx, hipMalloc(out, bytes));
     *got = bytes;
     return MIS_OK;
 }
@@ -39,6 +39,17 @@ int mis_host_stage(MisContext* ctx, size_t bytes, void** out) {
         ctx->host_stage_bytes = bytes + bytes / 2 + 4096;
     }
     *out = ctx->host_stage;
+    return MIS_OK;
+}
+
+// device scratch of at least `bytes` (valid until the next call): the context's grow-only staging block
+int mis_dev_stage(MisContext* ctx, size_t bytes, void** out) {
+    if (ctx->stage_bytes < bytes) {
+        if (ctx->stage) { MIS_HIP(ctx, hipStreamSynchronize(ctx->stream)); MIS_HIP(ctx, hipFree(ctx->stage)); ctx->stage = nullptr; ctx->stage_bytes = 0; }
+        MIS_HIP(ctx, hipMalloc(&ctx->stage, bytes * 2 + 4096));
+        ctx->stage_bytes = bytes * 2 + 4096;
+    }
+    *out = ctx->stage;
     return MIS_OK;
 }
 
@@ -146,63 +157,70 @@ extern "C" int mis_image_free(MisContext* ctx, MisImage* img) {
     return MIS_OK;
 }
 
-int mis_dev_image_in(MisContext* ctx, const MisImage* img, DevImage* out) {
+int DevView::read(MisContext* ctx, const MisImage* img) {
     MIS_CHECK(ctx, img && img->data && img->width > 0 && img->height > 0, MIS_E_INVALID, "null or empty input image");
     size_t row = (size_t)img->width * img->channels * mis_dtype_size(img->dtype);
     MIS_CHECK(ctx, img->stride >= row, MIS_E_INVALID, "stride %zu smaller than a row (%zu)", img->stride, row);
+    ctx_ = ctx;
     if (img->mem == MIS_MEM_DEVICE) {
-        out->data = img->data; out->stride = img->stride; out->owned = false;
+        data = img->data; stride = img->stride;
         return MIS_OK;
     }
     size_t pitch = mis_align_up(row, 256);
-    MIS_HIP(ctx, hipMalloc(&out->data, pitch * img->height));
-    out->stride = pitch; out->owned = true;
-    MIS_HIP(ctx, hipMemcpy2DAsync(out->data, pitch, img->data, img->stride, row, img->height, hipMemcpyHostToDevice, ctx->stream));
+    MIS_HIP(ctx, hipMalloc(&data, pitch * img->height));
+    stride = pitch; staged_ = true;
+    MIS_HIP(ctx, hipMemcpy2DAsync(data, pitch, img->data, img->stride, row, img->height, hipMemcpyHostToDevice, ctx->stream));
     return MIS_OK;
 }
 
-int mis_dev_image_release(MisContext* ctx, DevImage* d) {
-    if (d->owned && d->data) {
-        MIS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        MIS_HIP(ctx, hipFree(d->data));
-    }
-    d->data = nullptr; d->owned = false;
-    return MIS_OK;
+int DevView::read_write(MisContext* ctx, MisImage* img) {
+    out_ = img;
+    return read(ctx, img);
 }
 
-int mis_dev_image_out(MisContext* ctx, MisImage* img, int width, int height, int channels, int dtype, DevImage* out) {
+int DevView::write(MisContext* ctx, MisImage* img, int width, int height, int channels, int dtype) {
     MIS_CHECK(ctx, img, MIS_E_INVALID, "null output image");
     size_t row = (size_t)width * channels * mis_dtype_size(dtype);
+    ctx_ = ctx; out_ = img;
     if (!img->data) {
         size_t pitch = mis_align_up(row, 256);
-        void* p = nullptr;
-        MIS_HIP(ctx, hipMalloc(&p, pitch * (size_t)height));
-        img->data = p; img->width = width; img->height = height; img->channels = channels;
-        img->stride = pitch; img->dtype = dtype; img->mem = MIS_MEM_DEVICE;
+        MIS_HIP(ctx, hipMalloc(&data, pitch * (size_t)height));
+        entry_ = *img;
+        *img = MisImage{data, width, height, channels, pitch, dtype, MIS_MEM_DEVICE};
+        stride = pitch; fresh_ = true;
+        return MIS_OK;
     }
     MIS_CHECK(ctx, img->width == width && img->height == height && img->channels == channels && img->dtype == dtype,
               MIS_E_INVALID, "output image is %dx%dx%d dtype %d, expected %dx%dx%d dtype %d", img->width, img->height,
               img->channels, img->dtype, width, height, channels, dtype);
     MIS_CHECK(ctx, img->stride >= row, MIS_E_INVALID, "output stride too small");
     if (img->mem == MIS_MEM_DEVICE) {
-        out->data = img->data; out->stride = img->stride; out->owned = false;
+        data = img->data; stride = img->stride;
         return MIS_OK;
     }
     size_t pitch = mis_align_up(row, 256);
-    MIS_HIP(ctx, hipMalloc(&out->data, pitch * (size_t)height));
-    out->stride = pitch; out->owned = true;
+    MIS_HIP(ctx, hipMalloc(&data, pitch * (size_t)height));
+    stride = pitch; staged_ = true;
     return MIS_OK;
 }
 
-int mis_dev_image_commit(MisContext* ctx, const MisImage* img, DevImage* d) {
-    if (d->owned && d->data) {
-        size_t row = (size_t)img->width * img->channels * mis_dtype_size(img->dtype);
-        MIS_HIP(ctx, hipMemcpy2DAsync(img->data, img->stride, d->data, d->stride, row, img->height, hipMemcpyDeviceToHost, ctx->stream));
-        MIS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        MIS_HIP(ctx, hipFree(d->data));
+int DevView::commit() {
+    if (staged_ && out_) {
+        size_t row = (size_t)out_->width * out_->channels * mis_dtype_size(out_->dtype);
+        MIS_HIP(ctx_, hipMemcpy2DAsync(out_->data, out_->stride, data, stride, row, out_->height, hipMemcpyDeviceToHost, ctx_->stream));
+        MIS_HIP(ctx_, hipStreamSynchronize(ctx_->stream));
+        staged_ = false;
+        MIS_HIP(ctx_, hipFree(data));
     }
-    d->data = nullptr; d->owned = false;
+    fresh_ = false;
     return MIS_OK;
+}
+
+DevView::~DevView() {
+    if (!(staged_ || fresh_) || !data) return;
+    hipStreamSynchronize(ctx_->stream);
+    hipFree(data);
+    if (fresh_) *out_ = entry_;
 }
 
 // Feature sets of m frames into two dense device arrays for the descriptor all-gather: frame i's keypoints at

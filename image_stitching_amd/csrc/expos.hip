@@ -237,35 +237,31 @@ extern "C" int mis_compensator_feed(MisCompensator* c, const MisPoint* corners, 
         }
     const int np = (int)pairs.size();
 
-    std::vector<DevImage> di(n), dm(n);
-    std::vector<ImgDesc> desc(n);
-    int rc = MIS_OK;
-    for (int i = 0; i < n && rc == MIS_OK; i++) {
-        if ((rc = mis_dev_image_in(ctx, &images[i], &di[i])) != MIS_OK) break;
-        if ((rc = mis_dev_image_in(ctx, &masks[i], &dm[i])) != MIS_OK) break;
-        desc[i] = {(const uint8_t*)di[i].data, di[i].stride, (const uint8_t*)dm[i].data, dm[i].stride, corners[i].x, corners[i].y, images[i].width, images[i].height};
-    }
     std::vector<PairStat> stats(np);
-    if (rc == MIS_OK) {
+    {   // the staged frames live until the statistics are on the host
+        std::vector<DevView> di(n), dm(n);
+        std::vector<ImgDesc> desc(n);
+        int rc;
+        for (int i = 0; i < n; i++) {
+            if ((rc = di[i].read(ctx, &images[i])) != MIS_OK || (rc = dm[i].read(ctx, &masks[i])) != MIS_OK) return rc;
+            desc[i] = {(const uint8_t*)di[i].data, di[i].stride, (const uint8_t*)dm[i].data, dm[i].stride, corners[i].x, corners[i].y, images[i].width, images[i].height};
+        }
         const size_t b_desc = mis_align_up(sizeof(ImgDesc) * n, 256), b_pairs = mis_align_up(sizeof(PairDesc) * np, 256), b_stats = sizeof(PairStat) * np;
         void* buf = nullptr; size_t got = 0;
-        if ((rc = mis_pool_alloc(ctx, b_desc + b_pairs + b_stats, &buf, &got)) == MIS_OK) {
-            char* p = (char*)buf;
-            hipError_t e = hipMemcpyAsync(p, desc.data(), sizeof(ImgDesc) * n, hipMemcpyHostToDevice, ctx->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(p + b_desc, pairs.data(), sizeof(PairDesc) * np, hipMemcpyHostToDevice, ctx->stream);
-            if (e == hipSuccess) {
-                hipLaunchKernelGGL(overlap_stats_kernel, dim3((np + 3) / 4), dim3(256), 0, ctx->stream, (const ImgDesc*)p, (const PairDesc*)(p + b_desc), np,
-                                   (PairStat*)(p + b_desc + b_pairs));
-                e = hipGetLastError();
-            }
-            if (e == hipSuccess) e = hipMemcpyAsync(stats.data(), p + b_desc + b_pairs, b_stats, hipMemcpyDeviceToHost, ctx->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-            mis_pool_free(ctx, buf, got);
-            if (e != hipSuccess) rc = mis_set_error(ctx, MIS_E_HIP, "compensator feed: %s", hipGetErrorString(e));
+        if ((rc = mis_pool_alloc(ctx, b_desc + b_pairs + b_stats, &buf, &got)) != MIS_OK) return rc;
+        char* p = (char*)buf;
+        hipError_t e = hipMemcpyAsync(p, desc.data(), sizeof(ImgDesc) * n, hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(p + b_desc, pairs.data(), sizeof(PairDesc) * np, hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(overlap_stats_kernel, dim3((np + 3) / 4), dim3(256), 0, ctx->stream, (const ImgDesc*)p, (const PairDesc*)(p + b_desc), np,
+                               (PairStat*)(p + b_desc + b_pairs));
+            e = hipGetLastError();
         }
+        if (e == hipSuccess) e = hipMemcpyAsync(stats.data(), p + b_desc + b_pairs, b_stats, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        mis_pool_free(ctx, buf, got);
+        if (e != hipSuccess) return mis_set_error(ctx, MIS_E_HIP, "compensator feed: %s", hipGetErrorString(e));
     }
-    for (int i = 0; i < n; i++) { mis_dev_image_release(ctx, &di[i]); mis_dev_image_release(ctx, &dm[i]); }
-    if (rc != MIS_OK) return rc;
 
     // GainCompensator::singleFeed: N, I, then the normal equations over the blocks that meet another block
     std::vector<int> N((size_t)nb * nb, 0);
@@ -354,9 +350,9 @@ extern "C" int mis_compensator_apply(MisCompensator* c, int index, MisImage* ima
     MIS_CHECK(ctx, image && image->data && image->channels == 3 && (image->dtype == MIS_U8 || image->dtype == MIS_S16), MIS_E_UNSUPPORTED,
               "compensator apply: 8UC3 or 16SC3 (values 0..255) only");
     MIS_HIP(ctx, hipSetDevice(ctx->device));
-    DevImage d;
+    DevView d;
     int rc;
-    if ((rc = mis_dev_image_in(ctx, image, &d)) != MIS_OK) return rc;
+    if ((rc = d.read_write(ctx, image)) != MIS_OK) return rc;
     const int w = image->width, h = image->height, mw = c->mw[index], mh = c->mh[index];
     // resize(): inv_scale = dsize / ssize, scale = 1 / inv_scale
     const double sx = 1.0 / ((double)w / (double)mw), sy = 1.0 / ((double)h / (double)mh);
@@ -366,11 +362,7 @@ extern "C" int mis_compensator_apply(MisCompensator* c, int index, MisImage* ima
     else
         hipLaunchKernelGGL(gain_apply_kernel<int16_t>, grid, block, 0, ctx->stream, (int16_t*)d.data, d.stride / 2, w, h, c->dev_maps + c->dev_ofs[index], mw, mh, sx, sy);
     MIS_HIP(ctx, hipGetLastError());
-    if (d.owned) {
-        const size_t row = (size_t)w * 3 * mis_dtype_size(image->dtype);
-        MIS_HIP(ctx, hipMemcpy2DAsync(image->data, image->stride, d.data, d.stride, row, h, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    return mis_dev_image_release(ctx, &d);
+    return d.commit();
 }
 
 extern "C" int mis_seam_voronoi(MisContext* ctx, const MisPoint* corners, MisImage* masks, int n) {
@@ -379,11 +371,11 @@ extern "C" int mis_seam_voronoi(MisContext* ctx, const MisPoint* corners, MisIma
     for (int i = 0; i < n; i++)
         MIS_CHECK(ctx, masks[i].data && masks[i].dtype == MIS_U8 && masks[i].channels == 1, MIS_E_UNSUPPORTED, "voronoi seams: mask %d is not 8UC1", i);
     MIS_HIP(ctx, hipSetDevice(ctx->device));
-    std::vector<DevImage> dm(n);
+    std::vector<DevView> dm(n);
     std::vector<ImgDesc> desc(n);
     int rc = MIS_OK;
     for (int i = 0; i < n; i++) {
-        if ((rc = mis_dev_image_in(ctx, &masks[i], &dm[i])) != MIS_OK) return rc;
+        if ((rc = dm[i].read_write(ctx, &masks[i])) != MIS_OK) return rc;
         desc[i] = {nullptr, 0, (const uint8_t*)dm[i].data, dm[i].stride, corners[i].x, corners[i].y, masks[i].width, masks[i].height};
     }
     const int gap = 10;
@@ -408,10 +400,6 @@ extern "C" int mis_seam_voronoi(MisContext* ctx, const MisPoint* corners, MisIma
             mis_pool_free(ctx, buf, got);
             MIS_HIP(ctx, hipGetLastError());
         }
-    for (int i = 0; i < n; i++) {
-        if (dm[i].owned)
-            MIS_HIP(ctx, hipMemcpy2DAsync(masks[i].data, masks[i].stride, dm[i].data, dm[i].stride, (size_t)masks[i].width, masks[i].height, hipMemcpyDeviceToHost, ctx->stream));
-        if ((rc = mis_dev_image_release(ctx, &dm[i])) != MIS_OK) return rc;
-    }
-    return MIS_OK;
+    for (int i = 0; i < n && rc == MIS_OK; i++) rc = dm[i].commit();
+    return rc;
 }

@@ -31,15 +31,10 @@ int upload_tables(MisContext* ctx, int sw, int sh, int dw, int dh, double sx, do
     coeffs(dw, sw, sx, h.data(), h.data() + dw);
     coeffs(dh, sh, sy, h.data() + 2 * dw, h.data() + 2 * dw + dh);
     const size_t bytes = h.size() * sizeof(int);
-    if (ctx->stage_bytes < bytes) {
-        if (ctx->stage) { MIS_HIP(ctx, hipStreamSynchronize(ctx->stream)); MIS_HIP(ctx, hipFree(ctx->stage)); ctx->stage = nullptr; ctx->stage_bytes = 0; }
-        MIS_HIP(ctx, hipMalloc(&ctx->stage, bytes * 2 + 4096));
-        ctx->stage_bytes = bytes * 2 + 4096;
-    }
+    if (int rc = mis_dev_stage(ctx, bytes, (void**)tab)) return rc;
     // pageable source: the copy is complete for the host when the call returns, so `h` may go out of scope
-    MIS_HIP(ctx, hipMemcpyAsync(ctx->stage, h.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
+    MIS_HIP(ctx, hipMemcpyAsync((void*)*tab, h.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
     MIS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    *tab = (const int*)ctx->stage;
     return MIS_OK;
 }
 
@@ -276,10 +271,10 @@ extern "C" int mis_resize_linear_exact(MisContext* ctx, const MisImage* src, int
     const double sx = by_factor ? 1.0 / fx : 1.0 / ((double)dw / (double)src->width);
     const double sy = by_factor ? 1.0 / fy : 1.0 / ((double)dh / (double)src->height);
     MIS_HIP(ctx, hipSetDevice(ctx->device));
-    DevImage din, dout;
+    DevView din, dout;
     int rc;
-    if ((rc = mis_dev_image_in(ctx, src, &din)) != MIS_OK) return rc;
-    if ((rc = mis_dev_image_out(ctx, dst, dw, dh, src->channels, MIS_U8, &dout)) != MIS_OK) { mis_dev_image_release(ctx, &din); return rc; }
+    if ((rc = din.read(ctx, src)) != MIS_OK) return rc;
+    if ((rc = dout.write(ctx, dst, dw, dh, src->channels, MIS_U8)) != MIS_OK) return rc;
     const int* tab;
     if ((rc = upload_tables(ctx, src->width, src->height, dw, dh, sx, sy, &tab)) != MIS_OK) return rc;
     dim3 grid((dw + 255) / 256, dh), block(256);
@@ -288,8 +283,7 @@ extern "C" int mis_resize_linear_exact(MisContext* ctx, const MisImage* src, int
     else
         hipLaunchKernelGGL(resize_exact_kernel<1>, grid, block, 0, ctx->stream, (const uint8_t*)din.data, src->width, src->height, din.stride, (uint8_t*)dout.data, dw, dh, dout.stride, tab);
     MIS_HIP(ctx, hipGetLastError());
-    if ((rc = mis_dev_image_commit(ctx, dst, &dout)) != MIS_OK) return rc;
-    return mis_dev_image_release(ctx, &din);
+    return dout.commit();
 }
 
 extern "C" int mis_resize_linear_exact_batch(MisContext* ctx, const MisImage* srcs, int n, int dst_w, int dst_h, double fx, double fy, MisImage* dsts) {
@@ -322,10 +316,10 @@ extern "C" int mis_resize_linear_exact_batch(MisContext* ctx, const MisImage* sr
     const int* tab;
     if (int rc = cached_tables(ctx, s0.width, s0.height, dw, dh, sx, sy, &tab)) return rc;
     // device images are used in place; host images are staged as mis_resize_linear_exact stages them (a copy and a wait each)
-    std::vector<DevImage> din(n), dout(n);
+    std::vector<DevView> din(n), dout(n);
     int rc = MIS_OK, flags = 3;
-    for (int i = 0; i < n && rc == MIS_OK; i++) rc = mis_dev_image_in(ctx, &srcs[i], &din[i]);
-    for (int i = 0; i < n && rc == MIS_OK; i++) rc = mis_dev_image_out(ctx, &dsts[i], dw, dh, s0.channels, MIS_U8, &dout[i]);
+    for (int i = 0; i < n && rc == MIS_OK; i++) rc = din[i].read(ctx, &srcs[i]);
+    for (int i = 0; i < n && rc == MIS_OK; i++) rc = dout[i].write(ctx, &dsts[i], dw, dh, s0.channels, MIS_U8);
     constexpr int ROWS = 2;
     for (int b = 0; b < n && rc == MIS_OK; b += RB_MAX) {       // (a job's frames are one launch; more than RB_MAX frames take one per RB_MAX)
         const int m = n - b < RB_MAX ? n - b : RB_MAX;
@@ -347,10 +341,7 @@ extern "C" int mis_resize_linear_exact_batch(MisContext* ctx, const MisImage* sr
             hipLaunchKernelGGL((resize_batch_kernel<1, ROWS>), grid, block, 0, ctx->stream, A, s0.width, s0.height, dw, dh, tab, flags);
         if (hipGetLastError() != hipSuccess) rc = mis_set_error(ctx, MIS_E_HIP, "resize batch: launch failed");
     }
-    for (int i = 0; i < n; i++) {
-        if (dout[i].data) { const int r2 = mis_dev_image_commit(ctx, &dsts[i], &dout[i]); if (rc == MIS_OK) rc = r2; }
-        if (din[i].data) { const int r2 = mis_dev_image_release(ctx, &din[i]); if (rc == MIS_OK) rc = r2; }
-    }
+    for (int i = 0; i < n && rc == MIS_OK; i++) rc = dout[i].commit();
     return rc;
 }
 
@@ -361,18 +352,17 @@ extern "C" int mis_rotate(MisContext* ctx, const MisImage* src, int rotate_code,
     MIS_CHECK(ctx, rotate_code >= 0 && rotate_code <= 2, MIS_E_INVALID, "rotate code must be 0 (90 CW), 1 (180) or 2 (90 CCW)");
     const int dw = rotate_code == 1 ? src->width : src->height, dh = rotate_code == 1 ? src->height : src->width;
     MIS_HIP(ctx, hipSetDevice(ctx->device));
-    DevImage din, dout;
+    DevView din, dout;
     int rc;
-    if ((rc = mis_dev_image_in(ctx, src, &din)) != MIS_OK) return rc;
-    if ((rc = mis_dev_image_out(ctx, dst, dw, dh, src->channels, MIS_U8, &dout)) != MIS_OK) { mis_dev_image_release(ctx, &din); return rc; }
+    if ((rc = din.read(ctx, src)) != MIS_OK) return rc;
+    if ((rc = dout.write(ctx, dst, dw, dh, src->channels, MIS_U8)) != MIS_OK) return rc;
     dim3 grid((dw + 255) / 256, dh), block(256);
     if (src->channels == 3)
         hipLaunchKernelGGL(rotate_kernel<3>, grid, block, 0, ctx->stream, (const uint8_t*)din.data, src->width, src->height, din.stride, rotate_code, (uint8_t*)dout.data, dw, dh, dout.stride);
     else
         hipLaunchKernelGGL(rotate_kernel<1>, grid, block, 0, ctx->stream, (const uint8_t*)din.data, src->width, src->height, din.stride, rotate_code, (uint8_t*)dout.data, dw, dh, dout.stride);
     MIS_HIP(ctx, hipGetLastError());
-    if ((rc = mis_dev_image_commit(ctx, dst, &dout)) != MIS_OK) return rc;
-    return mis_dev_image_release(ctx, &din);
+    return dout.commit();
 }
 
 extern "C" int mis_seam_mask_apply(MisContext* ctx, const MisImage* seam, MisImage* mask) {
@@ -381,17 +371,14 @@ extern "C" int mis_seam_mask_apply(MisContext* ctx, const MisImage* seam, MisIma
     MIS_CHECK(ctx, seam->dtype == MIS_U8 && seam->channels == 1 && mask->dtype == MIS_U8 && mask->channels == 1, MIS_E_UNSUPPORTED, "masks must be 8UC1");
     MIS_CHECK(ctx, seam->width > 0 && seam->height > 0 && mask->width > 0 && mask->height > 0, MIS_E_INVALID, "empty mask");
     MIS_HIP(ctx, hipSetDevice(ctx->device));
-    DevImage ds, dm;
+    DevView ds, dm;
     int rc;
-    if ((rc = mis_dev_image_in(ctx, seam, &ds)) != MIS_OK) return rc;
-    if ((rc = mis_dev_image_out(ctx, mask, mask->width, mask->height, 1, MIS_U8, &dm)) != MIS_OK) { mis_dev_image_release(ctx, &ds); return rc; }
-    if (dm.owned) MIS_HIP(ctx, hipMemcpy2DAsync(dm.data, dm.stride, mask->data, mask->stride, (size_t)mask->width, (size_t)mask->height, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = ds.read(ctx, seam)) != MIS_OK || (rc = dm.read_write(ctx, mask)) != MIS_OK) return rc;
     const int* tab;
     const double sx = 1.0 / ((double)mask->width / (double)seam->width), sy = 1.0 / ((double)mask->height / (double)seam->height);
     if ((rc = upload_tables(ctx, seam->width, seam->height, mask->width, mask->height, sx, sy, &tab)) != MIS_OK) return rc;
     hipLaunchKernelGGL(seam_mask_kernel, dim3((mask->width + 1023) / 1024, mask->height), dim3(256), 0, ctx->stream, (const uint8_t*)ds.data, seam->width,
                        seam->height, ds.stride, (uint8_t*)dm.data, mask->width, mask->height, dm.stride, tab);
     MIS_HIP(ctx, hipGetLastError());
-    if ((rc = mis_dev_image_commit(ctx, mask, &dm)) != MIS_OK) return rc;
-    return mis_dev_image_release(ctx, &ds);
+    return dm.commit();
 }

@@ -723,14 +723,6 @@ struct Arena {
     void release() { if (p) { if (host) hipHostFree(p); else hipFree(p); } p = nullptr; bytes = 0; }
 };
 
-// an event of the workspace: created on first use, destroyed with the workspace
-struct OwnedEvent {
-    hipEvent_t ev = nullptr;
-    OwnedEvent() = default; OwnedEvent(const OwnedEvent&) = delete;
-    ~OwnedEvent() { if (ev) hipEventDestroy(ev); }
-    hipError_t ready(unsigned flags = hipEventDisableTiming) { return ev ? hipSuccess : hipEventCreateWithFlags(&ev, flags); }
-};
-
 struct MatchWorkspace : MisWorkspace {
     Arena dev, pinned, l2;
     // b1: first estimation of every pair; b2 / b3: the inlier-only estimation of the pairs whose first one finished in

@@ -1162,7 +1162,7 @@ inline int* feat_count(const MisFeatures* f, int cap) {
 }
 
 // enqueue the whole detect + describe path of a group of ng <= ORB_BATCH frames (one launch per stage); no host synchronisation
-int enqueue_detect_group(MisOrb* o, const DevImage* img, int w, int h, MisFeatures* out, int ng) {
+int enqueue_detect_group(MisOrb* o, const DevView* img, int w, int h, MisFeatures* out, int ng) {
     MisContext* ctx = o->ctx;
     const Levels& L = o->L;
     const Work& W = o->w;
@@ -1305,9 +1305,9 @@ int orb_ensure_frames(MisOrb* o, int frames) {
 }  // namespace
 
 // (common.h) a device block for a feature set from ctx's pool, registered so that mis_features_free recycles it: the SIFT finders' outputs
-int mis_feat_block_alloc(MisContext* ctx, size_t bytes, void** out) {
+int mis_feat_block_alloc(MisContext* ctx, size_t bytes, void** out, MisContext* errs) {
     size_t got = 0;
-    const int rc = mis_pool_alloc(ctx, bytes, out, &got);
+    const int rc = mis_pool_alloc(ctx, bytes, out, &got, errs);
     if (rc != MIS_OK) return rc;
     std::lock_guard<std::mutex> lock(g_feat_mutex);
     g_feat_sizes[*out] = got;
@@ -1404,21 +1404,19 @@ extern "C" int mis_orb_detect_batch(MisOrb* o, const MisImage* imgs, int n, MisF
     }
     if ((rc = replan_if_needed(o, imgs[0].width, imgs[0].height)) != MIS_OK) return rc;
     if ((rc = orb_ensure_frames(o, n)) != MIS_OK) return rc;
-    std::vector<DevImage> dimg(n);
+    std::vector<DevView> dimg(n);
     for (int i = 0; i < n; i++) memset(&out[i], 0, sizeof(MisFeatures));
     // an error must not leak the outputs / staged inputs of the frames already set up
     auto fail = [&](int code) {
         hipStreamSynchronize(ctx->stream);
-        for (int i = 0; i < n; i++) {
+        for (int i = 0; i < n; i++)
             if (out[i].keypoints || out[i].descriptors) mis_features_free(ctx, &out[i]);
-            if (dimg[i].data) mis_dev_image_release(ctx, &dimg[i]);
-        }
         return code;
     };
     for (int i = 0; i < n; i++) {
         out[i].img_idx = i; out[i].img_w = imgs[i].width; out[i].img_h = imgs[i].height;
         if ((rc = alloc_features(ctx, o->out_cap, 32, MIS_U8, &out[i])) != MIS_OK) return fail(rc);
-        if ((rc = mis_dev_image_in(ctx, &imgs[i], &dimg[i])) != MIS_OK) return fail(rc);
+        if ((rc = dimg[i].read(ctx, &imgs[i])) != MIS_OK) return fail(rc);
     }
     const bool trace = getenv("MIS_ORB_TRACE") != nullptr;
     const auto t_enq0 = std::chrono::steady_clock::now();
@@ -1456,7 +1454,7 @@ extern "C" int mis_orb_detect_batch(MisOrb* o, const MisImage* imgs, int n, MisF
     int flags = 0;
     for (int k = 0; k < nl; k++) flags |= ws_flags[k];
     if (flags) hipMemset2DAsync(o->w.flags, o->ws_stride, 0, sizeof(int), (size_t)nl, ctx->stream);
-    for (int i = 0; i < n; i++) { out[i].n = counts[i]; mis_dev_image_release(ctx, &dimg[i]); }
+    for (int i = 0; i < n; i++) out[i].n = counts[i];
     if (flags) {
         return mis_set_error(ctx, MIS_E_OVERFLOW, "ORB candidate buffers overflowed (flags %d): too many tied scores", flags);
     }

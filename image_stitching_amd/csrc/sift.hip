@@ -988,7 +988,7 @@ static void blur(MisSift* s, const float* src, float* dst, int w, int h, double 
 }
 
 // scale space of one image (everything up to and including the DoG pyramid)
-static int sift_build(MisSift* s, const MisImage* bgr, const DevImage& din) {
+static int sift_build(MisSift* s, const MisImage* bgr, const DevView& din) {
     MisContext* ctx = s->ctx;
     hipStream_t st = ctx->stream;
     const int w = bgr->width, h = bgr->height, nl = s->p.n_octave_layers;
@@ -1023,9 +1023,9 @@ extern "C" int mis_sift_detect(MisSift* s, const MisImage* bgr, MisFeatures* out
               "image %dx%d outside the detector's range (16x16 .. %dx%d)", bgr->width, bgr->height, s->max_w, s->max_h);
     MIS_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    DevImage din;
+    DevView din;
     int rc;
-    if ((rc = mis_dev_image_in(ctx, bgr, &din)) != MIS_OK) return rc;
+    if ((rc = din.read(ctx, bgr)) != MIS_OK) return rc;
     if ((rc = sift_build(s, bgr, din)) != MIS_OK) return rc;
     const Pyr& P = s->pyr;
     const int nl = s->p.n_octave_layers, firstOctave = -1;
@@ -1059,7 +1059,7 @@ extern "C" int mis_sift_detect(MisSift* s, const MisImage* bgr, MisFeatures* out
     // (from the pool of recycled feature blocks: a hipMalloc / hipFree pair per frame synchronises the device -- with three frames in
     // flight every few steps of config 5 took 160 - 360 ms instead of 78)
     uint8_t* blk = nullptr;
-    if ((rc = mis_feat_block_alloc(s->pool_ctx ? s->pool_ctx : ctx, kb + db, (void**)&blk)) != MIS_OK) return rc;
+    if ((rc = mis_feat_block_alloc(s->pool_ctx ? s->pool_ctx : ctx, kb + db, (void**)&blk, ctx)) != MIS_OK) return rc;    // (a lane reports on its own context)
     out->owner_ = blk; out->keypoints = (MisKeyPoint*)blk; out->descriptors = blk + kb;
     if (nraw) {
         // KeyPointsFilter::removeDuplicatedSorted (a total order, so the atomics' append order never shows) + the
@@ -1079,7 +1079,7 @@ extern "C" int mis_sift_detect(MisSift* s, const MisImage* bgr, MisFeatures* out
         MIS_HIP(ctx, hipStreamSynchronize(st));
     }
     out->n = (int)counts[2];
-    return mis_dev_image_release(ctx, &din);
+    return MIS_OK;
 }
 
 extern "C" int mis_sift_debug_level(MisSift* s, const MisImage* bgr, int octave, int layer, int dog, float* host_out, int* width, int* height) {
@@ -1087,9 +1087,9 @@ extern "C" int mis_sift_debug_level(MisSift* s, const MisImage* bgr, int octave,
     MisContext* ctx = s->ctx;
     MIS_CHECK(ctx, bgr && bgr->data && width && height, MIS_E_INVALID, "null argument");
     MIS_HIP(ctx, hipSetDevice(ctx->device));
-    DevImage din;
+    DevView din;
     int rc;
-    if ((rc = mis_dev_image_in(ctx, bgr, &din)) != MIS_OK) return rc;
+    if ((rc = din.read(ctx, bgr)) != MIS_OK) return rc;
     if ((rc = sift_build(s, bgr, din)) != MIS_OK) return rc;
     const Pyr& P = s->pyr;
     const int nl = s->p.n_octave_layers;
@@ -1100,7 +1100,7 @@ extern "C" int mis_sift_debug_level(MisSift* s, const MisImage* bgr, int octave,
         MIS_HIP(ctx, hipMemcpyAsync(host_out, src, sizeof(float) * (size_t)P.w[octave] * P.h[octave], hipMemcpyDeviceToHost, ctx->stream));
         MIS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
-    return mis_dev_image_release(ctx, &din);
+    return MIS_OK;
 }
 
 // Several frames: up to four lanes (this finder and helpers with their own scale space, context and stream), one host thread

@@ -1464,9 +1464,9 @@ extern "C" int mis_warper_warp(MisContext* ctx, int kind, const MisImage* src, f
     int brx, bry, rc;
     if ((rc = setup(ctx, kind, src, scale, K, R, &a, &brx, &bry)) != MIS_OK) return rc;
     MIS_HIP(ctx, hipSetDevice(ctx->device));
-    DevImage din, dout;
-    if ((rc = mis_dev_image_in(ctx, src, &din)) != MIS_OK) return rc;
-    if ((rc = mis_dev_image_out(ctx, dst, a.dw, a.dh, src->channels, MIS_U8, &dout)) != MIS_OK) { mis_dev_image_release(ctx, &din); return rc; }
+    DevView din, dout;
+    if ((rc = din.read(ctx, src)) != MIS_OK) return rc;
+    if ((rc = dout.write(ctx, dst, a.dw, a.dh, src->channels, MIS_U8)) != MIS_OK) return rc;
     a.src = (const uint8_t*)din.data; a.sstride = din.stride;
     a.dst = dout.data; a.dstride = dout.stride; a.mask = nullptr; a.mstride = 0;
     dim3 grid((a.dw + TILE_W - 1) / TILE_W, (a.dh + TILE_H - 1) / TILE_H), block(256);
@@ -1478,8 +1478,7 @@ extern "C" int mis_warper_warp(MisContext* ctx, int kind, const MisImage* src, f
         else hipLaunchKernelGGL((warp_u8_kernel<1, false>), grid, block, 0, ctx->stream, a);
     }
     MIS_HIP(ctx, hipGetLastError());
-    if ((rc = mis_dev_image_commit(ctx, dst, &dout)) != MIS_OK) return rc;
-    if ((rc = mis_dev_image_release(ctx, &din)) != MIS_OK) return rc;
+    if ((rc = dout.commit()) != MIS_OK) return rc;
     if (tl) { tl->x = a.tlx; tl->y = a.tly; }
     return MIS_OK;
 }
@@ -1505,29 +1504,24 @@ static int warp_fused_impl(MisContext* ctx, int kind, const MisImage* src, float
         return warp_fused_batch_impl(ctx, kind, src, 1, scale, K, R, &r, dst, dmask, tl, 1, nullptr);
     }
     MIS_HIP(ctx, hipSetDevice(ctx->device));
-    DevImage din, dout, dm;
-    if ((rc = mis_dev_image_in(ctx, src, &din)) != MIS_OK) return rc;
-    if ((rc = mis_dev_image_out(ctx, dst, a.dw, a.dh, 3, MIS_S16, &dout)) != MIS_OK) return rc;
-    if ((rc = mis_dev_image_out(ctx, dmask, a.dw, a.dh, 1, MIS_U8, &dm)) != MIS_OK) return rc;
+    DevView din, dout, dm;
+    if ((rc = din.read(ctx, src)) != MIS_OK) return rc;
+    if ((rc = dout.write(ctx, dst, a.dw, a.dh, 3, MIS_S16)) != MIS_OK) return rc;
+    if ((rc = dm.write(ctx, dmask, a.dw, a.dh, 1, MIS_U8)) != MIS_OK) return rc;
     MIS_CHECK(ctx, dout.stride % 4 == 0 && dm.stride % 2 == 0 && ((uintptr_t)dout.data % 4) == 0 && ((uintptr_t)dm.data % 2) == 0,
               MIS_E_INVALID, "fused warp outputs need 4-byte (image) / 2-byte (mask) aligned rows");
     a.src = (const uint8_t*)din.data; a.sstride = din.stride;
     a.dst = dout.data; a.dstride = dout.stride; a.mask = (uint8_t*)dm.data; a.mstride = dm.stride;
     // separable trig tables live in the context's grow-only scratch
-    const size_t tab_bytes = sizeof(float) * trig_table_floats(a.dw, a.dh);
-    if (ctx->stage_bytes < tab_bytes) {
-        if (ctx->stage) { MIS_HIP(ctx, hipStreamSynchronize(ctx->stream)); MIS_HIP(ctx, hipFree(ctx->stage)); ctx->stage = nullptr; ctx->stage_bytes = 0; }
-        MIS_HIP(ctx, hipMalloc(&ctx->stage, tab_bytes * 2 + 4096));
-        ctx->stage_bytes = tab_bytes * 2 + 4096;
-    }
-    float* tab = (float*)ctx->stage;
+    float* tab = nullptr;
+    if ((rc = mis_dev_stage(ctx, sizeof(float) * trig_table_floats(a.dw, a.dh), (void**)&tab)) != MIS_OK) return rc;
     hipLaunchKernelGGL(warp_trig_kernel, dim3((trig_cols(a.dw) + a.dh + 255) / 256), dim3(256), 0, ctx->stream, a, tab);
     const int nwg = grid_of(a);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    OwnedEvent e0, e1;
     if (avg_us) {
-        MIS_HIP(ctx, hipEventCreate(&e0));
-        MIS_HIP(ctx, hipEventCreate(&e1));
-        MIS_HIP(ctx, hipEventRecord(e0, ctx->stream));
+        MIS_HIP(ctx, e0.ready(hipEventDefault));
+        MIS_HIP(ctx, e1.ready(hipEventDefault));
+        MIS_HIP(ctx, hipEventRecord(e0.ev, ctx->stream));
     }
     // one frame per launch: round 2's tile kernel (measured faster there than the strip forms: 23.2 us against 29.3 for one-tile
     // strips and more for longer ones -- a frame alone is 3.5 tiles per wave slot, gpurun_out/r4_plan_ab3.txt)
@@ -1536,16 +1530,13 @@ static int warp_fused_impl(MisContext* ctx, int kind, const MisImage* src, float
         else hipLaunchKernelGGL(warp_fused_kernel<true>, dim3(nwg), dim3(64 * TILE_WAVES), 0, ctx->stream, a, (const float*)tab);
     if (avg_us) {
         float ms = 0.f;
-        MIS_HIP(ctx, hipEventRecord(e1, ctx->stream));
-        MIS_HIP(ctx, hipEventSynchronize(e1));
-        MIS_HIP(ctx, hipEventElapsedTime(&ms, e0, e1));
+        MIS_HIP(ctx, hipEventRecord(e1.ev, ctx->stream));
+        MIS_HIP(ctx, hipEventSynchronize(e1.ev));
+        MIS_HIP(ctx, hipEventElapsedTime(&ms, e0.ev, e1.ev));
         *avg_us = ms * 1000.f / (float)repeats;
-        hipEventDestroy(e0); hipEventDestroy(e1);
     }
     MIS_HIP(ctx, hipGetLastError());
-    if ((rc = mis_dev_image_commit(ctx, dst, &dout)) != MIS_OK) return rc;
-    if ((rc = mis_dev_image_commit(ctx, dmask, &dm)) != MIS_OK) return rc;
-    if ((rc = mis_dev_image_release(ctx, &din)) != MIS_OK) return rc;
+    if ((rc = dout.commit()) != MIS_OK || (rc = dm.commit()) != MIS_OK) return rc;
     if (tl) { tl->x = a.tlx; tl->y = a.tly; }
     return MIS_OK;
 }
@@ -1588,34 +1579,19 @@ static int warp_fused_batch_impl(MisContext* ctx, int kind, const MisImage* srcs
     MIS_CHECK(ctx, srcs && Ks && Rs && rois && dsts && dmasks && n >= 1, MIS_E_INVALID, "null argument");
     MIS_HIP(ctx, hipSetDevice(ctx->device));
     std::vector<WarpArgs> args((size_t)n);
-    std::vector<DevImage> din((size_t)n), dout((size_t)n), dm((size_t)n);
+    std::vector<DevView> din((size_t)n), dout((size_t)n), dm((size_t)n);
     std::vector<size_t> tab_off((size_t)n);
     size_t tab_total = 0;
-    int rc = MIS_OK, got = 0;
-    // which outputs this call allocates (data == NULL on entry): an error hands them back and leaves the caller's structs as they were
-    std::vector<uint8_t> fresh_d((size_t)n), fresh_m((size_t)n);
-    for (int i = 0; i < n; i++) { fresh_d[i] = dsts[i].data == nullptr; fresh_m[i] = dmasks[i].data == nullptr; }
-    auto undo = [&](int upto) {      // frames 0 .. upto (inclusive) may hold staged inputs, device twins of host outputs, fresh outputs
-        hipStreamSynchronize(ctx->stream);
-        for (int i = 0; i <= upto && i < n; i++) {
-            if (din[i].owned && din[i].data) hipFree(din[i].data);
-            if (dout[i].owned && dout[i].data) hipFree(dout[i].data);
-            if (dm[i].owned && dm[i].data) hipFree(dm[i].data);
-            if (fresh_d[i] && dsts[i].data) { hipFree(dsts[i].data); dsts[i].data = nullptr; }
-            if (fresh_m[i] && dmasks[i].data) { hipFree(dmasks[i].data); dmasks[i].data = nullptr; }
-            din[i] = DevImage(); dout[i] = DevImage(); dm[i] = DevImage();
-        }
-    };
-    for (; got < n; got++) {
-        const int i = got;
+    int rc = MIS_OK;
+    for (int i = 0; i < n && rc == MIS_OK; i++) {
         WarpArgs& a = args[i];
         int brx, bry;
         if (!(rois[i].width > 0 && rois[i].height > 0)) { rc = mis_set_error(ctx, MIS_E_INVALID, "frame %d: empty roi", i); break; }
         if ((rc = setup(ctx, kind, &srcs[i], scale, Ks + 9 * i, Rs + 9 * i, &a, &brx, &bry, &rois[i])) != MIS_OK) break;
         if (srcs[i].channels != 3) { rc = mis_set_error(ctx, MIS_E_UNSUPPORTED, "fused warp needs an 8UC3 source"); break; }
-        if ((rc = mis_dev_image_in(ctx, &srcs[i], &din[i])) != MIS_OK) break;
-        if ((rc = mis_dev_image_out(ctx, &dsts[i], a.dw, a.dh, 3, MIS_S16, &dout[i])) != MIS_OK) break;
-        if ((rc = mis_dev_image_out(ctx, &dmasks[i], a.dw, a.dh, 1, MIS_U8, &dm[i])) != MIS_OK) break;
+        if ((rc = din[i].read(ctx, &srcs[i])) != MIS_OK) break;
+        if ((rc = dout[i].write(ctx, &dsts[i], a.dw, a.dh, 3, MIS_S16)) != MIS_OK) break;
+        if ((rc = dm[i].write(ctx, &dmasks[i], a.dw, a.dh, 1, MIS_U8)) != MIS_OK) break;
         if (!(dout[i].stride % 4 == 0 && dm[i].stride % 2 == 0 && ((uintptr_t)dout[i].data % 4) == 0 && ((uintptr_t)dm[i].data % 2) == 0)) {
             rc = mis_set_error(ctx, MIS_E_INVALID, "fused warp outputs need 4-byte (image) / 2-byte (mask) aligned rows"); break;
         }
@@ -1624,13 +1600,9 @@ static int warp_fused_batch_impl(MisContext* ctx, int kind, const MisImage* srcs
         tab_off[i] = tab_total;
         tab_total += mis_align_up(sizeof(float) * trig_table_floats(a.dw, a.dh), 256);
     }
-    if (rc != MIS_OK) { undo(got); return rc; }
-    if (ctx->stage_bytes < tab_total) {
-        if (ctx->stage) { MIS_HIP(ctx, hipStreamSynchronize(ctx->stream)); MIS_HIP(ctx, hipFree(ctx->stage)); ctx->stage = nullptr; ctx->stage_bytes = 0; }
-        MIS_HIP(ctx, hipMalloc(&ctx->stage, tab_total * 2 + 4096));
-        ctx->stage_bytes = tab_total * 2 + 4096;
-    }
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    uint8_t* tabs = nullptr;
+    if (rc != MIS_OK || (rc = mis_dev_stage(ctx, tab_total, (void**)&tabs)) != MIS_OK) return rc;
+    OwnedEvent e0, e1;
     std::vector<V3Batch> v3batches;
     int nt3 = 1 << 30;      // tiles per strip: one value for the grid (the smallest any frame asks for)
     for (int i = 0; i < n; i++) nt3 = std::min(nt3, v3_strip_tiles(ctx, args[i], n));
@@ -1640,7 +1612,7 @@ static int warp_fused_batch_impl(MisContext* ctx, int kind, const MisImage* srcs
         int max_trig = 0;
         for (int k = 0; k < WB_MAX; k++) {
             const int i = g0 + (k < ng ? k : 0);
-            b.a[k] = args[i]; b.tab[k] = (const float*)((uint8_t*)ctx->stage + tab_off[i]);
+            b.a[k] = args[i]; b.tab[k] = (const float*)(tabs + tab_off[i]);
             if (k < ng) max_trig = std::max(max_trig, (trig_cols(args[i].dw) + args[i].dh + 255) / 256);
         }
         hipLaunchKernelGGL(warp_trig_batch_kernel, dim3(max_trig, ng), dim3(256), 0, ctx->stream, b);
@@ -1662,9 +1634,9 @@ static int warp_fused_batch_impl(MisContext* ctx, int kind, const MisImage* srcs
         v3batches.push_back(vb);
     }
     if (avg_us) {
-        MIS_HIP(ctx, hipEventCreate(&e0));
-        MIS_HIP(ctx, hipEventCreate(&e1));
-        MIS_HIP(ctx, hipEventRecord(e0, ctx->stream));
+        MIS_HIP(ctx, e0.ready(hipEventDefault));
+        MIS_HIP(ctx, e1.ready(hipEventDefault));
+        MIS_HIP(ctx, hipEventRecord(e0.ev, ctx->stream));
     }
     for (int rep = 0; rep < repeats; rep++)
         for (const V3Batch& vb : v3batches)
@@ -1672,16 +1644,14 @@ static int warp_fused_batch_impl(MisContext* ctx, int kind, const MisImage* srcs
             else hipLaunchKernelGGL(warp_strip_batch_kernel<true>, dim3(vb.wg_base[WB_MAX]), dim3(64 * V3_WAVES), 0, ctx->stream, vb);
     if (avg_us) {
         float ms = 0.f;
-        MIS_HIP(ctx, hipEventRecord(e1, ctx->stream));
-        MIS_HIP(ctx, hipEventSynchronize(e1));
-        MIS_HIP(ctx, hipEventElapsedTime(&ms, e0, e1));
+        MIS_HIP(ctx, hipEventRecord(e1.ev, ctx->stream));
+        MIS_HIP(ctx, hipEventSynchronize(e1.ev));
+        MIS_HIP(ctx, hipEventElapsedTime(&ms, e0.ev, e1.ev));
         *avg_us = ms * 1000.f / (float)repeats;
-        hipEventDestroy(e0); hipEventDestroy(e1);
     }
     MIS_HIP(ctx, hipGetLastError());
     for (int i = 0; i < n; i++) {
-        int r1 = mis_dev_image_commit(ctx, &dsts[i], &dout[i]), r2 = mis_dev_image_commit(ctx, &dmasks[i], &dm[i]), r3 = mis_dev_image_release(ctx, &din[i]);
-        if (rc == MIS_OK) rc = r1 != MIS_OK ? r1 : (r2 != MIS_OK ? r2 : r3);
+        if (rc == MIS_OK && (rc = dout[i].commit()) == MIS_OK) rc = dm[i].commit();
         if (tls) { tls[i].x = args[i].tlx; tls[i].y = args[i].tly; }
     }
     return rc;

@@ -154,6 +154,73 @@ def test_batched_warp_error_hands_back_what_it_allocated(ctx):
         ctx.lib.mis_image_free(ctx.h, C.byref(ds[k])); ctx.lib.mis_image_free(ctx.h, C.byref(ms[k]))
 
 
+def test_fused_warp_refused_mask_hands_back_the_fresh_image(ctx):
+    """mis_warper_warp_fused with a host source, dst.data == NULL and a caller mask of the wrong size: MIS_E_INVALID with a
+    message, and dst is back to data == NULL (the image the library allocated before it saw the mask is released, not left in
+    the caller's struct); the same call with host outputs of the right size then gives the device run's result."""
+    import ctypes as C
+    import image_stitching_amd as isa
+    from image_stitching_amd import _capi as capi
+    from image_stitching_amd.stitching import _mat9, as_image
+    cams, frames = _cam_frames(1)
+    cam, host = cams[0], frames[0].cpu().numpy()
+    scale = isa.Stitcher.warped_image_scale(cams)
+    w = isa.SphericalWarper(ctx, scale)
+    want = w.warp_fused(frames[0], cam["K"], cam["R"])
+    ctx.synchronize()
+    (ka, kp), (ra, rp) = _mat9(cam["K"]), _mat9(cam["R"])
+    rh, rw = want[2].shape[:2]
+
+    def call(dst, msk):
+        src, tl = as_image(host), capi.MisPoint()
+        rc = ctx.lib.mis_warper_warp_fused(ctx.h, w.kind, C.byref(src), float(scale), kp, rp, C.byref(dst), C.byref(msk), C.byref(tl))
+        return rc, (tl.x, tl.y)
+    dst, small = capi.MisImage(), np.zeros((rh - 1, rw), np.uint8)
+    rc, _ = call(dst, as_image(small))
+    assert rc == E_INVALID and ctx.lib.mis_last_error(ctx.h)
+    assert not dst.data
+    img, msk = np.zeros((rh, rw, 3), np.int16), np.zeros((rh, rw), np.uint8)
+    rc, tl = call(as_image(img), as_image(msk))
+    assert rc == 0 and tl == tuple(want[0])
+    assert np.array_equal(img, want[1].cpu().numpy()) and np.array_equal(msk, want[2].cpu().numpy().reshape(rh, rw))
+
+
+def test_blend_refused_mask_hands_back_the_fresh_image(ctx):
+    """mis_blender_blend after host feeds, with dst.data == NULL and a caller mask of the wrong size: MIS_E_INVALID with a message
+    and dst back to data == NULL; the blender is still prepared, and its blend() is that of a blender that never saw the bad call."""
+    import ctypes as C
+    import torch
+    import image_stitching_amd as isa
+    from image_stitching_amd import _capi as capi
+    from image_stitching_amd.stitching import as_image
+    cams, frames = _cam_frames(2)
+    scale = isa.Stitcher.warped_image_scale(cams)
+    w = isa.SphericalWarper(ctx, scale)
+    warped = [w.warp_fused(f, c["K"], c["R"]) for f, c in zip(frames, cams)]
+    ctx.synchronize()
+    host = [(tl, np.ascontiguousarray(i.cpu().numpy()), np.ascontiguousarray(m.cpu().numpy().reshape(m.shape[0], m.shape[1]))) for tl, i, m in warped]
+    corners = [t[0] for t in warped]
+    sizes = [(t[1].shape[1], t[1].shape[0]) for t in warped]
+
+    def fed():
+        b = isa.MultiBandBlender(ctx, 3)
+        b.prepare(corners, sizes)
+        for tl, img, msk in host:
+            b.feed(img, msk, tl)
+        return b
+    b = fed()
+    pw, ph = b._size
+    dst, small = capi.MisImage(), np.zeros((ph - 1, pw), np.uint8)
+    bad = as_image(small)
+    rc = ctx.lib.mis_blender_blend(b.h, C.byref(dst), C.byref(bad))
+    assert rc == E_INVALID and ctx.lib.mis_last_error(ctx.h)
+    assert not dst.data
+    got, gmask = b.blend()
+    want, wmask = fed().blend()
+    ctx.synchronize()
+    assert torch.equal(got, want) and torch.equal(gmask, wmask)
+
+
 def _detect_matches_reference(finder, frame, kw):
     import torch
     import refimpl_orb as ro
