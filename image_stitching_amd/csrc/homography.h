@@ -59,7 +59,14 @@ enum HomoRun {
     HOMO_TAIL1_REFINE = 13,
 };
 // `calls` (device array of b->count entries) must be filled before this is enqueued on `stream` (nullptr: the context's stream).
-// Optional ordering hook of a run: rec is recorded behind the draw_kernel of the second phase (rec_pos 0) or of the first (2).
-struct HomoSync { hipEvent_t rec = nullptr; int rec_pos = 0; };
+// Optional ordering hooks of a run: rec is recorded behind the draw_kernel of the second phase (rec_pos 0) or of the first (2).
+// Speculative drawing of the second phase's subsets (homography.hip, DRAW_SPEC): a HOMO_PHASE0_REPLAY run given spec_stream enqueues
+// it there, behind spec_fork (recorded behind the first phase's draw) and in front of spec_join (and of spec_mark, a timing
+// event, when set); the HOMO_PHASE1_REPLAY run of the same batch is given spec_join alone and queues its draw behind it.
+struct HomoSync {
+    hipEvent_t rec = nullptr; int rec_pos = 0;
+    hipStream_t spec_stream = nullptr;
+    hipEvent_t spec_fork = nullptr, spec_join = nullptr, spec_mark = nullptr;
+};
 int homo_batch_run(MisContext* ctx, HomoBatch* b, double thresh, int max_iters, double confidence, HomoRun run = HOMO_BOTH_PHASES,
                    hipStream_t stream = nullptr, const HomoSync* sync = nullptr);

@@ -11,7 +11,8 @@
 //                     position is simulated as the start of ONE attempt in parallel, then one thread
 //                     chases start -> end -> ... through the table: the exact sequential sequence.
 //                     When a phase's drawing ends, the problem appends its hypotheses [lo, min(n_sub, niters)) to the batch's
-//                     work list in blocks of HQ_HYPS (one atomic per problem).
+//                     work list in blocks of HQ_HYPS (one atomic per problem).  A third, speculative mode draws the second
+//                     phase's subsets of the few-match problems while the first phase is solved (DRAW_SPEC below).
 //   hyp_quad_kernel   four lanes per hypothesis: 4-point normalised DLT, 9x9 Jacobi on the upper triangle;
 //   hyp_count_kernel  one wave per HC_HYPS hypotheses: their inlier counts.  Both are persistent (grids sized by the number of
 //                     compute units, not by max_iters or the problem count) and work through the list's tickets.
@@ -47,6 +48,11 @@ struct RansacState {
     int tail_pending;   // the loop ended in a scan-only launch: mask / DLT / LM refinement still to run (scan_tail_kernel parts 3 / 4)
     int draw_k, draw_fail;   // next iteration to draw; getSubset exhausted its 10000 attempts
     long long draw_pos;      // RNG stream position after the last drawn subset
+    // where the speculative drawing (draw_kernel, DRAW_SPEC) stopped: subsets [0, spec_k) are in sub_idx, the stream stands at spec_pos
+    // behind the last of them, spec_fail: getSubset gave up looking for subset spec_k.  Fields of their own: the first phase's solves,
+    // counts and replay run at the same time and read n_sub / draw_fail.  The second phase's draw adopts them (spec_k > draw_k)
+    int spec_k, spec_fail;
+    long long spec_pos;
 };
 
 // ---------------------------------------------------------------- shared scalar helpers --------
@@ -268,14 +274,28 @@ constexpr int DRAW_CHUNK = 4096;
 #endif
 constexpr int DRAW_TB = MIS_DRAW_TB;   // threads of a problem's workgroup: a chunk's positions are simulated DRAW_CHUNK / DRAW_TB per thread (256 threads: 0.54 + 1.08 ms for the two draw launches on the matcher's critical path)
 constexpr int DRAW_PTS = 2048;
+// phase DRAW_SPEC: the subsets of the second phase, drawn before the first phase's replay has said how many are needed.  The subset
+// sequence depends on the RNG stream and the points alone; the replay only decides where it stops.  A model replaces the best one
+// with >= 4 inliers, so from the first accepted model on niters <= B4(n) = RANSACUpdateNumIters(confidence, (n - 4) / n, max_iters).
+// The problems with PHASE0 < B4(n) < max_iters (n <= 17 at the defaults: the pairs without an overlap, whose loop is capped by four
+// inliers alone) are drawn up to B4(n) here, on another stream, beside the first phase's solves; the second phase's launch takes
+// the state over and draws on only where niters reaches past it.  Nothing is appended to the work list, and n_sub / draw_k /
+// draw_fail keep the first phase's values until then.
+constexpr int DRAW_SPEC = 2;
+// chunks of stream positions a problem may spend here: a problem whose attempts are mostly rejected (collinear or coincident
+// points: a million positions for 2000 subsets) would hold the stream the second phase waits for, for subsets it may never need.
+// The few-match pairs of a 16-frame job take 7 chunks at most (tools/tail_prof.py): their launch runs 0.30 ms beside the first
+// phase's solves and ends 28 us before that phase's replay does, so 8 -- one chunk more than that job needs -- costs the chain nothing.
+constexpr int DRAW_SPEC_CHUNKS = 8;
 __global__ __launch_bounds__(DRAW_TB) void draw_kernel(const HomoCall* calls, RansacState* states, int* sub_idx, int* draw_idx, const unsigned* U,
-                                                  unsigned long long state_T, int max_iters, int phase, int k_hi_arg, int2* work, unsigned* work_ctr) {
+                                                  unsigned long long state_T, int max_iters, int phase, int k_hi_arg, int2* work, unsigned* work_ctr,
+                                                  double confidence) {
 #if MIS_CHAIN_PRIO
     __builtin_amdgcn_s_setprio(MIS_CHAIN_PRIO);      // a latency-bound chain beside the composition's bandwidth-bound kernels: its few waves issue first
 #endif
     __shared__ unsigned char tab[DRAW_CHUNK];  // per position: min(end - start, 127) | pass << 7
     __shared__ float2 pts[2 * DRAW_PTS];       // src then dst of small problems: the random gathers stay on chip
-    __shared__ long long s_pos;
+    __shared__ long long s_pos, s_accpos, s_accend;    // s_accpos: the stream position behind the last accepted subset (s_accend: of this chunk)
     __shared__ int s_k, s_attempts, s_more, s_kfirst, s_nacc;
     __shared__ unsigned short acc_o[DRAW_CHUNK / 4];  // chunk offsets of the accepted attempts (serial path)
     __shared__ unsigned short nxtA[DRAW_CHUNK + 1], nxtB[DRAW_CHUNK + 1];  // J^(2^r): start of the attempt 2^r hops ahead
@@ -295,15 +315,31 @@ __global__ __launch_bounds__(DRAW_TB) void draw_kernel(const HomoCall* calls, Ra
             st->mode = (!c.active || c.n < 4) ? 0 : (c.n == 4 ? 1 : 2);
             st->n_sub = 0; st->iter = 0; st->niters = max_iters > 1 ? max_iters : 1; st->max_good = 0; st->done = 0; st->best_k = -1; st->result = 0; st->tail_pending = 0;
             st->draw_k = 0; st->draw_fail = 0; st->draw_pos = 0;
+            st->spec_k = 0; st->spec_fail = 0; st->spec_pos = 0;
         }
         if (!c.active || c.n <= 4) return;
+    } else if (phase == DRAW_SPEC) {
+        // (the first phase's replay may be writing iter / niters / done / ... of this problem: none of them is read here)
+        if (st->mode != 2 || st->draw_fail) return;
     } else {
-        if (st->mode != 2 || st->done || st->draw_fail) return;
+        if (st->mode != 2 || st->done || st->draw_fail) return;     // (a failure of the first phase's drawing: n_sub < PHASE0)
+        __syncthreads();                                            // every thread has read draw_fail before the adoption may set it
+        if (t == 0 && st->spec_k > st->draw_k) { st->draw_k = st->n_sub = st->spec_k; st->draw_pos = st->spec_pos; st->draw_fail = st->spec_fail; }
     }
     __syncthreads();
-    const int k_hi = min(k_hi_arg, phase == 0 ? max_iters : st->niters);
-    if (t == 0) { s_pos = st->draw_pos; s_k = st->draw_k; s_attempts = 0; s_more = s_k < k_hi; }
+    int k_hi = min(k_hi_arg, phase == 0 ? max_iters : st->niters);
+    if (phase == DRAW_SPEC) {
+        k_hi = ransac_update_num_iters(confidence, (double)(c.n - 4) / c.n, max_iters);
+        if (!(k_hi > PHASE0 && k_hi < max_iters)) return;      // uniform
+    }
+    // (an adopted give-up lies at n_sub: nothing more to draw, its hypotheses go to the list below)
+    if (t == 0) { s_pos = s_accpos = st->draw_pos; s_k = st->draw_k; s_attempts = 0; s_more = s_k < k_hi && !st->draw_fail; }
     __syncthreads();
+    // the end of a problem's drawing in this launch
+    auto draw_ends = [&](long long pos, int k, int fail) {
+        if (phase == DRAW_SPEC) { st->spec_pos = pos; st->spec_k = k; st->spec_fail = fail; }
+        else { st->draw_pos = pos; st->draw_k = k; st->draw_fail = fail; st->n_sub = k; }
+    };
     DrawCtx d;
     d.U = U; d.state_T = state_T; d.cur_state = state_T; d.cur_pos = RNG_TABLE;
     const float* psrc = c.src;
@@ -360,7 +396,14 @@ __global__ __launch_bounds__(DRAW_TB) void draw_kernel(const HomoCall* calls, Ra
     int dp_chunks = 0;
 
 #endif
+    int spec_chunks = 0;
     while (s_more) {
+        if (phase == DRAW_SPEC && spec_chunks++ == DRAW_SPEC_CHUNKS) {
+            // out of budget in the middle of a run of attempts: the state behind the last accepted subset, where a phase boundary
+            // stands too (no failed attempt counted yet), is what the second phase's launch continues from
+            if (t == 0) draw_ends(s_accpos, s_k, 0);
+            break;
+        }
 #ifdef MIS_TAIL_PROF
         dp_chunks++;
 #endif
@@ -431,7 +474,7 @@ __global__ __launch_bounds__(DRAW_TB) void draw_kernel(const HomoCall* calls, Ra
             const int total_v = total >> 16, total_a = total & 0xffff;
             int vr = (incl >> 16) - lv, ar = (incl & 0xffff) - la;  // exclusive ranks at q0
             const int need = k_hi - s_k, cut = min(total_a, need);
-            if (t == 0) { s_firstvis = -1; s_lastaccvis = -1; s_endpos = -1; }
+            if (t == 0) { s_firstvis = -1; s_lastaccvis = -1; s_endpos = -1; s_accend = -1; }
             __syncthreads();
             for (int q = q0; q < q0 + C / DRAW_TB; q++) {
                 if (!reach[q]) continue;
@@ -439,7 +482,7 @@ __global__ __launch_bounds__(DRAW_TB) void draw_kernel(const HomoCall* calls, Ra
                 if (e & 0x80) {
                     if (ar == 0) s_firstvis = vr;
                     if (ar < cut) *reinterpret_cast<int4*>(sidx + 4 * (s_k + ar)) = *reinterpret_cast<const int4*>(didx + 4 * q);
-                    if (ar == cut - 1) { s_lastaccvis = vr; if (cut == need) s_endpos = base + q + (e & 0x7f); }
+                    if (ar == cut - 1) { s_lastaccvis = vr; s_accend = base + q + (e & 0x7f); if (cut == need) s_endpos = s_accend; }
                     ar++;
                 }
                 if (vr == total_v - 1 && cut < need) s_endpos = base + q + (e & 0x7f);  // the chain leaves the chunk here
@@ -456,8 +499,9 @@ __global__ __launch_bounds__(DRAW_TB) void draw_kernel(const HomoCall* calls, Ra
                 }
                 const int k = fail ? s_k : s_k + cut;
                 s_pos = s_endpos; s_k = k; s_attempts = attempts;
+                if (!fail && cut > 0) s_accpos = s_accend;
                 s_more = !fail && k < k_hi;
-                if (!s_more) { st->draw_pos = s_pos; st->draw_k = k; st->draw_fail = fail; st->n_sub = k; }
+                if (!s_more) draw_ends(s_pos, k, fail);
 #ifdef MIS_TAIL_PROF
                 const unsigned long long cs3 = wall_clock64();
                 atomicAdd(&g_draw_prof[8], cs1 - (dp_last)); atomicAdd(&g_draw_prof[9], cs2 - cs1); atomicAdd(&g_draw_prof[10], cs3 - cs2); atomicAdd(&g_draw_prof[11], 1ull);
@@ -482,6 +526,7 @@ __global__ __launch_bounds__(DRAW_TB) void draw_kernel(const HomoCall* calls, Ra
         if (t == 0) {
             long long pos = base;
             int k = s_k, attempts = s_attempts, nacc = 0;
+            long long accpos = s_accpos;
             bool fail = false;
             while (k < k_hi && pos < base + DRAW_CHUNK) {
                 unsigned char e = tab[pos - base];
@@ -496,13 +541,13 @@ __global__ __launch_bounds__(DRAW_TB) void draw_kernel(const HomoCall* calls, Ra
                     if (pass) { acc_o[nacc++] = 0xffff; sidx[4 * k] = idx[0]; sidx[4 * k + 1] = idx[1]; sidx[4 * k + 2] = idx[2]; sidx[4 * k + 3] = idx[3]; }
                 }
                 attempts++;
-                if (pass) { k++; attempts = 0; }
+                if (pass) { k++; attempts = 0; accpos = pos; }
                 else if (attempts >= 10000) { fail = true; break; }  // getSubset gave up: the RANSAC loop ends here
             }
             s_kfirst = s_k; s_nacc = nacc;
-            s_pos = pos; s_k = k; s_attempts = attempts;
+            s_pos = pos; s_k = k; s_attempts = attempts; s_accpos = accpos;
             s_more = !fail && k < k_hi;
-            if (!s_more) { st->draw_pos = pos; st->draw_k = k; st->draw_fail = fail; st->n_sub = k; }
+            if (!s_more) draw_ends(pos, k, fail);
         }
         __syncthreads();
         for (int j = t; j < s_nacc; j += DRAW_TB) {
@@ -512,7 +557,7 @@ __global__ __launch_bounds__(DRAW_TB) void draw_kernel(const HomoCall* calls, Ra
         __syncthreads();
     }
 #ifdef MIS_TAIL_PROF
-    if (t == 0 && dp_chunks) {
+    if (t == 0 && dp_chunks && phase != DRAW_SPEC) {
         const int ph = phase ? 4 : 0;
         atomicAdd(&g_draw_prof[ph], (unsigned long long)dp_chunks); atomicMax(&g_draw_prof[ph + 1], (unsigned long long)dp_chunks);
         atomicMax(&g_draw_prof[ph + 2], wall_clock64() - dp0); atomicAdd(&g_draw_prof[ph + 3], 1ull);
@@ -520,8 +565,9 @@ __global__ __launch_bounds__(DRAW_TB) void draw_kernel(const HomoCall* calls, Ra
 #endif
     // the phase's hypotheses [lo, min(n_sub, niters)) -- at or beyond niters they can never be replayed -- go to the work list in
     // blocks of HQ_HYPS, with ONE atomic per problem.  Every return above leaves an empty range: mode 0 / 1, n_sub = 0 (no feasible
-    // subset), or in phase 1 a problem that is done or whose drawing failed in phase 0 (n_sub < PHASE0 then)
-    if (t == 0) {
+    // subset), or in phase 1 a problem that is done or whose drawing failed in phase 0 (n_sub < PHASE0 then).  A speculative
+    // launch lists nothing: its subsets are listed by the second phase's launch, which knows how many of them count
+    if (t == 0 && phase != DRAW_SPEC) {
         const int lo = phase == 0 ? 0 : min(PHASE0, max_iters), hi = min(st->n_sub, st->niters);
         if (st->mode == 2 && !st->done && hi > lo) {
             const int nb = (hi - lo + HQ_HYPS - 1) / HQ_HYPS;
@@ -1887,8 +1933,17 @@ int homo_batch_run(MisContext* ctx, HomoBatch* b, double thresh, int max_iters, 
     if (run == HOMO_BOTH_PHASES || run == HOMO_PHASE0_REPLAY) {
         MIS_HIP(ctx, hipMemsetAsync(b->fin, 0xff, sizeof(int) * (size_t)b->count, st));
         hipLaunchKernelGGL(draw_kernel, dim3(b->count), dim3(DRAW_TB), 0, st, b->calls, states, b->sub_idx, b->draw_idx, rt.U, rt.state_T, max_iters, 0, p0, b->work,
-                           b->work_ctr);
+                           b->work_ctr, confidence);
         if (sy.rec && sy.rec_pos == 2) MIS_HIP(ctx, hipEventRecord(sy.rec, st));
+        if (sy.spec_stream && max_iters > p0) {
+            // the second phase's subsets of the few-match problems, drawn on a stream of their own beside the solves below (DRAW_SPEC)
+            MIS_HIP(ctx, hipEventRecord(sy.spec_fork, st));
+            MIS_HIP(ctx, hipStreamWaitEvent(sy.spec_stream, sy.spec_fork, 0));
+            hipLaunchKernelGGL(draw_kernel, dim3(b->count), dim3(DRAW_TB), 0, sy.spec_stream, b->calls, states, b->sub_idx, b->draw_idx, rt.U, rt.state_T, max_iters,
+                               DRAW_SPEC, max_iters, b->work, b->work_ctr, confidence);
+            MIS_HIP(ctx, hipEventRecord(sy.spec_join, sy.spec_stream));
+            if (sy.spec_mark) MIS_HIP(ctx, hipEventRecord(sy.spec_mark, sy.spec_stream));
+        }
         hypotheses();
         hipLaunchKernelGGL(scan_tail_kernel, dim3(b->count), dim3(TB), tail_lds(replay_part), st, b->calls, states, b->Hc, b->valid, b->good, b->scr, b->rec, b->results, 0, p0,
                            max_iters, confidence, thr, b->fin, replay_part, 0, tail_staged(replay_part), b->work_ctr);
@@ -1899,8 +1954,9 @@ int homo_batch_run(MisContext* ctx, HomoBatch* b, double thresh, int max_iters, 
                            max_iters, confidence, thr, b->fin, part, want, tail_staged(part), nullptr);
     }
     if ((run == HOMO_BOTH_PHASES || run == HOMO_PHASE1_REPLAY) && max_iters > p0) {
+        if (sy.spec_join && !sy.spec_stream) MIS_HIP(ctx, hipStreamWaitEvent(st, sy.spec_join, 0));      // the speculative drawing a HOMO_PHASE0_REPLAY run started
         hipLaunchKernelGGL(draw_kernel, dim3(b->count), dim3(DRAW_TB), 0, st, b->calls, states, b->sub_idx, b->draw_idx, rt.U, rt.state_T, max_iters, 1, max_iters,
-                           b->work, b->work_ctr);
+                           b->work, b->work_ctr, confidence);
         if (sy.rec && sy.rec_pos == 0) MIS_HIP(ctx, hipEventRecord(sy.rec, st));
         hypotheses();
         hipLaunchKernelGGL(scan_tail_kernel, dim3(b->count), dim3(TB), tail_lds(replay_part), st, b->calls, states, b->Hc, b->valid, b->good, b->scr, b->rec, b->results, p0,
