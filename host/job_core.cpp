@@ -47,6 +47,7 @@ JobCore::JobCore(const char* who, std::string where, int device, void* main_stre
         if (cfg_.features_type != "orb" || cfg_.ba_cost_func != "no" || cfg_.expos_comp_type != "no" || cfg_.seam_find_type != "no")
             throw std::runtime_error(std::string(who) + " runs the hot path (ORB, supplied cameras, no seam-scale step); use mis::Stitcher for the other options");
         kind_ = warp_kind(cfg_.warp_type);
+        check_range_width(cfg_.range_width);
         if (mis_context_create(device, mstream_, &ctx_) != MIS_OK) throw std::runtime_error("mis_context_create failed: no HIP device (there is no CPU fallback)");
         check(ctx_, mis_stream_create(device, 0, &cstream_), "mis_stream_create");
         if (mis_context_create(device, cstream_, &cctx_) != MIS_OK) throw std::runtime_error("mis_context_create (compose stream) failed");

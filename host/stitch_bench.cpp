@@ -1,6 +1,6 @@
 // stitch_bench.cpp -- the job of bench.py (4K frames stitched per second, frames resident in HBM) driven from C++:
 // mis::StitchJob over the C ABI, synthetic frames rendered into HBM by synth/libmissynth_gpu.so.
-//   stitch_bench <cams.txt> [--steps K] [--warmup W] [--dump prefix] [--ranks N] [--comm host|rccl] [--one-gpu] [--warp kind] [--work_megapix f]
+//   stitch_bench <cams.txt> [--steps K] [--warmup W] [--dump prefix] [--ranks N] [--comm host|rccl] [--one-gpu] [--warp kind] [--work_megapix f] [--rangewidth N]
 // --ranks N > 1: the SHARDED job (mis::ShardedJob, host/sharded_job.hpp): this process never touches the GPU -- it creates the ranks'
 // rendezvous file, starts N child processes of itself (rank r on GPU r; --one-gpu: all on GPU 0, a rehearsal), relays rank 0's line,
 // and when a rank fails it ends the others and exits non-zero.  --comm rccl (default for N > 1): RCCL called directly; --comm host:
@@ -41,6 +41,7 @@ struct Args {
     int steps = 20, warmup = 5, ranks = 1, child_rank = -1;
     bool one_gpu = false;
     double work_megapix = -1;      // features at work scale (image_stitching.cpp:589-603); -1: full resolution
+    int range_width = -1;          // BestOf2NearestRangeMatcher (:83, :646-649); -1: all pairs
 };
 
 static bool read_cams(const std::string& path, int* n, int* W, int* H, std::vector<SyCamera>* sy, std::vector<mis::CameraParams>* cams) {
@@ -122,6 +123,7 @@ static int run_single(const Args& a) {
         mis::StitchConfig cfg;
         cfg.warp_type = a.warp;
         cfg.work_megapix = a.work_megapix;
+        cfg.range_width = a.range_width;
         mis::StitchJob job(0, W, H, cams, cfg);
         std::vector<int> everyone(n);
         for (int i = 0; i < n; i++) everyone[i] = i;
@@ -133,9 +135,9 @@ static int run_single(const Args& a) {
         if (!a.dump.empty() && write_dump(a.dump, out)) return 1;
         std::printf("{\"host\": \"c++ (host/stitch_bench: mis::StitchJob over the C ABI)\", \"metric\": \"4K frames stitched/sec\", \"value\": %.3f, \"unit\": \"frames/s\", "
                     "\"n_gpus\": 1, \"steps\": %d, \"warmup\": %d, \"ms_per_step\": %.3f, \"frames\": %d, \"frame_size\": [%d, %d], \"pano_size\": [%d, %d], "
-                    "\"num_bands\": %d, \"kept\": %d, \"speculation_kept\": %s}\n",
+                    "\"num_bands\": %d, \"kept\": %d, \"speculation_kept\": %s, \"range_width\": %d, \"pairs_matched\": %d}\n",
                     n * a.steps / dt, a.steps, a.warmup, dt / a.steps * 1e3, n, W, H, out.pano_width, out.pano_height, out.num_bands, (int)out.indices.size(),
-                    out.speculation_kept ? "true" : "false");
+                    out.speculation_kept ? "true" : "false", a.range_width, mis::selected_pair_count(out.num_features, a.range_width));
         for (auto& f : frames) (void)hipFree(f.data);
     } catch (const std::exception& e) {
         std::printf("error: %s\n", e.what());
@@ -157,6 +159,7 @@ static int run_rank(const Args& a, int rank) {
         mis::StitchConfig cfg;
         cfg.warp_type = a.warp;
         cfg.work_megapix = a.work_megapix;
+        cfg.range_width = a.range_width;
         mis::ShardedJob job(device, W, H, cams, *comm, cfg);
         std::vector<MisImage> frames;
         if (render_frames(sy, job.my_frames(), W, H, &frames)) return 1;
@@ -170,9 +173,10 @@ static int run_rank(const Args& a, int rank) {
             if (!a.dump.empty() && write_dump(a.dump, out)) return 1;
             std::printf("{\"host\": \"c++ (host/stitch_bench: mis::ShardedJob, %d rank%s, %s)\", \"metric\": \"4K frames stitched/sec\", \"value\": %.3f, \"unit\": \"frames/s\", "
                         "\"n_gpus\": %d, \"one_gpu_rehearsal\": %s, \"steps\": %d, \"warmup\": %d, \"ms_per_step\": %.3f, \"frames\": %d, \"frame_size\": [%d, %d], \"pano_size\": [%d, %d], "
-                        "\"num_bands\": %d, \"kept\": %d, \"speculation_kept\": %s}\n",
+                        "\"num_bands\": %d, \"kept\": %d, \"speculation_kept\": %s, \"range_width\": %d, \"pairs_matched\": %d}\n",
                         a.ranks, a.ranks == 1 ? "" : "s", comm->name(), n * a.steps / dt, a.one_gpu ? 1 : a.ranks, a.one_gpu ? "true" : "false", a.steps, a.warmup,
-                        dt / a.steps * 1e3, n, W, H, out.pano_width, out.pano_height, out.num_bands, (int)out.indices.size(), out.speculation_kept ? "true" : "false");
+                        dt / a.steps * 1e3, n, W, H, out.pano_width, out.pano_height, out.num_bands, (int)out.indices.size(), out.speculation_kept ? "true" : "false",
+                        a.range_width, mis::selected_pair_count(out.num_features, a.range_width));
             std::fflush(stdout);
         }
         comm->barrier();
@@ -221,7 +225,7 @@ static int launch(const Args& a, int argc, char** argv) {
 }
 
 int main(int argc, char** argv) {
-    if (argc < 2) { std::fprintf(stderr, "usage: stitch_bench cams.txt [--steps K] [--warmup W] [--dump prefix] [--ranks N] [--comm host|rccl] [--one-gpu] [--warp spherical|cylindrical|plane] [--work_megapix f]\n"); return 2; }
+    if (argc < 2) { std::fprintf(stderr, "usage: stitch_bench cams.txt [--steps K] [--warmup W] [--dump prefix] [--ranks N] [--comm host|rccl] [--one-gpu] [--warp spherical|cylindrical|plane] [--work_megapix f] [--rangewidth N]\n"); return 2; }
     Args a;
     a.cams_path = argv[1];
     for (int i = 2; i < argc; i++) {
@@ -233,6 +237,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--one-gpu")) a.one_gpu = true;
         else if (!std::strcmp(argv[i], "--warp") && i + 1 < argc) a.warp = argv[++i];
         else if (!std::strcmp(argv[i], "--work_megapix") && i + 1 < argc) a.work_megapix = std::strtod(argv[++i], nullptr);
+        else if (!std::strcmp(argv[i], "--rangewidth") && i + 1 < argc) a.range_width = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--rank-child") && i + 1 < argc) a.child_rank = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--session") && i + 1 < argc) a.session = argv[++i];
     }

@@ -87,6 +87,7 @@ StitchResult Stitcher::stitch(const std::vector<HostImage>& frames, const std::v
     if (cfg_.seam_find_type != "no" && cfg_.seam_find_type != "voronoi" && cfg_.seam_find_type != "dp_color")
         throw std::runtime_error("seam finder '" + cfg_.seam_find_type + "' is not implemented ('no', 'voronoi' and 'dp_color' are)");
     const int kind = warp_kind(cfg_.warp_type);
+    check_range_width(cfg_.range_width);
     MisOrb* orb = nullptr;
     MisSift* sift = nullptr;
     std::vector<MisFeatures> features(n);
@@ -121,7 +122,7 @@ StitchResult Stitcher::stitch(const std::vector<HostImage>& frames, const std::v
     mis_match_default_params(&mp);
     mp.match_conf = cfg_.match_conf;
     std::vector<MisMatchesInfo> pairwise((size_t)n * n);
-    check(mis_match_all_pairs(ctx_, features.data(), n, &mp, pairwise.data()), "mis_match_all_pairs");
+    check(mis_match_pairs_select(ctx_, features.data(), n, &mp, nullptr, cfg_.range_width, 0, 1, pairwise.data()), "mis_match_pairs_select");
     for (auto& m : pairwise) out.confidence.push_back(m.confidence);
     out.indices.resize(n);
     int kept = 0;

@@ -34,7 +34,23 @@ struct StitchConfig {
     std::string seam_find_type = "no";     // "no" | "voronoi" | "dp_color" (the reference's default; this driver's default is the hot path)
     // warper (:917-969): the three of the reference's GPU branch are built; its other names throw by name (warp_kind)
     std::string warp_type = "spherical";   // "spherical" | "cylindrical" | "plane"
+    // matcher (:83, :646-649): -1 BestOf2NearestMatcher (all pairs), w >= 1 BestOf2NearestRangeMatcher (pairs with j < i + w only)
+    int range_width = -1;
 };
+
+// range_width of the config: -1 or >= 1 (mis_match_pairs_select refuses the rest too; this is the check before any device work)
+inline int check_range_width(int w) {
+    if (w != -1 && w < 1) throw std::runtime_error("range_width " + std::to_string(w) + ": -1 (match all pairs) or a width >= 1");
+    return w;
+}
+// how many pairs a matcher call selects for these keypoint counts (the rule of mis_match_pairs_select without a mask)
+inline int selected_pair_count(const std::vector<int>& counts, int range_width) {
+    int np = 0;
+    for (size_t i = 0; i < counts.size(); i++)
+        for (size_t j = i + 1; j < counts.size(); j++)
+            np += counts[i] > 0 && counts[j] > 0 && (range_width == -1 || (int)j < (int)i + range_width);
+    return np;
+}
 
 // warp_type -> MIS_WARP_*; the reference's other warpers (:933-964) are not implemented, anything else is not a warper at all
 inline int warp_kind(const std::string& t) {

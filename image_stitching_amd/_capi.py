@@ -118,6 +118,7 @@ PROTOTYPES = {
     "mis_match_default_params": (None, [_P(MisMatchParams)]),
     "mis_match_all_pairs": (_i, [_vp, _P(MisFeatures), _i, _P(MisMatchParams), _P(MisMatchesInfo)]),
     "mis_match_pairs_sharded": (_i, [_vp, _P(MisFeatures), _i, _P(MisMatchParams), _i, _i, _P(MisMatchesInfo)]),
+    "mis_match_pairs_select": (_i, [_vp, _P(MisFeatures), _i, _P(MisMatchParams), _vp, _i, _i, _i, _P(MisMatchesInfo)]),
     "mis_matches_free": (_i, [_P(MisMatchesInfo), _i]),
     "mis_match_sequence": (C.c_longlong, [_vp]),
     "mis_match_knn_fence": (_i, [_vp, _vp, C.c_longlong, _i]),

@@ -805,16 +805,17 @@ int l2_knn2_pairs(MisContext* ctx, Arena& arena, const MisFeatures* f, int nsets
 
 enum DescKind { DESC_NONE, DESC_BINARY, DESC_L2 };
 // What a matcher call does, decided on the host before anything is enqueued.  FeaturesMatcher::operator(): all i < j with
-// non-empty keypoint lists, dealt round-robin over ranks.
+// non-empty keypoint lists that the mask (strict upper triangle, NULL: all) and BestOf2NearestRangeMatcher's range_width
+// (-1: all, else j < i + range_width) select, dealt round-robin over ranks.
 struct MatchPlan {
     std::vector<PairDesc> pairs;
     std::vector<FeatDev> fd;               // one per frame
     size_t knn_total = 0, m_total = 0;     // 2-NN queries of both directions of every pair; match capacity of every pair
-    int maxq = 0;                          // the largest keypoint count of a frame
+    int maxq = 0;                          // the largest keypoint count of a frame of a selected pair
     DescKind kind = DESC_NONE;
     std::vector<HmJob> hm_jobs;            // workgroup table of the Hamming pass on the matrix cores (binary, <= HM_MAX_TRAINS)
 };
-int plan_match(MisContext* ctx, const MisFeatures* feats, int n, int rank, int world, MatchPlan* pl) {
+int plan_match(MisContext* ctx, const MisFeatures* feats, int n, const uint8_t* mask, int range_width, int rank, int world, MatchPlan* pl) {
     std::vector<PairDesc>& pairs = pl->pairs;
     pl->fd.resize(n);
     bool use_l2 = false, use_bin = false;
@@ -826,14 +827,16 @@ int plan_match(MisContext* ctx, const MisFeatures* feats, int n, int rank, int w
         MIS_CHECK(ctx, feats[i].n < (1 << 22), MIS_E_UNSUPPORTED, "more than 4 M keypoints in one image");   // index bits of the 2-NN keys
         if (feats[i].n > 0) { if (l2_i) use_l2 = true; else use_bin = true; }
         pl->fd[i] = FeatDev{(const uint8_t*)feats[i].descriptors, feats[i].keypoints, feats[i].n, feats[i].img_w, feats[i].img_h};
-        pl->maxq = std::max(pl->maxq, feats[i].n);
     }
     int pair_index = 0;
     for (int i = 0; i < n; i++)
         for (int j = i + 1; j < n; j++) {
             if (feats[i].n <= 0 || feats[j].n <= 0) continue;
+            if (mask && !mask[(size_t)i * n + j]) continue;
+            if (range_width != -1 && j >= i + range_width) continue;
             if ((pair_index++ % world) != rank) continue;
             const int cap = feats[i].n + feats[j].n;
+            pl->maxq = std::max(pl->maxq, std::max(feats[i].n, feats[j].n));
             pairs.push_back(PairDesc{i, j, pl->knn_total, pl->knn_total + feats[i].n, pl->m_total, cap});
             pl->knn_total += cap; pl->m_total += cap;
         }
@@ -1091,9 +1094,11 @@ void trace_report(MatchWorkspace* ws, std::chrono::steady_clock::time_point t_be
             ms(1), ms(6), ms(2), ms(3), ms(4), ms(5));
 }
 
-int match_impl(MisContext* ctx, const MisFeatures* feats, int n, const MisMatchParams* p, int rank, int world, MisMatchesInfo* out) {
+int match_impl(MisContext* ctx, const MisFeatures* feats, int n, const MisMatchParams* p, const uint8_t* mask, int range_width, int rank, int world,
+               MisMatchesInfo* out) {
     MIS_CHECK(ctx, feats && p && out && n >= 1, MIS_E_INVALID, "null argument");
     MIS_CHECK(ctx, world >= 1 && rank >= 0 && rank < world, MIS_E_INVALID, "bad rank / world size");
+    MIS_CHECK(ctx, range_width == -1 || range_width >= 1, MIS_E_INVALID, "range_width must be -1 (all pairs) or >= 1");
     MIS_HIP(ctx, hipSetDevice(ctx->device));
     // whatever happens below, a thread waiting in mis_match_knn_fence for this call is released when it returns
     const auto t_begin = std::chrono::steady_clock::now();
@@ -1105,7 +1110,7 @@ int match_impl(MisContext* ctx, const MisFeatures* feats, int n, const MisMatchP
     for (int i = 0; i < n * n; i++) init_info(&out[i]);
     MatchPlan pl;
     int rc;
-    if ((rc = plan_match(ctx, feats, n, rank, world, &pl)) != MIS_OK) return rc;
+    if ((rc = plan_match(ctx, feats, n, mask, range_width, rank, world, &pl)) != MIS_OK) return rc;
     const int np = (int)pl.pairs.size();
     if (np == 0) return MIS_OK;
     MatchWorkspace* ws = workspace(ctx);
@@ -1163,7 +1168,7 @@ int match_impl(MisContext* ctx, const MisFeatures* feats, int n, const MisMatchP
 }  // namespace
 
 // One-shot hook of this context's NEXT matcher call: fn(user) runs on the calling thread of mis_match_all_pairs /
-// mis_match_pairs_sharded once all of the call's device work is enqueued, before the call waits for the device.
+// mis_match_pairs_sharded / mis_match_pairs_select once all of the call's device work is enqueued, before the call waits for the device.
 extern "C" int mis_match_on_enqueued(MisContext* ctx, void (*fn)(void*), void* user) {
     if (!ctx) return MIS_E_INVALID;
     MatchWorkspace* ws = workspace(ctx);
@@ -1208,13 +1213,19 @@ extern "C" void mis_match_default_params(MisMatchParams* p) {
 
 extern "C" int mis_match_all_pairs(MisContext* ctx, const MisFeatures* feats, int n, const MisMatchParams* p, MisMatchesInfo* out) {
     if (!ctx) return MIS_E_INVALID;
-    return match_impl(ctx, feats, n, p, 0, 1, out);
+    return match_impl(ctx, feats, n, p, nullptr, -1, 0, 1, out);
 }
 
 extern "C" int mis_match_pairs_sharded(MisContext* ctx, const MisFeatures* feats, int n, const MisMatchParams* p, int rank, int world,
                                        MisMatchesInfo* out) {
     if (!ctx) return MIS_E_INVALID;
-    return match_impl(ctx, feats, n, p, rank, world, out);
+    return match_impl(ctx, feats, n, p, nullptr, -1, rank, world, out);
+}
+
+extern "C" int mis_match_pairs_select(MisContext* ctx, const MisFeatures* feats, int n, const MisMatchParams* p, const uint8_t* mask, int range_width,
+                                      int rank, int world, MisMatchesInfo* out) {
+    if (!ctx) return MIS_E_INVALID;
+    return match_impl(ctx, feats, n, p, mask, range_width, rank, world, out);
 }
 
 extern "C" int mis_matches_free(MisMatchesInfo* m, int count) {

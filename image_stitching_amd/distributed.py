@@ -154,6 +154,7 @@ class HipEngine:
         self.cfg = config or st.StitchConfig.hot_path()
         self.warp_type = self.cfg.warp_type            # the warper this engine runs (StitchJob checks it against the job's)
         self.kind = st.check_warp_config(self.cfg)
+        self.range_width = st.check_range_config(self.cfg)      # the pair selection this engine's matcher makes (StitchJob checks it against the job's)
         self.frame_size = frame_size
         # features come from the work image (image_stitching.cpp:589-603, :613): the finder is sized for it, and the work frames
         # live in buffers allocated on first use and kept (an allocation per run would synchronise the device)
@@ -161,7 +162,7 @@ class HipEngine:
         self._work_frames = []
         # finder per features_type (image_stitching.cpp:543-563): ORB, or SIFT (float descriptors -> the L2 matcher)
         self.finder = st.SiftFeatureFinder(ctx, self.work_size) if self.cfg.features_type == "sift" else st.OrbFeatureFinder(ctx, self.work_size)
-        self.matcher = st.BestOf2NearestMatcher(ctx, self.cfg.match_conf)
+        self.matcher = st.make_matcher(ctx, self.cfg)
         self.blender = None
         self._keep = []
         # warp + blend run in a context of their own (second stream): StitchJob composes speculatively while the
@@ -457,11 +458,16 @@ class StitchJob:
         self.cfg = config or st.StitchConfig.hot_path()
         st.check_seam_config(self.cfg)
         self.kind = st.check_warp_config(self.cfg)
+        st.check_range_config(self.cfg)
         self.engine = engine or HipEngine(ctx, frame_size, self.cfg)
         # an engine warps one kind (its own config's; spherical when it does not say): never another than the job's
         engine_warp = getattr(self.engine, "warp_type", "spherical")
         if engine_warp != self.cfg.warp_type:
             raise NotImplementedError("warp_type %r: the engine %s warps %r only" % (self.cfg.warp_type, type(self.engine).__name__, engine_warp))
+        # range_width (:646-649): the engine's matcher makes the selection; an engine that does not declare one matches all pairs
+        engine_range = getattr(self.engine, "range_width", -1)
+        if engine_range != self.cfg.range_width:
+            raise NotImplementedError("range_width %r: the engine %s matches with range_width %r only" % (self.cfg.range_width, type(self.engine).__name__, engine_range))
         # work scale (image_stitching.cpp:589-603): the engine detects on resized frames and everything between features and
         # composition is in work units; an engine that does not resize is refused, not run at full resolution
         self.work_scale, self.work_size = st.work_geometry(self.cfg, frame_size)

@@ -865,14 +865,25 @@ class BestOf2NearestMatcher:
         self.params = match_params(match_conf=match_conf, num_matches_thresh1=num_matches_thresh1,
                                    num_matches_thresh2=num_matches_thresh2)
 
-    def __call__(self, features, rank=0, world_size=1):
-        """(*matcher)(features, pairwise_matches) -> list of n*n MatchesInfo (row-major)."""
+    range_width = -1
+
+    def __call__(self, features, rank=0, world_size=1, mask=None):
+        """(*matcher)(features, pairwise_matches, mask) -> list of n*n MatchesInfo (row-major).  mask: n x n, non-zero at (i, j),
+        i < j, where the pair is to be matched (only the strict upper triangle is read); unselected entries stay default."""
         n = len(features)
+        if mask is not None:
+            mask = np.ascontiguousarray(mask)
+            if mask.shape != (n, n):
+                raise ValueError("mask must be %d x %d, got shape %r" % (n, n, mask.shape))
+            mask = np.ascontiguousarray(mask != 0, np.uint8)
         arr = (capi.MisFeatures * n)()
         for k, f in enumerate(features):
             C.memmove(C.byref(arr[k]), C.byref(f.raw), C.sizeof(capi.MisFeatures))
         mis = (capi.MisMatchesInfo * (n * n))()
-        if world_size == 1:
+        if mask is not None or self.range_width != -1:
+            rc = self.ctx.lib.mis_match_pairs_select(self.ctx.h, arr, n, C.byref(self.params), None if mask is None else mask.ctypes.data_as(C.c_void_p),
+                                                     int(self.range_width), rank, world_size, mis)
+        elif world_size == 1:
             rc = self.ctx.lib.mis_match_all_pairs(self.ctx.h, arr, n, C.byref(self.params), mis)
         else:
             rc = self.ctx.lib.mis_match_pairs_sharded(self.ctx.h, arr, n, C.byref(self.params), rank, world_size, mis)
@@ -881,6 +892,30 @@ class BestOf2NearestMatcher:
 
     def collectGarbage(self):
         pass
+
+
+class BestOf2NearestRangeMatcher(BestOf2NearestMatcher):
+    """makePtr<BestOf2NearestRangeMatcher>(range_width, try_cuda, match_conf) (image_stitching.cpp:649): only the pairs with
+    j < i + range_width are matched (2: adjacent frames; 1: none).  The width is checked by the library call (-1 or >= 1)."""
+
+    def __init__(self, ctx, range_width=5, match_conf=0.32, num_matches_thresh1=6, num_matches_thresh2=6):
+        super().__init__(ctx, match_conf, num_matches_thresh1, num_matches_thresh2)
+        self.range_width = int(range_width)
+
+
+def make_matcher(ctx, cfg):
+    """if (range_width == -1) BestOf2NearestMatcher else BestOf2NearestRangeMatcher (image_stitching.cpp:646-649)"""
+    if cfg.range_width == -1:
+        return BestOf2NearestMatcher(ctx, cfg.match_conf)
+    return BestOf2NearestRangeMatcher(ctx, cfg.range_width, cfg.match_conf)
+
+
+def selected_pairs(counts, range_width=-1, mask=None):
+    """The pairs a matcher call selects, in the order it matches and shards them (pair k goes to rank k % world_size): (i, j),
+    i < j, both frames with keypoints (counts[i] > 0), mask None or mask[i][j] != 0, range_width -1 or j < i + range_width."""
+    n = len(counts)
+    return [(i, j) for i in range(n) for j in range(i + 1, n)
+            if counts[i] > 0 and counts[j] > 0 and (mask is None or mask[i][j] != 0) and (range_width == -1 or j < i + range_width)]
 
 
 def leaveBiggestComponent(pairwise_matches, n, conf_threshold):
@@ -998,6 +1033,14 @@ def check_warp_config(cfg):
     return warp_kind(cfg.warp_type)
 
 
+def check_range_config(cfg):
+    """range_width of the config: -1 (all pairs) or a width >= 1, else ValueError before any device work."""
+    rw = cfg.range_width
+    if isinstance(rw, bool) or not isinstance(rw, (int, np.integer)) or not (rw == -1 or rw >= 1):
+        raise ValueError("range_width %r: -1 (match all pairs) or an integer >= 1 (image_stitching.cpp:83, :646-649)" % (rw,))
+    return int(rw)
+
+
 def check_seam_config(cfg):
     if cfg.seam_find_type not in ("no", "voronoi", "dp_color"):
         raise NotImplementedError("seam_find_type %r: 'no', 'voronoi' and 'dp_color' are implemented (dp_colorgrad and the "
@@ -1100,6 +1143,7 @@ class StitchConfig:
     conf_thresh: float = 0.95
     features_type: str = "orb"
     match_conf: float = 0.32
+    range_width: int = -1             # -1: all pairs; w >= 1: BestOf2NearestRangeMatcher, pairs with j < i + w only (:83, :646-649)
     warp_type: str = "spherical"
     blend_type: int = capi.BLEND_MULTI_BAND
     blend_strength: float = 5.0
@@ -1142,11 +1186,12 @@ class Stitcher:
         self.ctx = ctx
         self.cfg = config or StitchConfig()
         self.kind = check_warp_config(self.cfg)
+        check_range_config(self.cfg)
         self.frame_size = frame_size
         # features come from the work image (image_stitching.cpp:602, :613): the finder is sized for it
         self.work_scale, self.work_size = work_geometry(self.cfg, frame_size)
         self.finder = OrbFeatureFinder(ctx, self.work_size)
-        self.matcher = BestOf2NearestMatcher(ctx, self.cfg.match_conf)
+        self.matcher = make_matcher(ctx, self.cfg)
 
     def work_cameras(self, cameras):
         """The caller's full-resolution cameras in work units (cam.focal, ppx, ppy *= work_scale, image_stitching.cpp:635-637);

@@ -167,6 +167,14 @@ int mis_match_all_pairs(MisContext* ctx, const MisFeatures* feats, int n, const 
 /* sharded form: only the pairs with (pair_index % world_size) == rank are matched (others left default) */
 int mis_match_pairs_sharded(MisContext* ctx, const MisFeatures* feats, int n, const MisMatchParams* p, int rank,
                             int world_size, MisMatchesInfo* out);
+/* BestOf2NearestRangeMatcher(range_width, ...) and the pair mask of FeaturesMatcher::operator() -- replaces
+ * image_stitching.cpp:646-649.  A pair (i, j), i < j, is matched iff both frames have keypoints, `mask` is NULL or
+ * mask[i*n + j] != 0 (n*n row-major; only the strict upper triangle is read), and range_width == -1 or j < i + range_width
+ * (2: adjacent frames only; 1: nothing).  The selected pairs keep their row-major order and are dealt
+ * (selected_pair_index % world_size) == rank; every other entry stays default-initialised.  range_width must be -1 or >= 1.
+ * mis_match_all_pairs and mis_match_pairs_sharded are the (NULL, -1) case. */
+int mis_match_pairs_select(MisContext* ctx, const MisFeatures* feats, int n, const MisMatchParams* p, const uint8_t* mask,
+                           int range_width, int rank, int world_size, MisMatchesInfo* out);
 int mis_matches_free(MisMatchesInfo* m, int count);
 /* Ordering aid for a caller that overlaps other device work with a matcher call made by another host thread (the
  * job's speculative composition): mis_match_sequence = number of matcher calls this context has started;
@@ -177,7 +185,7 @@ int mis_matches_free(MisMatchesInfo* m, int count);
 long long mis_match_sequence(MisContext* ctx);
 int mis_match_knn_fence(MisContext* ctx, void* stream, long long target_seq, int timeout_ms);
 /* The same without a second host thread: a one-shot hook of this context's NEXT matcher call.  fn(user) runs on the thread that
- * calls mis_match_all_pairs / mis_match_pairs_sharded, once all of the call's device work is enqueued and before the call waits
+ * calls mis_match_all_pairs / mis_match_pairs_sharded / mis_match_pairs_select, once all of the call's device work is enqueued and before the call waits
  * for the device (the ~5 ms in which that thread is idle); inside it mis_match_knn_fence(ctx, stream, mis_match_sequence(ctx), 0)
  * returns at once and queues `stream` behind the 2-NN pass.  The hook is not called when the matcher call fails earlier. */
 int mis_match_on_enqueued(MisContext* ctx, void (*fn)(void*), void* user);
