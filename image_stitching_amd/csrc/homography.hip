@@ -44,8 +44,8 @@ constexpr int TB = 256;           // threads of draw / scan_tail workgroups
 struct RansacState {
     int mode;      // 0 skip, 1 exactly 4 points, 2 RANSAC
     int n_sub;     // subsets drawn so far (the sequential getSubset sequence)
-    int iter, niters, max_good, done, best_k, result;
-    int tail_pending;   // the loop ended in a scan-only launch: mask / DLT / LM refinement still to run (scan_tail_kernel parts 3 / 4)
+    int iter, niters, max_good, done, best_k;
+    int tail_pending;   // the loop ended in a replay-only launch: 1 = mask / compaction, 2 = DLT + LM refinement still to run (TAIL_MASK_ONLY, TAIL_REFINE_ONLY)
     int draw_k, draw_fail;   // next iteration to draw; getSubset exhausted its 10000 attempts
     long long draw_pos;      // RNG stream position after the last drawn subset
     // where the speculative drawing (draw_kernel, DRAW_SPEC) stopped: subsets [0, spec_k) are in sub_idx, the stream stands at spec_pos
@@ -53,6 +53,91 @@ struct RansacState {
     // counts and replay run at the same time and read n_sub / draw_fail.  The second phase's draw adopts them (spec_k > draw_k)
     int spec_k, spec_fail;
     long long spec_pos;
+};
+
+// What a draw_kernel launch draws: the first phase's subsets, the second phase's, or the second phase's ahead of time (see
+// DRAW_SPEC_CHUNKS below)
+enum DrawPhase { DRAW_FIRST, DRAW_SECOND, DRAW_SPEC };
+// What a scan_tail_kernel launch does.  The split lets the tails of the problems that end in the first RANSAC phase (latency
+// bound, ~2 ms) run on another stream while the second phase of the others -- which only needs the replay's verdict -- goes on.
+enum TailKind {
+    TAIL_REPLAY_FINISH,   // replay, then the whole tail of the problems that end here (mask, DLT on the inliers, LM refinement)
+    TAIL_REPLAY_ONLY,     // replay; a problem that ends here is marked tail_pending
+    TAIL_MASK_ONLY,       // the pending problems whose fin equals `want`: inlier mask + ordered compaction
+    TAIL_REFINE_ONLY,     // ... DLT + LM refinement on the compacted inliers
+};
+
+// ---------------------------------------------------------------- instrumentation --------------
+// Section timers, counters and one log line per tail for tools/tail_prof.py, in a library built with -DMIS_TAIL_PROF
+// (-DMIS_JAC_PROF adds the per-rotation timers of the cooperative Jacobi, -DMIS_PS_PROF the stage timers of ordered_sums; both
+// slow what they measure).  The kernels below only name these helpers: all of them compile to nothing in the product build.
+#ifdef MIS_TAIL_PROF
+#define PROF_ONLY(...) __VA_ARGS__
+__device__ unsigned long long g_draw_prof[12];  // per phase p (0, 1): [4p] chunks (all problems), [4p+1] most chunks of a problem, [4p+2] longest problem (wall ticks), [4p+3] problems with work;
+                                                // [8..11], per chunk of the parallel path: attempt simulation, pointer doubling, ranks + copy (wall ticks), chunks
+__device__ unsigned long long g_hyp_prof[8];    // [6], [7]: summed / longest replay of a second phase (scan_tail_kernel)
+__device__ unsigned long long g_jac_prof[8];    // shader cycles: pivot search, math, rotation, index update (summed over rotations); [6], [7]: points, passes of the normal equations
+__device__ unsigned long long g_tail_log[6 * 1024];
+__device__ unsigned g_tail_log_n;
+__device__ unsigned long long g_tail_prof[12];  // jacobi ticks, rotations, normal_eq ticks, LM iterations, dlt ticks, tail ticks, tails, max tail ticks;
+                                                // [8..11], TAIL_REFINE_ONLY launches of the first phase: first entry (wall clock) + 1, last exit, longest workgroup, workgroups with work
+#else
+#define PROF_ONLY(...)
+#endif
+#if defined(MIS_TAIL_PROF) && defined(MIS_JAC_PROF)     // per-rotation section timers: they serialise the rotation (s_memtime waits for the LDS queue), use the coarse ones for totals
+#define JAC_ONLY(...) __VA_ARGS__
+#else
+#define JAC_ONLY(...)
+#endif
+#if defined(MIS_TAIL_PROF) && defined(MIS_PS_PROF)
+#define PS_ONLY(...) __VA_ARGS__
+#else
+#define PS_ONLY(...)
+#endif
+// wall-clock sections of g_tail_prof (thread 0 of a workgroup)
+#define PROF_T0(v) PROF_ONLY(unsigned long long v = wall_clock64())
+#define PROF_ADD(i, v) PROF_ONLY(do { if (threadIdx.x == 0) atomicAdd(&g_tail_prof[i], wall_clock64() - (v)); } while (0))
+// shader-cycle sections of g_jac_prof: the cooperative Jacobi (JP_KEEP: the section's results exist before the next timer is read) ...
+#define JP_T(v) JAC_ONLY(const unsigned long long v = __builtin_readcyclecounter())
+#define JP_ADD(i, a, b) JAC_ONLY(do { if (threadIdx.x == 0) atomicAdd(&g_jac_prof[i], (b) - (a)); } while (0))
+#define JP_KEEP(...) JAC_ONLY(asm volatile("" :: __VA_ARGS__))
+// ... and the stages of ordered_sums (PS_SUM / PS_ACC: a section summed over the stages, PS_ADD: by thread `who`)
+#define PS_T(v) PS_ONLY(const unsigned long long v = __builtin_readcyclecounter())
+#define PS_SUM(v) PS_ONLY(unsigned long long v = 0)
+#define PS_ACC(v, a, b) PS_ONLY(v += (b) - (a))
+#define PS_KEEP(x) PS_ONLY(asm volatile("" :: "v"(x)))
+#define PS_ADD(i, who, a, b) PS_ONLY(do { if (threadIdx.x == (who)) atomicAdd(&g_jac_prof[i], (b) - (a)); } while (0))
+// a tail's rotations and LM iterations (totals, and TailShared's prof_rot / prof_lm for its log line); a pass of the normal equations
+#define PROF_ROTATIONS(S, n) PROF_ONLY(do { if (threadIdx.x == 0) { atomicAdd(&g_tail_prof[1], (unsigned long long)(n)); (S).prof_rot += (n); } } while (0))
+#define PROF_LM_ITERATION(S) PROF_ONLY(do { if (threadIdx.x == 0) { atomicAdd(&g_tail_prof[3], 1ull); (S).prof_lm++; } } while (0))
+#define PROF_LM_PASS(np) PROF_ONLY(do { if (threadIdx.x == 0) { atomicAdd(&g_jac_prof[6], (unsigned long long)(np)); atomicAdd(&g_jac_prof[7], 1ull); } } while (0))
+// scan_tail_kernel: entry and exit of the workgroups of the first phase's TAIL_REFINE_ONLY launch; a second phase's replay (thread 0)
+#define PROF_FIRST_ENTRY(kind, want, wg_in) PROF_ONLY(const unsigned long long wg_in = wall_clock64(); if ((kind) == TAIL_REFINE_ONLY && (want) == 0 && threadIdx.x == 0) atomicMin(&g_tail_prof[8], wg_in))
+#define PROF_LAST_EXIT(kind, want, wg_in) PROF_ONLY(do { if ((kind) == TAIL_REFINE_ONLY && (want) == 0 && threadIdx.x == 0) { const unsigned long long o = wall_clock64(); \
+        atomicMax(&g_tail_prof[9], o); atomicMax(&g_tail_prof[10], o - (wg_in)); atomicAdd(&g_tail_prof[11], 1ull); } } while (0))
+#define PROF_REPLAY(lo, t0) PROF_ONLY(do { if ((lo) > 0) { const unsigned long long d = wall_clock64() - (t0); atomicAdd(&g_hyp_prof[6], d); atomicMax(&g_hyp_prof[7], d); } } while (0))
+// a tail's DLT + LM refinement: PROF_TAIL_BEGIN starts its timer `pt`, PROF_TAIL_END adds the totals and the tail's log line --
+// points, LM iterations, rotations, ticks, launch kind, entry tick.  The launch kind is 10 x {0, 1, 3, 4}[kind] + want: the
+// numbers tools/tail_prof.py groups by
+#define PROF_TAIL_BEGIN(S, pt) PROF_ONLY(unsigned long long pt = wall_clock64(); if (threadIdx.x == 0) { (S).prof_rot = 0; (S).prof_lm = 0; })
+#define PROF_TAIL_END(S, np, kind, want, pt) PROF_ONLY(do { if (threadIdx.x == 0) { \
+        atomicAdd(&g_tail_prof[5], wall_clock64() - (pt)); atomicAdd(&g_tail_prof[6], 1ull); atomicMax(&g_tail_prof[7], wall_clock64() - (pt)); \
+        const int code[4] = {0, 1, 3, 4}; const unsigned k = atomicAdd(&g_tail_log_n, 1u); if (k < 1024) { unsigned long long* e = g_tail_log + 6 * k; e[0] = np; e[1] = (S).prof_lm; e[2] = (S).prof_rot; e[3] = wall_clock64() - (pt); e[4] = code[kind] * 10 + (want); e[5] = pt; } } } while (0))
+// draw_kernel: a problem's chunks and wall time per phase, and the three sections of a chunk of the pointer-doubling path
+struct DrawProf {
+    PROF_ONLY(unsigned long long t0 = wall_clock64(), last = t0, sim, dbl; int chunks = 0;)
+    __device__ __forceinline__ void simulated() { PROF_ONLY(chunks++; sim = wall_clock64();) }      // a chunk: the attempt lengths of its positions are known
+    __device__ __forceinline__ void doubled() { PROF_ONLY(dbl = wall_clock64();) }        // ... the attempts the chain visits
+    __device__ __forceinline__ void ranked() {                                            // ... the accepted subsets copied (thread 0)
+        PROF_ONLY(const unsigned long long now = wall_clock64(); atomicAdd(&g_draw_prof[8], sim - last); atomicAdd(&g_draw_prof[9], dbl - sim); atomicAdd(&g_draw_prof[10], now - dbl); atomicAdd(&g_draw_prof[11], 1ull);)
+    }
+    __device__ __forceinline__ void chunk_end() { PROF_ONLY(last = wall_clock64();) }
+    __device__ __forceinline__ void end(DrawPhase phase) {
+        PROF_ONLY(if (threadIdx.x == 0 && chunks && phase != DRAW_SPEC) {
+            unsigned long long* g = g_draw_prof + (phase == DRAW_SECOND ? 4 : 0);
+            atomicAdd(&g[0], (unsigned long long)chunks); atomicMax(&g[1], (unsigned long long)chunks); atomicMax(&g[2], wall_clock64() - t0); atomicAdd(&g[3], 1ull);
+        })
+    }
 };
 
 // ---------------------------------------------------------------- shared scalar helpers --------
@@ -181,9 +266,6 @@ __device__ void dlt_denormalise(const double* H0, const double* nrm /* cmx cmy c
 #ifndef MIS_CHAIN_PRIO
 #define MIS_CHAIN_PRIO 3
 #endif
-#ifdef MIS_TAIL_PROF
-__device__ unsigned long long g_draw_prof[12];   // per phase p (0, 1): [4p] chunks (all problems), [4p+1] most chunks of a problem, [4p+2] longest problem (wall ticks), [4p+3] problems with work
-#endif
 // ---------------------------------------------------------------- draw_kernel ------------------
 // cv::RNG multiply-with-carry stream: U[s] is the (s+1)-th output from seed (uint64)-1
 struct DrawCtx {
@@ -192,8 +274,7 @@ struct DrawCtx {
     long long lds_base = 0;
     int lds_n = 0;
     bool lds_mod = false;              // the staged values are draw % n
-    unsigned long long state_T;  // generator state after RNG_TABLE draws
-    // serial continuation beyond the table (positions are visited in increasing order)
+    // serial continuation beyond the table (positions are visited in increasing order), from the generator's state after RNG_TABLE draws
     unsigned long long cur_state;
     long long cur_pos;
 };
@@ -281,305 +362,309 @@ constexpr int DRAW_PTS = 2048;
 // inliers alone) are drawn up to B4(n) here, on another stream, beside the first phase's solves; the second phase's launch takes
 // the state over and draws on only where niters reaches past it.  Nothing is appended to the work list, and n_sub / draw_k /
 // draw_fail keep the first phase's values until then.
-constexpr int DRAW_SPEC = 2;
-// chunks of stream positions a problem may spend here: a problem whose attempts are mostly rejected (collinear or coincident
+// chunks of stream positions a problem may spend there: a problem whose attempts are mostly rejected (collinear or coincident
 // points: a million positions for 2000 subsets) would hold the stream the second phase waits for, for subsets it may never need.
 // The few-match pairs of a 16-frame job take 7 chunks at most (tools/tail_prof.py): their launch runs 0.30 ms beside the first
 // phase's solves and ends 28 us before that phase's replay does, so 8 -- one chunk more than that job needs -- costs the chain nothing.
 constexpr int DRAW_SPEC_CHUNKS = 8;
-__global__ __launch_bounds__(DRAW_TB) void draw_kernel(const HomoCall* calls, RansacState* states, int* sub_idx, int* draw_idx, const unsigned* U,
-                                                  unsigned long long state_T, int max_iters, int phase, int k_hi_arg, int2* work, unsigned* work_ctr,
-                                                  double confidence) {
-#if MIS_CHAIN_PRIO
-    __builtin_amdgcn_s_setprio(MIS_CHAIN_PRIO);      // a latency-bound chain beside the composition's bandwidth-bound kernels: its few waves issue first
-#endif
-    __shared__ unsigned char tab[DRAW_CHUNK];  // per position: min(end - start, 127) | pass << 7
-    __shared__ float2 pts[2 * DRAW_PTS];       // src then dst of small problems: the random gathers stay on chip
-    __shared__ long long s_pos, s_accpos, s_accend;    // s_accpos: the stream position behind the last accepted subset (s_accend: of this chunk)
-    __shared__ int s_k, s_attempts, s_more, s_kfirst, s_nacc;
-    __shared__ unsigned short acc_o[DRAW_CHUNK / 4];  // chunk offsets of the accepted attempts (serial path)
-    __shared__ unsigned short nxtA[DRAW_CHUNK + 1], nxtB[DRAW_CHUNK + 1];  // J^(2^r): start of the attempt 2^r hops ahead
-    __shared__ unsigned char reach[DRAW_CHUNK];
-    __shared__ unsigned su[DRAW_CHUNK + 128];
-    __shared__ int scan[DRAW_TB];
-    __shared__ int s_big, s_firstvis, s_lastaccvis;
-    __shared__ long long s_endpos;
-    const int b = blockIdx.x, t = threadIdx.x;
-#ifdef MIS_TAIL_PROF
-    const unsigned long long dpk = wall_clock64();
-#endif
-    const HomoCall c = calls[b];
-    RansacState* st = states + b;
-    if (phase == 0) {
+struct DrawShared {
+    float2 pts[2 * DRAW_PTS];       // src then dst of small problems: the random gathers stay on chip
+    long long pos, accpos, accend, endpos;    // pos: where the next chunk starts; accpos: the stream position behind the last accepted subset (accend: of this chunk)
+    unsigned su[DRAW_CHUNK + 128];  // the chunk's draws % n, and those of the 127 positions an attempt can reach past it
+    int scan[DRAW_TB];
+    int k, attempts, more, kfirst, nacc, firstvis, lastaccvis;
+    unsigned short acc_o[DRAW_CHUNK / 4];     // chunk offsets of the accepted attempts (serial path)
+    unsigned short nxtA[DRAW_CHUNK + 1], nxtB[DRAW_CHUNK + 1];  // J^(2^r): start of the attempt 2^r hops ahead
+    unsigned char tab[DRAW_CHUNK], reach[DRAW_CHUNK];  // tab, per position: min(end - start, 127) | pass << 7
+};
+// one problem's drawing in this launch, as its steps see it
+struct DrawProblem {
+    HomoCall c; RansacState* st; DrawPhase phase;
+    int k_hi;                                // draw the subsets of the iterations below this one
+    const float* psrc; const float* pdst;    // the points: in LDS (DrawShared::pts) when they fit
+    int* didx; int* sidx;                    // the indices of a chunk's attempts, by chunk offset; the problem's subsets, by iteration
+};
+
+// Entry of a phase: the first resets the problem's state, the second adopts what the speculative launch drew.  False: nothing to
+// draw or to list for this problem in this launch.  Otherwise *k_hi is set and the chunk loop's state stands in sh
+__device__ __forceinline__ bool draw_enter(DrawShared& sh, const HomoCall& c, RansacState* st, DrawPhase phase, int max_iters, int k_hi_arg, double confidence, int* k_hi_) {
+    const int t = threadIdx.x;
+    if (phase == DRAW_FIRST) {
         if (t == 0) {
             st->mode = (!c.active || c.n < 4) ? 0 : (c.n == 4 ? 1 : 2);
-            st->n_sub = 0; st->iter = 0; st->niters = max_iters > 1 ? max_iters : 1; st->max_good = 0; st->done = 0; st->best_k = -1; st->result = 0; st->tail_pending = 0;
+            st->n_sub = 0; st->iter = 0; st->niters = max_iters > 1 ? max_iters : 1; st->max_good = 0; st->done = 0; st->best_k = -1; st->tail_pending = 0;
             st->draw_k = 0; st->draw_fail = 0; st->draw_pos = 0;
             st->spec_k = 0; st->spec_fail = 0; st->spec_pos = 0;
         }
-        if (!c.active || c.n <= 4) return;
+        if (!c.active || c.n <= 4) return false;
     } else if (phase == DRAW_SPEC) {
         // (the first phase's replay may be writing iter / niters / done / ... of this problem: none of them is read here)
-        if (st->mode != 2 || st->draw_fail) return;
+        if (st->mode != 2 || st->draw_fail) return false;
     } else {
-        if (st->mode != 2 || st->done || st->draw_fail) return;     // (a failure of the first phase's drawing: n_sub < PHASE0)
+        if (st->mode != 2 || st->done || st->draw_fail) return false;     // (a failure of the first phase's drawing: n_sub < PHASE0)
         __syncthreads();                                            // every thread has read draw_fail before the adoption may set it
         if (t == 0 && st->spec_k > st->draw_k) { st->draw_k = st->n_sub = st->spec_k; st->draw_pos = st->spec_pos; st->draw_fail = st->spec_fail; }
     }
     __syncthreads();
-    int k_hi = min(k_hi_arg, phase == 0 ? max_iters : st->niters);
+    int k_hi = min(k_hi_arg, phase == DRAW_FIRST ? max_iters : st->niters);
     if (phase == DRAW_SPEC) {
         k_hi = ransac_update_num_iters(confidence, (double)(c.n - 4) / c.n, max_iters);
-        if (!(k_hi > PHASE0 && k_hi < max_iters)) return;      // uniform
+        if (!(k_hi > PHASE0 && k_hi < max_iters)) return false;      // uniform
     }
-    // (an adopted give-up lies at n_sub: nothing more to draw, its hypotheses go to the list below)
-    if (t == 0) { s_pos = s_accpos = st->draw_pos; s_k = st->draw_k; s_attempts = 0; s_more = s_k < k_hi && !st->draw_fail; }
+    // (an adopted give-up lies at n_sub: nothing more to draw, its hypotheses go to the list)
+    if (t == 0) { sh.pos = sh.accpos = st->draw_pos; sh.k = st->draw_k; sh.attempts = 0; sh.more = sh.k < k_hi && !st->draw_fail; }
     __syncthreads();
-    // the end of a problem's drawing in this launch
-    auto draw_ends = [&](long long pos, int k, int fail) {
-        if (phase == DRAW_SPEC) { st->spec_pos = pos; st->spec_k = k; st->spec_fail = fail; }
-        else { st->draw_pos = pos; st->draw_k = k; st->draw_fail = fail; st->n_sub = k; }
-    };
-    DrawCtx d;
-    d.U = U; d.state_T = state_T; d.cur_state = state_T; d.cur_pos = RNG_TABLE;
-    const float* psrc = c.src;
-    const float* pdst = c.dst;
-    if (c.n <= DRAW_PTS) {
-        for (int i = t; i < c.n; i += DRAW_TB) { pts[i] = reinterpret_cast<const float2*>(c.src)[i]; pts[DRAW_PTS + i] = reinterpret_cast<const float2*>(c.dst)[i]; }
-        psrc = reinterpret_cast<const float*>(pts); pdst = reinterpret_cast<const float*>(pts + DRAW_PTS);
-        __syncthreads();
-    }
-    int* didx = draw_idx + (size_t)b * DRAW_CHUNK * 4;
-    int* sidx = sub_idx + (size_t)b * max_iters * 4;
-    if (phase == 0 && c.n <= 10) {
-        // Tiny problems (a handful of spurious matches) are often infeasible outright: every ordered 4-tuple of distinct
-        // points fails checkSubset, so getSubset burns its 10000 attempts and the RANSAC loop ends without a model.
-        // All n (n-1)(n-2)(n-3) <= 5040 tuples are tested here; if none passes, that outcome is known without simulating
-        // ~150k stream positions (two such problems set the duration of the whole launch in a 16-frame job).
-        const int n = c.n, total = n * (n - 1) * (n - 2) * (n - 3);
-        int any = 0;
-        for (int q = t; q < total && !any; q += DRAW_TB) {
-            int r = q, id[4];
-            id[0] = r % n; r /= n;
-            int a1 = r % (n - 1); r /= (n - 1);
-            int a2 = r % (n - 2); r /= (n - 2);
-            int a3 = r;
-            // k-th unused index, in increasing order
-            auto pick = [&](int kth, int cnt) {
-                for (int v = 0; v < n; v++) {
-                    bool used = false;
-                    for (int u = 0; u < cnt; u++) used |= id[u] == v;
-                    if (!used && kth-- == 0) return v;
-                }
-                return 0;
-            };
-            id[1] = pick(a1, 1); id[2] = pick(a2, 2); id[3] = pick(a3, 3);
-            float ms1[8], ms2[8];
-            for (int i = 0; i < 4; i++) {
-                const float2 ps = reinterpret_cast<const float2*>(psrc)[id[i]], pd = reinterpret_cast<const float2*>(pdst)[id[i]];
-                ms1[2 * i] = ps.x; ms1[2 * i + 1] = ps.y; ms2[2 * i] = pd.x; ms2[2 * i + 1] = pd.y;
-            }
-            any |= check_subset(ms1, ms2) ? 1 : 0;
-        }
-        const int found = __syncthreads_or(any);
-#ifdef MIS_TAIL_PROF
-        (void)dpk;
-#endif
-        if (!found) {
-            if (t == 0) { st->draw_fail = 1; st->n_sub = 0; st->draw_k = 0; }
-            return;
-        }
-    }
-#ifdef MIS_TAIL_PROF
-    const unsigned long long dp0 = wall_clock64();
-    unsigned long long dp_last = dp0;
-    int dp_chunks = 0;
+    *k_hi_ = k_hi;
+    return true;
+}
+// the end of a problem's drawing in this launch
+__device__ __forceinline__ void draw_ends(const DrawProblem& p, long long pos, int k, int fail) {
+    if (p.phase == DRAW_SPEC) { p.st->spec_pos = pos; p.st->spec_k = k; p.st->spec_fail = fail; }
+    else { p.st->draw_pos = pos; p.st->draw_k = k; p.st->draw_fail = fail; p.st->n_sub = k; }
+}
 
-#endif
-    int spec_chunks = 0;
-    while (s_more) {
-        if (phase == DRAW_SPEC && spec_chunks++ == DRAW_SPEC_CHUNKS) {
-            // out of budget in the middle of a run of attempts: the state behind the last accepted subset, where a phase boundary
-            // stands too (no failed attempt counted yet), is what the second phase's launch continues from
-            if (t == 0) draw_ends(s_accpos, s_k, 0);
-            break;
-        }
-#ifdef MIS_TAIL_PROF
-        dp_chunks++;
-#endif
-        const long long base = s_pos;
-        // the chunk's random numbers (+ the 127 positions an attempt can reach past it) staged in LDS: an attempt is a chain of
-        // draw -> modulo -> duplicate test -> next draw, and from the table in global memory every link was a memory latency
-        // (17 of a chunk's 31 us)
-        __syncthreads();        // (the previous chunk's serial path may still read the staging)
-        for (int o = t; o < DRAW_CHUNK + 128; o += DRAW_TB) su[o] = (base + o < RNG_TABLE ? U[base + o] : 0u) % (unsigned)c.n;
-        d.lds_u = su; d.lds_base = base; d.lds_n = (int)max(0ll, min((long long)(DRAW_CHUNK + 128), (long long)RNG_TABLE - base)); d.lds_mod = true;
-        __syncthreads();
-        for (int o = t; o < DRAW_CHUNK; o += DRAW_TB) {      // lengths only; the verdicts of the visited attempts follow the chase
-            int idx[4];
-            const long long delta = attempt_len(d, base + o, c.n, idx) - (base + o);
-            tab[o] = (unsigned char)(delta > 127 ? 127 : delta);
-        }
-        if (t == 0) s_big = 0;
-        __syncthreads();
-#ifdef MIS_TAIL_PROF
-        const unsigned long long cs1 = wall_clock64();
-#endif
-        // ---- which attempts does the sequential chain visit?  start -> end -> ... by pointer doubling ----
-        constexpr int C = DRAW_CHUNK;
-        for (int q = t; q < C; q += DRAW_TB) {
-            const unsigned char e = tab[q];
-            if ((e & 0x7f) == 127) s_big = 1;  // an attempt longer than 126 draws: take the serial path for this chunk
-            nxtA[q] = (unsigned short)(q + (e & 0x7f));
-            reach[q] = q == 0;
-        }
-        if (t == 0) { nxtA[C] = C; nxtB[C] = C; }
-        __syncthreads();
-        if (!s_big) {
-            unsigned short* cur = nxtA;
-            unsigned short* oth = nxtB;
-            for (int r = 0; r < 11; r++) {  // 2^11 hops > C / 4 attempts
-                for (int q = t; q < C; q += DRAW_TB) if (reach[q]) { const int j = cur[q]; if (j < C) reach[j] = 1; }
-                __syncthreads();
-                for (int q = t; q < C; q += DRAW_TB) { const int j = min((int)cur[q], C); oth[q] = j < C ? cur[j] : (unsigned short)C; }
-                __syncthreads();
-                unsigned short* tmp = cur; cur = oth; oth = tmp;
+// Tiny problems (a handful of spurious matches) are often infeasible outright: every ordered 4-tuple of distinct
+// points fails checkSubset, so getSubset burns its 10000 attempts and the RANSAC loop ends without a model.
+// All n (n-1)(n-2)(n-3) <= 5040 tuples (n <= 10) are tested here; if none passes, that outcome is known without simulating
+// ~150k stream positions (two such problems set the duration of the whole launch in a 16-frame job).
+__device__ __forceinline__ bool any_feasible_subset(const float* psrc, const float* pdst, const int n) {
+    const int t = threadIdx.x, total = n * (n - 1) * (n - 2) * (n - 3);
+    int any = 0;
+    for (int q = t; q < total && !any; q += DRAW_TB) {
+        int r = q, id[4];
+        id[0] = r % n; r /= n;
+        int a1 = r % (n - 1); r /= (n - 1);
+        int a2 = r % (n - 2); r /= (n - 2);
+        int a3 = r;
+        // k-th unused index, in increasing order
+        auto pick = [&](int kth, int cnt) {
+            for (int v = 0; v < n; v++) {
+                bool used = false;
+                for (int u = 0; u < cnt; u++) used |= id[u] == v;
+                if (!used && kth-- == 0) return v;
             }
-#ifdef MIS_TAIL_PROF
-            const unsigned long long cs2 = wall_clock64();
-#endif
-            // checkSubset of the visited attempts: hops are >= 4 positions, so a thread's C / DRAW_TB = 4 consecutive positions hold at
-            // most one (every thread has at most one attempt to test)
-            const int q0 = t * (C / DRAW_TB);
-            int qv = -1;
-            for (int q = q0; q < q0 + C / DRAW_TB; q++) qv = reach[q] ? q : qv;
-            if (qv >= 0) {       // outside the loop: inside it the wave would run the test once per loop trip, a quarter of its lanes each time
+            return 0;
+        };
+        id[1] = pick(a1, 1); id[2] = pick(a2, 2); id[3] = pick(a3, 3);
+        float ms1[8], ms2[8];
+        for (int i = 0; i < 4; i++) {
+            const float2 ps = reinterpret_cast<const float2*>(psrc)[id[i]], pd = reinterpret_cast<const float2*>(pdst)[id[i]];
+            ms1[2 * i] = ps.x; ms1[2 * i + 1] = ps.y; ms2[2 * i] = pd.x; ms2[2 * i + 1] = pd.y;
+        }
+        any |= check_subset(ms1, ms2) ? 1 : 0;
+    }
+    return __syncthreads_or(any);
+}
+
+// The chunk's random numbers (+ the 127 positions an attempt can reach past it) staged in LDS: an attempt is a chain of
+// draw -> modulo -> duplicate test -> next draw, and from the table in global memory every link was a memory latency
+// (17 of a chunk's 31 us).  Then the length of the attempt that starts at every position: sh.tab (not yet fenced)
+__device__ __forceinline__ void simulate_attempts(DrawShared& sh, DrawCtx& d, const unsigned* U, const long long base, const int n) {
+    const int t = threadIdx.x;
+    __syncthreads();        // (the previous chunk's serial path may still read the staging)
+    for (int o = t; o < DRAW_CHUNK + 128; o += DRAW_TB) sh.su[o] = (base + o < RNG_TABLE ? U[base + o] : 0u) % (unsigned)n;
+    d.lds_u = sh.su; d.lds_base = base; d.lds_n = (int)max(0ll, min((long long)(DRAW_CHUNK + 128), (long long)RNG_TABLE - base)); d.lds_mod = true;
+    __syncthreads();
+    for (int o = t; o < DRAW_CHUNK; o += DRAW_TB) {      // lengths only; the verdicts of the visited attempts follow the chase
+        int idx[4];
+        const long long delta = attempt_len(d, base + o, n, idx) - (base + o);
+        sh.tab[o] = (unsigned char)(delta > 127 ? 127 : delta);
+    }
+}
+// start -> end of every attempt as the first table of the pointer doubling.  False: an attempt of the chunk is longer than 126
+// draws (tiny n) and the chunk takes the serial path
+__device__ __forceinline__ bool link_attempts(DrawShared& sh, DrawProf& prof) {
+    constexpr int C = DRAW_CHUNK;
+    const int t = threadIdx.x;
+    __shared__ int big;       // (this step's own: an attempt longer than 126 draws)
+    if (t == 0) big = 0;
+    __syncthreads();          // ... and every length is in sh.tab
+    prof.simulated();
+    for (int q = t; q < C; q += DRAW_TB) {
+        const unsigned char e = sh.tab[q];
+        if ((e & 0x7f) == 127) big = 1;
+        sh.nxtA[q] = (unsigned short)(q + (e & 0x7f));
+        sh.reach[q] = q == 0;
+    }
+    if (t == 0) { sh.nxtA[C] = C; sh.nxtB[C] = C; }
+    __syncthreads();
+    return !big;
+}
+// Which attempts does the sequential chain visit?  start -> end -> ... by pointer doubling; then checkSubset of the visited ones,
+// their ranks in stream order, and the accepted ones among them as the problem's next subsets
+__device__ __forceinline__ void doubling_chunk(DrawShared& sh, DrawCtx& d, const DrawProblem& p, const long long base, DrawProf& prof) {
+    constexpr int C = DRAW_CHUNK;
+    const int t = threadIdx.x;
+    unsigned short* cur = sh.nxtA;
+    unsigned short* oth = sh.nxtB;
+    for (int r = 0; r < 11; r++) {  // 2^11 hops > C / 4 attempts
+        for (int q = t; q < C; q += DRAW_TB) if (sh.reach[q]) { const int j = cur[q]; if (j < C) sh.reach[j] = 1; }
+        __syncthreads();
+        for (int q = t; q < C; q += DRAW_TB) { const int j = min((int)cur[q], C); oth[q] = j < C ? cur[j] : (unsigned short)C; }
+        __syncthreads();
+        unsigned short* tmp = cur; cur = oth; oth = tmp;
+    }
+    prof.doubled();
+    // checkSubset of the visited attempts: hops are >= 4 positions, so a thread's C / DRAW_TB = 4 consecutive positions hold at
+    // most one (every thread has at most one attempt to test)
+    const int q0 = t * (C / DRAW_TB);
+    int qv = -1;
+    for (int q = q0; q < q0 + C / DRAW_TB; q++) qv = sh.reach[q] ? q : qv;
+    if (qv >= 0) {       // outside the loop: inside it the wave would run the test once per loop trip, a quarter of its lanes each time
+        int idx[4];
+        attempt_len(d, base + qv, p.c.n, idx);
+        if (subset_passes(p.psrc, p.pdst, idx)) sh.tab[qv] |= 0x80;
+        *reinterpret_cast<int4*>(p.didx + 4 * qv) = make_int4(idx[0], idx[1], idx[2], idx[3]);
+    }
+    // ranks of the visited / accepted attempts in stream order (each thread owns C / DRAW_TB consecutive positions)
+    int lv = 0, la = 0;
+    for (int q = q0; q < q0 + C / DRAW_TB; q++) { const int rv = sh.reach[q]; lv += rv; la += rv && (sh.tab[q] & 0x80); }
+    sh.scan[t] = (lv << 16) | la;
+    __syncthreads();
+    for (int o = 1; o < DRAW_TB; o <<= 1) {
+        const int add = t >= o ? sh.scan[t - o] : 0;
+        __syncthreads();
+        sh.scan[t] += add;
+        __syncthreads();
+    }
+    const int incl = sh.scan[t], total = sh.scan[DRAW_TB - 1];
+    const int total_v = total >> 16, total_a = total & 0xffff;
+    int vr = (incl >> 16) - lv, ar = (incl & 0xffff) - la;  // exclusive ranks at q0
+    const int need = p.k_hi - sh.k, cut = min(total_a, need);
+    if (t == 0) { sh.firstvis = -1; sh.lastaccvis = -1; sh.endpos = -1; sh.accend = -1; }
+    __syncthreads();
+    for (int q = q0; q < q0 + C / DRAW_TB; q++) {
+        if (!sh.reach[q]) continue;
+        const unsigned char e = sh.tab[q];
+        if (e & 0x80) {
+            if (ar == 0) sh.firstvis = vr;
+            if (ar < cut) *reinterpret_cast<int4*>(p.sidx + 4 * (sh.k + ar)) = *reinterpret_cast<const int4*>(p.didx + 4 * q);
+            if (ar == cut - 1) { sh.lastaccvis = vr; sh.accend = base + q + (e & 0x7f); if (cut == need) sh.endpos = sh.accend; }
+            ar++;
+        }
+        if (vr == total_v - 1 && cut < need) sh.endpos = base + q + (e & 0x7f);  // the chain leaves the chunk here
+        vr++;
+    }
+    __syncthreads();
+    if (t == 0) {
+        int attempts = sh.attempts;
+        bool fail = false;
+        if (total_a == 0 || cut == 0) { attempts += total_v; fail = attempts >= 10000; }
+        else {
+            fail = attempts + sh.firstvis >= 10000;                 // getSubset gave up before the first accept
+            attempts = cut == need ? 0 : total_v - (sh.lastaccvis + 1);  // failures trailing the last accepted attempt
+        }
+        const int k = fail ? sh.k : sh.k + cut;
+        sh.pos = sh.endpos; sh.k = k; sh.attempts = attempts;
+        if (!fail && cut > 0) sh.accpos = sh.accend;
+        sh.more = !fail && k < p.k_hi;
+        if (!sh.more) draw_ends(p, sh.pos, k, fail);
+        prof.ranked();
+    }
+    __syncthreads();
+    prof.chunk_end();
+}
+// serial path (an attempt of the chunk consumed > 126 draws: tiny n): the verdict of every position, then one thread walks
+__device__ __forceinline__ void serial_chunk(DrawShared& sh, DrawCtx& d, const DrawProblem& p, const long long base) {
+    const int t = threadIdx.x;
+    __syncthreads();
+    for (int o = t; o < DRAW_CHUNK; o += DRAW_TB) {
+        if ((sh.tab[o] & 0x7f) == 127) continue;
+        int idx[4];
+        attempt_len(d, base + o, p.c.n, idx);
+        if (subset_passes(p.psrc, p.pdst, idx)) sh.tab[o] |= 0x80;
+        *reinterpret_cast<int4*>(p.didx + 4 * o) = make_int4(idx[0], idx[1], idx[2], idx[3]);
+    }
+    __syncthreads();
+    if (t == 0) {
+        long long pos = base;
+        int k = sh.k, attempts = sh.attempts, nacc = 0;
+        long long accpos = sh.accpos;
+        bool fail = false;
+        while (k < p.k_hi && pos < base + DRAW_CHUNK) {
+            unsigned char e = sh.tab[pos - base];
+            bool pass;
+            if ((e & 0x7f) != 127) {
+                pass = (e & 0x80) != 0;
+                if (pass) sh.acc_o[nacc++] = (unsigned short)(pos - base);  // indices copied in parallel after the chase
+                pos += e & 0x7f;
+            } else {  // an attempt that consumed > 126 draws (tiny n): redo it serially
                 int idx[4];
-                attempt_len(d, base + qv, c.n, idx);
-                if (subset_passes(psrc, pdst, idx)) tab[qv] |= 0x80;
-                *reinterpret_cast<int4*>(didx + 4 * qv) = make_int4(idx[0], idx[1], idx[2], idx[3]);
+                pos = attempt_at(d, pos, p.psrc, p.pdst, p.c.n, idx, &pass);
+                if (pass) { sh.acc_o[nacc++] = 0xffff; p.sidx[4 * k] = idx[0]; p.sidx[4 * k + 1] = idx[1]; p.sidx[4 * k + 2] = idx[2]; p.sidx[4 * k + 3] = idx[3]; }
             }
-            // ranks of the visited / accepted attempts in stream order (each thread owns C / DRAW_TB consecutive positions)
-            int lv = 0, la = 0;
-            for (int q = q0; q < q0 + C / DRAW_TB; q++) { const int rv = reach[q]; lv += rv; la += rv && (tab[q] & 0x80); }
-            scan[t] = (lv << 16) | la;
-            __syncthreads();
-            for (int o = 1; o < DRAW_TB; o <<= 1) {
-                const int add = t >= o ? scan[t - o] : 0;
-                __syncthreads();
-                scan[t] += add;
-                __syncthreads();
-            }
-            const int incl = scan[t], total = scan[DRAW_TB - 1];
-            const int total_v = total >> 16, total_a = total & 0xffff;
-            int vr = (incl >> 16) - lv, ar = (incl & 0xffff) - la;  // exclusive ranks at q0
-            const int need = k_hi - s_k, cut = min(total_a, need);
-            if (t == 0) { s_firstvis = -1; s_lastaccvis = -1; s_endpos = -1; s_accend = -1; }
-            __syncthreads();
-            for (int q = q0; q < q0 + C / DRAW_TB; q++) {
-                if (!reach[q]) continue;
-                const unsigned char e = tab[q];
-                if (e & 0x80) {
-                    if (ar == 0) s_firstvis = vr;
-                    if (ar < cut) *reinterpret_cast<int4*>(sidx + 4 * (s_k + ar)) = *reinterpret_cast<const int4*>(didx + 4 * q);
-                    if (ar == cut - 1) { s_lastaccvis = vr; s_accend = base + q + (e & 0x7f); if (cut == need) s_endpos = s_accend; }
-                    ar++;
-                }
-                if (vr == total_v - 1 && cut < need) s_endpos = base + q + (e & 0x7f);  // the chain leaves the chunk here
-                vr++;
-            }
-            __syncthreads();
-            if (t == 0) {
-                int attempts = s_attempts;
-                bool fail = false;
-                if (total_a == 0 || cut == 0) { attempts += total_v; fail = attempts >= 10000; }
-                else {
-                    fail = attempts + s_firstvis >= 10000;                 // getSubset gave up before the first accept
-                    attempts = cut == need ? 0 : total_v - (s_lastaccvis + 1);  // failures trailing the last accepted attempt
-                }
-                const int k = fail ? s_k : s_k + cut;
-                s_pos = s_endpos; s_k = k; s_attempts = attempts;
-                if (!fail && cut > 0) s_accpos = s_accend;
-                s_more = !fail && k < k_hi;
-                if (!s_more) draw_ends(s_pos, k, fail);
-#ifdef MIS_TAIL_PROF
-                const unsigned long long cs3 = wall_clock64();
-                atomicAdd(&g_draw_prof[8], cs1 - (dp_last)); atomicAdd(&g_draw_prof[9], cs2 - cs1); atomicAdd(&g_draw_prof[10], cs3 - cs2); atomicAdd(&g_draw_prof[11], 1ull);
-#endif
-            }
-            __syncthreads();
-#ifdef MIS_TAIL_PROF
-            dp_last = wall_clock64();
-#endif
-            continue;
+            attempts++;
+            if (pass) { k++; attempts = 0; accpos = pos; }
+            else if (attempts >= 10000) { fail = true; break; }  // getSubset gave up: the RANSAC loop ends here
         }
-        __syncthreads();
-        // serial path (an attempt of the chunk consumed > 126 draws: tiny n): the verdict of every position, then one thread walks
-        for (int o = t; o < DRAW_CHUNK; o += DRAW_TB) {
-            if ((tab[o] & 0x7f) == 127) continue;
-            int idx[4];
-            attempt_len(d, base + o, c.n, idx);
-            if (subset_passes(psrc, pdst, idx)) tab[o] |= 0x80;
-            *reinterpret_cast<int4*>(didx + 4 * o) = make_int4(idx[0], idx[1], idx[2], idx[3]);
-        }
-        __syncthreads();
-        if (t == 0) {
-            long long pos = base;
-            int k = s_k, attempts = s_attempts, nacc = 0;
-            long long accpos = s_accpos;
-            bool fail = false;
-            while (k < k_hi && pos < base + DRAW_CHUNK) {
-                unsigned char e = tab[pos - base];
-                bool pass;
-                if ((e & 0x7f) != 127) {
-                    pass = (e & 0x80) != 0;
-                    if (pass) acc_o[nacc++] = (unsigned short)(pos - base);  // indices copied in parallel after the chase
-                    pos += e & 0x7f;
-                } else {  // an attempt that consumed > 126 draws (tiny n): redo it serially
-                    int idx[4];
-                    pos = attempt_at(d, pos, psrc, pdst, c.n, idx, &pass);
-                    if (pass) { acc_o[nacc++] = 0xffff; sidx[4 * k] = idx[0]; sidx[4 * k + 1] = idx[1]; sidx[4 * k + 2] = idx[2]; sidx[4 * k + 3] = idx[3]; }
-                }
-                attempts++;
-                if (pass) { k++; attempts = 0; accpos = pos; }
-                else if (attempts >= 10000) { fail = true; break; }  // getSubset gave up: the RANSAC loop ends here
-            }
-            s_kfirst = s_k; s_nacc = nacc;
-            s_pos = pos; s_k = k; s_attempts = attempts; s_accpos = accpos;
-            s_more = !fail && k < k_hi;
-            if (!s_more) draw_ends(pos, k, fail);
-        }
-        __syncthreads();
-        for (int j = t; j < s_nacc; j += DRAW_TB) {
-            const unsigned o = acc_o[j];
-            if (o != 0xffff) *reinterpret_cast<int4*>(sidx + 4 * (s_kfirst + j)) = *reinterpret_cast<const int4*>(didx + 4 * o);
-        }
-        __syncthreads();
+        sh.kfirst = sh.k; sh.nacc = nacc;
+        sh.pos = pos; sh.k = k; sh.attempts = attempts; sh.accpos = accpos;
+        sh.more = !fail && k < p.k_hi;
+        if (!sh.more) draw_ends(p, pos, k, fail);
     }
-#ifdef MIS_TAIL_PROF
-    if (t == 0 && dp_chunks && phase != DRAW_SPEC) {
-        const int ph = phase ? 4 : 0;
-        atomicAdd(&g_draw_prof[ph], (unsigned long long)dp_chunks); atomicMax(&g_draw_prof[ph + 1], (unsigned long long)dp_chunks);
-        atomicMax(&g_draw_prof[ph + 2], wall_clock64() - dp0); atomicAdd(&g_draw_prof[ph + 3], 1ull);
+    __syncthreads();
+    for (int j = t; j < sh.nacc; j += DRAW_TB) {
+        const unsigned o = sh.acc_o[j];
+        if (o != 0xffff) *reinterpret_cast<int4*>(p.sidx + 4 * (sh.kfirst + j)) = *reinterpret_cast<const int4*>(p.didx + 4 * o);
     }
-#endif
-    // the phase's hypotheses [lo, min(n_sub, niters)) -- at or beyond niters they can never be replayed -- go to the work list in
-    // blocks of HQ_HYPS, with ONE atomic per problem.  Every return above leaves an empty range: mode 0 / 1, n_sub = 0 (no feasible
-    // subset), or in phase 1 a problem that is done or whose drawing failed in phase 0 (n_sub < PHASE0 then).  A speculative
-    // launch lists nothing: its subsets are listed by the second phase's launch, which knows how many of them count
-    if (t == 0 && phase != DRAW_SPEC) {
-        const int lo = phase == 0 ? 0 : min(PHASE0, max_iters), hi = min(st->n_sub, st->niters);
-        if (st->mode == 2 && !st->done && hi > lo) {
-            const int nb = (hi - lo + HQ_HYPS - 1) / HQ_HYPS;
-            const unsigned at = atomicAdd(work_ctr, (unsigned)nb);
-            for (int i = 0; i < nb; i++) work[at + i] = make_int2(b, lo + i * HQ_HYPS);
-        }
+    __syncthreads();
+}
+// The phase's hypotheses [lo, min(n_sub, niters)) -- at or beyond niters they can never be replayed -- go to the work list in
+// blocks of HQ_HYPS, with ONE atomic per problem (thread 0).  A problem that is done lists nothing
+__device__ __forceinline__ void list_hypotheses(const RansacState* st, const int b, DrawPhase phase, int max_iters, int2* work, unsigned* work_ctr) {
+    const int lo = phase == DRAW_FIRST ? 0 : min(PHASE0, max_iters), hi = min(st->n_sub, st->niters);
+    if (st->mode == 2 && !st->done && hi > lo) {
+        const int nb = (hi - lo + HQ_HYPS - 1) / HQ_HYPS;
+        const unsigned at = atomicAdd(work_ctr, (unsigned)nb);
+        for (int i = 0; i < nb; i++) work[at + i] = make_int2(b, lo + i * HQ_HYPS);
     }
 }
 
-#ifdef MIS_TAIL_PROF
-__device__ unsigned long long g_hyp_prof[8];    // [6], [7]: summed / longest replay of a second phase (scan_tail_kernel)
+__global__ __launch_bounds__(DRAW_TB) void draw_kernel(const HomoCall* calls, RansacState* states, int* sub_idx, int* draw_idx, const unsigned* U,
+                                                  unsigned long long state_T, int max_iters, DrawPhase phase, int k_hi_arg, int2* work, unsigned* work_ctr,
+                                                  double confidence) {
+#if MIS_CHAIN_PRIO
+    __builtin_amdgcn_s_setprio(MIS_CHAIN_PRIO);      // a latency-bound chain beside the composition's bandwidth-bound kernels: its few waves issue first
 #endif
+    __shared__ DrawShared sh;
+    const int b = blockIdx.x, t = threadIdx.x;
+    DrawProblem p;
+    p.c = calls[b]; p.st = states + b; p.phase = phase;
+    // every return from here to the chunk loop leaves the work list alone: mode 0 / 1, a problem that is done or whose drawing
+    // failed in the first phase (n_sub < PHASE0 then), a problem outside the speculative launch's class
+    if (!draw_enter(sh, p.c, p.st, phase, max_iters, k_hi_arg, confidence, &p.k_hi)) return;
+    DrawCtx d;
+    d.U = U; d.cur_state = state_T; d.cur_pos = RNG_TABLE;
+    p.psrc = p.c.src; p.pdst = p.c.dst;
+    if (p.c.n <= DRAW_PTS) {
+        for (int i = t; i < p.c.n; i += DRAW_TB) { sh.pts[i] = reinterpret_cast<const float2*>(p.c.src)[i]; sh.pts[DRAW_PTS + i] = reinterpret_cast<const float2*>(p.c.dst)[i]; }
+        p.psrc = reinterpret_cast<const float*>(sh.pts); p.pdst = reinterpret_cast<const float*>(sh.pts + DRAW_PTS);
+        __syncthreads();
+    }
+    p.didx = draw_idx + (size_t)b * DRAW_CHUNK * 4; p.sidx = sub_idx + (size_t)b * max_iters * 4;
+    if (phase == DRAW_FIRST && p.c.n <= 10 && !any_feasible_subset(p.psrc, p.pdst, p.c.n)) {
+        if (t == 0) { p.st->draw_fail = 1; p.st->n_sub = 0; p.st->draw_k = 0; }      // (n_sub = 0: nothing to list either)
+        return;
+    }
+    DrawProf prof;
+    int spec_chunks = 0;
+    while (sh.more) {
+        if (phase == DRAW_SPEC && spec_chunks++ == DRAW_SPEC_CHUNKS) {
+            // out of budget in the middle of a run of attempts: the state behind the last accepted subset, where a phase boundary
+            // stands too (no failed attempt counted yet), is what the second phase's launch continues from
+            if (t == 0) draw_ends(p, sh.accpos, sh.k, 0);
+            break;
+        }
+        const long long base = sh.pos;
+        simulate_attempts(sh, d, U, base, p.c.n);
+        if (link_attempts(sh, prof)) doubling_chunk(sh, d, p, base, prof);
+        else serial_chunk(sh, d, p, base);
+    }
+    prof.end(phase);
+    // a speculative launch lists nothing: its subsets are listed by the second phase's launch, which knows how many of them count
+    if (t == 0 && phase != DRAW_SPEC) list_hypotheses(p.st, b, phase, max_iters, work, work_ctr);
+}
+
 // ---------------------------------------------------------------- hyp_quad_kernel --------------
 // The 4-point solves (normalised DLT + 9 x 9 Jacobi of every hypothesis) with FOUR lanes per hypothesis (a DPP quad).  One thread
 // per solve (rounds 1-2's hyp_kernel, removed in round 4) ran ~1300 instructions per rotation on a wave that is alone on its SIMD (126 doubles of LDS per solve allow two waves per compute
@@ -905,29 +990,6 @@ __global__ __launch_bounds__(256) void hyp_count_kernel(const HomoCall* calls, c
 }
 
 // ---------------------------------------------------------------- scan_tail_kernel -------------
-#ifdef MIS_TAIL_PROF
-__device__ unsigned long long g_jac_prof[8];    // shader cycles: pivot search, math, rotation, index update (summed over rotations)
-#ifdef MIS_JAC_PROF     // per-rotation section timers: they serialise the rotation (s_memtime waits for the LDS queue), use the coarse ones for totals
-#define JP_T(v) const unsigned long long v = __builtin_readcyclecounter()
-#define JP_ADD(i, a, b) do { if (threadIdx.x == 0) atomicAdd(&g_jac_prof[i], (b) - (a)); } while (0)
-#else
-#define JP_T(v)
-#define JP_ADD(i, a, b)
-#endif
-__device__ unsigned long long g_tail_log[6 * 1024];
-__device__ unsigned g_tail_log_n;
-__device__ unsigned long long g_tail_prof[12];  // [8..11], part 4 launches: first entry (wall clock) + 1, last exit, longest workgroup, workgroups with work
-//   // jacobi ticks, rotations, normal_eq ticks, LM iterations, dlt ticks, tail ticks, tails, max tail ticks
-#define PROF_T0(v) unsigned long long v = wall_clock64()
-#define PROF_ADD(i, v) do { if (threadIdx.x == 0) atomicAdd(&g_tail_prof[i], wall_clock64() - (v)); } while (0)
-#define PROF_INC(i, n) do { if (threadIdx.x == 0) atomicAdd(&g_tail_prof[i], (unsigned long long)(n)); } while (0)
-#else
-#define PROF_T0(v)
-#define PROF_ADD(i, v)
-#define PROF_INC(i, n)
-#define JP_T(v)
-#define JP_ADD(i, a, b)
-#endif
 #ifndef MIS_PS_PTS
 #define MIS_PS_PTS 32
 #endif
@@ -948,9 +1010,9 @@ struct TailShared {
     double chunk[TB * 10];  // per-point records of the current 256-point chunk of a sequential sum
     int staged;             // the launch carries ordered_sums' term stages (PS_PTS points, double-buffered) in its dynamic LDS (none in the
                             // launches that only replay or mask: 23 KB workgroups find a compute unit beside the composition's kernels, larger ones wait)
-#ifdef MIS_TAIL_PROF
-    int prof_rot, prof_lm;  // this tail's rotations / LM iterations (g_tail_log)
-#endif
+    int done_now;           // the replay ended this problem's loop in this launch
+    int base, wcnt[TB / 64];  // inliers compacted so far, and those among each wave's 64 points of the current round
+    PROF_ONLY(int prof_rot, prof_lm;)  // this tail's rotations / LM iterations (g_tail_log)
 };
 // The DLT (two passes for the normalisation, one for L^T L) and every normal-equations pass of the LM refinement (1 + up to 20)
 // walk the same inlier set 256 points at a time, thread t taking point base + t.  From global memory each chunk would start with an
@@ -1081,9 +1143,7 @@ __device__ __forceinline__ void jacobi_eigen_coop(TailShared& S) {
                 jacobi_rotation<true>(p, y, &c, &sn, &tt);
             else
                 jacobi_rotation<false>(p, y, &c, &sn, &tt);
-#ifdef MIS_JAC_PROF
-            asm volatile("" :: "v"(c), "v"(sn), "v"(tt));
-#endif
+            JP_KEEP("v"(c), "v"(sn), "v"(tt));
             JP_T(j2);
             // everything below is selects, not branches: a divergent region costs a VALU -> SALU -> exec round trip each
             const bool uk = q == k, ul = q == l;
@@ -1132,10 +1192,7 @@ __device__ __forceinline__ void jacobi_eigen_coop(TailShared& S) {
             JP_T(j4);
             JP_ADD(1, j1, j2); JP_ADD(2, j2, j3); JP_ADD(3, j3, j4);
         }
-        PROF_INC(1, iters);
-#ifdef MIS_TAIL_PROF
-        if (t == 0) S.prof_rot += iters;
-#endif
+        PROF_ROTATIONS(S, iters);
         JP_T(j_sort);
         if (t < n) W[t] = Wt;
         wave_sync();
@@ -1152,9 +1209,7 @@ __device__ __forceinline__ void jacobi_eigen_coop(TailShared& S) {
         }
         JP_T(j_end);
         JP_ADD(4, j_sort, j_end);
-#ifdef MIS_JAC_PROF
-        if (t == 0) atomicAdd(&g_jac_prof[5], 1ull);
-#endif
+        JP_ADD(5, 0ull, 1ull);
     }
     __syncthreads();
     PROF_ADD(0, pj);
@@ -1236,13 +1291,6 @@ template <int ADDS, int W, int A> struct PsEmit {
 };
 template <int ADDS, int W> struct PsEmit<ADDS, W, 45> { static __device__ __forceinline__ void put(const double (&)[10], double*) {} };
 
-#if defined(MIS_TAIL_PROF) && defined(MIS_PS_PROF)
-#define PS_T(v) const unsigned long long v = __builtin_readcyclecounter()
-#define PS_ADD(i, who, a, b) do { if (threadIdx.x == (who)) atomicAdd(&g_jac_prof[i], (b) - (a)); } while (0)
-#else
-#define PS_T(v)
-#define PS_ADD(i, who, a, b)
-#endif
 // The sums of one chunk: cnt <= TB records in S.chunk, written by all threads, not yet fenced.  `all`: every accumulator; otherwise only
 // the 45th (|r|^2 of an LM trial step).  kind / off: this lane's accumulator (lane t < 45 of wave 0; ps_kind / ps_off of t), ent:
 // its packed operand indices for the plain loop.  Barriers wait for LDS only: the caller's load of the next chunk's point is in flight.
@@ -1285,18 +1333,14 @@ __device__ __forceinline__ void ordered_sums(TailShared& S, int cnt, bool all, i
         else PsEmit<ADDS, 2, 0>::put(r, out);
     };
     PS_T(ps0);
-#if defined(MIS_TAIL_PROF) && defined(MIS_PS_PROF)
-    unsigned long long ps_acc = 0, ps_prod = 0, ps_bar = 0;
-#endif
+    PS_SUM(ps_acc); PS_SUM(ps_prod); PS_SUM(ps_bar);
     produce(0);
     lds_barrier();
     for (int sb = 0; sb < nsub; sb++) {
         PS_T(ps1);
         if (sb + 1 < nsub) produce(sb + 1);
         PS_T(ps2);
-#if defined(MIS_TAIL_PROF) && defined(MIS_PS_PROF)
-        ps_prod += ps2 - ps1;
-#endif
+        PS_ACC(ps_prod, ps1, ps2);
         if (accumulate) {
             // a lane's second term: the slot behind its first (two-term accumulators) or the point's zero (x + 0 = x: no select on the chain)
             const double* P = tail_dyn + (sb & 1) * PS_STAGE;
@@ -1317,25 +1361,19 @@ __device__ __forceinline__ void ordered_sums(TailShared& S, int cnt, bool all, i
                 }
             }
         }
-#if defined(MIS_TAIL_PROF) && defined(MIS_PS_PROF)
-        asm volatile("" :: "v"(acc));
-#endif
+        PS_KEEP(acc);
         PS_T(ps3);
         lds_barrier();
-#if defined(MIS_TAIL_PROF) && defined(MIS_PS_PROF)
-        ps_acc += ps3 - ps2;
-        ps_bar += __builtin_readcyclecounter() - ps3;
-#endif
+        PS_T(ps3b);
+        PS_ACC(ps_acc, ps2, ps3); PS_ACC(ps_bar, ps3, ps3b);
     }
     PS_T(ps4);
-#if defined(MIS_TAIL_PROF) && defined(MIS_PS_PROF)
     PS_ADD(0, 44, 0ull, ps_acc);
     PS_ADD(1, 64, 0ull, ps_prod);
     PS_ADD(2, 44, ps0, ps4);
     PS_ADD(3, 44, 0ull, (unsigned long long)nsub);
     PS_ADD(4, 44, 0ull, ps_bar);
     PS_ADD(5, 64, 0ull, ps_bar);
-#endif
 }
 // a record's entries are all finite (their sum of magnitudes is: an overflowing sum only sends the chunk to the plain loop)
 __device__ __forceinline__ bool ps_record_bad(const double* r) {
@@ -1501,9 +1539,7 @@ __device__ void lm_refine_coop(TailShared& S, const float* s1, const float* d1, 
         }
         __syncthreads();
         PROF_ADD(2, pn);
-#ifdef MIS_TAIL_PROF
-        if (t == 0) { atomicAdd(&g_jac_prof[6], (unsigned long long)np); atomicAdd(&g_jac_prof[7], 1ull); }
-#endif
+        PROF_LM_PASS(np);
     };
     if (t < 8) x[t] = S.best[t];
     __syncthreads();
@@ -1593,10 +1629,7 @@ __device__ void lm_refine_coop(TailShared& S, const float* s1, const float* d1, 
         __syncthreads();
         if (sc[3] != 0.) normal_eq(x, true);
         iter++;
-        PROF_INC(3, 1);
-#ifdef MIS_TAIL_PROF
-        if (t == 0) S.prof_lm++;
-#endif
+        PROF_LM_ITERATION(S);
         double dmax = 0;
         for (int i = 0; i < 8; i++) { double a = fabs(d[i]); if (a > dmax) dmax = a; }
         bool proceed = iter < 10 && dmax >= (double)FLT_EPSILON && sc[2] >= (double)FLT_EPSILON;
@@ -1607,182 +1640,180 @@ __device__ void lm_refine_coop(TailShared& S, const float* s1, const float* d1, 
     __syncthreads();
 }
 
-// part 0: replay + tail (the finished problems' mask, DLT on the inliers, LM refinement) in one launch;
-// part 1: replay only -- a problem that ends here is marked tail_pending; parts 3 / 4: the tail of the pending problems whose
-// fin equals `want`, mask + inlier compaction / DLT + LM.  The split lets the tails of the problems that end in RANSAC phase 0
-// (latency bound, ~2 ms) run on another stream while phase 1 of the others -- which only needs the replay's verdict -- goes on.
 #ifndef MIS_TAIL_WAVES
 #define MIS_TAIL_WAVES 3      // <= 168 registers: a 200-register workgroup waits longer for room beside the composition's grids (6.65 vs 6.9 ms per step; 4 waves = 128 registers spill into the Jacobi loop)
 #endif
-__global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(MIS_TAIL_WAVES, 8))) void scan_tail_kernel(const HomoCall* calls, RansacState* states, const double* Hc, const int* valid, const int* good,
-                                                       float* scr_all, double* rec_all, HomoResult* results, int lo, int hi, int max_iters,
-                                                       double confidence, float thr, int* fin, int part, int want, int staged, unsigned* work_ctr) {
-    // a replay launch runs behind the phase's last reader of the hypothesis work list: empty it for the next phase or call
-    if (work_ctr && blockIdx.x == 0 && threadIdx.x < WL_CTRS) work_ctr[threadIdx.x] = 0;
-#if MIS_CHAIN_PRIO
-    __builtin_amdgcn_s_setprio(MIS_CHAIN_PRIO);      // a latency-bound chain beside the composition's bandwidth-bound kernels: its few waves issue first
-#endif
-#ifdef MIS_TAIL_PROF
-    const unsigned long long wg_in = wall_clock64();
-    if (part == 4 && want == 0 && threadIdx.x == 0) atomicMin(&g_tail_prof[8], wg_in);
-#endif
-    __shared__ TailShared S;
-    __shared__ int s_done_now;
-    if (threadIdx.x == 0) { S.staged = staged; S.bad = 0; }
-    if (staged)
-        for (int i = threadIdx.x; i < 2 * PS_PTS; i += TB) tail_dyn[i * PS_PITCH + PS_TERMS] = 0.;      // (stage 1 follows stage 0 at PS_PTS * PS_PITCH)
-    __syncthreads();
-    __shared__ int wcnt[TB / 64];
-    __shared__ int s_base;
-    const int b = blockIdx.x, t = threadIdx.x;
-    const HomoCall c = calls[b];
-    RansacState* st = states + b;
-    HomoResult* res = results + b;
-    const int n = c.n;
-    float* s1 = scr_all + 4 * c.pt_off;
-    float* d1 = s1 + 2 * (size_t)(n > 0 ? n : 0);
-    double* rec = rec_all + 10 * c.pt_off;
-    if (part >= 3) {
-        // the tail of a pending problem: mask + compaction (flag 1 -> 2), then DLT + LM (2 -> 0)
-        if (st->tail_pending != (part == 4 ? 2 : 1) || fin[b] != want) return;   // uniform
-        __syncthreads();                                    // every thread has read the flag before it changes
-    } else {
-    if (st->done) return;  // finished in an earlier phase (uniform)
-    const int mode = st->mode;
-    if (t == 0) s_done_now = 0;
-    __syncthreads();
+// one problem of a scan_tail_kernel launch, as its steps see it
+struct TailProblem {
+    int b, n; HomoCall c; RansacState* st; HomoResult* res;
+    float* s1; float* d1; double* rec;      // s1, d1: the compacted inliers, src and dst
+};
+
+// A problem without a RANSAC loop ends in the replay launch of the first phase: mode 0 has no model, mode 1 (exactly four
+// correspondences) is runKernel directly, mask all ones, no refinement
+__device__ __forceinline__ void finish_without_loop(TailShared& S, const TailProblem& p, const int mode, const int lo, int* fin) {
+    const int t = threadIdx.x, n = p.n;
+    const HomoCall& c = p.c;
     if (mode == 0) {
         for (int i = t; c.mask && c.active && i < n; i += TB) c.mask[i] = 0;
-        if (t == 0) { res->ok = 0; res->iters = 0; res->ninl = 0; st->done = 1; fin[b] = lo == 0 ? 0 : 1; }
+        if (t == 0) { p.res->ok = 0; p.res->iters = 0; p.res->ninl = 0; p.st->done = 1; fin[p.b] = lo == 0 ? 0 : 1; }
         return;
     }
-    if (mode == 1) {
-        // exactly four correspondences: runKernel directly, mask all ones, no refinement
-        if (t == 0) for (int i = 0; i < 9; i++) S.best[i] = 0;
+    if (t == 0) for (int i = 0; i < 9; i++) S.best[i] = 0;
+    __syncthreads();
+    dlt_coop(S, c.src, c.dst, 4, t < 4 ? tail_load_point(c.src, c.dst, t) : make_float4(0.f, 0.f, 0.f, 0.f), p.rec);
+    const int ok = S.go;
+    for (int i = t; c.mask && i < n; i += TB) c.mask[i] = ok ? 1 : 0;
+    if (t == 0) { p.res->ok = ok; p.res->iters = 0; p.res->ninl = ok ? 4 : 0; if (ok) for (int i = 0; i < 9; i++) p.res->H[i] = S.best[i]; p.st->done = 1; fin[p.b] = lo == 0 ? 0 : 1; }
+}
+
+// Replay of RANSACPointSetRegistrator::run over hypotheses [lo, hi); S.done_now (zero on entry) is set when the loop ends here.
+// The loop only changes state at a hypothesis that beats every earlier one (a new maximum of `good`), so the workgroup stages
+// good[] (-1 for a degenerate sample) in LDS with the maximum of every run of `seg` entries beside it, and the replaying thread
+// steps over the runs that hold no new maximum.  A serial walk over global memory paid a load latency per hypothesis: 0.43 ms
+// for the 1872 hypotheses of phase 1, on the matcher's critical path.
+__device__ __forceinline__ void replay_hypotheses(TailShared& S, const TailProblem& p, const int* valid, const int* good, const int lo, const int hi, const int max_iters,
+                                                  const double confidence, int* fin) {
+    const int t = threadIdx.x, b = p.b, n = p.n;
+    RansacState* st = p.st;
+    PROF_T0(rp0);
+    // (niters never grows: nothing at or beyond the current limit is visited -- or has been computed)
+    const int nsub = st->n_sub, kmax = min(hi, nsub), cnt = max(min(kmax - lo, st->niters - st->iter), 0);
+    int* gl = reinterpret_cast<int*>(S.chunk);            // cnt entries (<= 4096), then the run maxima at + 4096
+    int* segmax = gl + 4096;
+    const bool staged = cnt <= 4096;
+    const int seg = (cnt + TB - 1) / TB > 0 ? (cnt + TB - 1) / TB : 1;
+    if (staged) {
+        for (int i = t; i < cnt; i += TB) gl[i] = valid[(size_t)b * max_iters + lo + i] ? good[(size_t)b * max_iters + lo + i] : -1;
         __syncthreads();
-        dlt_coop(S, c.src, c.dst, 4, t < 4 ? tail_load_point(c.src, c.dst, t) : make_float4(0.f, 0.f, 0.f, 0.f), rec);
-        const int ok = S.go;
-        for (int i = t; c.mask && i < n; i += TB) c.mask[i] = ok ? 1 : 0;
-        if (t == 0) { res->ok = ok; res->iters = 0; res->ninl = ok ? 4 : 0; if (ok) for (int i = 0; i < 9; i++) res->H[i] = S.best[i]; st->done = 1; fin[b] = lo == 0 ? 0 : 1; }
-        return;
+        int mx = -1;
+        for (int i = t * seg; i < min((t + 1) * seg, cnt); i++) mx = max(mx, gl[i]);
+        segmax[t] = mx;
+        __syncthreads();
     }
-    // ---- replay of RANSACPointSetRegistrator::run over hypotheses [lo, hi) ----
-    // The loop only changes state at a hypothesis that beats every earlier one (a new maximum of `good`), so the workgroup stages
-    // good[] (-1 for a degenerate sample) in LDS with the maximum of every run of `seg` entries beside it, and the replaying thread
-    // steps over the runs that hold no new maximum.  A serial walk over global memory paid a load latency per hypothesis: 0.43 ms
-    // for the 1872 hypotheses of phase 1, on the matcher's critical path.
-    {
-#ifdef MIS_TAIL_PROF
-        const unsigned long long rp0 = wall_clock64();
-#endif
-        // (niters never grows: nothing at or beyond the current limit is visited -- or has been computed)
-        const int nsub = st->n_sub, kmax = min(hi, nsub), cnt = max(min(kmax - lo, st->niters - st->iter), 0);
-        int* gl = reinterpret_cast<int*>(S.chunk);            // cnt entries (<= 4096), then the run maxima at + 4096
-        int* segmax = gl + 4096;
-        const bool staged = cnt <= 4096;
-        const int seg = (cnt + TB - 1) / TB > 0 ? (cnt + TB - 1) / TB : 1;
-        if (staged) {
-            for (int i = t; i < cnt; i += TB) gl[i] = valid[(size_t)b * max_iters + lo + i] ? good[(size_t)b * max_iters + lo + i] : -1;
-            __syncthreads();
-            int mx = -1;
-            for (int i = t * seg; i < min((t + 1) * seg, cnt); i++) mx = max(mx, gl[i]);
-            segmax[t] = mx;
-            __syncthreads();
-        }
-        if (t == 0) {
-            int iter = st->iter, niters = st->niters, max_good = st->max_good, best_k = st->best_k;
-            int k = lo;
-            while (k < kmax && iter < niters) {
-                const int off = k - lo;
-                if (staged && off % seg == 0 && segmax[off / seg] <= (max_good > 3 ? max_good : 3)) {
-                    // nothing in this run changes the state: the loop walks to its end, or to the iteration limit
-                    const int adv = min(min(seg, kmax - k), niters - iter);
-                    k += adv; iter += adv;
-                    continue;
-                }
-                iter++;
-                const int g = staged ? gl[off] : (valid[(size_t)b * max_iters + k] ? good[(size_t)b * max_iters + k] : -1);
-                if (g >= 0 && g > (max_good > 3 ? max_good : 3)) {
-                    best_k = k; max_good = g;
-                    niters = ransac_update_num_iters(confidence, (double)(n - g) / n, niters);
-                }
-                k++;
-            }
-            st->iter = iter; st->niters = niters; st->max_good = max_good; st->best_k = best_k;
-            // the loop ends when iter reaches niters, when getSubset failed (subsets exhausted) or at maxIters
-            if (iter >= niters || (k >= nsub && st->draw_fail) || hi >= max_iters) { s_done_now = 1; st->done = 1; fin[b] = lo == 0 ? 0 : 1; }
-#ifdef MIS_TAIL_PROF
-            if (lo > 0) { const unsigned long long d = wall_clock64() - rp0; atomicAdd(&g_hyp_prof[6], d); atomicMax(&g_hyp_prof[7], d); }
-#endif
-        }
-    }
-    __syncthreads();
-    if (!s_done_now) return;
-    if (part == 1) {
-        if (t == 0) st->tail_pending = 1;
-        return;
-    }
-    }   // part < 3
-    const int result = st->max_good > 0;
-    if (part != 4 && t == 0) { res->iters = st->iter; res->ok = result; res->ninl = 0; }
-    if (!result) {
-        for (int i = t; c.mask && i < n; i += TB) c.mask[i] = 0;
-        if (t == 0) st->tail_pending = 0;
-        return;
-    }
-    // best model -> mask, ordered compaction of the inliers (compressElems)
     if (t == 0) {
-        const double* hb = Hc + ((size_t)b * max_iters + st->best_k) * 9;
-        for (int i = 0; i < 9; i++) { S.best[i] = hb[i]; S.Hf[i] = (float)hb[i]; }
-        s_base = part == 4 ? res->ninl : 0;
+        int iter = st->iter, niters = st->niters, max_good = st->max_good, best_k = st->best_k;
+        int k = lo;
+        while (k < kmax && iter < niters) {
+            const int off = k - lo;
+            if (staged && off % seg == 0 && segmax[off / seg] <= (max_good > 3 ? max_good : 3)) {
+                // nothing in this run changes the state: the loop walks to its end, or to the iteration limit
+                const int adv = min(min(seg, kmax - k), niters - iter);
+                k += adv; iter += adv;
+                continue;
+            }
+            iter++;
+            const int g = staged ? gl[off] : (valid[(size_t)b * max_iters + k] ? good[(size_t)b * max_iters + k] : -1);
+            if (g >= 0 && g > (max_good > 3 ? max_good : 3)) {
+                best_k = k; max_good = g;
+                niters = ransac_update_num_iters(confidence, (double)(n - g) / n, niters);
+            }
+            k++;
+        }
+        st->iter = iter; st->niters = niters; st->max_good = max_good; st->best_k = best_k;
+        // the loop ends when iter reaches niters, when getSubset failed (subsets exhausted) or at maxIters
+        if (iter >= niters || (k >= nsub && st->draw_fail) || hi >= max_iters) { S.done_now = 1; st->done = 1; fin[b] = lo == 0 ? 0 : 1; }
+        PROF_REPLAY(lo, rp0);
     }
-    __syncthreads();
-    if (part != 4)
+}
+
+// best model (S.Hf) -> mask, ordered compaction of the inliers (compressElems) into s1 / d1; their number ends in S.base
+__device__ __forceinline__ void mask_and_compact(TailShared& S, const TailProblem& p, const float thr) {
+    const int t = threadIdx.x, n = p.n;
+    const HomoCall& c = p.c;
     for (int i0 = 0; i0 < n; i0 += TB) {
         int i = i0 + t, f = 0;
         if (i < n) f = is_inlier(S.Hf, c.src[2 * i], c.src[2 * i + 1], c.dst[2 * i], c.dst[2 * i + 1], thr);
         if (c.mask && i < n) c.mask[i] = (uint8_t)f;
         unsigned long long bal = __ballot(f);
         int within = __popcll(bal & ((1ull << (t & 63)) - 1ull));
-        if ((t & 63) == 0) wcnt[t >> 6] = __popcll(bal);
+        if ((t & 63) == 0) S.wcnt[t >> 6] = __popcll(bal);
         __syncthreads();
-        int off = s_base;
-        for (int k = 0; k < (t >> 6); k++) off += wcnt[k];
+        int off = S.base;
+        for (int k = 0; k < (t >> 6); k++) off += S.wcnt[k];
         if (f) {
-            s1[2 * (off + within)] = c.src[2 * i]; s1[2 * (off + within) + 1] = c.src[2 * i + 1];
-            d1[2 * (off + within)] = c.dst[2 * i]; d1[2 * (off + within) + 1] = c.dst[2 * i + 1];
+            p.s1[2 * (off + within)] = c.src[2 * i]; p.s1[2 * (off + within) + 1] = c.src[2 * i + 1];
+            p.d1[2 * (off + within)] = c.dst[2 * i]; p.d1[2 * (off + within) + 1] = c.dst[2 * i + 1];
         }
         __syncthreads();
-        if (t == 0) { int s = 0; for (int k = 0; k < TB / 64; k++) s += wcnt[k]; s_base += s; }
+        if (t == 0) { int s = 0; for (int k = 0; k < TB / 64; k++) s += S.wcnt[k]; S.base += s; }
         __syncthreads();
     }
-    const int np = s_base;
-    if (part == 3) {   // the inlier set is final here; DLT + LM on it (part 4) only changes H
-        if (t == 0) { res->ninl = np; for (int i = 0; i < 9; i++) res->H[i] = S.best[i]; st->tail_pending = 2; }
+}
+
+// runKernel on all np inliers (keeps the RANSAC model if degenerate), then the LM refinement: S.best
+__device__ __forceinline__ void refine_on_inliers(TailShared& S, const TailProblem& p, const int np, const TailKind kind, const int want) {
+    const int t = threadIdx.x;
+    PROF_TAIL_BEGIN(S, pt);
+    if (np > 0) {
+        // this thread's point of every pass's first chunk: loaded once (the compaction wrote it: its stores are fenced by the loop's barriers)
+        const float4 pt0 = t < np ? tail_load_point(p.s1, p.d1, t) : make_float4(0.f, 0.f, 0.f, 0.f);
+        dlt_coop(S, p.s1, p.d1, np, pt0, p.rec);
+        PROF_ADD(4, pt);
+        lm_refine_coop(S, p.s1, p.d1, np, pt0, p.rec);
+    }
+    PROF_TAIL_END(S, np, kind, want, pt);
+}
+
+__global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(MIS_TAIL_WAVES, 8))) void scan_tail_kernel(const HomoCall* calls, RansacState* states, const double* Hc, const int* valid, const int* good,
+                                                       float* scr_all, double* rec_all, HomoResult* results, int lo, int hi, int max_iters,
+                                                       double confidence, float thr, int* fin, TailKind kind, int want, int staged, unsigned* work_ctr) {
+    // a replay launch runs behind the phase's last reader of the hypothesis work list: empty it for the next phase or call
+    if (work_ctr && blockIdx.x == 0 && threadIdx.x < WL_CTRS) work_ctr[threadIdx.x] = 0;
+#if MIS_CHAIN_PRIO
+    __builtin_amdgcn_s_setprio(MIS_CHAIN_PRIO);      // a latency-bound chain beside the composition's bandwidth-bound kernels: its few waves issue first
+#endif
+    PROF_FIRST_ENTRY(kind, want, wg_in);
+    __shared__ TailShared S;
+    if (threadIdx.x == 0) { S.staged = staged; S.bad = 0; }
+    if (staged)
+        for (int i = threadIdx.x; i < 2 * PS_PTS; i += TB) tail_dyn[i * PS_PITCH + PS_TERMS] = 0.;      // (stage 1 follows stage 0 at PS_PTS * PS_PITCH)
+    __syncthreads();
+    const int b = blockIdx.x, t = threadIdx.x;
+    TailProblem p;
+    p.b = b; p.c = calls[b]; p.n = p.c.n; p.st = states + b; p.res = results + b;
+    p.s1 = scr_all + 4 * p.c.pt_off; p.d1 = p.s1 + 2 * (size_t)(p.n > 0 ? p.n : 0); p.rec = rec_all + 10 * p.c.pt_off;
+    RansacState* const st = p.st;
+    const bool refines = kind == TAIL_REFINE_ONLY;
+    if (kind == TAIL_MASK_ONLY || refines) {
+        // the tail of a pending problem: mask + compaction (flag 1 -> 2), then DLT + LM (2 -> 0)
+        if (st->tail_pending != (refines ? 2 : 1) || fin[b] != want) return;   // uniform
+        __syncthreads();                                    // every thread has read the flag before it changes
+    } else {
+        if (st->done) return;  // finished in an earlier phase (uniform)
+        const int mode = st->mode;
+        if (t == 0) S.done_now = 0;
+        __syncthreads();
+        if (mode != 2) { finish_without_loop(S, p, mode, lo, fin); return; }
+        replay_hypotheses(S, p, valid, good, lo, hi, max_iters, confidence, fin);
+        __syncthreads();
+        if (!S.done_now) return;
+        if (kind == TAIL_REPLAY_ONLY) { if (t == 0) st->tail_pending = 1; return; }
+    }
+    // the loop has ended: its verdict ...
+    const int result = st->max_good > 0;
+    if (!refines && t == 0) { p.res->iters = st->iter; p.res->ok = result; p.res->ninl = 0; }
+    if (!result) {
+        for (int i = t; p.c.mask && i < p.n; i += TB) p.c.mask[i] = 0;
+        if (t == 0) st->tail_pending = 0;
         return;
     }
-    PROF_T0(pt);
-#ifdef MIS_TAIL_PROF
-    if (t == 0) { S.prof_rot = 0; S.prof_lm = 0; }
-#endif
-    if (np > 0) {
-        // this thread's point of every pass's first chunk: loaded once (the compaction above wrote it: its stores are fenced by the loop's barriers)
-        const float4 pt0 = t < np ? tail_load_point(s1, d1, t) : make_float4(0.f, 0.f, 0.f, 0.f);
-        dlt_coop(S, s1, d1, np, pt0, rec);   // runKernel on all inliers (keeps the RANSAC model if degenerate)
-        PROF_ADD(4, pt);
-        lm_refine_coop(S, s1, d1, np, pt0, rec);
+    // ... and the best model's tail
+    if (t == 0) {
+        const double* hb = Hc + ((size_t)b * max_iters + st->best_k) * 9;
+        for (int i = 0; i < 9; i++) { S.best[i] = hb[i]; S.Hf[i] = (float)hb[i]; }
+        S.base = refines ? p.res->ninl : 0;
     }
-    PROF_ADD(5, pt);
-    PROF_INC(6, 1);
-#ifdef MIS_TAIL_PROF
-    if (t == 0) atomicMax(&g_tail_prof[7], wall_clock64() - pt);
-    if (t == 0) {      // one line per tail: points, LM iterations, rotations, ticks, launch kind, entry tick
-        const unsigned k = atomicAdd(&g_tail_log_n, 1u);
-        if (k < 1024) { unsigned long long* e = g_tail_log + 6 * k; e[0] = np; e[1] = S.prof_lm; e[2] = S.prof_rot; e[3] = wall_clock64() - pt; e[4] = part * 10 + want; e[5] = pt; }
+    __syncthreads();
+    if (!refines) mask_and_compact(S, p, thr);
+    const int np = S.base;
+    if (kind == TAIL_MASK_ONLY) {   // the inlier set is final here; DLT + LM on it (TAIL_REFINE_ONLY) only changes H
+        if (t == 0) { p.res->ninl = np; for (int i = 0; i < 9; i++) p.res->H[i] = S.best[i]; st->tail_pending = 2; }
+        return;
     }
-    if (part == 4 && want == 0 && t == 0) { const unsigned long long o = wall_clock64(); atomicMax(&g_tail_prof[9], o); atomicMax(&g_tail_prof[10], o - wg_in); atomicAdd(&g_tail_prof[11], 1ull); }
-#endif
-    if (t == 0) { for (int i = 0; i < 9; i++) res->H[i] = S.best[i]; res->ninl = np; if (part == 4) st->tail_pending = 0; }
+    refine_on_inliers(S, p, np, kind, want);
+    PROF_LAST_EXIT(kind, want, wg_in);
+    if (t == 0) { for (int i = 0; i < 9; i++) p.res->H[i] = S.best[i]; p.res->ninl = np; if (refines) st->tail_pending = 0; }
 }
 
 // ---------------------------------------------------------------- host side --------------------
@@ -1822,7 +1853,7 @@ int homo_batch_reserve(MisContext* ctx, HomoBatch* b, int count, long long point
     size_t o_sub = carve(sizeof(int) * 4 * (size_t)count * max_iters), o_hc = carve(sizeof(double) * 9 * (size_t)count * max_iters);
     size_t o_valid = carve(sizeof(int) * (size_t)count * max_iters), o_good = carve(sizeof(int) * (size_t)count * max_iters);
     size_t o_scr = carve(sizeof(float) * 4 * (size_t)points), o_rec = carve(sizeof(double) * 10 * (size_t)points);
-    size_t o_dn = carve(256), o_di = carve(sizeof(int) * 4 * (size_t)count * DRAW_CHUNK), o_fin = carve(sizeof(int) * (size_t)count);
+    size_t o_di = carve(sizeof(int) * 4 * (size_t)count * DRAW_CHUNK), o_fin = carve(sizeof(int) * (size_t)count);
     const size_t o_work = carve(sizeof(int2) * (size_t)count * ((max_iters + HQ_HYPS - 1) / HQ_HYPS));   // one phase's blocks at most
     if (off > b->bytes) {
         if (b->mem) { MIS_HIP(ctx, hipStreamSynchronize(ctx->stream)); MIS_HIP(ctx, hipFree(b->mem)); b->mem = nullptr; b->bytes = 0; }
@@ -1835,19 +1866,26 @@ int homo_batch_reserve(MisContext* ctx, HomoBatch* b, int count, long long point
     uint8_t* m = (uint8_t*)b->mem;
     b->calls = (HomoCall*)(m + o_calls); b->results = (HomoResult*)(m + o_res); b->state = m + o_state;
     b->sub_idx = (int*)(m + o_sub); b->Hc = (double*)(m + o_hc); b->valid = (int*)(m + o_valid); b->good = (int*)(m + o_good);
-    b->scr = (float*)(m + o_scr); b->rec = (double*)(m + o_rec); b->draw_next = (unsigned*)(m + o_dn); b->draw_idx = (int*)(m + o_di); b->fin = (int*)(m + o_fin);
+    b->scr = (float*)(m + o_scr); b->rec = (double*)(m + o_rec); b->draw_idx = (int*)(m + o_di); b->fin = (int*)(m + o_fin);
     b->work = (int2*)(m + o_work); b->work_ctr = (unsigned*)(m + o_wctr);
     b->count = count; b->points = points; b->max_iters = max_iters;
     return MIS_OK;
 }
 
 #ifdef MIS_TAIL_PROF
-extern "C" int mis_debug_tail_prof(unsigned long long* out, int reset) {
+// a counter array to the host (n <= 12 values); reset: back to zero, except that a minimum (index `min_at`) starts from the largest value
+static int prof_read(const void* symbol, int n, unsigned long long* out, int reset, int min_at = -1) {
     hipDeviceSynchronize();
-    hipMemcpyFromSymbol(out, HIP_SYMBOL(g_tail_prof), sizeof(unsigned long long) * 12);
-    if (reset) { unsigned long long z[12] = {0}; z[8] = ~0ull; hipMemcpyToSymbol(HIP_SYMBOL(g_tail_prof), z, sizeof(z)); }
+    hipMemcpyFromSymbol(out, symbol, sizeof(unsigned long long) * n);
+    unsigned long long z[12] = {0};
+    if (min_at >= 0) z[min_at] = ~0ull;
+    if (reset) hipMemcpyToSymbol(symbol, z, sizeof(unsigned long long) * n);
     return 0;
 }
+extern "C" int mis_debug_tail_prof(unsigned long long* out, int reset) { return prof_read(HIP_SYMBOL(g_tail_prof), 12, out, reset, 8); }
+extern "C" int mis_debug_draw_prof(unsigned long long* out, int reset) { return prof_read(HIP_SYMBOL(g_draw_prof), 12, out, reset); }
+extern "C" int mis_debug_hyp_prof(unsigned long long* out, int reset) { return prof_read(HIP_SYMBOL(g_hyp_prof), 8, out, reset); }
+extern "C" int mis_debug_jac_prof(unsigned long long* out, int reset) { return prof_read(HIP_SYMBOL(g_jac_prof), 8, out, reset); }
 extern "C" int mis_debug_tail_log(unsigned long long* out, int cap, int reset) {      // -> entries copied (6 values each)
     unsigned n = 0;
     if (hipMemcpyFromSymbol(&n, HIP_SYMBOL(g_tail_log_n), sizeof(n)) != hipSuccess) return -1;
@@ -1856,24 +1894,6 @@ extern "C" int mis_debug_tail_log(unsigned long long* out, int cap, int reset) {
     if (n && hipMemcpyFromSymbol(out, HIP_SYMBOL(g_tail_log), sizeof(unsigned long long) * 6 * n) != hipSuccess) return -1;
     if (reset) { unsigned z = 0; if (hipMemcpyToSymbol(HIP_SYMBOL(g_tail_log_n), &z, sizeof(z)) != hipSuccess) return -1; }
     return (int)n;
-}
-extern "C" int mis_debug_draw_prof(unsigned long long* out, int reset) {
-    hipDeviceSynchronize();
-    hipMemcpyFromSymbol(out, HIP_SYMBOL(g_draw_prof), sizeof(unsigned long long) * 12);
-    if (reset) { unsigned long long z[12] = {0}; hipMemcpyToSymbol(HIP_SYMBOL(g_draw_prof), z, sizeof(z)); }
-    return 0;
-}
-extern "C" int mis_debug_hyp_prof(unsigned long long* out, int reset) {
-    hipDeviceSynchronize();
-    hipMemcpyFromSymbol(out, HIP_SYMBOL(g_hyp_prof), sizeof(unsigned long long) * 8);
-    if (reset) { unsigned long long z[8] = {0}; hipMemcpyToSymbol(HIP_SYMBOL(g_hyp_prof), z, sizeof(z)); }
-    return 0;
-}
-extern "C" int mis_debug_jac_prof(unsigned long long* out, int reset) {
-    hipDeviceSynchronize();
-    hipMemcpyFromSymbol(out, HIP_SYMBOL(g_jac_prof), sizeof(unsigned long long) * 8);
-    if (reset) { unsigned long long z[8] = {0}; hipMemcpyToSymbol(HIP_SYMBOL(g_jac_prof), z, sizeof(z)); }
-    return 0;
 }
 #endif
 
@@ -1897,71 +1917,101 @@ void homo_batch_release(HomoBatch* b) {
     b->mem = nullptr; b->bytes = 0;
 }
 
-int homo_batch_run(MisContext* ctx, HomoBatch* b, double thresh, int max_iters, double confidence, HomoRun run, hipStream_t stream, const HomoSync* sync) {
-    const HomoSync none;
-    const HomoSync& sy = sync ? *sync : none;
-    MIS_CHECK(ctx, max_iters >= 1 && max_iters <= b->max_iters, MIS_E_INVALID, "max_iters %d outside the reserved range", max_iters);
-    MIS_CHECK(ctx, confidence > 0 && confidence < 1, MIS_E_INVALID, "confidence must be in (0,1)");
-    RngTable rt;
-    int rc = rng_table(ctx, &rt);
-    if (rc != MIS_OK) return rc;
-    if (thresh <= 0) thresh = 3;
-    const float thr = (float)(thresh * thresh);
-    hipStream_t st = stream ? stream : ctx->stream;
-    static bool attr_set[64] = {false};
-    const size_t hq_lds = sizeof(double) * HQ_ELEMS * HQ_STRIDE;
-    if (!attr_set[ctx->device & 63]) {
-        MIS_HIP(ctx, hipFuncSetAttribute((const void*)hyp_quad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hq_lds));
-        attr_set[ctx->device & 63] = true;
+namespace {
+
+// What every entry point below starts with -- the parameters validated, the RNG table, the solves' dynamic LDS allowed, the
+// stream and the hooks -- and the launches of the engine's steps on that batch
+struct Engine {
+    MisContext* ctx; HomoBatch* b; hipStream_t st; RngTable rt; HomoHooks hk;
+    int max_iters, p0; double confidence; float thr;      // the first phase covers hypotheses [0, p0); thr: the squared threshold
+    static constexpr size_t hq_lds = sizeof(double) * HQ_ELEMS * HQ_STRIDE;
+
+    int open(MisContext* ctx_, HomoBatch* b_, const HomoParams& prm, hipStream_t stream, const HomoHooks* hooks) {
+        ctx = ctx_; b = b_; hk = hooks ? *hooks : HomoHooks();
+        MIS_CHECK(ctx, prm.max_iters >= 1 && prm.max_iters <= b->max_iters, MIS_E_INVALID, "max_iters %d outside the reserved range", prm.max_iters);
+        MIS_CHECK(ctx, prm.confidence > 0 && prm.confidence < 1, MIS_E_INVALID, "confidence must be in (0,1)");
+        if (int rc = rng_table(ctx, &rt); rc != MIS_OK) return rc;
+        const double thresh = prm.thresh <= 0 ? 3 : prm.thresh;
+        thr = (float)(thresh * thresh);
+        max_iters = prm.max_iters; p0 = std::min(PHASE0, max_iters); confidence = prm.confidence;
+        st = stream ? stream : ctx->stream;
+        static bool attr_set[64] = {false};
+        if (!attr_set[ctx->device & 63]) {
+            MIS_HIP(ctx, hipFuncSetAttribute((const void*)hyp_quad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hq_lds));
+            attr_set[ctx->device & 63] = true;
+        }
+        return MIS_OK;
     }
-    RansacState* states = (RansacState*)b->state;
-    const int p0 = std::min(PHASE0, max_iters);
-    // the launches that run a DLT / LM refinement (parts 0, 4) carry the term stages of ordered_sums in dynamic LDS; replay-only and mask-only ones do not
-    // (MIS_TAIL_PLAIN=1: none anywhere -- every ordered sum takes round 3's plain loop; the parity tests run both)
-    static const bool plain = getenv("MIS_TAIL_PLAIN") != nullptr && atoi(getenv("MIS_TAIL_PLAIN")) != 0;
-    auto tail_staged = [&](int part) { return (part == 1 || part == 3 || plain) ? 0 : 1; };
-    auto tail_lds = [&](int part) { return tail_staged(part) ? TAIL_DYN_LDS : (size_t)0; };
-    const int replay_part = run == HOMO_BOTH_PHASES ? 0 : 1;      // 1: replay only, the finishers' tails are left pending
+    int close(int rc) const { if (rc == MIS_OK) MIS_HIP(ctx, hipGetLastError()); return rc; }      // the end of an entry point whose enqueues returned rc
+    void draw(DrawPhase phase, hipStream_t s) const {
+        hipLaunchKernelGGL(draw_kernel, dim3(b->count), dim3(DRAW_TB), 0, s, b->calls, (RansacState*)b->state, b->sub_idx, b->draw_idx, rt.U, rt.state_T, max_iters, phase,
+                           phase == DRAW_FIRST ? p0 : max_iters, b->work, b->work_ctr, confidence);
+    }
     // the solves and counts of the work list draw_kernel has just written (the replay launch behind them empties it again)
-    const int ncu = std::max(ctx->num_cu, 1);
-    auto hypotheses = [&]() {
-        hipLaunchKernelGGL(hyp_quad_kernel, dim3(HQ_WG_PER_CU * ncu), dim3(4 * HQ_HYPS), hq_lds, st, b->calls, states, b->sub_idx, b->Hc, b->valid, max_iters,
+    void hypotheses() const {
+        const int ncu = std::max(ctx->num_cu, 1);
+        hipLaunchKernelGGL(hyp_quad_kernel, dim3(HQ_WG_PER_CU * ncu), dim3(4 * HQ_HYPS), hq_lds, st, b->calls, (RansacState*)b->state, b->sub_idx, b->Hc, b->valid, max_iters,
                            (const int2*)b->work, b->work_ctr);
-        hipLaunchKernelGGL(hyp_count_kernel, dim3(HC_WG_PER_CU * ncu), dim3(256), 0, st, b->calls, states, (const double*)b->Hc, (const int*)b->valid, b->good,
+        hipLaunchKernelGGL(hyp_count_kernel, dim3(HC_WG_PER_CU * ncu), dim3(256), 0, st, b->calls, (RansacState*)b->state, (const double*)b->Hc, (const int*)b->valid, b->good,
                            max_iters, thr, (const int2*)b->work, b->work_ctr);
-    };
-    if (run == HOMO_BOTH_PHASES || run == HOMO_PHASE0_REPLAY) {
-        MIS_HIP(ctx, hipMemsetAsync(b->fin, 0xff, sizeof(int) * (size_t)b->count, st));
-        hipLaunchKernelGGL(draw_kernel, dim3(b->count), dim3(DRAW_TB), 0, st, b->calls, states, b->sub_idx, b->draw_idx, rt.U, rt.state_T, max_iters, 0, p0, b->work,
-                           b->work_ctr, confidence);
-        if (sy.rec && sy.rec_pos == 2) MIS_HIP(ctx, hipEventRecord(sy.rec, st));
-        if (sy.spec_stream && max_iters > p0) {
-            // the second phase's subsets of the few-match problems, drawn on a stream of their own beside the solves below (DRAW_SPEC)
-            MIS_HIP(ctx, hipEventRecord(sy.spec_fork, st));
-            MIS_HIP(ctx, hipStreamWaitEvent(sy.spec_stream, sy.spec_fork, 0));
-            hipLaunchKernelGGL(draw_kernel, dim3(b->count), dim3(DRAW_TB), 0, sy.spec_stream, b->calls, states, b->sub_idx, b->draw_idx, rt.U, rt.state_T, max_iters,
-                               DRAW_SPEC, max_iters, b->work, b->work_ctr, confidence);
-            MIS_HIP(ctx, hipEventRecord(sy.spec_join, sy.spec_stream));
-            if (sy.spec_mark) MIS_HIP(ctx, hipEventRecord(sy.spec_mark, sy.spec_stream));
+    }
+    // A scan_tail_kernel launch.  Those that run a DLT / LM refinement carry the term stages of ordered_sums in dynamic LDS; replay-only
+    // and mask-only ones do not (MIS_TAIL_PLAIN=1: none anywhere -- every ordered sum takes the plain loop; the parity tests run both).
+    // A replay covers the phase's hypotheses and empties the work list; the other kinds take the problems pending from that phase
+    void scan_tail(TailKind kind, RansacPhase phase) const {
+        static const bool plain = getenv("MIS_TAIL_PLAIN") != nullptr && atoi(getenv("MIS_TAIL_PLAIN")) != 0;
+        const int staged = (kind == TAIL_REPLAY_ONLY || kind == TAIL_MASK_ONLY || plain) ? 0 : 1;
+        const bool replay = kind == TAIL_REPLAY_FINISH || kind == TAIL_REPLAY_ONLY, second = phase == PHASE_SECOND;
+        const int lo = replay && second ? p0 : 0, hi = replay && second ? max_iters : p0, want = !replay && second ? 1 : 0;      // want: the value of fin[]
+        hipLaunchKernelGGL(scan_tail_kernel, dim3(b->count), dim3(TB), staged ? TAIL_DYN_LDS : (size_t)0, st, b->calls, (RansacState*)b->state, b->Hc, b->valid, b->good, b->scr,
+                           b->rec, b->results, lo, hi, max_iters, confidence, thr, b->fin, kind, want, staged, replay ? b->work_ctr : nullptr);
+    }
+    // one RANSAC phase: draw, solves, counts, replay (`replay` says whether the finishers' tails run in that launch or stay pending)
+    int run_phase(RansacPhase ph, TailKind replay) const {
+        if (ph == PHASE_FIRST) {
+            MIS_HIP(ctx, hipMemsetAsync(b->fin, 0xff, sizeof(int) * (size_t)b->count, st));
+            draw(DRAW_FIRST, st);
+            if (hk.after_first_draw) MIS_HIP(ctx, hipEventRecord(hk.after_first_draw, st));
+            if (hk.spec_stream && max_iters > p0) {
+                // the second phase's subsets of the few-match problems, drawn on a stream of their own beside the solves below
+                MIS_HIP(ctx, hipEventRecord(hk.spec_fork, st));
+                MIS_HIP(ctx, hipStreamWaitEvent(hk.spec_stream, hk.spec_fork, 0));
+                draw(DRAW_SPEC, hk.spec_stream);
+                MIS_HIP(ctx, hipEventRecord(hk.spec_join, hk.spec_stream));
+                if (hk.spec_mark) MIS_HIP(ctx, hipEventRecord(hk.spec_mark, hk.spec_stream));
+            }
+        } else {
+            if (max_iters <= p0) return MIS_OK;      // the first phase covered every hypothesis
+            if (hk.spec_stream) MIS_HIP(ctx, hipStreamWaitEvent(st, hk.spec_join, 0));
+            draw(DRAW_SECOND, st);
+            if (hk.after_second_draw) MIS_HIP(ctx, hipEventRecord(hk.after_second_draw, st));
         }
         hypotheses();
-        hipLaunchKernelGGL(scan_tail_kernel, dim3(b->count), dim3(TB), tail_lds(replay_part), st, b->calls, states, b->Hc, b->valid, b->good, b->scr, b->rec, b->results, 0, p0,
-                           max_iters, confidence, thr, b->fin, replay_part, 0, tail_staged(replay_part), b->work_ctr);
+        scan_tail(replay, ph);
+        return MIS_OK;
     }
-    if (run >= HOMO_TAIL0_MASK) {   // the problems a replay-only run left pending with fin == w
-        const int want = (run - HOMO_TAIL0_MASK) >> 1, part = 3 + ((run - HOMO_TAIL0_MASK) & 1);
-        hipLaunchKernelGGL(scan_tail_kernel, dim3(b->count), dim3(TB), tail_lds(part), st, b->calls, states, b->Hc, b->valid, b->good, b->scr, b->rec, b->results, 0, p0,
-                           max_iters, confidence, thr, b->fin, part, want, tail_staged(part), nullptr);
-    }
-    if ((run == HOMO_BOTH_PHASES || run == HOMO_PHASE1_REPLAY) && max_iters > p0) {
-        if (sy.spec_join && !sy.spec_stream) MIS_HIP(ctx, hipStreamWaitEvent(st, sy.spec_join, 0));      // the speculative drawing a HOMO_PHASE0_REPLAY run started
-        hipLaunchKernelGGL(draw_kernel, dim3(b->count), dim3(DRAW_TB), 0, st, b->calls, states, b->sub_idx, b->draw_idx, rt.U, rt.state_T, max_iters, 1, max_iters,
-                           b->work, b->work_ctr, confidence);
-        if (sy.rec && sy.rec_pos == 0) MIS_HIP(ctx, hipEventRecord(sy.rec, st));
-        hypotheses();
-        hipLaunchKernelGGL(scan_tail_kernel, dim3(b->count), dim3(TB), tail_lds(replay_part), st, b->calls, states, b->Hc, b->valid, b->good, b->scr, b->rec, b->results, p0,
-                           max_iters, max_iters, confidence, thr, b->fin, replay_part, 0, tail_staged(replay_part), b->work_ctr);
-    }
-    MIS_HIP(ctx, hipGetLastError());
-    return MIS_OK;
+};
+
+}  // namespace
+
+int homo_solve(MisContext* ctx, HomoBatch* b, const HomoParams& prm, hipStream_t stream, const HomoHooks* hooks) {
+    Engine e;
+    int rc = e.open(ctx, b, prm, stream, hooks);
+    if (rc == MIS_OK) rc = e.run_phase(PHASE_FIRST, TAIL_REPLAY_FINISH);
+    if (rc == MIS_OK) rc = e.run_phase(PHASE_SECOND, TAIL_REPLAY_FINISH);
+    return e.close(rc);
+}
+
+int homo_phase(MisContext* ctx, HomoBatch* b, const HomoParams& prm, RansacPhase phase, hipStream_t stream, const HomoHooks* hooks) {
+    Engine e;
+    int rc = e.open(ctx, b, prm, stream, hooks);
+    if (rc == MIS_OK) rc = e.run_phase(phase, TAIL_REPLAY_ONLY);
+    return e.close(rc);
+}
+
+int homo_tails(MisContext* ctx, HomoBatch* b, const HomoParams& prm, RansacPhase phase, TailStep step, hipStream_t stream) {
+    Engine e;
+    const int rc = e.open(ctx, b, prm, stream, nullptr);
+    if (rc == MIS_OK) e.scan_tail(step == TAIL_MASK ? TAIL_MASK_ONLY : TAIL_REFINE_ONLY, phase);
+    return e.close(rc);
 }

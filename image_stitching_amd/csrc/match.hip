@@ -948,7 +948,7 @@ int enqueue_chains(MisContext* ctx, MatchWorkspace* ws, int np, const MisMatchPa
     if (!ws->side && (rc = mis_aux_stream(ctx, 0, &ws->side)) != MIS_OK) return rc;
     trace_mark(ws, 0, st);
     if (!ws->third && (rc = mis_aux_stream(ctx, 1, &ws->third)) != MIS_OK) return rc;
-    auto run = [&](HomoBatch* b, HomoRun what, hipStream_t s, const HomoSync* sy = nullptr) { return homo_batch_run(ctx, b, p->ransac_thresh, p->max_iters, p->confidence, what, s, sy); };
+    const HomoParams prm{p->ransac_thresh, p->max_iters, p->confidence};
     // the match lists are final once the ratio test has run: their download (megabytes) goes to the third stream now, under the
     // RANSAC chains, instead of behind them (0.3 ms at the end of the call); pair k's matches land at the sum of the counts before it
     MIS_HIP(ctx, hipEventRecord(ws->ev_matches.ev, st));
@@ -957,44 +957,42 @@ int enqueue_chains(MisContext* ctx, MatchWorkspace* ws, int np, const MisMatchPa
     MIS_HIP(ctx, hipEventRecord(ws->ev_lists.ev, ws->third));
     // main chain: first estimation of every pair, RANSAC phase 0 and the inlier masks of the pairs that finish there.  The side
     // stream is idle until then: it draws the second phase's subsets of the few-match pairs meanwhile (0.19 ms of one workgroup
-    // per pair that stood between the two phases)
-    HomoSync spec;
-    spec.spec_stream = ws->side; spec.spec_fork = ws->ev_spec_fork.ev; spec.spec_join = ws->ev_spec_join.ev;
-    if (match_trace() && ws->tev[8].ready(hipEventDefault) == hipSuccess) spec.spec_mark = ws->tev[8].ev;
-    if ((rc = run(&ws->b1, HOMO_PHASE0_REPLAY, st, &spec)) != MIS_OK || (rc = run(&ws->b1, HOMO_TAIL0_MASK, st)) != MIS_OK) return rc;
+    // per pair that stood between the two phases).  Diagnostics: the ends of that draw and of the main chain's second one
+    HomoHooks chain;
+    chain.spec_stream = ws->side; chain.spec_fork = ws->ev_spec_fork.ev; chain.spec_join = ws->ev_spec_join.ev;
+    if (match_trace() && ws->tev[8].ready(hipEventDefault) == hipSuccess) chain.spec_mark = ws->tev[8].ev;
+    if (match_trace() && ws->tev[7].ready(hipEventDefault) == hipSuccess) chain.after_second_draw = ws->tev[7].ev;
+    if ((rc = homo_phase(ctx, &ws->b1, prm, PHASE_FIRST, st, &chain)) != MIS_OK || (rc = homo_tails(ctx, &ws->b1, prm, PHASE_FIRST, TAIL_MASK, st)) != MIS_OK) return rc;
     MIS_HIP(ctx, hipEventRecord(ws->ev_phase0.ev, st));
     trace_mark(ws, 1, st);
     // side chain: the inlier-only estimation of those pairs
     MIS_HIP(ctx, hipStreamWaitEvent(ws->side, ws->ev_phase0.ev, 0));
     hipLaunchKernelGGL(second_calls_kernel, dim3((np + 127) / 128), dim3(128), 0, ws->side, np, (const HomoCall*)ws->b1.calls, (const HomoResult*)ws->b1.results,
-                       (const float*)ws->b1.scr, (const int*)ws->b1.fin, 0, p->num_matches_thresh2, ws->b2.calls, d.out);
+                       (const float*)ws->b1.scr, (const int*)ws->b1.fin, PHASE_FIRST, p->num_matches_thresh2, ws->b2.calls, d.out);
     // the compose gate: behind the side chain's first draw, 0.05 - 0.1 ms behind the first phase -- the tails and that draw
     // hold their compute units by then
-    HomoSync gate;
-    gate.rec = ws->ev_draw1.ev; gate.rec_pos = 2; ws->ev_gate = ws->ev_draw1.ev;
-    if ((rc = run(&ws->b2, HOMO_BOTH_PHASES, ws->side, &gate)) != MIS_OK) return rc;
+    HomoHooks gate;
+    gate.after_first_draw = ws->ev_gate = ws->ev_draw1.ev;
+    if ((rc = homo_solve(ctx, &ws->b2, prm, ws->side, &gate)) != MIS_OK) return rc;
     MIS_HIP(ctx, hipEventRecord(ws->ev_side_done.ev, ws->side));
     trace_mark(ws, 4, ws->side);
     // third chain: DLT + LM refinement of the first H of the pairs that finished in phase 0
     MIS_HIP(ctx, hipStreamWaitEvent(ws->third, ws->ev_phase0.ev, 0));
-    if ((rc = run(&ws->b1, HOMO_TAIL0_REFINE, ws->third)) != MIS_OK) return rc;
+    if ((rc = homo_tails(ctx, &ws->b1, prm, PHASE_FIRST, TAIL_REFINE, ws->third)) != MIS_OK) return rc;
     trace_mark(ws, 6, ws->third);
-    // main chain: RANSAC phase 1 of the others
-    HomoSync draw2;      // behind the speculative drawing; diagnostics: the end of the main chain's second draw
-    draw2.spec_join = ws->ev_spec_join.ev;
-    if (match_trace() && ws->tev[7].ready(hipEventDefault) == hipSuccess) draw2.rec = ws->tev[7].ev;
-    if ((rc = run(&ws->b1, HOMO_PHASE1_REPLAY, st, &draw2)) != MIS_OK || (rc = run(&ws->b1, HOMO_TAIL1_MASK, st)) != MIS_OK) return rc;
+    // main chain: RANSAC phase 1 of the others, behind the speculative drawing
+    if ((rc = homo_phase(ctx, &ws->b1, prm, PHASE_SECOND, st, &chain)) != MIS_OK || (rc = homo_tails(ctx, &ws->b1, prm, PHASE_SECOND, TAIL_MASK, st)) != MIS_OK) return rc;
     MIS_HIP(ctx, hipEventRecord(ws->ev_phase1.ev, st));
     trace_mark(ws, 2, st);
     // the refinement of the phase-1 finishers' first H stays on this stream (1.7 ms of latency-bound work: behind the 2 ms
     // refinement of the phase-0 finishers on the third stream it ended the matcher 0.6 ms later); their inlier-only second
     // estimation goes to the third stream instead
-    if ((rc = run(&ws->b1, HOMO_TAIL1_REFINE, st)) != MIS_OK) return rc;
+    if ((rc = homo_tails(ctx, &ws->b1, prm, PHASE_SECOND, TAIL_REFINE, st)) != MIS_OK) return rc;
     trace_mark(ws, 3, st);
     MIS_HIP(ctx, hipStreamWaitEvent(ws->third, ws->ev_phase1.ev, 0));
     hipLaunchKernelGGL(second_calls_kernel, dim3((np + 127) / 128), dim3(128), 0, ws->third, np, (const HomoCall*)ws->b1.calls, (const HomoResult*)ws->b1.results,
-                       (const float*)ws->b1.scr, (const int*)ws->b1.fin, 1, p->num_matches_thresh2, ws->b3.calls, d.out);
-    if ((rc = run(&ws->b3, HOMO_BOTH_PHASES, ws->third)) != MIS_OK) return rc;
+                       (const float*)ws->b1.scr, (const int*)ws->b1.fin, PHASE_SECOND, p->num_matches_thresh2, ws->b3.calls, d.out);
+    if ((rc = homo_solve(ctx, &ws->b3, prm, ws->third)) != MIS_OK) return rc;
     MIS_HIP(ctx, hipEventRecord(ws->ev_third_done.ev, ws->third));
     trace_mark(ws, 5, ws->third);
     MIS_HIP(ctx, hipStreamWaitEvent(st, ws->ev_third_done.ev, 0));
@@ -1298,7 +1296,7 @@ extern "C" int mis_find_homography(MisContext* ctx, const float* src, const floa
     c.src = (const float*)(D + o_src); c.dst = (const float*)(D + o_dst); c.mask = D + o_mask; c.pt_off = 0; c.n = n; c.active = 1;
     MIS_HIP(ctx, hipMemcpyAsync(ws->b1.calls, &c, sizeof(c), hipMemcpyHostToDevice, st));
     MIS_HIP(ctx, hipStreamSynchronize(st));  // `c` lives on this stack frame
-    if ((rc = homo_batch_run(ctx, &ws->b1, thresh, max_iters, confidence)) != MIS_OK) return rc;
+    if ((rc = homo_solve(ctx, &ws->b1, HomoParams{thresh, max_iters, confidence})) != MIS_OK) return rc;
     HomoResult r;
     MIS_HIP(ctx, hipMemcpyAsync(&r, ws->b1.results, sizeof(r), hipMemcpyDeviceToHost, st));
     if (mask && n) MIS_HIP(ctx, hipMemcpyAsync(mask, D + o_mask, n, hipMemcpyDeviceToHost, st));
