@@ -115,6 +115,7 @@ PROTOTYPES = {
     "mis_sift_detect": (_i, [_vp, _P(MisImage), _P(MisFeatures)]),
     "mis_sift_detect_batch": (_i, [_vp, _P(MisImage), _i, _P(MisFeatures)]),
     "mis_sift_debug_level": (_i, [_vp, _P(MisImage), _i, _i, _i, _vp, _P(_i), _P(_i)]),
+    "mis_sift_debug_counts": (_i, [_vp, _P(C.c_uint)]),
     "mis_match_default_params": (None, [_P(MisMatchParams)]),
     "mis_match_all_pairs": (_i, [_vp, _P(MisFeatures), _i, _P(MisMatchParams), _P(MisMatchesInfo)]),
     "mis_match_pairs_sharded": (_i, [_vp, _P(MisFeatures), _i, _P(MisMatchParams), _i, _i, _P(MisMatchesInfo)]),

@@ -23,18 +23,23 @@ namespace {
 constexpr int SIFT_IMG_BORDER = 5, SIFT_MAX_INTERP_STEPS = 5, SIFT_ORI_HIST_BINS = 36;
 constexpr float SIFT_INIT_SIGMA = 0.5f, SIFT_ORI_SIG_FCTR = 1.5f, SIFT_ORI_RADIUS = 3 * 1.5f, SIFT_ORI_PEAK_RATIO = 0.8f;
 constexpr float SIFT_DESCR_SCL_FCTR = 3.f, SIFT_DESCR_MAG_THR = 0.2f, SIFT_INT_DESCR_FCTR = 512.f;
-constexpr int MAX_OCT = 16, MAX_LAYERS = 8, MAX_TAPS = 64;
+constexpr int MAX_OCT = 16, MAX_LAYERS = 8;
+// A Gaussian kernel is never truncated: Taps (a kernel argument) and the row pass's LDS staging hold MAX_TAPS - 1 taps, and
+// mis_sift_create refuses a parameter set that needs more (n_octave_layers = 1 with sigma 1.6 needs 91).
+constexpr int MAX_TAPS = 128;
 
 struct Taps {
     int n;
     float k[MAX_TAPS];
 };
 
-// GaussianBlur: ksize from sigma for float images; getGaussianKernel in double, normalised, stored as float
+// GaussianBlur's ksize for float images: cvRound(sigma * 8 + 1) | 1, uncapped
+int gaussian_ksize(double sigma) { return mis_round_d(sigma * 8 + 1) | 1; }
+
+// getGaussianKernel in double, normalised, stored as float (ksize <= MAX_TAPS - 1: checked by mis_sift_create)
 Taps gaussian_taps(double sigma) {
     Taps t;
-    int n = mis_round_d(sigma * 8 + 1) | 1;
-    if (n > MAX_TAPS - 1) n = MAX_TAPS - 1;
+    const int n = gaussian_ksize(sigma);
     double v[MAX_TAPS], sum = 0, scale2x = -0.5 / (sigma * sigma);
     for (int i = 0; i < n; i++) {
         double x = i - (n - 1) * 0.5;
@@ -866,6 +871,7 @@ struct MisSift {
     uint8_t* dup = nullptr;         // sorted position -> duplicate of an earlier one
     unsigned* rank = nullptr;       // raw index -> sorted position, and raw index -> duplicate flag (2 x kp_cap, zeroed per frame)
     unsigned cand_cap = 0, kp_cap = 0;
+    unsigned last_counts[4] = {0, 0, 0, 0};   // the counters of the last detect, for mis_sift_debug_counts
     double sig[MAX_LAYERS + 4];
     // second lane of mis_sift_detect_batch: a finder of its own on its own context / stream, driven by a host thread
     MisContext* pool_ctx = nullptr;       // a helper lane's output blocks come from (and go back to) the parent's context
@@ -926,6 +932,20 @@ extern "C" int mis_sift_create(MisContext* ctx, const MisSiftParams* params, int
     MIS_CHECK(ctx, p.nfeatures == 0, MIS_E_UNSUPPORTED, "SIFT: only nfeatures = 0 (the reference's SIFT::create()) is supported");
     MIS_CHECK(ctx, p.n_octave_layers >= 1 && p.n_octave_layers <= MAX_LAYERS && p.sigma > 0.5, MIS_E_INVALID, "SIFT: bad parameters");
     MIS_CHECK(ctx, max_width >= 16 && max_height >= 16 && max_width <= 16384 && max_height <= 16384, MIS_E_INVALID, "SIFT: image size out of range");
+    // buildGaussianPyramid: incremental sigmas; the base blur and every one of them must fit the tap buffer whole
+    const int nl = p.n_octave_layers;
+    double sig[MAX_LAYERS + 3];
+    sig[0] = p.sigma;
+    const double k = pow(2., 1. / nl);
+    for (int i = 1; i < nl + 3; i++) {
+        const double sig_prev = pow(k, (double)(i - 1)) * p.sigma, sig_total = sig_prev * k;
+        sig[i] = sqrt(sig_total * sig_total - sig_prev * sig_prev);
+    }
+    MIS_CHECK(ctx, p.sigma < 1e4, MIS_E_UNSUPPORTED, "SIFT: sigma %g needs a Gaussian kernel beyond the limit of %d taps", p.sigma, MAX_TAPS - 1);   // (keeps ksize an int)
+    int max_taps = gaussian_ksize((double)sqrtf(fmaxf((float)(p.sigma * p.sigma) - SIFT_INIT_SIGMA * SIFT_INIT_SIGMA * 4, 0.01f)));
+    for (int i = 1; i < nl + 3; i++) max_taps = std::max(max_taps, gaussian_ksize(sig[i]));
+    MIS_CHECK(ctx, max_taps <= MAX_TAPS - 1, MIS_E_UNSUPPORTED, "SIFT: sigma %g with %d octave layers needs a %d-tap Gaussian kernel (limit %d)", p.sigma, nl,
+              max_taps, MAX_TAPS - 1);
     MIS_HIP(ctx, hipSetDevice(ctx->device));
     MisSift* s = new MisSift();
     s->ctx = ctx; s->p = p; s->max_w = max_width; s->max_h = max_height;
@@ -933,14 +953,7 @@ extern "C" int mis_sift_create(MisContext* ctx, const MisSiftParams* params, int
     const size_t need = s->bytes;
     if (hipMalloc((void**)&s->mem, need) != hipSuccess) { delete s; return mis_set_error(ctx, MIS_E_HIP, "SIFT: cannot allocate %zu bytes of scale space", need); }
     sift_plan(s, max_width, max_height);
-    // buildGaussianPyramid: incremental sigmas
-    const int nl = p.n_octave_layers;
-    s->sig[0] = p.sigma;
-    const double k = pow(2., 1. / nl);
-    for (int i = 1; i < nl + 3; i++) {
-        const double sig_prev = pow(k, (double)(i - 1)) * p.sigma, sig_total = sig_prev * k;
-        s->sig[i] = sqrt(sig_total * sig_total - sig_prev * sig_prev);
-    }
+    for (int i = 0; i < nl + 3; i++) s->sig[i] = sig[i];
     *out = s;
     return MIS_OK;
 }
@@ -1079,6 +1092,14 @@ extern "C" int mis_sift_detect(MisSift* s, const MisImage* bgr, MisFeatures* out
         MIS_HIP(ctx, hipStreamSynchronize(st));
     }
     out->n = (int)counts[2];
+    memcpy(s->last_counts, counts, sizeof(counts));
+    return MIS_OK;
+}
+
+extern "C" int mis_sift_debug_counts(MisSift* s, unsigned* counts4) {
+    if (!s) return MIS_E_INVALID;
+    MIS_CHECK(s->ctx, counts4, MIS_E_INVALID, "null argument");
+    memcpy(counts4, s->last_counts, sizeof(s->last_counts));
     return MIS_OK;
 }
 

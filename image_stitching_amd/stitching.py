@@ -738,6 +738,12 @@ class SiftFeatureFinder:
         self.ctx.check(self.ctx.lib.mis_sift_debug_level(self.h, C.byref(i), octave, layer, int(dog), out.ctypes.data_as(C.c_void_p), C.byref(w), C.byref(h)))
         return out
 
+    def debug_counts(self):
+        """Counters of the last detect(): dict(candidates, refined, raw, keypoints)."""
+        c = (C.c_uint * 4)()
+        self.ctx.check(self.ctx.lib.mis_sift_debug_counts(self.h, c))
+        return dict(candidates=int(c[0]), raw=int(c[1]), keypoints=int(c[2]), refined=int(c[3]))
+
     def close(self):
         if getattr(self, "h", None) and self.ctx.h:
             self.ctx.lib.mis_sift_destroy(self.h)

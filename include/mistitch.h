@@ -272,7 +272,10 @@ int mis_warper_warp_fused_batch(MisContext* ctx, int kind, const MisImage* srcs_
 
 /* ---------------------------------------------------------------- SIFT ---------------------- */
 /* SIFT::create() -- replaces image_stitching/image_stitching.cpp:559 (features_type == "sift").  Defaults of the
- * reference: nfeatures 0 (only value supported), nOctaveLayers 3, contrastThreshold 0.04, edgeThreshold 10, sigma 1.6. */
+ * reference: nfeatures 0 (only value supported), nOctaveLayers 3, contrastThreshold 0.04, edgeThreshold 10, sigma 1.6.
+ * n_octave_layers 1 .. 8, sigma > 0.5.  A Gaussian kernel is never truncated: GaussianBlur's ksize = cvRound(8 s + 1) | 1 of the
+ * base blur and of every incremental sigma must not exceed 127 taps (n_octave_layers 1 at sigma 1.6 needs 91, 3 at sigma 8.1 needs
+ * 127); a parameter set that needs more returns MIS_E_UNSUPPORTED. */
 typedef struct {
     int nfeatures, n_octave_layers;
     double contrast_threshold, edge_threshold, sigma;
@@ -288,6 +291,8 @@ int mis_sift_detect(MisSift* sift, const MisImage* bgr, MisFeatures* out);
 int mis_sift_detect_batch(MisSift* sift, const MisImage* bgr, int n_images, MisFeatures* out);
 /* test aid: one image of the Gaussian (dog = 0) or DoG (dog = 1) pyramid of `bgr`, copied to host_out (may be NULL) */
 int mis_sift_debug_level(MisSift* sift, const MisImage* bgr, int octave, int layer, int dog, float* host_out, int* width, int* height);
+/* counters of this finder's last mis_sift_detect: extrema candidates, raw keypoints, keypoints after duplicate removal, refined candidates */
+int mis_sift_debug_counts(MisSift* sift, unsigned* counts4);
 
 /* ---------------------------------------------------------------- image operators ----------- */
 /* cv::resize(src, dst, dsize, fx, fy, INTER_LINEAR_EXACT) -- replaces image_stitching.cpp:580 (work scale), :619 (seam

@@ -668,6 +668,8 @@ class Sift:
         self.params = p
         self.w, self.h = width, height
         self.h_ = C.c_void_p(L.mo_sift_create(C.byref(p), width, height))
+        if not self.h_:
+            raise ValueError("the oracle has no finder for these SIFT parameters (largest Gaussian kernel beyond the tap limit)")
 
     def __del__(self):
         try:
@@ -691,6 +693,12 @@ class Sift:
     def num_raw_keypoints(self):
         return lib().mo_sift_num_raw_keypoints(self.h_)
 
+    def num_candidates(self):
+        return lib().mo_sift_num_candidates(self.h_)
+
+    def num_refined(self):
+        return lib().mo_sift_num_refined(self.h_)
+
     def gauss(self, o, i):
         w, h = C.c_int(), C.c_int()
         p = lib().mo_sift_gauss(self.h_, o, i, C.byref(w), C.byref(h))
@@ -709,8 +717,10 @@ def expf(x):
 
 
 def gaussian_taps_f32(sigma):
-    buf = (C.c_float * 64)()
+    buf = (C.c_float * 127)()
     n = lib().mo_gaussian_taps_f32(C.c_double(sigma), buf)
+    if n < 0:
+        raise ValueError("sigma %r needs more taps than the oracle holds" % (sigma,))
     return np.array(buf[:n], np.float32)
 
 

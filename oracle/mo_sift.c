@@ -47,11 +47,13 @@ float mo_expf(float xx) {
 }
 static float pow2f(float x) { return mo_expf(x * 0.69314718055994530942f); }
 
+int mo_gaussian_ksize(double sigma) { return mo_round_d(sigma * 8 + 1) | 1; }
+
 int mo_gaussian_taps_f32(double sigma, float* taps) {
     /* GaussianBlur: ksize from sigma for float images; getGaussianKernel in double, normalised, stored as float */
-    int n = mo_round_d(sigma * 8 + 1) | 1;
-    double scale2x = -0.5 / (sigma * sigma), sum = 0, t[64];
-    if (n > 63) n = 63;
+    int n = mo_gaussian_ksize(sigma);
+    double scale2x = -0.5 / (sigma * sigma), sum = 0, t[MO_SIFT_MAX_TAPS];
+    if (n > MO_SIFT_MAX_TAPS) return -1; /* never truncated: mo_sift_create refuses such parameters */
     for (int i = 0; i < n; i++) {
         double x = i - (n - 1) * 0.5;
         t[i] = exp(scale2x * x * x);
@@ -72,7 +74,7 @@ struct MoSift {
     float* grayf;
     float* tmp;
     MoKeyPoint* kps;
-    int nk, capk, nraw;
+    int nk, capk, nraw, ncand, nrefined;
     float* desc;
 };
 
@@ -80,10 +82,31 @@ void mo_sift_default_params(MoSiftParams* p) {
     p->nfeatures = 0; p->n_octave_layers = 3; p->contrast_threshold = 0.04; p->edge_threshold = 10; p->sigma = 1.6;
 }
 
+static float base_sigma(double sigma) { return sqrtf(fmaxf((float)(sigma * sigma) - SIFT_INIT_SIGMA * SIFT_INIT_SIGMA * 4, 0.01f)); }
+
+static void incremental_sigmas(double sigma, int nl, double* sig /* nl + 3 */) {
+    double k = pow(2., 1. / nl);
+    sig[0] = sigma;
+    for (int i = 1; i < nl + 3; i++) {
+        double sig_prev = pow(k, (double)(i - 1)) * sigma, sig_total = sig_prev * k;
+        sig[i] = sqrt(sig_total * sig_total - sig_prev * sig_prev);
+    }
+}
+
 MoSift* mo_sift_create(const MoSiftParams* pp, int width, int height) {
+    MoSiftParams p;
+    mo_sift_default_params(&p);
+    if (pp) p = *pp;
+    if (p.n_octave_layers < 1 || p.n_octave_layers > 8 || !(p.sigma > 0.5) || !(p.sigma < 1e4)) return NULL;
+    {   /* no finder for a parameter set whose largest Gaussian kernel does not fit the tap buffer */
+        double sig[16];
+        int most = mo_gaussian_ksize((double)base_sigma(p.sigma));
+        incremental_sigmas(p.sigma, p.n_octave_layers, sig);
+        for (int i = 1; i < p.n_octave_layers + 3; i++) most = most > mo_gaussian_ksize(sig[i]) ? most : mo_gaussian_ksize(sig[i]);
+        if (most > MO_SIFT_MAX_TAPS) return NULL;
+    }
     MoSift* s = (MoSift*)calloc(1, sizeof(MoSift));
-    mo_sift_default_params(&s->p);
-    if (pp) s->p = *pp;
+    s->p = p;
     s->w = width; s->h = height; s->nl = s->p.n_octave_layers;
     int bw = width * 2, bh = height * 2, firstOctave = -1;
     s->noct = mo_round_d(log((double)(bw < bh ? bw : bh)) / log(2.) - 2) - firstOctave;
@@ -142,7 +165,7 @@ static void upsample2x(const uint8_t* g, int w, int h, float* dst) {
 
 /* GaussianBlur(src, dst, Size(), sigma, sigma), BORDER_REFLECT_101: rows then columns, taps in ascending order */
 static void gaussian_blur(const float* src, int w, int h, double sigma, float* tmp, float* dst) {
-    float k[64];
+    float k[MO_SIFT_MAX_TAPS];
     int n = mo_gaussian_taps_f32(sigma, k), r = n / 2, y;
 #pragma omp parallel for schedule(static)
     for (y = 0; y < h; y++)
@@ -341,19 +364,12 @@ int mo_sift_run(MoSift* s, const uint8_t* bgr, size_t stride) {
     mo_bgr2gray(bgr, s->w, s->h, stride, s->gray, (size_t)s->w);
     upsample2x(s->gray, s->w, s->h, s->grayf);
     {
-        float sd = sqrtf(fmaxf((float)(sigma * sigma) - SIFT_INIT_SIGMA * SIFT_INIT_SIGMA * 4, 0.01f));
+        float sd = base_sigma(sigma);
         gaussian_blur(s->grayf, s->ow[0], s->oh[0], (double)sd, s->tmp, s->gauss[0]);
     }
     /* buildGaussianPyramid */
     double sig[16];
-    sig[0] = sigma;
-    {
-        double k = pow(2., 1. / nl);
-        for (int i = 1; i < nl + 3; i++) {
-            double sig_prev = pow(k, (double)(i - 1)) * sigma, sig_total = sig_prev * k;
-            sig[i] = sqrt(sig_total * sig_total - sig_prev * sig_prev);
-        }
-    }
+    incremental_sigmas(sigma, nl, sig);
     for (int o = 0; o < s->noct; o++) {
         const int w = s->ow[o], h = s->oh[o];
         for (int i = 0; i < nl + 3; i++) {
@@ -380,6 +396,7 @@ int mo_sift_run(MoSift* s, const uint8_t* bgr, size_t stride) {
     }
     /* findScaleSpaceExtrema */
     s->nk = 0;
+    s->ncand = s->nrefined = 0;
     const int threshold = mo_floor_d(0.5 * s->p.contrast_threshold / nl * 255);
     const int n = SIFT_ORI_HIST_BINS;
     for (int o = 0; o < s->noct; o++) {
@@ -403,10 +420,12 @@ int mo_sift_run(MoSift* s, const uint8_t* bgr, size_t stride) {
                                 if (!(val <= AT(img, r + dr, c + dc) && val <= AT(prev, r + dr, c + dc) && val <= AT(next, r + dr, c + dc))) { is_ext = 0; break; }
                     }
                     if (!is_ext) continue;
+                    s->ncand++;
                     MoKeyPoint kpt;
                     int r1 = r, c1 = c, layer = i;
                     memset(&kpt, 0, sizeof(kpt));
                     if (!adjust_local_extrema(s, o, &layer, &r1, &c1, &kpt)) continue;
+                    s->nrefined++;
                     float scl_octv = kpt.size * 0.5f / (1 << o);
                     float hist[SIFT_ORI_HIST_BINS];
                     float omax = calc_orientation_hist(s->gauss[o * (nl + 3) + layer], w, h, c1, r1, mo_round_f(SIFT_ORI_RADIUS * scl_octv),
@@ -472,3 +491,5 @@ int mo_sift_num_octaves(const MoSift* s) { return s->noct; }
 const float* mo_sift_gauss(const MoSift* s, int o, int i, int* w, int* h) { *w = s->ow[o]; *h = s->oh[o]; return s->gauss[o * (s->nl + 3) + i]; }
 const float* mo_sift_dog(const MoSift* s, int o, int i, int* w, int* h) { *w = s->ow[o]; *h = s->oh[o]; return s->dog[o * (s->nl + 2) + i]; }
 int mo_sift_num_raw_keypoints(const MoSift* s) { return s->nraw; }
+int mo_sift_num_candidates(const MoSift* s) { return s->ncand; }
+int mo_sift_num_refined(const MoSift* s) { return s->nrefined; }
