@@ -46,10 +46,10 @@ JobOutput StitchJob::run(const std::vector<MisImage>& frames) {
         finalize();
     });
     check(ctx_, mis_match_on_enqueued(ctx_, &Hook::fire, &match_), "mis_match_on_enqueued");
-    const int rc = mis_match_pairs_select(ctx_, feats.data(), n_, &mp, nullptr, cfg_.range_width, 0, 1, pairwise_.data());
+    const int rc = mis_match_pairs_model(ctx_, feats.data(), n_, &mp, model_, nullptr, cfg_.range_width, 0, 1, pairwise_.data());
     mis_match_on_enqueued(ctx_, nullptr, nullptr);
     for (auto& f : feats) mis_features_free(ctx_, &f);
-    check(ctx_, rc, "mis_match_pairs_select");
+    check(ctx_, rc, "mis_match_pairs_model");
     match_.finish();
     // ---- pruning (:215-278) ----
     out.confidence.resize((size_t)n_ * n_);

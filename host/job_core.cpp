@@ -48,6 +48,7 @@ JobCore::JobCore(const char* who, std::string where, int device, void* main_stre
             throw std::runtime_error(std::string(who) + " runs the hot path (ORB, supplied cameras, no seam-scale step); use mis::Stitcher for the other options");
         kind_ = warp_kind(cfg_.warp_type);
         check_range_width(cfg_.range_width);
+        model_ = matcher_model(cfg_.matcher_type, cfg_.range_width);
         if (mis_context_create(device, mstream_, &ctx_) != MIS_OK) throw std::runtime_error("mis_context_create failed: no HIP device (there is no CPU fallback)");
         check(ctx_, mis_stream_create(device, 0, &cstream_), "mis_stream_create");
         if (mis_context_create(device, cstream_, &cctx_) != MIS_OK) throw std::runtime_error("mis_context_create (compose stream) failed");
@@ -159,10 +160,7 @@ void JobCore::compose(const std::vector<MisImage>& frames, const std::vector<int
 MisMatchParams JobCore::reset_matches() {
     if (!pairwise_.empty()) { mis_matches_free(pairwise_.data(), (int)pairwise_.size()); pairwise_.clear(); }
     pairwise_.assign((size_t)n_ * n_, MisMatchesInfo{});
-    MisMatchParams mp;
-    mis_match_default_params(&mp);
-    mp.match_conf = cfg_.match_conf;
-    return mp;
+    return match_params(model_, cfg_.match_conf);
 }
 
 }  // namespace mis

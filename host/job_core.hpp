@@ -75,6 +75,7 @@ protected:
     StitchConfig cfg_;
     std::vector<int> everyone_;       // 0 .. n-1
     int kind_ = MIS_WARP_SPHERICAL;   // the warper (cfg_.warp_type)
+    int model_ = MIS_MATCH_HOMOGRAPHY;   // the matcher's motion model (cfg_.matcher_type): both are accepted
     bool spec_ok_ = true;             // warpRoi of ALL frames succeeds: the composition may be speculated (see JobCore::JobCore)
     void* mstream_ = nullptr;         // main stream (nullptr: the null stream): features, matcher, the feature all-gather
     void* cstream_ = nullptr;         // compose stream: warp, feed, blend (and the sharded job's blend exchange)

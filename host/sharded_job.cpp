@@ -196,10 +196,10 @@ JobOutput ShardedJob::run(const std::vector<MisImage>& frames) {
         compose(frames, mine_, everyone_);
     });
     check(ctx_, mis_match_on_enqueued(ctx_, &Hook::fire, &match_), "mis_match_on_enqueued");
-    const int rc = mis_match_pairs_select(ctx_, feats.data(), n_, &mp, nullptr, cfg_.range_width, comm_.rank(), world, pairwise_.data());
+    const int rc = mis_match_pairs_model(ctx_, feats.data(), n_, &mp, model_, nullptr, cfg_.range_width, comm_.rank(), world, pairwise_.data());
     mis_match_on_enqueued(ctx_, nullptr, nullptr);
     for (auto& f : local) mis_features_free(ctx_, &f);
-    check(ctx_, rc, "mis_match_pairs_select");
+    check(ctx_, rc, "mis_match_pairs_model");
     match_.finish();
     // ---- the n x n confidences: every pair has exactly one owner, the sum is a gather ----
     out.confidence.resize((size_t)n_ * n_);

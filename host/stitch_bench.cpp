@@ -1,6 +1,6 @@
 // stitch_bench.cpp -- the job of bench.py (4K frames stitched per second, frames resident in HBM) driven from C++:
 // mis::StitchJob over the C ABI, synthetic frames rendered into HBM by synth/libmissynth_gpu.so.
-//   stitch_bench <cams.txt> [--steps K] [--warmup W] [--dump prefix] [--ranks N] [--comm host|rccl] [--one-gpu] [--warp kind] [--work_megapix f] [--rangewidth N]
+//   stitch_bench <cams.txt> [--steps K] [--warmup W] [--dump prefix] [--ranks N] [--comm host|rccl] [--one-gpu] [--warp kind] [--work_megapix f] [--rangewidth N] [--matcher homography|affine]
 // --ranks N > 1: the SHARDED job (mis::ShardedJob, host/sharded_job.hpp): this process never touches the GPU -- it creates the ranks'
 // rendezvous file, starts N child processes of itself (rank r on GPU r; --one-gpu: all on GPU 0, a rehearsal), relays rank 0's line,
 // and when a rank fails it ends the others and exits non-zero.  --comm rccl (default for N > 1): RCCL called directly; --comm host:
@@ -42,6 +42,7 @@ struct Args {
     bool one_gpu = false;
     double work_megapix = -1;      // features at work scale (image_stitching.cpp:589-603); -1: full resolution
     int range_width = -1;          // BestOf2NearestRangeMatcher (:83, :646-649); -1: all pairs
+    std::string matcher = "homography";      // matcher_type (:64, :644-645): "affine" = AffineBestOf2NearestMatcher
 };
 
 static bool read_cams(const std::string& path, int* n, int* W, int* H, std::vector<SyCamera>* sy, std::vector<mis::CameraParams>* cams) {
@@ -124,6 +125,7 @@ static int run_single(const Args& a) {
         cfg.warp_type = a.warp;
         cfg.work_megapix = a.work_megapix;
         cfg.range_width = a.range_width;
+        cfg.matcher_type = a.matcher;
         mis::StitchJob job(0, W, H, cams, cfg);
         std::vector<int> everyone(n);
         for (int i = 0; i < n; i++) everyone[i] = i;
@@ -160,6 +162,7 @@ static int run_rank(const Args& a, int rank) {
         cfg.warp_type = a.warp;
         cfg.work_megapix = a.work_megapix;
         cfg.range_width = a.range_width;
+        cfg.matcher_type = a.matcher;
         mis::ShardedJob job(device, W, H, cams, *comm, cfg);
         std::vector<MisImage> frames;
         if (render_frames(sy, job.my_frames(), W, H, &frames)) return 1;
@@ -225,7 +228,7 @@ static int launch(const Args& a, int argc, char** argv) {
 }
 
 int main(int argc, char** argv) {
-    if (argc < 2) { std::fprintf(stderr, "usage: stitch_bench cams.txt [--steps K] [--warmup W] [--dump prefix] [--ranks N] [--comm host|rccl] [--one-gpu] [--warp spherical|cylindrical|plane] [--work_megapix f] [--rangewidth N]\n"); return 2; }
+    if (argc < 2) { std::fprintf(stderr, "usage: stitch_bench cams.txt [--steps K] [--warmup W] [--dump prefix] [--ranks N] [--comm host|rccl] [--one-gpu] [--warp spherical|cylindrical|plane] [--work_megapix f] [--rangewidth N] [--matcher homography|affine]\n"); return 2; }
     Args a;
     a.cams_path = argv[1];
     for (int i = 2; i < argc; i++) {
@@ -238,9 +241,12 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--warp") && i + 1 < argc) a.warp = argv[++i];
         else if (!std::strcmp(argv[i], "--work_megapix") && i + 1 < argc) a.work_megapix = std::strtod(argv[++i], nullptr);
         else if (!std::strcmp(argv[i], "--rangewidth") && i + 1 < argc) a.range_width = std::atoi(argv[++i]);
+        else if (!std::strcmp(argv[i], "--matcher") && i + 1 < argc) a.matcher = argv[++i];
         else if (!std::strcmp(argv[i], "--rank-child") && i + 1 < argc) a.child_rank = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--session") && i + 1 < argc) a.session = argv[++i];
     }
+    // refused by name before any process is started or any device is touched
+    try { mis::check_range_width(a.range_width); mis::matcher_model(a.matcher, a.range_width); } catch (const std::exception& e) { std::fprintf(stderr, "%s\n", e.what()); return 2; }
     if (a.ranks < 1 || a.ranks > 16) { std::fprintf(stderr, "--ranks 1..16\n"); return 2; }
     if (a.comm.empty() && a.ranks > 1) a.comm = "rccl";
     if (!a.comm.empty() && a.comm != "host" && a.comm != "rccl") { std::fprintf(stderr, "--comm host | rccl\n"); return 2; }

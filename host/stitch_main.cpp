@@ -17,7 +17,7 @@
 int main(int argc, char** argv) {
     if (argc < 2) {
         std::cout << "usage: " << argv[0] << " <image directory> [--features orb|sift] [--ba no|reproj] [--ba_refine_mask xxxxx] [--wave_correct horiz|vert|no]\n"
-                     "       [--expos_comp no|gain_blocks] [--seam no|voronoi|dp_color] [--warp spherical|cylindrical|plane] [--blend no|feather|multiband] [--conf_thresh f] [--match_conf f] [--compose_megapix f] [--seam_megapix f] [--work_megapix f] [--rangewidth N]\n"
+                     "       [--expos_comp no|gain_blocks] [--seam no|voronoi|dp_color] [--warp spherical|cylindrical|plane] [--blend no|feather|multiband] [--conf_thresh f] [--match_conf f] [--compose_megapix f] [--seam_megapix f] [--work_megapix f] [--rangewidth N] [--matcher homography|affine]\n"
                      "(the reference sets these as globals, image_stitching.cpp:49-85)\n";
         return -1;
     }
@@ -38,9 +38,10 @@ int main(int argc, char** argv) {
         else if (k == "--conf_thresh") cfg.conf_thresh = std::strtof(v.c_str(), nullptr);
         else if (k == "--match_conf") cfg.match_conf = std::strtof(v.c_str(), nullptr);
         else if (k == "--rangewidth") cfg.range_width = std::atoi(v.c_str());
+        else if (k == "--matcher") cfg.matcher_type = v;
         else { std::cout << "unknown option " << k << "\n"; return -1; }
     }
-    try { mis::check_range_width(cfg.range_width); } catch (const std::exception& e) { std::cout << e.what() << "\n"; return -1; }
+    try { mis::check_range_width(cfg.range_width); mis::matcher_model(cfg.matcher_type, cfg.range_width); } catch (const std::exception& e) { std::cout << e.what() << "\n"; return -1; }
     namespace fs = std::filesystem;
     std::vector<std::string> img_names;
     for (auto& e : fs::directory_iterator(argv[1])) {

@@ -88,6 +88,7 @@ StitchResult Stitcher::stitch(const std::vector<HostImage>& frames, const std::v
         throw std::runtime_error("seam finder '" + cfg_.seam_find_type + "' is not implemented ('no', 'voronoi' and 'dp_color' are)");
     const int kind = warp_kind(cfg_.warp_type);
     check_range_width(cfg_.range_width);
+    const int model = matcher_model(cfg_.matcher_type, cfg_.range_width);
     MisOrb* orb = nullptr;
     MisSift* sift = nullptr;
     std::vector<MisFeatures> features(n);
@@ -118,11 +119,9 @@ StitchResult Stitcher::stitch(const std::vector<HostImage>& frames, const std::v
 
     // ---- pairwise matching (:647-655) and pruning (:661) ----
     t = now();
-    MisMatchParams mp;
-    mis_match_default_params(&mp);
-    mp.match_conf = cfg_.match_conf;
+    const MisMatchParams mp = match_params(model, cfg_.match_conf);
     std::vector<MisMatchesInfo> pairwise((size_t)n * n);
-    check(mis_match_pairs_select(ctx_, features.data(), n, &mp, nullptr, cfg_.range_width, 0, 1, pairwise.data()), "mis_match_pairs_select");
+    check(mis_match_pairs_model(ctx_, features.data(), n, &mp, model, nullptr, cfg_.range_width, 0, 1, pairwise.data()), "mis_match_pairs_model");
     for (auto& m : pairwise) out.confidence.push_back(m.confidence);
     out.indices.resize(n);
     int kept = 0;

@@ -36,7 +36,26 @@ struct StitchConfig {
     std::string warp_type = "spherical";   // "spherical" | "cylindrical" | "plane"
     // matcher (:83, :646-649): -1 BestOf2NearestMatcher (all pairs), w >= 1 BestOf2NearestRangeMatcher (pairs with j < i + w only)
     int range_width = -1;
+    // matcher_type (:64, :644-645): "homography" (the two above) | "affine": AffineBestOf2NearestMatcher(false, ...), all pairs
+    std::string matcher_type = "homography";
 };
+
+// matcher_type of the config -> MIS_MATCH_*, the check before any device work.  An unknown name is refused by name; so is "affine"
+// together with a range_width: the reference silently ignores range_width there (:644 comes first), no option is ignored here
+inline int matcher_model(const std::string& t, int range_width) {
+    if (t == "homography") return MIS_MATCH_HOMOGRAPHY;
+    if (t != "affine") throw std::runtime_error("matcher_type '" + t + "': 'homography' or 'affine' (--matcher)");
+    if (range_width != -1)
+        throw std::runtime_error("matcher_type 'affine' with range_width " + std::to_string(range_width) + " (--matcher affine --rangewidth): AffineBestOf2NearestMatcher matches all pairs");
+    return MIS_MATCH_AFFINE_PARTIAL;
+}
+// the matcher's parameters for a model: mis_match_default_params / mis_match_affine_default_params with the config's match_conf
+inline MisMatchParams match_params(int model, float match_conf) {
+    MisMatchParams mp;
+    if (model == MIS_MATCH_AFFINE_PARTIAL) mis_match_affine_default_params(&mp); else mis_match_default_params(&mp);
+    mp.match_conf = match_conf;
+    return mp;
+}
 
 // range_width of the config: -1 or >= 1 (mis_match_pairs_select refuses the rest too; this is the check before any device work)
 inline int check_range_width(int w) {

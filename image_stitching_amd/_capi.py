@@ -20,6 +20,7 @@ INTER_NEAREST, INTER_LINEAR = 0, 1
 BORDER_CONSTANT, BORDER_REFLECT = 0, 2
 BLEND_NO, BLEND_FEATHER, BLEND_MULTI_BAND = 0, 1, 2
 WARP_SPHERICAL, WARP_CYLINDRICAL, WARP_PLANE = 0, 1, 2
+MATCH_HOMOGRAPHY, MATCH_AFFINE_PARTIAL = 0, 1
 
 
 class MisPoint(C.Structure):
@@ -120,6 +121,9 @@ PROTOTYPES = {
     "mis_match_all_pairs": (_i, [_vp, _P(MisFeatures), _i, _P(MisMatchParams), _P(MisMatchesInfo)]),
     "mis_match_pairs_sharded": (_i, [_vp, _P(MisFeatures), _i, _P(MisMatchParams), _i, _i, _P(MisMatchesInfo)]),
     "mis_match_pairs_select": (_i, [_vp, _P(MisFeatures), _i, _P(MisMatchParams), _vp, _i, _i, _i, _P(MisMatchesInfo)]),
+    "mis_match_affine_default_params": (None, [_P(MisMatchParams)]),
+    "mis_match_pairs_model": (_i, [_vp, _P(MisFeatures), _i, _P(MisMatchParams), _i, _vp, _i, _i, _i, _P(MisMatchesInfo)]),
+    "mis_estimate_affine_partial": (_i, [_vp, _vp, _vp, _i, _d, _i, _d, _i, _vp, _vp, _P(_i)]),
     "mis_matches_free": (_i, [_P(MisMatchesInfo), _i]),
     "mis_match_sequence": (C.c_longlong, [_vp]),
     "mis_match_knn_fence": (_i, [_vp, _vp, C.c_longlong, _i]),

@@ -46,8 +46,15 @@ struct HomoBatch {
 int homo_batch_reserve(MisContext* ctx, HomoBatch* b, int count, long long points, int max_iters);
 int homo_batch_debug_states(MisContext* ctx, const HomoBatch* b, int* out, int cap);
 void homo_batch_release(HomoBatch* b);
+// The motion model of an estimation.  MODEL_HOMOGRAPHY: cv::findHomography, 4-point subsets (everything above).
+// MODEL_AFFINE_PARTIAL: cv::estimateAffinePartial2D, 2-point subsets (calib3d ptsetreg.cpp, restated in homography.hip under
+// "the affine-partial model"): the same draw / work list / replay / tail steps with kernels of its own -- a closed-form hypothesis
+// solved and counted in one kernel (no Hc, no Jacobi), the replay with bar max(max_good, 1) and exponent 2, a 4-parameter LM tail.
+// HomoResult::H then holds [a -b tx; b a ty; 0 0 1].
+enum MotionModel { MODEL_HOMOGRAPHY = 0, MODEL_AFFINE_PARTIAL = 1 };
 // The RANSAC parameters of an estimation; every entry below validates them (thresh <= 0: the default of 3 pixels).
-struct HomoParams { double thresh; int max_iters; double confidence; };
+// refine_iters: LM iterations of the affine-partial tail (0: the RANSAC model itself); the homography's refinement is fixed at 10.
+struct HomoParams { double thresh; int max_iters; double confidence; MotionModel model = MODEL_HOMOGRAPHY; int refine_iters = 10; };
 // Optional ordering hooks of a batch's phases.  after_first_draw / after_second_draw: recorded behind that phase's draw_kernel.
 // Speculative drawing of the second phase's subsets (homography.hip, DRAW_SPEC): given spec_stream, the first phase enqueues it
 // there, behind spec_fork (recorded behind its own draw) and in front of spec_join (and of spec_mark, a timing event, when set);

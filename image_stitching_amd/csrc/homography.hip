@@ -22,6 +22,8 @@
 //                     parallel, then ONE thread per accumulator; Jacobi rotations spread over n threads.
 // Phase 0 covers hypotheses [0,128) (overlapping pairs converge there), phase 1 the rest.  The replay launch of a phase empties the
 // work list again for the next phase or call.
+// A second motion model, cv::estimateAffinePartial2D (HomoParams::model = MODEL_AFFINE_PARTIAL), runs the same steps with three
+// kernels of its own: "the affine-partial model" below, where its reading of OpenCV is written down.
 #include "homography.h"
 #include "dev_math.h"
 #include <algorithm>
@@ -224,12 +226,14 @@ __device__ bool check_subset(const float* s, const float* d) {
     return negative == 0 || negative == 4;
 }
 
+template <int MODEL_POINTS = 4>      // RANSACUpdateNumIters(p, ep, modelPoints, maxIters): 4 (homography) or 2 (affine-partial)
 __device__ int ransac_update_num_iters(double p, double ep, int max_iters) {
+    static_assert(MODEL_POINTS == 4 || MODEL_POINTS == 2, "pow(1 - ep, modelPoints) as exact products");
     if (p < 0.) p = 0.; if (p > 1.) p = 1.;
     if (ep < 0.) ep = 0.; if (ep > 1.) ep = 1.;
     double num = 1. - p; if (num < DBL_MIN) num = DBL_MIN;
     double w = 1. - ep, w2 = w * w;
-    double denom = 1. - w2 * w2;
+    double denom = MODEL_POINTS == 4 ? 1. - w2 * w2 : 1. - w2;
     if (denom < DBL_MIN) return 0;
     num = mis_log_d(num);
     denom = mis_log_d(denom);
@@ -1672,6 +1676,8 @@ __device__ __forceinline__ void finish_without_loop(TailShared& S, const TailPro
 // good[] (-1 for a degenerate sample) in LDS with the maximum of every run of `seg` entries beside it, and the replaying thread
 // steps over the runs that hold no new maximum.  A serial walk over global memory paid a load latency per hypothesis: 0.43 ms
 // for the 1872 hypotheses of phase 1, on the matcher's critical path.
+// MODEL_POINTS: a model replaces the best one with more than max(max_good, MODEL_POINTS - 1) inliers, and the update's exponent
+template <int MODEL_POINTS = 4>
 __device__ __forceinline__ void replay_hypotheses(TailShared& S, const TailProblem& p, const int* valid, const int* good, const int lo, const int hi, const int max_iters,
                                                   const double confidence, int* fin) {
     const int t = threadIdx.x, b = p.b, n = p.n;
@@ -1696,7 +1702,7 @@ __device__ __forceinline__ void replay_hypotheses(TailShared& S, const TailProbl
         int k = lo;
         while (k < kmax && iter < niters) {
             const int off = k - lo;
-            if (staged && off % seg == 0 && segmax[off / seg] <= (max_good > 3 ? max_good : 3)) {
+            if (staged && off % seg == 0 && segmax[off / seg] <= (max_good > MODEL_POINTS - 1 ? max_good : MODEL_POINTS - 1)) {
                 // nothing in this run changes the state: the loop walks to its end, or to the iteration limit
                 const int adv = min(min(seg, kmax - k), niters - iter);
                 k += adv; iter += adv;
@@ -1704,9 +1710,9 @@ __device__ __forceinline__ void replay_hypotheses(TailShared& S, const TailProbl
             }
             iter++;
             const int g = staged ? gl[off] : (valid[(size_t)b * max_iters + k] ? good[(size_t)b * max_iters + k] : -1);
-            if (g >= 0 && g > (max_good > 3 ? max_good : 3)) {
+            if (g >= 0 && g > (max_good > MODEL_POINTS - 1 ? max_good : MODEL_POINTS - 1)) {
                 best_k = k; max_good = g;
-                niters = ransac_update_num_iters(confidence, (double)(n - g) / n, niters);
+                niters = ransac_update_num_iters<MODEL_POINTS>(confidence, (double)(n - g) / n, niters);
             }
             k++;
         }
@@ -1718,12 +1724,21 @@ __device__ __forceinline__ void replay_hypotheses(TailShared& S, const TailProbl
 }
 
 // best model (S.Hf) -> mask, ordered compaction of the inliers (compressElems) into s1 / d1; their number ends in S.base
+// the affine-partial model's inlier test (computeError of Affine2DEstimatorCallback, float32; its reading: "the affine-partial model" below)
+__device__ __forceinline__ int aff_is_inlier(const float* F, float x, float y, float X, float Y, float t) {
+    const float a = ((F[0] * x + F[1] * y) + F[2]) - X;
+    const float b = ((F[3] * x + F[4] * y) + F[5]) - Y;
+    const float e = a * a + b * b;
+    return e <= t;
+}
+template <bool AFFINE = false>
 __device__ __forceinline__ void mask_and_compact(TailShared& S, const TailProblem& p, const float thr) {
     const int t = threadIdx.x, n = p.n;
     const HomoCall& c = p.c;
     for (int i0 = 0; i0 < n; i0 += TB) {
         int i = i0 + t, f = 0;
-        if (i < n) f = is_inlier(S.Hf, c.src[2 * i], c.src[2 * i + 1], c.dst[2 * i], c.dst[2 * i + 1], thr);
+        if (i < n) f = AFFINE ? aff_is_inlier(S.Hf, c.src[2 * i], c.src[2 * i + 1], c.dst[2 * i], c.dst[2 * i + 1], thr)
+                              : is_inlier(S.Hf, c.src[2 * i], c.src[2 * i + 1], c.dst[2 * i], c.dst[2 * i + 1], thr);
         if (c.mask && i < n) c.mask[i] = (uint8_t)f;
         unsigned long long bal = __ballot(f);
         int within = __popcll(bal & ((1ull << (t & 63)) - 1ull));
@@ -1814,6 +1829,441 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(MIS_TAIL_WAV
     refine_on_inliers(S, p, np, kind, want);
     PROF_LAST_EXIT(kind, want, wg_in);
     if (t == 0) { for (int i = 0; i < 9; i++) p.res->H[i] = S.best[i]; p.res->ninl = np; if (refines) st->tail_pending = 0; }
+}
+
+// ================================================================ the affine-partial model =====
+// cv::estimateAffinePartial2D(src, dst, inliers, RANSAC, thresh, maxIters, confidence, refineIters), the estimator behind
+// AffineBestOf2NearestMatcher(full_affine = false)::match (image_stitching/image_stitching.cpp:644-645).  OpenCV 4.x sources
+// restated: calib3d ptsetreg.cpp (AffinePartial2DEstimatorCallback, AffinePartial2DRefineCallback, estimateAffinePartial2D,
+// RANSACPointSetRegistrator) and LMSolver.  The reading:
+//  * RANSACPointSetRegistrator with modelPoints = 2, cv::RNG((uint64)-1) per call.  n < 2: no model.  n == 2: the model of both
+//    points, mask all ones, no refinement.  n > 2: the loop -- niters = max(maxIters, 1); a model replaces the best one when
+//    good > max(max_good, 1), strictly; then niters = RANSACUpdateNumIters(confidence, (n - good) / n, 2, niters); a model exists
+//    when max_good > 0.
+//  * getSubset: two indices, the second redrawn while it equals the first.  [uncertain] checkSubset: the collinearity test of
+//    Affine2DEstimatorCallback looks at triples only, so with two points every subset is accepted (an attempt never fails, and the
+//    10000-attempt limit of getSubset is never reached).
+//  * [uncertain: expression order] runKernel, in double, from (x1,y1)->(X1,Y1), (x2,y2)->(X2,Y2): aff_hypothesis below, evaluated
+//    as written (the library is built without FMA contraction).  Coincident source points give a non-finite model: it has no
+//    inliers (NaN <= t is false) and still counts as an iteration.
+//  * computeError / findInliers in float32: F = (float)M, a = F0 x + F1 y + F2 - X, b = F3 x + F4 y + F5 - Y, inlier when
+//    a a + b b <= (float)(thresh thresh).
+//  * refinement, only with a model, n > 2 and refineIters > 0: the inliers compressed in order; [uncertain] LMSolver (the <= 4.5
+//    LMSolverImpl::run restated by lm_refine_coop above, same stop rule, refineIters iterations) over (a, b, tx, ty) from
+//    (M0, M3, M2, M5); residuals (a x - b y + tx - X, b x + a y + ty - Y), Jacobian rows (x, -y, 1, 0), (y, x, 0, 1); the result is
+//    written back as [a -b tx; b a ty].  The returned mask is the RANSAC mask: it is not recomputed after the refinement.
+// The steps are the homography's -- draw, hypotheses from the work list, replay, tails -- with these kernels:
+//   aff_draw_kernel   per problem: the subset sequence.  A subset is "draw a; draw b until b != a", a two-state automaton over the
+//                     stream (state 0: expecting a; state 1: holding a, and a always equals the previous draw % n), so a chunk of
+//                     stream positions is a scan over transition functions: exact, no serial chase.
+//   aff_score_kernel    solve and count in one: a workgroup per work-list entry (HQ_HYPS hypotheses of one problem); the 64 models
+//                     are solved by 64 lanes into LDS (closed form, ~40 f64 operations: no Hc, no Jacobi), the problem's points
+//                     are staged in LDS once per workgroup (AH_TILE at a time), each wave counts 16 hypotheses, lanes striding
+//                     the points, counts from ballots.
+//   aff_tail_kernel   replay (replay_hypotheses<2>), mask + ordered compaction, 4-parameter LM.  The best model is solved again
+//                     from its subset (same function, same bits) instead of being stored per hypothesis.
+// Nothing here depends on the grid size or on which workgroup takes which entry: every count lands at its (problem, hypothesis).
+__device__ __forceinline__ void aff_hypothesis(const float2 p1, const float2 P1, const float2 p2, const float2 P2, double* M) {
+    const double x1 = p1.x, y1 = p1.y, X1 = P1.x, Y1 = P1.y, x2 = p2.x, y2 = p2.y, X2 = P2.x, Y2 = P2.y;
+    const double d = 1. / ((x1 - x2) * (x1 - x2) + (y1 - y2) * (y1 - y2));
+    const double S0 = d * ((X1 - X2) * (x1 - x2) + (Y1 - Y2) * (y1 - y2));
+    const double S1 = d * ((Y1 - Y2) * (x1 - x2) - (X1 - X2) * (y1 - y2));
+    const double S2 = d * ((Y1 - Y2) * (x1 * y2 - x2 * y1) - (X1 * y2 - X2 * y1) * (y1 - y2) - (X1 * x2 - X2 * x1) * (x1 - x2));
+    const double S3 = d * (-(X1 - X2) * (x1 * y2 - x2 * y1) - (Y1 * x2 - Y2 * x1) * (x1 - x2) - (Y1 * y2 - Y2 * y1) * (y1 - y2));
+    M[0] = S0; M[1] = -S1; M[2] = S2; M[3] = S1; M[4] = S0; M[5] = S3;
+}
+__device__ __forceinline__ void aff_hypothesis_of(const HomoCall& c, const int* id, double* M) {
+    const float2* src = reinterpret_cast<const float2*>(c.src);
+    const float2* dst = reinterpret_cast<const float2*>(c.dst);
+    aff_hypothesis(src[id[0]], dst[id[0]], src[id[1]], dst[id[1]], M);
+}
+
+// ---- aff_draw_kernel ----
+// An element of the scan: where a run of stream positions leaves the automaton from state 0 / from state 1 (bits 0, 1) and how
+// many subsets it completes on the way (bits 2 .. 16 from state 0, 17 .. 31 from state 1; a chunk completes at most half its positions)
+constexpr int AD_CHUNK = 4096;                 // stream positions per round
+constexpr int AD_PER = AD_CHUNK / TB;          // consecutive positions per thread
+constexpr unsigned AD_IDENTITY = 2u;
+__device__ __forceinline__ unsigned ad_to(unsigned e, unsigned s) { return (e >> s) & 1u; }
+__device__ __forceinline__ unsigned ad_cnt(unsigned e, unsigned s) { return (e >> (s ? 17 : 2)) & 0x7fffu; }
+__device__ __forceinline__ unsigned ad_then(unsigned a, unsigned b) {      // a, then b
+    const unsigned a0 = ad_to(a, 0), a1 = ad_to(a, 1);
+    return ad_to(b, a0) | (ad_to(b, a1) << 1) | ((ad_cnt(a, 0) + ad_cnt(b, a0)) << 2) | ((ad_cnt(a, 1) + ad_cnt(b, a1)) << 17);
+}
+__global__ __launch_bounds__(TB) void aff_draw_kernel(const HomoCall* calls, RansacState* states, int* sub_idx, const unsigned* U, unsigned long long state_T,
+                                                      int max_iters, DrawPhase phase, int k_hi_arg, int2* work, unsigned* work_ctr) {
+#if MIS_CHAIN_PRIO
+    __builtin_amdgcn_s_setprio(MIS_CHAIN_PRIO);
+#endif
+    __shared__ unsigned m[AD_CHUNK + 1];       // draw % n of the chunk's positions behind the value in front of it
+    __shared__ unsigned scan[TB];
+    __shared__ long long endpos;
+    const int b = blockIdx.x, t = threadIdx.x;
+    const HomoCall c = calls[b];
+    RansacState* st = states + b;
+    int k = 0;
+    long long pos = 0;
+    if (phase == DRAW_FIRST) {
+        if (t == 0) {
+            st->mode = (!c.active || c.n < 2) ? 0 : (c.n == 2 ? 1 : 2);
+            st->n_sub = 0; st->iter = 0; st->niters = max_iters > 1 ? max_iters : 1; st->max_good = 0; st->done = 0; st->best_k = -1; st->tail_pending = 0;
+            st->draw_k = 0; st->draw_fail = 0; st->draw_pos = 0;
+            st->spec_k = 0; st->spec_fail = 0; st->spec_pos = 0;
+        }
+        if (!c.active || c.n <= 2) return;
+    } else {
+        if (st->mode != 2 || st->done) return;
+        k = st->draw_k; pos = st->draw_pos;
+    }
+    const int k_hi = min(k_hi_arg, phase == DRAW_FIRST ? max_iters : st->niters);
+    __syncthreads();        // (every thread has read the state thread 0 writes at the end)
+    const unsigned n = (unsigned)c.n;
+    int* sidx = sub_idx + (size_t)b * max_iters * 4;
+    // beyond the table (never reached by the 2000 subsets of a real call: they take ~5000 positions at n = 3): thread 0 continues
+    // the generator serially from its state after RNG_TABLE draws
+    unsigned long long cur_state = state_T;
+    long long cur_pos = RNG_TABLE;
+    unsigned state = 0;         // the automaton's state in front of the chunk (a phase ends behind a subset: state 0)
+    while (k < k_hi) {
+        for (int o = t; o < AD_CHUNK; o += TB) if (pos + o < RNG_TABLE) m[1 + o] = U[pos + o] % n;
+        if (pos + AD_CHUNK > RNG_TABLE && t == 0)
+            for (long long q = max(pos, (long long)RNG_TABLE); q < pos + AD_CHUNK; q++) {
+                unsigned v = 0;
+                while (cur_pos <= q) {
+                    cur_state = (unsigned long long)(unsigned)cur_state * 4164903690u + (unsigned)(cur_state >> 32);
+                    v = (unsigned)cur_state;
+                    cur_pos++;
+                }
+                m[1 + (q - pos)] = v % n;
+            }
+        if (t == 0) { endpos = -1; if (state == 0) m[0] = 0; }
+        __syncthreads();
+        // this thread's run of positions as a scan element
+        const int q0 = t * AD_PER;
+        unsigned s0 = 0, s1 = 1, c0 = 0, c1 = 0;
+#pragma unroll
+        for (int q = q0; q < q0 + AD_PER; q++) {
+            const unsigned ne = m[1 + q] != m[q];      // in state 1: the second index differs from the first -- the subset is complete
+            c0 += s0 & ne; c1 += s1 & ne;
+            s0 = s0 ? (ne ^ 1u) : 1u; s1 = s1 ? (ne ^ 1u) : 1u;
+        }
+        scan[t] = s0 | (s1 << 1) | (c0 << 2) | (c1 << 17);
+        __syncthreads();
+        for (int o = 1; o < TB; o <<= 1) {
+            const unsigned mine = scan[t], before = t >= o ? scan[t - o] : AD_IDENTITY;
+            __syncthreads();
+            scan[t] = ad_then(before, mine);
+            __syncthreads();
+        }
+        const unsigned pre = t ? scan[t - 1] : AD_IDENTITY, all = scan[TB - 1];
+        const int total = (int)ad_cnt(all, state), need = k_hi - k;
+        unsigned s = ad_to(pre, state);
+        int r = (int)ad_cnt(pre, state);
+        for (int q = q0; q < q0 + AD_PER; q++) {
+            const unsigned ne = m[1 + q] != m[q];
+            if (s & ne) {
+                if (r < need) { sidx[4 * (k + r)] = (int)m[q]; sidx[4 * (k + r) + 1] = (int)m[1 + q]; }
+                if (r == need - 1) endpos = pos + q + 1;
+                r++;
+            }
+            s = s ? (ne ^ 1u) : 1u;
+        }
+        const unsigned last = m[AD_CHUNK];
+        __syncthreads();
+        if (total >= need) { k = k_hi; pos = endpos; state = 0; }
+        else { k += total; pos += AD_CHUNK; state = ad_to(all, state); }
+        __syncthreads();        // endpos and the chunk are read before the next round rewrites them
+        if (t == 0) m[0] = last;
+    }
+    if (t == 0) {
+        st->draw_pos = pos; st->draw_k = k; st->draw_fail = 0; st->n_sub = k;
+        list_hypotheses(st, b, phase, max_iters, work, work_ctr);
+    }
+}
+
+// ---- aff_score_kernel ----
+// Budget (MI355X: 160 KB of LDS and 2048 lanes per compute unit): a workgroup stages AH_TILE points as float4 (32 KB) and its 64
+// models (2 KB), so four workgroups (16 waves) share a compute unit on 136 KB.  A point costs one 16-byte LDS read and ~15 f32
+// operations per model for four models a pass: the kernel is bound by VALU issue, not by LDS (one ds_read_b128 per 60 VALU
+// instructions) nor by latency (16 waves a compute unit, four independent models per point).
+constexpr int AH_TILE = 2048;
+constexpr int AH_WG_PER_CU = 4;
+static_assert(HQ_HYPS == 64, "a work-list entry is one model per lane of a wave, 16 per wave of the workgroup");
+__global__ __launch_bounds__(256) void aff_score_kernel(const HomoCall* calls, const RansacState* states, const int* sub_idx, int* valid, int* good, int max_iters, float thr,
+                                                      const int2* work, const unsigned* work_ctr) {
+#if MIS_CHAIN_PRIO
+    __builtin_amdgcn_s_setprio(MIS_CHAIN_PRIO);
+#endif
+    __shared__ float4 pts[AH_TILE];
+    __shared__ float mdl[HQ_HYPS][8];
+    const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
+    const unsigned entries = work_ctr[WL_N];
+    for (unsigned e = blockIdx.x; e < entries; e += gridDim.x) {
+        const int2 w = work[e];
+        const int b = w.x, k0 = w.y;
+        const RansacState& st = states[b];
+        const int limit = min(st.n_sub, st.niters);
+        const HomoCall c = calls[b];
+        __syncthreads();        // the previous entry's models and points have been read
+        if (t < HQ_HYPS) {
+            double M[6] = {0, 0, 0, 0, 0, 0};
+            if (k0 + t < limit) aff_hypothesis_of(c, sub_idx + ((size_t)b * max_iters + k0 + t) * 4, M);
+#pragma unroll
+            for (int i = 0; i < 6; i++) mdl[t][i] = (float)M[i];
+        }
+        int cnt[16];
+#pragma unroll
+        for (int j = 0; j < 16; j++) cnt[j] = 0;
+        const float2* src = reinterpret_cast<const float2*>(c.src);
+        const float2* dst = reinterpret_cast<const float2*>(c.dst);
+        const int kw = k0 + wave * 16;      // this wave's hypotheses
+        for (int tile0 = 0; tile0 < c.n; tile0 += AH_TILE) {
+            const int tn = min(AH_TILE, c.n - tile0);
+            if (tile0) __syncthreads();
+            for (int i = t; i < tn; i += 256) { const float2 s = src[tile0 + i], d = dst[tile0 + i]; pts[i] = make_float4(s.x, s.y, d.x, d.y); }
+            __syncthreads();
+#pragma unroll
+            for (int g = 0; g < 4; g++) {
+                if (kw + 4 * g >= limit) continue;      // wave-uniform
+                float F[4][6];
+#pragma unroll
+                for (int j = 0; j < 4; j++)
+#pragma unroll
+                    for (int i = 0; i < 6; i++) F[j][i] = mdl[wave * 16 + 4 * g + j][i];
+                for (int i0 = 0; i0 < tn; i0 += 64) {
+                    const int i = i0 + lane;
+                    const float4 p = pts[min(i, tn - 1)];
+#pragma unroll
+                    for (int j = 0; j < 4; j++) cnt[4 * g + j] += __popcll(__ballot(i < tn && aff_is_inlier(F[j], p.x, p.y, p.z, p.w, thr)));
+                }
+            }
+        }
+        // the counts are wave-uniform: every lane stores them
+#pragma unroll
+        for (int j = 0; j < 16; j++)
+            if (kw + j < limit) { good[(size_t)b * max_iters + kw + j] = cnt[j]; valid[(size_t)b * max_iters + kw + j] = 1; }
+    }
+}
+
+// ---- aff_tail_kernel ----
+// The LM refinement over (a, b, tx, ty).  The problem is linear, so J^T J is a function of the points alone:
+// [sq 0 sx sy; 0 sq -sy sx; sx -sy N 0; sy sx 0 N] with sx = sum x, sy = sum y, sq = sum (x x + y y).  Every sum -- those three, the
+// four of J^T e and |e|^2 -- adds its terms in point order, one lane per sum (two terms a point, row after row of J, where a point
+// has two: acc += u; acc += w), the discipline of the homography tail; the 4 x 4 solve is LMSolver's solve(DECOMP_EIG) on
+// jacobi_eigen_coop<4>, not the 9 x 9 path.
+__device__ void aff_lm_refine(TailShared& S, const float* s1, const float* d1, const int np, const int lm_iters) {
+    const int t = threadIdx.x;
+    double* x = S.lm;            double* xd = x + 4;   double* A = xd + 4;  double* Ap = A + 16;
+    double* v = Ap + 16;         double* d = v + 4;    double* D = d + 4;   double* sc = D + 4;  // S, Sd, rmax, accepted, lambda, lc, need_invert, nu
+    double* sums = S.nrm;        // sx sy sq v0 v1 v2 v3 |e|^2
+    // this lane's sum (lane t < 8 of wave 0): its terms in a point's record {x, y, xx, yy, x e0, y e1, -y e0, x e1, e0, e1}
+    const int i0 = t == 0 ? 0 : t == 1 ? 1 : t == 2 ? 2 : t == 3 ? 4 : t == 4 ? 6 : t == 5 ? 8 : t == 6 ? 9 : 8;
+    const int i1 = t == 2 ? 3 : t == 3 ? 5 : t == 4 ? 7 : 9;
+    const bool two = t == 2 || t == 3 || t == 4 || t == 7, sq = t == 7;
+    auto normal_eq = [&](const double* h, bool with_J) {
+        double acc = 0, mx = 0;
+        const double a = h[0], bb = h[1], tx = h[2], ty = h[3];
+        for (int base = 0; base < np; base += TB) {
+            const int p = base + t, cnt = min(TB, np - base);
+            if (p < np) {
+                const double px = (double)s1[2 * p], py = (double)s1[2 * p + 1], PX = (double)d1[2 * p], PY = (double)d1[2 * p + 1];
+                const double e0 = ((a * px - bb * py) + tx) - PX, e1 = ((bb * px + a * py) + ty) - PY;
+                double* r = S.chunk + 10 * t;
+                r[0] = px; r[1] = py; r[2] = px * px; r[3] = py * py; r[4] = px * e0; r[5] = py * e1; r[6] = -py * e0; r[7] = px * e1; r[8] = e0; r[9] = e1;
+                mx = fmax(mx, fmax(fabs(e0), fabs(e1)));
+            }
+            __syncthreads();
+            if (t < 8 && (with_J || t == 7))
+                for (int q = 0; q < cnt; q++) {
+                    double u = S.chunk[10 * q + i0], w = S.chunk[10 * q + i1];
+                    if (sq) { u = u * u; w = w * w; }
+                    const double one = acc + u;
+                    acc = two ? one + w : one;
+                }
+            __syncthreads();
+        }
+        if (with_J && t < 8) sums[t] = acc;
+        else if (t == 7) sc[1] = acc;
+        if (with_J) {
+            S.chunk[t] = mx;
+            __syncthreads();
+            if (t == 0) {
+                double mm = 0;
+                for (int i = 0; i < TB; i++) mm = fmax(mm, S.chunk[i]);
+                const double sx = sums[0], sy = sums[1], sxy = sums[2], N = (double)np;
+                const double JtJ[16] = {sxy, 0, sx, sy, 0, sxy, -sy, sx, sx, -sy, N, 0, sy, sx, 0, N};
+                for (int i = 0; i < 16; i++) A[i] = JtJ[i];
+                for (int i = 0; i < 4; i++) v[i] = sums[3 + i];
+                sc[0] = sums[7]; sc[2] = mm;
+            }
+        }
+        __syncthreads();
+    };
+    if (t == 0) { x[0] = S.best[0]; x[1] = S.best[3]; x[2] = S.best[2]; x[3] = S.best[5]; }
+    __syncthreads();
+    normal_eq(x, true);
+    if (t < 4) D[t] = A[t * 4 + t];
+    if (t == 0) { sc[4] = 1; sc[5] = 0.75; }  // lambda, lc
+    __syncthreads();
+    for (int iter = 0;;) {
+        if (t < 16) S.A[t] = (t / 4 == t % 4) ? A[t] + sc[4] * D[t / 4] : A[t];
+        __syncthreads();
+        jacobi_eigen_coop<4>(S);
+        if (t == 0) {
+            // solve(Ap, v, d, DECOMP_EIG): Jacobi + SVBkSb back substitution
+            double thrw = 0;
+            for (int i = 0; i < 4; i++) thrw += S.W[i];
+            thrw *= DBL_EPSILON * 2;
+            for (int j = 0; j < 4; j++) d[j] = 0;
+            for (int i = 0; i < 4; i++) {
+                double wi = S.W[i];
+                if (fabs(wi) <= thrw) continue;
+                wi = 1 / wi;
+                double s = 0;
+                for (int j = 0; j < 4; j++) s += S.V[i * 4 + j] * v[j];
+                s *= wi;
+                for (int j = 0; j < 4; j++) d[j] = d[j] + s * S.V[i * 4 + j];
+            }
+            for (int i = 0; i < 4; i++) xd[i] = x[i] - d[i];
+        }
+        __syncthreads();
+        normal_eq(xd, false);  // Sd
+        if (t == 0) {
+            double Sv = sc[0], Sd = sc[1], lambda = sc[4], lc = sc[5];
+            double temp_d[4], dS = 0;
+            for (int i = 0; i < 4; i++) {
+                double s = 0;
+                for (int j = 0; j < 4; j++) s += A[i * 4 + j] * d[j];
+                temp_d[i] = s * -1. + v[i] * 2.;
+            }
+            for (int i = 0; i < 4; i++) dS += d[i] * temp_d[i];
+            double R = (Sv - Sd) / (fabs(dS) > DBL_EPSILON ? dS : 1);
+            sc[6] = 0;
+            if (R > 0.75) {
+                lambda *= 0.5;
+                if (lambda < lc) lambda = 0;
+            } else if (R < 0.25) {
+                double tt = 0;
+                for (int i = 0; i < 4; i++) tt += d[i] * v[i];
+                double nu = (Sd - Sv) / (fabs(tt) > DBL_EPSILON ? tt : 1) + 2;
+                nu = nu < 2. ? 2. : (nu > 10. ? 10. : nu);
+                if (lambda == 0) sc[6] = 1;  // needs invert(A)
+                else lambda *= nu;
+                sc[7] = nu;
+            }
+            sc[4] = lambda; sc[5] = lc;
+        }
+        __syncthreads();
+        if (sc[6] != 0.) {
+            // invert(A, Ap, DECOMP_EIG) -> lambda = lc = 1 / max |diag|, nu halved
+            if (t < 16) S.A[t] = A[t];
+            __syncthreads();
+            jacobi_eigen_coop<4>(S);
+            if (t == 0) {
+                double thrw = 0;
+                for (int i = 0; i < 4; i++) thrw += S.W[i];
+                thrw *= DBL_EPSILON * 2;
+                for (int e = 0; e < 16; e++) Ap[e] = 0;
+                for (int i = 0; i < 4; i++) {
+                    double wi = S.W[i];
+                    if (fabs(wi) <= thrw) continue;
+                    wi = 1 / wi;
+                    for (int r = 0; r < 4; r++)
+                        for (int cc = 0; cc < 4; cc++) Ap[r * 4 + cc] = Ap[r * 4 + cc] + S.V[i * 4 + r] * (S.V[i * 4 + cc] * wi);
+                }
+                double maxval = DBL_EPSILON;
+                for (int i = 0; i < 4; i++) { double aa = fabs(Ap[i * 4 + i]); if (aa > maxval) maxval = aa; }
+                double lambda = 1. / maxval, nu = sc[7] * 0.5;
+                sc[5] = lambda;
+                sc[4] = lambda * nu;
+            }
+            __syncthreads();
+        }
+        if (t == 0) {
+            double Sv = sc[0], Sd = sc[1];
+            sc[3] = Sd < Sv ? 1. : 0.;
+            if (Sd < Sv) { sc[0] = Sd; for (int i = 0; i < 4; i++) x[i] = xd[i]; }
+        }
+        __syncthreads();
+        if (sc[3] != 0.) normal_eq(x, true);
+        iter++;
+        double dmax = 0;
+        for (int i = 0; i < 4; i++) { double aa = fabs(d[i]); if (aa > dmax) dmax = aa; }
+        bool proceed = iter < lm_iters && dmax >= (double)FLT_EPSILON && sc[2] >= (double)FLT_EPSILON;
+        __syncthreads();
+        if (!proceed) break;
+    }
+    if (t == 0) { S.best[0] = x[0]; S.best[1] = -x[1]; S.best[2] = x[2]; S.best[3] = x[1]; S.best[4] = x[0]; S.best[5] = x[3]; }
+    __syncthreads();
+}
+
+// [a -b tx; b a ty] as the 3 x 3 of HomoResult: the last row is exactly (0, 0, 1)
+__device__ __forceinline__ void aff_store(HomoResult* res, const double* M) {
+    for (int i = 0; i < 6; i++) res->H[i] = M[i];
+    res->H[6] = 0; res->H[7] = 0; res->H[8] = 1;
+}
+
+// The launch kinds, want and the pending flags are scan_tail_kernel's
+__global__ __launch_bounds__(TB) void aff_tail_kernel(const HomoCall* calls, RansacState* states, const int* sub_idx, const int* valid, const int* good, float* scr_all,
+                                                      HomoResult* results, int lo, int hi, int max_iters, double confidence, float thr, int* fin, TailKind kind, int want,
+                                                      int lm_iters, unsigned* work_ctr) {
+    if (work_ctr && blockIdx.x == 0 && threadIdx.x < WL_CTRS) work_ctr[threadIdx.x] = 0;
+#if MIS_CHAIN_PRIO
+    __builtin_amdgcn_s_setprio(MIS_CHAIN_PRIO);
+#endif
+    __shared__ TailShared S;
+    if (threadIdx.x == 0) { S.staged = 0; S.bad = 0; }
+    __syncthreads();
+    const int b = blockIdx.x, t = threadIdx.x;
+    TailProblem p;
+    p.b = b; p.c = calls[b]; p.n = p.c.n; p.st = states + b; p.res = results + b;
+    p.s1 = scr_all + 4 * p.c.pt_off; p.d1 = p.s1 + 2 * (size_t)(p.n > 0 ? p.n : 0); p.rec = nullptr;
+    RansacState* const st = p.st;
+    const bool refines = kind == TAIL_REFINE_ONLY;
+    if (kind == TAIL_MASK_ONLY || refines) {
+        if (st->tail_pending != (refines ? 2 : 1) || fin[b] != want) return;   // uniform
+        __syncthreads();                                    // every thread has read the flag before it changes
+    } else {
+        if (st->done) return;
+        const int mode = st->mode;
+        if (t == 0) S.done_now = 0;
+        __syncthreads();
+        if (mode != 2) {
+            // no loop: n < 2 (or a skipped problem) has no model; n == 2 is runKernel on both points, mask all ones, no refinement
+            for (int i = t; p.c.mask && p.c.active && i < p.n; i += TB) p.c.mask[i] = mode ? 1 : 0;
+            if (t == 0) {
+                p.res->ok = mode ? 1 : 0; p.res->iters = 0; p.res->ninl = mode ? 2 : 0;
+                if (mode) { const int id[2] = {0, 1}; double M[6]; aff_hypothesis_of(p.c, id, M); aff_store(p.res, M); }
+                st->done = 1; fin[b] = lo == 0 ? 0 : 1;
+            }
+            return;
+        }
+        replay_hypotheses<2>(S, p, valid, good, lo, hi, max_iters, confidence, fin);
+        __syncthreads();
+        if (!S.done_now) return;
+        if (kind == TAIL_REPLAY_ONLY) { if (t == 0) st->tail_pending = 1; return; }
+    }
+    const int result = st->max_good > 0;
+    if (!refines && t == 0) { p.res->iters = st->iter; p.res->ok = result; p.res->ninl = 0; }
+    if (!result) {
+        for (int i = t; p.c.mask && i < p.n; i += TB) p.c.mask[i] = 0;
+        if (t == 0) st->tail_pending = 0;
+        return;
+    }
+    if (t == 0) {
+        aff_hypothesis_of(p.c, sub_idx + ((size_t)b * max_iters + st->best_k) * 4, S.best);
+        for (int i = 0; i < 6; i++) S.Hf[i] = (float)S.best[i];
+        S.base = refines ? p.res->ninl : 0;
+    }
+    __syncthreads();
+    if (!refines) mask_and_compact<true>(S, p, thr);
+    const int np = S.base;
+    if (kind == TAIL_MASK_ONLY) {
+        if (t == 0) { p.res->ninl = np; aff_store(p.res, S.best); st->tail_pending = 2; }
+        return;
+    }
+    if (lm_iters > 0 && np > 0) aff_lm_refine(S, p.s1, p.d1, np, lm_iters);
+    if (t == 0) { aff_store(p.res, S.best); p.res->ninl = np; if (refines) st->tail_pending = 0; }
 }
 
 // ---------------------------------------------------------------- host side --------------------
@@ -1924,12 +2374,16 @@ namespace {
 struct Engine {
     MisContext* ctx; HomoBatch* b; hipStream_t st; RngTable rt; HomoHooks hk;
     int max_iters, p0; double confidence; float thr;      // the first phase covers hypotheses [0, p0); thr: the squared threshold
+    bool affine; int lm_iters;                            // MODEL_AFFINE_PARTIAL: the aff_* kernels; its refineIters
     static constexpr size_t hq_lds = sizeof(double) * HQ_ELEMS * HQ_STRIDE;
 
     int open(MisContext* ctx_, HomoBatch* b_, const HomoParams& prm, hipStream_t stream, const HomoHooks* hooks) {
         ctx = ctx_; b = b_; hk = hooks ? *hooks : HomoHooks();
         MIS_CHECK(ctx, prm.max_iters >= 1 && prm.max_iters <= b->max_iters, MIS_E_INVALID, "max_iters %d outside the reserved range", prm.max_iters);
         MIS_CHECK(ctx, prm.confidence > 0 && prm.confidence < 1, MIS_E_INVALID, "confidence must be in (0,1)");
+        MIS_CHECK(ctx, prm.model == MODEL_HOMOGRAPHY || prm.model == MODEL_AFFINE_PARTIAL, MIS_E_UNSUPPORTED, "unknown motion model %d", (int)prm.model);
+        MIS_CHECK(ctx, prm.refine_iters >= 0, MIS_E_INVALID, "refine_iters must be >= 0");
+        affine = prm.model == MODEL_AFFINE_PARTIAL; lm_iters = prm.refine_iters;
         if (int rc = rng_table(ctx, &rt); rc != MIS_OK) return rc;
         const double thresh = prm.thresh <= 0 ? 3 : prm.thresh;
         thr = (float)(thresh * thresh);
@@ -1944,12 +2398,22 @@ struct Engine {
     }
     int close(int rc) const { if (rc == MIS_OK) MIS_HIP(ctx, hipGetLastError()); return rc; }      // the end of an entry point whose enqueues returned rc
     void draw(DrawPhase phase, hipStream_t s) const {
+        if (affine) {
+            hipLaunchKernelGGL(aff_draw_kernel, dim3(b->count), dim3(TB), 0, s, b->calls, (RansacState*)b->state, b->sub_idx, rt.U, rt.state_T, max_iters, phase,
+                               phase == DRAW_FIRST ? p0 : max_iters, b->work, b->work_ctr);
+            return;
+        }
         hipLaunchKernelGGL(draw_kernel, dim3(b->count), dim3(DRAW_TB), 0, s, b->calls, (RansacState*)b->state, b->sub_idx, b->draw_idx, rt.U, rt.state_T, max_iters, phase,
                            phase == DRAW_FIRST ? p0 : max_iters, b->work, b->work_ctr, confidence);
     }
     // the solves and counts of the work list draw_kernel has just written (the replay launch behind them empties it again)
     void hypotheses() const {
         const int ncu = std::max(ctx->num_cu, 1);
+        if (affine) {
+            hipLaunchKernelGGL(aff_score_kernel, dim3(AH_WG_PER_CU * ncu), dim3(256), 0, st, b->calls, (RansacState*)b->state, (const int*)b->sub_idx, b->valid, b->good,
+                               max_iters, thr, (const int2*)b->work, (const unsigned*)b->work_ctr);
+            return;
+        }
         hipLaunchKernelGGL(hyp_quad_kernel, dim3(HQ_WG_PER_CU * ncu), dim3(4 * HQ_HYPS), hq_lds, st, b->calls, (RansacState*)b->state, b->sub_idx, b->Hc, b->valid, max_iters,
                            (const int2*)b->work, b->work_ctr);
         hipLaunchKernelGGL(hyp_count_kernel, dim3(HC_WG_PER_CU * ncu), dim3(256), 0, st, b->calls, (RansacState*)b->state, (const double*)b->Hc, (const int*)b->valid, b->good,
@@ -1963,6 +2427,11 @@ struct Engine {
         const int staged = (kind == TAIL_REPLAY_ONLY || kind == TAIL_MASK_ONLY || plain) ? 0 : 1;
         const bool replay = kind == TAIL_REPLAY_FINISH || kind == TAIL_REPLAY_ONLY, second = phase == PHASE_SECOND;
         const int lo = replay && second ? p0 : 0, hi = replay && second ? max_iters : p0, want = !replay && second ? 1 : 0;      // want: the value of fin[]
+        if (affine) {
+            hipLaunchKernelGGL(aff_tail_kernel, dim3(b->count), dim3(TB), 0, st, b->calls, (RansacState*)b->state, (const int*)b->sub_idx, (const int*)b->valid,
+                               (const int*)b->good, b->scr, b->results, lo, hi, max_iters, confidence, thr, b->fin, kind, want, lm_iters, replay ? b->work_ctr : nullptr);
+            return;
+        }
         hipLaunchKernelGGL(scan_tail_kernel, dim3(b->count), dim3(TB), staged ? TAIL_DYN_LDS : (size_t)0, st, b->calls, (RansacState*)b->state, b->Hc, b->valid, b->good, b->scr,
                            b->rec, b->results, lo, hi, max_iters, confidence, thr, b->fin, kind, want, staged, replay ? b->work_ctr : nullptr);
     }
@@ -1972,7 +2441,7 @@ struct Engine {
             MIS_HIP(ctx, hipMemsetAsync(b->fin, 0xff, sizeof(int) * (size_t)b->count, st));
             draw(DRAW_FIRST, st);
             if (hk.after_first_draw) MIS_HIP(ctx, hipEventRecord(hk.after_first_draw, st));
-            if (hk.spec_stream && max_iters > p0) {
+            if (hk.spec_stream && max_iters > p0 && !affine) {      // (the affine draw is a scan: nothing worth drawing ahead)
                 // the second phase's subsets of the few-match problems, drawn on a stream of their own beside the solves below
                 MIS_HIP(ctx, hipEventRecord(hk.spec_fork, st));
                 MIS_HIP(ctx, hipStreamWaitEvent(hk.spec_stream, hk.spec_fork, 0));
@@ -1982,7 +2451,7 @@ struct Engine {
             }
         } else {
             if (max_iters <= p0) return MIS_OK;      // the first phase covered every hypothesis
-            if (hk.spec_stream) MIS_HIP(ctx, hipStreamWaitEvent(st, hk.spec_join, 0));
+            if (hk.spec_stream && !affine) MIS_HIP(ctx, hipStreamWaitEvent(st, hk.spec_join, 0));
             draw(DRAW_SECOND, st);
             if (hk.after_second_draw) MIS_HIP(ctx, hipEventRecord(hk.after_second_draw, st));
         }

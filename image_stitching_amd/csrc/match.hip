@@ -558,9 +558,10 @@ __device__ __forceinline__ int block_scan_flag(int flag, int* total) {
 }
 
 // CpuMatcher::match: accepted 1->2 matches in query order, then 2->1 matches that are not already
-// in the set; BestOf2NearestMatcher::match: point lists shifted by half the image size.
+// in the set; BestOf2NearestMatcher::match: point lists shifted by half the image size (centre != 0).
+// AffineBestOf2NearestMatcher::match takes the keypoint positions as they are (centre == 0: x - 0.f is x, bit for bit).
 __global__ __launch_bounds__(1024) void ratio_union_kernel(const FeatDev* feats, const PairDesc* pairs, const int* idx2, const float* dist2, float ratio,
-                                                           MisDMatch* matches, float* src_xy, float* dst_xy, int* n_matches) {
+                                                           MisDMatch* matches, float* src_xy, float* dst_xy, int* n_matches, int centre) {
     const PairDesc pd = pairs[blockIdx.x];
     const FeatDev F1 = feats[pd.i], F2 = feats[pd.j];
     MisDMatch* m = matches + pd.m_off;
@@ -570,7 +571,7 @@ __global__ __launch_bounds__(1024) void ratio_union_kernel(const FeatDev* feats,
     const float* d12 = dist2 + pd.knn_off12 * 2;
     const int* i21 = idx2 + pd.knn_off21 * 2;
     const float* d21 = dist2 + pd.knn_off21 * 2;
-    const float hw1 = (float)F1.w * 0.5f, hh1 = (float)F1.h * 0.5f, hw2 = (float)F2.w * 0.5f, hh2 = (float)F2.h * 0.5f;
+    const float hw1 = centre ? (float)F1.w * 0.5f : 0.f, hh1 = centre ? (float)F1.h * 0.5f : 0.f, hw2 = centre ? (float)F2.w * 0.5f : 0.f, hh2 = centre ? (float)F2.h * 0.5f : 0.f;
     int base = 0;
     if (F2.n >= 2)
         for (int q0 = 0; q0 < F1.n; q0 += 1024) {
@@ -942,19 +943,32 @@ int enqueue_knn(MisContext* ctx, MatchWorkspace* ws, const MatchPlan& pl, const 
 // the reference moves to the host assembly.  Side and third are the context's two auxiliary streams -- the streams the ORB batch's
 // helper lanes ran on a moment ago -- so that the job keeps to four streams (an earlier version created two more here, one in
 // a priority class of its own to dodge a shared hardware queue: the step then moved by 25 % with GPU_MAX_HW_QUEUES).
-int enqueue_chains(MisContext* ctx, MatchWorkspace* ws, int np, const MisMatchParams* p, const MatchDev& d, const MatchPinned& h) {
+//
+// MIS_MATCH_AFFINE_PARTIAL (AffineBestOf2NearestMatcher::match): ONE chain on the main stream -- the first estimation's two phases,
+// each with the masks and the refinement of the problems that end in it.  There is no second estimation, so no second_calls_kernel
+// and no side chain; the third stream only packs the match lists.  mis_match_knn_fence releases at the end of the 2-NN pass for
+// this model (ev_knn: there is no side chain's first draw to wait for, and the chain's kernels are short).
+int enqueue_chains(MisContext* ctx, MatchWorkspace* ws, int np, const MisMatchParams* p, int model, const MatchDev& d, const MatchPinned& h) {
     hipStream_t st = ctx->stream;
     int rc;
     if (!ws->side && (rc = mis_aux_stream(ctx, 0, &ws->side)) != MIS_OK) return rc;
     trace_mark(ws, 0, st);
     if (!ws->third && (rc = mis_aux_stream(ctx, 1, &ws->third)) != MIS_OK) return rc;
-    const HomoParams prm{p->ransac_thresh, p->max_iters, p->confidence};
     // the match lists are final once the ratio test has run: their download (megabytes) goes to the third stream now, under the
     // RANSAC chains, instead of behind them (0.3 ms at the end of the call); pair k's matches land at the sum of the counts before it
     MIS_HIP(ctx, hipEventRecord(ws->ev_matches.ev, st));
     MIS_HIP(ctx, hipStreamWaitEvent(ws->third, ws->ev_matches.ev, 0));
     hipLaunchKernelGGL(pack_lists_kernel, dim3(np), dim3(256), 0, ws->third, (const PairDesc*)d.pairs, np, (const int*)d.nm, (const MisDMatch*)d.matches, h.m, h.nm);
     MIS_HIP(ctx, hipEventRecord(ws->ev_lists.ev, ws->third));
+    if (model == MIS_MATCH_AFFINE_PARTIAL) {
+        const HomoParams aprm{p->ransac_thresh, p->max_iters, p->confidence, MODEL_AFFINE_PARTIAL, 10};
+        for (RansacPhase ph : {PHASE_FIRST, PHASE_SECOND})
+            if ((rc = homo_phase(ctx, &ws->b1, aprm, ph, st)) != MIS_OK || (rc = homo_tails(ctx, &ws->b1, aprm, ph, TAIL_MASK, st)) != MIS_OK ||
+                (rc = homo_tails(ctx, &ws->b1, aprm, ph, TAIL_REFINE, st)) != MIS_OK) return rc;
+        MIS_HIP(ctx, hipStreamWaitEvent(st, ws->ev_lists.ev, 0));
+        return MIS_OK;
+    }
+    const HomoParams prm{p->ransac_thresh, p->max_iters, p->confidence};
     // main chain: first estimation of every pair, RANSAC phase 0 and the inlier masks of the pairs that finish there.  The side
     // stream is idle until then: it draws the second phase's subsets of the few-match pairs meanwhile (0.19 ms of one workgroup
     // per pair that stood between the two phases).  Diagnostics: the ends of that draw and of the main chain's second one
@@ -1001,19 +1015,20 @@ int enqueue_chains(MisContext* ctx, MatchWorkspace* ws, int np, const MisMatchPa
 }
 
 // the small per-pair results into the pinned staging, behind the chains
-void enqueue_results(MatchWorkspace* ws, int np, size_t m_total, const MatchDev& d, const MatchPinned& h, hipStream_t st) {
+void enqueue_results(MatchWorkspace* ws, int np, size_t m_total, const MatchDev& d, const MatchPinned& h, hipStream_t st, int model) {
     CopySegs cs{};
     const void* srcs[6] = {d.out, ws->b1.results, ws->b2.results, ws->b3.results, ws->b1.fin, d.mask};
     void* dsts[6] = {h.out, h.r1, h.r2, h.r3, h.fin, h.mask};
     const size_t sizes[6] = {sizeof(PairOut) * np, sizeof(HomoResult) * np, sizeof(HomoResult) * np, sizeof(HomoResult) * np, sizeof(int) * np, m_total};
     cs.n = 6;
-    for (int k = 0; k < 6; k++) { cs.src[k] = (const uint8_t*)srcs[k]; cs.dst[k] = (uint8_t*)dsts[k]; cs.bytes[k] = (unsigned)sizes[k]; }
+    // (the affine model has no second estimation: b2 / b3 hold nothing of such a call, their segments stay empty)
+    for (int k = 0; k < 6; k++) { cs.src[k] = (const uint8_t*)srcs[k]; cs.dst[k] = (uint8_t*)dsts[k]; cs.bytes[k] = model == MIS_MATCH_AFFINE_PARTIAL && (k == 2 || k == 3) ? 0u : (unsigned)sizes[k]; }
     hipLaunchKernelGGL(copy_segments_kernel, dim3(64), dim3(256), 0, st, cs);
 }
 
 // MatchesInfo (host), part 1 under the RANSAC chains: the match lists (packed by pack_lists_kernel) and their mirrors; part 2
 // once the device is done (*ts: then): masks, H, confidence, the mirror entry with H^-1 and swapped indices
-int assemble_matches(MisContext* ctx, MatchWorkspace* ws, const MatchPlan& pl, const MatchPinned& h, int n, MisMatchesInfo* out,
+int assemble_matches(MisContext* ctx, MatchWorkspace* ws, const MatchPlan& pl, const MatchPinned& h, int n, int model, MisMatchesInfo* out,
                      std::chrono::steady_clock::time_point* ts) {
     const int np = (int)pl.pairs.size();
     // an error after the lists exist must not leave half-built entries behind: `out` goes back to its zeroed state
@@ -1051,6 +1066,27 @@ int assemble_matches(MisContext* ctx, MatchWorkspace* ws, const MatchPlan& pl, c
         if (po.ran_ransac) {
             a->inliers_mask = (uint8_t*)malloc((size_t)nm + 1);
             memcpy(a->inliers_mask, h.mask + pd.m_off, (size_t)nm);
+        }
+        if (model == MIS_MATCH_AFFINE_PARTIAL) {
+            // AffineBestOf2NearestMatcher::match: no model -> confidence 0, no inliers, no H.  Otherwise the mask's count and
+            // num_inliers / (8 + 0.3 matches) -- the "> 3" zeroing is commented out in OpenCV --, no |det H| test, no second
+            // estimation; H is [a -b tx; b a ty] extended by the row (0, 0, 1)
+            const HomoResult& ar = h.r1[k];
+            a->has_H = po.ran_ransac ? ar.ok : 0;
+            if (a->has_H) {
+                memcpy(a->H, ar.H, sizeof(a->H));
+                a->num_inliers = ar.ninl;
+                a->confidence = a->num_inliers / (8 + 0.3 * nm);
+            }
+            *b = *a;
+            b->src_img_idx = pd.j; b->dst_img_idx = pd.i;
+            b->matches = bm;
+            if (a->inliers_mask) {
+                b->inliers_mask = (uint8_t*)malloc((size_t)nm + 1);
+                memcpy(b->inliers_mask, a->inliers_mask, (size_t)nm);
+            }
+            if (a->has_H) invert3(a->H, b->H);
+            continue;
         }
         // matchers.cpp: "if (H.empty() || |det H| < eps) return" after the first estimation.  The second estimation runs
         // without waiting for the refined H, and a degenerate first H drops it here (same expression, same rounding: no FMA contraction)
@@ -1092,9 +1128,10 @@ void trace_report(MatchWorkspace* ws, std::chrono::steady_clock::time_point t_be
             ms(1), ms(6), ms(2), ms(3), ms(4), ms(5));
 }
 
-int match_impl(MisContext* ctx, const MisFeatures* feats, int n, const MisMatchParams* p, const uint8_t* mask, int range_width, int rank, int world,
+int match_impl(MisContext* ctx, const MisFeatures* feats, int n, const MisMatchParams* p, int model, const uint8_t* mask, int range_width, int rank, int world,
                MisMatchesInfo* out) {
     MIS_CHECK(ctx, feats && p && out && n >= 1, MIS_E_INVALID, "null argument");
+    MIS_CHECK(ctx, model == MIS_MATCH_HOMOGRAPHY || model == MIS_MATCH_AFFINE_PARTIAL, MIS_E_UNSUPPORTED, "unknown matcher model %d (MIS_MATCH_HOMOGRAPHY, MIS_MATCH_AFFINE_PARTIAL)", model);
     MIS_CHECK(ctx, world >= 1 && rank >= 0 && rank < world, MIS_E_INVALID, "bad rank / world size");
     MIS_CHECK(ctx, range_width == -1 || range_width >= 1, MIS_E_INVALID, "range_width must be -1 (all pairs) or >= 1");
     MIS_HIP(ctx, hipSetDevice(ctx->device));
@@ -1131,19 +1168,19 @@ int match_impl(MisContext* ctx, const MisFeatures* feats, int n, const MisMatchP
     MIS_HIP(ctx, hipEventRecord(ws->ev_knn.ev, st));
     ws->ev_gate = ws->ev_knn.ev;
     hipLaunchKernelGGL(ratio_union_kernel, dim3(np), dim3(1024), 0, st, (const FeatDev*)d.feats, (const PairDesc*)d.pairs, (const int*)d.idx,
-                       (const float*)d.dist, 1.f - p->match_conf, d.matches, d.src, d.dst, d.nm);
+                       (const float*)d.dist, 1.f - p->match_conf, d.matches, d.src, d.dst, d.nm, model == MIS_MATCH_HOMOGRAPHY ? 1 : 0);
     hipLaunchKernelGGL(first_calls_kernel, dim3((np + 127) / 128), dim3(128), 0, st, (const PairDesc*)d.pairs, np, (const int*)d.nm, (const float*)d.src,
                        (const float*)d.dst, d.mask, p->num_matches_thresh1, ws->b1.calls, d.out);
     // the chains fork to the context's auxiliary streams, shared with the feature finders: an error in there must not leave them
     // with work pending or a copy in flight
-    if ((rc = enqueue_chains(ctx, ws, np, p, d, h)) != MIS_OK) {
+    if ((rc = enqueue_chains(ctx, ws, np, p, model, d, h)) != MIS_OK) {
         if (ws->side) hipStreamSynchronize(ws->side);
         if (ws->third) hipStreamSynchronize(ws->third);
         hipStreamSynchronize(st);
         return rc;
     }
     MIS_HIP(ctx, hipGetLastError());
-    enqueue_results(ws, np, pl.m_total, d, h, st);
+    enqueue_results(ws, np, pl.m_total, d, h, st, model);
     // everything of this call is enqueued: a thread waiting in mis_match_knn_fence may start launching now without
     // competing with this one for the runtime's launch path
     ws->knn_seq.store(seq_guard.seq);
@@ -1158,8 +1195,8 @@ int match_impl(MisContext* ctx, const MisFeatures* feats, int n, const MisMatchP
     }
     const auto tq = std::chrono::steady_clock::now();
     std::chrono::steady_clock::time_point ts;
-    if ((rc = assemble_matches(ctx, ws, pl, h, n, out, &ts)) != MIS_OK) return rc;
-    if (match_trace()) trace_report(ws, t_begin, tq, ts);
+    if ((rc = assemble_matches(ctx, ws, pl, h, n, model, out, &ts)) != MIS_OK) return rc;
+    if (match_trace() && model == MIS_MATCH_HOMOGRAPHY) trace_report(ws, t_begin, tq, ts);      // (the chain stamps are the homography chains')
     return MIS_OK;
 }
 
@@ -1211,19 +1248,29 @@ extern "C" void mis_match_default_params(MisMatchParams* p) {
 
 extern "C" int mis_match_all_pairs(MisContext* ctx, const MisFeatures* feats, int n, const MisMatchParams* p, MisMatchesInfo* out) {
     if (!ctx) return MIS_E_INVALID;
-    return match_impl(ctx, feats, n, p, nullptr, -1, 0, 1, out);
+    return match_impl(ctx, feats, n, p, MIS_MATCH_HOMOGRAPHY, nullptr, -1, 0, 1, out);
 }
 
 extern "C" int mis_match_pairs_sharded(MisContext* ctx, const MisFeatures* feats, int n, const MisMatchParams* p, int rank, int world,
                                        MisMatchesInfo* out) {
     if (!ctx) return MIS_E_INVALID;
-    return match_impl(ctx, feats, n, p, nullptr, -1, rank, world, out);
+    return match_impl(ctx, feats, n, p, MIS_MATCH_HOMOGRAPHY, nullptr, -1, rank, world, out);
 }
 
 extern "C" int mis_match_pairs_select(MisContext* ctx, const MisFeatures* feats, int n, const MisMatchParams* p, const uint8_t* mask, int range_width,
                                       int rank, int world, MisMatchesInfo* out) {
     if (!ctx) return MIS_E_INVALID;
-    return match_impl(ctx, feats, n, p, mask, range_width, rank, world, out);
+    return match_impl(ctx, feats, n, p, MIS_MATCH_HOMOGRAPHY, mask, range_width, rank, world, out);
+}
+
+extern "C" void mis_match_affine_default_params(MisMatchParams* p) {
+    if (p) *p = MisMatchParams{0.32f, 6, 6, 3.0, 2000, 0.99};
+}
+
+extern "C" int mis_match_pairs_model(MisContext* ctx, const MisFeatures* feats, int n, const MisMatchParams* p, int model, const uint8_t* mask, int range_width,
+                                     int rank, int world, MisMatchesInfo* out) {
+    if (!ctx) return MIS_E_INVALID;
+    return match_impl(ctx, feats, n, p, model, mask, range_width, rank, world, out);
 }
 
 extern "C" int mis_matches_free(MisMatchesInfo* m, int count) {
@@ -1303,6 +1350,39 @@ extern "C" int mis_find_homography(MisContext* ctx, const float* src, const floa
     MIS_HIP(ctx, hipStreamSynchronize(st));
     *ok = r.ok;
     if (r.ok) memcpy(H, r.H, sizeof(r.H)); else memset(H, 0, sizeof(r.H));
+    return MIS_OK;
+}
+
+extern "C" int mis_estimate_affine_partial(MisContext* ctx, const float* src, const float* dst, int n, double thresh, int max_iters, double confidence,
+                                           int refine_iters, double M[6], uint8_t* mask, int* ok) {
+    if (!ctx) return MIS_E_INVALID;
+    MIS_CHECK(ctx, src && dst && M && ok && n >= 0, MIS_E_INVALID, "null argument");
+    MIS_HIP(ctx, hipSetDevice(ctx->device));
+    MatchWorkspace* ws = workspace(ctx);
+    hipStream_t st = ctx->stream;
+    MIS_HIP(ctx, hipStreamSynchronize(st));
+    const size_t nn = (size_t)std::max(n, 1);
+    Carver dc;
+    const size_t o_src = dc.take(sizeof(float) * 2 * nn), o_dst = dc.take(sizeof(float) * 2 * nn), o_mask = dc.take(nn);
+    MIS_HIP(ctx, ws->dev.reserve(dc.off));
+    uint8_t* D = (uint8_t*)ws->dev.p;
+    int rc;
+    if ((rc = homo_batch_reserve(ctx, &ws->b1, 1, (long long)nn, max_iters)) != MIS_OK) return rc;
+    if (n) {
+        MIS_HIP(ctx, hipMemcpyAsync(D + o_src, src, sizeof(float) * 2 * n, hipMemcpyHostToDevice, st));
+        MIS_HIP(ctx, hipMemcpyAsync(D + o_dst, dst, sizeof(float) * 2 * n, hipMemcpyHostToDevice, st));
+    }
+    HomoCall c;
+    c.src = (const float*)(D + o_src); c.dst = (const float*)(D + o_dst); c.mask = D + o_mask; c.pt_off = 0; c.n = n; c.active = 1;
+    MIS_HIP(ctx, hipMemcpyAsync(ws->b1.calls, &c, sizeof(c), hipMemcpyHostToDevice, st));
+    MIS_HIP(ctx, hipStreamSynchronize(st));  // `c` lives on this stack frame
+    if ((rc = homo_solve(ctx, &ws->b1, HomoParams{thresh, max_iters, confidence, MODEL_AFFINE_PARTIAL, refine_iters})) != MIS_OK) return rc;
+    HomoResult r;
+    MIS_HIP(ctx, hipMemcpyAsync(&r, ws->b1.results, sizeof(r), hipMemcpyDeviceToHost, st));
+    if (mask && n) MIS_HIP(ctx, hipMemcpyAsync(mask, D + o_mask, n, hipMemcpyDeviceToHost, st));
+    MIS_HIP(ctx, hipStreamSynchronize(st));
+    *ok = r.ok;
+    if (r.ok) memcpy(M, r.H, sizeof(double) * 6); else memset(M, 0, sizeof(double) * 6);
     return MIS_OK;
 }
 

@@ -155,6 +155,7 @@ class HipEngine:
         self.warp_type = self.cfg.warp_type            # the warper this engine runs (StitchJob checks it against the job's)
         self.kind = st.check_warp_config(self.cfg)
         self.range_width = st.check_range_config(self.cfg)      # the pair selection this engine's matcher makes (StitchJob checks it against the job's)
+        self.matcher_type = st.check_matcher_config(self.cfg)   # the matcher's motion model (StitchJob checks it against the job's)
         self.frame_size = frame_size
         # features come from the work image (image_stitching.cpp:589-603, :613): the finder is sized for it, and the work frames
         # live in buffers allocated on first use and kept (an allocation per run would synchronise the device)
@@ -459,6 +460,7 @@ class StitchJob:
         st.check_seam_config(self.cfg)
         self.kind = st.check_warp_config(self.cfg)
         st.check_range_config(self.cfg)
+        st.check_matcher_config(self.cfg)
         self.engine = engine or HipEngine(ctx, frame_size, self.cfg)
         # an engine warps one kind (its own config's; spherical when it does not say): never another than the job's
         engine_warp = getattr(self.engine, "warp_type", "spherical")
@@ -468,6 +470,11 @@ class StitchJob:
         engine_range = getattr(self.engine, "range_width", -1)
         if engine_range != self.cfg.range_width:
             raise NotImplementedError("range_width %r: the engine %s matches with range_width %r only" % (self.cfg.range_width, type(self.engine).__name__, engine_range))
+        # matcher_type (:64, :644-645): the engine's matcher estimates one motion model; an engine that does not declare one runs
+        # the homography matcher
+        engine_matcher = getattr(self.engine, "matcher_type", "homography")
+        if engine_matcher != self.cfg.matcher_type:
+            raise NotImplementedError("matcher_type %r: the engine %s matches with matcher_type %r only" % (self.cfg.matcher_type, type(self.engine).__name__, engine_matcher))
         # work scale (image_stitching.cpp:589-603): the engine detects on resized frames and everything between features and
         # composition is in work units; an engine that does not resize is refused, not run at full resolution
         self.work_scale, self.work_size = st.work_geometry(self.cfg, frame_size)

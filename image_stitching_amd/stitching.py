@@ -872,6 +872,7 @@ class BestOf2NearestMatcher:
                                    num_matches_thresh2=num_matches_thresh2)
 
     range_width = -1
+    model = capi.MATCH_HOMOGRAPHY
 
     def __call__(self, features, rank=0, world_size=1, mask=None):
         """(*matcher)(features, pairwise_matches, mask) -> list of n*n MatchesInfo (row-major).  mask: n x n, non-zero at (i, j),
@@ -886,7 +887,10 @@ class BestOf2NearestMatcher:
         for k, f in enumerate(features):
             C.memmove(C.byref(arr[k]), C.byref(f.raw), C.sizeof(capi.MisFeatures))
         mis = (capi.MisMatchesInfo * (n * n))()
-        if mask is not None or self.range_width != -1:
+        if self.model != capi.MATCH_HOMOGRAPHY:
+            rc = self.ctx.lib.mis_match_pairs_model(self.ctx.h, arr, n, C.byref(self.params), int(self.model),
+                                                    None if mask is None else mask.ctypes.data_as(C.c_void_p), int(self.range_width), rank, world_size, mis)
+        elif mask is not None or self.range_width != -1:
             rc = self.ctx.lib.mis_match_pairs_select(self.ctx.h, arr, n, C.byref(self.params), None if mask is None else mask.ctypes.data_as(C.c_void_p),
                                                      int(self.range_width), rank, world_size, mis)
         elif world_size == 1:
@@ -909,8 +913,46 @@ class BestOf2NearestRangeMatcher(BestOf2NearestMatcher):
         self.range_width = int(range_width)
 
 
+class AffineBestOf2NearestMatcher(BestOf2NearestMatcher):
+    """makePtr<AffineBestOf2NearestMatcher>(false, try_cuda, match_conf) (image_stitching.cpp:645): the 2-NN and ratio test of
+    BestOf2NearestMatcher, then cv::estimateAffinePartial2D on the keypoint positions as they are (threshold 3, 2000 iterations,
+    confidence 0.99, 10 refinement iterations); confidence = inliers / (8 + 0.3 matches), never zeroed; no second estimation.
+    full_affine=True (cv::estimateAffine2D) is not built: the reference hard-codes false."""
+    model = capi.MATCH_AFFINE_PARTIAL
+
+    def __init__(self, ctx, full_affine=False, match_conf=0.3, num_matches_thresh1=6):
+        if full_affine:
+            raise NotImplementedError("AffineBestOf2NearestMatcher(full_affine=True): cv::estimateAffine2D is not built, only the "
+                                      "affine-partial model the reference uses (image_stitching.cpp:645; DESIGN.md section 8)")
+        self.ctx = ctx
+        p = capi.MisMatchParams()
+        capi.load().mis_match_affine_default_params(C.byref(p))
+        p.match_conf = match_conf
+        p.num_matches_thresh1 = num_matches_thresh1
+        self.params = p
+
+
+MATCHER_TYPES = ("homography", "affine")
+
+
+def check_matcher_config(cfg):
+    """matcher_type of the config (image_stitching.cpp:64, :644-649): 'homography' or 'affine', else ValueError by name before any
+    device work.  'affine' with a range_width is refused too: the reference silently ignores range_width there (:644 comes first),
+    and no option is ignored silently here."""
+    mt = getattr(cfg, "matcher_type", "homography")
+    if mt not in MATCHER_TYPES:
+        raise ValueError("matcher_type %r: 'homography' or 'affine' (image_stitching.cpp:64, :644-649)" % (mt,))
+    if mt == "affine" and cfg.range_width != -1:
+        raise ValueError("matcher_type 'affine' with range_width %r: AffineBestOf2NearestMatcher matches all pairs "
+                         "(image_stitching.cpp:644-645 ignores range_width); set range_width = -1" % (cfg.range_width,))
+    return mt
+
+
 def make_matcher(ctx, cfg):
-    """if (range_width == -1) BestOf2NearestMatcher else BestOf2NearestRangeMatcher (image_stitching.cpp:646-649)"""
+    """if (matcher_type == "affine") AffineBestOf2NearestMatcher(false, ...) else if (range_width == -1) BestOf2NearestMatcher
+    else BestOf2NearestRangeMatcher (image_stitching.cpp:644-649)"""
+    if check_matcher_config(cfg) == "affine":
+        return AffineBestOf2NearestMatcher(ctx, False, cfg.match_conf)
     if cfg.range_width == -1:
         return BestOf2NearestMatcher(ctx, cfg.match_conf)
     return BestOf2NearestRangeMatcher(ctx, cfg.range_width, cfg.match_conf)
@@ -1033,6 +1075,21 @@ def find_homography(ctx, src, dst, thresh=3.0, max_iters=2000, confidence=0.995)
     return bool(ok.value), H.reshape(3, 3), mask[:n]
 
 
+def estimate_affine_partial(ctx, src, dst, thresh=3.0, max_iters=2000, confidence=0.99, refine_iters=10):
+    """cv::estimateAffinePartial2D(src, dst, mask, RANSAC, ...) on the GPU -> (ok, M 2 x 3 = [a -b tx; b a ty], mask)."""
+    src = np.ascontiguousarray(src, np.float32).reshape(-1, 2)
+    dst = np.ascontiguousarray(dst, np.float32).reshape(-1, 2)
+    n = src.shape[0]
+    if dst.shape[0] != n:
+        raise ValueError("src and dst must hold the same number of points")
+    M = np.zeros(6, np.float64)
+    mask = np.zeros(max(n, 1), np.uint8)
+    ok = C.c_int()
+    ctx.check(ctx.lib.mis_estimate_affine_partial(ctx.h, src.ctypes.data_as(C.c_void_p), dst.ctypes.data_as(C.c_void_p), n, thresh, max_iters,
+                                                  confidence, refine_iters, M.ctypes.data_as(C.c_void_p), mask.ctypes.data_as(C.c_void_p), C.byref(ok)))
+    return bool(ok.value), M.reshape(2, 3), mask[:n]
+
+
 # ------------------------------------------------------------------------------------------------
 def check_warp_config(cfg):
     """warp_type of the config -> MIS_WARP_* kind, or NotImplementedError / ValueError by name before any device work."""
@@ -1150,6 +1207,7 @@ class StitchConfig:
     features_type: str = "orb"
     match_conf: float = 0.32
     range_width: int = -1             # -1: all pairs; w >= 1: BestOf2NearestRangeMatcher, pairs with j < i + w only (:83, :646-649)
+    matcher_type: str = "homography"  # "homography" | "affine": AffineBestOf2NearestMatcher(false, ...), all pairs (:64, :644-645)
     warp_type: str = "spherical"
     blend_type: int = capi.BLEND_MULTI_BAND
     blend_strength: float = 5.0
@@ -1193,6 +1251,7 @@ class Stitcher:
         self.cfg = config or StitchConfig()
         self.kind = check_warp_config(self.cfg)
         check_range_config(self.cfg)
+        check_matcher_config(self.cfg)
         self.frame_size = frame_size
         # features come from the work image (image_stitching.cpp:602, :613): the finder is sized for it
         self.work_scale, self.work_size = work_geometry(self.cfg, frame_size)

@@ -175,6 +175,21 @@ int mis_match_pairs_sharded(MisContext* ctx, const MisFeatures* feats, int n, co
  * mis_match_all_pairs and mis_match_pairs_sharded are the (NULL, -1) case. */
 int mis_match_pairs_select(MisContext* ctx, const MisFeatures* feats, int n, const MisMatchParams* p, const uint8_t* mask,
                            int range_width, int rank, int world_size, MisMatchesInfo* out);
+/* The matcher's motion model -- the matcher_type switch of image_stitching.cpp:64, :644-649.  MIS_MATCH_HOMOGRAPHY:
+ * BestOf2NearestMatcher / BestOf2NearestRangeMatcher, the three entries above.  MIS_MATCH_AFFINE_PARTIAL:
+ * AffineBestOf2NearestMatcher(full_affine = false, try_cuda, match_conf) of :644-645 -- the same 2-NN and ratio test; the points are
+ * the keypoint positions as they are (not shifted by half the image size); cv::estimateAffinePartial2D (RANSAC, threshold 3,
+ * 2000 iterations, confidence 0.99, 10 refinement iterations) in place of findHomography; num_inliers is its mask's count and
+ * confidence = num_inliers / (8 + 0.3 matches) WITHOUT the "> 3" zeroing; no |det H| test, no second estimation; H is
+ * [a -b tx; b a ty] with the last row exactly (0, 0, 1), the mirrored entry holds its inverse. */
+enum { MIS_MATCH_HOMOGRAPHY = 0, MIS_MATCH_AFFINE_PARTIAL = 1 };
+/* AffineBestOf2NearestMatcher's defaults (:645 with match_conf as mis_match_default_params has it): threshold 3.0, 2000 iterations,
+ * confidence 0.99, num_matches_thresh1 6.  num_matches_thresh2 is ignored for this model. */
+void mis_match_affine_default_params(MisMatchParams* p);
+/* mis_match_pairs_select with the model (:644-649): the pair mask, range_width and the sharding are orthogonal to it.  An unknown
+ * model returns MIS_E_UNSUPPORTED.  For MIS_MATCH_AFFINE_PARTIAL mis_match_knn_fence releases at the end of the 2-NN pass. */
+int mis_match_pairs_model(MisContext* ctx, const MisFeatures* feats, int n, const MisMatchParams* p, int model, const uint8_t* mask,
+                          int range_width, int rank, int world_size, MisMatchesInfo* out);
 int mis_matches_free(MisMatchesInfo* m, int count);
 /* Ordering aid for a caller that overlaps other device work with a matcher call made by another host thread (the
  * job's speculative composition): mis_match_sequence = number of matcher calls this context has started;
@@ -194,6 +209,11 @@ int mis_knn2(MisContext* ctx, const MisFeatures* query, const MisFeatures* train
 /* cv::findHomography(src, dst, mask, RANSAC, thresh, max_iters, confidence) on host point lists */
 int mis_find_homography(MisContext* ctx, const float* src_xy, const float* dst_xy, int n, double thresh, int max_iters,
                         double confidence, double H[9], uint8_t* mask, int* ok);
+/* cv::estimateAffinePartial2D(src, dst, mask, RANSAC, thresh, max_iters, confidence, refine_iters) on host point lists -- the
+ * estimator of AffineBestOf2NearestMatcher::match (image_stitching.cpp:644-645); M = [a -b tx; b a ty] row-major.  *ok = 0: no
+ * model (M zeroed, mask zeroed).  refine_iters 0 returns the RANSAC model itself. */
+int mis_estimate_affine_partial(MisContext* ctx, const float* src_xy, const float* dst_xy, int n, double thresh, int max_iters,
+                                double confidence, int refine_iters, double M[6], uint8_t* mask, int* ok);
 /* myLeaveBiggestComponent -- replaces image_stitching.cpp:215-278 (host logic on the matcher output) */
 int mis_leave_biggest_component(const MisMatchesInfo* pairwise, int n, float conf_threshold, int* indices, int* n_indices);
 /* the same on the bare n x n confidence matrix (row-major; what a sharded job has after its all-reduce) */
