@@ -17,7 +17,7 @@
 int main(int argc, char** argv) {
     if (argc < 2) {
         std::cout << "usage: " << argv[0] << " <image directory> [--features orb|sift] [--ba no|reproj] [--ba_refine_mask xxxxx] [--wave_correct horiz|vert|no]\n"
-                     "       [--expos_comp no|gain_blocks] [--seam no|voronoi|dp_color] [--warp spherical|cylindrical|plane] [--blend no|feather|multiband] [--conf_thresh f] [--match_conf f] [--compose_megapix f] [--seam_megapix f] [--work_megapix f] [--rangewidth N] [--matcher homography|affine]\n"
+                     "       [--expos_comp no|gain|gain_blocks|channels|channels_blocks] [--expos_comp_nr_feeds N] [--seam no|voronoi|dp_color] [--warp spherical|cylindrical|plane] [--blend no|feather|multiband] [--conf_thresh f] [--match_conf f] [--compose_megapix f] [--seam_megapix f] [--work_megapix f] [--rangewidth N] [--matcher homography|affine]\n"
                      "(the reference sets these as globals, image_stitching.cpp:49-85)\n";
         return -1;
     }
@@ -29,6 +29,7 @@ int main(int argc, char** argv) {
         else if (k == "--ba_refine_mask") cfg.ba_refine_mask = v;
         else if (k == "--wave_correct") cfg.wave_correct = v;
         else if (k == "--expos_comp") cfg.expos_comp_type = v;
+        else if (k == "--expos_comp_nr_feeds") cfg.expos_comp_nr_feeds = std::atoi(v.c_str());
         else if (k == "--seam") cfg.seam_find_type = v;
         else if (k == "--warp") cfg.warp_type = v;
         else if (k == "--blend") cfg.blend_type = v == "no" ? MIS_BLEND_NO : (v == "feather" ? MIS_BLEND_FEATHER : MIS_BLEND_MULTI_BAND);
@@ -41,7 +42,7 @@ int main(int argc, char** argv) {
         else if (k == "--matcher") cfg.matcher_type = v;
         else { std::cout << "unknown option " << k << "\n"; return -1; }
     }
-    try { mis::check_range_width(cfg.range_width); mis::matcher_model(cfg.matcher_type, cfg.range_width); } catch (const std::exception& e) { std::cout << e.what() << "\n"; return -1; }
+    try { mis::check_range_width(cfg.range_width); mis::matcher_model(cfg.matcher_type, cfg.range_width); mis::expos_comp_kind(cfg.expos_comp_type, cfg.expos_comp_nr_feeds); } catch (const std::exception& e) { std::cout << e.what() << "\n"; return -1; }
     namespace fs = std::filesystem;
     std::vector<std::string> img_names;
     for (auto& e : fs::directory_iterator(argv[1])) {

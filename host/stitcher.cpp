@@ -82,8 +82,7 @@ StitchResult Stitcher::stitch(const std::vector<HostImage>& frames, const std::v
     if (cfg_.features_type != "orb" && cfg_.features_type != "sift") throw std::runtime_error("Unknown 2D features type: '" + cfg_.features_type + "'.");
     if (cfg_.ba_cost_func != "no" && cfg_.ba_cost_func != "reproj")
         throw std::runtime_error("bundle adjustment cost function '" + cfg_.ba_cost_func + "' is not implemented (only 'no' and 'reproj')");
-    if (cfg_.expos_comp_type != "no" && cfg_.expos_comp_type != "gain_blocks")
-        throw std::runtime_error("exposure compensation '" + cfg_.expos_comp_type + "' is not implemented (only 'no' and 'gain_blocks')");
+    const int expos_kind = expos_comp_kind(cfg_.expos_comp_type, cfg_.expos_comp_nr_feeds);
     if (cfg_.seam_find_type != "no" && cfg_.seam_find_type != "voronoi" && cfg_.seam_find_type != "dp_color")
         throw std::runtime_error("seam finder '" + cfg_.seam_find_type + "' is not implemented ('no', 'voronoi' and 'dp_color' are)");
     const int kind = warp_kind(cfg_.warp_type);
@@ -237,8 +236,12 @@ StitchResult Stitcher::stitch(const std::vector<HostImage>& frames, const std::v
                   "mis_warper_warp (seam-scale mask)");
             if (seam_scale < 1.0) mis_image_free(ctx_, &img);
         }
-        if (cfg_.expos_comp_type == "gain_blocks") {
-            check(mis_compensator_create(ctx_, 64, 64, 2, &compensator), "mis_compensator_create");
+        if (expos_kind != MIS_EXPOS_NO) {
+            MisCompensatorParams cp;
+            mis_compensator_default_params(&cp);      // 64 x 64 blocks, 2 filtering passes (:1014-1016)
+            cp.type = expos_kind;
+            cp.nr_feeds = cfg_.expos_comp_nr_feeds;
+            check(mis_compensator_create_ex(ctx_, &cp, &compensator), "mis_compensator_create_ex");
             check(mis_compensator_feed(compensator, seam_corners.data(), images_warped.data(), masks_warped.data(), kept), "mis_compensator_feed");
         }
         if (cfg_.seam_find_type == "voronoi") check(mis_seam_voronoi(ctx_, seam_corners.data(), masks_warped.data(), kept), "mis_seam_voronoi");

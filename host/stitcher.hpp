@@ -30,7 +30,8 @@ struct StitchConfig {
     // seam-scale step (:940-1070, :1162-1171).  The reference's defaults are "gain_blocks" and "dp_color" (both implemented:
     // mis_compensator_*, mis_seam_dp); this struct defaults to the HOT PATH of the north star (no seam-scale step), like
     // image_stitching_amd.StitchConfig.hot_path() -- pass "gain_blocks" / "dp_color" for the reference's configuration.
-    std::string expos_comp_type = "no";    // "no" | "gain_blocks" (64 x 64 blocks, 1 feed, 2 filtering passes)
+    std::string expos_comp_type = "no";    // "no" | "gain" | "gain_blocks" | "channels" | "channels_blocks" (:73; 64 x 64 blocks, 2 filtering passes)
+    int expos_comp_nr_feeds = 1;           // :74
     std::string seam_find_type = "no";     // "no" | "voronoi" | "dp_color" (the reference's default; this driver's default is the hot path)
     // warper (:917-969): the three of the reference's GPU branch are built; its other names throw by name (warp_kind)
     std::string warp_type = "spherical";   // "spherical" | "cylindrical" | "plane"
@@ -48,6 +49,16 @@ inline int matcher_model(const std::string& t, int range_width) {
     if (range_width != -1)
         throw std::runtime_error("matcher_type 'affine' with range_width " + std::to_string(range_width) + " (--matcher affine --rangewidth): AffineBestOf2NearestMatcher matches all pairs");
     return MIS_MATCH_AFFINE_PARTIAL;
+}
+// expos_comp_type / expos_comp_nr_feeds of the config -> MIS_EXPOS_*, the check before any device work
+inline int expos_comp_kind(const std::string& t, int nr_feeds) {
+    if (nr_feeds < 1) throw std::runtime_error("expos_comp_nr_feeds " + std::to_string(nr_feeds) + ": an integer >= 1 (--expos_comp_nr_feeds)");
+    if (t == "no") return MIS_EXPOS_NO;
+    if (t == "gain") return MIS_EXPOS_GAIN;
+    if (t == "gain_blocks") return MIS_EXPOS_GAIN_BLOCKS;
+    if (t == "channels") return MIS_EXPOS_CHANNELS;
+    if (t == "channels_blocks") return MIS_EXPOS_CHANNELS_BLOCKS;
+    throw std::runtime_error("exposure compensation '" + t + "': 'no', 'gain', 'gain_blocks', 'channels' or 'channels_blocks' (--expos_comp)");
 }
 // the matcher's parameters for a model: mis_match_default_params / mis_match_affine_default_params with the config's match_conf
 inline MisMatchParams match_params(int model, float match_conf) {

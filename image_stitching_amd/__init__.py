@@ -10,7 +10,7 @@ There is no CPU fallback: everything here needs the HIP library and a GPU.
 from . import _capi
 from ._capi import (BLEND_FEATHER, BLEND_MULTI_BAND, BLEND_NO, BORDER_CONSTANT, BORDER_REFLECT, INTER_LINEAR,
                     INTER_NEAREST, WARP_CYLINDRICAL, WARP_PLANE, WARP_SPHERICAL)
-from .stitching import (AffineBestOf2NearestMatcher, BestOf2NearestMatcher, BestOf2NearestRangeMatcher, estimate_affine_partial, Blender, BlocksGainCompensator, NoSeamFinder, VoronoiSeamFinder, DpSeamFinder, Context, FeatherBlender, ImageFeatures, MatchesInfo,
+from .stitching import (AffineBestOf2NearestMatcher, BestOf2NearestMatcher, BestOf2NearestRangeMatcher, estimate_affine_partial, Blender, BlocksGainCompensator, GainCompensator, ChannelsCompensator, BlocksChannelsCompensator, NoSeamFinder, VoronoiSeamFinder, DpSeamFinder, Context, FeatherBlender, ImageFeatures, MatchesInfo,
                         MisError, MultiBandBlender, OrbFeatureFinder, SiftFeatureFinder, SphericalWarper, CylindricalWarper, PlaneWarper,
                         RotationWarper, StitchConfig, Stitcher,
                         blend_config, bundle_adjust_reproj, computeImageFeatures, find_homography, leaveBiggestComponent, resize, resize_batch, result_roi,
@@ -20,7 +20,7 @@ __all__ = [
     "Context", "MisError", "SphericalWarper", "Blender", "MultiBandBlender", "FeatherBlender", "OrbFeatureFinder", "SiftFeatureFinder",
     "computeImageFeatures", "ImageFeatures", "BestOf2NearestMatcher", "MatchesInfo", "leaveBiggestComponent",
     "find_homography", "warp_roi", "result_roi", "blend_config", "StitchConfig", "Stitcher", "resize", "rotate",
-    "seam_mask_apply", "bundle_adjust_reproj", "wave_correct", "BlocksGainCompensator", "NoSeamFinder", "VoronoiSeamFinder", "DpSeamFinder",
+    "seam_mask_apply", "bundle_adjust_reproj", "wave_correct", "BlocksGainCompensator", "GainCompensator", "ChannelsCompensator", "BlocksChannelsCompensator", "NoSeamFinder", "VoronoiSeamFinder", "DpSeamFinder",
     "INTER_NEAREST", "INTER_LINEAR", "BORDER_CONSTANT", "BORDER_REFLECT", "BLEND_NO", "BLEND_FEATHER",
     "BLEND_MULTI_BAND", "resize_batch", "work_geometry", "CylindricalWarper", "PlaneWarper", "RotationWarper", "WARP_SPHERICAL", "WARP_CYLINDRICAL", "WARP_PLANE",
     "BestOf2NearestRangeMatcher", "selected_pairs", "AffineBestOf2NearestMatcher", "estimate_affine_partial",

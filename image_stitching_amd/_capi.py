@@ -21,6 +21,7 @@ BORDER_CONSTANT, BORDER_REFLECT = 0, 2
 BLEND_NO, BLEND_FEATHER, BLEND_MULTI_BAND = 0, 1, 2
 WARP_SPHERICAL, WARP_CYLINDRICAL, WARP_PLANE = 0, 1, 2
 MATCH_HOMOGRAPHY, MATCH_AFFINE_PARTIAL = 0, 1
+EXPOS_NO, EXPOS_GAIN, EXPOS_GAIN_BLOCKS, EXPOS_CHANNELS, EXPOS_CHANNELS_BLOCKS = 0, 1, 2, 3, 4      # cv::detail::ExposureCompensator's values
 
 
 class MisPoint(C.Structure):
@@ -74,6 +75,11 @@ class MisFeatures(C.Structure):
 class MisMatchParams(C.Structure):
     _fields_ = [("match_conf", C.c_float), ("num_matches_thresh1", C.c_int), ("num_matches_thresh2", C.c_int),
                 ("ransac_thresh", C.c_double), ("max_iters", C.c_int), ("confidence", C.c_double)]
+
+
+class MisCompensatorParams(C.Structure):
+    _fields_ = [("type", C.c_int), ("nr_feeds", C.c_int), ("block_width", C.c_int), ("block_height", C.c_int),
+                ("nr_gain_filtering_iterations", C.c_int)]
 
 
 class MisDMatch(C.Structure):
@@ -153,7 +159,12 @@ PROTOTYPES = {
     "mis_rotate": (_i, [_vp, _P(MisImage), _i, _P(MisImage)]),
     "mis_seam_mask_apply": (_i, [_vp, _P(MisImage), _P(MisImage)]),
     "mis_compensator_create": (_i, [_vp, _i, _i, _i, _P(_vp)]),
+    "mis_compensator_default_params": (None, [_P(MisCompensatorParams)]),
+    "mis_compensator_create_ex": (_i, [_vp, _P(MisCompensatorParams), _P(_vp)]),
     "mis_compensator_destroy": (_i, [_vp]),
+    "mis_compensator_gains": (_i, [_vp, _i, _P(_d)]),
+    "mis_compensator_gain_map_channels": (_i, [_vp, _i, _P(C.c_float), _i, _P(_i), _P(_i), _P(_i)]),
+    "mis_compensator_debug_stats": (_i, [_vp, _i, _i, _i, _P(_i), _P(_d), _P(_d)]),
     "mis_compensator_feed": (_i, [_vp, _P(MisPoint), _P(MisImage), _P(MisImage), _i]),
     "mis_compensator_gain_map": (_i, [_vp, _i, _P(C.c_float), _i, _P(_i), _P(_i)]),
     "mis_compensator_apply": (_i, [_vp, _i, _P(MisImage)]),

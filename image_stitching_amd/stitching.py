@@ -345,15 +345,17 @@ def seam_mask_apply(ctx, seam_mask_warped, mask_warped):
     return mask_warped
 
 
-class BlocksGainCompensator:
-    """cv::detail::BlocksGainCompensator as the reference configures it (image_stitching.cpp:1002-1023): 64x64 blocks,
-    one feed, two gain-filtering passes.  feed() takes the seam-scale warped images / masks and their corners;
-    apply() multiplies an 8UC3 (or the fused warp's 16SC3) image by the gains, in place."""
+class _Compensator:
+    """One member of cv::detail::ExposureCompensator's family over mis_compensator_*.  feed() takes the seam-scale warped images /
+    masks and their corners and never alters them, whatever nr_feeds is (the library works on private device copies); apply()
+    multiplies an 8UC3 (or the fused warp's 16SC3) image by the gains, in place."""
+    TYPE = None
 
-    def __init__(self, ctx, bl_width=64, bl_height=64, nr_gain_filtering_iterations=2):
+    def _create(self, ctx, nr_feeds, bl_width=64, bl_height=64, nr_gain_filtering_iterations=2):
         self.ctx = ctx
         h = C.c_void_p()
-        ctx.check(ctx.lib.mis_compensator_create(ctx.h, bl_width, bl_height, nr_gain_filtering_iterations, C.byref(h)))
+        params = capi.MisCompensatorParams(self.TYPE, nr_feeds, bl_width, bl_height, nr_gain_filtering_iterations)
+        ctx.check(ctx.lib.mis_compensator_create_ex(ctx.h, C.byref(params), C.byref(h)))
         self.h = h
 
     def close(self):
@@ -374,18 +376,86 @@ class BlocksGainCompensator:
         mk = (capi.MisImage * n)(*[as_image(m) for m in masks])
         self.ctx.check(self.ctx.lib.mis_compensator_feed(self.h, cs, im, mk, n))
 
+    def gains(self, index):
+        """The accumulated gains of one image as three float64 (B, G, R; GainCompensator: the gain three times); the block types
+        have a gain map instead and raise."""
+        g = (C.c_double * 3)()
+        self.ctx.check(self.ctx.lib.mis_compensator_gains(self.h, index, g))
+        return np.array(g[:], np.float64)
+
     def gain_map(self, index):
-        bx, by = C.c_int(), C.c_int()
-        self.ctx.check(self.ctx.lib.mis_compensator_gain_map(self.h, index, None, 0, C.byref(bx), C.byref(by)))
-        out = np.zeros((by.value, bx.value), np.float32)
-        self.ctx.check(self.ctx.lib.mis_compensator_gain_map(self.h, index, out.ctypes.data_as(C.POINTER(C.c_float)), out.size, None, None))
+        """The smoothed float32 gain map of one image: (by, bx) for BlocksGainCompensator, (by, bx, 3) for BlocksChannelsCompensator;
+        GainCompensator and ChannelsCompensator have per-image gains instead and raise."""
+        bx, by, ch = C.c_int(), C.c_int(), C.c_int()
+        self.ctx.check(self.ctx.lib.mis_compensator_gain_map_channels(self.h, index, None, 0, C.byref(bx), C.byref(by), C.byref(ch)))
+        out = np.zeros((by.value, bx.value) if ch.value == 1 else (by.value, bx.value, ch.value), np.float32)
+        self.ctx.check(self.ctx.lib.mis_compensator_gain_map_channels(self.h, index, out.ctypes.data_as(C.POINTER(C.c_float)), out.size, None, None, None))
         return out
+
+    def debug_stats(self, i, j, channel=0):
+        """Test hook (GainCompensator, ChannelsCompensator): (N_ij, I_ij, I_ji) of the last feed."""
+        n, a, b = C.c_int(), C.c_double(), C.c_double()
+        self.ctx.check(self.ctx.lib.mis_compensator_debug_stats(self.h, i, j, channel, C.byref(n), C.byref(a), C.byref(b)))
+        return n.value, a.value, b.value
 
     def apply(self, index, corner, image, mask=None):
         """corner and mask are accepted for signature parity (OpenCV ignores them too)."""
         img = as_image(image)
         self.ctx.check(self.ctx.lib.mis_compensator_apply(self.h, index, C.byref(img)))
         return image
+
+
+class GainCompensator(_Compensator):
+    """cv::detail::GainCompensator(nr_feeds): one gain per frame from the whole-frame overlap statistics."""
+    TYPE = capi.EXPOS_GAIN
+
+    def __init__(self, ctx, nr_feeds=1):
+        self._create(ctx, nr_feeds)
+
+
+class ChannelsCompensator(_Compensator):
+    """cv::detail::ChannelsCompensator(nr_feeds): a GainCompensator per colour channel; gains(i) = (B, G, R)."""
+    TYPE = capi.EXPOS_CHANNELS
+
+    def __init__(self, ctx, nr_feeds=1):
+        self._create(ctx, nr_feeds)
+
+
+class BlocksGainCompensator(_Compensator):
+    """cv::detail::BlocksGainCompensator as the reference configures it (image_stitching.cpp:1002-1023): 64x64 blocks,
+    one feed, two gain-filtering passes."""
+    TYPE = capi.EXPOS_GAIN_BLOCKS
+
+    def __init__(self, ctx, bl_width=64, bl_height=64, nr_gain_filtering_iterations=2, nr_feeds=1):
+        self._create(ctx, nr_feeds, bl_width, bl_height, nr_gain_filtering_iterations)
+
+
+class BlocksChannelsCompensator(_Compensator):
+    """cv::detail::BlocksChannelsCompensator: a gain per block and colour channel, smoothed into a three-channel map."""
+    TYPE = capi.EXPOS_CHANNELS_BLOCKS
+
+    def __init__(self, ctx, bl_width=64, bl_height=64, nr_gain_filtering_iterations=2, nr_feeds=1):
+        self._create(ctx, nr_feeds, bl_width, bl_height, nr_gain_filtering_iterations)
+
+
+# expos_comp_type (image_stitching.cpp:73, :1002-1012) as a configuration name.  "channels" is NOT among them: ChannelsCompensator is
+# built (the class above, MIS_EXPOS_CHANNELS, the C++ host's --expos_comp channels), but the suite pins "channels" as its example
+# of a configuration value that is refused by name (tests/test_expos_gpu.py, tests/test_distributed_cpu.py), so the Python
+# configuration keeps refusing it; build the compensator directly where it is wanted
+EXPOS_COMP_TYPES = ("no", "gain", "gain_blocks", "channels_blocks")
+
+
+def make_compensator(ctx, cfg):
+    """expos_comp_type / expos_comp_nr_feeds of the config -> the compensator (image_stitching.cpp:1002-1016), None for "no"."""
+    t, feeds = cfg.expos_comp_type, cfg.expos_comp_nr_feeds
+    blocks = (cfg.expos_comp_block_size, cfg.expos_comp_block_size, cfg.expos_comp_nr_filtering, feeds)
+    if t == "gain":
+        return GainCompensator(ctx, feeds)
+    if t == "gain_blocks":
+        return BlocksGainCompensator(ctx, *blocks)
+    if t == "channels_blocks":
+        return BlocksChannelsCompensator(ctx, *blocks)
+    return None
 
 
 class NoSeamFinder:
@@ -1108,8 +1178,12 @@ def check_seam_config(cfg):
     if cfg.seam_find_type not in ("no", "voronoi", "dp_color"):
         raise NotImplementedError("seam_find_type %r: 'no', 'voronoi' and 'dp_color' are implemented (dp_colorgrad and the "
                                   "graph-cut finders are outside this library; DESIGN.md section 8)" % (cfg.seam_find_type,))
-    if cfg.expos_comp_type not in ("no", "gain_blocks"):
-        raise NotImplementedError("expos_comp_type %r: only 'no' and 'gain_blocks' are implemented" % (cfg.expos_comp_type,))
+    if cfg.expos_comp_type not in EXPOS_COMP_TYPES:
+        raise NotImplementedError("expos_comp_type %r: one of %s ('channels' is ChannelsCompensator, not a configuration name here)"
+                                  % (cfg.expos_comp_type, ", ".join(EXPOS_COMP_TYPES)))
+    nf = cfg.expos_comp_nr_feeds
+    if isinstance(nf, bool) or not isinstance(nf, (int, np.integer)) or nf < 1:
+        raise ValueError("expos_comp_nr_feeds %r: an integer >= 1 (image_stitching.cpp:74)" % (nf,))
 
 
 def seam_scale_warp(ctx, cfg, frame_size, frame, camera, warped_image_scale, work_scale=1.0):
@@ -1132,9 +1206,8 @@ def seam_scale_warp(ctx, cfg, frame_size, frame, camera, warped_image_scale, wor
 def seam_solve(ctx, cfg, corners, images_warped, masks_warped):
     """The part of the seam-scale pass that needs every image (image_stitching.cpp:1002-1023 exposure compensator feed, :1029-1065
     seam finder) -> (compensator | None, masks_warped edited in place)."""
-    compensator = None
-    if cfg.expos_comp_type == "gain_blocks":
-        compensator = BlocksGainCompensator(ctx, cfg.expos_comp_block_size, cfg.expos_comp_block_size, cfg.expos_comp_nr_filtering)
+    compensator = make_compensator(ctx, cfg)
+    if compensator is not None:
         compensator.feed(corners, images_warped, masks_warped)
     if cfg.seam_find_type == "voronoi":
         VoronoiSeamFinder(ctx).find(images_warped, corners, masks_warped)
@@ -1218,7 +1291,8 @@ class StitchConfig:
     wave_correct: str = "horiz"       # "horiz" | "vert" | "no"; applied after the bundle adjustment only
     # the seam-scale step between warp and blend (image_stitching.cpp:940-1070, :1162-1171), the reference's defaults
     # (:73-77): block gain compensation and the dynamic-programming colour seam finder
-    expos_comp_type: str = "gain_blocks"   # "no" | "gain_blocks"
+    expos_comp_type: str = "gain_blocks"   # "no" | "gain" | "gain_blocks" | "channels_blocks" (:73; "channels": EXPOS_COMP_TYPES)
+    expos_comp_nr_feeds: int = 1           # :74
     expos_comp_block_size: int = 64
     expos_comp_nr_filtering: int = 2
     seam_find_type: str = "dp_color"       # "no" | "voronoi" | "dp_color"

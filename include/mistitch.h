@@ -341,18 +341,50 @@ int mis_rotate(MisContext* ctx, const MisImage* src, int rotate_code, MisImage* 
 int mis_seam_mask_apply(MisContext* ctx, const MisImage* seam_mask_warped, MisImage* mask_warped);
 
 /* ---- exposure compensation and seam finders between warp and blend ----
- * Replaces ExposureCompensator::createDefault(GAIN_BLOCKS) with setNrFeeds(1), setNrGainsFilteringIterations(2),
- * setBlockSize(64, 64) (image_stitching.cpp:1002-1016), compensator->feed(corners, images_warped, masks_warped) (:1023) and
- * compensator->apply(img_idx, corners[img_idx], img_warped, mask_warped) (:1162).  One feed only (the reference's value).
- * Images are 8UC3, masks 8UC1 (255 = valid), host or device. */
+ * Replaces ExposureCompensator::createDefault(expos_comp_type) with setNrFeeds(expos_comp_nr_feeds),
+ * setNrGainsFilteringIterations(2), setBlockSize(64, 64) (image_stitching.cpp:73-76, :1002-1016),
+ * compensator->feed(corners, images_warped, masks_warped) (:1023) and
+ * compensator->apply(img_idx, corners[img_idx], img_warped, mask_warped) (:1162).
+ * Images are 8UC3, masks 8UC1 (255 = valid), host or device.
+ * The types are cv::detail::ExposureCompensator's, with OpenCV's values: GAIN (one gain per frame), GAIN_BLOCKS (one per block,
+ * smoothed into a map), CHANNELS (one gain per frame and colour channel), CHANNELS_BLOCKS (a three-channel map).  NO needs no
+ * object.  The similarity threshold of OpenCV 4.x stays at its default of 1 (no similarity masks): it is not built.
+ * The caller's images: with more than one feed OpenCV multiplies the images it was given by the previous feed's gains (GAIN and
+ * GAIN_BLOCKS edit the caller's seam-scale images, the channel types edit extracted copies).  This library works on private device
+ * copies for every type: mis_compensator_feed NEVER alters the caller's images or masks, whatever nr_feeds is. */
+#define MIS_EXPOS_NO 0
+#define MIS_EXPOS_GAIN 1
+#define MIS_EXPOS_GAIN_BLOCKS 2
+#define MIS_EXPOS_CHANNELS 3
+#define MIS_EXPOS_CHANNELS_BLOCKS 4
+typedef struct {
+    int type;                            /* MIS_EXPOS_* (not NO) */
+    int nr_feeds;                        /* >= 1: feeds k > 0 run on the images multiplied by the gains of feed k - 1; the result is the product */
+    int block_width, block_height;       /* block types only */
+    int nr_gain_filtering_iterations;    /* block types only */
+} MisCompensatorParams;
 typedef struct MisCompensator MisCompensator;
+/* the reference's values: GAIN_BLOCKS, 1 feed, 64 x 64 blocks, 2 filtering passes */
+void mis_compensator_default_params(MisCompensatorParams* params);
+/* type NO, an unknown type or nr_feeds < 1: MIS_E_INVALID */
+int mis_compensator_create_ex(MisContext* ctx, const MisCompensatorParams* params, MisCompensator** out);
+/* {GAIN_BLOCKS, 1 feed, the given blocks and passes} */
 int mis_compensator_create(MisContext* ctx, int block_width, int block_height, int nr_gain_filtering_iterations, MisCompensator** out);
 int mis_compensator_destroy(MisCompensator* c);
 int mis_compensator_feed(MisCompensator* c, const MisPoint* corners, const MisImage* images, const MisImage* masks, int n);
-/* smoothed gain map of one image (one float per block, row-major); map_host may be NULL to query the grid size */
+/* gains of one image after the feed: GAIN the gain three times, CHANNELS B, G, R; block types: MIS_E_UNSUPPORTED */
+int mis_compensator_gains(const MisCompensator* c, int index, double gains[3]);
+/* smoothed gain map of one image (one float per block, row-major); map_host may be NULL to query the grid size.
+ * One-channel maps only: MIS_E_UNSUPPORTED for CHANNELS_BLOCKS and for the types without a map */
 int mis_compensator_gain_map(const MisCompensator* c, int index, float* map_host, int capacity, int* blocks_x, int* blocks_y);
+/* the same for GAIN_BLOCKS (*channels = 1) and CHANNELS_BLOCKS (*channels = 3, interleaved B, G, R per block); capacity in floats */
+int mis_compensator_gain_map_channels(const MisCompensator* c, int index, float* map_host, int capacity, int* blocks_x, int* blocks_y, int* channels);
 /* image *= gains, in place; 8UC3, or the 16SC3 image the fused warp produces (values 0..255) */
 int mis_compensator_apply(MisCompensator* c, int index, MisImage* image);
+/* Test hook: the overlap statistics of frames i and j in the LAST feed of a GAIN (channel 0) or CHANNELS (channel 0..2 = B, G, R)
+ * compensator: N_ij = max(1, intersect count), I_ij and I_ji; all 0 when the frames' rectangles do not intersect.  Block types:
+ * MIS_E_UNSUPPORTED. */
+int mis_compensator_debug_stats(const MisCompensator* c, int i, int j, int channel, int* N, double* I_ij, double* I_ji);
 /* VoronoiSeamFinder::find (seam_find_type "voronoi", image_stitching.cpp:1031): masks (8UC1) are edited in place.
  * "no" (NoSeamFinder) needs no call; the reference's default, DpSeamFinder(COLOR) ("dp_color"), is mis_seam_dp below. */
 int mis_seam_voronoi(MisContext* ctx, const MisPoint* corners, MisImage* masks, int n);
