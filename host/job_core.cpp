@@ -73,7 +73,12 @@ JobCore::JobCore(const char* who, std::string where, int device, void* main_stre
     if (kind_ != MIS_WARP_SPHERICAL) {
         const float scale = warp_scale(everyone_);
         MisRect r;
-        for (int i = 0; i < n_ && spec_ok_; i++) spec_ok_ = mis_warper_roi(kind_, scale, w_, h_, &Ks_[9 * i], &Rs_[9 * i], &r) == MIS_OK;
+        // (the Mercator roi scans every source pixel: the batch entry runs that on the device, one call for all frames)
+        if (kind_ == MIS_WARP_MERCATOR) {
+            std::vector<MisRect> rr((size_t)n_);
+            spec_ok_ = n_ == 0 || mis_warper_roi_batch(cctx_, kind_, scale, w_, h_, n_, Ks_.data(), Rs_.data(), rr.data()) == MIS_OK;
+        } else
+            for (int i = 0; i < n_ && spec_ok_; i++) spec_ok_ = mis_warper_roi(kind_, scale, w_, h_, &Ks_[9 * i], &Rs_[9 * i], &r) == MIS_OK;
     }
 }
 

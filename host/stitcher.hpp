@@ -33,8 +33,8 @@ struct StitchConfig {
     std::string expos_comp_type = "no";    // "no" | "gain" | "gain_blocks" | "channels" | "channels_blocks" (:73; 64 x 64 blocks, 2 filtering passes)
     int expos_comp_nr_feeds = 1;           // :74
     std::string seam_find_type = "no";     // "no" | "voronoi" | "dp_color" (the reference's default; this driver's default is the hot path)
-    // warper (:917-969): the three of the reference's GPU branch are built; its other names throw by name (warp_kind)
-    std::string warp_type = "spherical";   // "spherical" | "cylindrical" | "plane"
+    // warper (:917-969): the three of the reference's GPU branch and its Mercator warper are built; its other names throw by name (warp_kind)
+    std::string warp_type = "spherical";   // "spherical" | "cylindrical" | "plane" | "mercator"
     // matcher (:83, :646-649): -1 BestOf2NearestMatcher (all pairs), w >= 1 BestOf2NearestRangeMatcher (pairs with j < i + w only)
     int range_width = -1;
     // matcher_type (:64, :644-645): "homography" (the two above) | "affine": AffineBestOf2NearestMatcher(false, ...), all pairs
@@ -87,11 +87,12 @@ inline int warp_kind(const std::string& t) {
     if (t == "spherical") return MIS_WARP_SPHERICAL;
     if (t == "cylindrical") return MIS_WARP_CYLINDRICAL;
     if (t == "plane") return MIS_WARP_PLANE;
+    if (t == "mercator") return MIS_WARP_MERCATOR;
     static const char* unbuilt[] = {"affine", "fisheye", "stereographic", "compressedPlaneA2B1", "compressedPlaneA1.5B1", "compressedPlanePortraitA2B1",
                                     "compressedPlanePortraitA1.5B1", "paniniA2B1", "paniniA1.5B1", "paniniPortraitA2B1", "paniniPortraitA1.5B1",
-                                    "mercator", "transverseMercator"};
+                                    "transverseMercator"};
     for (const char* u : unbuilt)
-        if (t == u) throw std::runtime_error("warper '" + t + "' is not implemented ('spherical', 'cylindrical' and 'plane' are)");
+        if (t == u) throw std::runtime_error("warper '" + t + "' is not implemented ('spherical', 'cylindrical', 'plane' and 'mercator' are)");
     throw std::runtime_error("Can't create the following warper '" + t + "'");
 }
 

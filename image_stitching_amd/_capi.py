@@ -19,7 +19,8 @@ U8, S16, F32 = 0, 1, 2
 INTER_NEAREST, INTER_LINEAR = 0, 1
 BORDER_CONSTANT, BORDER_REFLECT = 0, 2
 BLEND_NO, BLEND_FEATHER, BLEND_MULTI_BAND = 0, 1, 2
-WARP_SPHERICAL, WARP_CYLINDRICAL, WARP_PLANE = 0, 1, 2
+WARP_SPHERICAL, WARP_CYLINDRICAL, WARP_PLANE, WARP_MERCATOR = 0, 1, 2, 3
+MATH_LOG, MATH_TAN, MATH_SINH, MATH_ASIN, MATH_ATAN, MATH_EXP = 0, 1, 2, 3, 4, 5     # mis_debug_math_f32
 MATCH_HOMOGRAPHY, MATCH_AFFINE_PARTIAL = 0, 1
 EXPOS_NO, EXPOS_GAIN, EXPOS_GAIN_BLOCKS, EXPOS_CHANNELS, EXPOS_CHANNELS_BLOCKS = 0, 1, 2, 3, 4      # cv::detail::ExposureCompensator's values
 
@@ -147,9 +148,11 @@ PROTOTYPES = {
     "mis_warp_spherical_fused_batch": (_i, [_vp, _P(MisImage), _i, C.c_float, _P(C.c_float), _P(C.c_float), _P(MisRect), _P(MisImage), _P(MisImage), _P(MisPoint)]),
     "mis_warp_spherical_fused_batch_timed": (_i, [_vp, _P(MisImage), _i, C.c_float, _P(C.c_float), _P(C.c_float), _P(MisRect), _P(MisImage), _P(MisImage), _P(MisPoint), _i,
                                                _P(C.c_float)]),
+    "mis_debug_math_f32": (_i, [_vp, _i, _vp, _vp, _i]),
     "mis_warper_roi": (_i, [_i, _f, _i, _i, _vp, _vp, _P(MisRect)]),
     "mis_warper_roi_batch": (_i, [_vp, _i, _f, _i, _i, _i, _vp, _vp, _P(MisRect)]),
     "mis_warper_warp": (_i, [_vp, _i, _P(MisImage), _f, _vp, _vp, _i, _i, _P(MisImage), _P(MisPoint)]),
+    "mis_warper_warp_roi": (_i, [_vp, _i, _P(MisImage), _f, _vp, _vp, _P(MisRect), _i, _i, _P(MisImage), _P(MisPoint)]),
     "mis_warper_warp_fused": (_i, [_vp, _i, _P(MisImage), _f, _vp, _vp, _P(MisImage), _P(MisImage), _P(MisPoint)]),
     "mis_warper_warp_fused_roi": (_i, [_vp, _i, _P(MisImage), _f, _vp, _vp, _P(MisRect), _P(MisImage), _P(MisImage), _P(MisPoint)]),
     "mis_warper_warp_fused_batch": (_i, [_vp, _i, _P(MisImage), _i, C.c_float, _P(C.c_float), _P(C.c_float), _P(MisRect), _P(MisImage), _P(MisImage), _P(MisPoint)]),

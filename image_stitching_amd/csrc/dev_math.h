@@ -195,6 +195,82 @@ MIS_HD float mis_expf(float xx) {
 }
 MIS_HD int mis_floor_f(float v) { int i = (int)v; return i - ((float)i > v); }
 
+// Cephes logf: x = m 2^e with m in [sqrt(1/2), sqrt(2)), a degree-8 polynomial in m - 1, e ln 2 added in two pieces.  The edge cases
+// are the C library's, not Cephes': log(+-0) = -inf, log(x < 0) = NaN, log(inf) = inf, log(NaN) = NaN (the Mercator roi scan relies
+// on them: a pixel at the lower pole gives -inf and is refused, one past the upper pole gives NaN and is skipped).
+MIS_HD float mis_logf(float xx) {
+    union { float f; uint32_t u; } v;
+    v.f = xx;
+    if (xx != xx) return xx;
+    if (xx == 0.0f) return -INFINITY;
+    if (xx < 0.0f) return NAN;
+    if (v.u == 0x7f800000u) return xx;
+    int e = 0;
+    if (v.u < 0x00800000u) { v.f = xx * 8388608.0f; e = -23; }   // subnormal: exact scaling by 2^23
+    e += (int)(v.u >> 23) - 126;                                  // frexpf: m in [0.5, 1)
+    v.u = (v.u & 0x007fffffu) | 0x3f000000u;
+    float x = v.f;
+    if (x < 0.707106781186547524f) { e -= 1; x = (x + x) - 1.0f; }
+    else x = x - 1.0f;
+    float z = x * x;
+    float y = 7.0376836292E-2f * x - 1.1514610310E-1f;
+    y = y * x + 1.1676998740E-1f;
+    y = y * x - 1.2420140846E-1f;
+    y = y * x + 1.4249322787E-1f;
+    y = y * x - 1.6668057665E-1f;
+    y = y * x + 2.0000714765E-1f;
+    y = y * x - 2.4999993993E-1f;
+    y = y * x + 3.3333331174E-1f;
+    y = y * x;
+    y = y * z;
+    const float fe = (float)e;
+    if (e) y = y + -2.12194440e-4f * fe;
+    y = y + -0.5f * z;
+    z = x + y;
+    if (e) z = z + 0.693359375f * fe;
+    return z;
+}
+
+// Cephes tanf (|x| <= 8192, 0 beyond as there): the octant reduction of mis_sincosf, a degree-13 odd polynomial on [-pi/4, pi/4],
+// -1 / y in the odd octants.  tan of the float nearest pi/2 is the large negative value the real function has there.
+MIS_HD float mis_tanf(float xx) {
+    float x = fabsf(xx);
+    if (x > 8192.0f) return 0.0f;
+    unsigned j = (unsigned)(1.27323954473516f * x);
+    float y = (float)j;
+    if (j & 1u) { j += 1; y += 1.0f; }
+    float z = ((x - y * 0.78515625f) - y * 2.4187564849853515625e-4f) - y * 3.77489497744594108e-8f;
+    float zz = z * z;
+    if (x > 1.0e-4f) {
+        y = 9.38540185543E-3f * zz + 3.11992232697E-3f;
+        y = y * zz + 2.44301354525E-2f;
+        y = y * zz + 5.34112807005E-2f;
+        y = y * zz + 1.33387994085E-1f;
+        y = y * zz + 3.33331568548E-1f;
+        y = y * zz;
+        y = y * z;
+        y = y + z;
+    } else y = z;
+    if (j & 2u) y = -1.0f / y;
+    return xx < 0 ? -y : y;
+}
+
+// Cephes sinhf: an odd degree-7 polynomial for |x| <= 1, (e^|x| - e^-|x|) / 2 beyond; +-inf (never NaN) where e^|x| overflows
+MIS_HD float mis_sinhf(float xx) {
+    float z = fabsf(xx);
+    if (z > 1.0f) {
+        z = mis_expf(z);
+        z = 0.5f * z - (0.5f / z);
+        return xx < 0 ? -z : z;
+    }
+    z = xx * xx;
+    float y = 2.03721912945E-4f * z + 8.33028376239E-3f;
+    y = y * z + 1.66667160211E-1f;
+    y = y * z;
+    y = y * xx;
+    return y + xx;
+}
+
 // natural log in f64 from + * / and exponent extraction (RANSAC iteration-count update)
 MIS_HD double mis_log_d(double x) {
     union { double d; uint64_t u; } v;

@@ -1,10 +1,11 @@
-// warp.hip -- rotation warps, replaces the reference's cv::detail::{Spherical,Cylindrical,Plane}Warper calls
+// warp.hip -- rotation warps, replaces the reference's cv::detail::{Spherical,Cylindrical,Plane,Mercator}Warper calls
 // (the warp_type switch of image_stitching/image_stitching.cpp:917-969): :973/:1117 (create(scale)),
 // :985/:988/:1154/:1159 (warp), :1138 (warpRoi), :1164 (convertTo CV_16S, fused here).
 // The three kinds share one per-pixel form: x_ = su * s, z_ = cu * s, y_ = c with a column table {su, cu} and a row table
 // {s, m1 c, m4 c, m7 c} (spherical: sin u', cos u' | sin(pi - v'), cos(pi - v'); cylindrical: sin u', cos u' | 1, v';
-// plane: u', 1 | 1, v').  The products by 1 are exact, so the float operations per pixel are OpenCV's for every kind; the
-// plane projector divides by z whatever its sign (a compile-time switch of the fused kernels).
+// plane: u', 1 | 1, v'; mercator: sin u', cos u' | cos v_, sin v_ with v_ = atan(sinh v')).  The products by 1 are exact, so the
+// float operations per pixel are OpenCV's for every kind; the plane projector divides by z whatever its sign (a compile-time
+// switch of the fused kernels).
 //
 // One pass per frame: the inverse map (mapBackward) is evaluated in registers -- OpenCV's xmap/ymap
 // (8 B per output pixel written and read back) never exist -- and the bilinear gather (INTER_BITS = 5
@@ -25,7 +26,7 @@ struct Projector {
     int kind;   // MIS_WARP_*
 };
 
-static bool kind_ok(int kind) { return kind == MIS_WARP_SPHERICAL || kind == MIS_WARP_CYLINDRICAL || kind == MIS_WARP_PLANE; }
+static bool kind_ok(int kind) { return kind == MIS_WARP_SPHERICAL || kind == MIS_WARP_CYLINDRICAL || kind == MIS_WARP_PLANE || kind == MIS_WARP_MERCATOR; }
 
 // ProjectorBase::setCameraParams (stitching/src/warpers.cpp): float matrices, double intermediates
 void projector_set(Projector* p, int kind, float scale, const float K[9], const float R[9]) {
@@ -61,7 +62,7 @@ void projector_set(Projector* p, int kind, float scale, const float K[9], const 
         }
 }
 
-// {Spherical,Cylindrical,Plane}Projector::mapForward (warpers_inl.hpp); the same float operations on the host and on the
+// {Spherical,Cylindrical,Plane,Mercator}Projector::mapForward (warpers_inl.hpp); the same float operations on the host and on the
 // device.  Returns z_ > 0 (the plane's corners must lie in front of the panorama plane).
 MIS_HD bool map_forward(int kind, const float* m, float scale, float x, float y, float* u, float* v) {
     float x_ = (m[0] * x + m[1] * y) + m[2];
@@ -73,6 +74,10 @@ MIS_HD bool map_forward(int kind, const float* m, float scale, float x, float y,
     } else if (kind == MIS_WARP_CYLINDRICAL) {
         *u = scale * mis_atan2f(x_, z_);
         *v = scale * y_ / sqrtf(x_ * x_ + z_ * z_);
+    } else if (kind == MIS_WARP_MERCATOR) {
+        *u = scale * mis_atan2f(x_, z_);
+        float v_ = mis_asinf(y_ / sqrtf((x_ * x_ + y_ * y_) + z_ * z_));
+        *v = scale * mis_logf(mis_tanf((float)(3.14159265358979323846 / 4) + v_ / 2));
     } else {
         *u = scale * mis_atan2f(x_, z_);
         float w = y_ / sqrtf((x_ * x_ + y_ * y_) + z_ * z_);
@@ -115,6 +120,8 @@ int roi_from_extremes(const Projector* p, int sw, int sh, float tl_uf, float tl_
 //  * spherical (SphericalWarper::detectResultRoi) and cylindrical (detectResultRoiByBorder): the 2(W+H) border pixels;
 //  * plane (PlaneWarper::detectResultRoi): the four corners (0,0), (0,h-1), (w-1,0), (w-1,h-1).  A corner with z_ <= 0 lies behind
 //    the panorama plane and OpenCV's rectangle means nothing: MIS_E_INVALID.
+//  * mercator (RotationWarperBase::detectResultRoi: MercatorWarper has no override): every pixel, O(w h).  With a pole inside the
+//    frame the extreme v lies at an interior pixel; a NaN (the upper pole) is skipped as std::min / std::max skip it.
 int detect_result_roi(const Projector* p, int sw, int sh, int* tlx, int* tly, int* brx, int* bry) {
     float tl_uf = FLT_MAX, tl_vf = FLT_MAX, br_uf = -FLT_MAX, br_vf = -FLT_MAX, u, v;
     auto upd = [&]() {
@@ -129,6 +136,9 @@ int detect_result_roi(const Projector* p, int sw, int sh, int* tlx, int* tly, in
         bool front = true;
         for (int c = 0; c < 4; c++) { front &= map_forward(kind, p->r_kinv, p->scale, cx[c], cy[c], &u, &v); upd(); }
         if (!front) return MIS_E_INVALID;
+    } else if (kind == MIS_WARP_MERCATOR) {
+        for (int y = 0; y < sh; ++y)
+            for (int x = 0; x < sw; ++x) { map_forward(kind, p->r_kinv, p->scale, (float)x, (float)y, &u, &v); upd(); }
     } else {
         for (int x = 0; x < sw; ++x) {
             map_forward(kind, p->r_kinv, p->scale, (float)x, 0, &u, &v); upd();
@@ -202,6 +212,56 @@ __global__ __launch_bounds__(256) void warp_roi_kernel(RoiJob* jobs) {
     }
 }
 
+// The full-frame scan of RotationWarperBase::detectResultRoi (the Mercator kind): workgroup (c, f) projects rows
+// c * rows .. c * rows + rows - 1 of frame f, every pixel, and writes one partial {min u, min v, max u, max v} to part[f * nchunk + c]
+// (pinned, device-visible, behind the jobs).  The host takes the min / max of a frame's partials after the entry's one stream
+// synchronisation: min / max of floats with NaN skipped, any order gives the host loop's floats (+-0 apart, and (int) of both is 0).
+// Only the Mercator kind scans (the host checks it): map_forward takes the kind as a constant and the other kinds' branches are
+// not compiled into the loop.
+constexpr int ROI_SCAN_MAX_PARTS = 1024;    // partials per frame
+__global__ __launch_bounds__(256) void warp_roi_scan_kernel(const RoiJob* jobs, float4* part, int rows, int nchunk) {
+    const RoiJob* j = jobs + blockIdx.y;
+    __shared__ float red[4][4];
+    float m[9];
+    for (int i = 0; i < 9; i++) m[i] = j->r_kinv[i];
+    const float scale = j->scale;
+    const int sw = j->sw, sh = j->sh;
+    constexpr int kind = MIS_WARP_MERCATOR;
+    const int y0 = (int)blockIdx.x * rows, y1 = min(sh, y0 + rows);
+    const unsigned npts = (unsigned)max(y1 - y0, 0) * (unsigned)sw;      // sizes <= 32767 (host check): below 2^30
+    float lo_u = FLT_MAX, lo_v = FLT_MAX, hi_u = -FLT_MAX, hi_v = -FLT_MAX;
+    // flat index over the chunk (odd widths fill the waves); (row, column) advance by the uniform (256 / sw, 256 % sw) with one carry:
+    // one division per thread, none per pixel
+    const int rstep = 256 / sw, cstep = 256 - rstep * sw;
+    int r = (int)threadIdx.x / sw, c = (int)threadIdx.x - r * sw;
+    for (unsigned i = threadIdx.x; i < npts; i += 256) {
+        float u, v;
+        map_forward(kind, m, scale, (float)c, (float)(y0 + r), &u, &v);
+        lo_u = fminf(lo_u, u); lo_v = fminf(lo_v, v); hi_u = fmaxf(hi_u, u); hi_v = fmaxf(hi_v, v);
+        c += cstep; r += rstep;
+        if (c >= sw) { c -= sw; r += 1; }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        lo_u = fminf(lo_u, __shfl_xor(lo_u, o)); lo_v = fminf(lo_v, __shfl_xor(lo_v, o));
+        hi_u = fmaxf(hi_u, __shfl_xor(hi_u, o)); hi_v = fmaxf(hi_v, __shfl_xor(hi_v, o));
+    }
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { red[wave][0] = lo_u; red[wave][1] = lo_v; red[wave][2] = hi_u; red[wave][3] = hi_v; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float4 e;
+        e.x = fminf(fminf(red[0][0], red[1][0]), fminf(red[2][0], red[3][0]));
+        e.y = fminf(fminf(red[0][1], red[1][1]), fminf(red[2][1], red[3][1]));
+        e.z = fmaxf(fmaxf(red[0][2], red[1][2]), fmaxf(red[2][2], red[3][2]));
+        e.w = fmaxf(fmaxf(red[0][3], red[1][3]), fmaxf(red[2][3], red[3][3]));
+        part[(size_t)blockIdx.y * nchunk + blockIdx.x] = e;
+    }
+}
+// rows per workgroup of the scan: at most ROI_SCAN_MAX_PARTS chunks per frame, and at least ~8 pixels per thread where the frame has them
+static int roi_scan_rows(int w, int h) {
+    return std::max((h + ROI_SCAN_MAX_PARTS - 1) / ROI_SCAN_MAX_PARTS, std::min(h, (2048 + w - 1) / w));
+}
+
 struct WarpArgs {
     float m[9];  // k_rinv
     float scale;
@@ -217,7 +277,7 @@ struct WarpArgs {
 
 constexpr int TILE_W = 128, TILE_H = 16;
 
-// {Spherical,Cylindrical,Plane}Projector::mapBackward with the separable terms pre-evaluated (table_terms); the plane divides
+// {Spherical,Cylindrical,Plane,Mercator}Projector::mapBackward with the separable terms pre-evaluated (table_terms); the plane divides
 // by z whatever its sign
 __device__ __forceinline__ void map_backward(int kind, const float* m, float sinu, float cosu, float sinv, float cosv, float* x, float* y) {
     float x_ = sinv * sinu, y_ = cosv, z_ = sinv * cosu;
@@ -229,7 +289,8 @@ __device__ __forceinline__ void map_backward(int kind, const float* m, float sin
 }
 
 // the separable terms of output column `col` ({su, cu}) and row `row` ({s, c}) of a warp kind (u' = u / scale, v' = v / scale):
-// spherical {sin u', cos u'} {sin(pi - v'), cos(pi - v')}; cylindrical {sin u', cos u'} {1, v'}; plane {u', 1} {1, v'}
+// spherical {sin u', cos u'} {sin(pi - v'), cos(pi - v')}; cylindrical {sin u', cos u'} {1, v'}; plane {u', 1} {1, v'};
+// mercator {sin u', cos u'} {cos v_, sin v_}, v_ = atan(sinh v') (a unit ray like the spherical one; v' = +-inf gives v_ = +-pi/2)
 __device__ __forceinline__ void col_terms(int kind, float scale, int col, float* su, float* cu) {
     const float u = (float)col / scale;
     if (kind == MIS_WARP_PLANE) { *su = u; *cu = 1.f; }
@@ -238,6 +299,7 @@ __device__ __forceinline__ void col_terms(int kind, float scale, int col, float*
 __device__ __forceinline__ void row_terms(int kind, float scale, int row, float* s, float* c) {
     const float v = (float)row / scale;
     if (kind == MIS_WARP_SPHERICAL) mis_sincosf(MIS_PI_F - v, s, c);
+    else if (kind == MIS_WARP_MERCATOR) mis_sincosf(mis_atanf(mis_sinhf(v)), c, s);
     else { *s = 1.f; *c = v; }
 }
 
@@ -461,7 +523,7 @@ __device__ __forceinline__ void tile_trig(const WarpArgs& a, const float* __rest
     for (int i = 0; i < LROWS; i++) g.rt[i] = rowtab[min(gy0 + i, a.dh - 1)];  // rows past the roi shadow the last one
 }
 
-// ZTEST: the generic branch maps z <= 0 to (-1, -1) (spherical, cylindrical); without it every pixel divides (plane)
+// ZTEST: the generic branch maps z <= 0 to (-1, -1) (spherical, cylindrical, mercator); without it every pixel divides (plane)
 template <bool ZTEST>
 __device__ __forceinline__ void tile_map(const WarpArgs& a, const TileTrig& g, int tx0, int ty0, int lane, TileState& t) {
     const int lx = lane & 15, ly = lane >> 4;
@@ -1286,7 +1348,9 @@ static int v3_strip_tiles(const MisContext* ctx, const WarpArgs& a, int frames) 
 }
 // The fast paths' upper bound on z: |z| <= (|m6| + |m7| + |m8|) max(|x_|, |y_|, |z_|).  Spherical terms are at most 1 (the kernels'
 // own guard); the cylinder's y_ = v' and the plane's x_ = u', y_ = v' grow with the roi, so those kinds scale the bound by the
-// largest |u'|, |v'| of the roi (a frame that fails it takes the generic map everywhere).
+// largest |u'|, |v'| of the roi (a frame that fails it takes the generic map everywhere).  The Mercator ray has unit length like the
+// spherical one; it takes the cylinder's (wider) bound with every other non-spherical kind, which only sends more frames down the
+// generic map.
 static bool fast_z_bound_ok(const WarpArgs& a) {
     const float msum = fabsf(a.m[6]) + fabsf(a.m[7]) + fabsf(a.m[8]);
     if (a.kind == MIS_WARP_SPHERICAL) return msum <= 1048576.f;
@@ -1407,6 +1471,13 @@ int setup(MisContext* ctx, int kind, const MisImage* src, float scale, const flo
     if (known) {
         projector_set(&p, kind, scale, K, R);
         tlx = known->x; tly = known->y; *brx = known->x + known->width - 1; *bry = known->y + known->height - 1;
+    } else if (kind == MIS_WARP_MERCATOR) {
+        // the full-frame scan runs on the device (the host loop of mis_warper_roi is O(w h)); same roi by construction
+        MisRect r;
+        int rc;
+        if ((rc = mis_warper_roi_batch(ctx, kind, scale, src->width, src->height, 1, K, R, &r)) != MIS_OK) return rc;
+        projector_set(&p, kind, scale, K, R);
+        tlx = r.x; tly = r.y; *brx = r.x + r.width - 1; *bry = r.y + r.height - 1;
     } else {
         MIS_CHECK(ctx, projector_and_roi(kind, scale, K, R, src->width, src->height, &p, &tlx, &tly, brx, bry) == MIS_OK, MIS_E_INVALID, "%s",
                   kind == MIS_WARP_PLANE ? "warp roi refused: a corner of the frame lies behind the panorama plane"
@@ -1445,6 +1516,7 @@ extern "C" int mis_debug_warp_stamps(unsigned long long* out, int n) {
 extern "C" int mis_warper_roi(int kind, float scale, int w, int h, const float K[9], const float R[9], MisRect* roi) {
     if (!kind_ok(kind)) return MIS_E_UNSUPPORTED;
     if (!K || !R || !roi || w < 1 || h < 1 || !(scale > 0.f)) return MIS_E_INVALID;
+    if (kind == MIS_WARP_MERCATOR && (w > 32767 || h > 32767)) return MIS_E_INVALID;     // a frame the warps refuse; the scan is O(w h)
     Projector p;
     int tlx, tly, brx, bry, rc;
     if ((rc = projector_and_roi(kind, scale, K, R, w, h, &p, &tlx, &tly, &brx, &bry)) != MIS_OK) return rc;
@@ -1455,14 +1527,14 @@ extern "C" int mis_warp_roi(float scale, int w, int h, const float K[9], const f
     return mis_warper_roi(MIS_WARP_SPHERICAL, scale, w, h, K, R, roi);
 }
 
-extern "C" int mis_warper_warp(MisContext* ctx, int kind, const MisImage* src, float scale, const float K[9], const float R[9],
-                               int interp, int border, MisImage* dst, MisPoint* tl) {
+static int warp_u8_impl(MisContext* ctx, int kind, const MisImage* src, float scale, const float K[9], const float R[9], const MisRect* known_roi,
+                       int interp, int border, MisImage* dst, MisPoint* tl) {
     if (!ctx) return MIS_E_INVALID;
     MIS_CHECK(ctx, (interp == MIS_INTER_LINEAR && border == MIS_BORDER_REFLECT) || (interp == MIS_INTER_NEAREST && border == MIS_BORDER_CONSTANT),
               MIS_E_UNSUPPORTED, "supported: (LINEAR, REFLECT) and (NEAREST, CONSTANT)");
     WarpArgs a;
     int brx, bry, rc;
-    if ((rc = setup(ctx, kind, src, scale, K, R, &a, &brx, &bry)) != MIS_OK) return rc;
+    if ((rc = setup(ctx, kind, src, scale, K, R, &a, &brx, &bry, known_roi)) != MIS_OK) return rc;
     MIS_HIP(ctx, hipSetDevice(ctx->device));
     DevView din, dout;
     if ((rc = din.read(ctx, src)) != MIS_OK) return rc;
@@ -1481,6 +1553,20 @@ extern "C" int mis_warper_warp(MisContext* ctx, int kind, const MisImage* src, f
     if ((rc = dout.commit()) != MIS_OK) return rc;
     if (tl) { tl->x = a.tlx; tl->y = a.tly; }
     return MIS_OK;
+}
+
+extern "C" int mis_warper_warp(MisContext* ctx, int kind, const MisImage* src, float scale, const float K[9], const float R[9],
+                               int interp, int border, MisImage* dst, MisPoint* tl) {
+    return warp_u8_impl(ctx, kind, src, scale, K, R, nullptr, interp, border, dst, tl);
+}
+
+// the same with the roi mis_warper_roi / mis_warper_roi_batch gave for these parameters: no second roi computation (the Mercator
+// roi is a scan of every source pixel)
+extern "C" int mis_warper_warp_roi(MisContext* ctx, int kind, const MisImage* src, float scale, const float K[9], const float R[9], const MisRect* roi,
+                                   int interp, int border, MisImage* dst, MisPoint* tl) {
+    if (!ctx) return MIS_E_INVALID;
+    MIS_CHECK(ctx, roi && roi->width > 0 && roi->height > 0, MIS_E_INVALID, "empty roi");
+    return warp_u8_impl(ctx, kind, src, scale, K, R, roi, interp, border, dst, tl);
 }
 
 extern "C" int mis_warp_spherical(MisContext* ctx, const MisImage* src, float scale, const float K[9], const float R[9],
@@ -1681,8 +1767,14 @@ extern "C" int mis_warper_roi_batch(MisContext* ctx, int kind, float scale, int 
     if (!ctx) return MIS_E_INVALID;
     MIS_CHECK(ctx, kind_ok(kind), MIS_E_UNSUPPORTED, "unknown warp kind %d", kind);
     MIS_CHECK(ctx, Ks && Rs && rois && n >= 1 && w >= 1 && h >= 1 && scale > 0.f, MIS_E_INVALID, "invalid argument");
+    const bool scan = kind == MIS_WARP_MERCATOR;
+    MIS_CHECK(ctx, !scan || (w <= 32767 && h <= 32767), MIS_E_INVALID, "source size %dx%d out of range", w, h);
+    MIS_CHECK(ctx, !scan || n <= 65535, MIS_E_INVALID, "%d frames in one roi call (at most 65535)", n);     // the grid's y extent; before anything is sized by n
     MIS_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t need = sizeof(RoiJob) * (size_t)n;
+    // the Mercator scan's partials lie behind the jobs in the same pinned block
+    const int rows = scan ? roi_scan_rows(w, h) : 0, nchunk = scan ? (h + rows - 1) / rows : 0;
+    const size_t part_off = mis_align_up(sizeof(RoiJob) * (size_t)n, 16);
+    const size_t need = part_off + sizeof(float4) * (size_t)n * nchunk;
     if (ctx->roi_pinned_bytes < need) {
         if (ctx->roi_pinned) { MIS_HIP(ctx, hipStreamSynchronize(ctx->stream)); MIS_HIP(ctx, hipHostFree(ctx->roi_pinned)); ctx->roi_pinned = nullptr; ctx->roi_pinned_bytes = 0; }
         MIS_HIP(ctx, hipHostMalloc(&ctx->roi_pinned, need * 2, hipHostMallocMapped));
@@ -1695,14 +1787,24 @@ extern "C" int mis_warper_roi_batch(MisContext* ctx, int kind, float scale, int 
         memcpy(jobs[i].r_kinv, proj[i].r_kinv, sizeof(jobs[i].r_kinv));
         jobs[i].scale = scale; jobs[i].sw = w; jobs[i].sh = h; jobs[i].kind = kind; jobs[i].behind = 0;
     }
-    hipLaunchKernelGGL(warp_roi_kernel, dim3(n), dim3(256), 0, ctx->stream, jobs);
+    float4* part = (float4*)((uint8_t*)ctx->roi_pinned + part_off);
+    if (scan) hipLaunchKernelGGL(warp_roi_scan_kernel, dim3(nchunk, n), dim3(256), 0, ctx->stream, (const RoiJob*)jobs, part, rows, nchunk);
+    else hipLaunchKernelGGL(warp_roi_kernel, dim3(n), dim3(256), 0, ctx->stream, jobs);
     MIS_HIP(ctx, hipGetLastError());
     MIS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     for (int i = 0; i < n; i++) {
         int tlx, tly, brx, bry;
+        if (scan) {
+            float e[4] = {FLT_MAX, FLT_MAX, -FLT_MAX, -FLT_MAX};
+            for (int c = 0; c < nchunk; c++) {
+                const float4 q = part[(size_t)i * nchunk + c];
+                e[0] = fminf(e[0], q.x); e[1] = fminf(e[1], q.y); e[2] = fmaxf(e[2], q.z); e[3] = fmaxf(e[3], q.w);
+            }
+            for (int k = 0; k < 4; k++) jobs[i].ext[k] = e[k];
+        }
         MIS_CHECK(ctx, !jobs[i].behind, MIS_E_INVALID, "frame %d: warp roi refused: a corner of the frame lies behind the panorama plane", i);
         MIS_CHECK(ctx, roi_from_extremes(&proj[i], w, h, jobs[i].ext[0], jobs[i].ext[1], jobs[i].ext[2], jobs[i].ext[3], &tlx, &tly, &brx, &bry) == MIS_OK,
-                  MIS_E_INVALID, "frame %d: warp roi refused: the border projects to a non-finite extreme", i);
+                  MIS_E_INVALID, "frame %d: warp roi refused: %s projects to a non-finite extreme", i, scan ? "a pixel (the lower pole)" : "the border");
         MIS_CHECK(ctx, roi_rect(tlx, tly, brx, bry, &rois[i]) == MIS_OK, MIS_E_INVALID, "frame %d: warp roi %d..%d x %d..%d does not fit an int size",
                   i, tlx, brx, tly, bry);
     }
@@ -1718,4 +1820,38 @@ extern "C" int mis_warp_spherical_fused_timed(MisContext* ctx, const MisImage* s
     if (!ctx) return MIS_E_INVALID;
     MIS_CHECK(ctx, repeats >= 1 && avg_us, MIS_E_INVALID, "repeats must be >= 1 and avg_us non-null");
     return warp_fused_impl(ctx, MIS_WARP_SPHERICAL, src, scale, K, R, dst, dmask, tl, repeats, avg_us);
+}
+
+// test aid: one of dev_math.h's float functions on the host (ctx NULL) or in a one-thread-per-element kernel
+MIS_HD float debug_math_eval(int fn, float x) {
+    switch (fn) {
+        case MIS_MATH_LOG: return mis_logf(x);
+        case MIS_MATH_TAN: return mis_tanf(x);
+        case MIS_MATH_SINH: return mis_sinhf(x);
+        case MIS_MATH_ASIN: return mis_asinf(x);
+        case MIS_MATH_ATAN: return mis_atanf(x);
+        default: return mis_expf(x);
+    }
+}
+__global__ __launch_bounds__(256) void debug_math_kernel(int fn, const float* in, float* out, int n) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) out[i] = debug_math_eval(fn, in[i]);
+}
+extern "C" int mis_debug_math_f32(MisContext* ctx, int fn, const float* in, float* out, int n) {
+    if (fn < MIS_MATH_LOG || fn > MIS_MATH_EXP || !in || !out || n < 0) return MIS_E_INVALID;
+    if (!ctx) {
+        for (int i = 0; i < n; i++) out[i] = debug_math_eval(fn, in[i]);
+        return MIS_OK;
+    }
+    if (n == 0) return MIS_OK;
+    MIS_HIP(ctx, hipSetDevice(ctx->device));
+    float* d = nullptr;
+    int rc;
+    if ((rc = mis_dev_stage(ctx, sizeof(float) * 2 * (size_t)n, (void**)&d)) != MIS_OK) return rc;
+    MIS_HIP(ctx, hipMemcpyAsync(d, in, sizeof(float) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(debug_math_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, fn, (const float*)d, d + n, n);
+    MIS_HIP(ctx, hipGetLastError());
+    MIS_HIP(ctx, hipMemcpyAsync(out, d + n, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    MIS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return MIS_OK;
 }

@@ -119,13 +119,13 @@ class Context:
 
 
 # ------------------------------------------------------------------------------------------------
-# warp: cv::detail::{Spherical,Cylindrical,Plane}Warper, chosen by warp_type (image_stitching.cpp:917-969; :973, :985, :988,
+# warp: cv::detail::{Spherical,Cylindrical,Plane,Mercator}Warper, chosen by warp_type (image_stitching.cpp:917-969; :973, :985, :988,
 # :1117, :1138, :1154, :1159)
-WARP_KINDS = {"spherical": capi.WARP_SPHERICAL, "cylindrical": capi.WARP_CYLINDRICAL, "plane": capi.WARP_PLANE}
+WARP_KINDS = {"spherical": capi.WARP_SPHERICAL, "cylindrical": capi.WARP_CYLINDRICAL, "plane": capi.WARP_PLANE, "mercator": capi.WARP_MERCATOR}
 # the reference's other warp_type names (image_stitching.cpp:933-964): known there, not built here
 UNBUILT_WARP_TYPES = ("affine", "fisheye", "stereographic", "compressedPlaneA2B1", "compressedPlaneA1.5B1", "compressedPlanePortraitA2B1",
                       "compressedPlanePortraitA1.5B1", "paniniA2B1", "paniniA1.5B1", "paniniPortraitA2B1", "paniniPortraitA1.5B1",
-                      "mercator", "transverseMercator")
+                      "transverseMercator")
 
 
 def warp_kind(warp_type):
@@ -134,8 +134,9 @@ def warp_kind(warp_type):
     if warp_type in WARP_KINDS:
         return WARP_KINDS[warp_type]
     if warp_type in UNBUILT_WARP_TYPES:
-        raise NotImplementedError("warp_type %r: only 'spherical', 'cylindrical' and 'plane' are implemented (the warpers of the "
-                                  "reference's GPU branch, image_stitching.cpp:921-931; DESIGN.md section 8)" % (warp_type,))
+        raise NotImplementedError("warp_type %r: only 'spherical', 'cylindrical', 'plane' and 'mercator' are implemented (the warpers of "
+                                  "the reference's GPU branch, image_stitching.cpp:921-931, and its Mercator warper; DESIGN.md section 8)"
+                                  % (warp_type,))
     raise ValueError("warp_type %r: not a warper the reference knows (image_stitching.cpp:917-969)" % (warp_type,))
 
 
@@ -175,19 +176,31 @@ class RotationWarper:
             raise NotImplementedError("warper kind %r" % (self.kind,))
 
     def warpRoi(self, src_size, K, R):
+        return self.warp_roi(src_size, K, R)
+
+    def warp_roi(self, src_size, K, R):
+        """warpRoi.  The Mercator roi is a scan of every source pixel (cv::MercatorWarper has no detectResultRoi of its own): with a
+        context at hand it runs on the device (warp_rois); the other kinds walk the border or the corners on the host."""
+        if self.kind == capi.WARP_MERCATOR and self.ctx is not None:
+            return warp_rois(self.ctx, self.scale, src_size, [{"K": K, "R": R}], self.kind)[0]
         return warp_roi(self.scale, src_size, K, R, self.kind)
 
     def warp(self, src, K, R, interp=capi.INTER_LINEAR, border=capi.BORDER_REFLECT):
         """Point warp(src, K, R, interp, border, dst) -> (tl, dst)."""
         simg = as_image(src)
-        x, y, w, h = warp_roi(self.scale, (simg.width, simg.height), K, R, self.kind)
+        x, y, w, h = self.warp_roi((simg.width, simg.height), K, R)
         dst = _empty_image(self.ctx, h, w, simg.channels, torch.uint8)
         dimg = as_image(dst)
         ka, kp = _mat9(K)
         ra, rp = _mat9(R)
         tl = capi.MisPoint()
-        self.ctx.check(self.ctx.lib.mis_warper_warp(self.ctx.h, self.kind, C.byref(simg), self.scale, kp, rp, interp, border,
-                                                    C.byref(dimg), C.byref(tl)))
+        if self.kind == capi.WARP_MERCATOR:     # the roi that sized dst was a scan of every source pixel: passed on, not computed again
+            rr = capi.MisRect(int(x), int(y), int(w), int(h))
+            self.ctx.check(self.ctx.lib.mis_warper_warp_roi(self.ctx.h, self.kind, C.byref(simg), self.scale, kp, rp, C.byref(rr), interp, border,
+                                                            C.byref(dimg), C.byref(tl)))
+        else:
+            self.ctx.check(self.ctx.lib.mis_warper_warp(self.ctx.h, self.kind, C.byref(simg), self.scale, kp, rp, interp, border,
+                                                        C.byref(dimg), C.byref(tl)))
         return (tl.x, tl.y), dst
 
     def alloc_fused(self, roi):
@@ -264,7 +277,7 @@ class RotationWarper:
         convertTo(CV_16S) (image_stitching.cpp:1154-1164) -> (tl, img_warped_s, mask_warped)."""
         if roi is None:
             simg = as_image(src_bgr)
-            roi = warp_roi(self.scale, (simg.width, simg.height), K, R, self.kind)
+            roi = self.warp_roi((simg.width, simg.height), K, R)
         dst, msk = self.alloc_fused(roi)
         tl = self.warp_fused_into(src_bgr, K, R, roi, dst, msk)
         return tl, dst, msk
@@ -283,6 +296,11 @@ class CylindricalWarper(RotationWarper):
 class PlaneWarper(RotationWarper):
     """PlaneWarper::create(scale) with T = 0 (image_stitching.cpp:923, :933)."""
     kind = capi.WARP_PLANE
+
+
+class MercatorWarper(RotationWarper):
+    """MercatorWarper::create(scale) (image_stitching.cpp:961-962)."""
+    kind = capi.WARP_MERCATOR
 
 
 def make_warper(ctx, scale, warp_type="spherical"):
@@ -1281,7 +1299,7 @@ class StitchConfig:
     match_conf: float = 0.32
     range_width: int = -1             # -1: all pairs; w >= 1: BestOf2NearestRangeMatcher, pairs with j < i + w only (:83, :646-649)
     matcher_type: str = "homography"  # "homography" | "affine": AffineBestOf2NearestMatcher(false, ...), all pairs (:64, :644-645)
-    warp_type: str = "spherical"
+    warp_type: str = "spherical"      # "spherical" | "cylindrical" | "plane" | "mercator" (:917-969; the other names raise by name, warp_kind)
     blend_type: int = capi.BLEND_MULTI_BAND
     blend_strength: float = 5.0
     # camera refinement between matching and warping (image_stitching.cpp:681-726).  The reference's default is
