@@ -4,7 +4,9 @@
 // The reference runs it on the CPU inside OpenCV (stitching/src/seam_finders.cpp: DpSeamFinder::find / process /
 // findComponents / findEdges / resolveConflicts / getSeamTips / computeCosts / estimateSeam / updateLabelsUsingSeam,
 // core's cv::partition, imgproc's floodFill) on the seam-scale images (~0.1 MP each); restated here from the published
-// algorithm.  PARITY UNPINNED (OpenCV absent offline).  Steps recalled with less than full confidence are marked [uncertain].
+// algorithm.  OpenCV is absent offline; the restatement is pinned, byte for byte and at every branch regime, to the independent
+// numpy / scipy reference tests/refimpl_seam_dp.py (tests/test_refimpl_seam_dp_gpu.py; the oracle twin oracle/mo_seam.c in
+// tests/test_refimpl_seam_dp_cpu.py).  NOT PINNED: the order of pairs at equal centre distance (mis_seam_dp below).
 // No kernels: the data is two ~420 x 240 images per pair and the algorithm is sequential (labelling, dynamic programming along
 // a seam, flood fills); images and masks are copied to the host, the masks go back to the device.
 #include "common.h"
@@ -237,8 +239,9 @@ struct DpPair {
     }
 
     // DpSeamFinder::computeCosts (COLOR): cost of cutting between horizontally / vertically adjacent pixels of the component.
-    // [uncertain] OpenCV reads labels_(y, x) for x == roi.br().x / y == roi.br().y, one past the component's box (possibly one
-    // past the union): here anything outside the union counts as "not this component" (the bad-region cost).
+    // OpenCV reads labels_(y, x) for x == roi.br().x / y == roi.br().y, one past the component's box (possibly one past the
+    // union): here anything outside the union counts as "not this component" (the bad-region cost).  Settled: estimate_seam never
+    // reads column rw of costV or row rh of costH, so that line reaches no result (tests/refimpl_seam_dp.py).
     void compute_costs(const HostImage& im1, const HostImage& im2, Pt tl1, Pt tl2, int comp, Grid<float>& costV, Grid<float>& costH) const {
         const int l = comp + 1;
         const int rx = tls[comp].x, ry = tls[comp].y, rw = brs[comp].x - rx, rh = brs[comp].y - ry;
@@ -441,7 +444,8 @@ struct DpPair {
                         }
                 }
             }
-            // [uncertain] the resolved edge leaves the graph in both directions
+            // the resolved edge leaves the graph in both directions (settled: only edges that start at an intersection component are
+            // ever read, and c2 is none, so erasing (c2, c1) or not cannot be observed; tests/refimpl_seam_dp.py)
             edges.erase(std::make_pair(c1, c2));
             edges.erase(std::make_pair(c2, c1));
         }
@@ -493,8 +497,8 @@ struct DpPair {
 }  // namespace
 
 // DpSeamFinder::find: every pair of images, the most distant centres first.
-// [uncertain] the reference orders the pairs with std::sort (unstable) + std::reverse; pairs at equal distance are ordered here as a
-// stable sort + reverse leaves them.
+// NOT PINNED: the reference orders the pairs with std::sort (unspecified for equal keys) + std::reverse; pairs at equal distance are
+// ordered here as a stable sort + reverse leaves them (tie_order="reversed" of tests/refimpl_seam_dp.py, which states both readings).
 extern "C" int mis_seam_dp(MisContext* ctx, const MisPoint* corners, const MisImage* images, MisImage* masks, int n, int cost_func) {
     if (!ctx) return MIS_E_INVALID;
     MIS_CHECK(ctx, corners && images && masks && n >= 0, MIS_E_INVALID, "null argument");

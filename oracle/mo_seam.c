@@ -5,7 +5,8 @@
  * OpenCV source restated: stitching/src/seam_finders.cpp (DpSeamFinder::find, process, findComponents, findEdges,
  * resolveConflicts, hasOnlyOneNeighbor, closeToContour, getSeamTips, computeCosts, estimateSeam, updateLabelsUsingSeam),
  * core/include/opencv2/core/operations.hpp (cv::partition), imgproc floodFill (4-connected, exact value).
- * PARITY UNPINNED (recalled; OpenCV is absent offline).  Steps recalled with less than full confidence carry [uncertain].
+ * Recalled (OpenCV is absent offline) and pinned, byte for byte at every branch regime, to the independent numpy / scipy reference
+ * tests/refimpl_seam_dp.py by tests/test_refimpl_seam_dp_cpu.py.  NOT PINNED: the order of pairs at equal centre distance.
  * Plain C with flat arrays: the edge set is an ncomps x ncomps matrix scanned row-major (= the order of std::set<pair>), the
  * std::map counters of updateLabelsUsingSeam are arrays indexed by the key.  Never linked into the product.
  */
@@ -210,7 +211,8 @@ static float diff3(const FImg* a, int y1, int x1, const FImg* b, int y2, int x2)
 
 static int lab_or0(const Dp* d, int y, int x) { return (x >= 0 && x < d->uw && y >= 0 && y < d->uh) ? LAB(d, y, x) : 0; }
 
-/* DpSeamFinder::estimateSeam (with computeCosts, COLOR).  [uncertain] labels one past the union count as "not this component". */
+/* DpSeamFinder::estimateSeam (with computeCosts, COLOR).  Labels one past the union count as "not this component"; the cost line one
+ * past the component's box is filled as OpenCV does but never read by the programme below (settled in tests/refimpl_seam_dp.py). */
 static int estimate_seam(const Dp* d, const FImg* im1, const FImg* im2, int tl1x, int tl1y, int tl2x, int tl2y, int comp, P2 p1, P2 p2, PVec* seam, int* horizontal) {
     const int l = comp + 1, rx = d->tls[comp].x, ry = d->tls[comp].y, rw = d->brs[comp].x - rx, rh = d->brs[comp].y - ry;
     const int dx1 = d->tlx - tl1x, dy1 = d->tly - tl1y, dx2 = d->tlx - tl2x, dy2 = d->tly - tl2y;
@@ -398,7 +400,7 @@ static void process_pair(const FImg* im1, const FImg* im2, int tl1x, int tl1y, i
         d.states[c1] = d.states[c2] == S_FIRST ? (S_INTERS | S_SECOND) : (S_INTERS | S_FIRST);
         refresh_comp(&d, c1);
         refresh_comp(&d, c2);
-        d.edges[(size_t)c1 * n + c2] = 0;                  /* [uncertain] the resolved edge leaves the graph, both directions */
+        d.edges[(size_t)c1 * n + c2] = 0;                  /* the resolved edge leaves the graph, both directions ((c2, c1) is never read again) */
         d.edges[(size_t)c2 * n + c1] = 0;
     }
     const int dx1 = d.tlx - tl1x, dy1 = d.tly - tl1y, dx2 = d.tlx - tl2x, dy2 = d.tly - tl2y;
@@ -416,7 +418,7 @@ static void process_pair(const FImg* im1, const FImg* im2, int tl1x, int tl1y, i
     free(seam.p); free(d.contours); free(d.states); free(d.tls); free(d.brs); free(d.edges); free(d.labels); free(d.mask1);
 }
 
-/* DpSeamFinder::find: all pairs, the most distant image centres first ([uncertain] ties: stable order, then reversed) */
+/* DpSeamFinder::find: all pairs, the most distant image centres first (NOT PINNED, ties: stable order, then reversed) */
 int mo_seam_dp_color(int n, const int* corners_xy, const int* sizes_wh, const uint8_t* const* images_bgr, uint8_t* const* masks) {
     if (n <= 0) return 0;
     FImg* im = (FImg*)calloc((size_t)n, sizeof(FImg));

@@ -218,7 +218,9 @@ def _seam_scene(n, W=960, H=540, step=14.0):
 @pytest.mark.parametrize("n,step", [(2, 14.0), (4, 11.0), (5, 23.0)])
 def test_dp_seam_finder_matches_oracle(ctx, oracle_mod, n, step):
     """DpSeamFinder(COLOR) -- the reference's default seam finder -- on seam-scale warped frames: the library's masks equal the
-    oracle's, every pair resolved (no pixel stays in two masks of a pair that overlapped), nothing outside the input masks."""
+    oracle's, every pair resolved (no pixel stays in two masks of a pair that overlapped), nothing outside the input masks.
+    The oracle is a twin of the library; both are pinned to an independent reference, branch by branch, in
+    tests/refimpl_seam_dp.py, tests/test_refimpl_seam_dp_cpu.py and tests/test_refimpl_seam_dp_gpu.py."""
     import image_stitching_amd as isa
     o = oracle_mod
     W, H = 960, 540
