@@ -319,13 +319,22 @@ constexpr int FT_SLOTS = FT_COLS * FT_ROWS / 4;       // survivors a tile can ho
 #ifdef MIS_ORB_STATS
 __device__ unsigned long long g_orb_stats[8];   // pixels tested, opposite-pair test passes, pre-test passes, corners (score > 0), survivors
 #endif
-__global__ __launch_bounds__(256) void fast_nms_kernel(Levels L, const uint8_t* pad, int* hist, int* tile_cnt, uint32_t* surv_xy, uint8_t* surv_sc, size_t ws) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void fast_nms_kernel(Levels L, const uint8_t* pad, int* hist, int* tile_cnt, uint32_t* surv_xy, uint8_t* surv_sc, size_t ws) {
     __shared__ __attribute__((aligned(16))) uint8_t g[(FT_ROWS + 10) * FG_PITCH];  // rows y0-4 .. y0+35, cols x0-16 .. x0+79 (+ two rows that are read by the last wave's column window and never used)
     __shared__ __attribute__((aligned(16))) uint8_t sc[(FT_ROWS + 2) * (FT_COLS + 4)];                          // rows y0-1 .. y0+32, cols x0-1 .. x0+64 (pitch 68)
-    __shared__ int lh[256];
     __shared__ int lcount;
-    __shared__ uint32_t lxy[FT_SLOTS];  // at most a quarter of the tile's pixels are strict local maxima
-    __shared__ uint8_t lsc[FT_SLOTS];
+    // The survivor list and the tile's histogram live in g's bytes: the last read of g is the arc evaluation, and they are first written behind
+    // the barrier that ends it (lh is zeroed there, not at the top).  Static LDS 26 464 -> 20 312 B: 20 480 B is an eighth of the CU's 160 KB.
+    // The bytes alone gave 7 waves per SIMD, not 8: the kernel held 106 scalar registers (a gfx9 SIMD has 800: 8 waves need <= 96), most of
+    // them the FT_WR + 1 ballots of stage A and, beside each, the lane verdicts it was made from.  The verdicts are now read back out of the
+    // ballots, and amdgpu_waves_per_eu(8) holds the allocation at 8 waves' worth (54 vector registers; the scalar values that do not fit
+    // sit in lanes of a vector register).  8 workgroups per CU are resident instead of 6 (tools/micro/orb_occupancy.hip asks the runtime):
+    // the five short barrier-separated phases have nothing but other workgroups to hide their latencies behind -- 565 -> 501 us per 16
+    // 4K frames; 549 with the LDS change alone at 7 waves.
+    uint32_t* const lxy = reinterpret_cast<uint32_t*>(g);                   // FT_SLOTS: at most a quarter of the tile's pixels are strict local maxima
+    uint8_t* const lsc = g + sizeof(uint32_t) * FT_SLOTS;                   // FT_SLOTS
+    int* const lh = reinterpret_cast<int*>(g + (sizeof(uint32_t) + 1) * FT_SLOTS);      // 256
+    static_assert((sizeof(uint32_t) + 1) * FT_SLOTS % 4 == 0 && (sizeof(uint32_t) + 1) * FT_SLOTS + 256 * sizeof(int) <= sizeof(g), "the survivor list and the histogram fit into g");
     __shared__ unsigned short queue[(FT_ROWS + 2) * (FT_COLS + 2)];  // pixels that pass the cheap pre-test
     __shared__ int qcount;
     const int fz = blockIdx.z / L.n, lz = blockIdx.z - fz * L.n;     // frame, level
@@ -333,7 +342,6 @@ __global__ __launch_bounds__(256) void fast_nms_kernel(Levels L, const uint8_t* 
     const int x0 = blockIdx.x * FT_COLS, y0 = blockIdx.y * FT_ROWS, t = threadIdx.x;
     if (x0 >= d.w || y0 >= d.h) return;
     WS_OFF(pad, fz, ws); WS_OFF(hist, fz, ws); WS_OFF(tile_cnt, fz, ws); WS_OFF(surv_xy, fz, ws); WS_OFF(surv_sc, fz, ws);
-    lh[t] = 0;
     if (t == 0) { lcount = 0; qcount = 0; }
     {
         // the gray tile: FT_ROWS + 8 rows x 96 bytes from column x0 - 16 -- six 16-byte pieces per row, one or two pieces per thread (x0 is a multiple of
@@ -364,8 +372,7 @@ __global__ __launch_bounds__(256) void fast_nms_kernel(Levels L, const uint8_t* 
         const int wv = __builtin_amdgcn_readfirstlane(t >> 6), lane = t & 63;       // the wave index in a scalar register: row conditions are scalar
         const unsigned ft = (unsigned)L.fast_t;
         const int r0 = FT_WR * wv;                                   // first scored row of the wave (g row of scored row r: r + 3)
-        bool pass[FT_WR + 1];
-        unsigned long long ball[FT_WR + 1];
+        unsigned long long ball[FT_WR + 1];       // (a lane's own verdicts are its bits of the ballots: kept as wave masks of their own they were 2 (FT_WR + 1) more scalar registers)
         int total = 0;
         {
             const uint8_t* colp = g + r0 * FG_PITCH + (lane + FG_COL0);      // g rows r0 .. r0 + FT_WR + 5 (the last wave reads two rows past the staged ones: g has FT_ROWS + 10)
@@ -383,8 +390,7 @@ __global__ __launch_bounds__(256) void fast_nms_kernel(Levels L, const uint8_t* 
                 // |a - v| of bytes held in dwords: v_sad_u8 (the three upper byte lanes are zero)
                 const unsigned dv = max(__builtin_amdgcn_sad_u8(col[k + 6], v, 0u), __builtin_amdgcn_sad_u8(col[k], v, 0u));
                 const unsigned dh = max(__builtin_amdgcn_sad_u8(rowp[k * FG_PITCH + 6], v, 0u), __builtin_amdgcn_sad_u8(rowp[k * FG_PITCH], v, 0u));
-                pass[k] = rowok & xin & (min(dv, dh) > ft);
-                ball[k] = __ballot(pass[k]);
+                ball[k] = __ballot(rowok & xin & (min(dv, dh) > ft));
                 total += __popcll(ball[k]);
             }
         }
@@ -399,7 +405,6 @@ __global__ __launch_bounds__(256) void fast_nms_kernel(Levels L, const uint8_t* 
                 const unsigned dh = max(__builtin_amdgcn_sad_u8(pp[3], v, 0u), __builtin_amdgcn_sad_u8(pp[-3], v, 0u));
                 ps = x >= 3 && x < d.w - 3 && y >= 3 && y < d.h - 3 && min(dv, dh) > ft;
             }
-            pass[FT_WR] = ps;
             ball[FT_WR] = __ballot(ps);
             total += __popcll(ball[FT_WR]);
         }
@@ -409,7 +414,7 @@ __global__ __launch_bounds__(256) void fast_nms_kernel(Levels L, const uint8_t* 
         const unsigned long long below = (1ull << lane) - 1ull;
 #pragma unroll
         for (int k = 0; k < FT_WR + 1; k++) {
-            if (pass[k]) {
+            if ((ball[k] >> lane) & 1ull) {
                 const int r = k < FT_WR ? r0 + k : r0 + (lane >> 1), c = k < FT_WR ? lane : FT_COLS + (lane & 1);
                 queue[base + __popcll(ball[k] & below)] = (unsigned short)(r * (FT_COLS + 2) + c);
             }
@@ -426,6 +431,7 @@ __global__ __launch_bounds__(256) void fast_nms_kernel(Levels L, const uint8_t* 
 #endif
     }
     __syncthreads();
+    lh[t] = 0;      // g is dead from here on: lxy, lsc and lh take its place (lh is next touched behind the barrier that ends the suppression)
     {
         // 3 x 3 strict non-max suppression of the corners, from the queue (1.4 % of the pixels have a score at all: a raster pass
         // over the tile read 9 scores per pixel for nothing).  Every lane takes part in every ballot: survivors are appended with
