@@ -73,8 +73,8 @@ JobCore::JobCore(const char* who, std::string where, int device, void* main_stre
     if (kind_ != MIS_WARP_SPHERICAL) {
         const float scale = warp_scale(everyone_);
         MisRect r;
-        // (the Mercator roi scans every source pixel: the batch entry runs that on the device, one call for all frames)
-        if (kind_ == MIS_WARP_MERCATOR) {
+        // (a roi that scans every source pixel: the batch entry runs that on the device, one call for all frames)
+        if (MIS_WARP_ROI_IS_FULL_SCAN(kind_)) {
             std::vector<MisRect> rr((size_t)n_);
             spec_ok_ = n_ == 0 || mis_warper_roi_batch(cctx_, kind_, scale, w_, h_, n_, Ks_.data(), Rs_.data(), rr.data()) == MIS_OK;
         } else

@@ -196,8 +196,8 @@ StitchResult Stitcher::stitch(const std::vector<HostImage>& frames, const std::v
         std::copy(R.m.begin(), R.m.end(), Rs[k].begin());
         std::copy(cK.m.begin(), cK.m.end(), cKs[k].begin());
         MisRect roi;
-        // (the Mercator roi scans every source pixel: the batch entry runs that on the device)
-        if ((kind == MIS_WARP_MERCATOR ? mis_warper_roi_batch(ctx_, kind, compose_warp_scale, cW, cH, 1, cKs[k].data(), Rs[k].data(), &roi)
+        // (a roi that scans every source pixel: the batch entry runs that on the device)
+        if ((MIS_WARP_ROI_IS_FULL_SCAN(kind) ? mis_warper_roi_batch(ctx_, kind, compose_warp_scale, cW, cH, 1, cKs[k].data(), Rs[k].data(), &roi)
                                        : mis_warper_roi(kind, compose_warp_scale, cW, cH, cKs[k].data(), Rs[k].data(), &roi)) != MIS_OK)
             throw std::runtime_error("mis_warper_roi failed: frame " + std::to_string(out.indices[k]) + " has no " + cfg_.warp_type + " warp roi");
         corners[k] = {roi.x, roi.y};

@@ -19,7 +19,15 @@ U8, S16, F32 = 0, 1, 2
 INTER_NEAREST, INTER_LINEAR = 0, 1
 BORDER_CONSTANT, BORDER_REFLECT = 0, 2
 BLEND_NO, BLEND_FEATHER, BLEND_MULTI_BAND = 0, 1, 2
-WARP_SPHERICAL, WARP_CYLINDRICAL, WARP_PLANE, WARP_MERCATOR = 0, 1, 2, 3
+WARP_SPHERICAL, WARP_CYLINDRICAL, WARP_PLANE, WARP_MERCATOR, WARP_FISHEYE, WARP_STEREOGRAPHIC = 0, 1, 2, 3, 4, 5
+
+
+def roi_is_full_scan(kind):
+    """MIS_WARP_ROI_IS_FULL_SCAN: the kinds whose warpRoi projects every source pixel (no detectResultRoi of their own), so the roi
+    belongs on the device (mis_warper_roi_batch) and is passed on to the warp instead of being computed again."""
+    return WARP_MERCATOR <= kind <= WARP_STEREOGRAPHIC
+
+
 MATH_LOG, MATH_TAN, MATH_SINH, MATH_ASIN, MATH_ATAN, MATH_EXP = 0, 1, 2, 3, 4, 5     # mis_debug_math_f32
 MATCH_HOMOGRAPHY, MATCH_AFFINE_PARTIAL = 0, 1
 EXPOS_NO, EXPOS_GAIN, EXPOS_GAIN_BLOCKS, EXPOS_CHANNELS, EXPOS_CHANNELS_BLOCKS = 0, 1, 2, 3, 4      # cv::detail::ExposureCompensator's values

@@ -1,4 +1,5 @@
-// warp.hip -- rotation warps, replaces the reference's cv::detail::{Spherical,Cylindrical,Plane,Mercator}Warper calls
+// warp.hip -- rotation warps, replaces the reference's cv::detail::{Spherical,Cylindrical,Plane,Mercator,Fisheye,
+// Stereographic}Warper calls
 // (the warp_type switch of image_stitching/image_stitching.cpp:917-969): :973/:1117 (create(scale)),
 // :985/:988/:1154/:1159 (warp), :1138 (warpRoi), :1164 (convertTo CV_16S, fused here).
 // The three kinds share one per-pixel form: x_ = su * s, z_ = cu * s, y_ = c with a column table {su, cu} and a row table
@@ -12,6 +13,8 @@
 // coordinates, Q15 weights, BORDER_REFLECT) writes the 16SC3 image and the 8U validity mask directly.
 // sin/cos of the column angle u and of the row angle v are separable: a tile computes them once
 // into LDS (128 + 16 evaluations per 2048 pixels).
+// The fisheye and stereographic maps are polar (u_ = atan2(v', u'), rho = |(u', v')|) and not separable: those two kinds evaluate
+// mapBackward per output pixel in kernels of their own (map_backward_polar, warp_polar_*), with the same sampling and stores.
 #include "common.h"
 #include "dev_math.h"
 #include <algorithm>
@@ -26,7 +29,9 @@ struct Projector {
     int kind;   // MIS_WARP_*
 };
 
-static bool kind_ok(int kind) { return kind == MIS_WARP_SPHERICAL || kind == MIS_WARP_CYLINDRICAL || kind == MIS_WARP_PLANE || kind == MIS_WARP_MERCATOR; }
+static bool kind_ok(int kind) { return kind >= MIS_WARP_SPHERICAL && kind <= MIS_WARP_STEREOGRAPHIC; }
+// the kinds whose backward map is evaluated per output pixel (no column / row tables)
+static bool kind_polar(int kind) { return kind == MIS_WARP_FISHEYE || kind == MIS_WARP_STEREOGRAPHIC; }
 
 // ProjectorBase::setCameraParams (stitching/src/warpers.cpp): float matrices, double intermediates
 void projector_set(Projector* p, int kind, float scale, const float K[9], const float R[9]) {
@@ -62,13 +67,33 @@ void projector_set(Projector* p, int kind, float scale, const float K[9], const 
         }
 }
 
-// {Spherical,Cylindrical,Plane,Mercator}Projector::mapForward (warpers_inl.hpp); the same float operations on the host and on the
-// device.  Returns z_ > 0 (the plane's corners must lie in front of the panorama plane).
+// {Spherical,Cylindrical,Plane,Mercator,Fisheye,Stereographic}Projector::mapForward (warpers_inl.hpp); the same float operations on
+// the host and on the device.  Returns z_ > 0 (the plane's corners must lie in front of the panorama plane).
+// LAST_KIND: the largest kind the caller can pass (the border walk never sees a kind whose roi is a full scan of its own kernel:
+// its instantiation leaves the polar branch out).
+// Fisheye / stereographic: no NaN guard and no special case at the singular points, as there: the stereographic quotient is 0 / 0 =
+// NaN on the ray (0, -1, 0) (v_ = 0) and huge next to it.
+template <int LAST_KIND = MIS_WARP_STEREOGRAPHIC>
 MIS_HD bool map_forward(int kind, const float* m, float scale, float x, float y, float* u, float* v) {
     float x_ = (m[0] * x + m[1] * y) + m[2];
     float y_ = (m[3] * x + m[4] * y) + m[5];
     float z_ = (m[6] * x + m[7] * y) + m[8];
-    if (kind == MIS_WARP_PLANE) {
+    if (LAST_KIND >= MIS_WARP_FISHEYE && (kind == MIS_WARP_FISHEYE || kind == MIS_WARP_STEREOGRAPHIC)) {
+        float u_ = mis_atan2f(x_, z_);
+        float v_ = MIS_PI_F - mis_acosf(y_ / sqrtf((x_ * x_ + y_ * y_) + z_ * z_));
+        float su, cu;
+        mis_sincosf(u_, &su, &cu);
+        if (kind == MIS_WARP_FISHEYE) {
+            *u = scale * v_ * cu;
+            *v = scale * v_ * su;
+        } else {
+            float sv, cv;
+            mis_sincosf(v_, &sv, &cv);
+            float r = sv / (1.f - cv);
+            *u = scale * r * cu;
+            *v = scale * r * su;
+        }
+    } else if (kind == MIS_WARP_PLANE) {
         *u = scale * (x_ / z_ * 1.f);
         *v = scale * (y_ / z_ * 1.f);
     } else if (kind == MIS_WARP_CYLINDRICAL) {
@@ -120,8 +145,9 @@ int roi_from_extremes(const Projector* p, int sw, int sh, float tl_uf, float tl_
 //  * spherical (SphericalWarper::detectResultRoi) and cylindrical (detectResultRoiByBorder): the 2(W+H) border pixels;
 //  * plane (PlaneWarper::detectResultRoi): the four corners (0,0), (0,h-1), (w-1,0), (w-1,h-1).  A corner with z_ <= 0 lies behind
 //    the panorama plane and OpenCV's rectangle means nothing: MIS_E_INVALID.
-//  * mercator (RotationWarperBase::detectResultRoi: MercatorWarper has no override): every pixel, O(w h).  With a pole inside the
-//    frame the extreme v lies at an interior pixel; a NaN (the upper pole) is skipped as std::min / std::max skip it.
+//  * mercator, fisheye, stereographic (RotationWarperBase::detectResultRoi: these warpers have no override): every pixel, O(w h).
+//    With a pole inside the frame the extreme lies at an interior pixel; a NaN (Mercator: the upper pole; stereographic: the ray
+//    (0, -1, 0)) is skipped as std::min / std::max skip it.
 int detect_result_roi(const Projector* p, int sw, int sh, int* tlx, int* tly, int* brx, int* bry) {
     float tl_uf = FLT_MAX, tl_vf = FLT_MAX, br_uf = -FLT_MAX, br_vf = -FLT_MAX, u, v;
     auto upd = [&]() {
@@ -136,7 +162,7 @@ int detect_result_roi(const Projector* p, int sw, int sh, int* tlx, int* tly, in
         bool front = true;
         for (int c = 0; c < 4; c++) { front &= map_forward(kind, p->r_kinv, p->scale, cx[c], cy[c], &u, &v); upd(); }
         if (!front) return MIS_E_INVALID;
-    } else if (kind == MIS_WARP_MERCATOR) {
+    } else if (MIS_WARP_ROI_IS_FULL_SCAN(kind)) {
         for (int y = 0; y < sh; ++y)
             for (int x = 0; x < sw; ++x) { map_forward(kind, p->r_kinv, p->scale, (float)x, (float)y, &u, &v); upd(); }
     } else {
@@ -193,7 +219,7 @@ __global__ __launch_bounds__(256) void warp_roi_kernel(RoiJob* jobs) {
         if (kind == MIS_WARP_PLANE) { x = i < 2 ? 0.f : (float)(sw - 1); y = (i & 1) ? (float)(sh - 1) : 0.f; }
         else if (i < 2 * sw) { x = (float)(i >> 1); y = (i & 1) ? (float)(sh - 1) : 0.f; }
         else { const int k = i - 2 * sw; y = (float)(k >> 1); x = (k & 1) ? (float)(sw - 1) : 0.f; }
-        if (!map_forward(kind, m, scale, x, y, &u, &v) && kind == MIS_WARP_PLANE) behind = 1;
+        if (!map_forward<MIS_WARP_MERCATOR>(kind, m, scale, x, y, &u, &v) && kind == MIS_WARP_PLANE) behind = 1;
         lo_u = fminf(lo_u, u); lo_v = fminf(lo_v, v); hi_u = fmaxf(hi_u, u); hi_v = fmaxf(hi_v, v);
     }
     for (int o = 32; o > 0; o >>= 1) {
@@ -212,13 +238,14 @@ __global__ __launch_bounds__(256) void warp_roi_kernel(RoiJob* jobs) {
     }
 }
 
-// The full-frame scan of RotationWarperBase::detectResultRoi (the Mercator kind): workgroup (c, f) projects rows
+// The full-frame scan of RotationWarperBase::detectResultRoi (the Mercator, fisheye and stereographic kinds): workgroup (c, f) projects rows
 // c * rows .. c * rows + rows - 1 of frame f, every pixel, and writes one partial {min u, min v, max u, max v} to part[f * nchunk + c]
 // (pinned, device-visible, behind the jobs).  The host takes the min / max of a frame's partials after the entry's one stream
 // synchronisation: min / max of floats with NaN skipped, any order gives the host loop's floats (+-0 apart, and (int) of both is 0).
-// Only the Mercator kind scans (the host checks it): map_forward takes the kind as a constant and the other kinds' branches are
-// not compiled into the loop.
+// One instantiation per scanning kind (the host picks it): map_forward takes the kind as a constant and the other kinds' branches
+// are not compiled into the loop.
 constexpr int ROI_SCAN_MAX_PARTS = 1024;    // partials per frame
+template <int KIND>
 __global__ __launch_bounds__(256) void warp_roi_scan_kernel(const RoiJob* jobs, float4* part, int rows, int nchunk) {
     const RoiJob* j = jobs + blockIdx.y;
     __shared__ float red[4][4];
@@ -226,7 +253,7 @@ __global__ __launch_bounds__(256) void warp_roi_scan_kernel(const RoiJob* jobs, 
     for (int i = 0; i < 9; i++) m[i] = j->r_kinv[i];
     const float scale = j->scale;
     const int sw = j->sw, sh = j->sh;
-    constexpr int kind = MIS_WARP_MERCATOR;
+    constexpr int kind = KIND;
     const int y0 = (int)blockIdx.x * rows, y1 = min(sh, y0 + rows);
     const unsigned npts = (unsigned)max(y1 - y0, 0) * (unsigned)sw;      // sizes <= 32767 (host check): below 2^30
     float lo_u = FLT_MAX, lo_v = FLT_MAX, hi_u = -FLT_MAX, hi_v = -FLT_MAX;
@@ -1457,6 +1484,116 @@ __global__ __launch_bounds__(256) void warp_u8_kernel(WarpArgs a) {
     }
 }
 
+// ---- the per-pixel map path: the kinds whose backward ray is not separable (fisheye, stereographic) ----
+// {Fisheye,Stereographic}Projector::mapBackward (warpers_inl.hpp), the reference's operation sequence kept literally: the polar angle
+// u_ = atan2(v', u') and the radius rho = |(u', v')| of the output pixel, the polar distance v_ = rho (fisheye) or 2 atan(1 / rho)
+// (stereographic), then the spherical ray of (u_, pi - v_) through k_rinv with the z > 0 test (map_backward).  Nothing is special-
+// cased at the centre pixel u' = v' = 0: atan2(0, 0) = 0; fisheye gets the ray (0, -1, 0); stereographic 1 / 0 = +inf,
+// atan(+inf) = pi / 2, v_ = pi, the ray (0, +1, 0).
+__device__ __forceinline__ void map_backward_polar(int kind, const float* m, float scale, float u, float v, float* x, float* y) {
+    const float up = u / scale, vp = v / scale;
+    const float u_ = mis_atan2f(vp, up);
+    float v_ = sqrtf(up * up + vp * vp);
+    if (kind == MIS_WARP_STEREOGRAPHIC) v_ = 2.f * mis_atanf(1.f / v_);
+    float sinv, cosv, sinu, cosu;
+    mis_sincosf(MIS_PI_F - v_, &sinv, &cosv);
+    mis_sincosf(u_, &sinu, &cosu);
+    map_backward(kind, m, sinu, cosu, sinv, cosv, x, y);
+}
+
+// Fused compose-scale warp of the polar kinds: 8UC3 source -> 16SC3 image + 8U mask, warp_fused_kernel's contract.  The map and
+// the sampling cost 478 (fisheye) / 532 (stereographic) vector instructions per pixel (four divisions, a square root, one or two
+// arctangents, two sincos, the 12-tap gather), so the kernel is issue bound and is kept simple: no tables, no LDS, the 12 taps per pixel gathered from global memory through L2 (the source footprint of
+// a 128 x 8 tile is compact under both maps).  A lane owns PP_LPX = 4 consecutive pixels of one row: its 16SC3 output is 24 bytes =
+// six whole dwords, its mask two 16-bit words (mask rows are 2-byte aligned only), and adjacent lanes write adjacent addresses; 32 lanes cover a tile row, a wave two rows,
+// the four waves of a workgroup the tile's 8 rows.  Tiles are numbered row-major over the roi in a one-dimensional grid.
+constexpr int PP_LPX = 4, PP_TW = 32 * PP_LPX, PP_TH = 8;
+static long long polar_tiles_of(const WarpArgs& a) { return (long long)((a.dw + PP_TW - 1) / PP_TW) * ((a.dh + PP_TH - 1) / PP_TH); }
+
+template <int KIND>
+__device__ __forceinline__ void polar_fused_tile(const WarpArgs& a, int tile) {
+    const int tiles_x = (a.dw + PP_TW - 1) / PP_TW;
+    const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
+    const int gx0 = tx * PP_TW + ((int)threadIdx.x & 31) * PP_LPX, gy = ty * PP_TH + ((int)threadIdx.x >> 5);
+    if (gx0 >= a.dw || gy >= a.dh) return;
+    const float v = (float)(a.tly + gy);
+    unsigned short px[PP_LPX * 3];
+    uint8_t mk[PP_LPX];
+#pragma unroll
+    for (int i = 0; i < PP_LPX; i++) {
+        float x, y;
+        int p[3], sx, sy;
+        map_backward_polar(KIND, a.m, a.scale, (float)(a.tlx + gx0 + i), v, &x, &y);     // (columns past the roi are computed and not stored)
+        sample_linear<3>(a.src, a.sstride, a.sw, a.sh, x, y, p);
+        px[3 * i] = (unsigned short)p[0]; px[3 * i + 1] = (unsigned short)p[1]; px[3 * i + 2] = (unsigned short)p[2];
+        mk[i] = nearest_inside(a.sw, a.sh, x, y, &sx, &sy) ? 255 : 0;
+    }
+    uint8_t* drow = (uint8_t*)a.dst + (size_t)gy * a.dstride + (size_t)gx0 * 6;      // 4-byte aligned: rows are (host check), gx0 * 6 = 24 k
+    uint8_t* mrow = a.mask + (size_t)gy * a.mstride + gx0;                           // 2-byte aligned: rows are, gx0 = 4 k
+    if (gx0 + PP_LPX <= a.dw) {
+        uint32_t* d = (uint32_t*)drow;
+#pragma unroll
+        for (int k = 0; k < PP_LPX * 3 / 2; k++) d[k] = (uint32_t)px[2 * k] | ((uint32_t)px[2 * k + 1] << 16);
+        unsigned short* q = (unsigned short*)mrow;
+        q[0] = (unsigned short)(mk[0] | (mk[1] << 8));
+        q[1] = (unsigned short)(mk[2] | (mk[3] << 8));
+    } else {
+        for (int i = 0; i < a.dw - gx0; i++) {
+            short* d = (short*)drow + 3 * i;
+            d[0] = (short)px[3 * i]; d[1] = (short)px[3 * i + 1]; d[2] = (short)px[3 * i + 2];
+            mrow[i] = mk[i];
+        }
+    }
+}
+
+template <int KIND>
+__global__ __launch_bounds__(256) void warp_polar_fused_kernel(WarpArgs a) {
+    polar_fused_tile<KIND>(a, (int)blockIdx.x);
+}
+
+// the compose loop's grid: the tiles of all frames of a batch, frame after frame, in one one-dimensional grid
+struct PolarBatch {
+    WarpArgs a[WB_MAX];
+    int wg_base[WB_MAX + 1];    // frame k owns workgroups wg_base[k] .. wg_base[k + 1] - 1; frames past the batch own none
+};
+template <int KIND>
+__global__ __launch_bounds__(256) void warp_polar_fused_batch_kernel(PolarBatch b) {
+    const int bid = (int)blockIdx.x;
+    int fi = 0;
+#pragma unroll
+    for (int k = 1; k < WB_MAX; k++) fi += bid >= b.wg_base[k] ? 1 : 0;       // (uniform: scalar compares on the kernel arguments)
+    polar_fused_tile<KIND>(b.a[fi], bid - b.wg_base[fi]);
+}
+
+// General warp of the polar kinds (seam-scale images and plain masks): warp_u8_kernel without its tables, one column per lane
+template <int CN, bool LINEAR>
+__global__ __launch_bounds__(256) void warp_polar_u8_kernel(WarpArgs a) {
+    const int tx0 = blockIdx.x * TILE_W, ty0 = blockIdx.y * TILE_H;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int half = 0; half < 2; half++) {
+        const int gx = tx0 + lane + 64 * half;
+        if (gx >= a.dw) continue;
+        for (int i = 0; i < 4; i++) {
+            const int gy = ty0 + wave * 4 + i;
+            if (gy >= a.dh) break;
+            float x, y;
+            map_backward_polar(a.kind, a.m, a.scale, (float)(a.tlx + gx), (float)(a.tly + gy), &x, &y);     // (the kind is uniform)
+            uint8_t* d = (uint8_t*)a.dst + (size_t)gy * a.dstride + (size_t)gx * CN;
+            if (LINEAR) {
+                int p[CN];
+                sample_linear<CN>(a.src, a.sstride, a.sw, a.sh, x, y, p);
+#pragma unroll
+                for (int c = 0; c < CN; c++) d[c] = (uint8_t)p[c];
+            } else {
+                int sx, sy;
+                bool in = nearest_inside(a.sw, a.sh, x, y, &sx, &sy);
+#pragma unroll
+                for (int c = 0; c < CN; c++) d[c] = in ? a.src[(size_t)sy * a.sstride + (size_t)sx * CN + c] : (uint8_t)0;
+            }
+        }
+    }
+}
+
 // `known`: the roi warpRoi / mis_warp_roi_batch returned for exactly these (scale, K, R, size) -- skips the border walk
 int setup(MisContext* ctx, int kind, const MisImage* src, float scale, const float K[9], const float R[9], WarpArgs* a, int* brx, int* bry, const MisRect* known = nullptr) {
     MIS_CHECK(ctx, kind_ok(kind), MIS_E_UNSUPPORTED, "unknown warp kind %d", kind);
@@ -1471,7 +1608,7 @@ int setup(MisContext* ctx, int kind, const MisImage* src, float scale, const flo
     if (known) {
         projector_set(&p, kind, scale, K, R);
         tlx = known->x; tly = known->y; *brx = known->x + known->width - 1; *bry = known->y + known->height - 1;
-    } else if (kind == MIS_WARP_MERCATOR) {
+    } else if (MIS_WARP_ROI_IS_FULL_SCAN(kind)) {
         // the full-frame scan runs on the device (the host loop of mis_warper_roi is O(w h)); same roi by construction
         MisRect r;
         int rc;
@@ -1516,7 +1653,7 @@ extern "C" int mis_debug_warp_stamps(unsigned long long* out, int n) {
 extern "C" int mis_warper_roi(int kind, float scale, int w, int h, const float K[9], const float R[9], MisRect* roi) {
     if (!kind_ok(kind)) return MIS_E_UNSUPPORTED;
     if (!K || !R || !roi || w < 1 || h < 1 || !(scale > 0.f)) return MIS_E_INVALID;
-    if (kind == MIS_WARP_MERCATOR && (w > 32767 || h > 32767)) return MIS_E_INVALID;     // a frame the warps refuse; the scan is O(w h)
+    if (MIS_WARP_ROI_IS_FULL_SCAN(kind) && (w > 32767 || h > 32767)) return MIS_E_INVALID;     // a frame the warps refuse; the scan is O(w h)
     Projector p;
     int tlx, tly, brx, bry, rc;
     if ((rc = projector_and_roi(kind, scale, K, R, w, h, &p, &tlx, &tly, &brx, &bry)) != MIS_OK) return rc;
@@ -1542,7 +1679,16 @@ static int warp_u8_impl(MisContext* ctx, int kind, const MisImage* src, float sc
     a.src = (const uint8_t*)din.data; a.sstride = din.stride;
     a.dst = dout.data; a.dstride = dout.stride; a.mask = nullptr; a.mstride = 0;
     dim3 grid((a.dw + TILE_W - 1) / TILE_W, (a.dh + TILE_H - 1) / TILE_H), block(256);
-    if (src->channels == 3) {
+    if (kind_polar(kind)) {
+        MIS_CHECK(ctx, grid.y <= 65535u, MIS_E_INVALID, "warp roi %dx%d: too many rows for one launch", a.dw, a.dh);
+        if (src->channels == 3) {
+            if (interp == MIS_INTER_LINEAR) hipLaunchKernelGGL((warp_polar_u8_kernel<3, true>), grid, block, 0, ctx->stream, a);
+            else hipLaunchKernelGGL((warp_polar_u8_kernel<3, false>), grid, block, 0, ctx->stream, a);
+        } else {
+            if (interp == MIS_INTER_LINEAR) hipLaunchKernelGGL((warp_polar_u8_kernel<1, true>), grid, block, 0, ctx->stream, a);
+            else hipLaunchKernelGGL((warp_polar_u8_kernel<1, false>), grid, block, 0, ctx->stream, a);
+        }
+    } else if (src->channels == 3) {
         if (interp == MIS_INTER_LINEAR) hipLaunchKernelGGL((warp_u8_kernel<3, true>), grid, block, 0, ctx->stream, a);
         else hipLaunchKernelGGL((warp_u8_kernel<3, false>), grid, block, 0, ctx->stream, a);
     } else {
@@ -1574,6 +1720,59 @@ extern "C" int mis_warp_spherical(MisContext* ctx, const MisImage* src, float sc
     return mis_warper_warp(ctx, MIS_WARP_SPHERICAL, src, scale, K, R, interp, border, dst, tl);
 }
 
+// events around `repeats` back-to-back launches (the measurement aid of the fused entries): begin() before, end() after
+struct RepeatTimer {
+    OwnedEvent e0, e1;
+    int begin(MisContext* ctx, float* avg_us) {
+        if (!avg_us) return MIS_OK;
+        MIS_HIP(ctx, e0.ready(hipEventDefault));
+        MIS_HIP(ctx, e1.ready(hipEventDefault));
+        MIS_HIP(ctx, hipEventRecord(e0.ev, ctx->stream));
+        return MIS_OK;
+    }
+    int end(MisContext* ctx, int repeats, float* avg_us) {
+        if (!avg_us) return MIS_OK;
+        float ms = 0.f;
+        MIS_HIP(ctx, hipEventRecord(e1.ev, ctx->stream));
+        MIS_HIP(ctx, hipEventSynchronize(e1.ev));
+        MIS_HIP(ctx, hipEventElapsedTime(&ms, e0.ev, e1.ev));
+        *avg_us = ms * 1000.f / (float)repeats;
+        return MIS_OK;
+    }
+};
+
+// the outputs of a fused warp: views, the alignment the kernels' dword / word stores need, pointers into the arguments
+static int fused_outputs(MisContext* ctx, WarpArgs& a, const MisImage* src, MisImage* dst, MisImage* dmask, DevView& din, DevView& dout, DevView& dm) {
+    int rc;
+    if ((rc = din.read(ctx, src)) != MIS_OK) return rc;
+    if ((rc = dout.write(ctx, dst, a.dw, a.dh, 3, MIS_S16)) != MIS_OK) return rc;
+    if ((rc = dm.write(ctx, dmask, a.dw, a.dh, 1, MIS_U8)) != MIS_OK) return rc;
+    MIS_CHECK(ctx, dout.stride % 4 == 0 && dm.stride % 2 == 0 && ((uintptr_t)dout.data % 4) == 0 && ((uintptr_t)dm.data % 2) == 0,
+              MIS_E_INVALID, "fused warp outputs need 4-byte (image) / 2-byte (mask) aligned rows");
+    a.src = (const uint8_t*)din.data; a.sstride = din.stride;
+    a.dst = dout.data; a.dstride = dout.stride; a.mask = (uint8_t*)dm.data; a.mstride = dm.stride;
+    return MIS_OK;
+}
+
+// one frame of a polar kind (setup() done): its tiles in one grid
+static int warp_polar_fused_one(MisContext* ctx, WarpArgs& a, const MisImage* src, MisImage* dst, MisImage* dmask, MisPoint* tl, int repeats, float* avg_us) {
+    MIS_HIP(ctx, hipSetDevice(ctx->device));
+    DevView din, dout, dm;
+    int rc;
+    if ((rc = fused_outputs(ctx, a, src, dst, dmask, din, dout, dm)) != MIS_OK) return rc;
+    const long long tiles = polar_tiles_of(a);       // area < 2^31 (setup): below 2^31 too
+    RepeatTimer t;
+    if ((rc = t.begin(ctx, avg_us)) != MIS_OK) return rc;
+    for (int rep = 0; rep < repeats; rep++)
+        if (a.kind == MIS_WARP_FISHEYE) hipLaunchKernelGGL(warp_polar_fused_kernel<MIS_WARP_FISHEYE>, dim3((unsigned)tiles), dim3(256), 0, ctx->stream, a);
+        else hipLaunchKernelGGL(warp_polar_fused_kernel<MIS_WARP_STEREOGRAPHIC>, dim3((unsigned)tiles), dim3(256), 0, ctx->stream, a);
+    if ((rc = t.end(ctx, repeats, avg_us)) != MIS_OK) return rc;
+    MIS_HIP(ctx, hipGetLastError());
+    if ((rc = dout.commit()) != MIS_OK || (rc = dm.commit()) != MIS_OK) return rc;
+    if (tl) { tl->x = a.tlx; tl->y = a.tly; }
+    return MIS_OK;
+}
+
 static int grid_of(const WarpArgs& a);
 static int warp_fused_batch_impl(MisContext* ctx, int kind, const MisImage* srcs, int n, float scale, const float* Ks, const float* Rs, const MisRect* rois,
                                  MisImage* dsts, MisImage* dmasks, MisPoint* tls, int repeats, float* avg_us);
@@ -1584,6 +1783,7 @@ static int warp_fused_impl(MisContext* ctx, int kind, const MisImage* src, float
     int brx, bry, rc;
     if ((rc = setup(ctx, kind, src, scale, K, R, &a, &brx, &bry, known_roi)) != MIS_OK) return rc;
     MIS_CHECK(ctx, src->channels == 3, MIS_E_UNSUPPORTED, "fused warp needs an 8UC3 source");
+    if (kind_polar(kind)) return warp_polar_fused_one(ctx, a, src, dst, dmask, tl, repeats, avg_us);
     if (kind != MIS_WARP_SPHERICAL && !fast_z_bound_ok(a) && repeats == 1 && !avg_us) {
         // the one-frame kernel's z guard is the spherical one: a roi this far out goes through the batch form (same results)
         const MisRect r{a.tlx, a.tly, a.dw, a.dh};
@@ -1686,8 +1886,39 @@ static int warp_fused_batch_impl(MisContext* ctx, int kind, const MisImage* srcs
         tab_off[i] = tab_total;
         tab_total += mis_align_up(sizeof(float) * trig_table_floats(a.dw, a.dh), 256);
     }
+    if (rc != MIS_OK) return rc;
+    if (kind_polar(kind)) {
+        // the per-pixel map: no tables, no strips; the tiles of up to WB_MAX frames per launch
+        std::vector<PolarBatch> batches;
+        for (int g0 = 0; g0 < n; g0 += WB_MAX) {
+            const int ng = std::min(WB_MAX, n - g0);
+            PolarBatch b;
+            long long wg = 0;
+            for (int k = 0; k < WB_MAX; k++) {
+                b.a[k] = args[g0 + (k < ng ? k : 0)];
+                b.wg_base[k] = (int)wg;
+                if (k < ng) wg += polar_tiles_of(args[g0 + k]);
+                MIS_CHECK(ctx, wg <= INT_MAX, MIS_E_INVALID, "frames %d..%d: too many tiles for one launch", g0, g0 + k);
+            }
+            b.wg_base[WB_MAX] = (int)wg;
+            batches.push_back(b);
+        }
+        RepeatTimer t;
+        if ((rc = t.begin(ctx, avg_us)) != MIS_OK) return rc;
+        for (int rep = 0; rep < repeats; rep++)
+            for (const PolarBatch& b : batches)
+                if (kind == MIS_WARP_FISHEYE) hipLaunchKernelGGL(warp_polar_fused_batch_kernel<MIS_WARP_FISHEYE>, dim3(b.wg_base[WB_MAX]), dim3(256), 0, ctx->stream, b);
+                else hipLaunchKernelGGL(warp_polar_fused_batch_kernel<MIS_WARP_STEREOGRAPHIC>, dim3(b.wg_base[WB_MAX]), dim3(256), 0, ctx->stream, b);
+        if ((rc = t.end(ctx, repeats, avg_us)) != MIS_OK) return rc;
+        MIS_HIP(ctx, hipGetLastError());
+        for (int i = 0; i < n; i++) {
+            if (rc == MIS_OK && (rc = dout[i].commit()) == MIS_OK) rc = dm[i].commit();
+            if (tls) { tls[i].x = args[i].tlx; tls[i].y = args[i].tly; }
+        }
+        return rc;
+    }
     uint8_t* tabs = nullptr;
-    if (rc != MIS_OK || (rc = mis_dev_stage(ctx, tab_total, (void**)&tabs)) != MIS_OK) return rc;
+    if ((rc = mis_dev_stage(ctx, tab_total, (void**)&tabs)) != MIS_OK) return rc;
     OwnedEvent e0, e1;
     std::vector<V3Batch> v3batches;
     int nt3 = 1 << 30;      // tiles per strip: one value for the grid (the smallest any frame asks for)
@@ -1767,11 +1998,11 @@ extern "C" int mis_warper_roi_batch(MisContext* ctx, int kind, float scale, int 
     if (!ctx) return MIS_E_INVALID;
     MIS_CHECK(ctx, kind_ok(kind), MIS_E_UNSUPPORTED, "unknown warp kind %d", kind);
     MIS_CHECK(ctx, Ks && Rs && rois && n >= 1 && w >= 1 && h >= 1 && scale > 0.f, MIS_E_INVALID, "invalid argument");
-    const bool scan = kind == MIS_WARP_MERCATOR;
+    const bool scan = MIS_WARP_ROI_IS_FULL_SCAN(kind);
     MIS_CHECK(ctx, !scan || (w <= 32767 && h <= 32767), MIS_E_INVALID, "source size %dx%d out of range", w, h);
     MIS_CHECK(ctx, !scan || n <= 65535, MIS_E_INVALID, "%d frames in one roi call (at most 65535)", n);     // the grid's y extent; before anything is sized by n
     MIS_HIP(ctx, hipSetDevice(ctx->device));
-    // the Mercator scan's partials lie behind the jobs in the same pinned block
+    // the scan's partials lie behind the jobs in the same pinned block
     const int rows = scan ? roi_scan_rows(w, h) : 0, nchunk = scan ? (h + rows - 1) / rows : 0;
     const size_t part_off = mis_align_up(sizeof(RoiJob) * (size_t)n, 16);
     const size_t need = part_off + sizeof(float4) * (size_t)n * nchunk;
@@ -1788,7 +2019,9 @@ extern "C" int mis_warper_roi_batch(MisContext* ctx, int kind, float scale, int 
         jobs[i].scale = scale; jobs[i].sw = w; jobs[i].sh = h; jobs[i].kind = kind; jobs[i].behind = 0;
     }
     float4* part = (float4*)((uint8_t*)ctx->roi_pinned + part_off);
-    if (scan) hipLaunchKernelGGL(warp_roi_scan_kernel, dim3(nchunk, n), dim3(256), 0, ctx->stream, (const RoiJob*)jobs, part, rows, nchunk);
+    if (kind == MIS_WARP_MERCATOR) hipLaunchKernelGGL(warp_roi_scan_kernel<MIS_WARP_MERCATOR>, dim3(nchunk, n), dim3(256), 0, ctx->stream, (const RoiJob*)jobs, part, rows, nchunk);
+    else if (kind == MIS_WARP_FISHEYE) hipLaunchKernelGGL(warp_roi_scan_kernel<MIS_WARP_FISHEYE>, dim3(nchunk, n), dim3(256), 0, ctx->stream, (const RoiJob*)jobs, part, rows, nchunk);
+    else if (kind == MIS_WARP_STEREOGRAPHIC) hipLaunchKernelGGL(warp_roi_scan_kernel<MIS_WARP_STEREOGRAPHIC>, dim3(nchunk, n), dim3(256), 0, ctx->stream, (const RoiJob*)jobs, part, rows, nchunk);
     else hipLaunchKernelGGL(warp_roi_kernel, dim3(n), dim3(256), 0, ctx->stream, jobs);
     MIS_HIP(ctx, hipGetLastError());
     MIS_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1804,7 +2037,7 @@ extern "C" int mis_warper_roi_batch(MisContext* ctx, int kind, float scale, int 
         }
         MIS_CHECK(ctx, !jobs[i].behind, MIS_E_INVALID, "frame %d: warp roi refused: a corner of the frame lies behind the panorama plane", i);
         MIS_CHECK(ctx, roi_from_extremes(&proj[i], w, h, jobs[i].ext[0], jobs[i].ext[1], jobs[i].ext[2], jobs[i].ext[3], &tlx, &tly, &brx, &bry) == MIS_OK,
-                  MIS_E_INVALID, "frame %d: warp roi refused: %s projects to a non-finite extreme", i, scan ? "a pixel (the lower pole)" : "the border");
+                  MIS_E_INVALID, "frame %d: warp roi refused: %s projects to a non-finite extreme", i, kind == MIS_WARP_MERCATOR ? "a pixel (the lower pole)" : scan ? "a pixel" : "the border");
         MIS_CHECK(ctx, roi_rect(tlx, tly, brx, bry, &rois[i]) == MIS_OK, MIS_E_INVALID, "frame %d: warp roi %d..%d x %d..%d does not fit an int size",
                   i, tlx, brx, tly, bry);
     }

@@ -303,7 +303,7 @@ class HipEngine:
 
     # ---- compose ----
     def warp_roi(self, scale, cam, size=None):
-        if self.kind == capi.WARP_MERCATOR:      # a scan of every source pixel: on the device, never the host loop at frame size
+        if capi.roi_is_full_scan(self.kind):     # a scan of every source pixel: on the device, never the host loop at frame size
             return self.warp_rois(scale, [cam], size)[0]
         return st.warp_roi(scale, size or self.frame_size, cam["K"], cam["R"], self.kind)
 
@@ -712,8 +712,8 @@ class StitchJob:
             return True
         g = st.compose_geometry(self.cfg, self.frame_size, st.Stitcher.warped_image_scale(self.cams), self.work_scale)
         try:
-            if self.kind == capi.WARP_MERCATOR and hasattr(self.engine, "warp_rois"):
-                # the Mercator roi scans every source pixel: one device call for all frames, never the host loop at frame size
+            if capi.roi_is_full_scan(self.kind) and hasattr(self.engine, "warp_rois"):
+                # such a roi scans every source pixel: one device call for all frames, never the host loop at frame size
                 self.engine.warp_rois(g.warp_scale, [st.scaled_camera(c, g.aspect) if g.aspect != 1.0 else c for c in self.cams], g.size)
                 return True
             for c in self.cams:

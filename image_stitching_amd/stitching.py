@@ -119,11 +119,12 @@ class Context:
 
 
 # ------------------------------------------------------------------------------------------------
-# warp: cv::detail::{Spherical,Cylindrical,Plane,Mercator}Warper, chosen by warp_type (image_stitching.cpp:917-969; :973, :985, :988,
+# warp: cv::detail::{Spherical,Cylindrical,Plane,Mercator,Fisheye,Stereographic}Warper, chosen by warp_type (image_stitching.cpp:917-969; :973, :985, :988,
 # :1117, :1138, :1154, :1159)
-WARP_KINDS = {"spherical": capi.WARP_SPHERICAL, "cylindrical": capi.WARP_CYLINDRICAL, "plane": capi.WARP_PLANE, "mercator": capi.WARP_MERCATOR}
+WARP_KINDS = {"spherical": capi.WARP_SPHERICAL, "cylindrical": capi.WARP_CYLINDRICAL, "plane": capi.WARP_PLANE, "mercator": capi.WARP_MERCATOR,
+              "fisheye": capi.WARP_FISHEYE, "stereographic": capi.WARP_STEREOGRAPHIC}
 # the reference's other warp_type names (image_stitching.cpp:933-964): known there, not built here
-UNBUILT_WARP_TYPES = ("affine", "fisheye", "stereographic", "compressedPlaneA2B1", "compressedPlaneA1.5B1", "compressedPlanePortraitA2B1",
+UNBUILT_WARP_TYPES = ("affine", "compressedPlaneA2B1", "compressedPlaneA1.5B1", "compressedPlanePortraitA2B1",
                       "compressedPlanePortraitA1.5B1", "paniniA2B1", "paniniA1.5B1", "paniniPortraitA2B1", "paniniPortraitA1.5B1",
                       "transverseMercator")
 
@@ -134,8 +135,9 @@ def warp_kind(warp_type):
     if warp_type in WARP_KINDS:
         return WARP_KINDS[warp_type]
     if warp_type in UNBUILT_WARP_TYPES:
-        raise NotImplementedError("warp_type %r: only 'spherical', 'cylindrical', 'plane' and 'mercator' are implemented (the warpers of "
-                                  "the reference's GPU branch, image_stitching.cpp:921-931, and its Mercator warper; DESIGN.md section 8)"
+        raise NotImplementedError("warp_type %r: only 'spherical', 'cylindrical', 'plane', 'mercator', 'fisheye' and 'stereographic' are "
+                                  "implemented (the warpers of the reference's GPU branch, image_stitching.cpp:921-931, and its Mercator, "
+                                  "fisheye and stereographic warpers; DESIGN.md section 8)"
                                   % (warp_type,))
     raise ValueError("warp_type %r: not a warper the reference knows (image_stitching.cpp:917-969)" % (warp_type,))
 
@@ -179,9 +181,10 @@ class RotationWarper:
         return self.warp_roi(src_size, K, R)
 
     def warp_roi(self, src_size, K, R):
-        """warpRoi.  The Mercator roi is a scan of every source pixel (cv::MercatorWarper has no detectResultRoi of its own): with a
-        context at hand it runs on the device (warp_rois); the other kinds walk the border or the corners on the host."""
-        if self.kind == capi.WARP_MERCATOR and self.ctx is not None:
+        """warpRoi.  The Mercator, fisheye and stereographic rois are a scan of every source pixel (those warpers have no
+        detectResultRoi of their own): with a context at hand it runs on the device (warp_rois); the other kinds walk the border or
+        the corners on the host."""
+        if capi.roi_is_full_scan(self.kind) and self.ctx is not None:
             return warp_rois(self.ctx, self.scale, src_size, [{"K": K, "R": R}], self.kind)[0]
         return warp_roi(self.scale, src_size, K, R, self.kind)
 
@@ -194,7 +197,7 @@ class RotationWarper:
         ka, kp = _mat9(K)
         ra, rp = _mat9(R)
         tl = capi.MisPoint()
-        if self.kind == capi.WARP_MERCATOR:     # the roi that sized dst was a scan of every source pixel: passed on, not computed again
+        if capi.roi_is_full_scan(self.kind):    # the roi that sized dst was a scan of every source pixel: passed on, not computed again
             rr = capi.MisRect(int(x), int(y), int(w), int(h))
             self.ctx.check(self.ctx.lib.mis_warper_warp_roi(self.ctx.h, self.kind, C.byref(simg), self.scale, kp, rp, C.byref(rr), interp, border,
                                                             C.byref(dimg), C.byref(tl)))
@@ -301,6 +304,16 @@ class PlaneWarper(RotationWarper):
 class MercatorWarper(RotationWarper):
     """MercatorWarper::create(scale) (image_stitching.cpp:961-962)."""
     kind = capi.WARP_MERCATOR
+
+
+class FisheyeWarper(RotationWarper):
+    """FisheyeWarper::create(scale) (image_stitching.cpp:941-942): the polar map, evaluated per output pixel."""
+    kind = capi.WARP_FISHEYE
+
+
+class StereographicWarper(RotationWarper):
+    """StereographicWarper::create(scale) (image_stitching.cpp:943-944): the polar map, evaluated per output pixel."""
+    kind = capi.WARP_STEREOGRAPHIC
 
 
 def make_warper(ctx, scale, warp_type="spherical"):
@@ -1299,7 +1312,7 @@ class StitchConfig:
     match_conf: float = 0.32
     range_width: int = -1             # -1: all pairs; w >= 1: BestOf2NearestRangeMatcher, pairs with j < i + w only (:83, :646-649)
     matcher_type: str = "homography"  # "homography" | "affine": AffineBestOf2NearestMatcher(false, ...), all pairs (:64, :644-645)
-    warp_type: str = "spherical"      # "spherical" | "cylindrical" | "plane" | "mercator" (:917-969; the other names raise by name, warp_kind)
+    warp_type: str = "spherical"      # "spherical" | "cylindrical" | "plane" | "mercator" | "fisheye" | "stereographic" (:917-969; the other names raise by name, warp_kind)
     blend_type: int = capi.BLEND_MULTI_BAND
     blend_strength: float = 5.0
     # camera refinement between matching and warping (image_stitching.cpp:681-726).  The reference's default is

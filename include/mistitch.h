@@ -40,9 +40,14 @@ enum { MIS_MEM_HOST = 0, MIS_MEM_DEVICE = 1 };
 enum { MIS_U8 = 0, MIS_S16 = 1, MIS_F32 = 2 };
 enum { MIS_INTER_NEAREST = 0, MIS_INTER_LINEAR = 1 };          /* cv::INTER_NEAREST / INTER_LINEAR */
 enum { MIS_BORDER_CONSTANT = 0, MIS_BORDER_REFLECT = 2 };       /* cv::BORDER_CONSTANT / BORDER_REFLECT */
-/* the warper kinds of the reference's GPU branch (warp_type, image_stitching.cpp:917-969) and its Mercator warper (:961-962); the float
- * maps are those of OpenCV's Spherical / Cylindrical / Plane (T = 0) / Mercator projectors, CPU path */
-enum { MIS_WARP_SPHERICAL = 0, MIS_WARP_CYLINDRICAL = 1, MIS_WARP_PLANE = 2, MIS_WARP_MERCATOR = 3 };
+/* the warper kinds of the reference's GPU branch (warp_type, image_stitching.cpp:917-969), its Mercator warper (:961-962) and its
+ * fisheye (:941-942) and stereographic (:943-944) warpers; the float maps are those of OpenCV's Spherical / Cylindrical / Plane (T = 0) /
+ * Mercator / Fisheye / Stereographic projectors, CPU path.  The first four have a separable backward ray (column and row tables, no
+ * transcendental per pixel); the fisheye and stereographic maps are polar and are evaluated per output pixel. */
+enum { MIS_WARP_SPHERICAL = 0, MIS_WARP_CYLINDRICAL = 1, MIS_WARP_PLANE = 2, MIS_WARP_MERCATOR = 3, MIS_WARP_FISHEYE = 4, MIS_WARP_STEREOGRAPHIC = 5 };
+/* the kinds whose warper has no detectResultRoi of its own: RotationWarperBase::detectResultRoi projects EVERY source pixel forward.
+ * For these mis_warper_roi is O(width * height) on the host and mis_warper_roi_batch a grid-wide reduction on the device. */
+#define MIS_WARP_ROI_IS_FULL_SCAN(kind) ((kind) >= MIS_WARP_MERCATOR && (kind) <= MIS_WARP_STEREOGRAPHIC)
 enum { MIS_BLEND_NO = 0, MIS_BLEND_FEATHER = 1, MIS_BLEND_MULTI_BAND = 2 }; /* cv::detail::Blender::NO/FEATHER/MULTI_BAND */
 
 typedef struct MisContext MisContext;
@@ -267,19 +272,22 @@ int mis_warp_spherical_fused_batch_timed(MisContext* ctx, const MisImage* srcs_u
 int mis_warp_spherical_fused_timed(MisContext* ctx, const MisImage* src_bgr, float scale, const float K[9], const float R[9],
                                    MisImage* dst_s16x3, MisImage* dst_mask, MisPoint* tl, int repeats, float* avg_us);
 /* The warpers of any kind (MIS_WARP_*): warper_creator = makePtr<{Spherical,Cylindrical,Plane}WarperGpu>() or
- * makePtr<MercatorWarper>() of image_stitching.cpp:917-969, then create(scale) (:973, :1117).  Each entry is the spherical one above with the kind added; the
+ * makePtr<{Mercator,Fisheye,Stereographic}Warper>() of image_stitching.cpp:917-969, then create(scale) (:973, :1117).  Each entry is the spherical one above with the kind added; the
  * spherical entries are these with MIS_WARP_SPHERICAL.  An unknown kind returns MIS_E_UNSUPPORTED.
  * Departures from OpenCV, each where OpenCV returns a meaningless rectangle: a plane roi with a corner behind the panorama plane
- * (z_ <= 0) and a cylindrical or Mercator roi with a non-finite extreme (Mercator: a source pixel at the lower pole projects to
- * v = -inf) return MIS_E_INVALID.  A roi whose width or height does not fit an int (any kind) is MIS_E_INVALID too, never a
+ * (z_ <= 0) and a cylindrical, Mercator, fisheye or stereographic roi with a non-finite extreme (Mercator: a source pixel at the
+ * lower pole projects to v = -inf; stereographic: a source pixel next to the ray (0, -1, 0) has 1 - cos v_ = 0 under a non-zero
+ * sin v_ and projects to +-inf, the pixel exactly on it gives 0 / 0 = NaN and is skipped) return MIS_E_INVALID.  A roi whose width or height does not fit an int (any kind) is MIS_E_INVALID too, never a
  * wrapped size. */
 /* warper->warpRoi(sz, K, R) -- replaces :1138.  Plane: the four corners (PlaneWarper::detectResultRoi); cylindrical: the border.
  * Mercator: cv::MercatorWarper has no detectResultRoi of its own, so RotationWarperBase projects EVERY source pixel forward and
  * takes the four extremes; this context-free entry does the same in a plain host loop and is O(width * height) for that kind (a
- * 4K frame: 8.3 M projections).  mis_warper_roi_batch and every entry with a context run that scan on the device. */
+ * 4K frame: 8.3 M projections).  mis_warper_roi_batch and every entry with a context run that scan on the device.  Fisheye and
+ * stereographic: the same (MIS_WARP_ROI_IS_FULL_SCAN). */
 int mis_warper_roi(int kind, float scale, int src_width, int src_height, const float K[9], const float R[9], MisRect* roi);
 /* the warpRoi loop of :1119-1140 in one call (one small kernel; the same rois as mis_warper_roi; the message names a refused frame).
- * Mercator: one grid-wide reduction over all pixels of all n frames, still one launch and one stream synchronisation. */
+ * Mercator, fisheye, stereographic: one grid-wide reduction over all pixels of all n frames, still one launch and one stream
+ * synchronisation. */
 int mis_warper_roi_batch(MisContext* ctx, int kind, float scale, int src_width, int src_height, int n, const float* Ks, const float* Rs,
                          MisRect* rois);
 /* warper->warp(src, K, R, interp, border, dst) -- replaces :985, :988, :1154, :1159 (u8, 1 or 3 channels) */
@@ -289,7 +297,8 @@ int mis_warper_warp(MisContext* ctx, int kind, const MisImage* src, float scale,
  * pixel: a caller that sized dst from the roi passes it on instead of having it computed again) */
 int mis_warper_warp_roi(MisContext* ctx, int kind, const MisImage* src, float scale, const float K[9], const float R[9], const MisRect* roi,
                         int interp, int border, MisImage* dst, MisPoint* tl);
-/* fused compose-scale warp -- replaces :1154 + :1157-1159 + :1164 */
+/* fused compose-scale warp -- replaces :1154 + :1157-1159 + :1164.  (Fisheye and stereographic: mapBackward per output pixel,
+ * atan2 / sqrt / atan / two sincos, in a kernel of its own; the same contract and the same sampling.) */
 int mis_warper_warp_fused(MisContext* ctx, int kind, const MisImage* src_bgr, float scale, const float K[9], const float R[9],
                           MisImage* dst_s16x3, MisImage* dst_mask, MisPoint* tl);
 /* the same with the roi mis_warper_roi gave for these parameters (:1138 then :1154) */
