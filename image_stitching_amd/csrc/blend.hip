@@ -1395,7 +1395,7 @@ extern "C" int mis_compose_frames_kind(MisBlender* b, int kind, const MisImage* 
                                        const MisRect* rois) {
     if (!b) return MIS_E_INVALID;
     MisContext* ctx = b->ctx;
-    MIS_CHECK(ctx, kind >= MIS_WARP_SPHERICAL && kind <= MIS_WARP_STEREOGRAPHIC, MIS_E_UNSUPPORTED, "unknown warp kind %d", kind);
+    MIS_CHECK(ctx, MIS_WARP_KIND_IS_KNOWN(kind), MIS_E_UNSUPPORTED, "unknown warp kind %d", kind);
     MIS_CHECK(ctx, b->prepared, MIS_E_STATE, "compose before prepare");
     MIS_CHECK(ctx, frames && Ks && Rs && rois && n >= 0, MIS_E_INVALID, "null argument");
     MIS_HIP(ctx, hipSetDevice(ctx->device));

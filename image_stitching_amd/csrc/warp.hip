@@ -2,7 +2,7 @@
 // Stereographic}Warper calls
 // (the warp_type switch of image_stitching/image_stitching.cpp:917-969): :973/:1117 (create(scale)),
 // :985/:988/:1154/:1159 (warp), :1138 (warpRoi), :1164 (convertTo CV_16S, fused here).
-// The three kinds share one per-pixel form: x_ = su * s, z_ = cu * s, y_ = c with a column table {su, cu} and a row table
+// The separable kinds share one per-pixel form: x_ = su * s, z_ = cu * s, y_ = c with a column table {su, cu} and a row table
 // {s, m1 c, m4 c, m7 c} (spherical: sin u', cos u' | sin(pi - v'), cos(pi - v'); cylindrical: sin u', cos u' | 1, v';
 // plane: u', 1 | 1, v'; mercator: sin u', cos u' | cos v_, sin v_ with v_ = atan(sinh v')).  The products by 1 are exact, so the
 // float operations per pixel are OpenCV's for every kind; the plane projector divides by z whatever its sign (a compile-time
@@ -19,6 +19,7 @@
 #include "dev_math.h"
 #include <algorithm>
 #include <climits>
+#include <type_traits>
 #include <vector>
 
 namespace {
@@ -29,7 +30,6 @@ struct Projector {
     int kind;   // MIS_WARP_*
 };
 
-static bool kind_ok(int kind) { return kind >= MIS_WARP_SPHERICAL && kind <= MIS_WARP_STEREOGRAPHIC; }
 // the kinds whose backward map is evaluated per output pixel (no column / row tables)
 static bool kind_polar(int kind) { return kind == MIS_WARP_FISHEYE || kind == MIS_WARP_STEREOGRAPHIC; }
 
@@ -202,6 +202,18 @@ struct RoiJob {
     int behind;     // out (plane): some corner lies behind the panorama plane
     float ext[4];   // out: min u, min v, max u, max v
 };
+// The workgroup reduction of both roi kernels (256 threads): every thread's four extremes -> the four waves' extremes in `red`
+// (wave shuffles, one LDS row per wave, one barrier); thread 0 of each kernel then combines the four rows.
+__device__ __forceinline__ void reduce_extremes(float& lo_u, float& lo_v, float& hi_u, float& hi_v, float (*red)[4]) {
+    for (int o = 32; o > 0; o >>= 1) {
+        lo_u = fminf(lo_u, __shfl_xor(lo_u, o)); lo_v = fminf(lo_v, __shfl_xor(lo_v, o));
+        hi_u = fmaxf(hi_u, __shfl_xor(hi_u, o)); hi_v = fmaxf(hi_v, __shfl_xor(hi_v, o));
+    }
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { red[wave][0] = lo_u; red[wave][1] = lo_v; red[wave][2] = hi_u; red[wave][3] = hi_v; }
+    __syncthreads();
+}
+
 __global__ __launch_bounds__(256) void warp_roi_kernel(RoiJob* jobs) {
     RoiJob* j = jobs + blockIdx.x;
     __shared__ float red[4][4];
@@ -222,13 +234,7 @@ __global__ __launch_bounds__(256) void warp_roi_kernel(RoiJob* jobs) {
         if (!map_forward<MIS_WARP_MERCATOR>(kind, m, scale, x, y, &u, &v) && kind == MIS_WARP_PLANE) behind = 1;
         lo_u = fminf(lo_u, u); lo_v = fminf(lo_v, v); hi_u = fmaxf(hi_u, u); hi_v = fmaxf(hi_v, v);
     }
-    for (int o = 32; o > 0; o >>= 1) {
-        lo_u = fminf(lo_u, __shfl_xor(lo_u, o)); lo_v = fminf(lo_v, __shfl_xor(lo_v, o));
-        hi_u = fmaxf(hi_u, __shfl_xor(hi_u, o)); hi_v = fmaxf(hi_v, __shfl_xor(hi_v, o));
-    }
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { red[wave][0] = lo_u; red[wave][1] = lo_v; red[wave][2] = hi_u; red[wave][3] = hi_v; }
-    __syncthreads();
+    reduce_extremes(lo_u, lo_v, hi_u, hi_v, red);
     if (threadIdx.x == 0) {
         j->behind = behind;
         j->ext[0] = fminf(fminf(red[0][0], red[1][0]), fminf(red[2][0], red[3][0]));
@@ -268,13 +274,7 @@ __global__ __launch_bounds__(256) void warp_roi_scan_kernel(const RoiJob* jobs, 
         c += cstep; r += rstep;
         if (c >= sw) { c -= sw; r += 1; }
     }
-    for (int o = 32; o > 0; o >>= 1) {
-        lo_u = fminf(lo_u, __shfl_xor(lo_u, o)); lo_v = fminf(lo_v, __shfl_xor(lo_v, o));
-        hi_u = fmaxf(hi_u, __shfl_xor(hi_u, o)); hi_v = fmaxf(hi_v, __shfl_xor(hi_v, o));
-    }
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { red[wave][0] = lo_u; red[wave][1] = lo_v; red[wave][2] = hi_u; red[wave][3] = hi_v; }
-    __syncthreads();
+    reduce_extremes(lo_u, lo_v, hi_u, hi_v, red);
     if (threadIdx.x == 0) {
         float4 e;
         e.x = fminf(fminf(red[0][0], red[1][0]), fminf(red[2][0], red[3][0]));
@@ -293,7 +293,7 @@ struct WarpArgs {
     float m[9];  // k_rinv
     float scale;
     int tlx, tly, dw, dh, sw, sh, cn;
-    int kind;        // MIS_WARP_* (read by the table fills and the u8 warp; in the padding before `src`: the layout is unchanged)
+    int kind;        // MIS_WARP_* (read by the table fills and the u8 warps; the fused kernels take it as a template argument)
     const uint8_t* src;
     size_t sstride;
     void* dst;       // s16x3 (fused) or u8 x cn
@@ -384,10 +384,7 @@ __device__ __forceinline__ void tile_trig(const WarpArgs& a, int tx0, int ty0, f
 //    LDS with direct global->LDS loads (16-byte pieces, several box rows per instruction, no staging
 //    registers), and gathers the 12 taps per pixel from LDS.  Tiles whose taps need BORDER_REFLECT fold
 //    the box once; boxes that do not fit take a global-memory gather (cold).
-#ifndef WV_LROWS
-#define WV_LROWS 4
-#endif
-constexpr int LROWS = WV_LROWS;          // rows per lane (4 lane rows per tile)
+constexpr int LROWS = 4;                  // rows per lane (4 lane rows per tile)
 constexpr int LPX = 2 * LROWS;            // pixels per lane
 constexpr int FT_W = 32, FT_H = 4 * LROWS;
 constexpr int STAGE_BYTES = 1280 * LROWS;  // LROWS = 4: 5 KB, 32 waves per CU fit the 160 KB of LDS
@@ -711,20 +708,9 @@ __device__ __forceinline__ void tile_sample_store(const WarpArgs& a, const TileS
 }
 
 // One tile per wave, TILE_WAVES independent waves per workgroup (no barriers; fewer, larger workgroups to dispatch).
-#ifndef WV_TILE_WAVES
-#define WV_TILE_WAVES 2
-#endif
-constexpr int TILE_WAVES = WV_TILE_WAVES;
-#ifndef WV_WAVES_MIN
-#define WV_WAVES_MIN 4     // occupancy floor the register allocator works to (6 and 8 measured in the batched grid: no gain)
-#endif
-#ifndef WV_CH_W
-#define WV_CH_W 4
-#endif
-#ifndef WV_CH_H
-#define WV_CH_H 4
-#endif
-constexpr int CH_W = WV_CH_W, CH_H = WV_CH_H;   // chunk of tiles owned by one XCD (CH_W a multiple of TILE_WAVES)
+constexpr int TILE_WAVES = 2;
+constexpr int WAVES_MIN = 4;        // occupancy floor the register allocator works to (6 and 8 measured in the batched grid: no gain)
+constexpr int CH_W = 4, CH_H = 4;   // chunk of tiles owned by one XCD (CH_W a multiple of TILE_WAVES)
 static_assert(CH_W % TILE_WAVES == 0, "chunk width must be a whole number of workgroups");
 // bid: the workgroup's index in the frame's grid
 template <bool ZTEST>
@@ -775,7 +761,7 @@ __device__ __forceinline__ void warp_fused_body(const WarpArgs& a, const float* 
 #endif
 }
 template <bool ZTEST>
-__global__ __launch_bounds__(64 * TILE_WAVES) __attribute__((amdgpu_waves_per_eu(WV_WAVES_MIN, 8))) void warp_fused_kernel(WarpArgs a, const float* __restrict__ tab) {
+__global__ __launch_bounds__(64 * TILE_WAVES) __attribute__((amdgpu_waves_per_eu(WAVES_MIN, 8))) void warp_fused_kernel(WarpArgs a, const float* __restrict__ tab) {
     __shared__ __attribute__((aligned(16))) uint8_t stage_all[TILE_WAVES][STAGE_BYTES];
     warp_fused_body<ZTEST>(a, tab, (int)blockIdx.x, stage_all);
 }
@@ -798,7 +784,7 @@ __global__ __launch_bounds__(256) void warp_trig_batch_kernel(WarpBatch b) {
 
 
 // =====================================================================================================================
-// K10, round 3: pipelined strips (warp_strip_kernel / warp_strip_batch_kernel).
+// K10, round 3: pipelined strips (warp_strip_batch_kernel).
 //
 // What the ablations of round 2's kernel said (gpurun_out/r3_abl1.txt; 23.9 us per frame in the batched grid on that box:
 // without its stores 17.8, without its global -> LDS copies 16.0, without the division 22.3, without the gather 20.2): the
@@ -824,35 +810,14 @@ __global__ __launch_bounds__(256) void warp_trig_batch_kernel(WarpBatch b) {
 //    frame that is not dword aligned or larger than 4 GB) are redone after the strip's loop by a compact per-pixel loop: IEEE
 //    division, x86 cvRound, global-memory taps.
 // The float operations per pixel, the guards and the results are those of round 2's kernel.
-#ifndef WV3_RING
-#define WV3_RING 10240
-#endif
-#ifndef WV3_WAVES
-#define WV3_WAVES 2
-#endif
-#ifndef WV3_CHX
-#define WV3_CHX 2
-#endif
-#ifndef WV3_CHY
-#define WV3_CHY 1
-#endif
-#ifndef WV3_WAVES_MIN
-#define WV3_WAVES_MIN 4
-#endif
-#ifndef WV3_TH
-#define WV3_TH 8
-#endif
-#ifndef WV3_GG
-#define WV3_GG 4
-#endif
-#ifndef WV3_MG
-#define WV3_MG 8
-#endif
-#ifndef WV3_PITCH_ALIGN
-#define WV3_PITCH_ALIGN 128
-#endif
-constexpr int V3_TW = 64, V3_TH = WV3_TH;
-constexpr int V3_RING = WV3_RING, V3_WAVES = WV3_WAVES, V3_GG = WV3_GG, V3_MG = WV3_MG, V3_PITCH_ALIGN = WV3_PITCH_ALIGN;
+constexpr int V3_TW = 64, V3_TH = 8;    // a tile: one column per lane, one group of 8 rows
+constexpr int V3_RING = 10240;          // LDS bytes per wave for the two boxes in flight: 2 waves x 10 KB per workgroup, 8 workgroups per CU
+constexpr int V3_WAVES = 2;             // waves (strips side by side) per workgroup
+constexpr int V3_CHX = 2, V3_CHY = 1;   // chunk of workgroups owned by one XCD (v3_strip_of)
+constexpr int V3_WAVES_MIN = 4;         // occupancy floor the register allocator works to
+constexpr int V3_GG = 4;                // pixels gathered between two scheduling barriers (bounds the taps in flight: registers)
+constexpr int V3_MG = 8;                // the same for the map's division chains (V3_TH: one group)
+constexpr int V3_PITCH_ALIGN = 128;     // a box's LDS pitch is a multiple of it: a tap's bank then does not depend on its row (V3Uni.pitch)
 constexpr int V3_OUT_IMG = V3_TW * 8 * 6, V3_OUT_BYTES = V3_OUT_IMG + V3_TW * 8;   // 8 rows of the 16SC3 tile + of the mask tile
 static_assert(V3_TH % 8 == 0 && V3_TH <= 16, "tiles are whole groups of 8 rows");
 static_assert(V3_OUT_BYTES <= V3_RING / 2 && V3_RING <= 65536, "two output groups must fit the ring; LDS addresses are 16 bits");
@@ -978,7 +943,6 @@ __device__ __forceinline__ unsigned v3_pack(int addr, unsigned xq, unsigned yq, 
 // Map stage: backward map of a lane's column x V3_TH rows of the tile at rows ty0.., box reduction, classification, packing
 // (tile_map's logic; the cold decisions only set u.fast = 0: the per-pixel loop redoes such a tile from scratch).
 // ring_lds / parity: where the tile's region of the ring will be (even tiles from the bottom, odd tiles from the top).
-template <int RING>
 __device__ __forceinline__ void v3_map(const V3Frame& f, cf4p rowtab, float su, float cu, int ty0, uint32_t ring_lds, int parity,
                                        unsigned* w, unsigned& msk_out, V3Uni& u) {
     int xq[V3_TH], yq[V3_TH];
@@ -1045,16 +1009,16 @@ __device__ __forceinline__ void v3_map(const V3Frame& f, cf4p rowtab, float su, 
     const int rowb = ((bx1 - bx0 + 1) * 3 + shift + amask) & ~amask;
     const int nrows = by1 - by0 + 1;
     const int pitch_cf = (rowb + V3_PITCH_ALIGN - 1) & ~(V3_PITCH_ALIGN - 1);       // conflict free; the tight pitch when that takes more than the tile's share of the ring
-    const int pitch = nrows * pitch_cf <= RING / 2 ? pitch_cf : rowb;
+    const int pitch = nrows * pitch_cf <= V3_RING / 2 ? pitch_cf : rowb;
     const unsigned gbase = (unsigned)by0 * f.sstride + (unsigned)(bx0 * 3 - shift);    // frames are < 4 GB on the fast path
-    const bool fast = good && (interior || foldable) && nrows * pitch <= RING && pitch <= (wide ? 1024 : 256) &&
+    const bool fast = good && (interior || foldable) && nrows * pitch <= V3_RING && pitch <= (wide ? 1024 : 256) &&
                       gbase + (unsigned)(nrows - 1) * f.sstride + (unsigned)rowb <= f.total_bytes;
     u.fast = fast; u.interior = interior; u.pitch = pitch; u.rowb = rowb; u.nrows = nrows; u.gbase = gbase;
     u.bytes = fast ? max((nrows * pitch + 15) & ~15, V3_OUT_BYTES) : V3_OUT_BYTES;
     unsigned msk = (1u << V3_TH) - 1u;
     if (fast) {
         // LDS address of source pixel (0, 0) in the tile's region
-        const int lbase = (int)ring_lds + (parity ? RING - u.bytes : 0) + shift - by0 * pitch - bx0 * 3;
+        const int lbase = (int)ring_lds + (parity ? V3_RING - u.bytes : 0) + shift - by0 * pitch - bx0 * 3;
         // integer parts: sign-extended bits 5..21 of the biased values (one v_bfe_i32 each)
         if (interior) {
 #pragma unroll
@@ -1147,9 +1111,7 @@ __device__ __forceinline__ void v3_store_piece(uint8_t* p, u4v v, bool wide_out)
 }
 
 // The strip a wave owns: columns tx0 .. tx0 + 63, tiles ty_first .. ty_first + nt - 1 (V3_TH rows each).
-// PIPE = false: the same stages one tile after the other (map, copies, wait, gather, stores) -- no second tile in flight, fewer
-// registers, more waves per SIMD: the form for a launch of ONE frame, whose strips are too short to fill a pipeline.
-template <bool PIPE, int RING, bool ZTEST>
+template <bool ZTEST>
 __device__ __forceinline__ void warp_strip_body(const V3Frame& f, int tx0, int ty_first, int nt, lds_p ring) {
     const int lane = threadIdx.x & 63;
     const int nty = (f.dh + V3_TH - 1) / V3_TH;
@@ -1178,7 +1140,7 @@ __device__ __forceinline__ void warp_strip_body(const V3Frame& f, int tx0, int t
     int pend = 0;        // vector-memory instructions issued after the copies of the tile that is gathered next (a lower bound)
     unsigned cold = 0;   // bit k: tile k is outside the fast path
     auto issue = [&](const V3Uni& u, int parity) -> int {      // the copies of a tile's box into its region of the ring
-        const uint32_t off = ring_lds + (parity ? (uint32_t)(RING - u.bytes) : 0u);
+        const uint32_t off = ring_lds + (parity ? (uint32_t)(V3_RING - u.bytes) : 0u);
         return (f.flags & V3F_WIDE_SRC) ? v3_stage_box<16>(f.src, u.gbase, f.sstride, off, u.pitch, u.rowb, u.nrows, lane)
                                         : v3_stage_box<4>(f.src, u.gbase, f.sstride, off, u.pitch, u.rowb, u.nrows, lane);
     };
@@ -1191,20 +1153,15 @@ __device__ __forceinline__ void warp_strip_body(const V3Frame& f, int tx0, int t
 #endif
     // one pipeline step: map + copies of tile k + 1 (into `nw`, `nu`), gather + stores of tile k (from `cw`, `cu`)
     auto step = [&](int k, unsigned* cw, unsigned& cmsk, V3Uni& cu_, unsigned* nw, unsigned& nmsk, V3Uni& nu) {
-        const int ty0 = (ty_first + k) * V3_TH, parity = PIPE ? (k & 1) : 0;
+        const int ty0 = (ty_first + k) * V3_TH, parity = k & 1;
         bool deferred = false;
         V3_STAMP(0);
-        if (!PIPE) {        // tile k itself: map, copies, (wait for everything)
-            v3_map<RING>(f, rowtab, cs.x, cs.y, ty0, ring_lds, 0, cw, cmsk, cu_);
-            V3_STAMP(1);
-            if (cu_.fast) issue(cu_, 0);
-            pend = 0;
-        } else if (k + 1 < nt) {
-            v3_map<RING>(f, rowtab, cs.x, cs.y, ty0 + V3_TH, ring_lds, parity ^ 1, nw, nmsk, nu);
+        if (k + 1 < nt) {
+            v3_map(f, rowtab, cs.x, cs.y, ty0 + V3_TH, ring_lds, parity ^ 1, nw, nmsk, nu);
             V3_STAMP(1);
             if (nu.fast) {
                 if (k < 0) { issue(nu, parity ^ 1); pend = 0; }     // the strip's first tile: nothing is younger than its copies yet
-                else if (cu_.bytes + nu.bytes <= RING) pend += issue(nu, parity ^ 1);
+                else if (cu_.bytes + nu.bytes <= V3_RING) pend += issue(nu, parity ^ 1);
                 else deferred = true;
             }
         }
@@ -1213,7 +1170,7 @@ __device__ __forceinline__ void warp_strip_body(const V3Frame& f, int tx0, int t
             WSTAT(cu_.fast ? (cu_.interior ? 0 : 1) : 2);
             if (deferred) WSTAT(4);
             if (cu_.fast) {
-                const uint32_t reg = ring_lds + (parity ? (uint32_t)(RING - cu_.bytes) : 0u);
+                const uint32_t reg = ring_lds + (parity ? (uint32_t)(V3_RING - cu_.bytes) : 0u);
                 unsigned p[V3_TH][3];     // a channel in the upper 16 bits
                 wait_vm_dyn(pend);
                 V3_STAMP(3);
@@ -1323,15 +1280,10 @@ __device__ __forceinline__ void warp_strip_body(const V3Frame& f, int tx0, int t
 #endif
         }
     };
-    if (PIPE) {
 #pragma unroll 1
-        for (int k = -1; k < nt; k += 2) {      // the two tiles in flight swap roles: no copies
-            step(k, wB, mskB, uB, wA, mskA, uA);
-            if (k + 1 < nt) step(k + 1, wA, mskA, uA, wB, mskB, uB);
-        }
-    } else {
-#pragma unroll 1
-        for (int k = 0; k < nt; k++) step(k, wA, mskA, uA, wB, mskB, uB);
+    for (int k = -1; k < nt; k += 2) {      // the two tiles in flight swap roles: no copies
+        step(k, wB, mskB, uB, wA, mskA, uA);
+        if (k + 1 < nt) step(k + 1, wA, mskA, uA, wB, mskB, uB);
     }
     if (cold) {
         const V3Frame fc = f;       // a copy for the call: the kernel's own arguments stay in registers
@@ -1344,11 +1296,11 @@ __device__ __forceinline__ void warp_strip_body(const V3Frame& f, int tx0, int t
 __device__ __forceinline__ bool v3_strip_of(int bid, int wave, int dw, int dh, int nt, int* tx0, int* ty_first) {
     const int nsx = (dw + V3_TW - 1) / V3_TW, nty = (dh + V3_TH - 1) / V3_TH, nsy = (nty + nt - 1) / nt;
     const int nwx = (nsx + V3_WAVES - 1) / V3_WAVES;
-    constexpr int WG_PER_CHUNK = WV3_CHX * WV3_CHY;
-    const int nchx = (nwx + WV3_CHX - 1) / WV3_CHX;
+    constexpr int WG_PER_CHUNK = V3_CHX * V3_CHY;
+    const int nchx = (nwx + V3_CHX - 1) / V3_CHX;
     const int i = bid >> 3, chunk = (i / WG_PER_CHUNK) * 8 + (bid & 7), within = i % WG_PER_CHUNK;
     const int chy = chunk / nchx, chx = chunk - chy * nchx;
-    const int wx = chx * WV3_CHX + within % WV3_CHX, wy = chy * WV3_CHY + within / WV3_CHX;
+    const int wx = chx * V3_CHX + within % V3_CHX, wy = chy * V3_CHY + within / V3_CHX;
     const int sx = wx * V3_WAVES + wave;
     if (sx >= nsx || wy >= nsy) return false;
     *tx0 = sx * V3_TW; *ty_first = wy * nt;
@@ -1357,21 +1309,17 @@ __device__ __forceinline__ bool v3_strip_of(int bid, int wave, int dw, int dh, i
 static int v3_grid_of(const WarpArgs& a, int nt) {
     const int nsx = (a.dw + V3_TW - 1) / V3_TW, nty = (a.dh + V3_TH - 1) / V3_TH, nsy = (nty + nt - 1) / nt;
     const int nwx = (nsx + V3_WAVES - 1) / V3_WAVES;
-    const int nchunks = ((nwx + WV3_CHX - 1) / WV3_CHX) * ((nsy + WV3_CHY - 1) / WV3_CHY);
-    return ((nchunks + 7) / 8) * 8 * WV3_CHX * WV3_CHY;
+    const int nchunks = ((nwx + V3_CHX - 1) / V3_CHX) * ((nsy + V3_CHY - 1) / V3_CHY);
+    return ((nchunks + 7) / 8) * 8 * V3_CHX * V3_CHY;
 }
-#ifndef WV3_NT_MAX
-#define WV3_NT_MAX 8       // <= 32: a strip's cold tiles are a bit mask
-#endif
-#ifndef WV3_SLOTS
-#define WV3_SLOTS 16       // strips wanted per compute unit before strips get longer
-#endif
-// Tiles per strip: long strips amortise the pipeline's fill, but a launch should still put WV3_SLOTS waves on every compute unit
+constexpr int V3_NT_MAX = 8;        // tiles per strip at most (<= 32: a strip's cold tiles are a bit mask)
+constexpr int V3_SLOTS = 16;        // strips wanted per compute unit before strips get longer
+// Tiles per strip: long strips amortise the pipeline's fill, but a launch should still put V3_SLOTS waves on every compute unit
 // (frames = the number of frames sharing the grid).
 static int v3_strip_tiles(const MisContext* ctx, const WarpArgs& a, int frames) {
     const long long tiles = (long long)((a.dw + V3_TW - 1) / V3_TW) * ((a.dh + V3_TH - 1) / V3_TH) * std::max(frames, 1);
-    const long long nt = tiles / ((long long)std::max(ctx->num_cu, 1) * WV3_SLOTS);
-    return (int)std::min<long long>(WV3_NT_MAX, std::max<long long>(1, nt));
+    const long long nt = tiles / ((long long)std::max(ctx->num_cu, 1) * V3_SLOTS);
+    return (int)std::min<long long>(V3_NT_MAX, std::max<long long>(1, nt));
 }
 // The fast paths' upper bound on z: |z| <= (|m6| + |m7| + |m8|) max(|x_|, |y_|, |z_|).  Spherical terms are at most 1 (the kernels'
 // own guard); the cylinder's y_ = v' and the plane's x_ = u', y_ = v' grow with the roi, so those kinds scale the bound by the
@@ -1413,22 +1361,17 @@ struct V3Batch {
 
 // Tiles per strip for every frame of one launch (frames in grid order).  `base` is what v3_strip_tiles asks for; the frames at the
 // end of the grid get shorter strips so that the launch's tail is made of short waves: a frame whose tiles all lie within the last
-// `WV3_TAIL2` tile-rounds of the launch (one round = one tile per wave slot of the device) takes 2-tile strips, within the last
-// WV3_TAIL4 rounds 4-tile strips.  (Short strips pay the pipeline's fill more often: 3 maps per 2 gathers instead of 9 per 8.)
-#ifndef WV3_TAIL2
-#define WV3_TAIL2 4
-#endif
-#ifndef WV3_TAIL4
-#define WV3_TAIL4 8
-#endif
+// `V3_TAIL2` tile-rounds of the launch (one round = one tile per wave slot of the device) takes 2-tile strips, within the last
+// V3_TAIL4 rounds 4-tile strips.  (Short strips pay the pipeline's fill more often: 3 maps per 2 gathers instead of 9 per 8.)
+constexpr int V3_TAIL2 = 4, V3_TAIL4 = 8;
 static void v3_plan_strips(const MisContext* ctx, const WarpArgs* args, int ng, int base, int* nt_out) {
-    const long long slots = (long long)std::max(ctx->num_cu, 1) * 4 * WV3_WAVES_MIN;
+    const long long slots = (long long)std::max(ctx->num_cu, 1) * 4 * V3_WAVES_MIN;
     long long after = 0;        // tiles of the frames behind frame k in the grid
     for (int k = ng - 1; k >= 0; k--) {
         const long long tiles = (long long)((args[k].dw + V3_TW - 1) / V3_TW) * ((args[k].dh + V3_TH - 1) / V3_TH);
         int nt = base;
-        if (after + tiles <= slots * WV3_TAIL2) nt = std::min(nt, 2);
-        else if (after + tiles <= slots * WV3_TAIL4) nt = std::min(nt, 4);
+        if (after + tiles <= slots * V3_TAIL2) nt = std::min(nt, 2);
+        else if (after + tiles <= slots * V3_TAIL4) nt = std::min(nt, 4);
         nt_out[k] = nt;
         after += tiles;
     }
@@ -1439,7 +1382,7 @@ static void v3_plan_strips(const MisContext* ctx, const WarpArgs* args, int ng, 
 // them shorter (v3_plan_strips) -- with 8-tile strips everywhere a 16-frame launch is 7.25 generations of ~37 us waves and a
 // quarter of the slots run an eighth wave while the others idle.
 template <bool ZTEST>
-__global__ __launch_bounds__(64 * V3_WAVES) __attribute__((amdgpu_waves_per_eu(WV3_WAVES_MIN, 8))) void warp_strip_batch_kernel(V3Batch b) {
+__global__ __launch_bounds__(64 * V3_WAVES) __attribute__((amdgpu_waves_per_eu(V3_WAVES_MIN, 8))) void warp_strip_batch_kernel(V3Batch b) {
     __shared__ __attribute__((aligned(16))) uint8_t ring_all[V3_WAVES][V3_RING];
     const int bid = (int)blockIdx.x;
     int fi = 0;
@@ -1450,7 +1393,7 @@ __global__ __launch_bounds__(64 * V3_WAVES) __attribute__((amdgpu_waves_per_eu(W
     const int nt = b.nt[fi];
     int tx0, ty_first;
     if (!v3_strip_of(bid - b.wg_base[fi], wave, f.dw, f.dh, nt, &tx0, &ty_first)) return;
-    warp_strip_body<true, V3_RING, ZTEST>(f, tx0, ty_first, nt, (lds_p)ring_all[wave]);
+    warp_strip_body<ZTEST>(f, tx0, ty_first, nt, (lds_p)ring_all[wave]);
 }
 
 // General warp (seam-scale path and plain masks): u8 with CN channels, one column per lane.
@@ -1594,9 +1537,30 @@ __global__ __launch_bounds__(256) void warp_polar_u8_kernel(WarpArgs a) {
     }
 }
 
+// Run-time value -> template instantiation, one helper per kernel family: `launch` is a generic lambda that takes the value as
+// std::integral_constant(s) and names the kernel with them, so only the instantiations listed here exist.
+template <int V> using int_c = std::integral_constant<int, V>;
+template <class F> void with_polar_kind(int kind, F&& launch) {         // warp_polar_fused_kernel, warp_polar_fused_batch_kernel
+    if (kind == MIS_WARP_FISHEYE) launch(int_c<MIS_WARP_FISHEYE>{});
+    else launch(int_c<MIS_WARP_STEREOGRAPHIC>{});
+}
+template <class F> void with_scan_kind(int kind, F&& launch) {          // warp_roi_scan_kernel (MIS_WARP_ROI_IS_FULL_SCAN kinds)
+    if (kind == MIS_WARP_MERCATOR) launch(int_c<MIS_WARP_MERCATOR>{});
+    else if (kind == MIS_WARP_FISHEYE) launch(int_c<MIS_WARP_FISHEYE>{});
+    else launch(int_c<MIS_WARP_STEREOGRAPHIC>{});
+}
+template <class F> void with_ztest(int kind, F&& launch) {              // warp_fused_kernel, warp_strip_batch_kernel: ZTEST = not plane
+    if (kind == MIS_WARP_PLANE) launch(std::false_type{});
+    else launch(std::true_type{});
+}
+template <class F> void with_cn_linear(int cn, bool linear, F&& launch) {       // warp_u8_kernel, warp_polar_u8_kernel
+    if (cn == 3) { if (linear) launch(int_c<3>{}, std::true_type{}); else launch(int_c<3>{}, std::false_type{}); }
+    else { if (linear) launch(int_c<1>{}, std::true_type{}); else launch(int_c<1>{}, std::false_type{}); }
+}
+
 // `known`: the roi warpRoi / mis_warp_roi_batch returned for exactly these (scale, K, R, size) -- skips the border walk
 int setup(MisContext* ctx, int kind, const MisImage* src, float scale, const float K[9], const float R[9], WarpArgs* a, int* brx, int* bry, const MisRect* known = nullptr) {
-    MIS_CHECK(ctx, kind_ok(kind), MIS_E_UNSUPPORTED, "unknown warp kind %d", kind);
+    MIS_CHECK(ctx, MIS_WARP_KIND_IS_KNOWN(kind), MIS_E_UNSUPPORTED, "unknown warp kind %d", kind);
     MIS_CHECK(ctx, src && K && R, MIS_E_INVALID, "null argument");
     MIS_CHECK(ctx, src->dtype == MIS_U8 && (src->channels == 1 || src->channels == 3), MIS_E_UNSUPPORTED,
               "warp source must be 8UC1 or 8UC3");
@@ -1651,7 +1615,7 @@ extern "C" int mis_debug_warp_stamps(unsigned long long* out, int n) {
 #endif
 
 extern "C" int mis_warper_roi(int kind, float scale, int w, int h, const float K[9], const float R[9], MisRect* roi) {
-    if (!kind_ok(kind)) return MIS_E_UNSUPPORTED;
+    if (!MIS_WARP_KIND_IS_KNOWN(kind)) return MIS_E_UNSUPPORTED;
     if (!K || !R || !roi || w < 1 || h < 1 || !(scale > 0.f)) return MIS_E_INVALID;
     if (MIS_WARP_ROI_IS_FULL_SCAN(kind) && (w > 32767 || h > 32767)) return MIS_E_INVALID;     // a frame the warps refuse; the scan is O(w h)
     Projector p;
@@ -1679,21 +1643,16 @@ static int warp_u8_impl(MisContext* ctx, int kind, const MisImage* src, float sc
     a.src = (const uint8_t*)din.data; a.sstride = din.stride;
     a.dst = dout.data; a.dstride = dout.stride; a.mask = nullptr; a.mstride = 0;
     dim3 grid((a.dw + TILE_W - 1) / TILE_W, (a.dh + TILE_H - 1) / TILE_H), block(256);
+    const bool linear = interp == MIS_INTER_LINEAR;
     if (kind_polar(kind)) {
         MIS_CHECK(ctx, grid.y <= 65535u, MIS_E_INVALID, "warp roi %dx%d: too many rows for one launch", a.dw, a.dh);
-        if (src->channels == 3) {
-            if (interp == MIS_INTER_LINEAR) hipLaunchKernelGGL((warp_polar_u8_kernel<3, true>), grid, block, 0, ctx->stream, a);
-            else hipLaunchKernelGGL((warp_polar_u8_kernel<3, false>), grid, block, 0, ctx->stream, a);
-        } else {
-            if (interp == MIS_INTER_LINEAR) hipLaunchKernelGGL((warp_polar_u8_kernel<1, true>), grid, block, 0, ctx->stream, a);
-            else hipLaunchKernelGGL((warp_polar_u8_kernel<1, false>), grid, block, 0, ctx->stream, a);
-        }
-    } else if (src->channels == 3) {
-        if (interp == MIS_INTER_LINEAR) hipLaunchKernelGGL((warp_u8_kernel<3, true>), grid, block, 0, ctx->stream, a);
-        else hipLaunchKernelGGL((warp_u8_kernel<3, false>), grid, block, 0, ctx->stream, a);
+        with_cn_linear(src->channels, linear, [&](auto cn, auto lin) {
+            hipLaunchKernelGGL((warp_polar_u8_kernel<cn.value, lin.value>), grid, block, 0, ctx->stream, a);
+        });
     } else {
-        if (interp == MIS_INTER_LINEAR) hipLaunchKernelGGL((warp_u8_kernel<1, true>), grid, block, 0, ctx->stream, a);
-        else hipLaunchKernelGGL((warp_u8_kernel<1, false>), grid, block, 0, ctx->stream, a);
+        with_cn_linear(src->channels, linear, [&](auto cn, auto lin) {
+            hipLaunchKernelGGL((warp_u8_kernel<cn.value, lin.value>), grid, block, 0, ctx->stream, a);
+        });
     }
     MIS_HIP(ctx, hipGetLastError());
     if ((rc = dout.commit()) != MIS_OK) return rc;
@@ -1754,28 +1713,10 @@ static int fused_outputs(MisContext* ctx, WarpArgs& a, const MisImage* src, MisI
     return MIS_OK;
 }
 
-// one frame of a polar kind (setup() done): its tiles in one grid
-static int warp_polar_fused_one(MisContext* ctx, WarpArgs& a, const MisImage* src, MisImage* dst, MisImage* dmask, MisPoint* tl, int repeats, float* avg_us) {
-    MIS_HIP(ctx, hipSetDevice(ctx->device));
-    DevView din, dout, dm;
-    int rc;
-    if ((rc = fused_outputs(ctx, a, src, dst, dmask, din, dout, dm)) != MIS_OK) return rc;
-    const long long tiles = polar_tiles_of(a);       // area < 2^31 (setup): below 2^31 too
-    RepeatTimer t;
-    if ((rc = t.begin(ctx, avg_us)) != MIS_OK) return rc;
-    for (int rep = 0; rep < repeats; rep++)
-        if (a.kind == MIS_WARP_FISHEYE) hipLaunchKernelGGL(warp_polar_fused_kernel<MIS_WARP_FISHEYE>, dim3((unsigned)tiles), dim3(256), 0, ctx->stream, a);
-        else hipLaunchKernelGGL(warp_polar_fused_kernel<MIS_WARP_STEREOGRAPHIC>, dim3((unsigned)tiles), dim3(256), 0, ctx->stream, a);
-    if ((rc = t.end(ctx, repeats, avg_us)) != MIS_OK) return rc;
-    MIS_HIP(ctx, hipGetLastError());
-    if ((rc = dout.commit()) != MIS_OK || (rc = dm.commit()) != MIS_OK) return rc;
-    if (tl) { tl->x = a.tlx; tl->y = a.tly; }
-    return MIS_OK;
-}
-
 static int grid_of(const WarpArgs& a);
 static int warp_fused_batch_impl(MisContext* ctx, int kind, const MisImage* srcs, int n, float scale, const float* Ks, const float* Rs, const MisRect* rois,
                                  MisImage* dsts, MisImage* dmasks, MisPoint* tls, int repeats, float* avg_us);
+// one frame per launch: its tiles in one grid
 static int warp_fused_impl(MisContext* ctx, int kind, const MisImage* src, float scale, const float K[9], const float R[9],
                            MisImage* dst, MisImage* dmask, MisPoint* tl, int repeats, float* avg_us, const MisRect* known_roi = nullptr) {
     if (!ctx) return MIS_E_INVALID;
@@ -1783,44 +1724,30 @@ static int warp_fused_impl(MisContext* ctx, int kind, const MisImage* src, float
     int brx, bry, rc;
     if ((rc = setup(ctx, kind, src, scale, K, R, &a, &brx, &bry, known_roi)) != MIS_OK) return rc;
     MIS_CHECK(ctx, src->channels == 3, MIS_E_UNSUPPORTED, "fused warp needs an 8UC3 source");
-    if (kind_polar(kind)) return warp_polar_fused_one(ctx, a, src, dst, dmask, tl, repeats, avg_us);
-    if (kind != MIS_WARP_SPHERICAL && !fast_z_bound_ok(a) && repeats == 1 && !avg_us) {
+    const bool polar = kind_polar(kind);
+    if (!polar && kind != MIS_WARP_SPHERICAL && !fast_z_bound_ok(a) && repeats == 1 && !avg_us) {
         // the one-frame kernel's z guard is the spherical one: a roi this far out goes through the batch form (same results)
         const MisRect r{a.tlx, a.tly, a.dw, a.dh};
         return warp_fused_batch_impl(ctx, kind, src, 1, scale, K, R, &r, dst, dmask, tl, 1, nullptr);
     }
     MIS_HIP(ctx, hipSetDevice(ctx->device));
     DevView din, dout, dm;
-    if ((rc = din.read(ctx, src)) != MIS_OK) return rc;
-    if ((rc = dout.write(ctx, dst, a.dw, a.dh, 3, MIS_S16)) != MIS_OK) return rc;
-    if ((rc = dm.write(ctx, dmask, a.dw, a.dh, 1, MIS_U8)) != MIS_OK) return rc;
-    MIS_CHECK(ctx, dout.stride % 4 == 0 && dm.stride % 2 == 0 && ((uintptr_t)dout.data % 4) == 0 && ((uintptr_t)dm.data % 2) == 0,
-              MIS_E_INVALID, "fused warp outputs need 4-byte (image) / 2-byte (mask) aligned rows");
-    a.src = (const uint8_t*)din.data; a.sstride = din.stride;
-    a.dst = dout.data; a.dstride = dout.stride; a.mask = (uint8_t*)dm.data; a.mstride = dm.stride;
-    // separable trig tables live in the context's grow-only scratch
+    if ((rc = fused_outputs(ctx, a, src, dst, dmask, din, dout, dm)) != MIS_OK) return rc;
     float* tab = nullptr;
-    if ((rc = mis_dev_stage(ctx, sizeof(float) * trig_table_floats(a.dw, a.dh), (void**)&tab)) != MIS_OK) return rc;
-    hipLaunchKernelGGL(warp_trig_kernel, dim3((trig_cols(a.dw) + a.dh + 255) / 256), dim3(256), 0, ctx->stream, a, tab);
-    const int nwg = grid_of(a);
-    OwnedEvent e0, e1;
-    if (avg_us) {
-        MIS_HIP(ctx, e0.ready(hipEventDefault));
-        MIS_HIP(ctx, e1.ready(hipEventDefault));
-        MIS_HIP(ctx, hipEventRecord(e0.ev, ctx->stream));
+    if (!polar) {
+        // separable trig tables live in the context's grow-only scratch
+        if ((rc = mis_dev_stage(ctx, sizeof(float) * trig_table_floats(a.dw, a.dh), (void**)&tab)) != MIS_OK) return rc;
+        hipLaunchKernelGGL(warp_trig_kernel, dim3((trig_cols(a.dw) + a.dh + 255) / 256), dim3(256), 0, ctx->stream, a, tab);
     }
-    // one frame per launch: round 2's tile kernel (measured faster there than the strip forms: 23.2 us against 29.3 for one-tile
+    const unsigned nwg = polar ? (unsigned)polar_tiles_of(a) : (unsigned)grid_of(a);      // polar: area < 2^31 (setup), so are its tiles
+    RepeatTimer t;
+    if ((rc = t.begin(ctx, avg_us)) != MIS_OK) return rc;
+    // the separable kinds: round 2's tile kernel (measured faster there than the strip forms: 23.2 us against 29.3 for one-tile
     // strips and more for longer ones -- a frame alone is 3.5 tiles per wave slot, gpurun_out/r4_plan_ab3.txt)
     for (int rep = 0; rep < repeats; rep++)
-        if (kind == MIS_WARP_PLANE) hipLaunchKernelGGL(warp_fused_kernel<false>, dim3(nwg), dim3(64 * TILE_WAVES), 0, ctx->stream, a, (const float*)tab);
-        else hipLaunchKernelGGL(warp_fused_kernel<true>, dim3(nwg), dim3(64 * TILE_WAVES), 0, ctx->stream, a, (const float*)tab);
-    if (avg_us) {
-        float ms = 0.f;
-        MIS_HIP(ctx, hipEventRecord(e1.ev, ctx->stream));
-        MIS_HIP(ctx, hipEventSynchronize(e1.ev));
-        MIS_HIP(ctx, hipEventElapsedTime(&ms, e0.ev, e1.ev));
-        *avg_us = ms * 1000.f / (float)repeats;
-    }
+        if (polar) with_polar_kind(kind, [&](auto k) { hipLaunchKernelGGL(warp_polar_fused_kernel<k.value>, dim3(nwg), dim3(256), 0, ctx->stream, a); });
+        else with_ztest(kind, [&](auto z) { hipLaunchKernelGGL(warp_fused_kernel<z.value>, dim3(nwg), dim3(64 * TILE_WAVES), 0, ctx->stream, a, (const float*)tab); });
+    if ((rc = t.end(ctx, repeats, avg_us)) != MIS_OK) return rc;
     MIS_HIP(ctx, hipGetLastError());
     if ((rc = dout.commit()) != MIS_OK || (rc = dm.commit()) != MIS_OK) return rc;
     if (tl) { tl->x = a.tlx; tl->y = a.tly; }
@@ -1856,71 +1783,31 @@ static int grid_of(const WarpArgs& a) {
     return ((nchunks + 7) / 8) * 8 * (CH_W / TILE_WAVES) * CH_H;
 }
 
-// n fused warps (the loop of image_stitching.cpp:1154-1164 for all frames) in one grid per WB_MAX frames; the results are those of
-// n mis_warp_spherical_fused_roi calls.  repeats / avg_us: the batch launched `repeats` times back to back between two HIP events
-// (avg_us = the average duration of one pass over all n frames), for the roofline measurement.
-static int warp_fused_batch_impl(MisContext* ctx, int kind, const MisImage* srcs, int n, float scale, const float* Ks, const float* Rs, const MisRect* rois,
-                                 MisImage* dsts, MisImage* dmasks, MisPoint* tls, int repeats, float* avg_us) {
-    MIS_CHECK(ctx, kind_ok(kind), MIS_E_UNSUPPORTED, "unknown warp kind %d", kind);
-    MIS_CHECK(ctx, srcs && Ks && Rs && rois && dsts && dmasks && n >= 1, MIS_E_INVALID, "null argument");
-    MIS_HIP(ctx, hipSetDevice(ctx->device));
-    std::vector<WarpArgs> args((size_t)n);
-    std::vector<DevView> din((size_t)n), dout((size_t)n), dm((size_t)n);
-    std::vector<size_t> tab_off((size_t)n);
-    size_t tab_total = 0;
-    int rc = MIS_OK;
-    for (int i = 0; i < n && rc == MIS_OK; i++) {
-        WarpArgs& a = args[i];
-        int brx, bry;
-        if (!(rois[i].width > 0 && rois[i].height > 0)) { rc = mis_set_error(ctx, MIS_E_INVALID, "frame %d: empty roi", i); break; }
-        if ((rc = setup(ctx, kind, &srcs[i], scale, Ks + 9 * i, Rs + 9 * i, &a, &brx, &bry, &rois[i])) != MIS_OK) break;
-        if (srcs[i].channels != 3) { rc = mis_set_error(ctx, MIS_E_UNSUPPORTED, "fused warp needs an 8UC3 source"); break; }
-        if ((rc = din[i].read(ctx, &srcs[i])) != MIS_OK) break;
-        if ((rc = dout[i].write(ctx, &dsts[i], a.dw, a.dh, 3, MIS_S16)) != MIS_OK) break;
-        if ((rc = dm[i].write(ctx, &dmasks[i], a.dw, a.dh, 1, MIS_U8)) != MIS_OK) break;
-        if (!(dout[i].stride % 4 == 0 && dm[i].stride % 2 == 0 && ((uintptr_t)dout[i].data % 4) == 0 && ((uintptr_t)dm[i].data % 2) == 0)) {
-            rc = mis_set_error(ctx, MIS_E_INVALID, "fused warp outputs need 4-byte (image) / 2-byte (mask) aligned rows"); break;
+// The launch descriptors of a batch, WB_MAX frames per grid.
+// Polar kinds: no tables, no strips; the tiles of the frames one after the other.
+static int plan_polar_batches(MisContext* ctx, const std::vector<WarpArgs>& args, std::vector<PolarBatch>& out) {
+    const int n = (int)args.size();
+    for (int g0 = 0; g0 < n; g0 += WB_MAX) {
+        const int ng = std::min(WB_MAX, n - g0);
+        PolarBatch b;
+        long long wg = 0;
+        for (int k = 0; k < WB_MAX; k++) {
+            b.a[k] = args[g0 + (k < ng ? k : 0)];
+            b.wg_base[k] = (int)wg;
+            if (k < ng) wg += polar_tiles_of(args[g0 + k]);
+            MIS_CHECK(ctx, wg <= INT_MAX, MIS_E_INVALID, "frames %d..%d: too many tiles for one launch", g0, g0 + k);
         }
-        a.src = (const uint8_t*)din[i].data; a.sstride = din[i].stride;
-        a.dst = dout[i].data; a.dstride = dout[i].stride; a.mask = (uint8_t*)dm[i].data; a.mstride = dm[i].stride;
-        tab_off[i] = tab_total;
-        tab_total += mis_align_up(sizeof(float) * trig_table_floats(a.dw, a.dh), 256);
+        b.wg_base[WB_MAX] = (int)wg;
+        out.push_back(b);
     }
-    if (rc != MIS_OK) return rc;
-    if (kind_polar(kind)) {
-        // the per-pixel map: no tables, no strips; the tiles of up to WB_MAX frames per launch
-        std::vector<PolarBatch> batches;
-        for (int g0 = 0; g0 < n; g0 += WB_MAX) {
-            const int ng = std::min(WB_MAX, n - g0);
-            PolarBatch b;
-            long long wg = 0;
-            for (int k = 0; k < WB_MAX; k++) {
-                b.a[k] = args[g0 + (k < ng ? k : 0)];
-                b.wg_base[k] = (int)wg;
-                if (k < ng) wg += polar_tiles_of(args[g0 + k]);
-                MIS_CHECK(ctx, wg <= INT_MAX, MIS_E_INVALID, "frames %d..%d: too many tiles for one launch", g0, g0 + k);
-            }
-            b.wg_base[WB_MAX] = (int)wg;
-            batches.push_back(b);
-        }
-        RepeatTimer t;
-        if ((rc = t.begin(ctx, avg_us)) != MIS_OK) return rc;
-        for (int rep = 0; rep < repeats; rep++)
-            for (const PolarBatch& b : batches)
-                if (kind == MIS_WARP_FISHEYE) hipLaunchKernelGGL(warp_polar_fused_batch_kernel<MIS_WARP_FISHEYE>, dim3(b.wg_base[WB_MAX]), dim3(256), 0, ctx->stream, b);
-                else hipLaunchKernelGGL(warp_polar_fused_batch_kernel<MIS_WARP_STEREOGRAPHIC>, dim3(b.wg_base[WB_MAX]), dim3(256), 0, ctx->stream, b);
-        if ((rc = t.end(ctx, repeats, avg_us)) != MIS_OK) return rc;
-        MIS_HIP(ctx, hipGetLastError());
-        for (int i = 0; i < n; i++) {
-            if (rc == MIS_OK && (rc = dout[i].commit()) == MIS_OK) rc = dm[i].commit();
-            if (tls) { tls[i].x = args[i].tlx; tls[i].y = args[i].tly; }
-        }
-        return rc;
-    }
-    uint8_t* tabs = nullptr;
-    if ((rc = mis_dev_stage(ctx, tab_total, (void**)&tabs)) != MIS_OK) return rc;
-    OwnedEvent e0, e1;
-    std::vector<V3Batch> v3batches;
+    return MIS_OK;
+}
+// Separable kinds: per grid the strips of the frames, frame after frame, with per-frame strip lengths (short strips for the frames
+// at the launch's end); the launch that fills the grid's trig tables goes out here, in front of everything the caller launches.
+// tabs + tab_off[i]: frame i's tables.
+static void plan_strip_batches(const MisContext* ctx, const std::vector<WarpArgs>& args, const uint8_t* tabs, const std::vector<size_t>& tab_off,
+                               std::vector<V3Batch>& out) {
+    const int n = (int)args.size();
     int nt3 = 1 << 30;      // tiles per strip: one value for the grid (the smallest any frame asks for)
     for (int i = 0; i < n; i++) nt3 = std::min(nt3, v3_strip_tiles(ctx, args[i], n));
     for (int g0 = 0; g0 < n; g0 += WB_MAX) {
@@ -1933,7 +1820,6 @@ static int warp_fused_batch_impl(MisContext* ctx, int kind, const MisImage* srcs
             if (k < ng) max_trig = std::max(max_trig, (trig_cols(args[i].dw) + args[i].dh + 255) / 256);
         }
         hipLaunchKernelGGL(warp_trig_batch_kernel, dim3(max_trig, ng), dim3(256), 0, ctx->stream, b);
-        // one-dimensional grid: frame after frame, per-frame strip lengths (short strips for the frames at the launch's end)
         V3Batch vb;
         int nts[WB_MAX];
         v3_plan_strips(ctx, &args[g0], ng, nt3, nts);
@@ -1948,24 +1834,53 @@ static int warp_fused_batch_impl(MisContext* ctx, int kind, const MisImage* srcs
             if (k < ng) wg += v3_grid_of(args[g0 + k], nts[k]);
         }
         vb.wg_base[WB_MAX] = wg;
-        v3batches.push_back(vb);
+        out.push_back(vb);
     }
-    if (avg_us) {
-        MIS_HIP(ctx, e0.ready(hipEventDefault));
-        MIS_HIP(ctx, e1.ready(hipEventDefault));
-        MIS_HIP(ctx, hipEventRecord(e0.ev, ctx->stream));
+}
+
+// n fused warps (the loop of image_stitching.cpp:1154-1164 for all frames) in one grid per WB_MAX frames; the results are those of
+// n mis_warp_spherical_fused_roi calls.  repeats / avg_us: the batch launched `repeats` times back to back between two HIP events
+// (avg_us = the average duration of one pass over all n frames), for the roofline measurement.
+// (the callers have checked the kind)
+static int warp_fused_batch_impl(MisContext* ctx, int kind, const MisImage* srcs, int n, float scale, const float* Ks, const float* Rs, const MisRect* rois,
+                                 MisImage* dsts, MisImage* dmasks, MisPoint* tls, int repeats, float* avg_us) {
+    MIS_CHECK(ctx, srcs && Ks && Rs && rois && dsts && dmasks && n >= 1, MIS_E_INVALID, "null argument");
+    MIS_HIP(ctx, hipSetDevice(ctx->device));
+    // per frame, whatever the kind: geometry, views, table offsets
+    std::vector<WarpArgs> args((size_t)n);
+    std::vector<DevView> din((size_t)n), dout((size_t)n), dm((size_t)n);
+    std::vector<size_t> tab_off((size_t)n);
+    size_t tab_total = 0;
+    int rc = MIS_OK;
+    for (int i = 0; i < n; i++) {
+        WarpArgs& a = args[i];
+        int brx, bry;
+        MIS_CHECK(ctx, rois[i].width > 0 && rois[i].height > 0, MIS_E_INVALID, "frame %d: empty roi", i);
+        if ((rc = setup(ctx, kind, &srcs[i], scale, Ks + 9 * i, Rs + 9 * i, &a, &brx, &bry, &rois[i])) != MIS_OK) return rc;
+        MIS_CHECK(ctx, srcs[i].channels == 3, MIS_E_UNSUPPORTED, "fused warp needs an 8UC3 source");
+        if ((rc = fused_outputs(ctx, a, &srcs[i], &dsts[i], &dmasks[i], din[i], dout[i], dm[i])) != MIS_OK) return rc;
+        tab_off[i] = tab_total;
+        tab_total += mis_align_up(sizeof(float) * trig_table_floats(a.dw, a.dh), 256);
     }
-    for (int rep = 0; rep < repeats; rep++)
-        for (const V3Batch& vb : v3batches)
-            if (kind == MIS_WARP_PLANE) hipLaunchKernelGGL(warp_strip_batch_kernel<false>, dim3(vb.wg_base[WB_MAX]), dim3(64 * V3_WAVES), 0, ctx->stream, vb);
-            else hipLaunchKernelGGL(warp_strip_batch_kernel<true>, dim3(vb.wg_base[WB_MAX]), dim3(64 * V3_WAVES), 0, ctx->stream, vb);
-    if (avg_us) {
-        float ms = 0.f;
-        MIS_HIP(ctx, hipEventRecord(e1.ev, ctx->stream));
-        MIS_HIP(ctx, hipEventSynchronize(e1.ev));
-        MIS_HIP(ctx, hipEventElapsedTime(&ms, e0.ev, e1.ev));
-        *avg_us = ms * 1000.f / (float)repeats;
+    // the launch descriptors; the separable kinds' table launches go out here, in front of the timed region
+    std::vector<PolarBatch> polar;
+    std::vector<V3Batch> strips;
+    if (kind_polar(kind)) {
+        if ((rc = plan_polar_batches(ctx, args, polar)) != MIS_OK) return rc;
+    } else {
+        uint8_t* tabs = nullptr;
+        if ((rc = mis_dev_stage(ctx, tab_total, (void**)&tabs)) != MIS_OK) return rc;
+        plan_strip_batches(ctx, args, tabs, tab_off, strips);
     }
+    RepeatTimer t;
+    if ((rc = t.begin(ctx, avg_us)) != MIS_OK) return rc;
+    for (int rep = 0; rep < repeats; rep++) {
+        for (const PolarBatch& b : polar)
+            with_polar_kind(kind, [&](auto k) { hipLaunchKernelGGL(warp_polar_fused_batch_kernel<k.value>, dim3(b.wg_base[WB_MAX]), dim3(256), 0, ctx->stream, b); });
+        for (const V3Batch& vb : strips)
+            with_ztest(kind, [&](auto z) { hipLaunchKernelGGL(warp_strip_batch_kernel<z.value>, dim3(vb.wg_base[WB_MAX]), dim3(64 * V3_WAVES), 0, ctx->stream, vb); });
+    }
+    if ((rc = t.end(ctx, repeats, avg_us)) != MIS_OK) return rc;
     MIS_HIP(ctx, hipGetLastError());
     for (int i = 0; i < n; i++) {
         if (rc == MIS_OK && (rc = dout[i].commit()) == MIS_OK) rc = dm[i].commit();
@@ -1977,7 +1892,7 @@ static int warp_fused_batch_impl(MisContext* ctx, int kind, const MisImage* srcs
 extern "C" int mis_warper_warp_fused_batch(MisContext* ctx, int kind, const MisImage* srcs, int n, float scale, const float* Ks, const float* Rs,
                                            const MisRect* rois, MisImage* dsts, MisImage* dmasks, MisPoint* tls) {
     if (!ctx) return MIS_E_INVALID;
-    MIS_CHECK(ctx, kind_ok(kind), MIS_E_UNSUPPORTED, "unknown warp kind %d", kind);
+    MIS_CHECK(ctx, MIS_WARP_KIND_IS_KNOWN(kind), MIS_E_UNSUPPORTED, "unknown warp kind %d", kind);
     if (n == 0) return MIS_OK;
     return warp_fused_batch_impl(ctx, kind, srcs, n, scale, Ks, Rs, rois, dsts, dmasks, tls, 1, nullptr);
 }
@@ -1996,7 +1911,7 @@ extern "C" int mis_warp_spherical_fused_batch_timed(MisContext* ctx, const MisIm
 
 extern "C" int mis_warper_roi_batch(MisContext* ctx, int kind, float scale, int w, int h, int n, const float* Ks, const float* Rs, MisRect* rois) {
     if (!ctx) return MIS_E_INVALID;
-    MIS_CHECK(ctx, kind_ok(kind), MIS_E_UNSUPPORTED, "unknown warp kind %d", kind);
+    MIS_CHECK(ctx, MIS_WARP_KIND_IS_KNOWN(kind), MIS_E_UNSUPPORTED, "unknown warp kind %d", kind);
     MIS_CHECK(ctx, Ks && Rs && rois && n >= 1 && w >= 1 && h >= 1 && scale > 0.f, MIS_E_INVALID, "invalid argument");
     const bool scan = MIS_WARP_ROI_IS_FULL_SCAN(kind);
     MIS_CHECK(ctx, !scan || (w <= 32767 && h <= 32767), MIS_E_INVALID, "source size %dx%d out of range", w, h);
@@ -2019,9 +1934,9 @@ extern "C" int mis_warper_roi_batch(MisContext* ctx, int kind, float scale, int 
         jobs[i].scale = scale; jobs[i].sw = w; jobs[i].sh = h; jobs[i].kind = kind; jobs[i].behind = 0;
     }
     float4* part = (float4*)((uint8_t*)ctx->roi_pinned + part_off);
-    if (kind == MIS_WARP_MERCATOR) hipLaunchKernelGGL(warp_roi_scan_kernel<MIS_WARP_MERCATOR>, dim3(nchunk, n), dim3(256), 0, ctx->stream, (const RoiJob*)jobs, part, rows, nchunk);
-    else if (kind == MIS_WARP_FISHEYE) hipLaunchKernelGGL(warp_roi_scan_kernel<MIS_WARP_FISHEYE>, dim3(nchunk, n), dim3(256), 0, ctx->stream, (const RoiJob*)jobs, part, rows, nchunk);
-    else if (kind == MIS_WARP_STEREOGRAPHIC) hipLaunchKernelGGL(warp_roi_scan_kernel<MIS_WARP_STEREOGRAPHIC>, dim3(nchunk, n), dim3(256), 0, ctx->stream, (const RoiJob*)jobs, part, rows, nchunk);
+    if (scan) with_scan_kind(kind, [&](auto k) {
+        hipLaunchKernelGGL(warp_roi_scan_kernel<k.value>, dim3(nchunk, n), dim3(256), 0, ctx->stream, (const RoiJob*)jobs, part, rows, nchunk);
+    });
     else hipLaunchKernelGGL(warp_roi_kernel, dim3(n), dim3(256), 0, ctx->stream, jobs);
     MIS_HIP(ctx, hipGetLastError());
     MIS_HIP(ctx, hipStreamSynchronize(ctx->stream));

@@ -225,6 +225,18 @@ class RotationWarper:
                                                               C.byref(mimg), C.byref(tl)))
         return (tl.x, tl.y)
 
+    @staticmethod
+    def _batch_args(imgs, cameras, rois, dsts, masks):
+        """The C arrays of a batched fused warp -> (im, ds, ms, Ks, Rs, rs, tls); Ks / Rs are the numpy arrays (they own the floats)."""
+        n = len(imgs)
+        im = (capi.MisImage * n)(*[as_image(i) for i in imgs])
+        ds = (capi.MisImage * n)(*[as_image(d) for d in dsts])
+        ms = (capi.MisImage * n)(*[as_image(m) for m in masks])
+        Ks = np.ascontiguousarray(np.stack([np.asarray(c["K"], np.float32).reshape(9) for c in cameras]))
+        Rs = np.ascontiguousarray(np.stack([np.asarray(c["R"], np.float32).reshape(9) for c in cameras]))
+        rs = (capi.MisRect * n)(*[capi.MisRect(int(r[0]), int(r[1]), int(r[2]), int(r[3])) for r in rois])
+        return im, ds, ms, Ks, Rs, rs, (capi.MisPoint * n)()
+
     def warp_fused_batch(self, imgs, cameras, rois):
         """mis_warper_warp_fused_batch: the compose-scale step of main() for all frames (one grid per 16 frames)
         -> [(tl, img_warped_s, mask_warped)], the results of warp_fused per frame."""
@@ -232,13 +244,7 @@ class RotationWarper:
         if n == 0:
             return []
         outs = [self.alloc_fused(r) for r in rois]
-        im = (capi.MisImage * n)(*[as_image(i) for i in imgs])
-        ds = (capi.MisImage * n)(*[as_image(o[0]) for o in outs])
-        ms = (capi.MisImage * n)(*[as_image(o[1]) for o in outs])
-        Ks = np.ascontiguousarray(np.stack([np.asarray(c["K"], np.float32).reshape(9) for c in cameras]))
-        Rs = np.ascontiguousarray(np.stack([np.asarray(c["R"], np.float32).reshape(9) for c in cameras]))
-        rs = (capi.MisRect * n)(*[capi.MisRect(int(r[0]), int(r[1]), int(r[2]), int(r[3])) for r in rois])
-        tls = (capi.MisPoint * n)()
+        im, ds, ms, Ks, Rs, rs, tls = self._batch_args(imgs, cameras, rois, [o[0] for o in outs], [o[1] for o in outs])
         fp = C.POINTER(C.c_float)
         self.ctx.check(self.ctx.lib.mis_warper_warp_fused_batch(self.ctx.h, self.kind, im, n, float(self.scale), Ks.ctypes.data_as(fp), Rs.ctypes.data_as(fp), rs, ds, ms, tls))
         return [((t.x, t.y), o[0], o[1]) for t, o in zip(tls, outs)]
@@ -250,13 +256,7 @@ class RotationWarper:
         if self.kind != capi.WARP_SPHERICAL:
             raise NotImplementedError("the timed warps measure the spherical kind only")
         n = len(imgs)
-        im = (capi.MisImage * n)(*[as_image(i) for i in imgs])
-        ds = (capi.MisImage * n)(*[as_image(d) for d in dsts])
-        ms = (capi.MisImage * n)(*[as_image(m) for m in masks])
-        Ks = np.ascontiguousarray(np.stack([np.asarray(c["K"], np.float32).reshape(9) for c in cameras]))
-        Rs = np.ascontiguousarray(np.stack([np.asarray(c["R"], np.float32).reshape(9) for c in cameras]))
-        rs = (capi.MisRect * n)(*[capi.MisRect(int(r[0]), int(r[1]), int(r[2]), int(r[3])) for r in rois])
-        tls = (capi.MisPoint * n)()
+        im, ds, ms, Ks, Rs, rs, tls = self._batch_args(imgs, cameras, rois, dsts, masks)
         us = C.c_float()
         fp = C.POINTER(C.c_float)
         self.ctx.check(self.ctx.lib.mis_warp_spherical_fused_batch_timed(self.ctx.h, im, n, float(self.scale), Ks.ctypes.data_as(fp), Rs.ctypes.data_as(fp), rs, ds, ms, tls,

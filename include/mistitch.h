@@ -45,6 +45,8 @@ enum { MIS_BORDER_CONSTANT = 0, MIS_BORDER_REFLECT = 2 };       /* cv::BORDER_CO
  * Mercator / Fisheye / Stereographic projectors, CPU path.  The first four have a separable backward ray (column and row tables, no
  * transcendental per pixel); the fisheye and stereographic maps are polar and are evaluated per output pixel. */
 enum { MIS_WARP_SPHERICAL = 0, MIS_WARP_CYLINDRICAL = 1, MIS_WARP_PLANE = 2, MIS_WARP_MERCATOR = 3, MIS_WARP_FISHEYE = 4, MIS_WARP_STEREOGRAPHIC = 5 };
+/* the kinds the library builds: every entry that takes a kind answers MIS_E_UNSUPPORTED ("unknown warp kind") for any other value */
+#define MIS_WARP_KIND_IS_KNOWN(kind) ((kind) >= MIS_WARP_SPHERICAL && (kind) <= MIS_WARP_STEREOGRAPHIC)
 /* the kinds whose warper has no detectResultRoi of its own: RotationWarperBase::detectResultRoi projects EVERY source pixel forward.
  * For these mis_warper_roi is O(width * height) on the host and mis_warper_roi_batch a grid-wide reduction on the device. */
 #define MIS_WARP_ROI_IS_FULL_SCAN(kind) ((kind) >= MIS_WARP_MERCATOR && (kind) <= MIS_WARP_STEREOGRAPHIC)

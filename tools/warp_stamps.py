@@ -1,4 +1,4 @@
-"""Per-wave phase stamps of warp_fused_tile_kernel (library built with -DWV_STAMPS)."""
+"""Per-wave phase stamps of warp_fused_kernel (library built with -DWV_STAMPS)."""
 import ctypes as C, sys, os, numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import image_stitching_amd as isa, synth
@@ -35,7 +35,7 @@ for tq in (2, 5, 8, 11, 14, 17, 20, 23):
 st = np.sort(s[:, 0] - t0)
 print("wave start times: p10 %d p25 %d p50 %d p75 %d p90 %d max %d" % tuple(np.percentile(st, [10, 25, 50, 75, 90, 100])))
 # per-XCD balance (tile -> workgroup -> XCD as in warp_fused_kernel: XCD j owns the j-th contiguous eighth of the workgroups)
-TW = int(os.environ.get("WV_TILE_WAVES", "2"))
+TW = 2      # TILE_WAVES of warp.hip: tiles (waves) per workgroup
 nwg = (n + TW - 1) // TW
 wg = np.arange(n) // TW
 q, rem = nwg >> 3, nwg & 7
