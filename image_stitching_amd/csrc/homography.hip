@@ -23,7 +23,10 @@
 // Phase 0 covers hypotheses [0,128) (overlapping pairs converge there), phase 1 the rest.  The replay launch of a phase empties the
 // work list again for the next phase or call.
 // A second motion model, cv::estimateAffinePartial2D (HomoParams::model = MODEL_AFFINE_PARTIAL), runs the same steps with three
-// kernels of its own: "the affine-partial model" below, where its reading of OpenCV is written down.
+// kernels of its own: "the affine-partial model" below, where its reading of OpenCV is written down.  What is not specific to a
+// model is written once for both: the RansacState reset (ransac_reset), the replay (replay_hypotheses<MODEL_POINTS>), the mask and
+// compaction (mask_and_compact<AFFINE>), LMSolverImpl::run (lm_solver_run<N>) and the control flow of a tail launch
+// (tail_problem<Model>: scan_tail_kernel and aff_tail_kernel are its two instances).
 #include "homography.h"
 #include "dev_math.h"
 #include <algorithm>
@@ -56,11 +59,18 @@ struct RansacState {
     int spec_k, spec_fail;
     long long spec_pos;
 };
+// a problem's state at the start of a call (one thread).  mode: from the model's minimum point count
+__device__ __forceinline__ void ransac_reset(RansacState* st, const int mode, const int max_iters) {
+    st->mode = mode;
+    st->n_sub = 0; st->iter = 0; st->niters = max_iters > 1 ? max_iters : 1; st->max_good = 0; st->done = 0; st->best_k = -1; st->tail_pending = 0;
+    st->draw_k = 0; st->draw_fail = 0; st->draw_pos = 0;
+    st->spec_k = 0; st->spec_fail = 0; st->spec_pos = 0;
+}
 
 // What a draw_kernel launch draws: the first phase's subsets, the second phase's, or the second phase's ahead of time (see
 // DRAW_SPEC_CHUNKS below)
 enum DrawPhase { DRAW_FIRST, DRAW_SECOND, DRAW_SPEC };
-// What a scan_tail_kernel launch does.  The split lets the tails of the problems that end in the first RANSAC phase (latency
+// What a tail launch (scan_tail_kernel, aff_tail_kernel) does.  The split lets the tails of the problems that end in the first RANSAC phase (latency
 // bound, ~2 ms) run on another stream while the second phase of the others -- which only needs the replay's verdict -- goes on.
 enum TailKind {
     TAIL_REPLAY_FINISH,   // replay, then the whole tail of the problems that end here (mask, DLT on the inliers, LM refinement)
@@ -394,12 +404,7 @@ struct DrawProblem {
 __device__ __forceinline__ bool draw_enter(DrawShared& sh, const HomoCall& c, RansacState* st, DrawPhase phase, int max_iters, int k_hi_arg, double confidence, int* k_hi_) {
     const int t = threadIdx.x;
     if (phase == DRAW_FIRST) {
-        if (t == 0) {
-            st->mode = (!c.active || c.n < 4) ? 0 : (c.n == 4 ? 1 : 2);
-            st->n_sub = 0; st->iter = 0; st->niters = max_iters > 1 ? max_iters : 1; st->max_good = 0; st->done = 0; st->best_k = -1; st->tail_pending = 0;
-            st->draw_k = 0; st->draw_fail = 0; st->draw_pos = 0;
-            st->spec_k = 0; st->spec_fail = 0; st->spec_pos = 0;
-        }
+        if (t == 0) ransac_reset(st, (!c.active || c.n < 4) ? 0 : (c.n == 4 ? 1 : 2), max_iters);
         if (!c.active || c.n <= 4) return false;
     } else if (phase == DRAW_SPEC) {
         // (the first phase's replay may be writing iter / niters / done / ... of this problem: none of them is read here)
@@ -1483,11 +1488,121 @@ __device__ void dlt_coop(TailShared& S, const float* s1, const float* d1, int np
     __syncthreads();
 }
 
-// createLMSolver(HomographyRefineCallback, 10)->run(H8): OpenCV <= 4.5 LMSolverImpl::run
+// LMSolverImpl::run's variables over N parameters, in TailShared::lm
+template <int N>
+struct LmVars {
+    double *x, *xd, *A, *Ap, *v, *d, *D, *sc;      // sc: S, Sd, rmax, accepted, lambda, lc, need_invert, nu
+    __device__ __forceinline__ explicit LmVars(double* lm) : x(lm), xd(x + N), A(xd + N), Ap(A + N * N), v(Ap + N * N), d(v + N), D(d + N), sc(D + N) {}
+};
+// createLMSolver(callback, lm_iters)->run(x): OpenCV <= 4.5 LMSolverImpl::run over N parameters, by the whole workgroup; x stands in
+// LmVars<N>::x on entry and on return.  normal_eq(h, with_J) is the callback at h: with_J, J^T J -> A, J^T r -> v, |r|^2 -> sc[0],
+// |r|_inf -> sc[2]; without, |r|^2 -> sc[1] alone.  It ends behind a barrier
+template <int N, class NormalEq>
+__device__ __forceinline__ void lm_solver_run(TailShared& S, const int lm_iters, NormalEq&& normal_eq) {
+    const int t = threadIdx.x;
+    const LmVars<N> L(S.lm);
+    double* const x = L.x; double* const xd = L.xd; double* const A = L.A; double* const Ap = L.Ap;
+    double* const v = L.v; double* const d = L.d; double* const D = L.D; double* const sc = L.sc;
+    normal_eq(x, true);
+    if (t < N) D[t] = A[t * N + t];
+    if (t == 0) { sc[4] = 1; sc[5] = 0.75; }  // lambda, lc
+    __syncthreads();
+    for (int iter = 0;;) {
+        if (t < N * N) S.A[t] = (t / N == t % N) ? A[t] + sc[4] * D[t / N] : A[t];
+        __syncthreads();
+        jacobi_eigen_coop<N>(S);
+        if (t == 0) {
+            // solve(Ap, v, d, DECOMP_EIG): Jacobi + SVBkSb back substitution
+            double thrw = 0;
+            for (int i = 0; i < N; i++) thrw += S.W[i];
+            thrw *= DBL_EPSILON * 2;
+            for (int j = 0; j < N; j++) d[j] = 0;
+            for (int i = 0; i < N; i++) {
+                double wi = S.W[i];
+                if (fabs(wi) <= thrw) continue;
+                wi = 1 / wi;
+                double s = 0;
+                for (int j = 0; j < N; j++) s += S.V[i * N + j] * v[j];
+                s *= wi;
+                for (int j = 0; j < N; j++) d[j] = d[j] + s * S.V[i * N + j];
+            }
+            for (int i = 0; i < N; i++) xd[i] = x[i] - d[i];
+        }
+        __syncthreads();
+        normal_eq(xd, false);  // Sd
+        if (t == 0) {
+            double Sv = sc[0], Sd = sc[1], lambda = sc[4], lc = sc[5];
+            double temp_d[N], dS = 0;
+            for (int i = 0; i < N; i++) {
+                double s = 0;
+                for (int j = 0; j < N; j++) s += A[i * N + j] * d[j];
+                temp_d[i] = s * -1. + v[i] * 2.;
+            }
+            for (int i = 0; i < N; i++) dS += d[i] * temp_d[i];
+            double R = (Sv - Sd) / (fabs(dS) > DBL_EPSILON ? dS : 1);
+            sc[6] = 0;
+            if (R > 0.75) {
+                lambda *= 0.5;
+                if (lambda < lc) lambda = 0;
+            } else if (R < 0.25) {
+                double tt = 0;
+                for (int i = 0; i < N; i++) tt += d[i] * v[i];
+                double nu = (Sd - Sv) / (fabs(tt) > DBL_EPSILON ? tt : 1) + 2;
+                nu = nu < 2. ? 2. : (nu > 10. ? 10. : nu);
+                if (lambda == 0) sc[6] = 1;  // needs invert(A): done by the whole workgroup below
+                else lambda *= nu;
+                sc[7] = nu;
+            }
+            sc[4] = lambda; sc[5] = lc;
+        }
+        __syncthreads();
+        if (sc[6] != 0.) {
+            // invert(A, Ap, DECOMP_EIG) -> lambda = lc = 1 / max |diag|, nu halved
+            if (t < N * N) S.A[t] = A[t];
+            __syncthreads();
+            jacobi_eigen_coop<N>(S);
+            if (t == 0) {
+                double thrw = 0;
+                for (int i = 0; i < N; i++) thrw += S.W[i];
+                thrw *= DBL_EPSILON * 2;
+                for (int e = 0; e < N * N; e++) Ap[e] = 0;
+                for (int i = 0; i < N; i++) {
+                    double wi = S.W[i];
+                    if (fabs(wi) <= thrw) continue;
+                    wi = 1 / wi;
+                    for (int r = 0; r < N; r++)
+                        for (int c = 0; c < N; c++) Ap[r * N + c] = Ap[r * N + c] + S.V[i * N + r] * (S.V[i * N + c] * wi);
+                }
+                double maxval = DBL_EPSILON;
+                for (int i = 0; i < N; i++) { double a = fabs(Ap[i * N + i]); if (a > maxval) maxval = a; }
+                double lambda = 1. / maxval, nu = sc[7] * 0.5;
+                sc[5] = lambda;
+                sc[4] = lambda * nu;
+            }
+            __syncthreads();
+        }
+        if (t == 0) {
+            double Sv = sc[0], Sd = sc[1];
+            sc[3] = Sd < Sv ? 1. : 0.;
+            if (Sd < Sv) { sc[0] = Sd; for (int i = 0; i < N; i++) x[i] = xd[i]; }
+        }
+        __syncthreads();
+        if (sc[3] != 0.) normal_eq(x, true);
+        iter++;
+        PROF_LM_ITERATION(S);
+        double dmax = 0;
+        for (int i = 0; i < N; i++) { double a = fabs(d[i]); if (a > dmax) dmax = a; }
+        bool proceed = iter < lm_iters && dmax >= (double)FLT_EPSILON && sc[2] >= (double)FLT_EPSILON;
+        __syncthreads();
+        if (!proceed) break;
+    }
+}
+
+// createLMSolver(HomographyRefineCallback, 10)->run(H8)
 __device__ void lm_refine_coop(TailShared& S, const float* s1, const float* d1, int np, float4 pt0, double* rec) {
     const int t = threadIdx.x;
-    double* x = S.lm;            double* xd = x + 8;   double* A = xd + 8;  double* Ap = A + 64;
-    double* v = Ap + 64;         double* d = v + 8;    double* D = d + 8;   double* sc = D + 8;  // S, Sd, rmax, accepted, lambda, lc, need_invert, nu
+    const LmVars<8> L(S.lm);
+    double* const x = L.x; double* const A = L.A; double* const v = L.v; double* const sc = L.sc;
     int ai = 0, aj = t;
     while (t < 36 && aj >= 8 - ai) { aj -= 8 - ai; ai++; }
     aj += ai;
@@ -1547,99 +1662,7 @@ __device__ void lm_refine_coop(TailShared& S, const float* s1, const float* d1, 
     };
     if (t < 8) x[t] = S.best[t];
     __syncthreads();
-    normal_eq(x, true);
-    if (t < 8) D[t] = A[t * 8 + t];
-    if (t == 0) { sc[4] = 1; sc[5] = 0.75; }  // lambda, lc
-    __syncthreads();
-    for (int iter = 0;;) {
-        if (t < 64) S.A[t] = (t / 8 == t % 8) ? A[t] + sc[4] * D[t / 8] : A[t];
-        __syncthreads();
-        jacobi_eigen_coop<8>(S);
-        if (t == 0) {
-            // solve(Ap, v, d, DECOMP_EIG): Jacobi + SVBkSb back substitution
-            double thrw = 0;
-            for (int i = 0; i < 8; i++) thrw += S.W[i];
-            thrw *= DBL_EPSILON * 2;
-            for (int j = 0; j < 8; j++) d[j] = 0;
-            for (int i = 0; i < 8; i++) {
-                double wi = S.W[i];
-                if (fabs(wi) <= thrw) continue;
-                wi = 1 / wi;
-                double s = 0;
-                for (int j = 0; j < 8; j++) s += S.V[i * 8 + j] * v[j];
-                s *= wi;
-                for (int j = 0; j < 8; j++) d[j] = d[j] + s * S.V[i * 8 + j];
-            }
-            for (int i = 0; i < 8; i++) xd[i] = x[i] - d[i];
-        }
-        __syncthreads();
-        normal_eq(xd, false);  // Sd
-        if (t == 0) {
-            double Sv = sc[0], Sd = sc[1], lambda = sc[4], lc = sc[5];
-            double temp_d[8], dS = 0;
-            for (int i = 0; i < 8; i++) {
-                double s = 0;
-                for (int j = 0; j < 8; j++) s += A[i * 8 + j] * d[j];
-                temp_d[i] = s * -1. + v[i] * 2.;
-            }
-            for (int i = 0; i < 8; i++) dS += d[i] * temp_d[i];
-            double R = (Sv - Sd) / (fabs(dS) > DBL_EPSILON ? dS : 1);
-            sc[6] = 0;
-            if (R > 0.75) {
-                lambda *= 0.5;
-                if (lambda < lc) lambda = 0;
-            } else if (R < 0.25) {
-                double tt = 0;
-                for (int i = 0; i < 8; i++) tt += d[i] * v[i];
-                double nu = (Sd - Sv) / (fabs(tt) > DBL_EPSILON ? tt : 1) + 2;
-                nu = nu < 2. ? 2. : (nu > 10. ? 10. : nu);
-                if (lambda == 0) sc[6] = 1;  // needs invert(A): done by the whole workgroup below
-                else lambda *= nu;
-                sc[7] = nu;
-            }
-            sc[4] = lambda; sc[5] = lc;
-        }
-        __syncthreads();
-        if (sc[6] != 0.) {
-            // invert(A, Ap, DECOMP_EIG) -> lambda = lc = 1 / max |diag|, nu halved
-            if (t < 64) S.A[t] = A[t];
-            __syncthreads();
-            jacobi_eigen_coop<8>(S);
-            if (t == 0) {
-                double thrw = 0;
-                for (int i = 0; i < 8; i++) thrw += S.W[i];
-                thrw *= DBL_EPSILON * 2;
-                for (int e = 0; e < 64; e++) Ap[e] = 0;
-                for (int i = 0; i < 8; i++) {
-                    double wi = S.W[i];
-                    if (fabs(wi) <= thrw) continue;
-                    wi = 1 / wi;
-                    for (int r = 0; r < 8; r++)
-                        for (int c = 0; c < 8; c++) Ap[r * 8 + c] = Ap[r * 8 + c] + S.V[i * 8 + r] * (S.V[i * 8 + c] * wi);
-                }
-                double maxval = DBL_EPSILON;
-                for (int i = 0; i < 8; i++) { double a = fabs(Ap[i * 8 + i]); if (a > maxval) maxval = a; }
-                double lambda = 1. / maxval, nu = sc[7] * 0.5;
-                sc[5] = lambda;
-                sc[4] = lambda * nu;
-            }
-            __syncthreads();
-        }
-        if (t == 0) {
-            double Sv = sc[0], Sd = sc[1];
-            sc[3] = Sd < Sv ? 1. : 0.;
-            if (Sd < Sv) { sc[0] = Sd; for (int i = 0; i < 8; i++) x[i] = xd[i]; }
-        }
-        __syncthreads();
-        if (sc[3] != 0.) normal_eq(x, true);
-        iter++;
-        PROF_LM_ITERATION(S);
-        double dmax = 0;
-        for (int i = 0; i < 8; i++) { double a = fabs(d[i]); if (a > dmax) dmax = a; }
-        bool proceed = iter < 10 && dmax >= (double)FLT_EPSILON && sc[2] >= (double)FLT_EPSILON;
-        __syncthreads();
-        if (!proceed) break;
-    }
+    lm_solver_run<8>(S, 10, normal_eq);
     if (t < 8) S.best[t] = x[t];
     __syncthreads();
 }
@@ -1647,7 +1670,7 @@ __device__ void lm_refine_coop(TailShared& S, const float* s1, const float* d1, 
 #ifndef MIS_TAIL_WAVES
 #define MIS_TAIL_WAVES 3      // <= 168 registers: a 200-register workgroup waits longer for room beside the composition's grids (6.65 vs 6.9 ms per step; 4 waves = 128 registers spill into the Jacobi loop)
 #endif
-// one problem of a scan_tail_kernel launch, as its steps see it
+// one problem of a tail launch, as its steps see it
 struct TailProblem {
     int b, n; HomoCall c; RansacState* st; HomoResult* res;
     float* s1; float* d1; double* rec;      // s1, d1: the compacted inliers, src and dst
@@ -1770,28 +1793,34 @@ __device__ __forceinline__ void refine_on_inliers(TailShared& S, const TailProbl
     PROF_TAIL_END(S, np, kind, want, pt);
 }
 
-__global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(MIS_TAIL_WAVES, 8))) void scan_tail_kernel(const HomoCall* calls, RansacState* states, const double* Hc, const int* valid, const int* good,
-                                                       float* scr_all, double* rec_all, HomoResult* results, int lo, int hi, int max_iters,
-                                                       double confidence, float thr, int* fin, TailKind kind, int want, int staged, unsigned* work_ctr) {
+// One problem (a workgroup) of a tail launch of either motion model: the launch kinds, `want` and the pending flags.  S is the
+// kernel's TailShared.  The Model says what differs between the models and nothing else:
+//   MODEL_POINTS, AFFINE         the replay's model size; the inlier test of mask_and_compact
+//   staged, reset_stages()       whether ordered_sums has its dynamic-LDS stages; their reset (all threads)
+//   rec(c)                       the problem's record scratch
+//   no_loop(S, p, mode, lo, fin) the problem without a RANSAC loop (all threads)
+//   load_best(S, p, max_iters)   the best hypothesis -> S.best, S.Hf (one thread)
+//   refine(S, p, np, kind, want) the refinement on the np compacted inliers: S.best (all threads)
+//   store(res, best)             S.best -> HomoResult::H (one thread)
+template <class Model>
+__device__ __forceinline__ void tail_problem(TailShared& S, const Model& m, const HomoCall* calls, RansacState* states, const int* valid, const int* good, float* scr_all,
+                                             HomoResult* results, int lo, int hi, int max_iters, double confidence, float thr, int* fin, TailKind kind, int want, unsigned* work_ctr) {
     // a replay launch runs behind the phase's last reader of the hypothesis work list: empty it for the next phase or call
     if (work_ctr && blockIdx.x == 0 && threadIdx.x < WL_CTRS) work_ctr[threadIdx.x] = 0;
 #if MIS_CHAIN_PRIO
     __builtin_amdgcn_s_setprio(MIS_CHAIN_PRIO);      // a latency-bound chain beside the composition's bandwidth-bound kernels: its few waves issue first
 #endif
-    PROF_FIRST_ENTRY(kind, want, wg_in);
-    __shared__ TailShared S;
-    if (threadIdx.x == 0) { S.staged = staged; S.bad = 0; }
-    if (staged)
-        for (int i = threadIdx.x; i < 2 * PS_PTS; i += TB) tail_dyn[i * PS_PITCH + PS_TERMS] = 0.;      // (stage 1 follows stage 0 at PS_PTS * PS_PITCH)
+    if (threadIdx.x == 0) { S.staged = m.staged; S.bad = 0; }
+    m.reset_stages();
     __syncthreads();
     const int b = blockIdx.x, t = threadIdx.x;
     TailProblem p;
     p.b = b; p.c = calls[b]; p.n = p.c.n; p.st = states + b; p.res = results + b;
-    p.s1 = scr_all + 4 * p.c.pt_off; p.d1 = p.s1 + 2 * (size_t)(p.n > 0 ? p.n : 0); p.rec = rec_all + 10 * p.c.pt_off;
+    p.s1 = scr_all + 4 * p.c.pt_off; p.d1 = p.s1 + 2 * (size_t)(p.n > 0 ? p.n : 0); p.rec = m.rec(p.c);
     RansacState* const st = p.st;
     const bool refines = kind == TAIL_REFINE_ONLY;
     if (kind == TAIL_MASK_ONLY || refines) {
-        // the tail of a pending problem: mask + compaction (flag 1 -> 2), then DLT + LM (2 -> 0)
+        // the tail of a pending problem: mask + compaction (flag 1 -> 2), then the refinement (2 -> 0)
         if (st->tail_pending != (refines ? 2 : 1) || fin[b] != want) return;   // uniform
         __syncthreads();                                    // every thread has read the flag before it changes
     } else {
@@ -1799,8 +1828,8 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(MIS_TAIL_WAV
         const int mode = st->mode;
         if (t == 0) S.done_now = 0;
         __syncthreads();
-        if (mode != 2) { finish_without_loop(S, p, mode, lo, fin); return; }
-        replay_hypotheses(S, p, valid, good, lo, hi, max_iters, confidence, fin);
+        if (mode != 2) { m.no_loop(S, p, mode, lo, fin); return; }
+        replay_hypotheses<Model::MODEL_POINTS>(S, p, valid, good, lo, hi, max_iters, confidence, fin);
         __syncthreads();
         if (!S.done_now) return;
         if (kind == TAIL_REPLAY_ONLY) { if (t == 0) st->tail_pending = 1; return; }
@@ -1814,22 +1843,48 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(MIS_TAIL_WAV
         return;
     }
     // ... and the best model's tail
-    if (t == 0) {
-        const double* hb = Hc + ((size_t)b * max_iters + st->best_k) * 9;
-        for (int i = 0; i < 9; i++) { S.best[i] = hb[i]; S.Hf[i] = (float)hb[i]; }
-        S.base = refines ? p.res->ninl : 0;
-    }
+    if (t == 0) { m.load_best(S, p, max_iters); S.base = refines ? p.res->ninl : 0; }
     __syncthreads();
-    if (!refines) mask_and_compact(S, p, thr);
+    if (!refines) mask_and_compact<Model::AFFINE>(S, p, thr);
     const int np = S.base;
-    if (kind == TAIL_MASK_ONLY) {   // the inlier set is final here; DLT + LM on it (TAIL_REFINE_ONLY) only changes H
-        if (t == 0) { p.res->ninl = np; for (int i = 0; i < 9; i++) p.res->H[i] = S.best[i]; st->tail_pending = 2; }
+    if (kind == TAIL_MASK_ONLY) {   // the inlier set is final here; the refinement (TAIL_REFINE_ONLY) only changes H
+        if (t == 0) { p.res->ninl = np; m.store(p.res, S.best); st->tail_pending = 2; }
         return;
     }
-    refine_on_inliers(S, p, np, kind, want);
-    PROF_LAST_EXIT(kind, want, wg_in);
-    if (t == 0) { for (int i = 0; i < 9; i++) p.res->H[i] = S.best[i]; p.res->ninl = np; if (refines) st->tail_pending = 0; }
+    m.refine(S, p, np, kind, want);
+    if (t == 0) { m.store(p.res, S.best); p.res->ninl = np; if (refines) st->tail_pending = 0; }
 }
+
+// the homography's steps of tail_problem: the model of hypothesis k is Hc's, the refinement is DLT on the inliers + 8-parameter LM
+struct HomographyTail {
+    static constexpr int MODEL_POINTS = 4;
+    static constexpr bool AFFINE = false;
+    const double* Hc; double* rec_all; int staged;
+    PROF_ONLY(unsigned long long wg_in;)
+    __device__ __forceinline__ void reset_stages() const {
+        if (staged)
+            for (int i = threadIdx.x; i < 2 * PS_PTS; i += TB) tail_dyn[i * PS_PITCH + PS_TERMS] = 0.;      // (stage 1 follows stage 0 at PS_PTS * PS_PITCH)
+    }
+    __device__ __forceinline__ double* rec(const HomoCall& c) const { return rec_all + 10 * c.pt_off; }
+    __device__ __forceinline__ void no_loop(TailShared& S, const TailProblem& p, const int mode, const int lo, int* fin) const { finish_without_loop(S, p, mode, lo, fin); }
+    __device__ __forceinline__ void load_best(TailShared& S, const TailProblem& p, const int max_iters) const {
+        const double* hb = Hc + ((size_t)p.b * max_iters + p.st->best_k) * 9;
+        for (int i = 0; i < 9; i++) { S.best[i] = hb[i]; S.Hf[i] = (float)hb[i]; }
+    }
+    __device__ __forceinline__ void refine(TailShared& S, const TailProblem& p, const int np, const TailKind kind, const int want) const {
+        refine_on_inliers(S, p, np, kind, want);
+        PROF_LAST_EXIT(kind, want, wg_in);
+    }
+    __device__ __forceinline__ void store(HomoResult* res, const double* best) const { for (int i = 0; i < 9; i++) res->H[i] = best[i]; }
+};
+__global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(MIS_TAIL_WAVES, 8))) void scan_tail_kernel(const HomoCall* calls, RansacState* states, const double* Hc, const int* valid, const int* good,
+                                                       float* scr_all, double* rec_all, HomoResult* results, int lo, int hi, int max_iters,
+                                                       double confidence, float thr, int* fin, TailKind kind, int want, int staged, unsigned* work_ctr) {
+    PROF_FIRST_ENTRY(kind, want, wg_in);
+    __shared__ TailShared S;
+    tail_problem(S, HomographyTail{Hc, rec_all, staged PROF_ONLY(, wg_in)}, calls, states, valid, good, scr_all, results, lo, hi, max_iters, confidence, thr, fin, kind, want, work_ctr);
+}
+
 
 // ================================================================ the affine-partial model =====
 // cv::estimateAffinePartial2D(src, dst, inliers, RANSAC, thresh, maxIters, confidence, refineIters), the estimator behind
@@ -1849,7 +1904,7 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(MIS_TAIL_WAV
 //  * computeError / findInliers in float32: F = (float)M, a = F0 x + F1 y + F2 - X, b = F3 x + F4 y + F5 - Y, inlier when
 //    a a + b b <= (float)(thresh thresh).
 //  * refinement, only with a model, n > 2 and refineIters > 0: the inliers compressed in order; [uncertain] LMSolver (the <= 4.5
-//    LMSolverImpl::run restated by lm_refine_coop above, same stop rule, refineIters iterations) over (a, b, tx, ty) from
+//    LMSolverImpl::run of lm_solver_run above, the homography's solver with N = 4 and refineIters iterations) over (a, b, tx, ty) from
 //    (M0, M3, M2, M5); residuals (a x - b y + tx - X, b x + a y + ty - Y), Jacobian rows (x, -y, 1, 0), (y, x, 0, 1); the result is
 //    written back as [a -b tx; b a ty].  The returned mask is the RANSAC mask: it is not recomputed after the refinement.
 // The steps are the homography's -- draw, hypotheses from the work list, replay, tails -- with these kernels:
@@ -1860,8 +1915,9 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(MIS_TAIL_WAV
 //                     are solved by 64 lanes into LDS (closed form, ~40 f64 operations: no Hc, no Jacobi), the problem's points
 //                     are staged in LDS once per workgroup (AH_TILE at a time), each wave counts 16 hypotheses, lanes striding
 //                     the points, counts from ballots.
-//   aff_tail_kernel   replay (replay_hypotheses<2>), mask + ordered compaction, 4-parameter LM.  The best model is solved again
-//                     from its subset (same function, same bits) instead of being stored per hypothesis.
+//   aff_tail_kernel   tail_problem<AffinePartialTail>: the homography's launch kinds, `want` and pending flags around this model's
+//                     replay (replay_hypotheses<2>), inlier test and 4-parameter LM.  The best model is solved again from its
+//                     subset (same function, same bits) instead of being stored per hypothesis.
 // Nothing here depends on the grid size or on which workgroup takes which entry: every count lands at its (problem, hypothesis).
 __device__ __forceinline__ void aff_hypothesis(const float2 p1, const float2 P1, const float2 p2, const float2 P2, double* M) {
     const double x1 = p1.x, y1 = p1.y, X1 = P1.x, Y1 = P1.y, x2 = p2.x, y2 = p2.y, X2 = P2.x, Y2 = P2.y;
@@ -1904,12 +1960,7 @@ __global__ __launch_bounds__(TB) void aff_draw_kernel(const HomoCall* calls, Ran
     int k = 0;
     long long pos = 0;
     if (phase == DRAW_FIRST) {
-        if (t == 0) {
-            st->mode = (!c.active || c.n < 2) ? 0 : (c.n == 2 ? 1 : 2);
-            st->n_sub = 0; st->iter = 0; st->niters = max_iters > 1 ? max_iters : 1; st->max_good = 0; st->done = 0; st->best_k = -1; st->tail_pending = 0;
-            st->draw_k = 0; st->draw_fail = 0; st->draw_pos = 0;
-            st->spec_k = 0; st->spec_fail = 0; st->spec_pos = 0;
-        }
+        if (t == 0) ransac_reset(st, (!c.active || c.n < 2) ? 0 : (c.n == 2 ? 1 : 2), max_iters);
         if (!c.active || c.n <= 2) return;
     } else {
         if (st->mode != 2 || st->done) return;
@@ -2049,12 +2100,12 @@ __global__ __launch_bounds__(256) void aff_score_kernel(const HomoCall* calls, c
 // The LM refinement over (a, b, tx, ty).  The problem is linear, so J^T J is a function of the points alone:
 // [sq 0 sx sy; 0 sq -sy sx; sx -sy N 0; sy sx 0 N] with sx = sum x, sy = sum y, sq = sum (x x + y y).  Every sum -- those three, the
 // four of J^T e and |e|^2 -- adds its terms in point order, one lane per sum (two terms a point, row after row of J, where a point
-// has two: acc += u; acc += w), the discipline of the homography tail; the 4 x 4 solve is LMSolver's solve(DECOMP_EIG) on
-// jacobi_eigen_coop<4>, not the 9 x 9 path.
+// has two: acc += u; acc += w), the discipline of the homography tail.  The solver is lm_solver_run<4>: its 4 x 4 solve is
+// LMSolver's solve(DECOMP_EIG) on jacobi_eigen_coop<4>, not the 9 x 9 path.
 __device__ void aff_lm_refine(TailShared& S, const float* s1, const float* d1, const int np, const int lm_iters) {
     const int t = threadIdx.x;
-    double* x = S.lm;            double* xd = x + 4;   double* A = xd + 4;  double* Ap = A + 16;
-    double* v = Ap + 16;         double* d = v + 4;    double* D = d + 4;   double* sc = D + 4;  // S, Sd, rmax, accepted, lambda, lc, need_invert, nu
+    const LmVars<4> L(S.lm);
+    double* const x = L.x; double* const A = L.A; double* const v = L.v; double* const sc = L.sc;
     double* sums = S.nrm;        // sx sy sq v0 v1 v2 v3 |e|^2
     // this lane's sum (lane t < 8 of wave 0): its terms in a point's record {x, y, xx, yy, x e0, y e1, -y e0, x e1, e0, e1}
     const int i0 = t == 0 ? 0 : t == 1 ? 1 : t == 2 ? 2 : t == 3 ? 4 : t == 4 ? 6 : t == 5 ? 8 : t == 6 ? 9 : 8;
@@ -2101,98 +2152,7 @@ __device__ void aff_lm_refine(TailShared& S, const float* s1, const float* d1, c
     };
     if (t == 0) { x[0] = S.best[0]; x[1] = S.best[3]; x[2] = S.best[2]; x[3] = S.best[5]; }
     __syncthreads();
-    normal_eq(x, true);
-    if (t < 4) D[t] = A[t * 4 + t];
-    if (t == 0) { sc[4] = 1; sc[5] = 0.75; }  // lambda, lc
-    __syncthreads();
-    for (int iter = 0;;) {
-        if (t < 16) S.A[t] = (t / 4 == t % 4) ? A[t] + sc[4] * D[t / 4] : A[t];
-        __syncthreads();
-        jacobi_eigen_coop<4>(S);
-        if (t == 0) {
-            // solve(Ap, v, d, DECOMP_EIG): Jacobi + SVBkSb back substitution
-            double thrw = 0;
-            for (int i = 0; i < 4; i++) thrw += S.W[i];
-            thrw *= DBL_EPSILON * 2;
-            for (int j = 0; j < 4; j++) d[j] = 0;
-            for (int i = 0; i < 4; i++) {
-                double wi = S.W[i];
-                if (fabs(wi) <= thrw) continue;
-                wi = 1 / wi;
-                double s = 0;
-                for (int j = 0; j < 4; j++) s += S.V[i * 4 + j] * v[j];
-                s *= wi;
-                for (int j = 0; j < 4; j++) d[j] = d[j] + s * S.V[i * 4 + j];
-            }
-            for (int i = 0; i < 4; i++) xd[i] = x[i] - d[i];
-        }
-        __syncthreads();
-        normal_eq(xd, false);  // Sd
-        if (t == 0) {
-            double Sv = sc[0], Sd = sc[1], lambda = sc[4], lc = sc[5];
-            double temp_d[4], dS = 0;
-            for (int i = 0; i < 4; i++) {
-                double s = 0;
-                for (int j = 0; j < 4; j++) s += A[i * 4 + j] * d[j];
-                temp_d[i] = s * -1. + v[i] * 2.;
-            }
-            for (int i = 0; i < 4; i++) dS += d[i] * temp_d[i];
-            double R = (Sv - Sd) / (fabs(dS) > DBL_EPSILON ? dS : 1);
-            sc[6] = 0;
-            if (R > 0.75) {
-                lambda *= 0.5;
-                if (lambda < lc) lambda = 0;
-            } else if (R < 0.25) {
-                double tt = 0;
-                for (int i = 0; i < 4; i++) tt += d[i] * v[i];
-                double nu = (Sd - Sv) / (fabs(tt) > DBL_EPSILON ? tt : 1) + 2;
-                nu = nu < 2. ? 2. : (nu > 10. ? 10. : nu);
-                if (lambda == 0) sc[6] = 1;  // needs invert(A)
-                else lambda *= nu;
-                sc[7] = nu;
-            }
-            sc[4] = lambda; sc[5] = lc;
-        }
-        __syncthreads();
-        if (sc[6] != 0.) {
-            // invert(A, Ap, DECOMP_EIG) -> lambda = lc = 1 / max |diag|, nu halved
-            if (t < 16) S.A[t] = A[t];
-            __syncthreads();
-            jacobi_eigen_coop<4>(S);
-            if (t == 0) {
-                double thrw = 0;
-                for (int i = 0; i < 4; i++) thrw += S.W[i];
-                thrw *= DBL_EPSILON * 2;
-                for (int e = 0; e < 16; e++) Ap[e] = 0;
-                for (int i = 0; i < 4; i++) {
-                    double wi = S.W[i];
-                    if (fabs(wi) <= thrw) continue;
-                    wi = 1 / wi;
-                    for (int r = 0; r < 4; r++)
-                        for (int cc = 0; cc < 4; cc++) Ap[r * 4 + cc] = Ap[r * 4 + cc] + S.V[i * 4 + r] * (S.V[i * 4 + cc] * wi);
-                }
-                double maxval = DBL_EPSILON;
-                for (int i = 0; i < 4; i++) { double aa = fabs(Ap[i * 4 + i]); if (aa > maxval) maxval = aa; }
-                double lambda = 1. / maxval, nu = sc[7] * 0.5;
-                sc[5] = lambda;
-                sc[4] = lambda * nu;
-            }
-            __syncthreads();
-        }
-        if (t == 0) {
-            double Sv = sc[0], Sd = sc[1];
-            sc[3] = Sd < Sv ? 1. : 0.;
-            if (Sd < Sv) { sc[0] = Sd; for (int i = 0; i < 4; i++) x[i] = xd[i]; }
-        }
-        __syncthreads();
-        if (sc[3] != 0.) normal_eq(x, true);
-        iter++;
-        double dmax = 0;
-        for (int i = 0; i < 4; i++) { double aa = fabs(d[i]); if (aa > dmax) dmax = aa; }
-        bool proceed = iter < lm_iters && dmax >= (double)FLT_EPSILON && sc[2] >= (double)FLT_EPSILON;
-        __syncthreads();
-        if (!proceed) break;
-    }
+    lm_solver_run<4>(S, lm_iters, normal_eq);
     if (t == 0) { S.best[0] = x[0]; S.best[1] = -x[1]; S.best[2] = x[2]; S.best[3] = x[1]; S.best[4] = x[0]; S.best[5] = x[3]; }
     __syncthreads();
 }
@@ -2203,68 +2163,41 @@ __device__ __forceinline__ void aff_store(HomoResult* res, const double* M) {
     res->H[6] = 0; res->H[7] = 0; res->H[8] = 1;
 }
 
-// The launch kinds, want and the pending flags are scan_tail_kernel's
+// the affine-partial model's steps of tail_problem: the model of hypothesis k is solved again from its subset, the refinement is the
+// 4-parameter LM
+struct AffinePartialTail {
+    static constexpr int MODEL_POINTS = 2;
+    static constexpr bool AFFINE = true;
+    static constexpr int staged = 0;
+    const int* sub_idx; int lm_iters;
+    __device__ __forceinline__ void reset_stages() const {}
+    __device__ __forceinline__ double* rec(const HomoCall&) const { return nullptr; }
+    // no loop: n < 2 (or a skipped problem) has no model; n == 2 is runKernel on both points, mask all ones, no refinement
+    __device__ __forceinline__ void no_loop(TailShared&, const TailProblem& p, const int mode, const int lo, int* fin) const {
+        const int t = threadIdx.x;
+        for (int i = t; p.c.mask && p.c.active && i < p.n; i += TB) p.c.mask[i] = mode ? 1 : 0;
+        if (t == 0) {
+            p.res->ok = mode ? 1 : 0; p.res->iters = 0; p.res->ninl = mode ? 2 : 0;
+            if (mode) { const int id[2] = {0, 1}; double M[6]; aff_hypothesis_of(p.c, id, M); aff_store(p.res, M); }
+            p.st->done = 1; fin[p.b] = lo == 0 ? 0 : 1;
+        }
+    }
+    __device__ __forceinline__ void load_best(TailShared& S, const TailProblem& p, const int max_iters) const {
+        aff_hypothesis_of(p.c, sub_idx + ((size_t)p.b * max_iters + p.st->best_k) * 4, S.best);
+        for (int i = 0; i < 6; i++) S.Hf[i] = (float)S.best[i];
+    }
+    __device__ __forceinline__ void refine(TailShared& S, const TailProblem& p, const int np, TailKind, int) const {
+        if (lm_iters > 0 && np > 0) aff_lm_refine(S, p.s1, p.d1, np, lm_iters);
+    }
+    __device__ __forceinline__ void store(HomoResult* res, const double* best) const { aff_store(res, best); }
+};
 __global__ __launch_bounds__(TB) void aff_tail_kernel(const HomoCall* calls, RansacState* states, const int* sub_idx, const int* valid, const int* good, float* scr_all,
                                                       HomoResult* results, int lo, int hi, int max_iters, double confidence, float thr, int* fin, TailKind kind, int want,
                                                       int lm_iters, unsigned* work_ctr) {
-    if (work_ctr && blockIdx.x == 0 && threadIdx.x < WL_CTRS) work_ctr[threadIdx.x] = 0;
-#if MIS_CHAIN_PRIO
-    __builtin_amdgcn_s_setprio(MIS_CHAIN_PRIO);
-#endif
     __shared__ TailShared S;
-    if (threadIdx.x == 0) { S.staged = 0; S.bad = 0; }
-    __syncthreads();
-    const int b = blockIdx.x, t = threadIdx.x;
-    TailProblem p;
-    p.b = b; p.c = calls[b]; p.n = p.c.n; p.st = states + b; p.res = results + b;
-    p.s1 = scr_all + 4 * p.c.pt_off; p.d1 = p.s1 + 2 * (size_t)(p.n > 0 ? p.n : 0); p.rec = nullptr;
-    RansacState* const st = p.st;
-    const bool refines = kind == TAIL_REFINE_ONLY;
-    if (kind == TAIL_MASK_ONLY || refines) {
-        if (st->tail_pending != (refines ? 2 : 1) || fin[b] != want) return;   // uniform
-        __syncthreads();                                    // every thread has read the flag before it changes
-    } else {
-        if (st->done) return;
-        const int mode = st->mode;
-        if (t == 0) S.done_now = 0;
-        __syncthreads();
-        if (mode != 2) {
-            // no loop: n < 2 (or a skipped problem) has no model; n == 2 is runKernel on both points, mask all ones, no refinement
-            for (int i = t; p.c.mask && p.c.active && i < p.n; i += TB) p.c.mask[i] = mode ? 1 : 0;
-            if (t == 0) {
-                p.res->ok = mode ? 1 : 0; p.res->iters = 0; p.res->ninl = mode ? 2 : 0;
-                if (mode) { const int id[2] = {0, 1}; double M[6]; aff_hypothesis_of(p.c, id, M); aff_store(p.res, M); }
-                st->done = 1; fin[b] = lo == 0 ? 0 : 1;
-            }
-            return;
-        }
-        replay_hypotheses<2>(S, p, valid, good, lo, hi, max_iters, confidence, fin);
-        __syncthreads();
-        if (!S.done_now) return;
-        if (kind == TAIL_REPLAY_ONLY) { if (t == 0) st->tail_pending = 1; return; }
-    }
-    const int result = st->max_good > 0;
-    if (!refines && t == 0) { p.res->iters = st->iter; p.res->ok = result; p.res->ninl = 0; }
-    if (!result) {
-        for (int i = t; p.c.mask && i < p.n; i += TB) p.c.mask[i] = 0;
-        if (t == 0) st->tail_pending = 0;
-        return;
-    }
-    if (t == 0) {
-        aff_hypothesis_of(p.c, sub_idx + ((size_t)b * max_iters + st->best_k) * 4, S.best);
-        for (int i = 0; i < 6; i++) S.Hf[i] = (float)S.best[i];
-        S.base = refines ? p.res->ninl : 0;
-    }
-    __syncthreads();
-    if (!refines) mask_and_compact<true>(S, p, thr);
-    const int np = S.base;
-    if (kind == TAIL_MASK_ONLY) {
-        if (t == 0) { p.res->ninl = np; aff_store(p.res, S.best); st->tail_pending = 2; }
-        return;
-    }
-    if (lm_iters > 0 && np > 0) aff_lm_refine(S, p.s1, p.d1, np, lm_iters);
-    if (t == 0) { aff_store(p.res, S.best); p.res->ninl = np; if (refines) st->tail_pending = 0; }
+    tail_problem(S, AffinePartialTail{sub_idx, lm_iters}, calls, states, valid, good, scr_all, results, lo, hi, max_iters, confidence, thr, fin, kind, want, work_ctr);
 }
+
 
 // ---------------------------------------------------------------- host side --------------------
 struct RngTable {

@@ -1320,10 +1320,9 @@ extern "C" int mis_knn2(MisContext* ctx, const MisFeatures* q, const MisFeatures
     return MIS_OK;
 }
 
-extern "C" int mis_find_homography(MisContext* ctx, const float* src, const float* dst, int n, double thresh, int max_iters, double confidence,
-                                   double H[9], uint8_t* mask, int* ok) {
-    if (!ctx) return MIS_E_INVALID;
-    MIS_CHECK(ctx, src && dst && H && ok && n >= 0, MIS_E_INVALID, "null argument");
+// One problem through the RANSAC engine: src / dst staged on the device, the context's one-call batch, the first n_out doubles of
+// the model (zeros without one), the mask when asked for
+static int solve_single(MisContext* ctx, const float* src, const float* dst, int n, const HomoParams& prm, double* out, int n_out, uint8_t* mask, int* ok) {
     MIS_HIP(ctx, hipSetDevice(ctx->device));
     MatchWorkspace* ws = workspace(ctx);
     hipStream_t st = ctx->stream;
@@ -1334,7 +1333,7 @@ extern "C" int mis_find_homography(MisContext* ctx, const float* src, const floa
     MIS_HIP(ctx, ws->dev.reserve(dc.off));
     uint8_t* D = (uint8_t*)ws->dev.p;
     int rc;
-    if ((rc = homo_batch_reserve(ctx, &ws->b1, 1, (long long)nn, max_iters)) != MIS_OK) return rc;
+    if ((rc = homo_batch_reserve(ctx, &ws->b1, 1, (long long)nn, prm.max_iters)) != MIS_OK) return rc;
     if (n) {
         MIS_HIP(ctx, hipMemcpyAsync(D + o_src, src, sizeof(float) * 2 * n, hipMemcpyHostToDevice, st));
         MIS_HIP(ctx, hipMemcpyAsync(D + o_dst, dst, sizeof(float) * 2 * n, hipMemcpyHostToDevice, st));
@@ -1343,47 +1342,28 @@ extern "C" int mis_find_homography(MisContext* ctx, const float* src, const floa
     c.src = (const float*)(D + o_src); c.dst = (const float*)(D + o_dst); c.mask = D + o_mask; c.pt_off = 0; c.n = n; c.active = 1;
     MIS_HIP(ctx, hipMemcpyAsync(ws->b1.calls, &c, sizeof(c), hipMemcpyHostToDevice, st));
     MIS_HIP(ctx, hipStreamSynchronize(st));  // `c` lives on this stack frame
-    if ((rc = homo_solve(ctx, &ws->b1, HomoParams{thresh, max_iters, confidence})) != MIS_OK) return rc;
+    if ((rc = homo_solve(ctx, &ws->b1, prm)) != MIS_OK) return rc;
     HomoResult r;
     MIS_HIP(ctx, hipMemcpyAsync(&r, ws->b1.results, sizeof(r), hipMemcpyDeviceToHost, st));
     if (mask && n) MIS_HIP(ctx, hipMemcpyAsync(mask, D + o_mask, n, hipMemcpyDeviceToHost, st));
     MIS_HIP(ctx, hipStreamSynchronize(st));
     *ok = r.ok;
-    if (r.ok) memcpy(H, r.H, sizeof(r.H)); else memset(H, 0, sizeof(r.H));
+    if (r.ok) memcpy(out, r.H, sizeof(double) * n_out); else memset(out, 0, sizeof(double) * n_out);
     return MIS_OK;
+}
+
+extern "C" int mis_find_homography(MisContext* ctx, const float* src, const float* dst, int n, double thresh, int max_iters, double confidence,
+                                   double H[9], uint8_t* mask, int* ok) {
+    if (!ctx) return MIS_E_INVALID;
+    MIS_CHECK(ctx, src && dst && H && ok && n >= 0, MIS_E_INVALID, "null argument");
+    return solve_single(ctx, src, dst, n, HomoParams{thresh, max_iters, confidence}, H, 9, mask, ok);
 }
 
 extern "C" int mis_estimate_affine_partial(MisContext* ctx, const float* src, const float* dst, int n, double thresh, int max_iters, double confidence,
                                            int refine_iters, double M[6], uint8_t* mask, int* ok) {
     if (!ctx) return MIS_E_INVALID;
     MIS_CHECK(ctx, src && dst && M && ok && n >= 0, MIS_E_INVALID, "null argument");
-    MIS_HIP(ctx, hipSetDevice(ctx->device));
-    MatchWorkspace* ws = workspace(ctx);
-    hipStream_t st = ctx->stream;
-    MIS_HIP(ctx, hipStreamSynchronize(st));
-    const size_t nn = (size_t)std::max(n, 1);
-    Carver dc;
-    const size_t o_src = dc.take(sizeof(float) * 2 * nn), o_dst = dc.take(sizeof(float) * 2 * nn), o_mask = dc.take(nn);
-    MIS_HIP(ctx, ws->dev.reserve(dc.off));
-    uint8_t* D = (uint8_t*)ws->dev.p;
-    int rc;
-    if ((rc = homo_batch_reserve(ctx, &ws->b1, 1, (long long)nn, max_iters)) != MIS_OK) return rc;
-    if (n) {
-        MIS_HIP(ctx, hipMemcpyAsync(D + o_src, src, sizeof(float) * 2 * n, hipMemcpyHostToDevice, st));
-        MIS_HIP(ctx, hipMemcpyAsync(D + o_dst, dst, sizeof(float) * 2 * n, hipMemcpyHostToDevice, st));
-    }
-    HomoCall c;
-    c.src = (const float*)(D + o_src); c.dst = (const float*)(D + o_dst); c.mask = D + o_mask; c.pt_off = 0; c.n = n; c.active = 1;
-    MIS_HIP(ctx, hipMemcpyAsync(ws->b1.calls, &c, sizeof(c), hipMemcpyHostToDevice, st));
-    MIS_HIP(ctx, hipStreamSynchronize(st));  // `c` lives on this stack frame
-    if ((rc = homo_solve(ctx, &ws->b1, HomoParams{thresh, max_iters, confidence, MODEL_AFFINE_PARTIAL, refine_iters})) != MIS_OK) return rc;
-    HomoResult r;
-    MIS_HIP(ctx, hipMemcpyAsync(&r, ws->b1.results, sizeof(r), hipMemcpyDeviceToHost, st));
-    if (mask && n) MIS_HIP(ctx, hipMemcpyAsync(mask, D + o_mask, n, hipMemcpyDeviceToHost, st));
-    MIS_HIP(ctx, hipStreamSynchronize(st));
-    *ok = r.ok;
-    if (r.ok) memcpy(M, r.H, sizeof(double) * 6); else memset(M, 0, sizeof(double) * 6);
-    return MIS_OK;
+    return solve_single(ctx, src, dst, n, HomoParams{thresh, max_iters, confidence, MODEL_AFFINE_PARTIAL, refine_iters}, M, 6, mask, ok);
 }
 
 // myLeaveBiggestComponent (image_stitching.cpp:215-278): union-find over pairs with
