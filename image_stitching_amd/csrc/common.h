@@ -28,7 +28,7 @@ struct MisContext {
     void* stage = nullptr;
     size_t stage_bytes = 0;
     // The context's two auxiliary streams (non-blocking, created on first use).  Every stage that forks work off the
-    // context's stream takes them from here -- the ORB batch's helper lanes, then the matcher's side chains -- so a job owns
+    // context's stream takes them from here -- the SIFT finder's lanes, then the matcher's side chains -- so a job owns
     // four streams in all (this one, the two auxiliaries, the caller's compose stream): one per hardware queue of the
     // runtime's default of four, whichever stage is running.
     hipStream_t aux[2] = {nullptr, nullptr};
@@ -46,8 +46,15 @@ int mis_dev_stage(MisContext* ctx, size_t bytes, void** out);    // the same in 
 int mis_pool_alloc(MisContext* ctx, size_t bytes, void** out, size_t* got, MisContext* errs = nullptr);
 int mis_aux_stream(MisContext* ctx, int k, hipStream_t* out);   // k = 0, 1
 void mis_pool_free(MisContext* ctx, void* p, size_t bytes);
-// a device block for a feature set from ctx's pool of recycled blocks, registered so that mis_features_free recycles it (orb.hip)
+// Feature blocks (features.hip): a feature set owns one device block from ctx's pool of recycled blocks, registered so that
+// mis_features_free recycles it.  mis_feat_block_alloc gives a bare block (the SIFT finders lay out their own two regions);
+// mis_feat_alloc lays out [keypoints][descriptors][count] for `cap` features, every region 256-byte aligned, the count one int
+// on the device that the finder's kernels publish (mis_feat_count).
 int mis_feat_block_alloc(MisContext* ctx, size_t bytes, void** out, MisContext* errs = nullptr);
+struct MisFeatLayout { size_t desc_off, count_off, bytes; };
+MisFeatLayout mis_feat_layout(int cap, int desc_cols, int desc_dtype);
+int mis_feat_alloc(MisContext* ctx, int cap, int desc_cols, int desc_dtype, MisFeatures* f);
+int* mis_feat_count(const MisFeatures* f, int cap);
 
 #define MIS_HIP(ctx, call)                                                                             \
     do {                                                                                               \

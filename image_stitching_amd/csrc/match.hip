@@ -940,8 +940,8 @@ int enqueue_knn(MisContext* ctx, MatchWorkspace* ws, const MatchPlan& pl, const 
 
 // Three chains behind the ratio test: findHomography returns the RANSAC mask, not one recomputed after its refinement, so the
 // second estimation starts from the mask while the DLT + LM refinement of the first H runs on a third stream; the |det H| test of
-// the reference moves to the host assembly.  Side and third are the context's two auxiliary streams -- the streams the ORB batch's
-// helper lanes ran on a moment ago -- so that the job keeps to four streams (an earlier version created two more here, one in
+// the reference moves to the host assembly.  Side and third are the context's two auxiliary streams -- the streams the SIFT finder's
+// lanes run on in the feature stage -- so that the job keeps to four streams (an earlier version created two more here, one in
 // a priority class of its own to dodge a shared hardware queue: the step then moved by 25 % with GPU_MAX_HW_QUEUES).
 //
 // MIS_MATCH_AFFINE_PARTIAL (AffineBestOf2NearestMatcher::match): ONE chain on the main stream -- the first estimation's two phases,

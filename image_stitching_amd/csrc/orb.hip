@@ -6,16 +6,16 @@
 // launch (grid.z = level), so a frame costs a fixed, small number of launches:
 //   gray -> [resize l = 1..n-1] -> reflect101 borders -> FAST score -> NMS + histogram ->
 //   score cut (retainBest 2N) -> compaction -> Harris -> Harris cut (retainBest N) + canonical
-//   ranking -> keypoint assembly + intensity-centroid angle -> Gaussian blur -> rBRIEF.
+//   ranking -> keypoint assembly -> intensity-centroid angle + rBRIEF, both on the keypoint's patch staged in LDS and
+//   Gaussian-blurred at its sample points only (no blurred pyramid).
 // retainBest() keeps every element >= the N-th best value; as a *set* that is order independent, so
 // the cuts are found with histograms / radix selection and the canonical keypoint order
 // (level, response desc, y, x) is produced by counting ranks -- no sort, no host round trip.
 #include "common.h"
 #include "dev_math.h"
 #include <algorithm>
+#include <chrono>
 #include <cmath>
-#include <mutex>
-#include <unordered_map>
 
 #define ORB_MAX_LEVELS 16
 #define ORB_BORDER 32
@@ -25,9 +25,9 @@ namespace {
 struct LevelDesc {
     int w, h;          // level size
     int pp;            // pitch of the padded buffers (bytes)
-    int sp;            // pitch of the score / nms maps
+    int sp;            // pitch of the level in the nms map (debug view)
     size_t pad_off;    // offset of the padded gray level inside `pad` / `blur`
-    size_t map_off;    // offset of the level inside `score` / `nms`
+    size_t map_off;    // offset of the level inside `nms`
     float scale;       // 1.2^l
     int nfeat;         // N_l
     int n2;            // retainBest #1 size (2 N_l with the Harris score)
@@ -44,7 +44,8 @@ struct Levels {
 };
 
 struct Work {  // device pointers of one MisOrb workspace
-    uint8_t *pad, *blur, *score, *nms;
+    uint8_t* pad;
+    uint8_t *nms, *blur;   // debug views only (mis_orb_debug_level which = 1 / 2): one of each behind the frames' blocks
     int* hist;      // nlevels x 256
     int* thr;       // nlevels: FAST score cut
     int* tile_cnt;      // per tile: NMS survivors
@@ -71,7 +72,6 @@ struct OrbIO {      // per-frame inputs / outputs of a batch group (not at a reg
     size_t sstride[ORB_BATCH];
     int aligned[ORB_BATCH];
     MisKeyPoint* kps[ORB_BATCH];
-    uint32_t* lxy[ORB_BATCH];
     int* n_dev[ORB_BATCH];
     uint8_t* desc[ORB_BATCH];
 };
@@ -125,10 +125,7 @@ __device__ __forceinline__ unsigned byte_at(unsigned w0, unsigned w1, unsigned w
     const unsigned long long lo = (unsigned long long)w0 | ((unsigned long long)w1 << 32);
     return (o < 8 ? (unsigned)(lo >> (8 * o)) : (w2 >> (8 * (o - 8)))) & 255u;
 }
-#ifndef MIS_RS_ROWS
-#define MIS_RS_ROWS 4
-#endif
-constexpr int RS_ROWS = MIS_RS_ROWS;     // output rows per wave
+constexpr int RS_ROWS = 4;     // output rows per wave
 __global__ __launch_bounds__(256) void resize_kernel(const uint8_t* __restrict__ src, int sw, int sh, int spp, uint8_t* __restrict__ dst, int dw, int dh, int dpp,
                                                      const int* __restrict__ tab, size_t ws) {
     // a workgroup = 256 columns x 4 RS_ROWS rows, a wave = 256 columns x RS_ROWS rows: the column tables are loaded once for the rows,
@@ -310,10 +307,7 @@ __device__ __forceinline__ int fast_score_px(const uint8_t* p, int pp, int t) { 
 // The gray tile (+4 halo) is staged with coalesced dword loads issued up front, the scores of the tile
 // (+1 halo) are computed from LDS, and the survivors go to a per-level list (x | y << 16, score) and a
 // per-level histogram: the score map never exists in HBM.
-#ifndef MIS_FT_ROWS
-#define MIS_FT_ROWS 64
-#endif
-constexpr int FT_COLS = 64, FT_ROWS = MIS_FT_ROWS, FG_PITCH = 96, FG_COL0 = 15, HIST_COPIES = 8;
+constexpr int FT_COLS = 64, FT_ROWS = 64, FG_PITCH = 96, FG_COL0 = 15, HIST_COPIES = 8;
 constexpr int FT_WR = (FT_ROWS + 2 + 3) / 4;          // scored rows per wave (the tile's rows + one above and below, over four waves)
 constexpr int FT_SLOTS = FT_COLS * FT_ROWS / 4;       // survivors a tile can hold: strict 3 x 3 maxima   // g: 96 columns from x0 - 16; scored column c (x = x0 - 1 + c) at g column c + FG_COL0
 #ifdef MIS_ORB_STATS
@@ -737,18 +731,16 @@ __global__ __launch_bounds__(1024) void select_rank_kernel(Levels L, const int* 
     if (t == 0) cnt2[l] = m;
 }
 
-// ---------------------------------------------------------------- K5 assembly + IC angle -----
-// One wave per keypoint: concatenates the per-level segments, evaluates the intensity centroid on
-// the un-blurred level (ICAngles), writes the cv::KeyPoint (pt scaled to level-0 coordinates).
-__global__ __launch_bounds__(256) void assemble_angle_kernel(Levels L, const uint8_t* pad, const int* cnt2, const uint32_t* fin_xy,
-                                                             const float* fin_resp, const int* umax, OrbIO io, int cap_out, size_t ws, int with_angle) {
+// ---------------------------------------------------------------- K5 assembly ----------------
+// One wave per keypoint: concatenates the per-level segments, writes the cv::KeyPoint (pt scaled to level-0 coordinates,
+// angle 0: describe_direct_kernel fills it in from the patch it stages) and publishes the frame's count.
+__global__ __launch_bounds__(256) void assemble_kernel(Levels L, const int* cnt2, const uint32_t* fin_xy, const float* fin_resp, OrbIO io, int cap_out, size_t ws) {
     // One wave per OUTPUT keypoint j (grid.x = ceil(cap_out / 4), grid.y = frame): its level is the one whose run of the output
     // holds j.  A grid of (capacity per level / 4) x levels x frames was 65 k workgroups of which three quarters found nothing to
     // do -- 0.18 ms of workgroup dispatch for 12 us of arithmetic.
     const int fr = blockIdx.y;
-    WS_OFF(pad, fr, ws); WS_OFF(cnt2, fr, ws); WS_OFF(fin_xy, fr, ws); WS_OFF(fin_resp, fr, ws);
+    WS_OFF(cnt2, fr, ws); WS_OFF(fin_xy, fr, ws); WS_OFF(fin_resp, fr, ws);
     MisKeyPoint* kps = io.kps[fr];
-    uint32_t* kp_lxy = io.lxy[fr];
     int* n_out = io.n_dev[fr];
     const int j = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     int base = 0, l = 0, total = 0;
@@ -768,55 +760,21 @@ __global__ __launch_bounds__(256) void assemble_angle_kernel(Levels L, const uin
     const int i = j - base;
     uint32_t xy = fin_xy[d.fin_off + i];
     int x = xy & 0xffff, y = xy >> 16;
-    const int pp = d.pp, hp = L.half_patch;
-    const uint8_t* ctr = pad + d.pad_off + (size_t)(y + ORB_BORDER) * pp + (x + ORB_BORDER);
-    int m01 = 0, m10 = 0;
-    const int u = lane - hp;  // lanes 0..2hp cover u = -hp..hp
-    if (with_angle && lane <= 2 * hp) {      // (describe_direct_kernel computes the angle from the patch it stages anyway)
-        m10 = u * ctr[u];
-        if (hp <= 15) {
-            // every load of the patch goes out before the first use: the row limits umax[1 .. hp] and the 2 hp pixels of the lane's
-            // column (a pixel outside the circle is read -- it lies inside the level's 32-pixel border -- and not added).  The loop
-            // below loaded umax[v], compared, then loaded two pixels, per row: hp dependent memory latencies per keypoint (10 us a wave).
-            int um[16], vp[16], vm[16];
-#pragma unroll
-            for (int v = 1; v <= 15; ++v) um[v] = umax[min(v, hp)];
-#pragma unroll
-            for (int v = 1; v <= 15; ++v) { const int vv = min(v, hp); vp[v] = ctr[u + vv * pp]; vm[v] = ctr[u - vv * pp]; }
-#pragma unroll
-            for (int v = 1; v <= 15; ++v) {
-                const bool in = v <= hp && abs(u) <= um[v];
-                m10 += in ? u * (vp[v] + vm[v]) : 0;
-                m01 += in ? v * (vp[v] - vm[v]) : 0;
-            }
-        } else {
-            for (int v = 1; v <= hp; ++v) {
-                if (abs(u) <= umax[v]) {
-                    int vp = ctr[u + v * pp], vm = ctr[u - v * pp];
-                    m10 += u * (vp + vm);
-                    m01 += v * (vp - vm);
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { m01 += __shfl_xor(m01, o); m10 += __shfl_xor(m10, o); }
     if (lane == 0) {
         MisKeyPoint kp;
         kp.x = (float)x * d.scale; kp.y = (float)y * d.scale;
         kp.size = (float)L.patch * d.scale;
-        kp.angle = with_angle ? mis_fast_atan2((float)m01, (float)m10) : 0.f;
+        kp.angle = 0.f;
         kp.response = fin_resp[d.fin_off + i];
         kp.octave = l;
         kps[base + i] = kp;
-        kp_lxy[base + i] = xy;
     }
 }
 
-// ---------------------------------------------------------------- K6 blur + rBRIEF ------------
+// debug view (mis_orb_debug_level which = 2; the detector never launches it): the blurred pyramid as the reference makes it.
 // GaussianBlur 7x7 sigma 2 (Q8 kernel 18 34 48 56 48 34 18, one rounding at bit 16) of the level
 // interior; the border ring keeps the un-blurred reflected pixels (the reference blurs the ROI of
-// the bordered pyramid in place).  64x16 output tile, separable through LDS.
+// the bordered pyramid in place).  64x32 output tile, separable through LDS.
 __global__ __launch_bounds__(256) void blur_kernel(Levels L, const uint8_t* pad, uint8_t* blur) {
     constexpr int TR = 32, TP = 80;                     // tile rows; LDS pitch (dword aligned, >= 64 + 6 + 3)
     __shared__ __attribute__((aligned(16))) uint8_t tile[(TR + 6) * TP];  // rows ty0-3 .. ty0+34, cols tx0-4 .. tx0+75
@@ -879,42 +837,20 @@ __global__ __launch_bounds__(256) void blur_kernel(Levels L, const uint8_t* pad,
     }
 }
 
-// computeOrbDescriptors, WTA_K = 2: lane b of a 32-lane half-wave builds byte b (8 tests)
-__global__ __launch_bounds__(256) void describe_kernel(Levels L, const uint8_t* blur, const MisKeyPoint* kps, const uint32_t* kp_lxy,
-                                                       const int* n_ptr, const int8_t* pattern, uint8_t* desc) {
-    const int i = blockIdx.x * 8 + (threadIdx.x >> 5), b = threadIdx.x & 31;
-    if (i >= *n_ptr) return;
-    const MisKeyPoint kp = kps[i];
-    const LevelDesc& d = L.d[kp.octave];
-    // the keypoint is already in level-0 coordinates; descriptors scale it back (1/scale) and round
-    const float inv = 1.f / d.scale;
-    const int cx = mis_round_f(kp.x * inv), cy = mis_round_f(kp.y * inv);
-    float ang = kp.angle * (float)(3.14159265358979323846 / 180.f);
-    float sa, ca;
-    mis_sincosf(ang, &sa, &ca);
-    const int pp = d.pp;
-    const uint8_t* ctr = blur + d.pad_off + (size_t)(cy + ORB_BORDER) * pp + (cx + ORB_BORDER);
-    const int8_t* pat = pattern + b * 32;  // 16 points x (x, y)
-    int val = 0;
-#pragma unroll
-    for (int bit = 0; bit < 8; bit++) {
-        float x0 = (float)pat[4 * bit], y0 = (float)pat[4 * bit + 1], x1 = (float)pat[4 * bit + 2], y1 = (float)pat[4 * bit + 3];
-        int ix0 = mis_round_f(x0 * ca - y0 * sa), iy0 = mis_round_f(x0 * sa + y0 * ca);
-        int ix1 = mis_round_f(x1 * ca - y1 * sa), iy1 = mis_round_f(x1 * sa + y1 * ca);
-        int t0 = ctr[iy0 * pp + ix0], t1 = ctr[iy1 * pp + ix1];
-        val |= (t0 < t1) << bit;
-    }
-    desc[(size_t)i * 32 + b] = (uint8_t)val;
-}
-
-// The same descriptors without blurring the pyramid: only the 512 sample points of a keypoint are ever read from the blurred
-// image, so one wave stages the keypoint's (2 (R + 3) + 1)^2 source patch in LDS and evaluates the 7 x 7 Gaussian at its samples
+// ---------------------------------------------------------------- K6 IC angle + rBRIEF --------
+// ICAngles + computeOrbDescriptors, WTA_K = 2, without blurring the pyramid: only the 512 sample points of a keypoint are ever read from the
+// blurred image, so one wave stages the keypoint's (2 (R + 3) + 1)^2 source patch in LDS and evaluates the 7 x 7 Gaussian at its samples
 // directly -- sum_j k[j] (sum_i k[i] p[y+j][x+i]), the separable filter's own integers (row sums <= 65280 fit the 16 bits
 // the two-pass form keeps) -- 25 k multiply-adds per keypoint instead of 14 per pixel of every level (84 us of blur_kernel per
 // 4K frame for 4000 keypoints' worth of samples).  R = the largest rounded pattern coordinate (28 for patchSize 40); samples
 // inside the level are blurred (their taps may reach into the reflected border ring), samples in the ring are not: the reference
 // blurs the level's ROI of the bordered pyramid only.
 constexpr int DD_R = 28, DD_P = DD_R + 3, DD_N = 2 * DD_P + 1, DD_ROW_DW = (DD_N + 3 + 3) / 4, DD_PITCH = 4 * DD_ROW_DW + 4;
+// Pattern coordinates lie in [-h, h], h = patch_size / 2 <= ORB_MAX_PATCH / 2, and |round(x cos - y sin)| <= round(|(x, y)|) <= round(sqrt(2) h):
+// the patch covers every finder that mis_orb_create accepts.  FAST keeps keypoints 3 pixels from the level's edge, so it stays inside the border ring.
+constexpr int ORB_MAX_PATCH = 40;
+static_assert(8 * (ORB_MAX_PATCH / 2) * (ORB_MAX_PATCH / 2) < (2 * DD_R + 1) * (2 * DD_R + 1), "round(sqrt(2) h) <= DD_R: every sample lies in the staged patch");
+static_assert(3 + ORB_BORDER >= DD_P, "the staged patch lies inside the padded level");
 struct UMax16 { int v[16]; };      // the disc's row limits umax[0 .. 15] by value: scalar loads from the kernel arguments
 __global__ __launch_bounds__(256) void describe_direct_kernel(Levels L, const uint8_t* pad, OrbIO io, const int8_t* pattern, const int* umax, UMax16 um16, size_t ws) {
     __shared__ __attribute__((aligned(16))) uint8_t patch[4][DD_N * DD_PITCH];
@@ -922,7 +858,6 @@ __global__ __launch_bounds__(256) void describe_direct_kernel(Levels L, const ui
     const int i = blockIdx.x * 4 + wave, fr = blockIdx.y;
     WS_OFF(pad, fr, ws);
     MisKeyPoint* kps = io.kps[fr];
-    const uint32_t* kp_lxy = io.lxy[fr];
     const int* n_ptr = io.n_dev[fr];
     uint8_t* desc = io.desc[fr];
     if (i >= *n_ptr) return;   // wave-uniform: no workgroup barrier below
@@ -1002,10 +937,7 @@ __global__ __launch_bounds__(256) void describe_direct_kernel(Levels L, const ui
         return inside ? (int)((acc + (1u << 15)) >> 16) : (int)centre;
     };
     int val = 0;
-#ifndef DD_UNROLL
-#define DD_UNROLL 1
-#endif
-#pragma unroll DD_UNROLL
+#pragma unroll 1
     for (int bit = 0; bit < 4; bit++) {
         float x0 = (float)pat[4 * bit], y0 = (float)pat[4 * bit + 1], x1 = (float)pat[4 * bit + 2], y1 = (float)pat[4 * bit + 3];
         int ix0 = mis_round_f(x0 * ca - y0 * sa), iy0 = mis_round_f(x0 * sa + y0 * ca);
@@ -1046,7 +978,6 @@ struct MisOrb {
     int cand_total = 0, fin_total = 0, tab_total = 0, surv_total = 0, out_cap = 0;
     std::vector<int> tab_host;
     int* host_counts = nullptr;   // pinned, device-visible: gather_ints_kernel writes the batch's counts / flags here
-    bool direct_describe = false;   // the pattern's reach fits describe_direct_kernel's patch: no blurred pyramid
 };
 
 namespace {
@@ -1136,37 +1067,6 @@ int upload_tables(MisOrb* o) {
     return MIS_OK;
 }
 
-std::mutex g_feat_mutex;
-std::unordered_map<void*, size_t> g_feat_sizes;  // block sizes of live feature sets (for the pool)
-
-// one device block per feature set: [size header 256 B][keypoints][descriptors][level xy][count]
-int alloc_features(MisContext* ctx, int cap, int desc_cols, int desc_dtype, MisFeatures* f) {
-    size_t kb = mis_align_up(sizeof(MisKeyPoint) * (size_t)cap, 256), db = mis_align_up((size_t)cap * desc_cols * mis_dtype_size(desc_dtype), 256);
-    size_t lb = mis_align_up(sizeof(uint32_t) * (size_t)cap, 256);
-    void* mem = nullptr;
-    size_t got = 0;
-    int rc = mis_pool_alloc(ctx, kb + db + lb + 256, &mem, &got);
-    if (rc != MIS_OK) return rc;
-    f->keypoints = (MisKeyPoint*)mem;
-    f->descriptors = (uint8_t*)mem + kb;
-    f->desc_cols = desc_cols; f->desc_dtype = desc_dtype;
-    f->owner_ = mem;
-    f->n = 0;
-    std::lock_guard<std::mutex> lock(g_feat_mutex);
-    g_feat_sizes[mem] = got;
-    return MIS_OK;
-}
-
-inline uint32_t* feat_lxy(const MisFeatures* f, int cap) {
-    size_t kb = mis_align_up(sizeof(MisKeyPoint) * (size_t)cap, 256), db = mis_align_up((size_t)cap * f->desc_cols * mis_dtype_size(f->desc_dtype), 256);
-    return (uint32_t*)((uint8_t*)f->owner_ + kb + db);
-}
-inline int* feat_count(const MisFeatures* f, int cap) {
-    size_t kb = mis_align_up(sizeof(MisKeyPoint) * (size_t)cap, 256), db = mis_align_up((size_t)cap * f->desc_cols * mis_dtype_size(f->desc_dtype), 256);
-    size_t lb = mis_align_up(sizeof(uint32_t) * (size_t)cap, 256);
-    return (int*)((uint8_t*)f->owner_ + kb + db + lb);
-}
-
 // enqueue the whole detect + describe path of a group of ng <= ORB_BATCH frames (one launch per stage); no host synchronisation
 int enqueue_detect_group(MisOrb* o, const DevView* img, int w, int h, MisFeatures* out, int ng) {
     MisContext* ctx = o->ctx;
@@ -1181,7 +1081,7 @@ int enqueue_detect_group(MisOrb* o, const DevView* img, int w, int h, MisFeature
         const int q = k < ng ? k : 0;
         io.src[k] = (const uint8_t*)img[q].data; io.sstride[k] = img[q].stride;
         io.aligned[k] = (img[q].stride % 4 == 0) && ((uintptr_t)img[q].data % 4 == 0);
-        io.kps[k] = out[q].keypoints; io.lxy[k] = feat_lxy(&out[q], o->out_cap); io.n_dev[k] = feat_count(&out[q], o->out_cap);
+        io.kps[k] = out[q].keypoints; io.n_dev[k] = mis_feat_count(&out[q], o->out_cap);
         io.desc[k] = (uint8_t*)out[q].descriptors;
     }
     // hist, thr, cnt0, cnt1, cnt2 of every frame of the group (same offset in each workspace)
@@ -1193,7 +1093,7 @@ int enqueue_detect_group(MisOrb* o, const DevView* img, int w, int h, MisFeature
         hipLaunchKernelGGL(resize_kernel, dim3((d.w + 255) / 256, (d.h + 4 * RS_ROWS - 1) / (4 * RS_ROWS), nf), dim3(256), 0, st, W.pad + s.pad_off, s.w, s.h, s.pp, W.pad + d.pad_off, d.w,
                            d.h, d.pp, W.tab + d.tab_off, ws);
     }
-    const int pw0 = d0.w + 2 * ORB_BORDER, ph0 = d0.h + 2 * ORB_BORDER;
+    const int pw0 = d0.w + 2 * ORB_BORDER;
     hipLaunchKernelGGL((border_kernel<true>), dim3((d0.h * 16 + 255) / 256, 1, L.n * nf), dim3(256), 0, st, L, W.pad, ws);   // sides first: the corners mirror them
     hipLaunchKernelGGL((border_kernel<false>), dim3((pw0 + 1023) / 1024, 2 * ORB_BORDER / 4, L.n * nf), dim3(256), 0, st, L, W.pad, ws);
     dim3 gmap((d0.w + FT_COLS - 1) / FT_COLS, (d0.h + FT_ROWS - 1) / FT_ROWS, L.n * nf);
@@ -1206,19 +1106,10 @@ int enqueue_detect_group(MisOrb* o, const DevView* img, int w, int h, MisFeature
         hipLaunchKernelGGL(harris_kernel, dim3((L.d[0].cap1 + 255) / 256, L.n, nf), dim3(256), 0, st, L, W.pad, W.cnt1, W.cand_xy, W.cand_resp, ws);
     hipLaunchKernelGGL(select_rank_kernel, dim3(L.n, nf), dim3(1024), 0, st, L, W.cnt1, W.cand_xy, W.cand_resp, W.cnt2, W.fin_xy, W.fin_resp, W.flags,
                        use_harris, ws);
-    hipLaunchKernelGGL(assemble_angle_kernel, dim3((o->out_cap + 3) / 4, nf), dim3(256), 0, st, L, W.pad, W.cnt2, W.fin_xy, W.fin_resp, W.umax, io, o->out_cap, ws, o->direct_describe ? 0 : 1);
-    if (o->direct_describe) {
-        UMax16 um16;
-        for (int v = 0; v < 16; v++) um16.v[v] = o->umax_host[v];
-        hipLaunchKernelGGL(describe_direct_kernel, dim3((o->out_cap + 3) / 4, nf), dim3(256), 0, st, L, W.pad, io, W.pattern, W.umax, um16, ws);
-    } else {
-        // patterns that reach beyond the direct kernel's patch: the blurred pyramid, frame by frame (not the default parameters)
-        for (int k = 0; k < ng; k++) {
-            hipLaunchKernelGGL(blur_kernel, dim3((pw0 + 63) / 64, (ph0 + 31) / 32, L.n), dim3(256), 0, st, L, W.pad + k * ws, W.blur + k * ws);
-            hipLaunchKernelGGL(describe_kernel, dim3((o->out_cap + 7) / 8), dim3(256), 0, st, L, W.blur + k * ws, out[k].keypoints, io.lxy[k], io.n_dev[k], W.pattern,
-                               (uint8_t*)out[k].descriptors);
-        }
-    }
+    hipLaunchKernelGGL(assemble_kernel, dim3((o->out_cap + 3) / 4, nf), dim3(256), 0, st, L, W.cnt2, W.fin_xy, W.fin_resp, io, o->out_cap, ws);
+    UMax16 um16;
+    for (int v = 0; v < 16; v++) um16.v[v] = o->umax_host[v];
+    hipLaunchKernelGGL(describe_direct_kernel, dim3((o->out_cap + 3) / 4, nf), dim3(256), 0, st, L, W.pad, io, W.pattern, W.umax, um16, ws);
     MIS_HIP(ctx, hipGetLastError());
     return MIS_OK;
 }
@@ -1247,24 +1138,22 @@ int orb_alloc_workspace(MisOrb* o, int frames) {
     MisContext* ctx = o->ctx;
     size_t off = 0;
     auto carve = [&](size_t bytes) { size_t o_ = off; off += mis_align_up(bytes, 256); return o_; };
-    // per frame: the padded gray pyramid and the small arrays; the blurred pyramid only when the descriptors need it (patterns that
-    // reach beyond describe_direct_kernel's patch).  The NMS map and, otherwise, the blurred pyramid exist ONCE behind the frames'
-    // blocks: only the debug views of the last single detect read them (16 complete workspaces were 2.2 GB at 4K)
-    const bool frame_blur = !o->direct_describe;
-    size_t o_pad = carve(o->pad_bytes), o_blur = frame_blur ? carve(o->pad_bytes) : 0;
+    // per frame: the padded gray pyramid and the small arrays.  The NMS map and the blurred pyramid exist ONCE behind the frames'
+    // blocks: only the debug views of the last single detect use them (16 complete workspaces were 2.2 GB at 4K)
+    size_t o_pad = carve(o->pad_bytes);
     size_t o_hist = carve(sizeof(int) * (256 * HIST_COPIES * ORB_MAX_LEVELS + 4 * ORB_MAX_LEVELS)), o_flags = carve(256);
     size_t o_sxy = carve(sizeof(uint32_t) * FT_SLOTS * (size_t)o->surv_total), o_ssc = carve(FT_SLOTS * (size_t)o->surv_total), o_tc = carve(sizeof(int) * (size_t)o->surv_total);
     size_t o_cxy = carve(sizeof(uint32_t) * o->cand_total), o_cr = carve(sizeof(float) * o->cand_total);
     size_t o_fxy = carve(sizeof(uint32_t) * o->fin_total), o_fr = carve(sizeof(float) * o->fin_total);
     size_t o_tab = carve(sizeof(int) * (o->tab_total + 4)), o_umax = carve(sizeof(int) * 64), o_pat = carve(1024);
-    const size_t tail = mis_align_up(o->map_bytes, 256) + (frame_blur ? 0 : mis_align_up(o->pad_bytes, 256));
+    const size_t tail = mis_align_up(o->map_bytes, 256) + mis_align_up(o->pad_bytes, 256);
     void* mem = nullptr;
     if (hipMalloc(&mem, off * (size_t)frames + tail) != hipSuccess) return mis_set_error(ctx, MIS_E_NOMEM, "hipMalloc of %zu bytes failed", off * (size_t)frames + tail);
     o->mem = mem; o->ws_stride = off; o->ws_frames = frames;
     uint8_t* m = (uint8_t*)o->mem;
     uint8_t* shared = m + off * (size_t)frames;
     Work& W = o->w;
-    W.pad = m + o_pad; W.nms = shared; W.blur = frame_blur ? m + o_blur : shared + mis_align_up(o->map_bytes, 256); W.score = nullptr;
+    W.pad = m + o_pad; W.nms = shared; W.blur = shared + mis_align_up(o->map_bytes, 256);
     W.hist = (int*)(m + o_hist); W.thr = W.hist + 256 * HIST_COPIES * ORB_MAX_LEVELS; W.cnt1 = W.thr + ORB_MAX_LEVELS; W.cnt2 = W.cnt1 + ORB_MAX_LEVELS;
     W.surv_xy = (uint32_t*)(m + o_sxy); W.surv_sc = m + o_ssc; W.tile_cnt = (int*)(m + o_tc);
     W.flags = (int*)(m + o_flags);
@@ -1308,18 +1197,31 @@ int orb_ensure_frames(MisOrb* o, int frames) {
     return orb_init_workspace(o);
 }
 
-}  // namespace
-
-// (common.h) a device block for a feature set from ctx's pool, registered so that mis_features_free recycles it: the SIFT finders' outputs
-int mis_feat_block_alloc(MisContext* ctx, size_t bytes, void** out, MisContext* errs) {
-    size_t got = 0;
-    const int rc = mis_pool_alloc(ctx, bytes, out, &got, errs);
-    if (rc != MIS_OK) return rc;
-    std::lock_guard<std::mutex> lock(g_feat_mutex);
-    g_feat_sizes[*out] = got;
+// the end of a batch: the n frames' keypoint counts into out[i].n and the workspaces' overflow flags, OR-ed, into *flags -- one
+// kernel and one synchronisation per ORB_GATHER_MAX values (a batch of up to ORB_GATHER_MAX - ORB_BATCH frames: the only synchronisation of the call)
+int gather_counts_and_flags(MisOrb* o, MisFeatures* out, int n, int* flags) {
+    MisContext* ctx = o->ctx;
+    const int total = n + o->ws_frames;
+    std::vector<int> vals(total);
+    if (!o->host_counts) MIS_HIP(ctx, hipHostMalloc((void**)&o->host_counts, sizeof(int) * ORB_GATHER_MAX, hipHostMallocMapped));
+    int* dev_view = nullptr;
+    MIS_HIP(ctx, hipHostGetDevicePointer((void**)&dev_view, o->host_counts, 0));
+    for (int i0 = 0; i0 < total; i0 += ORB_GATHER_MAX) {
+        const int m = std::min(ORB_GATHER_MAX, total - i0);
+        GatherPtrs gp;
+        for (int k = 0; k < m; k++)
+            gp.p[k] = i0 + k < n ? mis_feat_count(&out[i0 + k], o->out_cap) : (const int*)((const char*)o->w.flags + (size_t)(i0 + k - n) * o->ws_stride);
+        hipLaunchKernelGGL(gather_ints_kernel, dim3(1), dim3(ORB_GATHER_MAX), 0, ctx->stream, gp, m, dev_view);
+        MIS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        std::copy(o->host_counts, o->host_counts + m, vals.begin() + i0);
+    }
+    for (int i = 0; i < n; i++) out[i].n = vals[i];
+    *flags = 0;
+    for (int k = n; k < total; k++) *flags |= vals[k];
     return MIS_OK;
 }
 
+}  // namespace
 
 extern "C" void mis_orb_default_params(MisOrbParams* p) {
     if (p) *p = MisOrbParams{4000, 1.2f, 8, 1, 0, 2, 0, 40, 20};
@@ -1329,7 +1231,7 @@ extern "C" int mis_orb_create(MisContext* ctx, const MisOrbParams* p, int max_w,
     if (!ctx || !out) return MIS_E_INVALID;
     MIS_CHECK(ctx, p, MIS_E_INVALID, "null params");
     MIS_CHECK(ctx, p->nlevels >= 1 && p->nlevels <= ORB_MAX_LEVELS && p->first_level == 0 && p->wta_k == 2 && p->patch_size >= 2 &&
-                       p->patch_size <= 40 && p->nfeatures >= 1 && p->scale_factor > 1.f && (p->score_type == 0 || p->score_type == 1) &&
+                       p->patch_size <= ORB_MAX_PATCH && p->nfeatures >= 1 && p->scale_factor > 1.f && (p->score_type == 0 || p->score_type == 1) &&
                        p->edge_threshold >= 0 && p->fast_threshold >= 1 && p->fast_threshold < 255,
               MIS_E_UNSUPPORTED, "unsupported ORB parameters (need first_level 0, wta_k 2, patch <= 40, nlevels <= 16)");
     // patchSize 31 takes OpenCV's fixed bit_pattern_31_ table, not the random pattern this library generates
@@ -1368,15 +1270,7 @@ extern "C" int mis_orb_create(MisContext* ctx, const MisOrbParams* p, int max_w,
         int hp = p->patch_size / 2;
         for (int i = 0; i < 1024; i++) pat[i] = (int8_t)(int)(next() % (uint32_t)(2 * hp + 1) + (uint32_t)(-hp));
     }
-    {
-        int max_sq = 0;
-        for (int i = 0; i < 512; i++) max_sq = std::max(max_sq, (int)pat[2 * i] * pat[2 * i] + (int)pat[2 * i + 1] * pat[2 * i + 1]);
-        // |round(x cos - y sin)| <= round(|(x, y)|); the patch must also stay inside the padded level (border ring of ORB_BORDER)
-        const int reach = (int)floor(sqrt((double)max_sq) + 0.5);
-        // FAST keypoints keep 3 pixels from the edge, the level carries a border ring of ORB_BORDER: the patch stays inside the padded level
-        o->direct_describe = reach <= DD_R && 3 + ORB_BORDER >= DD_P;
-    }
-    int rc0 = orb_alloc_workspace(o, 1);      // (after direct_describe is known: it decides whether a frame's block carries a blurred pyramid)
+    int rc0 = orb_alloc_workspace(o, 1);
     if (rc0 != MIS_OK) { delete o; return rc0; }
     memcpy(o->umax_host, umax, sizeof(umax));
     memcpy(o->pattern_host, pat, sizeof(pat));
@@ -1421,7 +1315,7 @@ extern "C" int mis_orb_detect_batch(MisOrb* o, const MisImage* imgs, int n, MisF
     };
     for (int i = 0; i < n; i++) {
         out[i].img_idx = i; out[i].img_w = imgs[i].width; out[i].img_h = imgs[i].height;
-        if ((rc = alloc_features(ctx, o->out_cap, 32, MIS_U8, &out[i])) != MIS_OK) return fail(rc);
+        if ((rc = mis_feat_alloc(ctx, o->out_cap, 32, MIS_U8, &out[i])) != MIS_OK) return fail(rc);
         if ((rc = dimg[i].read(ctx, &imgs[i])) != MIS_OK) return fail(rc);
     }
     const bool trace = getenv("MIS_ORB_TRACE") != nullptr;
@@ -1441,27 +1335,10 @@ extern "C" int mis_orb_detect_batch(MisOrb* o, const MisImage* imgs, int n, MisF
         cb(user);
         MIS_HIP(ctx, hipSetDevice(ctx->device));
     }
-    // one synchronisation for the whole batch: counts + the workspaces' overflow flags
-    std::vector<int> counts(n);
-    const int nl = o->ws_frames;
-    std::vector<int> ws_flags(nl, 0);
-    if (!o->host_counts) MIS_HIP(ctx, hipHostMalloc((void**)&o->host_counts, sizeof(int) * ORB_GATHER_MAX, hipHostMallocMapped));
-    for (int i0 = 0; i0 < n + nl; i0 += ORB_GATHER_MAX) {
-        const int m = std::min(ORB_GATHER_MAX, n + nl - i0);
-        GatherPtrs gp;
-        for (int k = 0; k < m; k++)
-            gp.p[k] = i0 + k < n ? feat_count(&out[i0 + k], o->out_cap) : (const int*)((const char*)o->w.flags + (size_t)(i0 + k - n) * o->ws_stride);
-        int* dev_view = nullptr;
-        MIS_HIP(ctx, hipHostGetDevicePointer((void**)&dev_view, o->host_counts, 0));
-        hipLaunchKernelGGL(gather_ints_kernel, dim3(1), dim3(ORB_GATHER_MAX), 0, ctx->stream, gp, m, dev_view);
-        MIS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        for (int k = 0; k < m; k++) (i0 + k < n ? counts[i0 + k] : ws_flags[i0 + k - n]) = o->host_counts[k];
-    }
     int flags = 0;
-    for (int k = 0; k < nl; k++) flags |= ws_flags[k];
-    if (flags) hipMemset2DAsync(o->w.flags, o->ws_stride, 0, sizeof(int), (size_t)nl, ctx->stream);
-    for (int i = 0; i < n; i++) out[i].n = counts[i];
+    if ((rc = gather_counts_and_flags(o, out, n, &flags)) != MIS_OK) return rc;
     if (flags) {
+        hipMemset2DAsync(o->w.flags, o->ws_stride, 0, sizeof(int), (size_t)o->ws_frames, ctx->stream);
         return mis_set_error(ctx, MIS_E_OVERFLOW, "ORB candidate buffers overflowed (flags %d): too many tied scores", flags);
     }
     return MIS_OK;
@@ -1472,56 +1349,6 @@ extern "C" int mis_orb_detect(MisOrb* o, const MisImage* bgr, MisFeatures* out) 
 extern "C" int mis_orb_on_enqueued(MisOrb* o, void (*fn)(void*), void* user) {
     if (!o) return MIS_E_INVALID;
     o->enqueued_cb = fn; o->enqueued_user = user;
-    return MIS_OK;
-}
-
-extern "C" int mis_features_download(MisContext* ctx, const MisFeatures* f, MisKeyPoint* kps, void* desc) {
-    if (!ctx || !f) return MIS_E_INVALID;
-    MIS_HIP(ctx, hipSetDevice(ctx->device));
-    if (f->n > 0) {
-        if (kps) MIS_HIP(ctx, hipMemcpyAsync(kps, f->keypoints, sizeof(MisKeyPoint) * (size_t)f->n, hipMemcpyDeviceToHost, ctx->stream));
-        if (desc) MIS_HIP(ctx, hipMemcpyAsync(desc, f->descriptors, (size_t)f->n * f->desc_cols * mis_dtype_size(f->desc_dtype), hipMemcpyDeviceToHost, ctx->stream));
-    }
-    MIS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return MIS_OK;
-}
-
-extern "C" int mis_features_upload(MisContext* ctx, int img_w, int img_h, int n, const MisKeyPoint* kps, const void* desc, int desc_cols,
-                                   int desc_dtype, MisFeatures* out) {
-    if (!ctx || !out) return MIS_E_INVALID;
-    MIS_CHECK(ctx, n >= 0 && (n == 0 || (kps && desc)) && desc_cols > 0 && (desc_dtype == MIS_U8 || desc_dtype == MIS_F32), MIS_E_INVALID,
-              "bad feature arrays");
-    MIS_HIP(ctx, hipSetDevice(ctx->device));
-    memset(out, 0, sizeof(*out));
-    out->img_w = img_w; out->img_h = img_h;
-    int rc = alloc_features(ctx, std::max(n, 1), desc_cols, desc_dtype, out);
-    if (rc != MIS_OK) return rc;
-    if (n) {
-        MIS_HIP(ctx, hipMemcpyAsync(out->keypoints, kps, sizeof(MisKeyPoint) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-        MIS_HIP(ctx, hipMemcpyAsync(out->descriptors, desc, (size_t)n * desc_cols * mis_dtype_size(desc_dtype), hipMemcpyHostToDevice, ctx->stream));
-        MIS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    out->n = n;
-    return MIS_OK;
-}
-
-extern "C" int mis_features_free(MisContext* ctx, MisFeatures* f) {
-    if (!ctx || !f) return MIS_E_INVALID;
-    if (f->owner_) {
-        size_t bytes = 0;
-        {
-            std::lock_guard<std::mutex> lock(g_feat_mutex);
-            auto it = g_feat_sizes.find(f->owner_);
-            if (it != g_feat_sizes.end()) { bytes = it->second; g_feat_sizes.erase(it); }
-        }
-        if (bytes) mis_pool_free(ctx, f->owner_, bytes);  // recycled without synchronising the device
-        else {
-            MIS_HIP(ctx, hipSetDevice(ctx->device));
-            MIS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            MIS_HIP(ctx, hipFree(f->owner_));
-        }
-    }
-    f->owner_ = nullptr; f->keypoints = nullptr; f->descriptors = nullptr; f->n = 0;
     return MIS_OK;
 }
 
@@ -1544,10 +1371,9 @@ extern "C" int mis_orb_debug_level(MisOrb* o, int level, int which, uint8_t* hos
         src = o->w.nms + d.map_off; pitch = d.sp;
     }
     else {
-        if (o->direct_describe) {   // the detector no longer blurs the pyramid (describe_direct_kernel): this view computes it on demand
-            const int pw0 = o->L.d[0].w + 2 * ORB_BORDER, ph0 = o->L.d[0].h + 2 * ORB_BORDER;
-            hipLaunchKernelGGL(blur_kernel, dim3((pw0 + 63) / 64, (ph0 + 31) / 32, o->L.n), dim3(256), 0, ctx->stream, o->L, o->w.pad, o->w.blur);
-        }
+        // the detector blurs no pyramid (describe_direct_kernel): this view computes the first frame's on demand
+        const int pw0 = o->L.d[0].w + 2 * ORB_BORDER, ph0 = o->L.d[0].h + 2 * ORB_BORDER;
+        hipLaunchKernelGGL(blur_kernel, dim3((pw0 + 63) / 64, (ph0 + 31) / 32, o->L.n), dim3(256), 0, ctx->stream, o->L, o->w.pad, o->w.blur);
         src = o->w.blur + d.pad_off; pitch = d.pp;
     }
     MIS_HIP(ctx, hipMemcpy2DAsync(host_out, w, src, pitch, w, h, hipMemcpyDeviceToHost, ctx->stream));

@@ -2,9 +2,10 @@
 the NMS map and the blurred level of every pyramid level exactly, then the keypoints as sets per level, their canonical order,
 the angles within the reference's band and every determined descriptor bit.
 
-Every accepted patch size (2 .. 40) takes describe_direct_kernel: its pattern reaches at most round(20 sqrt 2) = 28 <= DD_R, so
-the blur_kernel + describe_kernel fallback is not reachable through mis_orb_create; blur_kernel runs here through the debug
-view of the blurred level."""
+describe_direct_kernel is the only descriptor path: the pattern of every accepted patch size (2 .. 40) reaches at most
+round(20 sqrt 2) = 28 = DD_R, which orb.hip asserts at compile time.  It computes the angle and blurs at the sample points of
+the patch it stages; no blurred pyramid is built.  blur_kernel exists for the debug view of the blurred level only and runs
+here through it."""
 import numpy as np
 import pytest
 
@@ -77,6 +78,27 @@ def test_detect_batch_of_three_frames(ctx):
         k, d, ref = check_gpu(finder, f, kw, "batch frame %d" % i, stages=False)
         assert np.array_equal(bk, k) and np.array_equal(bd, d)
         assert not ro.compare_features(bk, bd, ref)["errors"]
+
+
+def test_detect_batch_of_more_frames_than_a_group(ctx):
+    """17 frames in one batch: a full group of ORB_BATCH = 16 workspaces and a second group of one, the counts and the overflow
+    flags of 17 + 16 places gathered at the end.  Each result equals its single detect bit for bit; the first frame and the last
+    (the second group's) equal the reference."""
+    import torch
+    w, h = 97, 71
+    makers = [lambda s: synth_frame(w, h, 5.0 + 3.0 * s), lambda s: uniform_noise(w, h, 20 + s), lambda s: binary_noise(w, h, 40 + s)]
+    frames = [makers[i % 3](i) for i in range(17)]
+    kw = dict(nfeatures=300, nlevels=4)
+    finder = _finder(ctx, (w, h), kw)
+    imgs = [torch.from_numpy(f).cuda() for f in frames]
+    batch = [f.download() for f in finder.detect_batch(imgs)]
+    assert len(batch) == 17
+    for i, (img, (bk, bd)) in enumerate(zip(imgs, batch)):
+        if i in (0, 16):
+            k, d, _ = check_gpu(finder, frames[i], kw, "batch of 17, frame %d" % i, img=img)
+        else:
+            k, d = finder.detect(img).download()
+        assert np.array_equal(bk, k) and np.array_equal(bd, d), i
 
 
 def test_strided_unaligned_bgr_view(ctx):

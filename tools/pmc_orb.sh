@@ -6,4 +6,4 @@ run() { n=$1; shift; rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d 
 run inst SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAVE_CYCLES SQ_BUSY_CYCLES
 run wait SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAVE_CYCLES SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE
 cd $R
-python3 tools/pmc_summary.py gpurun_out/pmco_inst gpurun_out/pmco_wait -k=fast_nms -k=select_rank -k=assemble_angle -k=describe_direct -k=resize_kernel -k=gray_kernel -k=compact_kernel
+python3 tools/pmc_summary.py */pmco_inst */pmco_wait -k=fast_nms -k=select_rank -k=assemble_kernel -k=describe_direct -k=resize_kernel -k=gray_kernel -k=compact_kernel
