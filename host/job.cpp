@@ -29,6 +29,7 @@ JobOutput StitchJob::run(const std::vector<MisImage>& frames) {
     const MisImage* work = work_frames(frames);       // (:602, one launch on the main stream)
     prep_.arm([this] { if (spec_ok_) prepare(everyone_); });
     check(ctx_, mis_orb_on_enqueued(orb_, &Hook::fire, &prep_), "mis_orb_on_enqueued");
+    arm_knn_ahead();        // the matcher below takes this batch as it is: its 2-NN pass goes in behind the batch
     // ---- features (:567-622) ----
     std::vector<MisFeatures> feats(n_);
     std::memset(feats.data(), 0, sizeof(MisFeatures) * n_);

@@ -145,6 +145,10 @@ void JobCore::fence_knn() {
     if (rc < 0) check(ctx_, rc, "mis_match_knn_fence");
 }
 
+void JobCore::arm_knn_ahead() {
+    check(ctx_, mis_orb_arm_knn_ahead(orb_, n_, nullptr, cfg_.range_width, 0, 1), "mis_orb_arm_knn_ahead");
+}
+
 void JobCore::compose(const std::vector<MisImage>& frames, const std::vector<int>& frame_ids, const std::vector<int>& idx) {
     std::vector<MisImage> fr;
     std::vector<float> Ks, Rs;

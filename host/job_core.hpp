@@ -56,6 +56,9 @@ protected:
     Compose prepare(const std::vector<int>& idx);
     // the compose stream queued behind the 2-NN pass of the matcher call in flight (from the matcher's hook)
     void fence_knn();
+    // a job that matches its finder's own output next, on one rank: the next feature batch (of all n frames) enqueues the matcher's
+    // 2-NN pass behind its kernels (mis_orb_arm_knn_ahead); the matcher call adopts it
+    void arm_knn_ahead();
     // the frames at work scale (:589-603): resized in one launch into images the core keeps from its first run on (allocated by the
     // library then; an allocation per run would synchronise the device); the frames themselves when the work scale is 1
     const MisImage* work_frames(const std::vector<MisImage>& frames);

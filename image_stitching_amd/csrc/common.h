@@ -55,6 +55,17 @@ struct MisFeatLayout { size_t desc_off, count_off, bytes; };
 MisFeatLayout mis_feat_layout(int cap, int desc_cols, int desc_dtype);
 int mis_feat_alloc(MisContext* ctx, int cap, int desc_cols, int desc_dtype, MisFeatures* f);
 int* mis_feat_count(const MisFeatures* f, int cap);
+// The Hamming 2-NN pass enqueued ahead of the matcher call (match.hip).  mis_knn_ahead_enqueue: the expansion and the 2-NN pass
+// of the selected pairs (mask / range_width / rank / world as in mis_match_pairs_select) of a batch of n feature blocks whose
+// keypoint counts are still on the device only -- block i holds at most caps[i] features and its finder publishes the count at
+// counts[i] (device) --, on ctx's stream, planned from the capacities; it does nothing where the pass on the matrix cores does
+// not apply.  mis_knn_ahead_confirm: the batch now has its counts on the host (feats[i].n): the next matcher call of ctx may
+// adopt the pass.  mis_knn_ahead_drop: nobody will (owner != NULL: only if that block belongs to the pass).  Not adopting a
+// pass is always correct: its results are read by no one.
+int mis_knn_ahead_enqueue(MisContext* ctx, const MisFeatures* feats, int n, const int* caps, int* const* counts, const uint8_t* mask, int range_width,
+                          int rank, int world);
+void mis_knn_ahead_confirm(MisContext* ctx, const MisFeatures* feats, int n);
+void mis_knn_ahead_drop(MisContext* ctx, const void* owner);
 
 #define MIS_HIP(ctx, call)                                                                             \
     do {                                                                                               \

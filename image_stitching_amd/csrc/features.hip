@@ -82,6 +82,7 @@ extern "C" int mis_features_upload(MisContext* ctx, int img_w, int img_h, int n,
 extern "C" int mis_features_free(MisContext* ctx, MisFeatures* f) {
     if (!ctx || !f) return MIS_E_INVALID;
     if (f->owner_) {
+        mis_knn_ahead_drop(ctx, f->owner_);      // (the block may come back from the pool for another feature set)
         size_t bytes = 0;
         {
             std::lock_guard<std::mutex> lock(g_feat_mutex);

@@ -25,12 +25,9 @@ struct FeatDev {
     int n, w, h;
 };
 
-struct PairDesc {
-    int i, j;            // image indices, i < j
-    size_t knn_off12, knn_off21;  // offsets (in queries) into idx2 / dist2
-    size_t m_off;        // offset into the per-pair match / point / mask arrays
-    int cap;             // n_i + n_j
-};
+// PairDesc, HmFrame, HmJob, HM_ROWPAD, HM_MAX_TRAINS and the host-side planning of the 2-NN pass (in this namespace: the kernels'
+// symbols carry it)
+#include "knn_plan.h"
 
 // ---------------------------------------------------------------- K7: exact 2-NN, Hamming-256 --
 constexpr int KNN_TILE = 256;
@@ -103,19 +100,10 @@ __global__ __launch_bounds__(256) void knn2_hamming_kernel(const FeatDev* feats,
 // a lane's two running keys per query set cover half of the trains, the halves are merged at the end.
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
-constexpr int HM_ROWPAD = 256;         // expanded blocks are padded with zero rows to a multiple of this
-constexpr int HM_MAX_TRAINS = 8192;
 constexpr int HM_NONE = 0x7f000000;
 
-struct HmFrame { size_t train_off, query_off; };   // byte offsets of a frame's two expanded forms
-
 struct HmKeys { int k0[2], k1[2]; };
-// One workgroup of the pass: 256 queries of a directed pair against all trains.  The table is ordered so that workgroup L runs on
-// XCD L mod 8 (the dispatcher deals workgroups round-robin over the eight XCDs) and every XCD only ever sees the TRAIN sets of
-// the frames t with t mod 8 = its number: two frames of a 16-frame job, 2 MB of expanded descriptors, resident in its 4 MB L2
-// (with the (query block, pair) grid every XCD walked all 16 MB and every tile was a miss to the fabric: the tile loads' latency,
-// not the matrix pipe, paced the loop).
-struct HmJob { int pair, dir, q0, pad; };
+// (HmJob, one workgroup of the pass, and the XCD-ordered table of them: knn_plan.h)
 // The keys carry HM_FBIAS = the bits of 1.0f: bit patterns of positive normal floats order like the integers they are, and
 // v_min_f32 / v_med3_f32 issue at the full vector rate where v_min_i32 / v_med3_i32 take two issue slots (tools/valu_rate.hip) --
 // 64 of them per tile and wave were 512 of the 700 vector-issue cycles against 512 cycles of matrix work (rocprofv3: the
@@ -162,6 +150,19 @@ __global__ __launch_bounds__(256) void hamming_expand4_kernel(const FeatDev* fea
     }
     *reinterpret_cast<uint4*>(out + fr[blockIdx.y].train_off + (size_t)d * 128 + 16 * w) = make_uint4(tq[0], tq[1], tq[2], tq[3]);
     *reinterpret_cast<uint4*>(out + fr[blockIdx.y].query_off + (size_t)d * 128 + 16 * w) = make_uint4(qq[0], qq[1], qq[2], qq[3]);
+}
+// The FeatDev table of a pass that is enqueued while only the device knows the keypoint counts (mis_knn_ahead_enqueue): frame i's
+// count is the int its finder publishes at count[i], within its block's capacity; the blocks' pointers come as arguments.
+constexpr int AHEAD_MAX_FRAMES = 64;
+struct AheadFrames {
+    const uint8_t* desc[AHEAD_MAX_FRAMES];
+    const MisKeyPoint* kps[AHEAD_MAX_FRAMES];
+    const int* count[AHEAD_MAX_FRAMES];
+    int cap[AHEAD_MAX_FRAMES], w[AHEAD_MAX_FRAMES], h[AHEAD_MAX_FRAMES];
+};
+__global__ void feat_counts_kernel(FeatDev* feats, AheadFrames f, int n) {
+    const int i = threadIdx.x;
+    if (i < n) feats[i] = FeatDev{f.desc[i], f.kps[i], min(max(*f.count[i], 0), f.cap[i]), f.w[i], f.h[i]};
 }
 #define HM4_MFMA_FIRST(D, A, B, C, SA, SB) \
     asm volatile("v_mfma_scale_f32_32x32x64_f8f6f4 %0, %1, %2, %3, %4, %5 op_sel_hi:[0,0,0] cbsz:4 blgp:4" : "=&v"(D) : "v"(A), "v"(B), "v"(C), "v"(SA), "v"(SB))
@@ -741,9 +742,36 @@ struct MatchWorkspace : MisWorkspace {
     OwnedEvent ev_lists;                                 // the early download of the match lists has landed
     void (*enqueued_cb)(void*) = nullptr;                // mis_match_on_enqueued: one-shot hook of the next call
     void* enqueued_user = nullptr;
+    // The previous call's final synchronisation has run: nothing of it still reads the arenas.  Clear while a call is in flight
+    // and after one that returned early without synchronising; the next call then synchronises first.
+    bool drained = true;
+    // The expansion and the 2-NN pass of a feature batch, enqueued behind the batch's own kernels while its keypoint counts were
+    // on the device only (mis_knn_ahead_enqueue), for the next matcher call to adopt.  `valid` once the batch has confirmed its
+    // host counts (mis_knn_ahead_confirm); one-shot: the next matcher call adopts the pass or drops it.  Storage of its own --
+    // a call that does not adopt the pass may re-reserve dev / pinned / l2 while these kernels still run.
+    struct Ahead {
+        bool enqueued = false, valid = false;
+        std::vector<const void*> desc, owner;            // the batch: descriptor and block pointers, in order
+        std::vector<int> caps, counts;                   // the blocks' capacities; the host counts of the batch
+        std::vector<uint8_t> mask;                       // the selection: n x n, its strict upper triangle as 0 / 1 (empty: no mask)
+        bool has_mask = false;
+        int range_width = -1;
+        KnnCapPlan plan;
+        bool tables_ready = false;                       // the plan of (caps, mask, range_width) is made and its tables are on the device
+        Arena dev, pinned;                               // [expanded forms][pairs, frames, jobs][FeatDev][idx][dist]; the tables on their way up
+        OwnedEvent ev_tables;                            // the tables' copy has left `pinned`
+        PairDesc* d_pairs = nullptr;
+        HmFrame* d_frames = nullptr;
+        HmJob* d_jobs = nullptr;
+        FeatDev* d_feats = nullptr;
+        int* idx = nullptr;
+        float* dist = nullptr;
+        Ahead() { pinned.host = true; }
+    } ahead;
+    long long ahead_adopted = 0;                         // matcher calls that adopted a pass (mis_debug_knn_ahead_adopted)
     MatchWorkspace() { pinned.host = true; }
     ~MatchWorkspace() override {
-        dev.release(); pinned.release(); l2.release();
+        dev.release(); pinned.release(); l2.release(); ahead.dev.release(); ahead.pinned.release();
         homo_batch_release(&b1); homo_batch_release(&b2); homo_batch_release(&b3);
         // side / third are the context's auxiliary streams: not owned here
     }
@@ -833,8 +861,7 @@ int plan_match(MisContext* ctx, const MisFeatures* feats, int n, const uint8_t* 
     for (int i = 0; i < n; i++)
         for (int j = i + 1; j < n; j++) {
             if (feats[i].n <= 0 || feats[j].n <= 0) continue;
-            if (mask && !mask[(size_t)i * n + j]) continue;
-            if (range_width != -1 && j >= i + range_width) continue;
+            if (!knn_pair_selected(i, j, n, mask, range_width)) continue;
             if ((pair_index++ % world) != rank) continue;
             const int cap = feats[i].n + feats[j].n;
             pl->maxq = std::max(pl->maxq, std::max(feats[i].n, feats[j].n));
@@ -854,19 +881,9 @@ int plan_match(MisContext* ctx, const MisFeatures* feats, int n, const uint8_t* 
     if (np == 0) return MIS_OK;
     // workgroup table of the Hamming pass on the matrix cores (HmJob): eight lists by train frame mod 8, interleaved
     if (pl->kind == DESC_BINARY && pl->maxq <= HM_MAX_TRAINS) {
-        std::vector<HmJob> lists[8];
-        for (int t = 0; t < n; t++)
-            for (int k = 0; k < np; k++) {
-                const int dir = pairs[k].j == t ? 0 : (pairs[k].i == t ? 1 : -1);      // direction 0: queries of i against the trains of j
-                if (dir < 0) continue;
-                const int nqf = feats[dir == 0 ? pairs[k].i : pairs[k].j].n;
-                for (int q0 = 0; q0 < nqf; q0 += 256) lists[t & 7].push_back(HmJob{k, dir, q0, 0});
-            }
-        size_t longest = 0;
-        for (auto& l : lists) longest = std::max(longest, l.size());
-        pl->hm_jobs.assign(longest * 8, HmJob{-1, 0, 0, 0});
-        for (int c = 0; c < 8; c++)
-            for (size_t sl = 0; sl < lists[c].size(); sl++) pl->hm_jobs[sl * 8 + c] = lists[c][sl];
+        std::vector<int> nq(n);
+        for (int i = 0; i < n; i++) nq[i] = feats[i].n;
+        hm_job_table(pairs, n, nq.data(), &pl->hm_jobs);
     }
     return MIS_OK;
 }
@@ -1051,6 +1068,7 @@ int assemble_matches(MisContext* ctx, MatchWorkspace* ws, const MatchPlan& pl, c
         for (int q = 0; q < nm; q++) { b->matches[q] = a->matches[q]; std::swap(b->matches[q].query_idx, b->matches[q].train_idx); }
     }
     const hipError_t e = hipStreamSynchronize(ctx->stream);
+    ws->drained = e == hipSuccess;       // (the next call need not wait for this one)
     *ts = std::chrono::steady_clock::now();
     if (e != hipSuccess || *h.l2_bad) {
         drop_lists();
@@ -1128,8 +1146,27 @@ void trace_report(MatchWorkspace* ws, std::chrono::steady_clock::time_point t_be
             ms(1), ms(6), ms(2), ms(3), ms(4), ms(5));
 }
 
+// Whether the pass enqueued ahead is this call's: the armed batch itself (the same blocks in the same order, with the counts the
+// batch returned), the same selection, and counts that the Hamming pass on the matrix cores takes.  Anything else: not adopted.
+bool ahead_is_for(const MatchWorkspace::Ahead& A, const MisFeatures* feats, int n, const uint8_t* mask, int range_width, int rank, int world) {
+    if (world != 1 || rank != 0 || n != (int)A.desc.size() || range_width != A.range_width || (mask != nullptr) != A.has_mask) return false;
+    for (int i = 0; i < n; i++) {
+        const MisFeatures& f = feats[i];
+        if (f.descriptors != A.desc[i] || f.owner_ != A.owner[i] || f.desc_dtype != MIS_U8 || f.desc_cols != 32) return false;
+        if (f.n != A.counts[i] || f.n <= 0 || f.n > HM_MAX_TRAINS || f.n > A.caps[i]) return false;
+    }
+    for (int i = 0; mask && i < n; i++)
+        for (int j = i + 1; j < n; j++)
+            if ((mask[(size_t)i * n + j] != 0) != (A.mask[(size_t)i * n + j] != 0)) return false;
+    return true;
+}
+
 int match_impl(MisContext* ctx, const MisFeatures* feats, int n, const MisMatchParams* p, int model, const uint8_t* mask, int range_width, int rank, int world,
                MisMatchesInfo* out) {
+    // a pass enqueued ahead is this call's to adopt, or nobody's
+    MatchWorkspace::Ahead& ahead = workspace(ctx)->ahead;
+    const bool ahead_pending = ahead.valid;
+    ahead.valid = ahead.enqueued = false;
     MIS_CHECK(ctx, feats && p && out && n >= 1, MIS_E_INVALID, "null argument");
     MIS_CHECK(ctx, model == MIS_MATCH_HOMOGRAPHY || model == MIS_MATCH_AFFINE_PARTIAL, MIS_E_UNSUPPORTED, "unknown matcher model %d (MIS_MATCH_HOMOGRAPHY, MIS_MATCH_AFFINE_PARTIAL)", model);
     MIS_CHECK(ctx, world >= 1 && rank >= 0 && rank < world, MIS_E_INVALID, "bad rank / world size");
@@ -1148,20 +1185,34 @@ int match_impl(MisContext* ctx, const MisFeatures* feats, int n, const MisMatchP
     if ((rc = plan_match(ctx, feats, n, mask, range_width, rank, world, &pl)) != MIS_OK) return rc;
     const int np = (int)pl.pairs.size();
     if (np == 0) return MIS_OK;
+    // (with every count > 0 the call's pairs are the ahead plan's, in its order: checked all the same)
+    bool adopt = ahead_pending && ahead_is_for(ahead, feats, n, mask, range_width, rank, world) && pl.kind == DESC_BINARY && ahead.plan.pairs.size() == pl.pairs.size();
+    for (int k = 0; adopt && k < np; k++) adopt = pl.pairs[k].i == ahead.plan.pairs[k].i && pl.pairs[k].j == ahead.plan.pairs[k].j;
     MatchWorkspace* ws = workspace(ctx);
     hipStream_t st = ctx->stream;
-    MIS_HIP(ctx, hipStreamSynchronize(st));  // the arenas may still be read by a previous call's copies
+    // The arenas may still be read by a previous call's copies -- only when that call left without its final synchronisation.
+    // (Unconditionally, this wait parked the host behind a 2-NN pass enqueued ahead, and the chains were enqueued late.)
+    if (!ws->drained) MIS_HIP(ctx, hipStreamSynchronize(st));
+    ws->drained = false;
     MatchDev d; MatchPinned h;
     if ((rc = carve_dev(ctx, ws->dev, pl, &d)) != MIS_OK) return rc;
     for (HomoBatch* b : {&ws->b1, &ws->b2, &ws->b3})
         if ((rc = homo_batch_reserve(ctx, b, np, (long long)pl.m_total, p->max_iters)) != MIS_OK) return rc;
     if ((rc = carve_pinned(ctx, ws->pinned, pl, &h)) != MIS_OK) return rc;
+    if (adopt) {
+        // the pass ran from the capacity plan: its slots in its own idx / dist; m_off / cap stay this call's
+        for (int k = 0; k < np; k++) { pl.pairs[k].knn_off12 = ahead.plan.pairs[k].knn_off12; pl.pairs[k].knn_off21 = ahead.plan.pairs[k].knn_off21; }
+        d.idx = ahead.idx; d.dist = ahead.dist;
+        ws->ahead_adopted++;
+    }
     memcpy(h.feats, pl.fd.data(), sizeof(FeatDev) * n);
     memcpy(h.pairs, pl.pairs.data(), sizeof(PairDesc) * np);
-    MIS_HIP(ctx, hipMemcpyAsync(d.feats, h.feats, sizeof(FeatDev) * n, hipMemcpyHostToDevice, st));
-    MIS_HIP(ctx, hipMemcpyAsync(d.pairs, h.pairs, sizeof(PairDesc) * np, hipMemcpyHostToDevice, st));
+    // frames and pairs in one copy: both arenas begin with these two regions, laid out by the same Carver steps (behind an
+    // adopted pass's kernels in stream order, which read tables of their own)
+    MIS_CHECK(ctx, (uint8_t*)h.pairs - (uint8_t*)h.feats == (uint8_t*)d.pairs - (uint8_t*)d.feats, MIS_E_STATE, "matcher arenas: the input regions differ");
+    MIS_HIP(ctx, hipMemcpyAsync(d.feats, h.feats, (size_t)((uint8_t*)(h.pairs + np) - (uint8_t*)h.feats), hipMemcpyHostToDevice, st));
     *h.l2_bad = 0;
-    if ((rc = enqueue_knn(ctx, ws, pl, feats, d, h)) != MIS_OK) return rc;
+    if (!adopt && (rc = enqueue_knn(ctx, ws, pl, feats, d, h)) != MIS_OK) return rc;
     MIS_HIP(ctx, ws->events_ready());
     // the 2-NN pass fills the device on its own; what follows are latency-bound chains.  Work that wants to share the
     // device with the matcher (the job's speculative composition) can queue behind this event: mis_match_knn_fence
@@ -1176,7 +1227,7 @@ int match_impl(MisContext* ctx, const MisFeatures* feats, int n, const MisMatchP
     if ((rc = enqueue_chains(ctx, ws, np, p, model, d, h)) != MIS_OK) {
         if (ws->side) hipStreamSynchronize(ws->side);
         if (ws->third) hipStreamSynchronize(ws->third);
-        hipStreamSynchronize(st);
+        ws->drained = hipStreamSynchronize(st) == hipSuccess;
         return rc;
     }
     MIS_HIP(ctx, hipGetLastError());
@@ -1201,6 +1252,108 @@ int match_impl(MisContext* ctx, const MisFeatures* feats, int n, const MisMatchP
 }
 
 }  // namespace
+
+// The expansion and the Hamming 2-NN pass of a feature batch whose keypoint counts are still on the device only, enqueued on the
+// context's stream behind whatever fills the blocks (common.h).  Everything the host would take from the counts -- the directed
+// pairs' slots, the expanded blocks, the workgroup table -- is planned from the blocks' capacities (plan_knn_capacity); the kernels
+// take the counts from a FeatDev table that feat_counts_kernel fills on the device.  Capacities and selection are a job's constants:
+// the plan is made, and its tables uploaded (one copy from one pinned block), when they change, not per batch -- a batch costs
+// three launches, its blocks' pointers travel as feat_counts_kernel's arguments.  Nothing is enqueued, and MIS_OK returned, unless
+// world == 1, there are at most AHEAD_MAX_FRAMES blocks and each holds 32-byte binary descriptors with a capacity of 1 .. HM_MAX_TRAINS.
+int mis_knn_ahead_enqueue(MisContext* ctx, const MisFeatures* feats, int n, const int* caps, int* const* counts, const uint8_t* mask, int range_width,
+                          int rank, int world) {
+    MatchWorkspace* ws = workspace(ctx);
+    MatchWorkspace::Ahead& A = ws->ahead;
+    A.valid = A.enqueued = false;
+    if (!feats || !caps || !counts || n < 2 || n > AHEAD_MAX_FRAMES || world != 1 || rank != 0 || !(range_width == -1 || range_width >= 1)) return MIS_OK;
+    int maxcap = 0;
+    for (int i = 0; i < n; i++) {
+        if (feats[i].desc_dtype != MIS_U8 || feats[i].desc_cols != 32 || caps[i] < 1 || caps[i] > HM_MAX_TRAINS || !counts[i]) return MIS_OK;
+        maxcap = std::max(maxcap, caps[i]);
+    }
+    hipStream_t st = ctx->stream;
+    // the strict upper triangle of the mask as 0 / 1: what the selection reads
+    std::vector<uint8_t> sel;
+    if (mask) {
+        sel.assign((size_t)n * n, 0);
+        for (int i = 0; i < n; i++)
+            for (int j = i + 1; j < n; j++) sel[(size_t)i * n + j] = mask[(size_t)i * n + j] != 0;
+    }
+    const bool same_plan = A.tables_ready && (int)A.caps.size() == n && std::equal(caps, caps + n, A.caps.begin()) && A.has_mask == (mask != nullptr) &&
+                           A.mask == sel && A.range_width == range_width;
+    if (!same_plan) {
+        A.tables_ready = false;
+        plan_knn_capacity(n, caps, mask, range_width, rank, world, &A.plan);
+        const KnnCapPlan& P = A.plan;
+        const size_t np = P.pairs.size(), nj = P.jobs.size();
+        A.caps.assign(caps, caps + n);
+        A.has_mask = mask != nullptr;
+        A.mask = sel;
+        A.range_width = range_width;
+        if (np > 0) {
+            Carver c;
+            c.off = P.xp_bytes;                  // the expanded forms come first: HmFrame offsets are from the arena's start
+            const size_t o_tab = c.off, o_pairs = c.take(sizeof(PairDesc) * np), o_fr = c.take(sizeof(HmFrame) * n), o_jobs = c.take(sizeof(HmJob) * nj),
+                         tab_bytes = c.off - o_tab, o_feats = c.take(sizeof(FeatDev) * n), o_idx = c.take(sizeof(int) * 2 * P.knn_total),
+                         o_dist = c.take(sizeof(float) * 2 * P.knn_total);
+            // (an earlier plan's tables may still be leaving the pinned block)
+            if (A.ev_tables.ev) MIS_HIP(ctx, hipEventSynchronize(A.ev_tables.ev));
+            MIS_HIP(ctx, A.ev_tables.ready());
+            MIS_HIP(ctx, A.dev.reserve(c.off));
+            MIS_HIP(ctx, A.pinned.reserve(tab_bytes));
+            uint8_t *D = (uint8_t*)A.dev.p, *T = (uint8_t*)A.pinned.p;      // the pinned block mirrors the tables' region
+            memcpy(T + (o_pairs - o_tab), P.pairs.data(), sizeof(PairDesc) * np);
+            memcpy(T + (o_fr - o_tab), P.frames.data(), sizeof(HmFrame) * n);
+            memcpy(T + (o_jobs - o_tab), P.jobs.data(), sizeof(HmJob) * nj);
+            MIS_HIP(ctx, hipMemcpyAsync(D + o_tab, T, tab_bytes, hipMemcpyHostToDevice, st));
+            MIS_HIP(ctx, hipEventRecord(A.ev_tables.ev, st));
+            A.d_pairs = (PairDesc*)(D + o_pairs); A.d_frames = (HmFrame*)(D + o_fr); A.d_jobs = (HmJob*)(D + o_jobs); A.d_feats = (FeatDev*)(D + o_feats);
+            A.idx = (int*)(D + o_idx); A.dist = (float*)(D + o_dist);
+        }
+        A.tables_ready = true;
+    }
+    if (A.plan.pairs.empty()) return MIS_OK;
+    AheadFrames fr;
+    for (int i = 0; i < n; i++) {
+        fr.desc[i] = (const uint8_t*)feats[i].descriptors; fr.kps[i] = feats[i].keypoints; fr.count[i] = counts[i];
+        fr.cap[i] = caps[i]; fr.w[i] = feats[i].img_w; fr.h[i] = feats[i].img_h;
+    }
+    hipLaunchKernelGGL(feat_counts_kernel, dim3(1), dim3(AHEAD_MAX_FRAMES), 0, st, A.d_feats, fr, n);
+    const int maxpad = (int)knn_rows_padded(maxcap);
+    hipLaunchKernelGGL(hamming_expand4_kernel, dim3(maxpad * 8 / 256, n), dim3(256), 0, st, (const FeatDev*)A.d_feats, (const HmFrame*)A.d_frames, (int8_t*)A.dev.p);
+    hipLaunchKernelGGL(knn2_hamming_fp4_kernel, dim3((unsigned)A.plan.jobs.size()), dim3(256), 0, st, (const FeatDev*)A.d_feats, (const PairDesc*)A.d_pairs,
+                       (const HmFrame*)A.d_frames, (const int8_t*)A.dev.p, A.idx, A.dist, (const HmJob*)A.d_jobs);
+    MIS_HIP(ctx, hipGetLastError());
+    A.desc.resize(n); A.owner.resize(n);
+    for (int i = 0; i < n; i++) { A.desc[i] = feats[i].descriptors; A.owner[i] = feats[i].owner_; }
+    A.enqueued = true;
+    return MIS_OK;
+}
+
+// The batch has its host counts: the pass enqueued ahead is the next matcher call's to adopt -- for exactly these counts.
+void mis_knn_ahead_confirm(MisContext* ctx, const MisFeatures* feats, int n) {
+    if (!ctx->match_ws) return;
+    MatchWorkspace::Ahead& A = static_cast<MatchWorkspace*>(ctx->match_ws)->ahead;
+    if (!A.enqueued || n != (int)A.desc.size()) { A.valid = A.enqueued = false; return; }
+    A.counts.resize(n);
+    for (int i = 0; i < n; i++) A.counts[i] = feats[i].n;
+    A.valid = true;
+}
+
+// Nobody adopts the pass enqueued ahead (its kernels, if any, run to their end and their results are never read); with a block
+// pointer: only when that block is one of the pass's (mis_features_free: the pointer may come back for another feature set).
+void mis_knn_ahead_drop(MisContext* ctx, const void* owner) {
+    if (!ctx->match_ws) return;
+    MatchWorkspace::Ahead& A = static_cast<MatchWorkspace*>(ctx->match_ws)->ahead;
+    if (owner && std::find(A.owner.begin(), A.owner.end(), owner) == A.owner.end()) return;
+    A.valid = A.enqueued = false;
+}
+
+// diagnostics: how many matcher calls of this context have adopted a 2-NN pass enqueued ahead (mis_orb_arm_knn_ahead)
+extern "C" long long mis_debug_knn_ahead_adopted(MisContext* ctx) {
+    if (!ctx) return -1;
+    return ctx->match_ws ? static_cast<MatchWorkspace*>(ctx->match_ws)->ahead_adopted : 0;
+}
 
 // One-shot hook of this context's NEXT matcher call: fn(user) runs on the calling thread of mis_match_all_pairs /
 // mis_match_pairs_sharded / mis_match_pairs_select once all of the call's device work is enqueued, before the call waits for the device.

@@ -964,6 +964,12 @@ struct MisOrb {
     MisContext* ctx = nullptr;
     void (*enqueued_cb)(void*) = nullptr;      // mis_orb_on_enqueued: one-shot hook of the next batch call
     void* enqueued_user = nullptr;
+    // mis_orb_arm_knn_ahead: one-shot, the next batch call enqueues the matcher's 2-NN pass of this selection behind its kernels
+    bool knn_armed = false;
+    int knn_n = 0, knn_range_width = -1, knn_rank = 0, knn_world = 1;
+    bool knn_has_mask = false;
+    std::vector<uint8_t> knn_mask;
+    OwnedEvent ev_counts;                      // the batch's counts have landed in host_counts
     MisOrbParams p;
     int max_w = 0, max_h = 0;
     int cur_w = 0, cur_h = 0;
@@ -1221,6 +1227,32 @@ int gather_counts_and_flags(MisOrb* o, MisFeatures* out, int n, int* flags) {
     return MIS_OK;
 }
 
+// The same in two halves, for a batch that is followed on the stream by work the host must not wait for (the matcher's 2-NN pass,
+// mis_knn_ahead_enqueue) and whose values fit one gather: the kernel and an event go in FIRST, the host later waits for the event,
+// not for the stream -- a gather enqueued behind the pass would hand the counts over 0.4 ms late.
+bool gather_fits_one(const MisOrb* o, int n) { return n + o->ws_frames <= ORB_GATHER_MAX; }
+int gather_enqueue(MisOrb* o, MisFeatures* out, int n) {
+    MisContext* ctx = o->ctx;
+    const int total = n + o->ws_frames;
+    if (!o->host_counts) MIS_HIP(ctx, hipHostMalloc((void**)&o->host_counts, sizeof(int) * ORB_GATHER_MAX, hipHostMallocMapped));
+    int* dev_view = nullptr;
+    MIS_HIP(ctx, hipHostGetDevicePointer((void**)&dev_view, o->host_counts, 0));
+    MIS_HIP(ctx, o->ev_counts.ready());
+    GatherPtrs gp;
+    for (int k = 0; k < total; k++)
+        gp.p[k] = k < n ? mis_feat_count(&out[k], o->out_cap) : (const int*)((const char*)o->w.flags + (size_t)(k - n) * o->ws_stride);
+    hipLaunchKernelGGL(gather_ints_kernel, dim3(1), dim3(ORB_GATHER_MAX), 0, ctx->stream, gp, total, dev_view);
+    MIS_HIP(ctx, hipEventRecord(o->ev_counts.ev, ctx->stream));
+    return MIS_OK;
+}
+int gather_finish(MisOrb* o, MisFeatures* out, int n, int* flags) {
+    MIS_HIP(o->ctx, hipEventSynchronize(o->ev_counts.ev));
+    for (int i = 0; i < n; i++) out[i].n = o->host_counts[i];
+    *flags = 0;
+    for (int k = n; k < n + o->ws_frames; k++) *flags |= o->host_counts[k];
+    return MIS_OK;
+}
+
 }  // namespace
 
 extern "C" void mis_orb_default_params(MisOrbParams* p) {
@@ -1295,6 +1327,9 @@ extern "C" int mis_orb_destroy(MisOrb* o) {
 extern "C" int mis_orb_detect_batch(MisOrb* o, const MisImage* imgs, int n, MisFeatures* out) {
     if (!o) return MIS_E_INVALID;
     MisContext* ctx = o->ctx;
+    const bool armed = o->knn_armed;        // one-shot, like the hook
+    o->knn_armed = false;
+    mis_knn_ahead_drop(ctx, nullptr);       // (a pass behind an earlier batch that no matcher call took)
     MIS_CHECK(ctx, imgs && out && n >= 1, MIS_E_INVALID, "null argument");
     MIS_HIP(ctx, hipSetDevice(ctx->device));
     int rc;
@@ -1308,6 +1343,7 @@ extern "C" int mis_orb_detect_batch(MisOrb* o, const MisImage* imgs, int n, MisF
     for (int i = 0; i < n; i++) memset(&out[i], 0, sizeof(MisFeatures));
     // an error must not leak the outputs / staged inputs of the frames already set up
     auto fail = [&](int code) {
+        mis_knn_ahead_drop(ctx, nullptr);
         hipStreamSynchronize(ctx->stream);
         for (int i = 0; i < n; i++)
             if (out[i].keypoints || out[i].descriptors) mis_features_free(ctx, &out[i]);
@@ -1326,6 +1362,21 @@ extern "C" int mis_orb_detect_batch(MisOrb* o, const MisImage* imgs, int n, MisF
         if ((rc = enqueue_detect_group(o, &dimg[g0], imgs[0].width, imgs[0].height, &out[g0], ng)) != MIS_OK) return fail(rc);
     }
     if (trace) fprintf(stderr, "orb batch: %d frames enqueued in %.0f us\n", n, (double)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t_enq0).count());
+    // armed (mis_orb_arm_knn_ahead): the matcher's expansion and 2-NN pass go in right behind the batch's last kernel, planned
+    // from the blocks' capacity -- tens of microseconds of host time under the batch's device work, instead of a device that
+    // idles from the end of the batch until the host has fetched the counts, returned and entered the matcher.  The gather of
+    // the counts goes in ahead of the pass (gather_enqueue).  Whatever goes wrong, here or below, nobody adopts the pass.
+    bool ahead = false;
+    if (armed && n == o->knn_n && gather_fits_one(o, n)) {
+        if ((rc = gather_enqueue(o, out, n)) != MIS_OK) return fail(rc);
+        std::vector<int> caps(n, o->out_cap);
+        std::vector<int*> counts(n);
+        for (int i = 0; i < n; i++) counts[i] = mis_feat_count(&out[i], o->out_cap);
+        if ((rc = mis_knn_ahead_enqueue(ctx, out, n, caps.data(), counts.data(), o->knn_has_mask ? o->knn_mask.data() : nullptr, o->knn_range_width,
+                                        o->knn_rank, o->knn_world)) != MIS_OK) return fail(rc);
+        ahead = true;
+        if (trace) fprintf(stderr, "orb batch: 2-NN pass enqueued ahead at %.0f us\n", (double)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t_enq0).count());
+    }
     // one-shot hook (mis_orb_on_enqueued): the caller's own host work -- e.g. the job's warpRoi + blender sizing, which end in a
     // synchronisation of ANOTHER stream -- runs here, under the batch's 2 ms of device work, on the thread that would only wait
     if (o->enqueued_cb) {
@@ -1336,11 +1387,13 @@ extern "C" int mis_orb_detect_batch(MisOrb* o, const MisImage* imgs, int n, MisF
         MIS_HIP(ctx, hipSetDevice(ctx->device));
     }
     int flags = 0;
-    if ((rc = gather_counts_and_flags(o, out, n, &flags)) != MIS_OK) return rc;
+    if ((rc = ahead ? gather_finish(o, out, n, &flags) : gather_counts_and_flags(o, out, n, &flags)) != MIS_OK) { mis_knn_ahead_drop(ctx, nullptr); return rc; }
     if (flags) {
+        mis_knn_ahead_drop(ctx, nullptr);
         hipMemset2DAsync(o->w.flags, o->ws_stride, 0, sizeof(int), (size_t)o->ws_frames, ctx->stream);
         return mis_set_error(ctx, MIS_E_OVERFLOW, "ORB candidate buffers overflowed (flags %d): too many tied scores", flags);
     }
+    if (ahead) mis_knn_ahead_confirm(ctx, out, n);
     return MIS_OK;
 }
 
@@ -1349,6 +1402,18 @@ extern "C" int mis_orb_detect(MisOrb* o, const MisImage* bgr, MisFeatures* out) 
 extern "C" int mis_orb_on_enqueued(MisOrb* o, void (*fn)(void*), void* user) {
     if (!o) return MIS_E_INVALID;
     o->enqueued_cb = fn; o->enqueued_user = user;
+    return MIS_OK;
+}
+
+extern "C" int mis_orb_arm_knn_ahead(MisOrb* o, int n, const uint8_t* mask, int range_width, int rank, int world) {
+    if (!o) return MIS_E_INVALID;
+    o->knn_armed = false;
+    if (n <= 0) return MIS_OK;      // disarm
+    MIS_CHECK(o->ctx, (range_width == -1 || range_width >= 1) && world >= 1 && rank >= 0 && rank < world, MIS_E_INVALID, "bad selection (range_width -1 or >= 1, 0 <= rank < world)");
+    o->knn_n = n; o->knn_range_width = range_width; o->knn_rank = rank; o->knn_world = world;
+    o->knn_has_mask = mask != nullptr;
+    if (mask) o->knn_mask.assign(mask, mask + (size_t)n * n); else o->knn_mask.clear();
+    o->knn_armed = true;
     return MIS_OK;
 }
 

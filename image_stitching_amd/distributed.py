@@ -501,7 +501,13 @@ class StitchJob:
 
     # -- stages -------------------------------------------------------------------------------
     def stage_features(self, frames):
-        return self.engine.detect([frames[i] for i in self.my_frames])
+        mine = [frames[i] for i in self.my_frames]
+        # a single rank matches the finder's own output next: an ORB finder enqueues the matcher's 2-NN pass behind its batch, while
+        # the keypoint counts are still on their way to the host (the matcher call adopts it; sharded, the features are exchanged first)
+        finder = getattr(self.engine, "finder", None)
+        if self.world == 1 and not self.force_collectives and hasattr(finder, "arm_knn_ahead"):
+            finder.arm_knn_ahead(len(mine), None, self.cfg.range_width)
+        return self.engine.detect(mine)
 
     def stage_gather(self, local_feats):
         if self.world == 1 and not self.force_collectives:

@@ -759,6 +759,17 @@ class OrbFeatureFinder:
             self._enqueued_cb = C.CFUNCTYPE(None, C.c_void_p)(self._run_enqueued)
         self.ctx.check(self.ctx.lib.mis_orb_on_enqueued(self.h, C.cast(self._enqueued_cb, C.c_void_p), None))
 
+    def arm_knn_ahead(self, n, mask=None, range_width=-1, rank=0, world_size=1):
+        """One-shot: the NEXT detect_batch call, of n frames, enqueues the matcher's Hamming 2-NN pass for this pair selection behind
+        its own kernels (mis_orb_arm_knn_ahead); the context's next matcher call adopts the pass when it matches exactly that
+        batch with this selection, and runs its own otherwise -- the results are the same.  n=0 disarms."""
+        if mask is not None:
+            mask = np.ascontiguousarray(np.asarray(mask) != 0, np.uint8)
+            if mask.shape != (n, n):
+                raise ValueError("mask must be %d x %d, got shape %r" % (n, n, mask.shape))
+        self.ctx.check(self.ctx.lib.mis_orb_arm_knn_ahead(self.h, int(n), None if mask is None else mask.ctypes.data_as(C.c_void_p),
+                                                          int(range_width), int(rank), int(world_size)))
+
     def _run_enqueued(self, _user):
         fn, self._enqueued_fn = getattr(self, "_enqueued_fn", None), None
         if fn is not None:

@@ -128,6 +128,18 @@ int mis_orb_detect_batch(MisOrb* orb, const MisImage* bgr, int n_images, MisFeat
  * is enqueued and before the call waits for it (fn = NULL clears a pending hook).  The job sizes its blender there (warpRoi of all
  * cameras: a kernel and a synchronisation on the compose stream), under the feature stage instead of in front of it. */
 int mis_orb_on_enqueued(MisOrb* orb, void (*fn)(void*), void* user);
+/* One-shot arm of this finder's NEXT mis_orb_detect_batch call, for a batch of n frames that the matcher of the finder's context
+ * will match with this selection (mask: n x n or NULL, range_width, rank, world: as in mis_match_pairs_select; the mask is copied).
+ * The batch then enqueues the matcher's descriptor expansion and Hamming 2-NN pass of the selected pairs behind its own kernels, on
+ * the context's stream, while the keypoint counts are still on the device -- the device no longer idles while the host fetches
+ * the counts, returns and enters the matcher.  The next matcher call of that context ADOPTS the pass when its feature list is
+ * exactly the batch's output (the same MisFeatures, unmodified, in the same order), its selection is the armed one, world is 1
+ * and every frame has between 1 and 8192 keypoints; it then runs its ratio test and RANSAC chains on the pass's results.  In every
+ * other case -- another list, order or selection, an empty frame, a batch of another size or of more than 64 frames, blocks that
+ * hold more than 8192 features, an error or overflow in the batch, a
+ * feature set of the batch freed, another batch in between -- the pass is dropped and the matcher call runs its own: ignoring
+ * the pass is always correct, and the results are the same either way.  n <= 0 disarms. */
+int mis_orb_arm_knn_ahead(MisOrb* orb, int n, const uint8_t* mask, int range_width, int rank, int world);
 int mis_features_download(MisContext* ctx, const MisFeatures* f, MisKeyPoint* kps_host, void* desc_host);
 /* wrap caller-provided (host) keypoints/descriptors as device-resident features */
 int mis_features_upload(MisContext* ctx, int img_w, int img_h, int n, const MisKeyPoint* kps_host,
@@ -211,6 +223,8 @@ int mis_match_knn_fence(MisContext* ctx, void* stream, long long target_seq, int
  * for the device (the ~5 ms in which that thread is idle); inside it mis_match_knn_fence(ctx, stream, mis_match_sequence(ctx), 0)
  * returns at once and queues `stream` behind the 2-NN pass.  The hook is not called when the matcher call fails earlier. */
 int mis_match_on_enqueued(MisContext* ctx, void (*fn)(void*), void* user);
+/* diagnostics: the number of this context's matcher calls that adopted a 2-NN pass enqueued ahead (mis_orb_arm_knn_ahead) */
+long long mis_debug_knn_ahead_adopted(MisContext* ctx);
 /* exact 2-NN (distance, trainIdx) for one direction; results in host memory (stage test hook) */
 int mis_knn2(MisContext* ctx, const MisFeatures* query, const MisFeatures* train, int* idx2_host, float* dist2_host);
 /* cv::findHomography(src, dst, mask, RANSAC, thresh, max_iters, confidence) on host point lists */
