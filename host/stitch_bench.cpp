@@ -228,7 +228,7 @@ static int launch(const Args& a, int argc, char** argv) {
 }
 
 int main(int argc, char** argv) {
-    if (argc < 2) { std::fprintf(stderr, "usage: stitch_bench cams.txt [--steps K] [--warmup W] [--dump prefix] [--ranks N] [--comm host|rccl] [--one-gpu] [--warp spherical|cylindrical|plane|mercator|fisheye|stereographic] [--work_megapix f] [--rangewidth N] [--matcher homography|affine]\n"); return 2; }
+    if (argc < 2) { std::fprintf(stderr, "usage: stitch_bench cams.txt [--steps K] [--warmup W] [--dump prefix] [--ranks N] [--comm host|rccl] [--one-gpu] [--warp spherical|cylindrical|plane|mercator|fisheye|stereographic|compressedPlaneA2B1|compressedPlaneA1.5B1|paniniA2B1|paniniA1.5B1] [--work_megapix f] [--rangewidth N] [--matcher homography|affine]\n"); return 2; }
     Args a;
     a.cams_path = argv[1];
     for (int i = 2; i < argc; i++) {

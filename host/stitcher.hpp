@@ -33,9 +33,9 @@ struct StitchConfig {
     std::string expos_comp_type = "no";    // "no" | "gain" | "gain_blocks" | "channels" | "channels_blocks" (:73; 64 x 64 blocks, 2 filtering passes)
     int expos_comp_nr_feeds = 1;           // :74
     std::string seam_find_type = "no";     // "no" | "voronoi" | "dp_color" (the reference's default; this driver's default is the hot path)
-    // warper (:917-969): the three of the reference's GPU branch and its Mercator, fisheye and stereographic warpers are built; its
-    // other names throw by name (warp_kind)
-    std::string warp_type = "spherical";   // "spherical" | "cylindrical" | "plane" | "mercator" | "fisheye" | "stereographic"
+    // warper (:917-969): the three of the reference's GPU branch and its Mercator, fisheye, stereographic, compressed-plane and Panini
+    // warpers are built; its other names (the portrait variants, transverseMercator, affine) throw by name (warp_kind)
+    std::string warp_type = "spherical";   // "spherical" | "cylindrical" | "plane" | "mercator" | "fisheye" | "stereographic" | "compressedPlaneA2B1" | "compressedPlaneA1.5B1" | "paniniA2B1" | "paniniA1.5B1"
     // matcher (:83, :646-649): -1 BestOf2NearestMatcher (all pairs), w >= 1 BestOf2NearestRangeMatcher (pairs with j < i + w only)
     int range_width = -1;
     // matcher_type (:64, :644-645): "homography" (the two above) | "affine": AffineBestOf2NearestMatcher(false, ...), all pairs
@@ -91,11 +91,15 @@ inline int warp_kind(const std::string& t) {
     if (t == "mercator") return MIS_WARP_MERCATOR;
     if (t == "fisheye") return MIS_WARP_FISHEYE;
     if (t == "stereographic") return MIS_WARP_STEREOGRAPHIC;
-    static const char* unbuilt[] = {"affine", "compressedPlaneA2B1", "compressedPlaneA1.5B1", "compressedPlanePortraitA2B1",
-                                    "compressedPlanePortraitA1.5B1", "paniniA2B1", "paniniA1.5B1", "paniniPortraitA2B1", "paniniPortraitA1.5B1",
+    if (t == "compressedPlaneA2B1") return MIS_WARP_COMPRESSED_PLANE_A2B1;
+    if (t == "compressedPlaneA1.5B1") return MIS_WARP_COMPRESSED_PLANE_A15B1;
+    if (t == "paniniA2B1") return MIS_WARP_PANINI_A2B1;
+    if (t == "paniniA1.5B1") return MIS_WARP_PANINI_A15B1;
+    static const char* unbuilt[] = {"affine", "compressedPlanePortraitA2B1", "compressedPlanePortraitA1.5B1", "paniniPortraitA2B1", "paniniPortraitA1.5B1",
                                     "transverseMercator"};
     for (const char* u : unbuilt)
-        if (t == u) throw std::runtime_error("warper '" + t + "' is not implemented ('spherical', 'cylindrical', 'plane', 'mercator', 'fisheye' and 'stereographic' are)");
+        if (t == u) throw std::runtime_error("warper '" + t + "' is not implemented ('spherical', 'cylindrical', 'plane', 'mercator', 'fisheye', 'stereographic', "
+                                             "'compressedPlaneA2B1', 'compressedPlaneA1.5B1', 'paniniA2B1' and 'paniniA1.5B1' are)");
     throw std::runtime_error("Can't create the following warper '" + t + "'");
 }
 

@@ -2,16 +2,17 @@
 
 Host-side mirror (Python) of the interface the reference drives in ``main()``
 (image_stitching/image_stitching.cpp:545-1228): ``computeImageFeatures`` / ``BestOf2NearestMatcher`` /
-``SphericalWarper`` (``CylindricalWarper``, ``PlaneWarper``, ``MercatorWarper``, ``FisheyeWarper``, ``StereographicWarper``) / ``MultiBandBlender`` / ``FeatherBlender``, each a thin veneer over the C ABI of
+``SphericalWarper`` (``CylindricalWarper``, ``PlaneWarper``, ``MercatorWarper``, ``FisheyeWarper``, ``StereographicWarper``, ``CompressedRectilinearWarper``, ``PaniniWarper``) / ``MultiBandBlender`` / ``FeatherBlender``, each a thin veneer over the C ABI of
 ``libmistitch.so`` (include/mistitch.h).  torch is used only to own device memory and streams.
 
 There is no CPU fallback: everything here needs the HIP library and a GPU.
 """
 from . import _capi
 from ._capi import (BLEND_FEATHER, BLEND_MULTI_BAND, BLEND_NO, BORDER_CONSTANT, BORDER_REFLECT, INTER_LINEAR,
-                    INTER_NEAREST, WARP_CYLINDRICAL, WARP_FISHEYE, WARP_MERCATOR, WARP_PLANE, WARP_SPHERICAL, WARP_STEREOGRAPHIC)
+                    INTER_NEAREST, WARP_CYLINDRICAL, WARP_FISHEYE, WARP_MERCATOR, WARP_PLANE, WARP_SPHERICAL, WARP_STEREOGRAPHIC,
+                    WARP_COMPRESSED_PLANE_A2B1, WARP_COMPRESSED_PLANE_A15B1, WARP_PANINI_A2B1, WARP_PANINI_A15B1)
 from .stitching import (AffineBestOf2NearestMatcher, BestOf2NearestMatcher, BestOf2NearestRangeMatcher, estimate_affine_partial, Blender, BlocksGainCompensator, GainCompensator, ChannelsCompensator, BlocksChannelsCompensator, NoSeamFinder, VoronoiSeamFinder, DpSeamFinder, Context, FeatherBlender, ImageFeatures, MatchesInfo,
-                        MisError, MultiBandBlender, OrbFeatureFinder, SiftFeatureFinder, SphericalWarper, CylindricalWarper, PlaneWarper, MercatorWarper, FisheyeWarper, StereographicWarper,
+                        MisError, MultiBandBlender, OrbFeatureFinder, SiftFeatureFinder, SphericalWarper, CylindricalWarper, PlaneWarper, MercatorWarper, FisheyeWarper, StereographicWarper, CompressedRectilinearWarper, PaniniWarper,
                         RotationWarper, StitchConfig, Stitcher,
                         blend_config, bundle_adjust_reproj, computeImageFeatures, find_homography, leaveBiggestComponent, resize, resize_batch, result_roi,
                         rotate, seam_mask_apply, selected_pairs, warp_roi, wave_correct, work_geometry)
@@ -23,5 +24,6 @@ __all__ = [
     "seam_mask_apply", "bundle_adjust_reproj", "wave_correct", "BlocksGainCompensator", "GainCompensator", "ChannelsCompensator", "BlocksChannelsCompensator", "NoSeamFinder", "VoronoiSeamFinder", "DpSeamFinder",
     "INTER_NEAREST", "INTER_LINEAR", "BORDER_CONSTANT", "BORDER_REFLECT", "BLEND_NO", "BLEND_FEATHER",
     "BLEND_MULTI_BAND", "resize_batch", "work_geometry", "CylindricalWarper", "PlaneWarper", "RotationWarper", "WARP_SPHERICAL", "WARP_CYLINDRICAL", "WARP_PLANE", "WARP_MERCATOR", "MercatorWarper", "WARP_FISHEYE", "WARP_STEREOGRAPHIC", "FisheyeWarper", "StereographicWarper",
+    "WARP_COMPRESSED_PLANE_A2B1", "WARP_COMPRESSED_PLANE_A15B1", "WARP_PANINI_A2B1", "WARP_PANINI_A15B1", "CompressedRectilinearWarper", "PaniniWarper",
     "BestOf2NearestRangeMatcher", "selected_pairs", "AffineBestOf2NearestMatcher", "estimate_affine_partial",
 ]

@@ -20,12 +20,14 @@ INTER_NEAREST, INTER_LINEAR = 0, 1
 BORDER_CONSTANT, BORDER_REFLECT = 0, 2
 BLEND_NO, BLEND_FEATHER, BLEND_MULTI_BAND = 0, 1, 2
 WARP_SPHERICAL, WARP_CYLINDRICAL, WARP_PLANE, WARP_MERCATOR, WARP_FISHEYE, WARP_STEREOGRAPHIC = 0, 1, 2, 3, 4, 5
+# one kind per (A, B) setting the reference offers (the entries have no slot for the two parameters); 6 and 7 are not assigned
+WARP_COMPRESSED_PLANE_A2B1, WARP_COMPRESSED_PLANE_A15B1, WARP_PANINI_A2B1, WARP_PANINI_A15B1 = 8, 9, 10, 11
 
 
 def roi_is_full_scan(kind):
     """MIS_WARP_ROI_IS_FULL_SCAN: the kinds whose warpRoi projects every source pixel (no detectResultRoi of their own), so the roi
     belongs on the device (mis_warper_roi_batch) and is passed on to the warp instead of being computed again."""
-    return WARP_MERCATOR <= kind <= WARP_STEREOGRAPHIC
+    return WARP_MERCATOR <= kind <= WARP_STEREOGRAPHIC or WARP_COMPRESSED_PLANE_A2B1 <= kind <= WARP_PANINI_A15B1
 
 
 MATH_LOG, MATH_TAN, MATH_SINH, MATH_ASIN, MATH_ATAN, MATH_EXP = 0, 1, 2, 3, 4, 5     # mis_debug_math_f32
@@ -159,6 +161,7 @@ PROTOTYPES = {
     "mis_warp_spherical_fused_batch_timed": (_i, [_vp, _P(MisImage), _i, C.c_float, _P(C.c_float), _P(C.c_float), _P(MisRect), _P(MisImage), _P(MisImage), _P(MisPoint), _i,
                                                _P(C.c_float)]),
     "mis_debug_math_f32": (_i, [_vp, _i, _vp, _vp, _i]),
+    "mis_debug_warper_map_f32": (_i, [_vp, _i, _f, _vp, _vp, _P(MisRect), _vp]),
     "mis_warper_roi": (_i, [_i, _f, _i, _i, _vp, _vp, _P(MisRect)]),
     "mis_warper_roi_batch": (_i, [_vp, _i, _f, _i, _i, _i, _vp, _vp, _P(MisRect)]),
     "mis_warper_warp": (_i, [_vp, _i, _P(MisImage), _f, _vp, _vp, _i, _i, _P(MisImage), _P(MisPoint)]),

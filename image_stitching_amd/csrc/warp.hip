@@ -1,5 +1,5 @@
 // warp.hip -- rotation warps, replaces the reference's cv::detail::{Spherical,Cylindrical,Plane,Mercator,Fisheye,
-// Stereographic}Warper calls
+// Stereographic,CompressedRectilinear,Panini}Warper calls
 // (the warp_type switch of image_stitching/image_stitching.cpp:917-969): :973/:1117 (create(scale)),
 // :985/:988/:1154/:1159 (warp), :1138 (warpRoi), :1164 (convertTo CV_16S, fused here).
 // The separable kinds share one per-pixel form: x_ = su * s, z_ = cu * s, y_ = c with a column table {su, cu} and a row table
@@ -15,6 +15,9 @@
 // into LDS (128 + 16 evaluations per 2048 pixels).
 // The fisheye and stereographic maps are polar (u_ = atan2(v', u'), rho = |(u', v')|) and not separable: those two kinds evaluate
 // mapBackward per output pixel in kernels of their own (map_backward_polar, warp_polar_*), with the same sampling and stores.
+// The compressed-rectilinear and Panini maps (kinds 8 .. 11) are half separable: the horizontal angle lam = a atan(u' / a) depends on
+// the column only, the vertical angle v_ on the pixel.  Their kernels (col_*, warp_col_*) evaluate the column terms once per column of
+// a tile and the rest per pixel.
 #include "common.h"
 #include "dev_math.h"
 #include <algorithm>
@@ -28,10 +31,25 @@ struct Projector {
     float scale;
     float k[9], rinv[9], r_kinv[9], k_rinv[9];
     int kind;   // MIS_WARP_*
+    float a, b; // the (A, B) of a compressed-plane / Panini kind (col_kind_of), else 0
 };
 
 // the kinds whose backward map is evaluated per output pixel (no column / row tables)
 static bool kind_polar(int kind) { return kind == MIS_WARP_FISHEYE || kind == MIS_WARP_STEREOGRAPHIC; }
+
+// The half-separable kinds: kind -> {family, a, b}.  The kernels are instantiated per family and read a and b from their arguments;
+// the template value of a family is its A2B1 kind.
+struct ColKind { int family; float a, b; };     // family: MIS_WARP_COMPRESSED_PLANE_A2B1 or MIS_WARP_PANINI_A2B1; 0 = another kind
+static ColKind col_kind_of(int kind) {
+    switch (kind) {
+        case MIS_WARP_COMPRESSED_PLANE_A2B1: return {MIS_WARP_COMPRESSED_PLANE_A2B1, 2.f, 1.f};
+        case MIS_WARP_COMPRESSED_PLANE_A15B1: return {MIS_WARP_COMPRESSED_PLANE_A2B1, 1.5f, 1.f};
+        case MIS_WARP_PANINI_A2B1: return {MIS_WARP_PANINI_A2B1, 2.f, 1.f};
+        case MIS_WARP_PANINI_A15B1: return {MIS_WARP_PANINI_A2B1, 1.5f, 1.f};
+        default: return {0, 0.f, 0.f};
+    }
+}
+static bool kind_col(int kind) { return col_kind_of(kind).family != 0; }
 
 // ProjectorBase::setCameraParams (stitching/src/warpers.cpp): float matrices, double intermediates
 void projector_set(Projector* p, int kind, float scale, const float K[9], const float R[9]) {
@@ -39,6 +57,7 @@ void projector_set(Projector* p, int kind, float scale, const float K[9], const 
     float kinv_f[9];
     p->kind = kind;
     p->scale = scale;
+    p->a = col_kind_of(kind).a; p->b = col_kind_of(kind).b;
     for (int i = 0; i < 9; i++) p->k[i] = K[i];
     for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) p->rinv[i * 3 + j] = R[j * 3 + i];
     auto KD = [&](int r, int c) { return (double)K[r * 3 + c]; };
@@ -73,12 +92,27 @@ void projector_set(Projector* p, int kind, float scale, const float K[9], const 
 // its instantiation leaves the polar branch out).
 // Fisheye / stereographic: no NaN guard and no special case at the singular points, as there: the stereographic quotient is 0 / 0 =
 // NaN on the ray (0, -1, 0) (v_ = 0) and huge next to it.
-template <int LAST_KIND = MIS_WARP_STEREOGRAPHIC>
-MIS_HD bool map_forward(int kind, const float* m, float scale, float x, float y, float* u, float* v) {
+// {CompressedRectilinear,Panini}Projector(a, b)::mapForward (`kind` is the family's A2B1 kind or the kind itself): nothing special
+// at cosf(u_) = 0 (v infinite: the roi is refused), past tanf's pole (a = 1.5: u_ / a reaches 120 degrees) or at u_ beyond 90 degrees.
+template <int LAST_KIND = MIS_WARP_PANINI_A15B1>
+MIS_HD bool map_forward(int kind, const float* m, float scale, float x, float y, float* u, float* v, float a = 0.f, float b = 0.f) {
     float x_ = (m[0] * x + m[1] * y) + m[2];
     float y_ = (m[3] * x + m[4] * y) + m[5];
     float z_ = (m[6] * x + m[7] * y) + m[8];
-    if (LAST_KIND >= MIS_WARP_FISHEYE && (kind == MIS_WARP_FISHEYE || kind == MIS_WARP_STEREOGRAPHIC)) {
+    if (LAST_KIND >= MIS_WARP_COMPRESSED_PLANE_A2B1 && kind >= MIS_WARP_COMPRESSED_PLANE_A2B1) {
+        float u_ = mis_atan2f(x_, z_);
+        float v_ = mis_asinf(y_ / sqrtf((x_ * x_ + y_ * y_) + z_ * z_));
+        if (kind <= MIS_WARP_COMPRESSED_PLANE_A15B1) {
+            *u = scale * a * mis_tanf(u_ / a);
+            *v = scale * b * mis_tanf(v_) / mis_cosf(u_);
+        } else {
+            float tg = a * mis_tanf(u_ / a);
+            *u = scale * tg;
+            float sinu = mis_sinf(u_);
+            if (fabsf(sinu) < 1e-7f) *v = scale * b * mis_tanf(v_);
+            else *v = scale * b * tg * mis_tanf(v_) / sinu;
+        }
+    } else if (LAST_KIND >= MIS_WARP_FISHEYE && (kind == MIS_WARP_FISHEYE || kind == MIS_WARP_STEREOGRAPHIC)) {
         float u_ = mis_atan2f(x_, z_);
         float v_ = MIS_PI_F - mis_acosf(y_ / sqrtf((x_ * x_ + y_ * y_) + z_ * z_));
         float su, cu;
@@ -145,7 +179,8 @@ int roi_from_extremes(const Projector* p, int sw, int sh, float tl_uf, float tl_
 //  * spherical (SphericalWarper::detectResultRoi) and cylindrical (detectResultRoiByBorder): the 2(W+H) border pixels;
 //  * plane (PlaneWarper::detectResultRoi): the four corners (0,0), (0,h-1), (w-1,0), (w-1,h-1).  A corner with z_ <= 0 lies behind
 //    the panorama plane and OpenCV's rectangle means nothing: MIS_E_INVALID.
-//  * mercator, fisheye, stereographic (RotationWarperBase::detectResultRoi: these warpers have no override): every pixel, O(w h).
+//  * mercator, fisheye, stereographic, compressed-plane, Panini (RotationWarperBase::detectResultRoi: these warpers have no override):
+//    every pixel, O(w h).
 //    With a pole inside the frame the extreme lies at an interior pixel; a NaN (Mercator: the upper pole; stereographic: the ray
 //    (0, -1, 0)) is skipped as std::min / std::max skip it.
 int detect_result_roi(const Projector* p, int sw, int sh, int* tlx, int* tly, int* brx, int* bry) {
@@ -164,7 +199,7 @@ int detect_result_roi(const Projector* p, int sw, int sh, int* tlx, int* tly, in
         if (!front) return MIS_E_INVALID;
     } else if (MIS_WARP_ROI_IS_FULL_SCAN(kind)) {
         for (int y = 0; y < sh; ++y)
-            for (int x = 0; x < sw; ++x) { map_forward(kind, p->r_kinv, p->scale, (float)x, (float)y, &u, &v); upd(); }
+            for (int x = 0; x < sw; ++x) { map_forward(kind, p->r_kinv, p->scale, (float)x, (float)y, &u, &v, p->a, p->b); upd(); }
     } else {
         for (int x = 0; x < sw; ++x) {
             map_forward(kind, p->r_kinv, p->scale, (float)x, 0, &u, &v); upd();
@@ -198,6 +233,7 @@ int projector_and_roi(int kind, float scale, const float K[9], const float R[9],
 // (The plane kind: threads 0..3 project the four corners, and `behind` reports a corner with z_ <= 0.)
 struct RoiJob {
     float r_kinv[9], scale;
+    float a, b;     // compressed-plane / Panini
     int sw, sh, kind;
     int behind;     // out (plane): some corner lies behind the panorama plane
     float ext[4];   // out: min u, min v, max u, max v
@@ -244,7 +280,7 @@ __global__ __launch_bounds__(256) void warp_roi_kernel(RoiJob* jobs) {
     }
 }
 
-// The full-frame scan of RotationWarperBase::detectResultRoi (the Mercator, fisheye and stereographic kinds): workgroup (c, f) projects rows
+// The full-frame scan of RotationWarperBase::detectResultRoi (the Mercator, fisheye, stereographic, compressed-plane and Panini kinds): workgroup (c, f) projects rows
 // c * rows .. c * rows + rows - 1 of frame f, every pixel, and writes one partial {min u, min v, max u, max v} to part[f * nchunk + c]
 // (pinned, device-visible, behind the jobs).  The host takes the min / max of a frame's partials after the entry's one stream
 // synchronisation: min / max of floats with NaN skipped, any order gives the host loop's floats (+-0 apart, and (int) of both is 0).
@@ -257,7 +293,7 @@ __global__ __launch_bounds__(256) void warp_roi_scan_kernel(const RoiJob* jobs, 
     __shared__ float red[4][4];
     float m[9];
     for (int i = 0; i < 9; i++) m[i] = j->r_kinv[i];
-    const float scale = j->scale;
+    const float scale = j->scale, pa = j->a, pb = j->b;
     const int sw = j->sw, sh = j->sh;
     constexpr int kind = KIND;
     const int y0 = (int)blockIdx.x * rows, y1 = min(sh, y0 + rows);
@@ -269,7 +305,7 @@ __global__ __launch_bounds__(256) void warp_roi_scan_kernel(const RoiJob* jobs, 
     int r = (int)threadIdx.x / sw, c = (int)threadIdx.x - r * sw;
     for (unsigned i = threadIdx.x; i < npts; i += 256) {
         float u, v;
-        map_forward(kind, m, scale, (float)c, (float)(y0 + r), &u, &v);
+        map_forward(kind, m, scale, (float)c, (float)(y0 + r), &u, &v, pa, pb);
         lo_u = fminf(lo_u, u); lo_v = fminf(lo_v, v); hi_u = fmaxf(hi_u, u); hi_v = fmaxf(hi_v, v);
         c += cstep; r += rstep;
         if (c >= sw) { c -= sw; r += 1; }
@@ -294,6 +330,7 @@ struct WarpArgs {
     float scale;
     int tlx, tly, dw, dh, sw, sh, cn;
     int kind;        // MIS_WARP_* (read by the table fills and the u8 warps; the fused kernels take it as a template argument)
+    float pa, pb;    // the (A, B) of a compressed-plane / Panini kind
     const uint8_t* src;
     size_t sstride;
     void* dst;       // s16x3 (fused) or u8 x cn
@@ -1537,6 +1574,182 @@ __global__ __launch_bounds__(256) void warp_polar_u8_kernel(WarpArgs a) {
     }
 }
 
+// ---- the column-hoisted map path: the half-separable kinds (compressed-plane, Panini) ----
+// {CompressedRectilinear,Panini}Projector(a, b)::mapBackward (warpers_inl.hpp), the reference's operation sequence kept literally:
+//   u' = u / scale, v' = v / scale, lam = a atan(u' / a)
+//   compressed:  v_ = atan(v' cos(lam) / b)
+//   Panini:      v_ = |lam| > 1e-7 ? atan(v' sin(lam) / (b a tan(lam / a))) : atan(v' / b)
+//   ray (sin(lam) cos(v_), sin(v_), cos(lam) cos(v_)) through k_rinv with the z > 0 test (map_backward).
+// Nothing is special-cased where cos(lam) turns negative (|lam| > 90 degrees) or tan(lam / a) passes its pole (a = 1.5).
+// The sequence is split where its terms stop depending on the row: col_hoist evaluates, from u alone, lam, sin(lam), cos(lam) and for
+// Panini the divisor b a tan(lam / a) and the branch; col_pixel the rest.  Every float operation is the literal sequence's with the
+// same operands in the same order, so the split changes no bit (map_backward_col, the unsplit form, is what the host evaluates for
+// the test aid mis_debug_warper_map_f32).
+struct ColTerms { float sl, cl, den; bool big; };     // sin(lam), cos(lam); Panini: b a tan(lam / a), |lam| > 1e-7
+template <int FAM>
+MIS_HD ColTerms col_hoist(float scale, float pa, float pb, float u) {
+    ColTerms t;
+    const float lam = pa * mis_atanf(u / scale / pa);
+    mis_sincosf(lam, &t.sl, &t.cl);
+    t.big = fabsf(lam) > 1e-7f;
+    t.den = FAM == MIS_WARP_PANINI_A2B1 ? pb * pa * mis_tanf(lam / pa) : 0.f;
+    return t;
+}
+template <int FAM>
+MIS_HD void col_pixel(const ColTerms& t, float pb, float vp, float* sinv, float* cosv) {
+    float q;
+    if (FAM == MIS_WARP_PANINI_A2B1) q = t.big ? vp * t.sl / t.den : vp / pb;
+    else q = vp * t.cl / pb;
+    mis_sincosf(mis_atanf(q), sinv, cosv);
+}
+// the unsplit sequence for one pixel, every term evaluated where the reference evaluates it (host: the test aid's reference; the
+// kernels use the split form)
+MIS_HD void map_backward_col(int fam, const float* m, float scale, float pa, float pb, float u, float v, float* x, float* y) {
+    u /= scale; v /= scale;
+    const float lam = pa * mis_atanf(u / pa);
+    float v_;
+    if (fam == MIS_WARP_PANINI_A2B1) {
+        if (fabsf(lam) > 1e-7f) v_ = mis_atanf(v * mis_sinf(lam) / (pb * pa * mis_tanf(lam / pa)));
+        else v_ = mis_atanf(v / pb);
+    } else v_ = mis_atanf(v * mis_cosf(lam) / pb);
+    const float cosv = mis_cosf(v_);
+    const float x_ = mis_sinf(lam) * cosv, y_ = mis_sinf(v_), z_ = mis_cosf(lam) * cosv;
+    const float xx = (m[0] * x_ + m[1] * y_) + m[2] * z_;
+    const float yy = (m[3] * x_ + m[4] * y_) + m[5] * z_;
+    const float z = (m[6] * x_ + m[7] * y_) + m[8] * z_;
+    if (z > 0) { *x = xx / z; *y = yy / z; }
+    else { *x = -1.f; *y = -1.f; }
+}
+
+// Fused compose-scale warp of the half-separable kinds: polar_fused_tile's contract, stores (col_lane_store) and alignment rules (a lane owns PP_LPX = 4
+// consecutive columns: 24 bytes of 16SC3 image, two 16-bit mask words, adjacent lanes adjacent addresses, the byte tail at the roi's
+// edge).  A tile is PP_TW = 128 columns x PC_TH = 32 rows: a lane evaluates the column terms of its 4 columns once (a division, an
+// arctangent, a sincos, for Panini a tangent and a division more: ~110 / ~170 vector instructions per column) and reuses them over
+// PC_ROWS = 4 rows, rows (thread >> 5) + 8 k of the tile, so that the workgroup's waves work on 8 adjacent rows at a time (the source
+// footprint in flight stays that of a polar tile) and a roi lower than 8 rows still fills every lane row.  Per pixel remain the row
+// product / quotient, one arctangent, one sincos, the 3 x 3 product, the two divisions and the 12-tap gather.
+// `emit(gx0, gy, x, y)` receives the 4 source coordinates of a lane's row: the fused kernels sample and store, the test aid's
+// kernel stores the coordinates.
+constexpr int PC_ROWS = 4, PC_TH = 8 * PC_ROWS;
+static long long col_tiles_of(const WarpArgs& a) { return (long long)((a.dw + PP_TW - 1) / PP_TW) * ((a.dh + PC_TH - 1) / PC_TH); }
+
+template <int FAM, class Emit>
+__device__ __forceinline__ void col_tile(const WarpArgs& a, int tile, Emit&& emit) {
+    const int tiles_x = (a.dw + PP_TW - 1) / PP_TW;
+    const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
+    const int gx0 = tx * PP_TW + ((int)threadIdx.x & 31) * PP_LPX, gy0 = ty * PC_TH + ((int)threadIdx.x >> 5);
+    if (gx0 >= a.dw || gy0 >= a.dh) return;
+    ColTerms ct[PP_LPX];
+#pragma unroll
+    for (int i = 0; i < PP_LPX; i++) ct[i] = col_hoist<FAM>(a.scale, a.pa, a.pb, (float)(a.tlx + gx0 + i));    // (columns past the roi are computed and not stored)
+#pragma unroll 1
+    for (int k = 0; k < PC_ROWS; k++) {
+        const int gy = gy0 + 8 * k;
+        if (gy >= a.dh) break;
+        const float vp = (float)(a.tly + gy) / a.scale;
+        float x[PP_LPX], y[PP_LPX];
+#pragma unroll
+        for (int i = 0; i < PP_LPX; i++) {
+            float sinv, cosv;
+            col_pixel<FAM>(ct[i], a.pb, vp, &sinv, &cosv);
+            map_backward(FAM, a.m, ct[i].sl, ct[i].cl, cosv, sinv, &x[i], &y[i]);      // x_ = cos(v_) sin(lam), y_ = sin(v_), z_ = cos(v_) cos(lam)
+        }
+        emit(gx0, gy, x, y);
+    }
+}
+
+// the stores of a lane's PP_LPX pixels of row gy from column gx0: polar_fused_tile's, statement for statement (that function keeps its
+// own copy: taking the stores out of it changes its code generation, 61 -> 30 VGPRs and the taps of a lane's pixels no longer in flight together)
+__device__ __forceinline__ void col_lane_store(const WarpArgs& a, int gx0, int gy, const unsigned short* px, const uint8_t* mk) {
+    uint8_t* drow = (uint8_t*)a.dst + (size_t)gy * a.dstride + (size_t)gx0 * 6;      // 4-byte aligned: rows are (host check), gx0 * 6 = 24 k
+    uint8_t* mrow = a.mask + (size_t)gy * a.mstride + gx0;                           // 2-byte aligned: rows are, gx0 = 4 k
+    if (gx0 + PP_LPX <= a.dw) {
+        uint32_t* d = (uint32_t*)drow;
+#pragma unroll
+        for (int k = 0; k < PP_LPX * 3 / 2; k++) d[k] = (uint32_t)px[2 * k] | ((uint32_t)px[2 * k + 1] << 16);
+        unsigned short* q = (unsigned short*)mrow;
+        q[0] = (unsigned short)(mk[0] | (mk[1] << 8));
+        q[1] = (unsigned short)(mk[2] | (mk[3] << 8));
+    } else {
+        for (int i = 0; i < a.dw - gx0; i++) {
+            short* d = (short*)drow + 3 * i;
+            d[0] = (short)px[3 * i]; d[1] = (short)px[3 * i + 1]; d[2] = (short)px[3 * i + 2];
+            mrow[i] = mk[i];
+        }
+    }
+}
+
+// a lane's 4 pixels of row gy from column gx0: sampled and stored as polar_fused_tile does
+__device__ __forceinline__ void col_fused_emit(const WarpArgs& a, int gx0, int gy, const float* x, const float* y) {
+    unsigned short px[PP_LPX * 3];
+    uint8_t mk[PP_LPX];
+#pragma unroll
+    for (int i = 0; i < PP_LPX; i++) {
+        int p[3], sx, sy;
+        sample_linear<3>(a.src, a.sstride, a.sw, a.sh, x[i], y[i], p);
+        px[3 * i] = (unsigned short)p[0]; px[3 * i + 1] = (unsigned short)p[1]; px[3 * i + 2] = (unsigned short)p[2];
+        mk[i] = nearest_inside(a.sw, a.sh, x[i], y[i], &sx, &sy) ? 255 : 0;
+    }
+    col_lane_store(a, gx0, gy, px, mk);
+}
+
+template <int FAM>
+__global__ __launch_bounds__(256) void warp_col_fused_kernel(WarpArgs a) {
+    col_tile<FAM>(a, (int)blockIdx.x, [&](int gx0, int gy, const float* x, const float* y) { col_fused_emit(a, gx0, gy, x, y); });
+}
+// the compose loop's grid: PolarBatch's, with col_tiles_of tiles per frame
+template <int FAM>
+__global__ __launch_bounds__(256) void warp_col_fused_batch_kernel(PolarBatch b) {
+    const int bid = (int)blockIdx.x;
+    int fi = 0;
+#pragma unroll
+    for (int k = 1; k < WB_MAX; k++) fi += bid >= b.wg_base[k] ? 1 : 0;       // (uniform: scalar compares on the kernel arguments)
+    const WarpArgs& a = b.a[fi];
+    col_tile<FAM>(a, bid - b.wg_base[fi], [&](int gx0, int gy, const float* x, const float* y) { col_fused_emit(a, gx0, gy, x, y); });
+}
+// test aid: the kernels' map itself, (x, y) per roi pixel into a dense dw x dh x 2 float array
+template <int FAM>
+__global__ __launch_bounds__(256) void debug_col_map_kernel(WarpArgs a, float* xy) {
+    col_tile<FAM>(a, (int)blockIdx.x, [&](int gx0, int gy, const float* x, const float* y) {
+        for (int i = 0; i < PP_LPX && gx0 + i < a.dw; i++) {
+            float* o = xy + ((size_t)gy * a.dw + gx0 + i) * 2;
+            o[0] = x[i]; o[1] = y[i];
+        }
+    });
+}
+
+// General warp of the half-separable kinds: warp_polar_u8_kernel's walk (one column per lane, 4 rows per lane and column) with the
+// column terms evaluated once per column
+template <int FAM, int CN, bool LINEAR>
+__global__ __launch_bounds__(256) void warp_col_u8_kernel(WarpArgs a) {
+    const int tx0 = blockIdx.x * TILE_W, ty0 = blockIdx.y * TILE_H;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int half = 0; half < 2; half++) {
+        const int gx = tx0 + lane + 64 * half;
+        if (gx >= a.dw) continue;
+        const ColTerms ct = col_hoist<FAM>(a.scale, a.pa, a.pb, (float)(a.tlx + gx));
+        for (int i = 0; i < 4; i++) {
+            const int gy = ty0 + wave * 4 + i;
+            if (gy >= a.dh) break;
+            float x, y, sinv, cosv;
+            col_pixel<FAM>(ct, a.pb, (float)(a.tly + gy) / a.scale, &sinv, &cosv);
+            map_backward(FAM, a.m, ct.sl, ct.cl, cosv, sinv, &x, &y);
+            uint8_t* d = (uint8_t*)a.dst + (size_t)gy * a.dstride + (size_t)gx * CN;
+            if (LINEAR) {
+                int p[CN];
+                sample_linear<CN>(a.src, a.sstride, a.sw, a.sh, x, y, p);
+#pragma unroll
+                for (int c = 0; c < CN; c++) d[c] = (uint8_t)p[c];
+            } else {
+                int sx, sy;
+                bool in = nearest_inside(a.sw, a.sh, x, y, &sx, &sy);
+#pragma unroll
+                for (int c = 0; c < CN; c++) d[c] = in ? a.src[(size_t)sy * a.sstride + (size_t)sx * CN + c] : (uint8_t)0;
+            }
+        }
+    }
+}
+
 // Run-time value -> template instantiation, one helper per kernel family: `launch` is a generic lambda that takes the value as
 // std::integral_constant(s) and names the kernel with them, so only the instantiations listed here exist.
 template <int V> using int_c = std::integral_constant<int, V>;
@@ -1544,10 +1757,15 @@ template <class F> void with_polar_kind(int kind, F&& launch) {         // warp_
     if (kind == MIS_WARP_FISHEYE) launch(int_c<MIS_WARP_FISHEYE>{});
     else launch(int_c<MIS_WARP_STEREOGRAPHIC>{});
 }
+template <class F> void with_col_kind(int kind, F&& launch) {           // warp_col_fused_kernel, warp_col_fused_batch_kernel, warp_col_u8_kernel: the family
+    if (col_kind_of(kind).family == MIS_WARP_COMPRESSED_PLANE_A2B1) launch(int_c<MIS_WARP_COMPRESSED_PLANE_A2B1>{});
+    else launch(int_c<MIS_WARP_PANINI_A2B1>{});
+}
 template <class F> void with_scan_kind(int kind, F&& launch) {          // warp_roi_scan_kernel (MIS_WARP_ROI_IS_FULL_SCAN kinds)
     if (kind == MIS_WARP_MERCATOR) launch(int_c<MIS_WARP_MERCATOR>{});
     else if (kind == MIS_WARP_FISHEYE) launch(int_c<MIS_WARP_FISHEYE>{});
-    else launch(int_c<MIS_WARP_STEREOGRAPHIC>{});
+    else if (kind == MIS_WARP_STEREOGRAPHIC) launch(int_c<MIS_WARP_STEREOGRAPHIC>{});
+    else with_col_kind(kind, launch);
 }
 template <class F> void with_ztest(int kind, F&& launch) {              // warp_fused_kernel, warp_strip_batch_kernel: ZTEST = not plane
     if (kind == MIS_WARP_PLANE) launch(std::false_type{});
@@ -1585,7 +1803,7 @@ int setup(MisContext* ctx, int kind, const MisImage* src, float scale, const flo
                                          : "warp roi refused: the border projects to a non-finite extreme");
     }
     for (int i = 0; i < 9; i++) a->m[i] = p.k_rinv[i];
-    a->kind = kind;
+    a->kind = kind; a->pa = p.a; a->pb = p.b;
     a->scale = scale; a->tlx = tlx; a->tly = tly;
     MIS_CHECK(ctx, (long long)*brx - tlx + 1 <= INT_MAX && (long long)*bry - tly + 1 <= INT_MAX, MIS_E_INVALID,
               "warp roi %d..%d x %d..%d does not fit an int size", tlx, *brx, tly, *bry);
@@ -1644,10 +1862,18 @@ static int warp_u8_impl(MisContext* ctx, int kind, const MisImage* src, float sc
     a.dst = dout.data; a.dstride = dout.stride; a.mask = nullptr; a.mstride = 0;
     dim3 grid((a.dw + TILE_W - 1) / TILE_W, (a.dh + TILE_H - 1) / TILE_H), block(256);
     const bool linear = interp == MIS_INTER_LINEAR;
-    if (kind_polar(kind)) {
+    if (kind_polar(kind) || kind_col(kind)) {
         MIS_CHECK(ctx, grid.y <= 65535u, MIS_E_INVALID, "warp roi %dx%d: too many rows for one launch", a.dw, a.dh);
+    }
+    if (kind_polar(kind)) {
         with_cn_linear(src->channels, linear, [&](auto cn, auto lin) {
             hipLaunchKernelGGL((warp_polar_u8_kernel<cn.value, lin.value>), grid, block, 0, ctx->stream, a);
+        });
+    } else if (kind_col(kind)) {
+        with_col_kind(kind, [&](auto fam) {
+            with_cn_linear(src->channels, linear, [&](auto cn, auto lin) {
+                hipLaunchKernelGGL((warp_col_u8_kernel<fam.value, cn.value, lin.value>), grid, block, 0, ctx->stream, a);
+            });
         });
     } else {
         with_cn_linear(src->channels, linear, [&](auto cn, auto lin) {
@@ -1724,8 +1950,8 @@ static int warp_fused_impl(MisContext* ctx, int kind, const MisImage* src, float
     int brx, bry, rc;
     if ((rc = setup(ctx, kind, src, scale, K, R, &a, &brx, &bry, known_roi)) != MIS_OK) return rc;
     MIS_CHECK(ctx, src->channels == 3, MIS_E_UNSUPPORTED, "fused warp needs an 8UC3 source");
-    const bool polar = kind_polar(kind);
-    if (!polar && kind != MIS_WARP_SPHERICAL && !fast_z_bound_ok(a) && repeats == 1 && !avg_us) {
+    const bool polar = kind_polar(kind), col = kind_col(kind);
+    if (!polar && !col && kind != MIS_WARP_SPHERICAL && !fast_z_bound_ok(a) && repeats == 1 && !avg_us) {
         // the one-frame kernel's z guard is the spherical one: a roi this far out goes through the batch form (same results)
         const MisRect r{a.tlx, a.tly, a.dw, a.dh};
         return warp_fused_batch_impl(ctx, kind, src, 1, scale, K, R, &r, dst, dmask, tl, 1, nullptr);
@@ -1734,18 +1960,19 @@ static int warp_fused_impl(MisContext* ctx, int kind, const MisImage* src, float
     DevView din, dout, dm;
     if ((rc = fused_outputs(ctx, a, src, dst, dmask, din, dout, dm)) != MIS_OK) return rc;
     float* tab = nullptr;
-    if (!polar) {
+    if (!polar && !col) {
         // separable trig tables live in the context's grow-only scratch
         if ((rc = mis_dev_stage(ctx, sizeof(float) * trig_table_floats(a.dw, a.dh), (void**)&tab)) != MIS_OK) return rc;
         hipLaunchKernelGGL(warp_trig_kernel, dim3((trig_cols(a.dw) + a.dh + 255) / 256), dim3(256), 0, ctx->stream, a, tab);
     }
-    const unsigned nwg = polar ? (unsigned)polar_tiles_of(a) : (unsigned)grid_of(a);      // polar: area < 2^31 (setup), so are its tiles
+    const unsigned nwg = polar ? (unsigned)polar_tiles_of(a) : col ? (unsigned)col_tiles_of(a) : (unsigned)grid_of(a);      // per-pixel kinds: area < 2^31 (setup), so are its tiles
     RepeatTimer t;
     if ((rc = t.begin(ctx, avg_us)) != MIS_OK) return rc;
     // the separable kinds: round 2's tile kernel (measured faster there than the strip forms: 23.2 us against 29.3 for one-tile
     // strips and more for longer ones -- a frame alone is 3.5 tiles per wave slot, gpurun_out/r4_plan_ab3.txt)
     for (int rep = 0; rep < repeats; rep++)
         if (polar) with_polar_kind(kind, [&](auto k) { hipLaunchKernelGGL(warp_polar_fused_kernel<k.value>, dim3(nwg), dim3(256), 0, ctx->stream, a); });
+        else if (col) with_col_kind(kind, [&](auto k) { hipLaunchKernelGGL(warp_col_fused_kernel<k.value>, dim3(nwg), dim3(256), 0, ctx->stream, a); });
         else with_ztest(kind, [&](auto z) { hipLaunchKernelGGL(warp_fused_kernel<z.value>, dim3(nwg), dim3(64 * TILE_WAVES), 0, ctx->stream, a, (const float*)tab); });
     if ((rc = t.end(ctx, repeats, avg_us)) != MIS_OK) return rc;
     MIS_HIP(ctx, hipGetLastError());
@@ -1784,8 +2011,8 @@ static int grid_of(const WarpArgs& a) {
 }
 
 // The launch descriptors of a batch, WB_MAX frames per grid.
-// Polar kinds: no tables, no strips; the tiles of the frames one after the other.
-static int plan_polar_batches(MisContext* ctx, const std::vector<WarpArgs>& args, std::vector<PolarBatch>& out) {
+// Polar and half-separable kinds: no tables, no strips; the tiles of the frames (tiles_of: polar_tiles_of / col_tiles_of) one after the other.
+static int plan_polar_batches(MisContext* ctx, const std::vector<WarpArgs>& args, long long (*tiles_of)(const WarpArgs&), std::vector<PolarBatch>& out) {
     const int n = (int)args.size();
     for (int g0 = 0; g0 < n; g0 += WB_MAX) {
         const int ng = std::min(WB_MAX, n - g0);
@@ -1794,7 +2021,7 @@ static int plan_polar_batches(MisContext* ctx, const std::vector<WarpArgs>& args
         for (int k = 0; k < WB_MAX; k++) {
             b.a[k] = args[g0 + (k < ng ? k : 0)];
             b.wg_base[k] = (int)wg;
-            if (k < ng) wg += polar_tiles_of(args[g0 + k]);
+            if (k < ng) wg += tiles_of(args[g0 + k]);
             MIS_CHECK(ctx, wg <= INT_MAX, MIS_E_INVALID, "frames %d..%d: too many tiles for one launch", g0, g0 + k);
         }
         b.wg_base[WB_MAX] = (int)wg;
@@ -1865,8 +2092,9 @@ static int warp_fused_batch_impl(MisContext* ctx, int kind, const MisImage* srcs
     // the launch descriptors; the separable kinds' table launches go out here, in front of the timed region
     std::vector<PolarBatch> polar;
     std::vector<V3Batch> strips;
-    if (kind_polar(kind)) {
-        if ((rc = plan_polar_batches(ctx, args, polar)) != MIS_OK) return rc;
+    const bool col = kind_col(kind);
+    if (kind_polar(kind) || col) {
+        if ((rc = plan_polar_batches(ctx, args, col ? col_tiles_of : polar_tiles_of, polar)) != MIS_OK) return rc;
     } else {
         uint8_t* tabs = nullptr;
         if ((rc = mis_dev_stage(ctx, tab_total, (void**)&tabs)) != MIS_OK) return rc;
@@ -1876,7 +2104,8 @@ static int warp_fused_batch_impl(MisContext* ctx, int kind, const MisImage* srcs
     if ((rc = t.begin(ctx, avg_us)) != MIS_OK) return rc;
     for (int rep = 0; rep < repeats; rep++) {
         for (const PolarBatch& b : polar)
-            with_polar_kind(kind, [&](auto k) { hipLaunchKernelGGL(warp_polar_fused_batch_kernel<k.value>, dim3(b.wg_base[WB_MAX]), dim3(256), 0, ctx->stream, b); });
+            if (col) with_col_kind(kind, [&](auto k) { hipLaunchKernelGGL(warp_col_fused_batch_kernel<k.value>, dim3(b.wg_base[WB_MAX]), dim3(256), 0, ctx->stream, b); });
+            else with_polar_kind(kind, [&](auto k) { hipLaunchKernelGGL(warp_polar_fused_batch_kernel<k.value>, dim3(b.wg_base[WB_MAX]), dim3(256), 0, ctx->stream, b); });
         for (const V3Batch& vb : strips)
             with_ztest(kind, [&](auto z) { hipLaunchKernelGGL(warp_strip_batch_kernel<z.value>, dim3(vb.wg_base[WB_MAX]), dim3(64 * V3_WAVES), 0, ctx->stream, vb); });
     }
@@ -1931,7 +2160,7 @@ extern "C" int mis_warper_roi_batch(MisContext* ctx, int kind, float scale, int 
     for (int i = 0; i < n; i++) {
         projector_set(&proj[i], kind, scale, Ks + 9 * i, Rs + 9 * i);
         memcpy(jobs[i].r_kinv, proj[i].r_kinv, sizeof(jobs[i].r_kinv));
-        jobs[i].scale = scale; jobs[i].sw = w; jobs[i].sh = h; jobs[i].kind = kind; jobs[i].behind = 0;
+        jobs[i].scale = scale; jobs[i].a = proj[i].a; jobs[i].b = proj[i].b; jobs[i].sw = w; jobs[i].sh = h; jobs[i].kind = kind; jobs[i].behind = 0;
     }
     float4* part = (float4*)((uint8_t*)ctx->roi_pinned + part_off);
     if (scan) with_scan_kind(kind, [&](auto k) {
@@ -2000,6 +2229,39 @@ extern "C" int mis_debug_math_f32(MisContext* ctx, int fn, const float* in, floa
     hipLaunchKernelGGL(debug_math_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, fn, (const float*)d, d + n, n);
     MIS_HIP(ctx, hipGetLastError());
     MIS_HIP(ctx, hipMemcpyAsync(out, d + n, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    MIS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return MIS_OK;
+}
+
+// test aid: mapBackward of a half-separable kind for every pixel of `roi` -> xy[(row * roi->width + col) * 2 + {0, 1}] (host array).
+// ctx NULL: the unsplit sequence (map_backward_col) per pixel on the host; with a context: the kernels' tile walk with its hoisted
+// column terms (col_tile), whose every float must equal the host's.
+extern "C" int mis_debug_warper_map_f32(MisContext* ctx, int kind, float scale, const float K[9], const float R[9], const MisRect* roi, float* xy) {
+    const ColKind ck = col_kind_of(kind);
+    if (!ck.family) return MIS_E_UNSUPPORTED;
+    if (!K || !R || !roi || !xy || !(scale > 0.f) || roi->width < 1 || roi->height < 1 || (long long)roi->width * roi->height > (1 << 24)) return MIS_E_INVALID;
+    Projector p;
+    projector_set(&p, kind, scale, K, R);
+    if (!ctx) {
+        for (int r = 0; r < roi->height; r++)
+            for (int c = 0; c < roi->width; c++) {
+                float* o = xy + ((size_t)r * roi->width + c) * 2;
+                map_backward_col(ck.family, p.k_rinv, scale, ck.a, ck.b, (float)(roi->x + c), (float)(roi->y + r), &o[0], &o[1]);
+            }
+        return MIS_OK;
+    }
+    MIS_HIP(ctx, hipSetDevice(ctx->device));
+    WarpArgs a = {};
+    for (int i = 0; i < 9; i++) a.m[i] = p.k_rinv[i];
+    a.kind = kind; a.pa = ck.a; a.pb = ck.b; a.scale = scale;
+    a.tlx = roi->x; a.tly = roi->y; a.dw = roi->width; a.dh = roi->height;
+    const size_t bytes = sizeof(float) * 2 * (size_t)a.dw * a.dh;
+    float* d = nullptr;
+    int rc;
+    if ((rc = mis_dev_stage(ctx, bytes, (void**)&d)) != MIS_OK) return rc;
+    with_col_kind(kind, [&](auto k) { hipLaunchKernelGGL(debug_col_map_kernel<k.value>, dim3((unsigned)col_tiles_of(a)), dim3(256), 0, ctx->stream, a, d); });
+    MIS_HIP(ctx, hipGetLastError());
+    MIS_HIP(ctx, hipMemcpyAsync(xy, d, bytes, hipMemcpyDeviceToHost, ctx->stream));
     MIS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return MIS_OK;
 }

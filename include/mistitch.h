@@ -43,13 +43,19 @@ enum { MIS_BORDER_CONSTANT = 0, MIS_BORDER_REFLECT = 2 };       /* cv::BORDER_CO
 /* the warper kinds of the reference's GPU branch (warp_type, image_stitching.cpp:917-969), its Mercator warper (:961-962) and its
  * fisheye (:941-942) and stereographic (:943-944) warpers; the float maps are those of OpenCV's Spherical / Cylindrical / Plane (T = 0) /
  * Mercator / Fisheye / Stereographic projectors, CPU path.  The first four have a separable backward ray (column and row tables, no
- * transcendental per pixel); the fisheye and stereographic maps are polar and are evaluated per output pixel. */
-enum { MIS_WARP_SPHERICAL = 0, MIS_WARP_CYLINDRICAL = 1, MIS_WARP_PLANE = 2, MIS_WARP_MERCATOR = 3, MIS_WARP_FISHEYE = 4, MIS_WARP_STEREOGRAPHIC = 5 };
+ * transcendental per pixel); the fisheye and stereographic maps are polar and are evaluated per output pixel.
+ * Kinds 8 .. 11: the compressed-rectilinear (:945-948) and Panini (:953-956) warpers, one kind per (A, B) setting the reference offers
+ * (the entries have no slot for the two parameters).  Their backward map is half separable: the horizontal angle depends on the
+ * column only, the vertical one on the pixel.  Kinds 6 and 7 are not assigned. */
+enum { MIS_WARP_SPHERICAL = 0, MIS_WARP_CYLINDRICAL = 1, MIS_WARP_PLANE = 2, MIS_WARP_MERCATOR = 3, MIS_WARP_FISHEYE = 4, MIS_WARP_STEREOGRAPHIC = 5,
+       MIS_WARP_COMPRESSED_PLANE_A2B1 = 8, MIS_WARP_COMPRESSED_PLANE_A15B1 = 9, MIS_WARP_PANINI_A2B1 = 10, MIS_WARP_PANINI_A15B1 = 11 };
 /* the kinds the library builds: every entry that takes a kind answers MIS_E_UNSUPPORTED ("unknown warp kind") for any other value */
-#define MIS_WARP_KIND_IS_KNOWN(kind) ((kind) >= MIS_WARP_SPHERICAL && (kind) <= MIS_WARP_STEREOGRAPHIC)
+#define MIS_WARP_KIND_IS_KNOWN(kind) (((kind) >= MIS_WARP_SPHERICAL && (kind) <= MIS_WARP_STEREOGRAPHIC) || \
+                                      ((kind) >= MIS_WARP_COMPRESSED_PLANE_A2B1 && (kind) <= MIS_WARP_PANINI_A15B1))
 /* the kinds whose warper has no detectResultRoi of its own: RotationWarperBase::detectResultRoi projects EVERY source pixel forward.
  * For these mis_warper_roi is O(width * height) on the host and mis_warper_roi_batch a grid-wide reduction on the device. */
-#define MIS_WARP_ROI_IS_FULL_SCAN(kind) ((kind) >= MIS_WARP_MERCATOR && (kind) <= MIS_WARP_STEREOGRAPHIC)
+#define MIS_WARP_ROI_IS_FULL_SCAN(kind) (((kind) >= MIS_WARP_MERCATOR && (kind) <= MIS_WARP_STEREOGRAPHIC) || \
+                                        ((kind) >= MIS_WARP_COMPRESSED_PLANE_A2B1 && (kind) <= MIS_WARP_PANINI_A15B1))
 enum { MIS_BLEND_NO = 0, MIS_BLEND_FEATHER = 1, MIS_BLEND_MULTI_BAND = 2 }; /* cv::detail::Blender::NO/FEATHER/MULTI_BAND */
 
 typedef struct MisContext MisContext;
@@ -298,8 +304,9 @@ int mis_warp_spherical_fused_timed(MisContext* ctx, const MisImage* src_bgr, flo
 /* warper->warpRoi(sz, K, R) -- replaces :1138.  Plane: the four corners (PlaneWarper::detectResultRoi); cylindrical: the border.
  * Mercator: cv::MercatorWarper has no detectResultRoi of its own, so RotationWarperBase projects EVERY source pixel forward and
  * takes the four extremes; this context-free entry does the same in a plain host loop and is O(width * height) for that kind (a
- * 4K frame: 8.3 M projections).  mis_warper_roi_batch and every entry with a context run that scan on the device.  Fisheye and
- * stereographic: the same (MIS_WARP_ROI_IS_FULL_SCAN). */
+ * 4K frame: 8.3 M projections).  mis_warper_roi_batch and every entry with a context run that scan on the device.  Fisheye,
+ * stereographic, compressed-plane and Panini: the same (MIS_WARP_ROI_IS_FULL_SCAN).  A compressed-plane frame with a ray at
+ * u_ = +-90 degrees (1 / cosf(u_) infinite) is MIS_E_INVALID like the Mercator pole. */
 int mis_warper_roi(int kind, float scale, int src_width, int src_height, const float K[9], const float R[9], MisRect* roi);
 /* the warpRoi loop of :1119-1140 in one call (one small kernel; the same rois as mis_warper_roi; the message names a refused frame).
  * Mercator, fisheye, stereographic: one grid-wide reduction over all pixels of all n frames, still one launch and one stream
@@ -314,7 +321,8 @@ int mis_warper_warp(MisContext* ctx, int kind, const MisImage* src, float scale,
 int mis_warper_warp_roi(MisContext* ctx, int kind, const MisImage* src, float scale, const float K[9], const float R[9], const MisRect* roi,
                         int interp, int border, MisImage* dst, MisPoint* tl);
 /* fused compose-scale warp -- replaces :1154 + :1157-1159 + :1164.  (Fisheye and stereographic: mapBackward per output pixel,
- * atan2 / sqrt / atan / two sincos, in a kernel of its own; the same contract and the same sampling.) */
+ * atan2 / sqrt / atan / two sincos, in a kernel of its own; the same contract and the same sampling.  Compressed-plane and Panini:
+ * the column terms once per column and tile, an atan and a sincos per pixel, in a kernel of their own.) */
 int mis_warper_warp_fused(MisContext* ctx, int kind, const MisImage* src_bgr, float scale, const float K[9], const float R[9],
                           MisImage* dst_s16x3, MisImage* dst_mask, MisPoint* tl);
 /* the same with the roi mis_warper_roi gave for these parameters (:1138 then :1154) */
@@ -327,6 +335,11 @@ int mis_warper_warp_fused_batch(MisContext* ctx, int kind, const MisImage* srcs_
  * one-thread-per-element kernel on the context's stream (in / out are host arrays either way).  fn: MIS_MATH_*. */
 enum { MIS_MATH_LOG = 0, MIS_MATH_TAN = 1, MIS_MATH_SINH = 2, MIS_MATH_ASIN = 3, MIS_MATH_ATAN = 4, MIS_MATH_EXP = 5 };
 int mis_debug_math_f32(MisContext* ctx_or_null, int fn, const float* in, float* out, int n);
+/* test aid: mapBackward of a compressed-plane / Panini kind for every pixel of roi (at most 2^24 pixels) -> the source coordinates
+ * xy[(row * roi->width + column) * 2 + {0, 1}] (a host array).  ctx NULL: the reference's operation sequence, unsplit, per pixel on
+ * the host; with a context: the warp kernels' tile walk, which evaluates the column terms once per column.  The two must agree in
+ * every bit.  Another kind: MIS_E_UNSUPPORTED. */
+int mis_debug_warper_map_f32(MisContext* ctx_or_null, int kind, float scale, const float K[9], const float R[9], const MisRect* roi, float* xy);
 
 /* ---------------------------------------------------------------- SIFT ---------------------- */
 /* SIFT::create() -- replaces image_stitching/image_stitching.cpp:559 (features_type == "sift").  Defaults of the
