@@ -125,6 +125,7 @@ PROTOTYPES = {
     "mis_orb_on_enqueued": (_i, [_vp, _vp, _vp]),
     "mis_orb_arm_knn_ahead": (_i, [_vp, _i, _vp, _i, _i, _i]),
     "mis_debug_knn_ahead_adopted": (C.c_longlong, [_vp]),
+    "mis_debug_knn_ahead": (_i, [_vp, _P(MisFeatures), _i, _P(_i), _vp, _i, _i, _i]),
     "mis_features_download": (_i, [_vp, _P(MisFeatures), _vp, _vp]),
     "mis_features_upload": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _i, _P(MisFeatures)]),
     "mis_features_free": (_i, [_vp, _P(MisFeatures)]),

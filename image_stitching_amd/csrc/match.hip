@@ -1355,6 +1355,29 @@ extern "C" long long mis_debug_knn_ahead_adopted(MisContext* ctx) {
     return ctx->match_ws ? static_cast<MatchWorkspace*>(ctx->match_ws)->ahead_adopted : 0;
 }
 
+// test aid: what mis_orb_detect_batch does behind its gather, for uploaded blocks -- frame i's count goes into its block's count
+// slot on the context's stream, the pass is enqueued from the capacities (feats[i].n on entry) and those slots, and the structs
+// get their counts and are confirmed.  Whatever mis_knn_ahead_enqueue declines is MIS_OK here too, as it is for the finder.
+extern "C" int mis_debug_knn_ahead(MisContext* ctx, MisFeatures* feats, int n, const int* counts, const uint8_t* mask, int range_width, int rank, int world) {
+    if (!ctx || !feats || !counts || n < 1) return MIS_E_INVALID;
+    for (int i = 0; i < n; i++)
+        MIS_CHECK(ctx, feats[i].owner_ && feats[i].n >= 0 && counts[i] >= 0 && counts[i] <= feats[i].n, MIS_E_INVALID, "frame %d: count %d outside 0 .. capacity %d", i, counts[i], feats[i].n);
+    MIS_HIP(ctx, hipSetDevice(ctx->device));
+    mis_knn_ahead_drop(ctx, nullptr);
+    std::vector<int> caps(n);
+    std::vector<int*> slots(n);
+    for (int i = 0; i < n; i++) {
+        caps[i] = feats[i].n;
+        slots[i] = caps[i] ? mis_feat_count(&feats[i], caps[i]) : nullptr;      // (an empty set: the pass is declined below)
+        if (slots[i]) MIS_HIP(ctx, hipMemsetD32Async((hipDeviceptr_t)slots[i], counts[i], 1, ctx->stream));
+    }
+    const int rc = mis_knn_ahead_enqueue(ctx, feats, n, caps.data(), slots.data(), mask, range_width, rank, world);
+    if (rc != MIS_OK) { mis_knn_ahead_drop(ctx, nullptr); return rc; }
+    for (int i = 0; i < n; i++) feats[i].n = counts[i];
+    mis_knn_ahead_confirm(ctx, feats, n);
+    return MIS_OK;
+}
+
 // One-shot hook of this context's NEXT matcher call: fn(user) runs on the calling thread of mis_match_all_pairs /
 // mis_match_pairs_sharded / mis_match_pairs_select once all of the call's device work is enqueued, before the call waits for the device.
 extern "C" int mis_match_on_enqueued(MisContext* ctx, void (*fn)(void*), void* user) {

@@ -231,6 +231,14 @@ int mis_match_knn_fence(MisContext* ctx, void* stream, long long target_seq, int
 int mis_match_on_enqueued(MisContext* ctx, void (*fn)(void*), void* user);
 /* diagnostics: the number of this context's matcher calls that adopted a 2-NN pass enqueued ahead (mis_orb_arm_knn_ahead) */
 long long mis_debug_knn_ahead_adopted(MisContext* ctx);
+/* test aid: the 2-NN pass enqueued ahead, with counts of the caller's choice.  feats[i] is a set made by mis_features_upload whose
+ * n is its block's capacity (all of its rows are uploaded); counts[i], 0 .. that capacity, is written into the block's device
+ * count slot on the context's stream, the pass is enqueued from the capacities and those slots with this selection (mask,
+ * range_width, rank, world: as in mis_orb_arm_knn_ahead), feats[i].n becomes counts[i] and the pass is confirmed -- what
+ * mis_orb_detect_batch does behind its gather.  The caller then hands the same structs to a matcher entry.  MIS_E_INVALID: a
+ * null pointer, a count below 0 or above its capacity; where the finder would enqueue nothing, so does this, and returns MIS_OK. */
+int mis_debug_knn_ahead(MisContext* ctx, MisFeatures* feats, int n, const int* counts, const uint8_t* mask, int range_width, int rank,
+                        int world);
 /* exact 2-NN (distance, trainIdx) for one direction; results in host memory (stage test hook) */
 int mis_knn2(MisContext* ctx, const MisFeatures* query, const MisFeatures* train, int* idx2_host, float* dist2_host);
 /* cv::findHomography(src, dst, mask, RANSAC, thresh, max_iters, confidence) on host point lists */

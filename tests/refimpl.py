@@ -273,9 +273,15 @@ def _knn2_from_dist(d, nt):
     dd = np.full((n, 2), -1, np.int64)
     if nt == 0:
         return idx, dd
-    order = np.argsort(d, axis=1, kind="stable")[:, :2]
-    idx[:, : order.shape[1]] = order
-    dd[:, : order.shape[1]] = np.take_along_axis(d, order, 1)
+    # (the first two of a stable sort, without the sort: argmin returns the first of equal minima)
+    rows = np.arange(n)
+    idx[:, 0] = np.argmin(d, axis=1)
+    dd[:, 0] = d[rows, idx[:, 0]]
+    if nt >= 2:
+        rest = np.array(d, np.int64)
+        rest[rows, idx[:, 0]] = np.iinfo(np.int64).max
+        idx[:, 1] = np.argmin(rest, axis=1)
+        dd[:, 1] = rest[rows, idx[:, 1]]
     return idx, dd
 
 
@@ -287,8 +293,11 @@ def knn2_hamming_exact(q, t, chunk=256):
     nq, nt = q.shape[0], t.shape[0]
     idx = np.full((nq, 2), -1, np.int64)
     dist = np.full((nq, 2), -1, np.int64)
+    words = np.ascontiguousarray(t.T)            # word by word: a (chunk, nt) block at a time, not (chunk, nt, 4)
     for a in range(0, nq, chunk):
-        d = np.bitwise_count(q[a:a + chunk, None, :] ^ t[None, :, :]).sum(-1, dtype=np.int64)
+        d = np.zeros((min(chunk, nq - a), nt), np.int64)
+        for w in range(4):
+            d += np.bitwise_count(q[a:a + chunk, w, None] ^ words[w][None, :])
         idx[a:a + chunk], dist[a:a + chunk] = _knn2_from_dist(d, nt)
     return idx.astype(np.int32), dist
 

@@ -71,14 +71,19 @@ def hamming_edge_sets(rng, nq, nt):
     return q, t
 
 
+def _keypoints(n, i=0, size=(640, 480)):
+    """_upload's keypoint recipe: n seeded positions inside the frame (shared with test_knn_ahead_edges_gpu.py)"""
+    from image_stitching_amd.stitching import KP_DTYPE
+    rng = np.random.default_rng(n + 7 * i)
+    k = np.zeros(n, KP_DTYPE)
+    k["x"] = rng.uniform(0, size[0], n)
+    k["y"] = rng.uniform(0, size[1], n)
+    return k
+
+
 def _upload(ctx, d, i=0, size=(640, 480)):
     import image_stitching_amd as isa
-    from image_stitching_amd.stitching import KP_DTYPE
-    rng = np.random.default_rng(len(d) + 7 * i)
-    k = np.zeros(len(d), KP_DTYPE)
-    k["x"] = rng.uniform(0, size[0], len(d))
-    k["y"] = rng.uniform(0, size[1], len(d))
-    return isa.ImageFeatures.upload(ctx, size, k, d, i)
+    return isa.ImageFeatures.upload(ctx, size, _keypoints(len(d), i, size), d, i)
 
 
 def _knn2(ctx, q, t):
