@@ -80,8 +80,8 @@ StitchResult Stitcher::stitch(const std::vector<HostImage>& frames, const std::v
     const double work_scale = wg.scale;
     double t = now();
     if (cfg_.features_type != "orb" && cfg_.features_type != "sift") throw std::runtime_error("Unknown 2D features type: '" + cfg_.features_type + "'.");
-    if (cfg_.ba_cost_func != "no" && cfg_.ba_cost_func != "reproj")
-        throw std::runtime_error("bundle adjustment cost function '" + cfg_.ba_cost_func + "' is not implemented (only 'no' and 'reproj')");
+    if (cfg_.ba_cost_func != "no" && cfg_.ba_cost_func != "reproj" && cfg_.ba_cost_func != "ray")
+        throw std::runtime_error("bundle adjustment cost function '" + cfg_.ba_cost_func + "' is not implemented ('no', 'reproj' and 'ray' are)");
     const int expos_kind = expos_comp_kind(cfg_.expos_comp_type, cfg_.expos_comp_nr_feeds);
     if (cfg_.seam_find_type != "no" && cfg_.seam_find_type != "voronoi" && cfg_.seam_find_type != "dp_color")
         throw std::runtime_error("seam finder '" + cfg_.seam_find_type + "' is not implemented ('no', 'voronoi' and 'dp_color' are)");
@@ -126,8 +126,8 @@ StitchResult Stitcher::stitch(const std::vector<HostImage>& frames, const std::v
     int kept = 0;
     mis_leave_biggest_component(pairwise.data(), n, cfg_.conf_thresh, out.indices.data(), &kept);
     out.indices.resize(kept);
-    // ---- camera refinement on the kept subset (:671-726): bundle adjustment (reprojection cost), wave correction ----
-    if (kept >= 2 && cfg_.ba_cost_func == "reproj") {
+    // ---- camera refinement on the kept subset (:671-726): bundle adjustment (reprojection or ray cost), wave correction ----
+    if (kept >= 2 && cfg_.ba_cost_func != "no") {
         std::vector<MisFeatures> fsub(kept);
         std::vector<MisMatchesInfo> psub((size_t)kept * kept);
         std::vector<MisCameraParams> cp(kept);
@@ -143,7 +143,9 @@ StitchResult Stitcher::stitch(const std::vector<HostImage>& frames, const std::v
             std::copy(c.R.m.begin(), c.R.m.end(), cp[a].R);
             std::copy(c.t.begin(), c.t.end(), cp[a].t);
         }
-        if (mis_bundle_adjust_reproj(ctx_, fsub.data(), psub.data(), kept, cfg_.conf_thresh, cfg_.ba_refine_mask.c_str(), cp.data()) != MIS_OK)
+        const int ba_rc = cfg_.ba_cost_func == "ray" ? mis_bundle_adjust_ray(ctx_, fsub.data(), psub.data(), kept, cfg_.conf_thresh, cp.data())
+                                                     : mis_bundle_adjust_reproj(ctx_, fsub.data(), psub.data(), kept, cfg_.conf_thresh, cfg_.ba_refine_mask.c_str(), cp.data());
+        if (ba_rc != MIS_OK)
             throw std::runtime_error(std::string("Camera parameters adjusting failed: ") + mis_last_error(ctx_));
         if (cfg_.wave_correct != "no") {
             std::vector<double> rm((size_t)kept * 9);

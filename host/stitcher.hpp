@@ -24,7 +24,7 @@ struct StitchConfig {
     float blend_strength = 5;
     std::string features_type = "orb";     // "orb" | "sift" (:543-563)
     // camera refinement (:681-726).  The reference's default is "reproj"; "no" keeps the supplied (sensor) cameras.
-    std::string ba_cost_func = "no";       // "no" | "reproj"
+    std::string ba_cost_func = "no";       // "no" | "reproj" | "ray"
     std::string ba_refine_mask = "_____";  // the reference's default: rotations only
     std::string wave_correct = "horiz";    // "horiz" | "vert" | "no"; applied after the bundle adjustment only
     // seam-scale step (:940-1070, :1162-1171).  The reference's defaults are "gain_blocks" and "dp_color" (both implemented:

@@ -153,6 +153,7 @@ PROTOTYPES = {
     "mis_leave_biggest_component": (_i, [_P(MisMatchesInfo), _i, _f, _vp, _P(_i)]),
     "mis_leave_biggest_component_conf": (_i, [_vp, _i, _f, _vp, _P(_i)]),
     "mis_bundle_adjust_reproj": (_i, [_vp, _P(MisFeatures), _P(MisMatchesInfo), _i, _f, C.c_char_p, _P(MisCameraParams)]),
+    "mis_bundle_adjust_ray": (_i, [_vp, _P(MisFeatures), _P(MisMatchesInfo), _i, _f, _P(MisCameraParams)]),
     "mis_wave_correct": (_i, [_vp, _i, _i]),
     "mis_warp_roi": (_i, [_f, _i, _i, _vp, _vp, _P(MisRect)]),
     "mis_warp_spherical": (_i, [_vp, _P(MisImage), _f, _vp, _vp, _i, _i, _P(MisImage), _P(MisPoint)]),

@@ -463,6 +463,7 @@ class StitchJob:
         self.kind = st.check_warp_config(self.cfg)
         st.check_range_config(self.cfg)
         st.check_matcher_config(self.cfg)
+        st.check_ba_config(self.cfg)
         self.engine = engine or HipEngine(ctx, frame_size, self.cfg)
         # an engine warps one kind (its own config's; spherical when it does not say): never another than the job's
         engine_warp = getattr(self.engine, "warp_type", "spherical")
@@ -847,8 +848,7 @@ class StitchJob:
             pm, conf = self.stage_match(feats)
             indices = self.stage_prune(conf)
             if refine:
-                if self.cfg.ba_cost_func != "reproj":
-                    raise ValueError("ba_cost_func must be 'no' or 'reproj'")
+                st.check_ba_config(self.cfg)
                 if self.world > 1 or self.force_collectives:
                     # the adjuster needs every connected pair's inlier matches, and the pairs were dealt over the ranks: every
                     # rank contributes the entries it owns, all ranks assemble the same table and run the same (host) solver

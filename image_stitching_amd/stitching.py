@@ -1156,8 +1156,12 @@ def refine_cameras(ctx, features, pairwise_matches, indices, cameras, cfg):
     view._owner = pairwise_matches              # the match arrays belong to the full table
     start = [dict(focal=float(cameras[i]["K"][0, 0]), aspect=float(cameras[i]["K"][1, 1] / cameras[i]["K"][0, 0]), ppx=float(cameras[i]["K"][0, 2]),
                   ppy=float(cameras[i]["K"][1, 2]), R=cameras[i]["R"]) for i in indices]
+    cost_func = check_ba_config(cfg)
     try:
-        refined = bundle_adjust_reproj(ctx, [features[i] for i in indices], view, start, cfg.conf_thresh, cfg.ba_refine_mask)
+        if cost_func == "ray":
+            refined = bundle_adjust_ray(ctx, [features[i] for i in indices], view, start, cfg.conf_thresh)
+        else:
+            refined = bundle_adjust_reproj(ctx, [features[i] for i in indices], view, start, cfg.conf_thresh, cfg.ba_refine_mask)
     finally:
         view._mis = None                        # borrowed entries: nothing to free
     if cfg.wave_correct != "no":
@@ -1174,6 +1178,55 @@ def refine_cameras(ctx, features, pairwise_matches, indices, cameras, cfg):
     return out
 
 
+BA_COST_FUNCS = ("no", "reproj", "ray")
+
+
+def check_ba_config(cfg):
+    """ba_cost_func of the config: one of BA_COST_FUNCS; "affine" (BundleAdjusterAffinePartial, image_stitching.cpp:685) raises
+    NotImplementedError by name, any other name ValueError (the reference's "Unknown bundle adjustment cost function", :687-690),
+    before any device work."""
+    name = cfg.ba_cost_func
+    if name in BA_COST_FUNCS:
+        return name
+    if name == "affine":
+        raise NotImplementedError("ba_cost_func 'affine': BundleAdjusterAffinePartial is not built, only %s (DESIGN.md section 8)"
+                                  % ", ".join(repr(k) for k in BA_COST_FUNCS))
+    raise ValueError("ba_cost_func %r: not a cost function the reference knows (image_stitching.cpp:680-693)" % (name,))
+
+
+def _camera_array(cameras, n):
+    cams = (capi.MisCameraParams * n)()
+    for k, c in enumerate(cameras):
+        cams[k].focal, cams[k].aspect, cams[k].ppx, cams[k].ppy = float(c["focal"]), float(c.get("aspect", 1.0)), float(c["ppx"]), float(c["ppy"])
+        R = np.asarray(c["R"], np.float64).reshape(9)
+        t = np.asarray(c.get("t", np.zeros(3)), np.float64).reshape(3)
+        for i in range(9):
+            cams[k].R[i] = R[i]
+        for i in range(3):
+            cams[k].t[i] = t[i]
+    return cams
+
+
+def _camera_dicts(cams, n):
+    return [dict(focal=cams[k].focal, aspect=cams[k].aspect, ppx=cams[k].ppx, ppy=cams[k].ppy, R=np.array(list(cams[k].R)).reshape(3, 3),
+                 t=np.array(list(cams[k].t))) for k in range(n)]
+
+
+def bundle_adjust_ray(ctx, features, pairwise_matches, cameras, conf_thresh=0.95):
+    """(*makePtr<detail::BundleAdjusterRay>())(features, pairwise_matches, cameras) with setConfThresh
+    (image_stitching.cpp:683-684): focal and rotation of every camera refined on the rays of the inlier matches, evaluated on the
+    device; ppx, ppy, aspect and t come back as given.  cameras and the result as in bundle_adjust_reproj."""
+    n = len(features)
+    if not isinstance(pairwise_matches, PairwiseMatches):
+        raise TypeError("pairwise_matches must be the PairwiseMatches object a BestOf2NearestMatcher call returned")
+    arr = (capi.MisFeatures * n)()
+    for k, f in enumerate(features):
+        C.memmove(C.byref(arr[k]), C.byref(f.raw), C.sizeof(capi.MisFeatures))
+    cams = _camera_array(cameras, n)
+    ctx.check(ctx.lib.mis_bundle_adjust_ray(ctx.h, arr, pairwise_matches._mis, n, float(conf_thresh), cams))
+    return _camera_dicts(cams, n)
+
+
 def bundle_adjust_reproj(ctx, features, pairwise_matches, cameras, conf_thresh=0.95, refine_mask="xxxxx"):
     """(*makePtr<detail::BundleAdjusterReproj>())(features, pairwise_matches, cameras) with setConfThresh /
     setRefinementMask (image_stitching.cpp:681-712).  cameras: list of dicts with focal, ppx, ppy, R (3x3) and
@@ -1184,18 +1237,9 @@ def bundle_adjust_reproj(ctx, features, pairwise_matches, cameras, conf_thresh=0
     arr = (capi.MisFeatures * n)()
     for k, f in enumerate(features):
         C.memmove(C.byref(arr[k]), C.byref(f.raw), C.sizeof(capi.MisFeatures))
-    cams = (capi.MisCameraParams * n)()
-    for k, c in enumerate(cameras):
-        cams[k].focal, cams[k].aspect, cams[k].ppx, cams[k].ppy = float(c["focal"]), float(c.get("aspect", 1.0)), float(c["ppx"]), float(c["ppy"])
-        R = np.asarray(c["R"], np.float64).reshape(9)
-        t = np.asarray(c.get("t", np.zeros(3)), np.float64).reshape(3)
-        for i in range(9):
-            cams[k].R[i] = R[i]
-        for i in range(3):
-            cams[k].t[i] = t[i]
+    cams = _camera_array(cameras, n)
     ctx.check(ctx.lib.mis_bundle_adjust_reproj(ctx.h, arr, pairwise_matches._mis, n, float(conf_thresh), refine_mask.encode(), cams))
-    return [dict(focal=cams[k].focal, aspect=cams[k].aspect, ppx=cams[k].ppx, ppy=cams[k].ppy, R=np.array(list(cams[k].R)).reshape(3, 3),
-                 t=np.array(list(cams[k].t))) for k in range(n)]
+    return _camera_dicts(cams, n)
 
 
 def wave_correct(rmats, kind=WAVE_CORRECT_HORIZ):
@@ -1362,8 +1406,8 @@ class StitchConfig:
     blend_strength: float = 5.0
     # camera refinement between matching and warping (image_stitching.cpp:681-726).  The reference's default is
     # "reproj"; here the default is "no" because the jobs of this package take exact (sensor / ground-truth) cameras.
-    ba_cost_func: str = "no"          # "no" | "reproj"
-    ba_refine_mask: str = "_____"     # the reference's default (image_stitching.cpp:67): rotations only
+    ba_cost_func: str = "no"          # "no" | "reproj" | "ray" (BundleAdjusterRay, :683-684: focal + rotation, evaluated on the device; "affine" raises by name, check_ba_config)
+    ba_refine_mask: str = "_____"     # the reference's default (image_stitching.cpp:67): rotations only; read by "reproj" alone
     wave_correct: str = "horiz"       # "horiz" | "vert" | "no"; applied after the bundle adjustment only
     # the seam-scale step between warp and blend (image_stitching.cpp:940-1070, :1162-1171), the reference's defaults
     # (:73-77): block gain compensation and the dynamic-programming colour seam finder
@@ -1372,6 +1416,9 @@ class StitchConfig:
     expos_comp_block_size: int = 64
     expos_comp_nr_filtering: int = 2
     seam_find_type: str = "dp_color"       # "no" | "voronoi" | "dp_color"
+
+    def __post_init__(self):
+        check_ba_config(self)
 
     @classmethod
     def reference(cls, **kw):

@@ -267,6 +267,15 @@ typedef struct {
  * ba_refine_mask string ("xxxxx"); the rotations are normalised to the centre of the maximum spanning tree. */
 int mis_bundle_adjust_reproj(MisContext* ctx, const MisFeatures* features, const MisMatchesInfo* pairwise, int n, float conf_thresh,
                              const char* refine_mask, MisCameraParams* cameras);
+/* (*adjuster)(features, pairwise_matches, cameras) with makePtr<detail::BundleAdjusterRay>(), setConfThresh -- replaces
+ * image_stitching.cpp:683-684 (ba_cost_func = "ray").  Levenberg-Marquardt over 4 parameters per camera (focal, rotation vector)
+ * on the rays of the inlier correspondences of the pairs above conf_thresh: 3 errors per correspondence, sqrt(f_i f_j) times the
+ * difference of the two unit rays, K taken from the features' image sizes.  No refinement mask; ppx, ppy, aspect and t come back
+ * as given.  The solver is host logic; the errors, the central-difference Jacobian (step 1e-3) and the per-pair sums of the
+ * normal equations are evaluated by kernels on the context's stream, reading the keypoints in the features' device arrays.  The
+ * match indices are validated on the host first.  The rotations are normalised to the centre of the maximum spanning tree. */
+int mis_bundle_adjust_ray(MisContext* ctx, const MisFeatures* features, const MisMatchesInfo* pairwise, int n, float conf_thresh,
+                          MisCameraParams* cameras);
 /* waveCorrect(rmats, wave_correct) -- replaces image_stitching.cpp:718-726; rmats: n x 9 doubles in place; kind 0 = HORIZ, 1 = VERT */
 int mis_wave_correct(double* rmats, int n, int kind);
 
