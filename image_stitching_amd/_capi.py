@@ -31,6 +31,12 @@ def roi_is_full_scan(kind):
 
 
 MATH_LOG, MATH_TAN, MATH_SINH, MATH_ASIN, MATH_ATAN, MATH_EXP = 0, 1, 2, 3, 4, 5     # mis_debug_math_f32
+# mis_debug_math: name -> (MIS_MATHX_* code, dtype of a, dtype of b or None, dtype of out)
+MATHX = {"sin": (0, "f4", None, "f4"), "cos": (1, "f4", None, "f4"), "acos": (2, "f4", None, "f4"), "sqrt": (3, "f4", None, "f4"),
+         "rcp": (4, "f4", None, "f4"), "atan2": (5, "f4", "f4", "f4"), "fast_atan2": (6, "f4", "f4", "f4"), "div": (7, "f4", "f4", "f4"),
+         "round_f": (8, "f4", None, "i4"), "round_sat_f": (9, "f4", None, "i4"), "floor_f": (10, "f4", None, "i4"),
+         "sat_short": (11, "i4", None, "i4"), "reflect101": (12, "i4", "i4", "i4"), "reflect": (13, "i4", "i4", "i4"),
+         "reflect1": (14, "i4", "i4", "i4"), "log_d": (15, "f8", None, "f8"), "round_d": (16, "f8", None, "i4")}
 MATCH_HOMOGRAPHY, MATCH_AFFINE_PARTIAL = 0, 1
 EXPOS_NO, EXPOS_GAIN, EXPOS_GAIN_BLOCKS, EXPOS_CHANNELS, EXPOS_CHANNELS_BLOCKS = 0, 1, 2, 3, 4      # cv::detail::ExposureCompensator's values
 
@@ -163,7 +169,8 @@ PROTOTYPES = {
     "mis_warp_spherical_fused_batch_timed": (_i, [_vp, _P(MisImage), _i, C.c_float, _P(C.c_float), _P(C.c_float), _P(MisRect), _P(MisImage), _P(MisImage), _P(MisPoint), _i,
                                                _P(C.c_float)]),
     "mis_debug_math_f32": (_i, [_vp, _i, _vp, _vp, _i]),
-    "mis_debug_warper_map_f32": (_i, [_vp, _i, _f, _vp, _vp, _P(MisRect), _vp]),
+    "mis_debug_math": (_i, [_vp, _i, _vp, _vp, _vp, _i]),
+    "mis_debug_warper_map_f32":(_i, [_vp, _i, _f, _vp, _vp, _P(MisRect), _vp]),
     "mis_warper_roi": (_i, [_i, _f, _i, _i, _vp, _vp, _P(MisRect)]),
     "mis_warper_roi_batch": (_i, [_vp, _i, _f, _i, _i, _i, _vp, _vp, _P(MisRect)]),
     "mis_warper_warp": (_i, [_vp, _i, _P(MisImage), _f, _vp, _vp, _i, _i, _P(MisImage), _P(MisPoint)]),

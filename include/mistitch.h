@@ -352,6 +352,21 @@ int mis_warper_warp_fused_batch(MisContext* ctx, int kind, const MisImage* srcs_
  * one-thread-per-element kernel on the context's stream (in / out are host arrays either way).  fn: MIS_MATH_*. */
 enum { MIS_MATH_LOG = 0, MIS_MATH_TAN = 1, MIS_MATH_SINH = 2, MIS_MATH_ASIN = 3, MIS_MATH_ATAN = 4, MIS_MATH_EXP = 5 };
 int mis_debug_math_f32(MisContext* ctx_or_null, int fn, const float* in, float* out, int n);
+/* test aid: out[i] = f(a[i]) or f(a[i], b[i]) for every other function of dev_math.h and for the raw float32 sqrtf(x), 1.0f / x and
+ * a / b, evaluated as mis_debug_math_f32 evaluates: on the host (ctx NULL) or in a one-thread-per-element kernel on the context's
+ * stream (at most 2^20 elements per call then); a, b and out are host arrays.  The element types follow fn:
+ *   SIN .. RCP                float -> float           (b unused; sin and cos through mis_sincosf)
+ *   ATAN2, FAST_ATAN2, DIV    (float a, float b) -> float:  atan2(y = a, x = b), fastAtan2(y = a, x = b), a / b
+ *   ROUND_F .. FLOOR_F        float -> int
+ *   SAT_SHORT                 int -> int
+ *   REFLECT101 .. REFLECT1    (int p = a, int len = b) -> int
+ *   LOG_D                     double -> double
+ *   ROUND_D                   double -> int */
+enum { MIS_MATHX_SIN = 0, MIS_MATHX_COS = 1, MIS_MATHX_ACOS = 2, MIS_MATHX_SQRT = 3, MIS_MATHX_RCP = 4, MIS_MATHX_ATAN2 = 5,
+       MIS_MATHX_FAST_ATAN2 = 6, MIS_MATHX_DIV = 7, MIS_MATHX_ROUND_F = 8, MIS_MATHX_ROUND_SAT_F = 9, MIS_MATHX_FLOOR_F = 10,
+       MIS_MATHX_SAT_SHORT = 11, MIS_MATHX_REFLECT101 = 12, MIS_MATHX_REFLECT = 13, MIS_MATHX_REFLECT1 = 14, MIS_MATHX_LOG_D = 15,
+       MIS_MATHX_ROUND_D = 16 };
+int mis_debug_math(MisContext* ctx_or_null, int fn, const void* a, const void* b_or_null, void* out, int n);
 /* test aid: mapBackward of a compressed-plane / Panini kind for every pixel of roi (at most 2^24 pixels) -> the source coordinates
  * xy[(row * roi->width + column) * 2 + {0, 1}] (a host array).  ctx NULL: the reference's operation sequence, unsplit, per pixel on
  * the host; with a context: the warp kernels' tile walk, which evaluates the column terms once per column.  The two must agree in

@@ -11,7 +11,7 @@ band delta(x, y) of the float64 value (at most 2 per axis, 4 per pixel) and the 
 Error model of the float32 map (the band delta; stated once, not tuned to the tests), first order in every error:
   * angles theta = u / scale and phi = pi - v / scale: float32 roundings of the quotient and the difference plus the float32
     pi:  e_theta = 2^-24 |theta|,  e_phi = 2^-24 (|v / scale| + |phi|) + 8.8e-8.
-  * sin / cos: the 3e-7 absolute error pinned by test_oracle_kat.py::test_trig_polynomials per evaluation, so the unit ray
+  * sin / cos: the 3e-7 absolute error pinned by test_dev_math_cpu.py (the library's own functions) per evaluation, so the unit ray
     r = (sin phi sin theta, cos phi, sin phi cos theta) has component errors 3e-7 (|sin phi| + |sin theta|), 3e-7,
     3e-7 (|sin phi| + |cos theta|), plus 2^-24 |r_i| for the product, plus the angle errors through dr/dtheta, dr/dphi.
   * x = (m0 . r) / (m2 . r), m = K R^-1 rounded to float32: the ray errors propagate through the exact derivative
@@ -31,8 +31,8 @@ import math
 import numpy as np
 
 U24 = 2.0 ** -24
-TRIG_ERR = 3e-7          # test_oracle_kat.py::test_trig_polynomials (sin / cos)
-INV_TRIG_ERR = 1e-6      # test_oracle_kat.py::test_trig_polynomials (acos, atan2)
+TRIG_ERR = 3e-7          # test_dev_math_cpu.py::test_trig_err_is_tied_to_the_library (the library's mis_sinf / mis_cosf)
+INV_TRIG_ERR = 1e-6      # test_dev_math_cpu.py::test_inv_trig_err_is_tied_to_the_library (mis_acosf, mis_atan2f)
 PI_F32_ERR = 8.8e-8      # |pi - float32(pi)|
 PI_F32 = float(np.float32(math.pi))
 

@@ -49,7 +49,7 @@ Error model of the float32 quantities (the bands; derived once here, not tuned t
     polynomial is within u (7 + 9 + 8 + 3) T, and the up to three reflections 90 - a, 180 - a, 360 - a add u 360 each:
     band_angle = u (27 T + 1080) <= 2.1e-4 degrees.  The moments are exact in float32 (|m| < 2^24, asserted).
   * rotated sample coordinates x cos - y sin: the angle band (in radians, times the radius |(x, y)| <= 28.3), the degree ->
-    radian product (2 u |rad|), sin / cos (3e-7 absolute each, pinned by test_oracle_kat.py::test_trig_polynomials), two
+    radian product (2 u |rad|), sin / cos (3e-7 absolute each, pinned by test_dev_math_cpu.py on the library's functions), two
     products and a difference (u each): band = |(x, y)| band_rad + (|x| + |y|) (3e-7 + 2 u |rad|) + u (|x c| + |y s|) + u |x'|.
     A bit whose four rounded coordinates include one within its band of a .5 boundary is undetermined; every other bit is
     compared exactly.
@@ -61,7 +61,7 @@ import numpy as np
 BORDER = 32
 MAX_LEVEL_FEATURES = 1920       # the library's per-level budget limit (include/mistitch.h)
 U24 = 2.0 ** -24
-TRIG_ERR = 3e-7                 # test_oracle_kat.py::test_trig_polynomials (sin / cos)
+TRIG_ERR = 3e-7                 # test_dev_math_cpu.py::test_trig_err_is_tied_to_the_library (the library's mis_sinf / mis_cosf)
 F32 = np.float32
 KP_DTYPE = np.dtype([("x", "f4"), ("y", "f4"), ("size", "f4"), ("angle", "f4"), ("response", "f4"), ("octave", "i4")])
 

@@ -57,7 +57,7 @@ tested side's float32 deviation from it):
     denominator bands, then (dN + |x| dD) / |D|), its value comes from numpy.linalg.solve.  Exact operations (times a power of two,
     integer plus float with a representable sum excepted: that one rounds) add nothing.
   * the shared exponential polynomial: 2e-7 relative (test_oracle_kat.py::test_sift_helpers); sin / cos 3e-7 absolute
-    (test_trig_polynomials); fastAtan2: refimpl_orb.fast_atan2_f64's band u (27 T + 1080) degrees; sqrt: u relative.
+    (test_dev_math_cpu.py, which also holds mis_expf to the 2e-7); fastAtan2: refimpl_orb.fast_atan2_f64's band u (27 T + 1080) degrees; sqrt: u relative.
   * a branch on a banded quantity is DECIDED when its margin exceeds the band (or the band is 0: exact data, e.g. flat plateaus),
     otherwise the candidate (or the keypoint's orientation) is UNDECIDED, the reason recorded: `singular` (|det H| within its
     band), `converge` (an |offset| within its band of 0.5), `overflow`, `round` (an offset within its band of a half-integer
