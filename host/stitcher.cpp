@@ -83,8 +83,8 @@ StitchResult Stitcher::stitch(const std::vector<HostImage>& frames, const std::v
     if (cfg_.ba_cost_func != "no" && cfg_.ba_cost_func != "reproj" && cfg_.ba_cost_func != "ray")
         throw std::runtime_error("bundle adjustment cost function '" + cfg_.ba_cost_func + "' is not implemented ('no', 'reproj' and 'ray' are)");
     const int expos_kind = expos_comp_kind(cfg_.expos_comp_type, cfg_.expos_comp_nr_feeds);
-    if (cfg_.seam_find_type != "no" && cfg_.seam_find_type != "voronoi" && cfg_.seam_find_type != "dp_color")
-        throw std::runtime_error("seam finder '" + cfg_.seam_find_type + "' is not implemented ('no', 'voronoi' and 'dp_color' are)");
+    if (cfg_.seam_find_type != "no" && cfg_.seam_find_type != "voronoi" && cfg_.seam_find_type != "dp_color" && cfg_.seam_find_type != "dp_colorgrad")
+        throw std::runtime_error("seam finder '" + cfg_.seam_find_type + "' is not implemented ('no', 'voronoi', 'dp_color' and 'dp_colorgrad' are)");
     const int kind = warp_kind(cfg_.warp_type);
     check_range_width(cfg_.range_width);
     const int model = matcher_model(cfg_.matcher_type, cfg_.range_width);
@@ -251,6 +251,8 @@ StitchResult Stitcher::stitch(const std::vector<HostImage>& frames, const std::v
         if (cfg_.seam_find_type == "voronoi") check(mis_seam_voronoi(ctx_, seam_corners.data(), masks_warped.data(), kept), "mis_seam_voronoi");
         else if (cfg_.seam_find_type == "dp_color")      // the reference's default (image_stitching.cpp:77, :1056-1065)
             check(mis_seam_dp(ctx_, seam_corners.data(), images_warped.data(), masks_warped.data(), kept, MIS_SEAM_DP_COLOR), "mis_seam_dp");
+        else if (cfg_.seam_find_type == "dp_colorgrad")  // DpSeamFinder(COLOR_GRAD) (:1057-1058)
+            check(mis_seam_dp_colorgrad(ctx_, seam_corners.data(), images_warped.data(), masks_warped.data(), kept), "mis_seam_dp_colorgrad");
         for (auto& im : images_warped) mis_image_free(ctx_, &im);
     }
     for (int k = 0; k < kept; k++) {

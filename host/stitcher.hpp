@@ -28,11 +28,11 @@ struct StitchConfig {
     std::string ba_refine_mask = "_____";  // the reference's default: rotations only
     std::string wave_correct = "horiz";    // "horiz" | "vert" | "no"; applied after the bundle adjustment only
     // seam-scale step (:940-1070, :1162-1171).  The reference's defaults are "gain_blocks" and "dp_color" (both implemented:
-    // mis_compensator_*, mis_seam_dp); this struct defaults to the HOT PATH of the north star (no seam-scale step), like
+    // mis_compensator_*, mis_seam_dp; "dp_colorgrad" is mis_seam_dp_colorgrad); this struct defaults to the HOT PATH of the north star (no seam-scale step), like
     // image_stitching_amd.StitchConfig.hot_path() -- pass "gain_blocks" / "dp_color" for the reference's configuration.
     std::string expos_comp_type = "no";    // "no" | "gain" | "gain_blocks" | "channels" | "channels_blocks" (:73; 64 x 64 blocks, 2 filtering passes)
     int expos_comp_nr_feeds = 1;           // :74
-    std::string seam_find_type = "no";     // "no" | "voronoi" | "dp_color" (the reference's default; this driver's default is the hot path)
+    std::string seam_find_type = "no";     // "no" | "voronoi" | "dp_color" | "dp_colorgrad" (dp_color: the reference's default; this driver's default is the hot path)
     // warper (:917-969): the three of the reference's GPU branch and its Mercator, fisheye, stereographic, compressed-plane and Panini
     // warpers are built; its other names (the portrait variants, transverseMercator, affine) throw by name (warp_kind)
     std::string warp_type = "spherical";   // "spherical" | "cylindrical" | "plane" | "mercator" | "fisheye" | "stereographic" | "compressedPlaneA2B1" | "compressedPlaneA1.5B1" | "paniniA2B1" | "paniniA1.5B1"

@@ -15,7 +15,7 @@ from .stitching import (AffineBestOf2NearestMatcher, BestOf2NearestMatcher, Best
                         MisError, MultiBandBlender, OrbFeatureFinder, SiftFeatureFinder, SphericalWarper, CylindricalWarper, PlaneWarper, MercatorWarper, FisheyeWarper, StereographicWarper, CompressedRectilinearWarper, PaniniWarper,
                         RotationWarper, StitchConfig, Stitcher,
                         blend_config, bundle_adjust_ray, bundle_adjust_reproj, computeImageFeatures, find_homography, leaveBiggestComponent, resize, resize_batch, result_roi,
-                        rotate, seam_mask_apply, selected_pairs, warp_roi, wave_correct, work_geometry)
+                        rotate, seam_gradients, seam_mask_apply, selected_pairs, warp_roi, wave_correct, work_geometry)
 
 __all__ = [
     "Context", "MisError", "SphericalWarper", "Blender", "MultiBandBlender", "FeatherBlender", "OrbFeatureFinder", "SiftFeatureFinder",
@@ -25,5 +25,5 @@ __all__ = [
     "INTER_NEAREST", "INTER_LINEAR", "BORDER_CONSTANT", "BORDER_REFLECT", "BLEND_NO", "BLEND_FEATHER",
     "BLEND_MULTI_BAND", "resize_batch", "work_geometry", "CylindricalWarper", "PlaneWarper", "RotationWarper", "WARP_SPHERICAL", "WARP_CYLINDRICAL", "WARP_PLANE", "WARP_MERCATOR", "MercatorWarper", "WARP_FISHEYE", "WARP_STEREOGRAPHIC", "FisheyeWarper", "StereographicWarper",
     "WARP_COMPRESSED_PLANE_A2B1", "WARP_COMPRESSED_PLANE_A15B1", "WARP_PANINI_A2B1", "WARP_PANINI_A15B1", "CompressedRectilinearWarper", "PaniniWarper",
-    "BestOf2NearestRangeMatcher", "selected_pairs", "AffineBestOf2NearestMatcher", "estimate_affine_partial",
+    "BestOf2NearestRangeMatcher", "selected_pairs", "AffineBestOf2NearestMatcher", "estimate_affine_partial", "seam_gradients",
 ]

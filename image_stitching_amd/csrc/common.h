@@ -67,7 +67,12 @@ int mis_knn_ahead_enqueue(MisContext* ctx, const MisFeatures* feats, int n, cons
 void mis_knn_ahead_confirm(MisContext* ctx, const MisFeatures* feats, int n);
 void mis_knn_ahead_drop(MisContext* ctx, const void* owner);
 
-#define MIS_HIP(ctx, call)                                                                             \
+// DpSeamFinder::computeGradients of n 8UC3 device frames in one launch on ctx's stream (seam_grad.hip): gx / gy are f32 planes of
+// the frame's size on the device, strides in bytes (the planes' multiples of 4).  Nothing is checked here: the entries do.
+struct MisSeamGradJob { const uint8_t* src; size_t ss; float* gx; size_t gxs; float* gy; size_t gys; int w, h; };
+int mis_seam_grad_enqueue(MisContext* ctx, const MisSeamGradJob* jobs, int n);
+
+#define MIS_HIP(ctx, call)                                                                           \
     do {                                                                                               \
         hipError_t e_ = (call);                                                                        \
         if (e_ != hipSuccess)                                                                          \

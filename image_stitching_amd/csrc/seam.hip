@@ -9,6 +9,9 @@
 // tests/test_refimpl_seam_dp_cpu.py).  NOT PINNED: the order of pairs at equal centre distance (mis_seam_dp below).
 // No kernels: the data is two ~420 x 240 images per pair and the algorithm is sequential (labelling, dynamic programming along
 // a seam, flood fills); images and masks are copied to the host, the masks go back to the device.
+// DpSeamFinder(COLOR_GRAD) ("dp_colorgrad", :1057-1058) is the same finder with another cost (compute_costs) behind an entry of
+// its own, mis_seam_dp_colorgrad: its per-image pass, DpSeamFinder::computeGradients, is the kernel of seam_grad.hip, launched once
+// for all frames on the gathered device block; pinned to tests/refimpl_seam_dp_grad.py (tests/test_seam_dp_grad_gpu.py).
 #include "common.h"
 #include "dev_math.h"
 #include <algorithm>
@@ -44,6 +47,11 @@ struct HostImage {   // CV_32FC3 view of a seam-scale image (the reference conve
     int w = 0, h = 0;
     std::vector<float> px;   // 3 floats per pixel
     const float* at(int y, int x) const { return &px[((size_t)y * w + x) * 3]; }
+    // COLOR_GRAD: the image's two Sobel planes (DpSeamFinder::computeGradients; made on the device, seam_grad.hip), w floats a row
+    const float* gradx = nullptr;
+    const float* grady = nullptr;
+    float gx(int y, int x) const { return gradx[(size_t)y * w + x]; }
+    float gy(int y, int x) const { return grady[(size_t)y * w + x]; }
 };
 
 // cv::floodFill(image, seed, newVal) on a 32-bit integer image: 4-connected, the region of pixels equal to the seed's value
@@ -89,6 +97,7 @@ struct DpPair {
     std::vector<Pt> tls, brs;
     std::vector<std::vector<Pt>> contours;
     std::set<std::pair<int, int>> edges;
+    bool color_grad = false;     // costFunc_ == COLOR_GRAD (set by process)
 
     bool on_border(int y, int x, int l) const {
         return (x == 0 || labels(y, x - 1) != l) || (x == uw - 1 || labels(y, x + 1) != l) || (y == 0 || labels(y - 1, x) != l) || (y == uh - 1 || labels(y + 1, x) != l);
@@ -242,26 +251,31 @@ struct DpPair {
     // OpenCV reads labels_(y, x) for x == roi.br().x / y == roi.br().y, one past the component's box (possibly one past the
     // union): here anything outside the union counts as "not this component" (the bad-region cost).  Settled: estimate_seam never
     // reads column rw of costV or row rh of costH, so that line reaches no result (tests/refimpl_seam_dp.py).
+    // COLOR_GRAD (color_grad): the colour cost over 1 + the four absolute derivatives across the cut, both images' pixels on
+    // either side of it -- gradx for costV, grady for costH; a float32 sum from left to right (tests/refimpl_seam_dp_grad.py).
     void compute_costs(const HostImage& im1, const HostImage& im2, Pt tl1, Pt tl2, int comp, Grid<float>& costV, Grid<float>& costH) const {
         const int l = comp + 1;
         const int rx = tls[comp].x, ry = tls[comp].y, rw = brs[comp].x - rx, rh = brs[comp].y - ry;
         const int dx1 = union_tl.x - tl1.x, dy1 = union_tl.y - tl1.y, dx2 = union_tl.x - tl2.x, dy2 = union_tl.y - tl2.y;
         const float bad = 3.f * 255.f * 255.f;   // normL2(Point3f(255, 255, 255), Point3f(0, 0, 0)): the squared norm
+        const bool grad = color_grad;
         auto lab = [&](int y, int x) { return (x >= 0 && x < uw && y >= 0 && y < uh) ? labels(y, x) : 0; };
         costV.create(rw + 1, rh);
         for (int y = ry; y < ry + rh; y++)
             for (int x = rx; x < rx + rw + 1; x++) {
-                if (lab(y, x) == l && x > 0 && lab(y, x - 1) == l)
-                    costV(y - ry, x - rx) = (diff(im1, y + dy1, x + dx1 - 1, im2, y + dy2, x + dx2) + diff(im1, y + dy1, x + dx1, im2, y + dy2, x + dx2 - 1)) / 2;
-                else
+                if (lab(y, x) == l && x > 0 && lab(y, x - 1) == l) {
+                    const float c = (diff(im1, y + dy1, x + dx1 - 1, im2, y + dy2, x + dx2) + diff(im1, y + dy1, x + dx1, im2, y + dy2, x + dx2 - 1)) / 2;
+                    costV(y - ry, x - rx) = !grad ? c : c / ((((std::fabs(im1.gx(y + dy1, x + dx1)) + std::fabs(im1.gx(y + dy1, x + dx1 - 1))) + std::fabs(im2.gx(y + dy2, x + dx2))) + std::fabs(im2.gx(y + dy2, x + dx2 - 1))) + 1.f);
+                } else
                     costV(y - ry, x - rx) = bad;
             }
         costH.create(rw, rh + 1);
         for (int y = ry; y < ry + rh + 1; y++)
             for (int x = rx; x < rx + rw; x++) {
-                if (lab(y, x) == l && y > 0 && lab(y - 1, x) == l)
-                    costH(y - ry, x - rx) = (diff(im1, y + dy1 - 1, x + dx1, im2, y + dy2, x + dx2) + diff(im1, y + dy1, x + dx1, im2, y + dy2 - 1, x + dx2)) / 2;
-                else
+                if (lab(y, x) == l && y > 0 && lab(y - 1, x) == l) {
+                    const float c = (diff(im1, y + dy1 - 1, x + dx1, im2, y + dy2, x + dx2) + diff(im1, y + dy1, x + dx1, im2, y + dy2 - 1, x + dx2)) / 2;
+                    costH(y - ry, x - rx) = !grad ? c : c / ((((std::fabs(im1.gy(y + dy1, x + dx1)) + std::fabs(im1.gy(y + dy1 - 1, x + dx1))) + std::fabs(im2.gy(y + dy2, x + dx2))) + std::fabs(im2.gy(y + dy2 - 1, x + dx2))) + 1.f);
+                } else
                     costH(y - ry, x - rx) = bad;
             }
     }
@@ -464,7 +478,8 @@ struct DpPair {
     }
 
     // DpSeamFinder::process
-    void process(const HostImage& im1, const HostImage& im2, Pt tl1, Pt tl2, Grid<uint8_t>& m1, Grid<uint8_t>& m2) {
+    void process(const HostImage& im1, const HostImage& im2, Pt tl1, Pt tl2, Grid<uint8_t>& m1, Grid<uint8_t>& m2, bool grad) {
+        color_grad = grad;
         const Pt itl{std::max(tl1.x, tl2.x), std::max(tl1.y, tl2.y)};
         const Pt ibr{std::min(tl1.x + im1.w, tl2.x + im2.w), std::min(tl1.y + im1.h, tl2.y + im2.h)};
         if (itl.x >= ibr.x || itl.y >= ibr.y) return;   // no overlap: no conflicts
@@ -494,15 +509,12 @@ struct DpPair {
     }
 };
 
-}  // namespace
-
 // DpSeamFinder::find: every pair of images, the most distant centres first.
 // NOT PINNED: the reference orders the pairs with std::sort (unspecified for equal keys) + std::reverse; pairs at equal distance are
 // ordered here as a stable sort + reverse leaves them (tie_order="reversed" of tests/refimpl_seam_dp.py, which states both readings).
-extern "C" int mis_seam_dp(MisContext* ctx, const MisPoint* corners, const MisImage* images, MisImage* masks, int n, int cost_func) {
-    if (!ctx) return MIS_E_INVALID;
-    MIS_CHECK(ctx, corners && images && masks && n >= 0, MIS_E_INVALID, "null argument");
-    MIS_CHECK(ctx, cost_func == MIS_SEAM_DP_COLOR, MIS_E_UNSUPPORTED, "DpSeamFinder: only the COLOR cost (the reference's \"dp_color\") is implemented");
+// grad: the COLOR_GRAD cost.  Every image is then in the device block (host images are uploaded into their slots), the gradient
+// kernel runs on the block and its planes come over behind the images and masks in the same copy.
+int seam_dp_find(MisContext* ctx, const MisPoint* corners, const MisImage* images, MisImage* masks, int n, bool grad) {
     if (n == 0) return MIS_OK;
     MIS_HIP(ctx, hipSetDevice(ctx->device));
     if (getenv("MIS_SEAM_TRACE")) { const auto t_e = std::chrono::steady_clock::now(); hipStreamSynchronize(ctx->stream); fprintf(stderr, "dp seams: entry sync %.2f ms\n", std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t_e).count() / 1e3); }
@@ -521,11 +533,19 @@ extern "C" int mis_seam_dp(MisContext* ctx, const MisPoint* corners, const MisIm
         ioff[i] = stage_total; stage_total += mis_align_up((size_t)I.width * I.height * 3, 256);
         moff[i] = stage_total; stage_total += mis_align_up((size_t)M.width * M.height, 256);
     }
+    const size_t back_total = stage_total;      // what travels back with the masks: the gradient planes lie behind it
+    std::vector<size_t> gxoff((size_t)n), gyoff((size_t)n);
+    if (grad)
+        for (int i = 0; i < n; i++) {
+            const size_t plane = mis_align_up((size_t)images[i].width * images[i].height * sizeof(float), 256);
+            gxoff[i] = stage_total; stage_total += plane;
+            gyoff[i] = stage_total; stage_total += plane;
+        }
     uint8_t* stage = nullptr;
     { void* sp = nullptr; int rc = mis_host_stage(ctx, stage_total, &sp); if (rc != MIS_OK) return rc; stage = (uint8_t*)sp; }
     // device inputs are gathered into one device block first (device-to-device copies are cheap launches) and cross the bus in ONE
     // copy: 3 n separate device-to-host copies of ~0.1 MB took 1 ms each on the stream of a second context, 31 of the finder's 52 ms
-    bool any_dev = false;
+    bool any_dev = grad;
     for (int i = 0; i < n; i++) any_dev |= images[i].mem == MIS_MEM_DEVICE || masks[i].mem == MIS_MEM_DEVICE;
     void* dblk = nullptr; size_t dgot = 0;
     if (any_dev) { int rc = mis_pool_alloc(ctx, stage_total, &dblk, &dgot); if (rc != MIS_OK) return rc; }
@@ -543,7 +563,15 @@ extern "C" int mis_seam_dp(MisContext* ctx, const MisPoint* corners, const MisIm
         const MisImage& I = images[i];
         const MisImage& M = masks[i];
         if (I.mem == MIS_MEM_DEVICE) SEAM_HIP(hipMemcpy2DAsync(dstage + ioff[i], (size_t)I.width * 3, I.data, I.stride, (size_t)I.width * 3, I.height, hipMemcpyDeviceToDevice, ctx->stream));
+        else if (grad) SEAM_HIP(hipMemcpy2DAsync(dstage + ioff[i], (size_t)I.width * 3, I.data, I.stride, (size_t)I.width * 3, I.height, hipMemcpyHostToDevice, ctx->stream));
         if (M.mem == MIS_MEM_DEVICE) SEAM_HIP(hipMemcpy2DAsync(dstage + moff[i], M.width, M.data, M.stride, M.width, M.height, hipMemcpyDeviceToDevice, ctx->stream));
+    }
+    if (grad) {     // DpSeamFinder::computeGradients, once per frame instead of twice per pair: one launch on the gathered block
+        std::vector<MisSeamGradJob> jobs((size_t)n);
+        for (int i = 0; i < n; i++)
+            jobs[i] = MisSeamGradJob{dstage + ioff[i], (size_t)images[i].width * 3, (float*)(dstage + gxoff[i]), (size_t)images[i].width * sizeof(float),
+                                     (float*)(dstage + gyoff[i]), (size_t)images[i].width * sizeof(float), images[i].width, images[i].height};
+        if (int rc = mis_seam_grad_enqueue(ctx, jobs.data(), n)) { hipStreamSynchronize(ctx->stream); mis_pool_free(ctx, dblk, dgot); return rc; }
     }
     if (any_dev) SEAM_HIP(hipMemcpyAsync(stage, dstage, stage_total, hipMemcpyDeviceToHost, ctx->stream));
     const auto t_issued = std::chrono::steady_clock::now();
@@ -552,7 +580,7 @@ extern "C" int mis_seam_dp(MisContext* ctx, const MisPoint* corners, const MisIm
     for (int i = 0; i < n; i++) {   // host inputs go into their slots of the staging buffer directly
         const MisImage& I = images[i];
         const MisImage& M = masks[i];
-        if (I.mem != MIS_MEM_DEVICE) for (int y = 0; y < I.height; y++) memcpy(stage + ioff[i] + (size_t)y * I.width * 3, (const uint8_t*)I.data + (size_t)y * I.stride, (size_t)I.width * 3);
+        if (I.mem != MIS_MEM_DEVICE && !grad) for (int y = 0; y < I.height; y++) memcpy(stage + ioff[i] + (size_t)y * I.width * 3, (const uint8_t*)I.data + (size_t)y * I.stride, (size_t)I.width * 3);
         if (M.mem != MIS_MEM_DEVICE) for (int y = 0; y < M.height; y++) memcpy(stage + moff[i] + (size_t)y * M.width, (const uint8_t*)M.data + (size_t)y * M.stride, M.width);
     }
     for (int i = 0; i < n; i++) {
@@ -562,6 +590,7 @@ extern "C" int mis_seam_dp(MisContext* ctx, const MisPoint* corners, const MisIm
         im[i].px.resize(np3);
         const uint8_t* sp = stage + ioff[i];
         for (size_t k = 0; k < np3; k++) im[i].px[k] = (float)sp[k];     // convertTo(CV_32F), image_stitching.cpp:992-994
+        if (grad) { im[i].gradx = (const float*)(stage + gxoff[i]); im[i].grady = (const float*)(stage + gyoff[i]); }    // (read in place: the pinned staging is this call's)
         mk[i].w = I.width; mk[i].h = I.height;
         mk[i].v.assign(stage + moff[i], stage + moff[i] + (size_t)I.width * I.height);
     }
@@ -595,7 +624,7 @@ extern "C" int mis_seam_dp(MisContext* ctx, const MisPoint* corners, const MisIm
     const unsigned hw = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
     auto run_pair = [&](const PairD& p) {
         static thread_local DpPair dp;      // its grids keep their capacity from pair to pair
-        dp.process(im[p.i], im[p.j], Pt{corners[p.i].x, corners[p.i].y}, Pt{corners[p.j].x, corners[p.j].y}, mk[p.i], mk[p.j]);
+        dp.process(im[p.i], im[p.j], Pt{corners[p.i].x, corners[p.i].y}, Pt{corners[p.j].x, corners[p.j].y}, mk[p.i], mk[p.j], grad);
     };
     for (int lv = 1; lv <= nlevels; lv++) {
         std::vector<size_t> ids;
@@ -615,7 +644,9 @@ extern "C" int mis_seam_dp(MisContext* ctx, const MisPoint* corners, const MisIm
         else for (int y = 0; y < M.height; y++) memcpy((uint8_t*)M.data + (size_t)y * M.stride, mk[i].v.data() + (size_t)y * M.width, M.width);
     }
     if (any_dev) {
-        SEAM_HIP(hipMemcpyAsync(dstage, stage, stage_total, hipMemcpyHostToDevice, ctx->stream));   // (the image slots travel back unused: one copy)
+        bool dev_mask = false;      // (COLOR_GRAD on host buffers holds the block for its gradients only)
+        for (int i = 0; i < n; i++) dev_mask |= masks[i].mem == MIS_MEM_DEVICE;
+        if (dev_mask) SEAM_HIP(hipMemcpyAsync(dstage, stage, back_total, hipMemcpyHostToDevice, ctx->stream));   // (the image slots travel back unused: one copy)
         for (int i = 0; i < n; i++) {
             const MisImage& M = masks[i];
             if (M.mem == MIS_MEM_DEVICE) SEAM_HIP(hipMemcpy2DAsync(M.data, M.stride, dstage + moff[i], M.width, M.width, M.height, hipMemcpyDeviceToDevice, ctx->stream));
@@ -633,4 +664,19 @@ extern "C" int mis_seam_dp(MisContext* ctx, const MisPoint* corners, const MisIm
         for (auto& v : g_seam_ns) v = 0;
     }
     return MIS_OK;
+}
+
+}  // namespace
+
+extern "C" int mis_seam_dp(MisContext* ctx, const MisPoint* corners, const MisImage* images, MisImage* masks, int n, int cost_func) {
+    if (!ctx) return MIS_E_INVALID;
+    MIS_CHECK(ctx, corners && images && masks && n >= 0, MIS_E_INVALID, "null argument");
+    MIS_CHECK(ctx, cost_func == MIS_SEAM_DP_COLOR, MIS_E_UNSUPPORTED, "DpSeamFinder: this entry runs the COLOR cost (the reference's \"dp_color\") only; COLOR_GRAD is mis_seam_dp_colorgrad");
+    return seam_dp_find(ctx, corners, images, masks, n, false);
+}
+
+extern "C" int mis_seam_dp_colorgrad(MisContext* ctx, const MisPoint* corners, const MisImage* images, MisImage* masks, int n) {
+    if (!ctx) return MIS_E_INVALID;
+    MIS_CHECK(ctx, corners && images && masks && n >= 0, MIS_E_INVALID, "null argument");
+    return seam_dp_find(ctx, corners, images, masks, n, true);
 }

@@ -156,6 +156,7 @@ class HipEngine:
         self.kind = st.check_warp_config(self.cfg)
         self.range_width = st.check_range_config(self.cfg)      # the pair selection this engine's matcher makes (StitchJob checks it against the job's)
         self.matcher_type = st.check_matcher_config(self.cfg)   # the matcher's motion model (StitchJob checks it against the job's)
+        self.seam_find_types = st.SEAM_FIND_TYPES               # the seam finders seam_global runs (StitchJob checks the job's against them)
         self.frame_size = frame_size
         # features come from the work image (image_stitching.cpp:589-603, :613): the finder is sized for it, and the work frames
         # live in buffers allocated on first use and kept (an allocation per run would synchronise the device)
@@ -478,6 +479,11 @@ class StitchJob:
         engine_matcher = getattr(self.engine, "matcher_type", "homography")
         if engine_matcher != self.cfg.matcher_type:
             raise NotImplementedError("matcher_type %r: the engine %s matches with matcher_type %r only" % (self.cfg.matcher_type, type(self.engine).__name__, engine_matcher))
+        # seam_find_type (:77, :1029-1062): the engine's seam_global runs the finder; an engine that does not declare its finders
+        # runs "no", "voronoi" and "dp_color", and is refused for any other -- never run with another finder in its place
+        engine_seams = getattr(self.engine, "seam_find_types", ("no", "voronoi", "dp_color"))
+        if self.cfg.seam_find_type not in engine_seams:
+            raise NotImplementedError("seam_find_type %r: the engine %s finds seams with %s only" % (self.cfg.seam_find_type, type(self.engine).__name__, ", ".join(map(repr, engine_seams))))
         # work scale (image_stitching.cpp:589-603): the engine detects on resized frames and everything between features and
         # composition is in work units; an engine that does not resize is refused, not run at full resolution
         self.work_scale, self.work_size = st.work_geometry(self.cfg, frame_size)

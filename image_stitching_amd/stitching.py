@@ -545,11 +545,20 @@ class VoronoiSeamFinder:
 
 
 class DpSeamFinder:
-    """seam_find_type "dp_color" -- the reference's default (image_stitching.cpp:77, :1056-1057, :1065): DpSeamFinder(COLOR).
-    images: the seam-scale warped 8UC3 images; masks are edited in place."""
+    """seam_find_type "dp_color" -- the reference's default (image_stitching.cpp:77, :1056-1057, :1065): DpSeamFinder(COLOR) --
+    and "dp_colorgrad" (:1057-1058): DpSeamFinder(COLOR_GRAD), whose cut costs are divided by the images' Sobel derivatives
+    (one kernel launch for all frames, csrc/seam_grad.hip).  images: the seam-scale warped 8UC3 images; masks are edited in place.
+    cost_func: DpSeamFinder.COLOR (0), or a name as OpenCV 4's DpSeamFinder(String costFunc) takes it: "COLOR" | "COLOR_GRAD".
+    An integer goes to mis_seam_dp as it is (which runs COLOR only); COLOR_GRAD runs mis_seam_dp_colorgrad."""
     COLOR = 0
+    COLOR_GRAD = "COLOR_GRAD"
 
     def __init__(self, ctx, cost_func=0):
+        if isinstance(cost_func, str):
+            if cost_func not in ("COLOR", "COLOR_GRAD"):
+                raise ValueError("DpSeamFinder cost function %r: 'COLOR' or 'COLOR_GRAD'" % (cost_func,))
+            if cost_func == "COLOR":
+                cost_func = DpSeamFinder.COLOR
         self.ctx, self.cost_func = ctx, cost_func
 
     def find(self, images, corners, masks):
@@ -557,8 +566,34 @@ class DpSeamFinder:
         cs = (capi.MisPoint * n)(*[capi.MisPoint(int(c[0]), int(c[1])) for c in corners])
         im = (capi.MisImage * n)(*[as_image(i) for i in images])
         mk = (capi.MisImage * n)(*[as_image(m) for m in masks])
-        self.ctx.check(self.ctx.lib.mis_seam_dp(self.ctx.h, cs, im, mk, n, int(self.cost_func)))
+        if self.cost_func == DpSeamFinder.COLOR_GRAD:
+            self.ctx.check(self.ctx.lib.mis_seam_dp_colorgrad(self.ctx.h, cs, im, mk, n))
+        else:
+            self.ctx.check(self.ctx.lib.mis_seam_dp(self.ctx.h, cs, im, mk, n, int(self.cost_func)))
         return masks
+
+
+def seam_gradients(ctx, images, gradx=None, grady=None):
+    """DpSeamFinder::computeGradients of every image in one launch (mis_seam_gradients): BGR -> grey, then the 3 x 3 Sobel
+    derivatives along x and y (BORDER_REFLECT_101) -> (gradx, grady), lists of float32 planes.  images: 8UC3 device tensors or
+    host arrays; a plane is allocated where its image lives (a device tensor or a numpy array) unless gradx / grady give the
+    buffers to fill."""
+    n = len(images)
+
+    def planes(given):
+        if given is not None:
+            return list(given)
+        return [torch.empty(tuple(i.shape[:2]), dtype=torch.float32, device=i.device) if torch is not None and isinstance(i, torch.Tensor)
+                else np.empty(np.asarray(i).shape[:2], np.float32) for i in images]
+    gx, gy = planes(gradx), planes(grady)
+    if len(gx) != n or len(gy) != n:
+        raise ValueError("seam_gradients: %d images, %d gradx and %d grady planes" % (n, len(gx), len(gy)))
+    k = max(n, 1)
+    im = (capi.MisImage * k)(*[as_image(i) for i in images])
+    ax = (capi.MisImage * k)(*[as_image(g) for g in gx])
+    ay = (capi.MisImage * k)(*[as_image(g) for g in gy])
+    ctx.check(ctx.lib.mis_seam_gradients(ctx.h, im, n, ax, ay))
+    return gx, gy
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1294,10 +1329,14 @@ def check_range_config(cfg):
     return int(rw)
 
 
+# seam_find_type (image_stitching.cpp:77, :1029-1062) as a configuration name
+SEAM_FIND_TYPES = ("no", "voronoi", "dp_color", "dp_colorgrad")
+
+
 def check_seam_config(cfg):
-    if cfg.seam_find_type not in ("no", "voronoi", "dp_color"):
-        raise NotImplementedError("seam_find_type %r: 'no', 'voronoi' and 'dp_color' are implemented (dp_colorgrad and the "
-                                  "graph-cut finders are outside this library; DESIGN.md section 8)" % (cfg.seam_find_type,))
+    if cfg.seam_find_type not in SEAM_FIND_TYPES:
+        raise NotImplementedError("seam_find_type %r: 'no', 'voronoi', 'dp_color' and 'dp_colorgrad' are implemented (the "
+                                  "graph-cut finders gc_color / gc_colorgrad are outside this library; DESIGN.md section 8)" % (cfg.seam_find_type,))
     if cfg.expos_comp_type not in EXPOS_COMP_TYPES:
         raise NotImplementedError("expos_comp_type %r: one of %s ('channels' is ChannelsCompensator, not a configuration name here)"
                                   % (cfg.expos_comp_type, ", ".join(EXPOS_COMP_TYPES)))
@@ -1333,6 +1372,8 @@ def seam_solve(ctx, cfg, corners, images_warped, masks_warped):
         VoronoiSeamFinder(ctx).find(images_warped, corners, masks_warped)
     elif cfg.seam_find_type == "dp_color":
         DpSeamFinder(ctx, DpSeamFinder.COLOR).find(images_warped, corners, masks_warped)
+    elif cfg.seam_find_type == "dp_colorgrad":
+        DpSeamFinder(ctx, DpSeamFinder.COLOR_GRAD).find(images_warped, corners, masks_warped)
     return compensator, masks_warped
 
 
@@ -1415,7 +1456,7 @@ class StitchConfig:
     expos_comp_nr_feeds: int = 1           # :74
     expos_comp_block_size: int = 64
     expos_comp_nr_filtering: int = 2
-    seam_find_type: str = "dp_color"       # "no" | "voronoi" | "dp_color"
+    seam_find_type: str = "dp_color"       # "no" | "voronoi" | "dp_color" | "dp_colorgrad" (SEAM_FIND_TYPES)
 
     def __post_init__(self):
         check_ba_config(self)

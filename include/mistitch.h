@@ -474,9 +474,19 @@ int mis_seam_voronoi(MisContext* ctx, const MisPoint* corners, MisImage* masks, 
 /* seam_finder = makePtr<detail::DpSeamFinder>(DpSeamFinder::COLOR); seam_finder->find(images_warped_f, corners, masks_warped)
  * -- replaces image_stitching.cpp:1056-1057, :1065 (the reference's default seam finder, "dp_color").  images: the seam-scale
  * warped 8UC3 images (converted to float inside, as :992-994 does); masks: 8U, edited in place.  Host logic on copies of the
- * (~0.1 MP) images; device or host buffers.  cost_func: MIS_SEAM_DP_COLOR (COLOR_GRAD is not built). */
+ * (~0.1 MP) images; device or host buffers.  cost_func: MIS_SEAM_DP_COLOR only; any other value is MIS_E_UNSUPPORTED here
+ * (DpSeamFinder::COLOR_GRAD is the entry of its own below, mis_seam_dp_colorgrad). */
 #define MIS_SEAM_DP_COLOR 0
 int mis_seam_dp(MisContext* ctx, const MisPoint* corners, const MisImage* images, MisImage* masks, int n, int cost_func);
+/* seam_finder = makePtr<detail::DpSeamFinder>(DpSeamFinder::COLOR_GRAD) -- image_stitching.cpp:1057-1058, :1065 ("dp_colorgrad").
+ * Inputs, checks, pair order and mask write-back as mis_seam_dp; the colour cost of a cut is divided by 1 + the four absolute
+ * Sobel derivatives across it.  The derivatives are made once per frame by one kernel launch (mis_seam_gradients' kernel) on the
+ * gathered device copies and come to the host in the finder's one staged copy; host images are uploaded for it. */
+int mis_seam_dp_colorgrad(MisContext* ctx, const MisPoint* corners, const MisImage* images, MisImage* masks, int n);
+/* DpSeamFinder::computeGradients for n images in one launch; images: 8UC3, device or host; gradx / grady: f32 x 1 of the same
+ * sizes, device or host.  Host inputs are uploaded; there is one arithmetic, the kernel's (float32, no FMA: csrc/seam_grad.hip).
+ * n == 0: MIS_OK.  A size, type or channel mismatch: MIS_E_INVALID, nothing written. */
+int mis_seam_gradients(MisContext* ctx, const MisImage* images, int n, MisImage* gradx, MisImage* grady);
 
 /* ---------------------------------------------------------------- blend --------------------- */
 /* reference-side blender sizing, image_stitching.cpp:1176-1190: returns the blend type to use in
