@@ -11,7 +11,7 @@ from . import _capi
 from ._capi import (BLEND_FEATHER, BLEND_MULTI_BAND, BLEND_NO, BORDER_CONSTANT, BORDER_REFLECT, INTER_LINEAR,
                     INTER_NEAREST, WARP_CYLINDRICAL, WARP_FISHEYE, WARP_MERCATOR, WARP_PLANE, WARP_SPHERICAL, WARP_STEREOGRAPHIC,
                     WARP_COMPRESSED_PLANE_A2B1, WARP_COMPRESSED_PLANE_A15B1, WARP_PANINI_A2B1, WARP_PANINI_A15B1)
-from .stitching import (AffineBestOf2NearestMatcher, BestOf2NearestMatcher, BestOf2NearestRangeMatcher, estimate_affine_partial, Blender, BlocksGainCompensator, GainCompensator, ChannelsCompensator, BlocksChannelsCompensator, NoSeamFinder, VoronoiSeamFinder, DpSeamFinder, Context, FeatherBlender, ImageFeatures, MatchesInfo,
+from .stitching import (AffineBestOf2NearestMatcher, BestOf2NearestMatcher, BestOf2NearestRangeMatcher, estimate_affine_partial, Blender, BlocksGainCompensator, GainCompensator, ChannelsCompensator, BlocksChannelsCompensator, NoSeamFinder, VoronoiSeamFinder, DpSeamFinder, GraphCutSeamFinder, Context, FeatherBlender, ImageFeatures, MatchesInfo,
                         MisError, MultiBandBlender, OrbFeatureFinder, SiftFeatureFinder, SphericalWarper, CylindricalWarper, PlaneWarper, MercatorWarper, FisheyeWarper, StereographicWarper, CompressedRectilinearWarper, PaniniWarper,
                         RotationWarper, StitchConfig, Stitcher,
                         blend_config, bundle_adjust_ray, bundle_adjust_reproj, computeImageFeatures, find_homography, leaveBiggestComponent, resize, resize_batch, result_roi,
@@ -21,7 +21,7 @@ __all__ = [
     "Context", "MisError", "SphericalWarper", "Blender", "MultiBandBlender", "FeatherBlender", "OrbFeatureFinder", "SiftFeatureFinder",
     "computeImageFeatures", "ImageFeatures", "BestOf2NearestMatcher", "MatchesInfo", "leaveBiggestComponent",
     "find_homography", "warp_roi", "result_roi", "blend_config", "StitchConfig", "Stitcher", "resize", "rotate",
-    "seam_mask_apply", "bundle_adjust_reproj", "bundle_adjust_ray", "wave_correct", "BlocksGainCompensator", "GainCompensator", "ChannelsCompensator", "BlocksChannelsCompensator", "NoSeamFinder", "VoronoiSeamFinder", "DpSeamFinder",
+    "seam_mask_apply", "bundle_adjust_reproj", "bundle_adjust_ray", "wave_correct", "BlocksGainCompensator", "GainCompensator", "ChannelsCompensator", "BlocksChannelsCompensator", "NoSeamFinder", "VoronoiSeamFinder", "DpSeamFinder", "GraphCutSeamFinder",
     "INTER_NEAREST", "INTER_LINEAR", "BORDER_CONSTANT", "BORDER_REFLECT", "BLEND_NO", "BLEND_FEATHER",
     "BLEND_MULTI_BAND", "resize_batch", "work_geometry", "CylindricalWarper", "PlaneWarper", "RotationWarper", "WARP_SPHERICAL", "WARP_CYLINDRICAL", "WARP_PLANE", "WARP_MERCATOR", "MercatorWarper", "WARP_FISHEYE", "WARP_STEREOGRAPHIC", "FisheyeWarper", "StereographicWarper",
     "WARP_COMPRESSED_PLANE_A2B1", "WARP_COMPRESSED_PLANE_A15B1", "WARP_PANINI_A2B1", "WARP_PANINI_A15B1", "CompressedRectilinearWarper", "PaniniWarper",

@@ -197,6 +197,10 @@ PROTOTYPES = {
     "mis_seam_dp": (_i, [_vp, _P(MisPoint), _P(MisImage), _P(MisImage), _i, _i]),
     "mis_seam_dp_colorgrad": (_i, [_vp, _P(MisPoint), _P(MisImage), _P(MisImage), _i]),
     "mis_seam_gradients": (_i, [_vp, _P(MisImage), _i, _P(MisImage), _P(MisImage)]),
+    "mis_seam_graphcut": (_i, [_vp, _P(MisPoint), _P(MisImage), _P(MisImage), _i, _i, _f, _f]),
+    "mis_seam_graphcut_debug_pair": (_i, [_vp, _P(MisPoint), _P(MisImage), _P(MisImage), _i, _i, _i, _P(C.c_int32), _P(C.c_int32), _P(C.c_int32),
+                                          _P(C.c_uint8), C.c_size_t, _P(_i), _P(_i)]),
+    "mis_seam_graphcut_stats": (_i, [_vp, _P(_i), _i, _P(_i)]),
     "mis_warp_spherical_fused_timed": (_i, [_vp, _P(MisImage), _f, _vp, _vp, _P(MisImage), _P(MisImage), _P(MisPoint), _i, _P(C.c_float)]),
     "mis_blend_config": (_i, [_i, _f, _i, _i, _P(_i), _P(_i), _P(_f)]),
     "mis_result_roi": (_i, [_P(MisPoint), _P(MisSize), _i, _P(MisRect)]),

@@ -37,6 +37,9 @@ struct MisContext {
     size_t roi_pinned_bytes = 0;
     void* host_stage = nullptr;      // pinned host scratch of host-logic entries (mis_seam_dp): grow-only, see mis_host_stage
     size_t host_stage_bytes = 0;
+    // the last mis_seam_graphcut call's counts (seam_gc.hip): pairs, levels, grid nodes, the round-set cap, global relabels, relabel
+    // sweeps, then the round sets of every level
+    std::vector<int> gc_stats;
 };
 
 int mis_set_error(MisContext* ctx, int code, const char* fmt, ...);

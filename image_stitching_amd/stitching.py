@@ -573,6 +573,62 @@ class DpSeamFinder:
         return masks
 
 
+class GraphCutSeamFinder:
+    """cv::detail::GraphCutSeamFinder(COST_COLOR, terminal_cost, bad_region_penalty) -- the seam finder of the reference's try_cuda
+    branch (image_stitching.cpp:1037-1054) and of OpenCV's own stitcher -- over mis_seam_graphcut: a device max-flow per
+    overlapping pair (csrc/seam_gc.hip; the definition is SURVEY.md appendix A.13).  images: the seam-scale warped 8UC3 images;
+    masks are edited in place.  cost_type: "COST_COLOR"; "COST_COLOR_GRAD" is known and not built (NotImplementedError), any
+    other value is a ValueError.  The class is not a configuration name: hand an instance to Stitcher.set_seam_finder."""
+    COST_TYPES = {"COST_COLOR": 0, "COST_COLOR_GRAD": 1}
+
+    def __init__(self, ctx, cost_type="COST_COLOR", terminal_cost=10000.0, bad_region_penalty=1000.0):
+        if not isinstance(cost_type, str) or cost_type not in GraphCutSeamFinder.COST_TYPES:
+            raise ValueError("GraphCutSeamFinder cost type %r: 'COST_COLOR' or 'COST_COLOR_GRAD'" % (cost_type,))
+        if cost_type == "COST_COLOR_GRAD":
+            raise NotImplementedError("GraphCutSeamFinder cost type 'COST_COLOR_GRAD' is not built (DESIGN.md section 8); 'COST_COLOR' is")
+        self.ctx, self.cost_type = ctx, cost_type
+        self.terminal_cost, self.bad_region_penalty = float(terminal_cost), float(bad_region_penalty)
+
+    def find(self, images, corners, masks):
+        n = len(masks)
+        k = max(n, 1)
+        cs = (capi.MisPoint * k)(*[capi.MisPoint(int(c[0]), int(c[1])) for c in corners])
+        im = (capi.MisImage * k)(*[as_image(i) for i in images])
+        mk = (capi.MisImage * k)(*[as_image(m) for m in masks])
+        self.ctx.check(self.ctx.lib.mis_seam_graphcut(self.ctx.h, cs, im, mk, n, GraphCutSeamFinder.COST_TYPES[self.cost_type],
+                                                      self.terminal_cost, self.bad_region_penalty))
+        return masks
+
+    def stats(self):
+        """The counts of the context's last find: pairs, levels, grid nodes, the round-set cap, global relabels, relabel sweeps and
+        the round sets of every level."""
+        count = C.c_int(0)
+        self.ctx.check(self.ctx.lib.mis_seam_graphcut_stats(self.ctx.h, None, 0, C.byref(count)))
+        out = (C.c_int * max(count.value, 1))()
+        self.ctx.check(self.ctx.lib.mis_seam_graphcut_stats(self.ctx.h, out, count.value, C.byref(count)))
+        v = list(out[:count.value])
+        if len(v) < 6:
+            return None
+        return dict(pairs=v[0], levels=v[1], nodes=v[2], round_set_cap=v[3], relabels=v[4], sweeps=v[5], round_sets=v[6:])
+
+    def debug_pair(self, images, corners, masks, i, j):
+        """mis_seam_graphcut_debug_pair: pair (i, j) on the masks as given -> (cap_right, cap_down, terminals, labels), numpy planes
+        of the pair's grid (the gap included); nothing is edited."""
+        n = len(masks)
+        cs = (capi.MisPoint * n)(*[capi.MisPoint(int(c[0]), int(c[1])) for c in corners])
+        im = (capi.MisImage * n)(*[as_image(x) for x in images])
+        mk = (capi.MisImage * n)(*[as_image(m) for m in masks])
+        gw, gh = C.c_int(0), C.c_int(0)
+        self.ctx.check(self.ctx.lib.mis_seam_graphcut_debug_pair(self.ctx.h, cs, im, mk, n, i, j, None, None, None, None, 0, C.byref(gw), C.byref(gh)))
+        shape = (gh.value, gw.value)
+        cr, cd, term = np.empty(shape, np.int32), np.empty(shape, np.int32), np.empty(shape, np.int32)
+        lab = np.empty(shape, np.uint8)
+        p32 = C.POINTER(C.c_int32)
+        self.ctx.check(self.ctx.lib.mis_seam_graphcut_debug_pair(self.ctx.h, cs, im, mk, n, i, j, cr.ctypes.data_as(p32), cd.ctypes.data_as(p32), term.ctypes.data_as(p32),
+                                                                 lab.ctypes.data_as(C.POINTER(C.c_uint8)), cr.size, C.byref(gw), C.byref(gh)))
+        return cr, cd, term, lab
+
+
 def seam_gradients(ctx, images, gradx=None, grady=None):
     """DpSeamFinder::computeGradients of every image in one launch (mis_seam_gradients): BGR -> grey, then the 3 x 3 Sobel
     derivatives along x and y (BORDER_REFLECT_101) -> (gradx, grady), lists of float32 planes.  images: 8UC3 device tensors or
@@ -1335,8 +1391,9 @@ SEAM_FIND_TYPES = ("no", "voronoi", "dp_color", "dp_colorgrad")
 
 def check_seam_config(cfg):
     if cfg.seam_find_type not in SEAM_FIND_TYPES:
-        raise NotImplementedError("seam_find_type %r: 'no', 'voronoi', 'dp_color' and 'dp_colorgrad' are implemented (the "
-                                  "graph-cut finders gc_color / gc_colorgrad are outside this library; DESIGN.md section 8)" % (cfg.seam_find_type,))
+        raise NotImplementedError("seam_find_type %r: 'no', 'voronoi', 'dp_color' and 'dp_colorgrad' are implemented as configuration names "
+                                  "(gc_color / gc_colorgrad are not names here: the graph-cut finder is the class GraphCutSeamFinder, handed to "
+                                  "Stitcher.set_seam_finder; DESIGN.md section 8)" % (cfg.seam_find_type,))
     if cfg.expos_comp_type not in EXPOS_COMP_TYPES:
         raise NotImplementedError("expos_comp_type %r: one of %s ('channels' is ChannelsCompensator, not a configuration name here)"
                                   % (cfg.expos_comp_type, ", ".join(EXPOS_COMP_TYPES)))
@@ -1362,13 +1419,16 @@ def seam_scale_warp(ctx, cfg, frame_size, frame, camera, warped_image_scale, wor
     return tl, iw, mw
 
 
-def seam_solve(ctx, cfg, corners, images_warped, masks_warped):
+def seam_solve(ctx, cfg, corners, images_warped, masks_warped, seam_finder=None):
     """The part of the seam-scale pass that needs every image (image_stitching.cpp:1002-1023 exposure compensator feed, :1029-1065
-    seam finder) -> (compensator | None, masks_warped edited in place)."""
+    seam finder) -> (compensator | None, masks_warped edited in place).  seam_finder: a finder object (anything with
+    find(images, corners, masks)) that runs in place of the configured one, as cv::Stitcher::setSeamFinder's does."""
     compensator = make_compensator(ctx, cfg)
     if compensator is not None:
         compensator.feed(corners, images_warped, masks_warped)
-    if cfg.seam_find_type == "voronoi":
+    if seam_finder is not None:
+        seam_finder.find(images_warped, corners, masks_warped)
+    elif cfg.seam_find_type == "voronoi":
         VoronoiSeamFinder(ctx).find(images_warped, corners, masks_warped)
     elif cfg.seam_find_type == "dp_color":
         DpSeamFinder(ctx, DpSeamFinder.COLOR).find(images_warped, corners, masks_warped)
@@ -1495,6 +1555,14 @@ class Stitcher:
         self.work_scale, self.work_size = work_geometry(self.cfg, frame_size)
         self.finder = OrbFeatureFinder(ctx, self.work_size)
         self.matcher = make_matcher(ctx, self.cfg)
+        self.seam_finder = None       # set_seam_finder
+
+    def set_seam_finder(self, finder):
+        """cv::Stitcher::setSeamFinder: the seam step runs this finder object (e.g. GraphCutSeamFinder(ctx)) whatever
+        seam_find_type says, "no" included; None goes back to the configured finder."""
+        if finder is not None and (isinstance(finder, (str, bytes)) or not callable(getattr(finder, "find", None))):
+            raise TypeError("set_seam_finder: %r has no find(images, corners, masks)" % (finder,))
+        self.seam_finder = finder
 
     def work_cameras(self, cameras):
         """The caller's full-resolution cameras in work units (cam.focal, ppx, ppy *= work_scale, image_stitching.cpp:635-637);
@@ -1564,11 +1632,11 @@ class Stitcher:
         """The seam-scale pass of main() (image_stitching.cpp:604-622 resize, :973-990 warp, :1002-1023 exposure
         compensator feed, :1029-1065 seam finder) -> (compensator | None, masks_warped) or None when both are off."""
         check_seam_config(self.cfg)
-        if self.cfg.expos_comp_type == "no" and self.cfg.seam_find_type == "no":
+        if self.cfg.expos_comp_type == "no" and self.cfg.seam_find_type == "no" and self.seam_finder is None:
             return None
         work_scale = self.work_scale if work_scale is None else work_scale
         items = [seam_scale_warp(self.ctx, self.cfg, self.frame_size, frames[i], cameras[i], warped_image_scale, work_scale) for i in indices]
-        return seam_solve(self.ctx, self.cfg, [it[0] for it in items], [it[1] for it in items], [it[2] for it in items])
+        return seam_solve(self.ctx, self.cfg, [it[0] for it in items], [it[1] for it in items], [it[2] for it in items], self.seam_finder)
 
     def stitch(self, frames, cameras):
         feats = self.features(frames)

@@ -34,6 +34,7 @@ extern "C" {
 #define MIS_E_OVERFLOW (-4)    /* an internal candidate buffer was too small for the input */
 #define MIS_E_STATE (-5)       /* call order violated (e.g. feed before prepare) */
 #define MIS_E_UNSUPPORTED (-6)
+#define MIS_E_INTERNAL (-7)    /* a bounded iteration reached its cap (mis_seam_graphcut); nothing was written */
 #define MIS_FENCE_TIMEOUT 1     /* mis_match_knn_fence only, not an error: the matcher call did not show up within the timeout, nothing was queued */
 
 enum { MIS_MEM_HOST = 0, MIS_MEM_DEVICE = 1 };
@@ -487,6 +488,32 @@ int mis_seam_dp_colorgrad(MisContext* ctx, const MisPoint* corners, const MisIma
  * sizes, device or host.  Host inputs are uploaded; there is one arithmetic, the kernel's (float32, no FMA: csrc/seam_grad.hip).
  * n == 0: MIS_OK.  A size, type or channel mismatch: MIS_E_INVALID, nothing written. */
 int mis_seam_gradients(MisContext* ctx, const MisImage* images, int n, MisImage* gradx, MisImage* grady);
+/* seam_finder = makePtr<detail::GraphCutSeamFinder(Gpu)>(COST_COLOR, terminal_cost, bad_region_penalty); seam_finder->find(...)
+ * -- image_stitching.cpp:1037-1054, :1065 (the reference's try_cuda seam finder; OpenCV's defaults are 10000 and 1000).  Inputs
+ * and checks as mis_seam_dp: seam-scale 8UC3 images, 8U masks edited in place, device or host buffers; a size, type or channel
+ * mismatch is MIS_E_INVALID with nothing written, n == 0 is MIS_OK.  Per overlapping pair, in PairwiseSeamFinder::run order
+ * (i, then j > i), a maximum flow on the roi grown by 10 pixels decides which image keeps each pixel; the definition with its
+ * integer capacities is SURVEY.md appendix A.13, the kernels are csrc/seam_gc.hip (device push-relabel; the labels are the
+ * minimal source side, a property of the input).  cost_type: MIS_SEAM_GC_COST_COLOR; MIS_SEAM_GC_COST_COLOR_GRAD is refused by
+ * name with MIS_E_UNSUPPORTED, any other value is MIS_E_INVALID.  terminal_cost / bad_region_penalty: finite and >= 0, and small
+ * enough that a node's four edges and its terminal stay below 2^31 together, else MIS_E_INVALID.  The solver's launches are
+ * bounded: a pair that has not finished within the cap returns MIS_E_INTERNAL with the pair named, the masks untouched. */
+#define MIS_SEAM_GC_COST_COLOR 0
+#define MIS_SEAM_GC_COST_COLOR_GRAD 1
+int mis_seam_graphcut(MisContext* ctx, const MisPoint* corners, const MisImage* images, MisImage* masks, int n,
+                      int cost_type, float terminal_cost, float bad_region_penalty);
+/* Test aid: the graph of pair (i, j), 0 <= i < j < n, built and cut with the default costs on the masks AS GIVEN (no earlier pair
+ * has edited them; nothing is written to them) -> its integer capacities towards the right and the lower neighbour (0 in the
+ * last column / row), its terminals (> 0 source, < 0 sink) and its labels (1: in the minimal source side), row-major planes of
+ * grid_w x grid_h nodes, the 10-pixel gap included.  grid_w / grid_h are always written; capacity_elems == 0 asks for them alone;
+ * planes that hold fewer than grid_w * grid_h elements, or images that do not overlap: MIS_E_INVALID. */
+int mis_seam_graphcut_debug_pair(MisContext* ctx, const MisPoint* corners, const MisImage* images, const MisImage* masks, int n, int i, int j,
+                                 int32_t* cap_right, int32_t* cap_down, int32_t* terminals, uint8_t* labels, size_t capacity_elems,
+                                 int* grid_w, int* grid_h);
+/* The counts of the context's last mis_seam_graphcut call: overlapping pairs, dependency levels, grid nodes, the cap on a level's
+ * round sets, global relabels, relabel sweeps, then the round sets each level used.  *count: how many there are; out takes the
+ * first `capacity` of them. */
+int mis_seam_graphcut_stats(const MisContext* ctx, int* out, int capacity, int* count);
 
 /* ---------------------------------------------------------------- blend --------------------- */
 /* reference-side blender sizing, image_stitching.cpp:1176-1190: returns the blend type to use in
