@@ -68,6 +68,24 @@ static MisImage view(const HostImage& im) {
     return v;
 }
 
+// seam_find_type -> the library call of the seam step (find == nullptr: "no"); an unknown name throws
+struct SeamFinderEntry { const char *name, *what; int (*find)(MisContext*, const MisPoint*, const MisImage*, MisImage*, int); };
+static const SeamFinderEntry& seam_finder(const std::string& type) {
+    static const SeamFinderEntry table[] = {
+        {"no", "", nullptr},
+        {"voronoi", "mis_seam_voronoi", [](MisContext* c, const MisPoint* p, const MisImage*, MisImage* m, int n) { return mis_seam_voronoi(c, p, m, n); }},
+        // the reference's default (image_stitching.cpp:77, :1056-1065)
+        {"dp_color", "mis_seam_dp", [](MisContext* c, const MisPoint* p, const MisImage* i, MisImage* m, int n) { return mis_seam_dp(c, p, i, m, n, MIS_SEAM_DP_COLOR); }},
+        {"dp_colorgrad", "mis_seam_dp_colorgrad", mis_seam_dp_colorgrad},      // DpSeamFinder(COLOR_GRAD) (:1057-1058)
+    };
+    std::string names;      // 'a', 'b', 'c' and 'd'
+    for (const SeamFinderEntry& e : table) {
+        if (type == e.name) return e;
+        names += std::string(&e == table ? "'" : (&e + 1 == std::end(table) ? " and '" : ", '")) + e.name + "'";
+    }
+    throw std::runtime_error("seam finder '" + type + "' is not implemented (" + names + " are)");
+}
+
 StitchResult Stitcher::stitch(const std::vector<HostImage>& frames, const std::vector<CameraParams>& cams_in) {
     const int n = (int)frames.size();
     if (n < 2 || (int)cams_in.size() != n) throw std::runtime_error("Need more images");
@@ -83,8 +101,7 @@ StitchResult Stitcher::stitch(const std::vector<HostImage>& frames, const std::v
     if (cfg_.ba_cost_func != "no" && cfg_.ba_cost_func != "reproj" && cfg_.ba_cost_func != "ray")
         throw std::runtime_error("bundle adjustment cost function '" + cfg_.ba_cost_func + "' is not implemented ('no', 'reproj' and 'ray' are)");
     const int expos_kind = expos_comp_kind(cfg_.expos_comp_type, cfg_.expos_comp_nr_feeds);
-    if (cfg_.seam_find_type != "no" && cfg_.seam_find_type != "voronoi" && cfg_.seam_find_type != "dp_color" && cfg_.seam_find_type != "dp_colorgrad")
-        throw std::runtime_error("seam finder '" + cfg_.seam_find_type + "' is not implemented ('no', 'voronoi', 'dp_color' and 'dp_colorgrad' are)");
+    const SeamFinderEntry& seam = seam_finder(cfg_.seam_find_type);
     const int kind = warp_kind(cfg_.warp_type);
     check_range_width(cfg_.range_width);
     const int model = matcher_model(cfg_.matcher_type, cfg_.range_width);
@@ -216,7 +233,7 @@ StitchResult Stitcher::stitch(const std::vector<HostImage>& frames, const std::v
     check(mis_blender_create(ctx_, btype, bands, sharp, &blender), "mis_blender_create");
     check(mis_blender_prepare(blender, corners.data(), sizes.data(), kept), "mis_blender_prepare");
     // ---- seam-scale pass (:604-622 resize, :973-990 warp, :1002-1023 exposure compensator, :1029-1065 seam finder) ----
-    const bool seam_step = cfg_.expos_comp_type != "no" || cfg_.seam_find_type != "no";
+    const bool seam_step = cfg_.expos_comp_type != "no" || seam.find;
     MisCompensator* compensator = nullptr;
     std::vector<MisImage> masks_warped(kept);
     if (seam_step) {
@@ -248,11 +265,7 @@ StitchResult Stitcher::stitch(const std::vector<HostImage>& frames, const std::v
             check(mis_compensator_create_ex(ctx_, &cp, &compensator), "mis_compensator_create_ex");
             check(mis_compensator_feed(compensator, seam_corners.data(), images_warped.data(), masks_warped.data(), kept), "mis_compensator_feed");
         }
-        if (cfg_.seam_find_type == "voronoi") check(mis_seam_voronoi(ctx_, seam_corners.data(), masks_warped.data(), kept), "mis_seam_voronoi");
-        else if (cfg_.seam_find_type == "dp_color")      // the reference's default (image_stitching.cpp:77, :1056-1065)
-            check(mis_seam_dp(ctx_, seam_corners.data(), images_warped.data(), masks_warped.data(), kept, MIS_SEAM_DP_COLOR), "mis_seam_dp");
-        else if (cfg_.seam_find_type == "dp_colorgrad")  // DpSeamFinder(COLOR_GRAD) (:1057-1058)
-            check(mis_seam_dp_colorgrad(ctx_, seam_corners.data(), images_warped.data(), masks_warped.data(), kept), "mis_seam_dp_colorgrad");
+        if (seam.find) check(seam.find(ctx_, seam_corners.data(), images_warped.data(), masks_warped.data(), kept), seam.what);
         for (auto& im : images_warped) mis_image_free(ctx_, &im);
     }
     for (int k = 0; k < kept; k++) {

@@ -114,6 +114,19 @@ private:
     bool staged_ = false, fresh_ = false;
 };
 
+// A device block from the context's pool for the length of a scope.  It goes back to the pool on every way out, after a wait for
+// the context's stream: an error path may leave work on the block in flight.  release() hands it back at once, without the wait,
+// for a caller whose remaining work on the block is already enqueued: the pool's next user is ordered behind it on the stream.
+struct PoolBlock {
+    MisContext* ctx; void* p = nullptr; size_t got = 0;
+    explicit PoolBlock(MisContext* c) : ctx(c) {}
+    PoolBlock(const PoolBlock&) = delete;
+    PoolBlock& operator=(const PoolBlock&) = delete;
+    ~PoolBlock() { if (p) { hipStreamSynchronize(ctx->stream); release(); } }
+    int alloc(size_t bytes) { const int rc = mis_pool_alloc(ctx, bytes, &p, &got); if (rc != MIS_OK) p = nullptr; return rc; }
+    void release() { if (p) mis_pool_free(ctx, p, got); p = nullptr; }
+};
+
 // a HIP event that is destroyed with its scope
 struct OwnedEvent {
     hipEvent_t ev = nullptr;

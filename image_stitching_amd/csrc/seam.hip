@@ -6,14 +6,17 @@
 // core's cv::partition, imgproc's floodFill) on the seam-scale images (~0.1 MP each); restated here from the published
 // algorithm.  OpenCV is absent offline; the restatement is pinned, byte for byte and at every branch regime, to the independent
 // numpy / scipy reference tests/refimpl_seam_dp.py (tests/test_refimpl_seam_dp_gpu.py; the oracle twin oracle/mo_seam.c in
-// tests/test_refimpl_seam_dp_cpu.py).  NOT PINNED: the order of pairs at equal centre distance (mis_seam_dp below).
+// tests/test_refimpl_seam_dp_cpu.py).  NOT PINNED: the order of pairs at equal centre distance (seam_plan.h).
 // No kernels: the data is two ~420 x 240 images per pair and the algorithm is sequential (labelling, dynamic programming along
-// a seam, flood fills); images and masks are copied to the host, the masks go back to the device.
+// a seam, flood fills); images and masks are copied to the host, the masks go back to the device.  The pair plan (seam_plan.h) and
+// the packed staging block with its input contract (seam_stage.h) are shared with the graph-cut finder; seam_dp_find at the end of
+// this file is the call's four steps: stage in, plan, solve the levels on host threads, stage out.
 // DpSeamFinder(COLOR_GRAD) ("dp_colorgrad", :1057-1058) is the same finder with another cost (compute_costs) behind an entry of
 // its own, mis_seam_dp_colorgrad: its per-image pass, DpSeamFinder::computeGradients, is the kernel of seam_grad.hip, launched once
 // for all frames on the gathered device block; pinned to tests/refimpl_seam_dp_grad.py (tests/test_seam_dp_grad_gpu.py).
 #include "common.h"
 #include "dev_math.h"
+#include "seam_stage.h"
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -480,9 +483,8 @@ struct DpPair {
     // DpSeamFinder::process
     void process(const HostImage& im1, const HostImage& im2, Pt tl1, Pt tl2, Grid<uint8_t>& m1, Grid<uint8_t>& m2, bool grad) {
         color_grad = grad;
-        const Pt itl{std::max(tl1.x, tl2.x), std::max(tl1.y, tl2.y)};
-        const Pt ibr{std::min(tl1.x + im1.w, tl2.x + im2.w), std::min(tl1.y + im1.h, tl2.y + im2.h)};
-        if (itl.x >= ibr.x || itl.y >= ibr.y) return;   // no overlap: no conflicts
+        SeamRect inter;
+        if (!seam_overlap(SeamFrame{tl1.x, tl1.y, im1.w, im1.h}, SeamFrame{tl2.x, tl2.y, im2.w, im2.h}, &inter)) return;   // no overlap: no conflicts
         SeamTimer tm_setup(0);
         union_tl = Pt{std::min(tl1.x, tl2.x), std::min(tl1.y, tl2.y)};
         union_br = Pt{std::max(tl1.x + im1.w, tl2.x + im2.w), std::max(tl1.y + im1.h, tl2.y + im2.h)};
@@ -509,74 +511,58 @@ struct DpPair {
     }
 };
 
-// DpSeamFinder::find: every pair of images, the most distant centres first.
-// NOT PINNED: the reference orders the pairs with std::sort (unspecified for equal keys) + std::reverse; pairs at equal distance are
-// ordered here as a stable sort + reverse leaves them (tie_order="reversed" of tests/refimpl_seam_dp.py, which states both readings).
-// grad: the COLOR_GRAD cost.  Every image is then in the device block (host images are uploaded into their slots), the gradient
-// kernel runs on the block and its planes come over behind the images and masks in the same copy.
-int seam_dp_find(MisContext* ctx, const MisPoint* corners, const MisImage* images, MisImage* masks, int n, bool grad) {
-    if (n == 0) return MIS_OK;
-    MIS_HIP(ctx, hipSetDevice(ctx->device));
-    if (getenv("MIS_SEAM_TRACE")) { const auto t_e = std::chrono::steady_clock::now(); hipStreamSynchronize(ctx->stream); fprintf(stderr, "dp seams: entry sync %.2f ms\n", std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t_e).count() / 1e3); }
-    const auto t_begin = std::chrono::steady_clock::now();
-    std::vector<HostImage> im((size_t)n);
-    std::vector<Grid<uint8_t>> mk((size_t)n);
+using Clock = std::chrono::steady_clock;
+
+// What a call stages: the packed block of seam_stage.h on the device, its pinned twin on the host (COLOR_GRAD: the gradient planes
+// behind the slots), and the finder's own float images and masks made from the twin.
+struct DpStage {
+    SeamSlots slots;
+    std::vector<size_t> gxoff, gyoff;
+    size_t back_total = 0;          // what travels back with the masks: the gradient planes lie behind it
+    uint8_t* stage = nullptr;
+    PoolBlock dblk;
+    std::vector<HostImage> im;
+    std::vector<Grid<uint8_t>> mk;
+    Clock::time_point t_issued, t_synced, t_loaded;     // MIS_SEAM_TRACE
+    DpStage(MisContext* ctx, const MisImage* images, int n) : slots(images, n), gxoff((size_t)n), gyoff((size_t)n), dblk(ctx), im((size_t)n), mk((size_t)n) {}
+};
+
+// Images and masks -> S.im / S.mk.  grad: the COLOR_GRAD cost.  Every image is then in the device block (host images are uploaded
+// into their slots), the gradient kernel runs on the block and its planes come over behind the images and masks in the same copy.
+int dp_stage_in(MisContext* ctx, const MisImage* images, const MisImage* masks, int n, bool grad, DpStage& S) {
+    const std::vector<size_t>&ioff = S.slots.ioff, &moff = S.slots.moff;
     // device images and masks come over in one go: every copy into a pinned staging buffer, ONE synchronisation (a pageable
     // destination made each of the 3 n small 2-D copies a synchronous 0.8 ms affair: 39 of the finder's 52 ms)
-    size_t stage_total = 0;
-    std::vector<size_t> ioff((size_t)n), moff((size_t)n);
-    for (int i = 0; i < n; i++) {
-        const MisImage& I = images[i];
-        const MisImage& M = masks[i];
-        MIS_CHECK(ctx, I.data && M.data && I.dtype == MIS_U8 && I.channels == 3 && M.dtype == MIS_U8 && M.channels == 1 && I.width == M.width && I.height == M.height &&
-                           I.width > 0 && I.height > 0, MIS_E_INVALID, "image %d: need an 8UC3 image and an 8U mask of the same size", i);
-        ioff[i] = stage_total; stage_total += mis_align_up((size_t)I.width * I.height * 3, 256);
-        moff[i] = stage_total; stage_total += mis_align_up((size_t)M.width * M.height, 256);
-    }
-    const size_t back_total = stage_total;      // what travels back with the masks: the gradient planes lie behind it
-    std::vector<size_t> gxoff((size_t)n), gyoff((size_t)n);
+    size_t stage_total = S.back_total = S.slots.bytes;
     if (grad)
         for (int i = 0; i < n; i++) {
             const size_t plane = mis_align_up((size_t)images[i].width * images[i].height * sizeof(float), 256);
-            gxoff[i] = stage_total; stage_total += plane;
-            gyoff[i] = stage_total; stage_total += plane;
+            S.gxoff[i] = stage_total; stage_total += plane;
+            S.gyoff[i] = stage_total; stage_total += plane;
         }
-    uint8_t* stage = nullptr;
-    { void* sp = nullptr; int rc = mis_host_stage(ctx, stage_total, &sp); if (rc != MIS_OK) return rc; stage = (uint8_t*)sp; }
+    { void* sp = nullptr; int rc = mis_host_stage(ctx, stage_total, &sp); if (rc != MIS_OK) return rc; S.stage = (uint8_t*)sp; }
+    uint8_t* stage = S.stage;
     // device inputs are gathered into one device block first (device-to-device copies are cheap launches) and cross the bus in ONE
     // copy: 3 n separate device-to-host copies of ~0.1 MB took 1 ms each on the stream of a second context, 31 of the finder's 52 ms
     bool any_dev = grad;
     for (int i = 0; i < n; i++) any_dev |= images[i].mem == MIS_MEM_DEVICE || masks[i].mem == MIS_MEM_DEVICE;
-    void* dblk = nullptr; size_t dgot = 0;
-    if (any_dev) { int rc = mis_pool_alloc(ctx, stage_total, &dblk, &dgot); if (rc != MIS_OK) return rc; }
-    uint8_t* dstage = (uint8_t*)dblk;
-    // every HIP error below returns through here: the device block goes back to the pool
-#define SEAM_HIP(call)                                                                                                          \
-    do {                                                                                                                        \
-        hipError_t e_ = (call);                                                                                                 \
-        if (e_ != hipSuccess) {                                                                                                 \
-            if (dblk) { hipStreamSynchronize(ctx->stream); mis_pool_free(ctx, dblk, dgot); }                                     \
-            return mis_set_error(ctx, MIS_E_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__);    \
-        }                                                                                                                       \
-    } while (0)
+    if (any_dev) { int rc = S.dblk.alloc(stage_total); if (rc != MIS_OK) return rc; }
+    uint8_t* dstage = (uint8_t*)S.dblk.p;
     for (int i = 0; i < n; i++) {
-        const MisImage& I = images[i];
-        const MisImage& M = masks[i];
-        if (I.mem == MIS_MEM_DEVICE) SEAM_HIP(hipMemcpy2DAsync(dstage + ioff[i], (size_t)I.width * 3, I.data, I.stride, (size_t)I.width * 3, I.height, hipMemcpyDeviceToDevice, ctx->stream));
-        else if (grad) SEAM_HIP(hipMemcpy2DAsync(dstage + ioff[i], (size_t)I.width * 3, I.data, I.stride, (size_t)I.width * 3, I.height, hipMemcpyHostToDevice, ctx->stream));
-        if (M.mem == MIS_MEM_DEVICE) SEAM_HIP(hipMemcpy2DAsync(dstage + moff[i], M.width, M.data, M.stride, M.width, M.height, hipMemcpyDeviceToDevice, ctx->stream));
+        if (images[i].mem == MIS_MEM_DEVICE || grad) MIS_HIP(ctx, seam_gather(dstage + ioff[i], images[i], ctx->stream));
+        if (masks[i].mem == MIS_MEM_DEVICE) MIS_HIP(ctx, seam_gather(dstage + moff[i], masks[i], ctx->stream));
     }
     if (grad) {     // DpSeamFinder::computeGradients, once per frame instead of twice per pair: one launch on the gathered block
         std::vector<MisSeamGradJob> jobs((size_t)n);
         for (int i = 0; i < n; i++)
-            jobs[i] = MisSeamGradJob{dstage + ioff[i], (size_t)images[i].width * 3, (float*)(dstage + gxoff[i]), (size_t)images[i].width * sizeof(float),
-                                     (float*)(dstage + gyoff[i]), (size_t)images[i].width * sizeof(float), images[i].width, images[i].height};
-        if (int rc = mis_seam_grad_enqueue(ctx, jobs.data(), n)) { hipStreamSynchronize(ctx->stream); mis_pool_free(ctx, dblk, dgot); return rc; }
+            jobs[i] = MisSeamGradJob{dstage + ioff[i], (size_t)images[i].width * 3, (float*)(dstage + S.gxoff[i]), (size_t)images[i].width * sizeof(float),
+                                     (float*)(dstage + S.gyoff[i]), (size_t)images[i].width * sizeof(float), images[i].width, images[i].height};
+        if (int rc = mis_seam_grad_enqueue(ctx, jobs.data(), n)) return rc;
     }
-    if (any_dev) SEAM_HIP(hipMemcpyAsync(stage, dstage, stage_total, hipMemcpyDeviceToHost, ctx->stream));
-    const auto t_issued = std::chrono::steady_clock::now();
-    SEAM_HIP(hipStreamSynchronize(ctx->stream));
-    const auto t_synced = std::chrono::steady_clock::now();
+    if (any_dev) MIS_HIP(ctx, hipMemcpyAsync(stage, dstage, stage_total, hipMemcpyDeviceToHost, ctx->stream));
+    S.t_issued = Clock::now();
+    MIS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    S.t_synced = Clock::now();
     for (int i = 0; i < n; i++) {   // host inputs go into their slots of the staging buffer directly
         const MisImage& I = images[i];
         const MisImage& M = masks[i];
@@ -585,81 +571,81 @@ int seam_dp_find(MisContext* ctx, const MisPoint* corners, const MisImage* image
     }
     for (int i = 0; i < n; i++) {
         const MisImage& I = images[i];
-        im[i].w = I.width; im[i].h = I.height;
+        HostImage& im = S.im[i];
+        im.w = I.width; im.h = I.height;
         const size_t np3 = (size_t)I.width * I.height * 3;
-        im[i].px.resize(np3);
+        im.px.resize(np3);
         const uint8_t* sp = stage + ioff[i];
-        for (size_t k = 0; k < np3; k++) im[i].px[k] = (float)sp[k];     // convertTo(CV_32F), image_stitching.cpp:992-994
-        if (grad) { im[i].gradx = (const float*)(stage + gxoff[i]); im[i].grady = (const float*)(stage + gyoff[i]); }    // (read in place: the pinned staging is this call's)
-        mk[i].w = I.width; mk[i].h = I.height;
-        mk[i].v.assign(stage + moff[i], stage + moff[i] + (size_t)I.width * I.height);
+        for (size_t k = 0; k < np3; k++) im.px[k] = (float)sp[k];     // convertTo(CV_32F), image_stitching.cpp:992-994
+        if (grad) { im.gradx = (const float*)(stage + S.gxoff[i]); im.grady = (const float*)(stage + S.gyoff[i]); }    // (read in place: the pinned staging is this call's)
+        S.mk[i].w = I.width; S.mk[i].h = I.height;
+        S.mk[i].v.assign(stage + moff[i], stage + moff[i] + (size_t)I.width * I.height);
     }
-    const auto t_loaded = std::chrono::steady_clock::now();
-    struct PairD { int d, i, j; };
-    std::vector<PairD> pairs;
-    for (int i = 0; i + 1 < n; i++)
-        for (int j = i + 1; j < n; j++) {
-            const int c1x = corners[i].x + im[i].w / 2, c1y = corners[i].y + im[i].h / 2, c2x = corners[j].x + im[j].w / 2, c2y = corners[j].y + im[j].h / 2;
-            pairs.push_back(PairD{(c1x - c2x) * (c1x - c2x) + (c1y - c2y) * (c1y - c2y), i, j});
-        }
-    std::stable_sort(pairs.begin(), pairs.end(), [](const PairD& a, const PairD& b) { return a.d < b.d; });
-    std::reverse(pairs.begin(), pairs.end());
-    // A pair reads its two images and reads / writes its two masks, nothing else: pairs without a common image commute.  The
-    // pairs keep the reference's order wherever it matters -- a pair waits for every earlier pair that shares an image with it --
-    // and otherwise run side by side on host threads (level = 1 + the highest level among those earlier pairs).  Pairs whose
-    // images do not overlap change nothing and are dropped first.
-    std::vector<PairD> work;
-    for (const PairD& p : pairs) {
-        const int x0 = std::max(corners[p.i].x, corners[p.j].x), y0 = std::max(corners[p.i].y, corners[p.j].y);
-        const int x1 = std::min(corners[p.i].x + im[p.i].w, corners[p.j].x + im[p.j].w), y1 = std::min(corners[p.i].y + im[p.i].h, corners[p.j].y + im[p.j].h);
-        if (x0 < x1 && y0 < y1) work.push_back(p);
-    }
-    std::vector<int> level(work.size(), 0), last((size_t)n, 0);
-    int nlevels = 0;
-    for (size_t k = 0; k < work.size(); k++) {
-        level[k] = std::max(last[work[k].i], last[work[k].j]) + 1;
-        last[work[k].i] = last[work[k].j] = level[k];
-        nlevels = std::max(nlevels, level[k]);
-    }
+    S.t_loaded = Clock::now();
+    return MIS_OK;
+}
+
+// The plan's levels in turn, the pairs of a level side by side on host threads.
+void dp_solve_levels(const SeamPlan& plan, const MisPoint* corners, const std::vector<HostImage>& im, std::vector<Grid<uint8_t>>& mk, bool grad) {
     const unsigned hw = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-    auto run_pair = [&](const PairD& p) {
+    auto run_pair = [&](const SeamPair& p) {
         static thread_local DpPair dp;      // its grids keep their capacity from pair to pair
         dp.process(im[p.i], im[p.j], Pt{corners[p.i].x, corners[p.i].y}, Pt{corners[p.j].x, corners[p.j].y}, mk[p.i], mk[p.j], grad);
     };
-    for (int lv = 1; lv <= nlevels; lv++) {
+    for (int lv = 1; lv <= plan.nlevels; lv++) {
         std::vector<size_t> ids;
-        for (size_t k = 0; k < work.size(); k++) if (level[k] == lv) ids.push_back(k);
-        if (ids.size() == 1 || hw == 1) { for (size_t k : ids) run_pair(work[k]); continue; }
+        for (size_t k = 0; k < plan.pairs.size(); k++) if (plan.pairs[k].level == lv) ids.push_back(k);
+        if (ids.size() == 1 || hw == 1) { for (size_t k : ids) run_pair(plan.pairs[k]); continue; }
         std::atomic<size_t> next{0};
-        auto worker = [&]() { for (size_t q = next++; q < ids.size(); q = next++) run_pair(work[ids[q]]); };
+        auto worker = [&]() { for (size_t q = next++; q < ids.size(); q = next++) run_pair(plan.pairs[ids[q]]); };
         std::vector<std::thread> th;
         for (unsigned t = 1; t < std::min<size_t>(hw, ids.size()); t++) th.emplace_back(worker);
         worker();
         for (auto& t : th) t.join();
     }
-    const auto t_solved = std::chrono::steady_clock::now();
+}
+
+// S.mk -> the caller's masks: host masks directly, device masks through their slots in one copy of the block
+int dp_stage_out(MisContext* ctx, MisImage* masks, int n, DpStage& S) {
+    const std::vector<size_t>& moff = S.slots.moff;
+    uint8_t* dstage = (uint8_t*)S.dblk.p;
     for (int i = 0; i < n; i++) {
         const MisImage& M = masks[i];
-        if (M.mem == MIS_MEM_DEVICE) memcpy(stage + moff[i], mk[i].v.data(), (size_t)M.width * M.height);
-        else for (int y = 0; y < M.height; y++) memcpy((uint8_t*)M.data + (size_t)y * M.stride, mk[i].v.data() + (size_t)y * M.width, M.width);
+        if (M.mem == MIS_MEM_DEVICE) memcpy(S.stage + moff[i], S.mk[i].v.data(), (size_t)M.width * M.height);
+        else for (int y = 0; y < M.height; y++) memcpy((uint8_t*)M.data + (size_t)y * M.stride, S.mk[i].v.data() + (size_t)y * M.width, M.width);
     }
-    if (any_dev) {
+    if (dstage) {
         bool dev_mask = false;      // (COLOR_GRAD on host buffers holds the block for its gradients only)
         for (int i = 0; i < n; i++) dev_mask |= masks[i].mem == MIS_MEM_DEVICE;
-        if (dev_mask) SEAM_HIP(hipMemcpyAsync(dstage, stage, back_total, hipMemcpyHostToDevice, ctx->stream));   // (the image slots travel back unused: one copy)
-        for (int i = 0; i < n; i++) {
-            const MisImage& M = masks[i];
-            if (M.mem == MIS_MEM_DEVICE) SEAM_HIP(hipMemcpy2DAsync(M.data, M.stride, dstage + moff[i], M.width, M.width, M.height, hipMemcpyDeviceToDevice, ctx->stream));
-        }
-        mis_pool_free(ctx, dblk, dgot);
-        dblk = nullptr;
+        if (dev_mask) MIS_HIP(ctx, hipMemcpyAsync(dstage, S.stage, S.back_total, hipMemcpyHostToDevice, ctx->stream));   // (the image slots travel back unused: one copy)
+        for (int i = 0; i < n; i++)
+            if (masks[i].mem == MIS_MEM_DEVICE) MIS_HIP(ctx, seam_scatter(masks[i], dstage + moff[i], ctx->stream));
+        S.dblk.release();       // ahead of the wait below: the copies out of the block are enqueued, the pool's next user is behind them
     }
-#undef SEAM_HIP
     MIS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (getenv("MIS_SEAM_TRACE")) {
-        auto ms = [](auto a, auto b) { return std::chrono::duration_cast<std::chrono::microseconds>(b - a).count() / 1e3; };
-        fprintf(stderr, "dp seams wall: load %.2f ms (issue %.2f, sync %.2f, convert %.2f), pairs %.2f ms, store %.2f ms\n", ms(t_begin, t_loaded), ms(t_begin, t_issued), ms(t_issued, t_synced), ms(t_synced, t_loaded), ms(t_loaded, t_solved), ms(t_solved, std::chrono::steady_clock::now()));
-        fprintf(stderr, "dp seams: %zu overlapping pairs in %d levels; ms (summed over threads): setup+all %.2f components %.2f edges %.2f tips %.2f estimate %.2f labels %.2f rescan %.2f\n", work.size(), nlevels,
+    return MIS_OK;
+}
+
+// DpSeamFinder::find: every overlapping pair of images, the most distant centres first (SEAM_ORDER_DISTANCE of seam_plan.h).
+// A HIP error on any step returns at once: S's device block goes back to the pool behind a wait for the stream (PoolBlock).
+int seam_dp_find(MisContext* ctx, const MisPoint* corners, const MisImage* images, MisImage* masks, int n, bool grad) {
+    if (n == 0) return MIS_OK;
+    MIS_HIP(ctx, hipSetDevice(ctx->device));
+    auto ms = [](Clock::time_point a, Clock::time_point b) { return std::chrono::duration_cast<std::chrono::microseconds>(b - a).count() / 1e3; };
+    const bool trace = getenv("MIS_SEAM_TRACE") != nullptr;
+    if (trace) { const auto t_e = Clock::now(); hipStreamSynchronize(ctx->stream); fprintf(stderr, "dp seams: entry sync %.2f ms\n", ms(t_e, Clock::now())); }
+    const auto t_begin = Clock::now();
+    for (int i = 0; i < n; i++)
+        if (int rc = seam_check_input(ctx, images[i], masks[i], i)) return rc;
+    DpStage S(ctx, images, n);
+    if (int rc = dp_stage_in(ctx, images, masks, n, grad, S)) return rc;
+    const SeamPlan plan = seam_plan(seam_frames(corners, images, n), SEAM_ORDER_DISTANCE);
+    dp_solve_levels(plan, corners, S.im, S.mk, grad);
+    const auto t_solved = Clock::now();
+    if (int rc = dp_stage_out(ctx, masks, n, S)) return rc;
+    if (trace) {
+        fprintf(stderr, "dp seams wall: load %.2f ms (issue %.2f, sync %.2f, convert %.2f), pairs %.2f ms, store %.2f ms\n", ms(t_begin, S.t_loaded), ms(t_begin, S.t_issued), ms(S.t_issued, S.t_synced), ms(S.t_synced, S.t_loaded), ms(S.t_loaded, t_solved), ms(t_solved, Clock::now()));
+        fprintf(stderr, "dp seams: %zu overlapping pairs in %d levels; ms (summed over threads): setup+all %.2f components %.2f edges %.2f tips %.2f estimate %.2f labels %.2f rescan %.2f\n", plan.pairs.size(), plan.nlevels,
                 g_seam_ns[0] / 1e6, g_seam_ns[1] / 1e6, g_seam_ns[2] / 1e6, g_seam_ns[3] / 1e6, g_seam_ns[4] / 1e6, g_seam_ns[5] / 1e6, g_seam_ns[6] / 1e6);
         for (auto& v : g_seam_ns) v = 0;
     }

@@ -7,8 +7,9 @@
 // (the nodes the source reaches in the residual graph), which is the same set for every maximum flow: the result is a property of
 // the input and is pinned bit for bit to the numpy / scipy reference tests/refimpl_seam_graphcut.py (tests/test_seam_graphcut_gpu.py).
 //
-// The whole finder runs on the device, on gathered copies of the images and masks.  The pairs of one dependency level (pairs
-// that share no image; a pair waits for every earlier pair that shares one with it, as in seam.hip) go into one set of launches
+// The whole finder runs on the device, on gathered copies of the images and masks (the packed block and the input contract of
+// seam_stage.h, shared with seam.hip).  The pairs of one dependency level of the pair plan (seam_plan.h, in run order: pairs that
+// share no image; a pair waits for every earlier pair that shares one with it) go into one set of launches
 // with the pair on the grid's y; levels follow each other in stream order.  Per level:
 //   gc_build_kernel          a thread a node: four capacities, the terminal, the start state
 //   gc_relabel_init_kernel   | the global relabel: exact distances to a drain in the residual graph by relaxation sweeps, a tile
@@ -26,6 +27,7 @@
 // (GC_SET_CAP round sets a level, a sweep bound from the grid's size): a bug gives a wrong mask or MIS_E_INTERNAL, not a hang.
 #include "common.h"
 #include "seam_gc_core.h"
+#include "seam_stage.h"
 #include <algorithm>
 #include <cmath>
 
@@ -178,20 +180,11 @@ struct GcDebug {        // mis_seam_graphcut_debug_pair: the one pair to run, an
 
 struct HostPair { int i, j, level; GcPair p; };
 
-// frees the call's device block on every way out
-struct PoolBlock {
-    MisContext* ctx; void* p = nullptr; size_t got = 0;
-    explicit PoolBlock(MisContext* c) : ctx(c) {}
-    ~PoolBlock() { if (p) { hipStreamSynchronize(ctx->stream); mis_pool_free(ctx, p, got); } }
-};
-
 int gc_find(MisContext* ctx, const MisPoint* corners, const MisImage* images, MisImage* masks, int n, float terminal_cost, float penalty, const GcDebug* dbg) {
     // everything is checked before anything is staged or written
     for (int i = 0; i < n; i++) {
         const MisImage& I = images[i];
-        const MisImage& M = masks[i];
-        MIS_CHECK(ctx, I.data && M.data && I.dtype == MIS_U8 && I.channels == 3 && M.dtype == MIS_U8 && M.channels == 1 && I.width == M.width && I.height == M.height &&
-                           I.width > 0 && I.height > 0, MIS_E_INVALID, "image %d: need an 8UC3 image and an 8U mask of the same size", i);
+        if (int rc = seam_check_input(ctx, I, masks[i], i)) return rc;
         MIS_CHECK(ctx, I.width <= 32000 && I.height <= 32000 && std::abs((long long)corners[i].x) < (1 << 28) && std::abs((long long)corners[i].y) < (1 << 28),
                   MIS_E_UNSUPPORTED, "image %d: %dx%d at (%d, %d) is beyond the graph-cut finder's 32-bit node indices", i, I.width, I.height, corners[i].x, corners[i].y);
     }
@@ -199,31 +192,26 @@ int gc_find(MisContext* ctx, const MisPoint* corners, const MisImage* images, Mi
     if (n == 0) return MIS_OK;
     MIS_HIP(ctx, hipSetDevice(ctx->device));
 
-    // PairwiseSeamFinder::run: for i, for j > i, the pairs whose rectangles overlap; a pair's level is one above the highest level
-    // among the earlier pairs that share an image with it
+    // the pair plan in PairwiseSeamFinder::run order; the debug entry plans its one pair alone
+    std::vector<SeamFrame> frames = seam_frames(corners, images, n);
+    if (dbg) frames = {frames[dbg->i], frames[dbg->j]};
+    const SeamPlan plan = seam_plan(frames, SEAM_ORDER_RUN);
+    const int nlevels = plan.nlevels;
     std::vector<HostPair> work;
-    std::vector<int> last((size_t)n, 0);
-    int nlevels = 0;
-    for (int i = 0; i + 1 < n; i++)
-        for (int j = i + 1; j < n; j++) {
-            if (dbg && (i != dbg->i || j != dbg->j)) continue;
-            const int x0 = std::max(corners[i].x, corners[j].x), y0 = std::max(corners[i].y, corners[j].y);
-            const int x1 = std::min(corners[i].x + images[i].width, corners[j].x + images[j].width), y1 = std::min(corners[i].y + images[i].height, corners[j].y + images[j].height);
-            if (!(x0 < x1 && y0 < y1)) continue;
-            HostPair hp{};
-            hp.i = i; hp.j = j;
-            hp.level = std::max(last[i], last[j]) + 1;
-            last[i] = last[j] = hp.level;
-            nlevels = std::max(nlevels, hp.level);
-            GcPair& p = hp.p;
-            p.w1 = images[i].width; p.h1 = images[i].height; p.w2 = images[j].width; p.h2 = images[j].height;
-            p.ox1 = x0 - GC_GAP - corners[i].x; p.oy1 = y0 - GC_GAP - corners[i].y; p.ox2 = x0 - GC_GAP - corners[j].x; p.oy2 = y0 - GC_GAP - corners[j].y;
-            p.gw = x1 - x0 + 2 * GC_GAP; p.gh = y1 - y0 + 2 * GC_GAP;
-            p.tiles_x = (p.gw + GC_T - 1) / GC_T; p.tiles_y = (p.gh + GC_T - 1) / GC_T;
-            MIS_CHECK(ctx, (long long)p.gw * p.gh < (1 << 29), MIS_E_UNSUPPORTED, "pair (%d, %d): a grid of %dx%d nodes is beyond 32-bit node indices", i, j, p.gw, p.gh);
-            p.hmax = p.gw * p.gh + 2;
-            work.push_back(hp);
-        }
+    for (const SeamPair& sp : plan.pairs) {
+        const int i = dbg ? dbg->i : sp.i, j = dbg ? dbg->j : sp.j;
+        const SeamRect& r = sp.roi;
+        HostPair hp{};
+        hp.i = i; hp.j = j; hp.level = sp.level;
+        GcPair& p = hp.p;
+        p.w1 = images[i].width; p.h1 = images[i].height; p.w2 = images[j].width; p.h2 = images[j].height;
+        p.ox1 = r.x0 - GC_GAP - corners[i].x; p.oy1 = r.y0 - GC_GAP - corners[i].y; p.ox2 = r.x0 - GC_GAP - corners[j].x; p.oy2 = r.y0 - GC_GAP - corners[j].y;
+        p.gw = r.x1 - r.x0 + 2 * GC_GAP; p.gh = r.y1 - r.y0 + 2 * GC_GAP;
+        p.tiles_x = (p.gw + GC_T - 1) / GC_T; p.tiles_y = (p.gh + GC_T - 1) / GC_T;
+        MIS_CHECK(ctx, (long long)p.gw * p.gh < (1 << 29), MIS_E_UNSUPPORTED, "pair (%d, %d): a grid of %dx%d nodes is beyond 32-bit node indices", i, j, p.gw, p.gh);
+        p.hmax = p.gw * p.gh + 2;
+        work.push_back(hp);
+    }
     if (dbg) {
         MIS_CHECK(ctx, !work.empty(), MIS_E_INVALID, "debug pair (%d, %d): the images do not overlap", dbg->i, dbg->j);
         *dbg->grid_w = work[0].p.gw; *dbg->grid_h = work[0].p.gh;
@@ -252,19 +240,16 @@ int gc_find(MisContext* ctx, const MisPoint* corners, const MisImage* images, Mi
     for (int l = 0; l < nlevels; l++) { if (lv_first[l + 1] < lv_first[l]) lv_first[l + 1] = lv_first[l]; max_pairs = std::max(max_pairs, lv_first[l + 1] - lv_first[l]); }
 
     // the device block: packed images and masks, the pair table, the counters, the 12 planes
-    std::vector<size_t> ioff((size_t)n), moff((size_t)n);
-    size_t total = 0;
-    for (int i = 0; i < n; i++) {
-        ioff[i] = total; total += mis_align_up((size_t)images[i].width * images[i].height * 3, 256);
-        moff[i] = total; total += mis_align_up((size_t)images[i].width * images[i].height, 256);
-    }
+    const SeamSlots slots(images, n);
+    const std::vector<size_t>&ioff = slots.ioff, &moff = slots.moff;
+    size_t total = slots.bytes;
     const size_t table_off = total; total += mis_align_up(std::max<size_t>(1, work.size()) * sizeof(GcPair), 256);
     const int n_ctr = max_pairs * (2 + GC_K) + GC_SWEEP_BATCH;
     const size_t ctr_off = total; total += mis_align_up((size_t)n_ctr * sizeof(int), 256);
     const size_t plane_bytes = mis_align_up((size_t)plane_elems * sizeof(int), 256);
     const size_t planes_off = total; total += 12 * plane_bytes;
     PoolBlock blk(ctx);
-    if (int rc = mis_pool_alloc(ctx, total, &blk.p, &blk.got)) { blk.p = nullptr; return rc; }
+    if (int rc = blk.alloc(total)) return rc;
     uint8_t* d = (uint8_t*)blk.p;
     // the pinned job block: the pair table on its way up, the counters on their way down, the debug planes
     const size_t pin_ctr = mis_align_up(std::max<size_t>(1, work.size()) * sizeof(GcPair), 256);
@@ -276,10 +261,8 @@ int gc_find(MisContext* ctx, const MisPoint* corners, const MisImage* images, Mi
     int* hctr = (int*)(pin + pin_ctr);
 
     for (int i = 0; i < n; i++) {
-        const MisImage& I = images[i];
-        const MisImage& M = masks[i];
-        MIS_HIP(ctx, hipMemcpy2DAsync(d + ioff[i], (size_t)I.width * 3, I.data, I.stride, (size_t)I.width * 3, I.height, I.mem == MIS_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
-        MIS_HIP(ctx, hipMemcpy2DAsync(d + moff[i], M.width, M.data, M.stride, M.width, M.height, M.mem == MIS_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
+        MIS_HIP(ctx, seam_gather(d + ioff[i], images[i], ctx->stream));
+        MIS_HIP(ctx, seam_gather(d + moff[i], masks[i], ctx->stream));
     }
     for (size_t k = 0; k < work.size(); k++) {
         GcPair& p = work[k].p;
@@ -367,10 +350,7 @@ int gc_find(MisContext* ctx, const MisPoint* corners, const MisImage* images, Mi
     }
     if (dbg) return MIS_OK;
     // every level has finished: the masks go back to the caller, once
-    for (int i = 0; i < n; i++) {
-        const MisImage& M = masks[i];
-        MIS_HIP(ctx, hipMemcpy2DAsync(M.data, M.stride, d + moff[i], M.width, M.width, M.height, M.mem == MIS_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ctx->stream));
-    }
+    for (int i = 0; i < n; i++) MIS_HIP(ctx, seam_scatter(masks[i], d + moff[i], ctx->stream));
     MIS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return MIS_OK;
 }

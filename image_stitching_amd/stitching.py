@@ -70,6 +70,26 @@ def as_image(a):
     return img
 
 
+def _c_array(ctype, values):
+    """values as a C array of ctype; at least one element long, so that n = 0 still hands the library a valid pointer."""
+    values = list(values)
+    return (ctype * max(len(values), 1))(*values)
+
+
+def _points(pts):
+    return _c_array(capi.MisPoint, (capi.MisPoint(int(p[0]), int(p[1])) for p in pts))
+
+
+def _images(arrays):
+    """The MisImage array of tensors / arrays, which stay the caller's to keep alive for the call."""
+    return _c_array(capi.MisImage, (as_image(a) for a in arrays))
+
+
+def _seam_args(corners, images, masks):
+    """The (corners, images, masks, n) arguments of the compensator's and the seam finders' entries."""
+    return _points(corners), _images(images), _images(masks), len(masks)
+
+
 def _empty_image(ctx, h, w, c, tdtype):
     """Device image with 256-byte aligned row pitch, returned as a (possibly strided) tensor view."""
     es = torch.empty((), dtype=tdtype).element_size()
@@ -238,9 +258,9 @@ class RotationWarper:
     def _batch_args(imgs, cameras, rois, dsts, masks):
         """The C arrays of a batched fused warp -> (im, ds, ms, Ks, Rs, rs, tls); Ks / Rs are the numpy arrays (they own the floats)."""
         n = len(imgs)
-        im = (capi.MisImage * n)(*[as_image(i) for i in imgs])
-        ds = (capi.MisImage * n)(*[as_image(d) for d in dsts])
-        ms = (capi.MisImage * n)(*[as_image(m) for m in masks])
+        im = _images(imgs)
+        ds = _images(dsts)
+        ms = _images(masks)
         Ks = np.ascontiguousarray(np.stack([np.asarray(c["K"], np.float32).reshape(9) for c in cameras]))
         Rs = np.ascontiguousarray(np.stack([np.asarray(c["R"], np.float32).reshape(9) for c in cameras]))
         rs = (capi.MisRect * n)(*[capi.MisRect(int(r[0]), int(r[1]), int(r[2]), int(r[3])) for r in rois])
@@ -386,8 +406,8 @@ def resize_batch(ctx, frames, fx, fy, out=None):
         dw, dh = int(np.rint(simgs[0].width * fx)), int(np.rint(simgs[0].height * fy))   # cvRound: half to even
         out = [_empty_image(ctx, dh, dw, simgs[0].channels, torch.uint8) for _ in range(n)]
     out = list(out)[:n]
-    sa = (capi.MisImage * n)(*simgs)
-    da = (capi.MisImage * n)(*[as_image(o) for o in out])
+    sa = _c_array(capi.MisImage, simgs)
+    da = _images(out)
     ctx.check(ctx.lib.mis_resize_linear_exact_batch(ctx.h, sa, n, 0, 0, float(fx), float(fy), da))
     return out
 
@@ -435,11 +455,7 @@ class _Compensator:
             pass
 
     def feed(self, corners, images, masks):
-        n = len(images)
-        cs = (capi.MisPoint * n)(*[capi.MisPoint(int(c[0]), int(c[1])) for c in corners])
-        im = (capi.MisImage * n)(*[as_image(i) for i in images])
-        mk = (capi.MisImage * n)(*[as_image(m) for m in masks])
-        self.ctx.check(self.ctx.lib.mis_compensator_feed(self.h, cs, im, mk, n))
+        self.ctx.check(self.ctx.lib.mis_compensator_feed(self.h, *_seam_args(corners, images, masks)))
 
     def gains(self, index):
         """The accumulated gains of one image as three float64 (B, G, R; GainCompensator: the gain three times); the block types
@@ -523,6 +539,13 @@ def make_compensator(ctx, cfg):
     return None
 
 
+def make_seam_finder(ctx, cfg):
+    """seam_find_type of the config -> the seam finder (image_stitching.cpp:1029-1062), None for "no"."""
+    make = {"voronoi": lambda: VoronoiSeamFinder(ctx), "dp_color": lambda: DpSeamFinder(ctx, DpSeamFinder.COLOR),
+            "dp_colorgrad": lambda: DpSeamFinder(ctx, DpSeamFinder.COLOR_GRAD)}.get(cfg.seam_find_type)
+    return make() if make else None
+
+
 class NoSeamFinder:
     """seam_find_type "no" (image_stitching.cpp:1029): masks stay as warped."""
 
@@ -538,8 +561,8 @@ class VoronoiSeamFinder:
 
     def find(self, images, corners, masks):
         n = len(masks)
-        cs = (capi.MisPoint * n)(*[capi.MisPoint(int(c[0]), int(c[1])) for c in corners])
-        mk = (capi.MisImage * n)(*[as_image(m) for m in masks])
+        cs = _points(corners)
+        mk = _images(masks)
         self.ctx.check(self.ctx.lib.mis_seam_voronoi(self.ctx.h, cs, mk, n))
         return masks
 
@@ -562,10 +585,7 @@ class DpSeamFinder:
         self.ctx, self.cost_func = ctx, cost_func
 
     def find(self, images, corners, masks):
-        n = len(masks)
-        cs = (capi.MisPoint * n)(*[capi.MisPoint(int(c[0]), int(c[1])) for c in corners])
-        im = (capi.MisImage * n)(*[as_image(i) for i in images])
-        mk = (capi.MisImage * n)(*[as_image(m) for m in masks])
+        cs, im, mk, n = _seam_args(corners, images, masks)
         if self.cost_func == DpSeamFinder.COLOR_GRAD:
             self.ctx.check(self.ctx.lib.mis_seam_dp_colorgrad(self.ctx.h, cs, im, mk, n))
         else:
@@ -590,11 +610,7 @@ class GraphCutSeamFinder:
         self.terminal_cost, self.bad_region_penalty = float(terminal_cost), float(bad_region_penalty)
 
     def find(self, images, corners, masks):
-        n = len(masks)
-        k = max(n, 1)
-        cs = (capi.MisPoint * k)(*[capi.MisPoint(int(c[0]), int(c[1])) for c in corners])
-        im = (capi.MisImage * k)(*[as_image(i) for i in images])
-        mk = (capi.MisImage * k)(*[as_image(m) for m in masks])
+        cs, im, mk, n = _seam_args(corners, images, masks)
         self.ctx.check(self.ctx.lib.mis_seam_graphcut(self.ctx.h, cs, im, mk, n, GraphCutSeamFinder.COST_TYPES[self.cost_type],
                                                       self.terminal_cost, self.bad_region_penalty))
         return masks
@@ -614,10 +630,7 @@ class GraphCutSeamFinder:
     def debug_pair(self, images, corners, masks, i, j):
         """mis_seam_graphcut_debug_pair: pair (i, j) on the masks as given -> (cap_right, cap_down, terminals, labels), numpy planes
         of the pair's grid (the gap included); nothing is edited."""
-        n = len(masks)
-        cs = (capi.MisPoint * n)(*[capi.MisPoint(int(c[0]), int(c[1])) for c in corners])
-        im = (capi.MisImage * n)(*[as_image(x) for x in images])
-        mk = (capi.MisImage * n)(*[as_image(m) for m in masks])
+        cs, im, mk, n = _seam_args(corners, images, masks)
         gw, gh = C.c_int(0), C.c_int(0)
         self.ctx.check(self.ctx.lib.mis_seam_graphcut_debug_pair(self.ctx.h, cs, im, mk, n, i, j, None, None, None, None, 0, C.byref(gw), C.byref(gh)))
         shape = (gh.value, gw.value)
@@ -644,10 +657,9 @@ def seam_gradients(ctx, images, gradx=None, grady=None):
     gx, gy = planes(gradx), planes(grady)
     if len(gx) != n or len(gy) != n:
         raise ValueError("seam_gradients: %d images, %d gradx and %d grady planes" % (n, len(gx), len(gy)))
-    k = max(n, 1)
-    im = (capi.MisImage * k)(*[as_image(i) for i in images])
-    ax = (capi.MisImage * k)(*[as_image(g) for g in gx])
-    ay = (capi.MisImage * k)(*[as_image(g) for g in gy])
+    im = _images(images)
+    ax = _images(gx)
+    ay = _images(gy)
     ctx.check(ctx.lib.mis_seam_gradients(ctx.h, im, n, ax, ay))
     return gx, gy
 
@@ -657,7 +669,7 @@ def seam_gradients(ctx, images, gradx=None, grady=None):
 def result_roi(corners, sizes):
     lib = capi.load()
     n = len(corners)
-    cs = (capi.MisPoint * n)(*[capi.MisPoint(int(c[0]), int(c[1])) for c in corners])
+    cs = _points(corners)
     ss = (capi.MisSize * n)(*[capi.MisSize(int(s[0]), int(s[1])) for s in sizes])
     r = capi.MisRect()
     rc = lib.mis_result_roi(cs, ss, n, C.byref(r))
@@ -692,7 +704,7 @@ class Blender:
 
     def prepare(self, corners, sizes):
         n = len(corners)
-        cs = (capi.MisPoint * n)(*[capi.MisPoint(int(c[0]), int(c[1])) for c in corners])
+        cs = _points(corners)
         ss = (capi.MisSize * n)(*[capi.MisSize(int(s[0]), int(s[1])) for s in sizes])
         self.ctx.check(self.ctx.lib.mis_blender_prepare(self.h, cs, ss, n))
         x, y, w, h = result_roi(corners, sizes)
@@ -704,7 +716,7 @@ class Blender:
         n = len(frames)
         if n == 0:
             return
-        arr = (capi.MisImage * n)(*[as_image(f) for f in frames])
+        arr = _images(frames)
         Ks = np.ascontiguousarray(np.stack([np.asarray(c["K"], np.float32).reshape(9) for c in cameras]))
         Rs = np.ascontiguousarray(np.stack([np.asarray(c["R"], np.float32).reshape(9) for c in cameras]))
         rr = (capi.MisRect * n)(*[capi.MisRect(int(r[0]), int(r[1]), int(r[2]), int(r[3])) for r in rois])
@@ -718,9 +730,9 @@ class Blender:
     def feed_batch(self, imgs, masks, tls):
         """n feeds in one call (mis_blender_feed_batch): the result of feed(imgs[0], ...) ... feed(imgs[n - 1], ...) in that order."""
         n = len(imgs)
-        im = (capi.MisImage * n)(*[as_image(i) for i in imgs])
-        mk = (capi.MisImage * n)(*[as_image(m) for m in masks])
-        ts = (capi.MisPoint * n)(*[capi.MisPoint(int(t[0]), int(t[1])) for t in tls])
+        im = _images(imgs)
+        mk = _images(masks)
+        ts = _points(tls)
         self.ctx.check(self.ctx.lib.mis_blender_feed_batch(self.h, im, mk, ts, n))
 
     def blend(self):
@@ -902,7 +914,7 @@ class OrbFeatureFinder:
 
     def detect_batch(self, imgs):
         n = len(imgs)
-        arr = (capi.MisImage * n)(*[as_image(i) for i in imgs])
+        arr = _images(imgs)
         raws = (capi.MisFeatures * n)()
         self.ctx.check(self.ctx.lib.mis_orb_detect_batch(self.h, arr, n, raws))
         out = []
@@ -957,7 +969,7 @@ class SiftFeatureFinder:
         n = len(imgs)
         if n == 0:
             return []
-        arr = (capi.MisImage * n)(*[as_image(im) for im in imgs])
+        arr = _images(imgs)
         raws = (capi.MisFeatures * n)()
         self.ctx.check(self.ctx.lib.mis_sift_detect_batch(self.h, arr, n, raws))
         out = []
@@ -1426,14 +1438,10 @@ def seam_solve(ctx, cfg, corners, images_warped, masks_warped, seam_finder=None)
     compensator = make_compensator(ctx, cfg)
     if compensator is not None:
         compensator.feed(corners, images_warped, masks_warped)
+    if seam_finder is None:
+        seam_finder = make_seam_finder(ctx, cfg)
     if seam_finder is not None:
         seam_finder.find(images_warped, corners, masks_warped)
-    elif cfg.seam_find_type == "voronoi":
-        VoronoiSeamFinder(ctx).find(images_warped, corners, masks_warped)
-    elif cfg.seam_find_type == "dp_color":
-        DpSeamFinder(ctx, DpSeamFinder.COLOR).find(images_warped, corners, masks_warped)
-    elif cfg.seam_find_type == "dp_colorgrad":
-        DpSeamFinder(ctx, DpSeamFinder.COLOR_GRAD).find(images_warped, corners, masks_warped)
     return compensator, masks_warped
 
 

@@ -1,5 +1,5 @@
-"""GPU: the kernels of the step between warp and blend (expos.hip: overlap statistics, gain application, the Voronoi distance
-scans; imgops.hip: the fused seam-mask kernel) against the numpy reference of tests/refimpl_expos.py, over the scenes and block
+"""GPU: the kernels of the step between warp and blend (expos.hip: overlap statistics, gain application; seam_voronoi.hip: the
+Voronoi distance scans; imgops.hip: the fused seam-mask kernel) against the numpy reference of tests/refimpl_expos.py, over the scenes and block
 geometries of test_refimpl_expos_cpu.py: gain maps within the derived float32 bound, Voronoi and seam masks exactly, every
 applied byte inside its candidate range; then the memory forms (dense device tensors, host arrays, pitched device views that
 start at an odd address), which must agree byte for byte and leave everything outside a view untouched."""

@@ -9,8 +9,10 @@ dp_colorgrad alternate inside one process and the spread of the windows is repor
 between two device events around a window of mis_seam_gradients calls on device buffers (launch gaps included, no copies).  The
 host figure times tests/refimpl_seam_dp_grad.gradients (numpy) on one seam-scale frame and multiplies by 2 x the number of
 overlapping pairs: reported, not asserted.
---baseline-lib (default with --parent-tree: that tree's library): the parent's dp_color call alternates with this tree's two in
-the same windows, through the same argument arrays, and its masks are compared byte for byte.
+The Voronoi finder's call is timed by the same host clocks in the same alternation.
+--baseline-lib (default with --parent-tree: that tree's library): the parent's dp_color, dp_colorgrad and Voronoi calls alternate
+with this tree's in the same windows, through the same argument arrays; every finder's masks are compared byte for byte and its
+median is held to the parent's own window spread.
 --parent-tree: `bench.py --pipeline reference` (dp_color inside the whole job) runs alternately in that tree and in this one, in
 fresh processes before this one opens the device, then the default metric once in each; the lines go into the file with the
 verdict "inside the parent's own spread".  Needs a GPU."""
@@ -106,17 +108,27 @@ def main():
     im = (capi.MisImage * n)(*[st.as_image(i) for i in images])
     mk = (capi.MisImage * n)(*[st.as_image(m) for m in work])
     finders = {"dp_color": lambda: ctx.check(ctx.lib.mis_seam_dp(ctx.h, cs, im, mk, n, 0)),
-               "dp_colorgrad": lambda: ctx.check(ctx.lib.mis_seam_dp_colorgrad(ctx.h, cs, im, mk, n))}
-    if a.baseline_lib:      # the parent's dp_color through its own build of the library, on a context of its own over the same stream
+               "dp_colorgrad": lambda: ctx.check(ctx.lib.mis_seam_dp_colorgrad(ctx.h, cs, im, mk, n)),
+               "voronoi": lambda: ctx.check(ctx.lib.mis_seam_voronoi(ctx.h, cs, mk, n))}
+    if a.baseline_lib:      # the parent's finders through its own build of the library, on a context of its own over the same stream
         plib = C.CDLL(os.path.abspath(a.baseline_lib))
         pctx = C.c_void_p()
+        pp, pi = C.POINTER(capi.MisPoint), C.POINTER(capi.MisImage)
         plib.mis_context_create.argtypes = [C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]
-        plib.mis_seam_dp.argtypes = [C.c_void_p, C.POINTER(capi.MisPoint), C.POINTER(capi.MisImage), C.POINTER(capi.MisImage), C.c_int, C.c_int]
+        plib.mis_seam_dp.argtypes = [C.c_void_p, pp, pi, pi, C.c_int, C.c_int]
+        plib.mis_seam_dp_colorgrad.argtypes = [C.c_void_p, pp, pi, pi, C.c_int]
+        plib.mis_seam_voronoi.argtypes = [C.c_void_p, pp, pi, C.c_int]
         assert plib.mis_context_create(0, C.c_void_p(torch.cuda.current_stream().cuda_stream), C.byref(pctx)) == 0
 
         def parent_dp_color():
             assert plib.mis_seam_dp(pctx, cs, im, mk, n, 0) == 0
-        finders = {"parent_dp_color": parent_dp_color, **finders}
+
+        def parent_dp_colorgrad():
+            assert plib.mis_seam_dp_colorgrad(pctx, cs, im, mk, n) == 0
+
+        def parent_voronoi():
+            assert plib.mis_seam_voronoi(pctx, cs, mk, n) == 0
+        finders = {"parent_dp_color": parent_dp_color, "parent_dp_colorgrad": parent_dp_colorgrad, "parent_voronoi": parent_voronoi, **finders}
 
     def call(f):
         for w, m in zip(work, masks):
@@ -190,6 +202,13 @@ def main():
         res["dp_color_over_parent"] = new["median_ms"] / old["median_ms"]
         res["dp_color_slower_beyond_parent_spread"] = new["median_ms"] - old["median_ms"] > old["spread_ms"]
         res["dp_color_masks_equal_parent"] = all(torch.equal(x, y) for x, y in zip(result["dp_color"], result["parent_dp_color"]))
+        # every finder against the parent's build: the median inside the parent's own window spread, the masks byte for byte
+        res["against_parent"] = {k: {"median_difference_ms": res["find_ms"][k]["median_ms"] - res["find_ms"]["parent_" + k]["median_ms"],
+                                     "parent_spread_ms": res["find_ms"]["parent_" + k]["spread_ms"],
+                                     "median_inside_parent_windows": res["find_ms"]["parent_" + k]["min_ms"] <= res["find_ms"][k]["median_ms"] <= res["find_ms"]["parent_" + k]["max_ms"],
+                                     "median_difference_within_parent_spread": abs(res["find_ms"][k]["median_ms"] - res["find_ms"]["parent_" + k]["median_ms"]) <= res["find_ms"]["parent_" + k]["spread_ms"],
+                                     "masks_equal_parent": all(torch.equal(x, y) for x, y in zip(result[k], result["parent_" + k]))}
+                                 for k in ("dp_color", "dp_colorgrad", "voronoi")}
     res["dp_colorgrad_masks_differ_from_dp_color"] = not all(torch.equal(x, y) for x, y in zip(result["dp_color"], result["dp_colorgrad"]))
     if trees:
         res["bench_py"] = trees

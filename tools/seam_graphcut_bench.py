@@ -11,9 +11,11 @@ graph-cut finder alternate inside one process, the spread of the windows (max - 
 is reported whichever way it falls.  --profile-run: a warm-up and three graph-cut calls, nothing written -- the run to put under
 the profiler, whose kernel statistics --kernel-stats then folds into the file (the gc_* rows).  --parent-tree: bench.py's default
 metric runs alternately in that tree and in this one, in fresh processes before this one opens the device; the hot path does not
-touch the new file, the lines must agree within +- 3 %.  Needs a GPU."""
+touch the new file, the lines must agree within +- 3 %; that tree's library also runs its own graph-cut call in the finders'
+alternation, through the same argument arrays, and its masks are compared byte for byte.  Needs a GPU."""
 import argparse
 import csv
+import ctypes as C
 import json
 import os
 import statistics
@@ -99,6 +101,16 @@ def main():
     mk = (capi.MisImage * n)(*[st.as_image(m) for m in work])
     finders = {"dp_color": lambda: ctx.check(ctx.lib.mis_seam_dp(ctx.h, cs, im, mk, n, 0)),
                "graphcut": lambda: ctx.check(ctx.lib.mis_seam_graphcut(ctx.h, cs, im, mk, n, 0, 10000.0, 1000.0))}
+    if a.parent_tree and not a.profile_run:     # the parent's graph-cut call through its own build of the library, on a context of its own over the same stream
+        plib = C.CDLL(os.path.join(os.path.abspath(a.parent_tree), "image_stitching_amd", "libmistitch.so"))
+        pctx = C.c_void_p()
+        plib.mis_context_create.argtypes = [C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]
+        plib.mis_seam_graphcut.argtypes = [C.c_void_p, C.POINTER(capi.MisPoint), C.POINTER(capi.MisImage), C.POINTER(capi.MisImage), C.c_int, C.c_int, C.c_float, C.c_float]
+        assert plib.mis_context_create(0, C.c_void_p(torch.cuda.current_stream().cuda_stream), C.byref(pctx)) == 0
+
+        def parent_graphcut():
+            assert plib.mis_seam_graphcut(pctx, cs, im, mk, n, 0, 10000.0, 1000.0) == 0
+        finders = {"parent_graphcut": parent_graphcut, **finders}
 
     def call(f):
         for w, m in zip(work, masks):
@@ -147,6 +159,12 @@ def main():
                         "worst_round_sets": max(stats["round_sets"] or [0]), "round_set_cap": stats["round_set_cap"], "global_relabels": stats["relabels"],
                         "relabel_sweeps": stats["sweeps"], "second_call_gives_the_same_masks": bool(repeat_equal)},
            "mask_pixels_removed": changed}
+    if "parent_graphcut" in finders:
+        new, old = res["find_ms"]["graphcut"], res["find_ms"]["parent_graphcut"]
+        res["graphcut_against_parent"] = {"median_difference_ms": new["median_ms"] - old["median_ms"], "parent_spread_ms": old["spread_ms"],
+                                          "median_inside_parent_windows": old["min_ms"] <= new["median_ms"] <= old["max_ms"],
+                                          "median_difference_within_parent_spread": abs(new["median_ms"] - old["median_ms"]) <= old["spread_ms"],
+                                          "masks_equal_parent": all(torch.equal(x, y) for x, y in zip(result["graphcut"], result["parent_graphcut"]))}
     if a.kernel_stats:
         res["graphcut_kernels_rocprofv3"] = {"source": "rocprofv3 --kernel-trace --stats over --profile-run (a warm-up and three calls: 4 calls in all)", "rows": kernel_rows(a.kernel_stats)}
     if trees:
