@@ -46,6 +46,8 @@ JobCore::JobCore(const char* who, std::string where, int device, void* main_stre
     try {
         if (cfg_.features_type != "orb" || cfg_.ba_cost_func != "no" || cfg_.expos_comp_type != "no" || cfg_.seam_find_type != "no")
             throw std::runtime_error(std::string(who) + " runs the hot path (ORB, supplied cameras, no seam-scale step); use mis::Stitcher for the other options");
+        if (mode_is_scans(cfg_.mode))       // the jobs speculate the composition from supplied cameras; the scans mode has none
+            throw std::runtime_error(std::string(who) + " runs supplied cameras only; the scans mode is mis::Stitcher's");
         kind_ = warp_kind(cfg_.warp_type);
         check_range_width(cfg_.range_width);
         model_ = matcher_model(cfg_.matcher_type, cfg_.range_width);

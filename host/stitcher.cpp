@@ -51,7 +51,13 @@ CameraParams cameraFromImageDescription(const std::string& desc, bool* isPortrai
     return p;
 }
 
-Stitcher::Stitcher(int device, const StitchConfig& cfg) : cfg_(cfg) {
+// the scans mode as Stitcher::create(SCANS) sets it up: what the mode replaces is not read from the configuration
+static StitchConfig effective_config(StitchConfig cfg) {
+    if (mode_is_scans(cfg.mode)) { cfg.matcher_type = "affine"; cfg.wave_correct = "no"; cfg.expos_comp_type = "no"; }
+    return cfg;
+}
+
+Stitcher::Stitcher(int device, const StitchConfig& cfg) : cfg_(effective_config(cfg)) {
     int rc = mis_context_create(device, nullptr, &ctx_);
     if (rc != MIS_OK) throw std::runtime_error("mis_context_create failed: no HIP device (there is no CPU fallback)");
 }
@@ -88,9 +94,14 @@ static const SeamFinderEntry& seam_finder(const std::string& type) {
 
 StitchResult Stitcher::stitch(const std::vector<HostImage>& frames, const std::vector<CameraParams>& cams_in) {
     const int n = (int)frames.size();
-    if (n < 2 || (int)cams_in.size() != n) throw std::runtime_error("Need more images");
+    const bool scans = mode_is_scans(cfg_.mode);
+    if (n < 2 || (scans ? !cams_in.empty() : (int)cams_in.size() != n)) throw std::runtime_error("Need more images");
     StitchResult out;
     std::vector<CameraParams> cameras = cams_in;
+    if (scans) {        // default CameraParams until the estimator runs (focal 1, ppx = ppy = 0, R = I)
+        cameras.assign(n, CameraParams());
+        for (auto& c : cameras) c.R(0, 0) = c.R(1, 1) = c.R(2, 2) = 1;
+    }
     const int W = frames[0].width, H = frames[0].height;
 
     // ---- features (image_stitching.cpp:545, :567-622) on the work images (:589-603: every frame resized by work_scale, one launch) ----
@@ -102,7 +113,7 @@ StitchResult Stitcher::stitch(const std::vector<HostImage>& frames, const std::v
         throw std::runtime_error("bundle adjustment cost function '" + cfg_.ba_cost_func + "' is not implemented ('no', 'reproj' and 'ray' are)");
     const int expos_kind = expos_comp_kind(cfg_.expos_comp_type, cfg_.expos_comp_nr_feeds);
     const SeamFinderEntry& seam = seam_finder(cfg_.seam_find_type);
-    const int kind = warp_kind(cfg_.warp_type);
+    const int kind = scans ? MIS_WARP_AFFINE : warp_kind(cfg_.warp_type);
     check_range_width(cfg_.range_width);
     const int model = matcher_model(cfg_.matcher_type, cfg_.range_width);
     MisOrb* orb = nullptr;
@@ -144,7 +155,8 @@ StitchResult Stitcher::stitch(const std::vector<HostImage>& frames, const std::v
     mis_leave_biggest_component(pairwise.data(), n, cfg_.conf_thresh, out.indices.data(), &kept);
     out.indices.resize(kept);
     // ---- camera refinement on the kept subset (:671-726): bundle adjustment (reprojection or ray cost), wave correction ----
-    if (kept >= 2 && cfg_.ba_cost_func != "no") {
+    //      in the scans mode: AffineBasedEstimator on the kept subset's table, then BundleAdjusterAffinePartial
+    if (kept >= 2 && (scans || cfg_.ba_cost_func != "no")) {
         std::vector<MisFeatures> fsub(kept);
         std::vector<MisMatchesInfo> psub((size_t)kept * kept);
         std::vector<MisCameraParams> cp(kept);
@@ -160,7 +172,9 @@ StitchResult Stitcher::stitch(const std::vector<HostImage>& frames, const std::v
             std::copy(c.R.m.begin(), c.R.m.end(), cp[a].R);
             std::copy(c.t.begin(), c.t.end(), cp[a].t);
         }
-        const int ba_rc = cfg_.ba_cost_func == "ray" ? mis_bundle_adjust_ray(ctx_, fsub.data(), psub.data(), kept, cfg_.conf_thresh, cp.data())
+        if (scans) check(mis_estimate_affine_cameras(psub.data(), kept, cp.data()), "mis_estimate_affine_cameras");
+        const int ba_rc = scans ? mis_bundle_adjust_affine_partial(ctx_, fsub.data(), psub.data(), kept, cfg_.conf_thresh, cp.data())
+                        : cfg_.ba_cost_func == "ray" ? mis_bundle_adjust_ray(ctx_, fsub.data(), psub.data(), kept, cfg_.conf_thresh, cp.data())
                                                      : mis_bundle_adjust_reproj(ctx_, fsub.data(), psub.data(), kept, cfg_.conf_thresh, cfg_.ba_refine_mask.c_str(), cp.data());
         if (ba_rc != MIS_OK)
             throw std::runtime_error(std::string("Camera parameters adjusting failed: ") + mis_last_error(ctx_));
@@ -218,7 +232,7 @@ StitchResult Stitcher::stitch(const std::vector<HostImage>& frames, const std::v
         // (a roi that scans every source pixel: the batch entry runs that on the device)
         if ((MIS_WARP_ROI_IS_FULL_SCAN(kind) ? mis_warper_roi_batch(ctx_, kind, compose_warp_scale, cW, cH, 1, cKs[k].data(), Rs[k].data(), &roi)
                                        : mis_warper_roi(kind, compose_warp_scale, cW, cH, cKs[k].data(), Rs[k].data(), &roi)) != MIS_OK)
-            throw std::runtime_error("mis_warper_roi failed: frame " + std::to_string(out.indices[k]) + " has no " + cfg_.warp_type + " warp roi");
+            throw std::runtime_error("mis_warper_roi failed: frame " + std::to_string(out.indices[k]) + " has no " + (scans ? std::string("affine") : cfg_.warp_type) + " warp roi");
         corners[k] = {roi.x, roi.y};
         sizes[k] = {roi.width, roi.height};
     }

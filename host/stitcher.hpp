@@ -40,7 +40,18 @@ struct StitchConfig {
     int range_width = -1;
     // matcher_type (:64, :644-645): "homography" (the two above) | "affine": AffineBestOf2NearestMatcher(false, ...), all pairs
     std::string matcher_type = "homography";
+    // cv::Stitcher::Mode: "panorama" (everything above, cameras supplied by the caller) | "scans" (Stitcher::create(SCANS): flat material
+    // under similarities -- no cameras are supplied; the affine matcher, AffineBasedEstimator, BundleAdjusterAffinePartial and the
+    // AffineWarper run whatever matcher_type, ba_cost_func and warp_type say; no wave correction, no exposure compensation)
+    std::string mode = "panorama";
 };
+
+// mode of the config -> scans?; an unknown name is refused by name
+inline bool mode_is_scans(const std::string& m) {
+    if (m == "panorama") return false;
+    if (m != "scans") throw std::runtime_error("mode '" + m + "': 'panorama' or 'scans' (--mode)");
+    return true;
+}
 
 // matcher_type of the config -> MIS_MATCH_*, the check before any device work.  An unknown name is refused by name; so is "affine"
 // together with a range_width: the reference silently ignores range_width there (:644 comes first), no option is ignored here
@@ -152,7 +163,7 @@ class Stitcher {
 public:
     explicit Stitcher(int device = 0, const StitchConfig& cfg = StitchConfig());
     ~Stitcher();
-    // frames: 8UC3 BGR of one size; cameras: one per frame (sensor / ground-truth K, R)
+    // frames: 8UC3 BGR of one size; cameras: one per frame (sensor / ground-truth K, R); none in the scans mode
     StitchResult stitch(const std::vector<HostImage>& frames, const std::vector<CameraParams>& cameras);
 
 private:

@@ -2,7 +2,7 @@
 
 Host-side mirror (Python) of the interface the reference drives in ``main()``
 (image_stitching/image_stitching.cpp:545-1228): ``computeImageFeatures`` / ``BestOf2NearestMatcher`` /
-``SphericalWarper`` (``CylindricalWarper``, ``PlaneWarper``, ``MercatorWarper``, ``FisheyeWarper``, ``StereographicWarper``, ``CompressedRectilinearWarper``, ``PaniniWarper``) / ``MultiBandBlender`` / ``FeatherBlender``, each a thin veneer over the C ABI of
+``SphericalWarper`` (``CylindricalWarper``, ``PlaneWarper``, ``MercatorWarper``, ``FisheyeWarper``, ``StereographicWarper``, ``CompressedRectilinearWarper``, ``PaniniWarper``, ``AffineWarper``) / ``MultiBandBlender`` / ``FeatherBlender``, each a thin veneer over the C ABI of
 ``libmistitch.so`` (include/mistitch.h).  torch is used only to own device memory and streams.
 
 There is no CPU fallback: everything here needs the HIP library and a GPU.
@@ -10,11 +10,11 @@ There is no CPU fallback: everything here needs the HIP library and a GPU.
 from . import _capi
 from ._capi import (BLEND_FEATHER, BLEND_MULTI_BAND, BLEND_NO, BORDER_CONSTANT, BORDER_REFLECT, INTER_LINEAR,
                     INTER_NEAREST, WARP_CYLINDRICAL, WARP_FISHEYE, WARP_MERCATOR, WARP_PLANE, WARP_SPHERICAL, WARP_STEREOGRAPHIC,
-                    WARP_COMPRESSED_PLANE_A2B1, WARP_COMPRESSED_PLANE_A15B1, WARP_PANINI_A2B1, WARP_PANINI_A15B1)
+                    WARP_COMPRESSED_PLANE_A2B1, WARP_COMPRESSED_PLANE_A15B1, WARP_PANINI_A2B1, WARP_PANINI_A15B1, WARP_AFFINE)
 from .stitching import (AffineBestOf2NearestMatcher, BestOf2NearestMatcher, BestOf2NearestRangeMatcher, estimate_affine_partial, Blender, BlocksGainCompensator, GainCompensator, ChannelsCompensator, BlocksChannelsCompensator, NoSeamFinder, VoronoiSeamFinder, DpSeamFinder, GraphCutSeamFinder, Context, FeatherBlender, ImageFeatures, MatchesInfo,
-                        MisError, MultiBandBlender, OrbFeatureFinder, SiftFeatureFinder, SphericalWarper, CylindricalWarper, PlaneWarper, MercatorWarper, FisheyeWarper, StereographicWarper, CompressedRectilinearWarper, PaniniWarper,
+                        MisError, MultiBandBlender, OrbFeatureFinder, SiftFeatureFinder, SphericalWarper, CylindricalWarper, PlaneWarper, MercatorWarper, FisheyeWarper, StereographicWarper, CompressedRectilinearWarper, PaniniWarper, AffineWarper,
                         RotationWarper, StitchConfig, Stitcher,
-                        blend_config, bundle_adjust_ray, bundle_adjust_reproj, computeImageFeatures, find_homography, leaveBiggestComponent, resize, resize_batch, result_roi,
+                        blend_config, bundle_adjust_affine_partial, bundle_adjust_ray, bundle_adjust_reproj, estimate_affine_cameras, computeImageFeatures, find_homography, leaveBiggestComponent, resize, resize_batch, result_roi,
                         rotate, seam_gradients, seam_mask_apply, selected_pairs, warp_roi, wave_correct, work_geometry)
 
 __all__ = [
@@ -26,4 +26,5 @@ __all__ = [
     "BLEND_MULTI_BAND", "resize_batch", "work_geometry", "CylindricalWarper", "PlaneWarper", "RotationWarper", "WARP_SPHERICAL", "WARP_CYLINDRICAL", "WARP_PLANE", "WARP_MERCATOR", "MercatorWarper", "WARP_FISHEYE", "WARP_STEREOGRAPHIC", "FisheyeWarper", "StereographicWarper",
     "WARP_COMPRESSED_PLANE_A2B1", "WARP_COMPRESSED_PLANE_A15B1", "WARP_PANINI_A2B1", "WARP_PANINI_A15B1", "CompressedRectilinearWarper", "PaniniWarper",
     "BestOf2NearestRangeMatcher", "selected_pairs", "AffineBestOf2NearestMatcher", "estimate_affine_partial", "seam_gradients",
+    "WARP_AFFINE", "AffineWarper", "bundle_adjust_affine_partial", "estimate_affine_cameras",
 ]

@@ -22,6 +22,7 @@ BLEND_NO, BLEND_FEATHER, BLEND_MULTI_BAND = 0, 1, 2
 WARP_SPHERICAL, WARP_CYLINDRICAL, WARP_PLANE, WARP_MERCATOR, WARP_FISHEYE, WARP_STEREOGRAPHIC = 0, 1, 2, 3, 4, 5
 # one kind per (A, B) setting the reference offers (the entries have no slot for the two parameters); 6 and 7 are not assigned
 WARP_COMPRESSED_PLANE_A2B1, WARP_COMPRESSED_PLANE_A15B1, WARP_PANINI_A2B1, WARP_PANINI_A15B1 = 8, 9, 10, 11
+WARP_AFFINE = 13    # cv::detail::AffineWarper: `R` carries the 3x3 homogeneous affine H (12 is not assigned)
 
 
 def roi_is_full_scan(kind):
@@ -160,6 +161,8 @@ PROTOTYPES = {
     "mis_leave_biggest_component_conf": (_i, [_vp, _i, _f, _vp, _P(_i)]),
     "mis_bundle_adjust_reproj": (_i, [_vp, _P(MisFeatures), _P(MisMatchesInfo), _i, _f, C.c_char_p, _P(MisCameraParams)]),
     "mis_bundle_adjust_ray": (_i, [_vp, _P(MisFeatures), _P(MisMatchesInfo), _i, _f, _P(MisCameraParams)]),
+    "mis_bundle_adjust_affine_partial": (_i, [_vp, _P(MisFeatures), _P(MisMatchesInfo), _i, _f, _P(MisCameraParams)]),
+    "mis_estimate_affine_cameras": (_i, [_P(MisMatchesInfo), _i, _P(MisCameraParams)]),
     "mis_wave_correct": (_i, [_vp, _i, _i]),
     "mis_warp_roi": (_i, [_f, _i, _i, _vp, _vp, _P(MisRect)]),
     "mis_warp_spherical": (_i, [_vp, _P(MisImage), _f, _vp, _vp, _i, _i, _P(MisImage), _P(MisPoint)]),

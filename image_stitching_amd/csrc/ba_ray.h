@@ -68,6 +68,15 @@ MIS_HD void ba_ray_observation(const double* rec, int n, int i, int j, double x1
     }
 }
 
+// What the shared evaluators (ba_eval_device.h, the host twins) need to know of an adjuster: record size, errors per observation
+// and the observation itself.  ba_affine.h has the affine-partial adjuster's.
+struct BaRayObsModel {
+    enum { REC = BA_RAY_REC, ERRS = 3 };
+    static MIS_HD void observation(const double* rec, int n, int i, int j, double x1, double y1, double x2, double y2, double* err, double* jac) {
+        ba_ray_observation(rec, n, i, j, x1, y1, x2, y2, err, jac);
+    }
+};
+
 // Chain t of an edge's normal equations: t < 36 the entry (a, b), a <= b, of the 8 x 8 block in row-major order of the upper
 // triangle; t >= 36 the entry a = t - 36 of J^T err.
 MIS_HD void ba_ray_chain(int t, int* a, int* b) {

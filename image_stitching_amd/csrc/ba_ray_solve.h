@@ -10,6 +10,13 @@
 //       int run(MisContext*, bool jac);
 //       const double* err(); const double* partials();
 //   };
+// The loop itself (ba_obs_solve) is shared with BundleAdjusterAffinePartial (ba_affine_solve.h), which has 4 parameters per
+// camera too: what an adjuster brings is its MODEL -- the observation model of ba_ray.h / ba_affine.h plus, on the host,
+//       static constexpr double STEP;                                           // central-difference step
+//       static const char* tag();                                               // for the trace line
+//       static void start(const MisCameraParams&, double q[4]);                 // setUpInitialCameraParams
+//       static void record(const double q[4], const MisFeatures&, double* rec); // the camera record of parameters q
+//       static void refined(const double q[4], MisCameraParams*);               // obtainRefinedCameraParams
 #pragma once
 #include "ba_ray.h"
 #include "motion_host.h"
@@ -26,8 +33,19 @@ void ba_ray_record(const double* q, int img_w, int img_h, double* rec) {
     rec[9] = q[0];
 }
 
-template <class Eval>
-int ba_ray_solve(MisContext* ctx, const MisFeatures* features, const MisMatchesInfo* pairwise, int n, float conf_thresh, MisCameraParams* cameras, Eval& ev) {
+struct BaRayModel : BaRayObsModel {
+    static constexpr double STEP = BA_RAY_STEP;
+    static const char* tag() { return "ray"; }
+    // focal as given, R projected on SO(3) and turned into a rotation vector
+    static void start(const MisCameraParams& c, double* q) { q[0] = c.focal; ba_start_rvec(c.R, q + 1); }
+    static void record(const double* q, const MisFeatures& f, double* rec) { ba_ray_record(q, f.img_w, f.img_h, rec); }
+    // focal and R; ppx, ppy, aspect and t stay as given
+    static void refined(const double* q, MisCameraParams* c) { c->focal = q[0]; ba_refined_R(q + 1, c->R); }
+};
+
+template <class MODEL, class Eval>
+int ba_obs_solve(MisContext* ctx, const MisFeatures* features, const MisMatchesInfo* pairwise, int n, float conf_thresh, MisCameraParams* cameras, Eval& ev) {
+    constexpr int REC = MODEL::REC, ERRS = MODEL::ERRS;
     // leave only consistent image pairs; every index is checked here, before anything reads a keypoint through it
     std::vector<BaRayEdge> edges;
     std::vector<BaRayObs> obs;
@@ -47,37 +65,34 @@ int ba_ray_solve(MisContext* ctx, const MisFeatures* features, const MisMatchesI
         }
     const int total = (int)obs.size(), ne = (int)edges.size();
     MIS_CHECK(ctx, total > 0, MIS_E_INVALID, "bundle adjustment: no image pair above the confidence threshold");
-    // setUpInitialCameraParams: focal as given, R projected on SO(3) and turned into a rotation vector
+    // setUpInitialCameraParams
     std::vector<double> cam((size_t)n * 4);
-    for (int i = 0; i < n; i++) {
-        cam[i * 4] = cameras[i].focal;
-        ba_start_rvec(cameras[i].R, &cam[i * 4 + 1]);
-    }
+    for (int i = 0; i < n; i++) MODEL::start(cameras[i], &cam[i * 4]);
     if (int rc = ev.prepare(ctx, features, n, edges, obs)) return rc;
 
-    LevMarq solver(n * 4, total * 3, 1000, DBL_EPSILON, false);   // TermCriteria(EPS + COUNT, 1000, DBL_EPSILON); no host J
+    LevMarq solver(n * 4, total * ERRS, 1000, DBL_EPSILON, false);   // TermCriteria(EPS + COUNT, 1000, DBL_EPSILON); no host J
     solver.param = cam;
     int evals = 0;
     const bool trace = getenv("MIS_BA_TRACE") != nullptr;
     for (;;) {
         bool want_J, want_err;
         const bool proceed = solver.update(want_J, want_err);
-        if (trace) fprintf(stderr, "[ba ray] state %d iters %d lambdaLg10 %d prevErr %.17g err %.17g evaluations %d observations %d\n", solver.state, solver.iters, solver.lambdaLg10, solver.prevErrNorm, solver.errNorm, evals, total);
+        if (trace) fprintf(stderr, "[ba %s] state %d iters %d lambdaLg10 %d prevErr %.17g err %.17g evaluations %d observations %d\n", MODEL::tag(), solver.state, solver.iters, solver.lambdaLg10, solver.prevErrNorm, solver.errNorm, evals, total);
         cam = solver.param;
         if (!proceed || !want_err) break;
         double* rec = ev.records();
-        for (int c = 0; c < n; c++) ba_ray_record(&cam[c * 4], features[c].img_w, features[c].img_h, rec + (size_t)c * BA_RAY_REC);
+        for (int c = 0; c < n; c++) MODEL::record(&cam[c * 4], features[c], rec + (size_t)c * REC);
         if (want_J)
             for (int c = 0; c < n; c++)
                 for (int p = 0; p < 4; p++)
                     for (int s = 0; s < 2; s++) {
                         double q[4] = {cam[c * 4], cam[c * 4 + 1], cam[c * 4 + 2], cam[c * 4 + 3]};
-                        q[p] = s ? q[p] + BA_RAY_STEP : q[p] - BA_RAY_STEP;
-                        ba_ray_record(q, features[c].img_w, features[c].img_h, rec + (size_t)ba_ray_slot(n, c, p, s) * BA_RAY_REC);
+                        q[p] = s ? q[p] + MODEL::STEP : q[p] - MODEL::STEP;
+                        MODEL::record(q, features[c], rec + (size_t)ba_ray_slot(n, c, p, s) * REC);
                     }
         if (int rc = ev.run(ctx, want_J)) return rc;
         evals++;
-        memcpy(solver.err.data(), ev.err(), sizeof(double) * (size_t)total * 3);
+        memcpy(solver.err.data(), ev.err(), sizeof(double) * (size_t)total * ERRS);
         if (want_J) {
             // JtJ(a, b) = sum over the edges that hold both columns' cameras, ascending, from +0; the same for JtErr
             std::fill(solver.JtJ.v.begin(), solver.JtJ.v.end(), 0.);
@@ -95,13 +110,15 @@ int ba_ray_solve(MisContext* ctx, const MisFeatures* features, const MisMatchesI
         }
     }
     for (double v : cam) MIS_CHECK(ctx, std::isfinite(v), MIS_E_INVALID, "bundle adjustment diverged (non-finite camera parameter)");
-    // obtainRefinedCameraParams: focal and R; ppx, ppy, aspect and t stay as given
-    for (int i = 0; i < n; i++) {
-        cameras[i].focal = cam[i * 4];
-        ba_refined_R(&cam[i * 4 + 1], cameras[i].R);
-    }
+    // obtainRefinedCameraParams
+    for (int i = 0; i < n; i++) MODEL::refined(&cam[i * 4], &cameras[i]);
     ba_normalise_to_centre(n, pairwise, cameras);
     return MIS_OK;
+}
+
+template <class Eval>
+int ba_ray_solve(MisContext* ctx, const MisFeatures* features, const MisMatchesInfo* pairwise, int n, float conf_thresh, MisCameraParams* cameras, Eval& ev) {
+    return ba_obs_solve<BaRayModel>(ctx, features, pairwise, n, conf_thresh, cameras, ev);
 }
 
 }  // namespace

@@ -1,4 +1,5 @@
-// motion_host.h -- host pieces shared by the bundle adjusters (motion.hip: reprojection cost; motion_ray.hip: ray cost): small dense
+// motion_host.h -- host pieces shared by the bundle adjusters (motion.hip: reprojection cost; motion_ray.hip: ray cost; motion_affine.hip:
+// the affine-partial cost and the affine estimator): small dense
 // linear algebra, the Jacobi SVD and its solve, the Rodrigues pair, the CvLevMarq state machine and the spanning tree's centres.
 // Restated from the published algorithms with the reference's precisions (see motion.hip).  Everything sits in an unnamed
 // namespace: each translation unit that includes this header gets its own copy.
@@ -333,7 +334,8 @@ struct LevMarq {
 };
 
 // stitching/src/motion_estimators.cpp findMaxSpanningTree: Kruskal on num_inliers (descending), then the tree's centres
-void max_spanning_tree_centers(int n, const MisMatchesInfo* pm, std::vector<int>& centers) {
+// (tree: optionally the spanning tree's adjacency lists, neighbours in the order the edges were added)
+void max_spanning_tree_centers(int n, const MisMatchesInfo* pm, std::vector<int>& centers, std::vector<std::vector<int>>* tree = nullptr) {
     struct GE { int from, to; float w; };
     std::vector<GE> all;
     for (int i = 0; i < n; i++)
@@ -368,6 +370,37 @@ void max_spanning_tree_centers(int n, const MisMatchesInfo* pm, std::vector<int>
     int mn = max_dists.empty() ? 0 : *std::min_element(max_dists.begin(), max_dists.end());
     centers.clear();
     for (int i = 0; i < n; i++) if (max_dists[i] == mn) centers.push_back(i);
+    if (tree) *tree = adj;
+}
+
+// AffineBasedEstimator::estimate: every camera a default CameraParams (focal 1, aspect 1, ppx = ppy = 0, R = I,
+// t = 0); the maximum spanning tree on num_inliers walked breadth-first from its first centre, R_to = R_from * H(from, to) in
+// double.  It never fails; cameras no tree edge reaches keep R = I.  R is handed on as CV_32F values (the Stitcher's convertTo).
+void estimate_affine_cameras(int n, const MisMatchesInfo* pm, MisCameraParams* cameras) {
+    for (int i = 0; i < n; i++) {
+        MisCameraParams& c = cameras[i];
+        c.focal = 1.; c.aspect = 1.; c.ppx = 0.; c.ppy = 0.;
+        for (int k = 0; k < 9; k++) c.R[k] = (k % 4 == 0) ? 1. : 0.;
+        c.t[0] = c.t[1] = c.t[2] = 0.;
+    }
+    std::vector<int> centers;
+    std::vector<std::vector<int>> tree;
+    max_spanning_tree_centers(n, pm, centers, &tree);
+    if (!centers.empty()) {
+        std::vector<char> was((size_t)n, 0);
+        std::vector<int> q{centers[0]};
+        was[centers[0]] = 1;
+        for (size_t h = 0; h < q.size(); h++) {
+            const int from = q[h];
+            for (int to : tree[from]) {
+                if (was[to]) continue;
+                mul3(cameras[from].R, pm[from * n + to].H, cameras[to].R);
+                was[to] = 1;
+                q.push_back(to);
+            }
+        }
+    }
+    for (int i = 0; i < n; i++) for (int k = 0; k < 9; k++) cameras[i].R[k] = (double)(float)cameras[i].R[k];
 }
 
 

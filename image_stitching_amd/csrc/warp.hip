@@ -32,7 +32,26 @@ struct Projector {
     float k[9], rinv[9], r_kinv[9], k_rinv[9];
     int kind;   // MIS_WARP_*
     float a, b; // the (A, B) of a compressed-plane / Panini kind (col_kind_of), else 0
+    float t[3]; // PlaneProjector::t of the affine kind (affine_rt), else 0
 };
+
+// the kinds on the plane projector: the four-corner roi, the divide by z whatever its sign
+MIS_HD bool kind_planar(int kind) { return kind == MIS_WARP_PLANE || kind == MIS_WARP_AFFINE; }
+
+// AffineWarper::getRTfromHomogeneous (stitching/src/warpers.cpp): T0 = (H02, H12, 0); R = H without those two, transposed;
+// T = (R T0) * -1.  The float matrix product as projector_set's: double products and sums, one rounding to float.  T[2] is +-0.
+static void affine_rt(const float H[9], float R[9], float T[3]) {
+    const float t0[3] = {H[2], H[5], 0.f};
+    float r[9];
+    for (int i = 0; i < 9; i++) r[i] = H[i];
+    r[2] = 0.f; r[5] = 0.f;
+    for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) R[i * 3 + j] = r[j * 3 + i];
+    for (int i = 0; i < 3; i++) {
+        double s = 0;
+        for (int k = 0; k < 3; k++) s += (double)R[i * 3 + k] * (double)t0[k];
+        T[i] = (float)s * -1.f;
+    }
+}
 
 // the kinds whose backward map is evaluated per output pixel (no column / row tables)
 static bool kind_polar(int kind) { return kind == MIS_WARP_FISHEYE || kind == MIS_WARP_STEREOGRAPHIC; }
@@ -52,9 +71,13 @@ static ColKind col_kind_of(int kind) {
 static bool kind_col(int kind) { return col_kind_of(kind).family != 0; }
 
 // ProjectorBase::setCameraParams (stitching/src/warpers.cpp): float matrices, double intermediates
+// The affine kind: `R` is the homogeneous H; the projector takes the R and T of affine_rt (so rinv is H without its translation
+// column, the transpose of R and not its inverse -- as there).
 void projector_set(Projector* p, int kind, float scale, const float K[9], const float R[9]) {
     double kinv[9], d;
-    float kinv_f[9];
+    float kinv_f[9], r_affine[9];
+    p->t[0] = p->t[1] = p->t[2] = 0.f;
+    if (kind == MIS_WARP_AFFINE) { affine_rt(R, r_affine, p->t); R = r_affine; }
     p->kind = kind;
     p->scale = scale;
     p->a = col_kind_of(kind).a; p->b = col_kind_of(kind).b;
@@ -95,11 +118,12 @@ void projector_set(Projector* p, int kind, float scale, const float K[9], const 
 // {CompressedRectilinear,Panini}Projector(a, b)::mapForward (`kind` is the family's A2B1 kind or the kind itself): nothing special
 // at cosf(u_) = 0 (v infinite: the roi is refused), past tanf's pole (a = 1.5: u_ / a reaches 120 degrees) or at u_ beyond 90 degrees.
 template <int LAST_KIND = MIS_WARP_PANINI_A15B1>
-MIS_HD bool map_forward(int kind, const float* m, float scale, float x, float y, float* u, float* v, float a = 0.f, float b = 0.f) {
+MIS_HD bool map_forward(int kind, const float* m, float scale, float x, float y, float* u, float* v, float a = 0.f, float b = 0.f,
+                        const float* t = nullptr) {     // t: PlaneProjector::t, read by the affine kind only
     float x_ = (m[0] * x + m[1] * y) + m[2];
     float y_ = (m[3] * x + m[4] * y) + m[5];
     float z_ = (m[6] * x + m[7] * y) + m[8];
-    if (LAST_KIND >= MIS_WARP_COMPRESSED_PLANE_A2B1 && kind >= MIS_WARP_COMPRESSED_PLANE_A2B1) {
+    if (LAST_KIND >= MIS_WARP_COMPRESSED_PLANE_A2B1 && kind >= MIS_WARP_COMPRESSED_PLANE_A2B1 && kind <= MIS_WARP_PANINI_A15B1) {
         float u_ = mis_atan2f(x_, z_);
         float v_ = mis_asinf(y_ / sqrtf((x_ * x_ + y_ * y_) + z_ * z_));
         if (kind <= MIS_WARP_COMPRESSED_PLANE_A15B1) {
@@ -130,6 +154,9 @@ MIS_HD bool map_forward(int kind, const float* m, float scale, float x, float y,
     } else if (kind == MIS_WARP_PLANE) {
         *u = scale * (x_ / z_ * 1.f);
         *v = scale * (y_ / z_ * 1.f);
+    } else if (kind == MIS_WARP_AFFINE) {
+        *u = scale * (t[0] + x_ / z_ * (1.f - t[2]));
+        *v = scale * (t[1] + y_ / z_ * (1.f - t[2]));
     } else if (kind == MIS_WARP_CYLINDRICAL) {
         *u = scale * mis_atan2f(x_, z_);
         *v = scale * y_ / sqrtf(x_ * x_ + z_ * z_);
@@ -192,10 +219,10 @@ int detect_result_roi(const Projector* p, int sw, int sh, int* tlx, int* tly, in
         if (v > br_vf) br_vf = v;
     };
     const int kind = p->kind;
-    if (kind == MIS_WARP_PLANE) {
+    if (kind_planar(kind)) {
         const float cx[4] = {0.f, 0.f, (float)(sw - 1), (float)(sw - 1)}, cy[4] = {0.f, (float)(sh - 1), 0.f, (float)(sh - 1)};
         bool front = true;
-        for (int c = 0; c < 4; c++) { front &= map_forward(kind, p->r_kinv, p->scale, cx[c], cy[c], &u, &v); upd(); }
+        for (int c = 0; c < 4; c++) { front &= map_forward(kind, p->r_kinv, p->scale, cx[c], cy[c], &u, &v, 0.f, 0.f, p->t); upd(); }
         if (!front) return MIS_E_INVALID;
     } else if (MIS_WARP_ROI_IS_FULL_SCAN(kind)) {
         for (int y = 0; y < sh; ++y)
@@ -230,10 +257,11 @@ int projector_and_roi(int kind, float scale, const float K[9], const float R[9],
 // The border walk of detectResultRoi for a whole job: workgroup f projects the 2(W+H) border pixels of frame f and reduces
 // the four extremes (min / max of finite floats: any order gives the host loop's result).  Jobs and results live in pinned,
 // device-visible host memory: one launch + one stream synchronisation for all frames of a panorama.
-// (The plane kind: threads 0..3 project the four corners, and `behind` reports a corner with z_ <= 0.)
+// (The plane and affine kinds: threads 0..3 project the four corners, and `behind` reports a corner with z_ <= 0.)
 struct RoiJob {
     float r_kinv[9], scale;
     float a, b;     // compressed-plane / Panini
+    float t[3];     // affine (Projector::t), else 0
     int sw, sh, kind;
     int behind;     // out (plane): some corner lies behind the panorama plane
     float ext[4];   // out: min u, min v, max u, max v
@@ -258,16 +286,18 @@ __global__ __launch_bounds__(256) void warp_roi_kernel(RoiJob* jobs) {
     for (int i = 0; i < 9; i++) m[i] = j->r_kinv[i];
     const float scale = j->scale;
     const int sw = j->sw, sh = j->sh, kind = j->kind;
+    const float t[3] = {j->t[0], j->t[1], j->t[2]};
+    const bool planar = kind_planar(kind);
     if (threadIdx.x == 0) behind = 0;
     __syncthreads();
     float lo_u = FLT_MAX, lo_v = FLT_MAX, hi_u = -FLT_MAX, hi_v = -FLT_MAX;
-    const int npts = kind == MIS_WARP_PLANE ? 4 : 2 * (sw + sh);
+    const int npts = planar ? 4 : 2 * (sw + sh);
     for (int i = threadIdx.x; i < npts; i += 256) {
         float x, y, u, v;
-        if (kind == MIS_WARP_PLANE) { x = i < 2 ? 0.f : (float)(sw - 1); y = (i & 1) ? (float)(sh - 1) : 0.f; }
+        if (planar) { x = i < 2 ? 0.f : (float)(sw - 1); y = (i & 1) ? (float)(sh - 1) : 0.f; }
         else if (i < 2 * sw) { x = (float)(i >> 1); y = (i & 1) ? (float)(sh - 1) : 0.f; }
         else { const int k = i - 2 * sw; y = (float)(k >> 1); x = (k & 1) ? (float)(sw - 1) : 0.f; }
-        if (!map_forward<MIS_WARP_MERCATOR>(kind, m, scale, x, y, &u, &v) && kind == MIS_WARP_PLANE) behind = 1;
+        if (!map_forward<MIS_WARP_MERCATOR>(kind, m, scale, x, y, &u, &v, 0.f, 0.f, t) && planar) behind = 1;
         lo_u = fminf(lo_u, u); lo_v = fminf(lo_v, v); hi_u = fmaxf(hi_u, u); hi_v = fmaxf(hi_v, v);
     }
     reduce_extremes(lo_u, lo_v, hi_u, hi_v, red);
@@ -330,7 +360,9 @@ struct WarpArgs {
     float scale;
     int tlx, tly, dw, dh, sw, sh, cn;
     int kind;        // MIS_WARP_* (read by the table fills and the u8 warps; the fused kernels take it as a template argument)
-    float pa, pb;    // the (A, B) of a compressed-plane / Panini kind
+    float pa, pb;    // the (A, B) of a compressed-plane / Panini kind; the affine kind's (t0, t1) of Projector::t (its t2 is +-0: w = 1 -
+                     // t2 = 1), read by the table fills.  No member of its own: the struct keeps its 128 bytes, and with them every
+                     // kernel that takes it -- or an array of it -- its code
     const uint8_t* src;
     size_t sstride;
     void* dst;       // s16x3 (fused) or u8 x cn
@@ -348,21 +380,24 @@ __device__ __forceinline__ void map_backward(int kind, const float* m, float sin
     float xx = (m[0] * x_ + m[1] * y_) + m[2] * z_;
     float yy = (m[3] * x_ + m[4] * y_) + m[5] * z_;
     float z = (m[6] * x_ + m[7] * y_) + m[8] * z_;
-    if (kind == MIS_WARP_PLANE || z > 0) { *x = xx / z; *y = yy / z; }
+    if (kind_planar(kind) || z > 0) { *x = xx / z; *y = yy / z; }
     else { *x = -1.f; *y = -1.f; }
 }
 
 // the separable terms of output column `col` ({su, cu}) and row `row` ({s, c}) of a warp kind (u' = u / scale, v' = v / scale):
 // spherical {sin u', cos u'} {sin(pi - v'), cos(pi - v')}; cylindrical {sin u', cos u'} {1, v'}; plane {u', 1} {1, v'};
-// mercator {sin u', cos u'} {cos v_, sin v_}, v_ = atan(sinh v') (a unit ray like the spherical one; v' = +-inf gives v_ = +-pi/2)
-__device__ __forceinline__ void col_terms(int kind, float scale, int col, float* su, float* cu) {
+// mercator {sin u', cos u'} {cos v_, sin v_}, v_ = atan(sinh v') (a unit ray like the spherical one; v' = +-inf gives v_ = +-pi/2);
+// affine: the plane's with PlaneProjector::mapBackward's u' = u / scale - t0, v' = v / scale - t1 (its w = 1 - t2 is 1: t2 = +-0)
+__device__ __forceinline__ void col_terms(int kind, float scale, int col, float t0, float* su, float* cu) {
     const float u = (float)col / scale;
     if (kind == MIS_WARP_PLANE) { *su = u; *cu = 1.f; }
+    else if (kind == MIS_WARP_AFFINE) { *su = u - t0; *cu = 1.f; }
     else mis_sincosf(u, su, cu);
 }
-__device__ __forceinline__ void row_terms(int kind, float scale, int row, float* s, float* c) {
+__device__ __forceinline__ void row_terms(int kind, float scale, int row, float t1, float* s, float* c) {
     const float v = (float)row / scale;
-    if (kind == MIS_WARP_SPHERICAL) mis_sincosf(MIS_PI_F - v, s, c);
+    if (kind == MIS_WARP_AFFINE) { *s = 1.f; *c = v - t1; }
+    else if (kind == MIS_WARP_SPHERICAL) mis_sincosf(MIS_PI_F - v, s, c);
     else if (kind == MIS_WARP_MERCATOR) mis_sincosf(mis_atanf(mis_sinhf(v)), c, s);
     else { *s = 1.f; *c = v; }
 }
@@ -395,10 +430,10 @@ __device__ __forceinline__ bool nearest_inside(int sw, int sh, float x, float y,
 
 __device__ __forceinline__ void tile_trig(const WarpArgs& a, int tx0, int ty0, float* su, float* cu, float* sv, float* cv) {
     int t = threadIdx.x;
-    if (t < TILE_W) col_terms(a.kind, a.scale, a.tlx + tx0 + t, &su[t], &cu[t]);
+    if (t < TILE_W) col_terms(a.kind, a.scale, a.tlx + tx0 + t, a.pa, &su[t], &cu[t]);
     else if (t < TILE_W + TILE_H) {
         int r = t - TILE_W;
-        row_terms(a.kind, a.scale, a.tly + ty0 + r, &sv[r], &cv[r]);
+        row_terms(a.kind, a.scale, a.tly + ty0 + r, a.pb, &sv[r], &cv[r]);
     }
     __syncthreads();
 }
@@ -432,11 +467,11 @@ static size_t trig_table_floats(int dw, int dh) { return 2 * (size_t)trig_cols(d
 
 // entry i of a frame's tables: column i ({su, cu}) for i < ncol, else row i - ncol ({s, m1 c, m4 c, m7 c})
 __device__ __forceinline__ void trig_fill(const WarpArgs& a, float* tab, int i, int ncol) {
-    if (i < ncol) col_terms(a.kind, a.scale, a.tlx + i, &tab[2 * i], &tab[2 * i + 1]);
+    if (i < ncol) col_terms(a.kind, a.scale, a.tlx + i, a.pa, &tab[2 * i], &tab[2 * i + 1]);
     else if (i < ncol + a.dh) {
         const int r = i - ncol;
         float s, c;
-        row_terms(a.kind, a.scale, a.tly + r, &s, &c);
+        row_terms(a.kind, a.scale, a.tly + r, a.pb, &s, &c);
         float* t = tab + 2 * ncol + 4 * r;
         t[0] = s; t[1] = a.m[1] * c; t[2] = a.m[4] * c; t[3] = a.m[7] * c;
     }
@@ -1366,8 +1401,10 @@ static int v3_strip_tiles(const MisContext* ctx, const WarpArgs& a, int frames) 
 static bool fast_z_bound_ok(const WarpArgs& a) {
     const float msum = fabsf(a.m[6]) + fabsf(a.m[7]) + fabsf(a.m[8]);
     if (a.kind == MIS_WARP_SPHERICAL) return msum <= 1048576.f;
+    // (the affine kind's u' = u / scale - t0, v' = v / scale - t1: the bound takes |t0|, |t1| on top)
     const double uv = std::max({1.0, std::fabs((double)a.tlx), std::fabs((double)a.tlx + a.dw), std::fabs((double)a.tly),
-                                std::fabs((double)a.tly + a.dh)}) / (double)a.scale;
+                                std::fabs((double)a.tly + a.dh)}) / (double)a.scale +
+                      (a.kind == MIS_WARP_AFFINE ? std::max(std::fabs((double)a.pa), std::fabs((double)a.pb)) : 0.0);
     return (double)msum * std::max(1.0, uv) <= 1048576.0;
 }
 static V3Frame v3_frame_of(const WarpArgs& a, const float* tab) {
@@ -1767,8 +1804,8 @@ template <class F> void with_scan_kind(int kind, F&& launch) {          // warp_
     else if (kind == MIS_WARP_STEREOGRAPHIC) launch(int_c<MIS_WARP_STEREOGRAPHIC>{});
     else with_col_kind(kind, launch);
 }
-template <class F> void with_ztest(int kind, F&& launch) {              // warp_fused_kernel, warp_strip_batch_kernel: ZTEST = not plane
-    if (kind == MIS_WARP_PLANE) launch(std::false_type{});
+template <class F> void with_ztest(int kind, F&& launch) {              // warp_fused_kernel, warp_strip_batch_kernel: ZTEST = not plane / affine
+    if (kind_planar(kind)) launch(std::false_type{});
     else launch(std::true_type{});
 }
 template <class F> void with_cn_linear(int cn, bool linear, F&& launch) {       // warp_u8_kernel, warp_polar_u8_kernel
@@ -1799,11 +1836,12 @@ int setup(MisContext* ctx, int kind, const MisImage* src, float scale, const flo
         tlx = r.x; tly = r.y; *brx = r.x + r.width - 1; *bry = r.y + r.height - 1;
     } else {
         MIS_CHECK(ctx, projector_and_roi(kind, scale, K, R, src->width, src->height, &p, &tlx, &tly, brx, bry) == MIS_OK, MIS_E_INVALID, "%s",
-                  kind == MIS_WARP_PLANE ? "warp roi refused: a corner of the frame lies behind the panorama plane"
-                                         : "warp roi refused: the border projects to a non-finite extreme");
+                  kind_planar(kind) ? "warp roi refused: a corner of the frame lies behind the panorama plane"
+                                    : "warp roi refused: the border projects to a non-finite extreme");
     }
     for (int i = 0; i < 9; i++) a->m[i] = p.k_rinv[i];
     a->kind = kind; a->pa = p.a; a->pb = p.b;
+    if (kind == MIS_WARP_AFFINE) { a->pa = p.t[0]; a->pb = p.t[1]; }
     a->scale = scale; a->tlx = tlx; a->tly = tly;
     MIS_CHECK(ctx, (long long)*brx - tlx + 1 <= INT_MAX && (long long)*bry - tly + 1 <= INT_MAX, MIS_E_INVALID,
               "warp roi %d..%d x %d..%d does not fit an int size", tlx, *brx, tly, *bry);
@@ -2160,6 +2198,7 @@ extern "C" int mis_warper_roi_batch(MisContext* ctx, int kind, float scale, int 
     for (int i = 0; i < n; i++) {
         projector_set(&proj[i], kind, scale, Ks + 9 * i, Rs + 9 * i);
         memcpy(jobs[i].r_kinv, proj[i].r_kinv, sizeof(jobs[i].r_kinv));
+        for (int k = 0; k < 3; k++) jobs[i].t[k] = proj[i].t[k];
         jobs[i].scale = scale; jobs[i].a = proj[i].a; jobs[i].b = proj[i].b; jobs[i].sw = w; jobs[i].sh = h; jobs[i].kind = kind; jobs[i].behind = 0;
     }
     float4* part = (float4*)((uint8_t*)ctx->roi_pinned + part_off);
@@ -2236,10 +2275,60 @@ extern "C" int mis_debug_math_f32(MisContext* ctx, int fn, const float* in, floa
 // test aid: mapBackward of a half-separable kind for every pixel of `roi` -> xy[(row * roi->width + col) * 2 + {0, 1}] (host array).
 // ctx NULL: the unsplit sequence (map_backward_col) per pixel on the host; with a context: the kernels' tile walk with its hoisted
 // column terms (col_tile), whose every float must equal the host's.
+// The affine kind (R = the homogeneous H).  ctx NULL: PlaneProjector::mapBackward with t, the reference's operation sequence kept
+// literally; with a context: the separable terms of the warp kernels (col_terms, row_terms, map_backward), whose every float must
+// equal the host's.
+static void map_backward_plane_t(const float* k, const float* t, float scale, float u, float v, float* x, float* y) {
+    u = u / scale - t[0];
+    v = v / scale - t[1];
+    const float w = 1.f - t[2];
+    *x = (k[0] * u + k[1] * v) + k[2] * w;
+    *y = (k[3] * u + k[4] * v) + k[5] * w;
+    const float z = (k[6] * u + k[7] * v) + k[8] * w;
+    *x /= z;
+    *y /= z;
+}
+__global__ __launch_bounds__(256) void debug_affine_map_kernel(WarpArgs a, float* xy) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.dw * a.dh) return;       // area <= 2^24 (host check)
+    const int r = i / a.dw, c = i - r * a.dw;
+    float su, cu, sv, cv;
+    col_terms(a.kind, a.scale, a.tlx + c, a.pa, &su, &cu);
+    row_terms(a.kind, a.scale, a.tly + r, a.pb, &sv, &cv);
+    map_backward(a.kind, a.m, su, cu, sv, cv, &xy[2 * (size_t)i], &xy[2 * (size_t)i + 1]);
+}
+static int debug_affine_map(MisContext* ctx, float scale, const float K[9], const float H[9], const MisRect* roi, float* xy) {
+    Projector p;
+    projector_set(&p, MIS_WARP_AFFINE, scale, K, H);
+    if (!ctx) {
+        for (int r = 0; r < roi->height; r++)
+            for (int c = 0; c < roi->width; c++) {
+                float* o = xy + ((size_t)r * roi->width + c) * 2;
+                map_backward_plane_t(p.k_rinv, p.t, scale, (float)(roi->x + c), (float)(roi->y + r), &o[0], &o[1]);
+            }
+        return MIS_OK;
+    }
+    MIS_HIP(ctx, hipSetDevice(ctx->device));
+    WarpArgs a = {};
+    for (int i = 0; i < 9; i++) a.m[i] = p.k_rinv[i];
+    a.kind = MIS_WARP_AFFINE; a.pa = p.t[0]; a.pb = p.t[1]; a.scale = scale;
+    a.tlx = roi->x; a.tly = roi->y; a.dw = roi->width; a.dh = roi->height;
+    const size_t bytes = sizeof(float) * 2 * (size_t)a.dw * a.dh;
+    float* d = nullptr;
+    int rc;
+    if ((rc = mis_dev_stage(ctx, bytes, (void**)&d)) != MIS_OK) return rc;
+    hipLaunchKernelGGL(debug_affine_map_kernel, dim3((unsigned)((a.dw * a.dh + 255) / 256)), dim3(256), 0, ctx->stream, a, d);
+    MIS_HIP(ctx, hipGetLastError());
+    MIS_HIP(ctx, hipMemcpyAsync(xy, d, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    MIS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return MIS_OK;
+}
+
 extern "C" int mis_debug_warper_map_f32(MisContext* ctx, int kind, float scale, const float K[9], const float R[9], const MisRect* roi, float* xy) {
     const ColKind ck = col_kind_of(kind);
-    if (!ck.family) return MIS_E_UNSUPPORTED;
+    if (!ck.family && kind != MIS_WARP_AFFINE) return MIS_E_UNSUPPORTED;
     if (!K || !R || !roi || !xy || !(scale > 0.f) || roi->width < 1 || roi->height < 1 || (long long)roi->width * roi->height > (1 << 24)) return MIS_E_INVALID;
+    if (kind == MIS_WARP_AFFINE) return debug_affine_map(ctx, scale, K, R, roi, xy);
     Projector p;
     projector_set(&p, kind, scale, K, R);
     if (!ctx) {

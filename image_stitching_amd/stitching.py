@@ -148,7 +148,8 @@ WARP_KINDS = {"spherical": capi.WARP_SPHERICAL, "cylindrical": capi.WARP_CYLINDR
 # the kinds the library builds.  MIS_WARP_PANINI_A2B1 has no warp_type name here: "paniniA2B1" is the suite's example of a refused
 # warper (tests/test_refimpl_polar_warpers_cpu.py), so that kind is reached through PaniniWarper(ctx, scale, 2, 1), the C ABI and the
 # C++ host
-BUILT_WARP_KINDS = frozenset(WARP_KINDS.values()) | {capi.WARP_PANINI_A2B1}
+# MIS_WARP_AFFINE has no warp_type name either ("affine" stays a refused name): it is AffineWarper(ctx, scale).
+BUILT_WARP_KINDS = frozenset(WARP_KINDS.values()) | {capi.WARP_PANINI_A2B1, capi.WARP_AFFINE}
 # the reference's warp_type names beyond the first six kinds (image_stitching.cpp:933-964).  Three of them are built by now: the
 # tuple is kept only because tests/test_refimpl_polar_warpers_cpu.py pins its length at ten.  REFUSED_WARP_TYPES -- its names that
 # are not in WARP_KINDS -- is the list warp_kind refuses; drop this tuple (and define that one directly) once that test can change
@@ -328,6 +329,12 @@ class CylindricalWarper(RotationWarper):
 class PlaneWarper(RotationWarper):
     """PlaneWarper::create(scale) with T = 0 (image_stitching.cpp:923, :933)."""
     kind = capi.WARP_PLANE
+
+
+class AffineWarper(RotationWarper):
+    """AffineWarper::create(scale) (image_stitching.cpp:935-936): the plane warper with a translation.  Every `R` argument is the
+    3x3 homogeneous affine H of cv::detail::AffineWarper::warp(src, K, H, ...)."""
+    kind = capi.WARP_AFFINE
 
 
 class MercatorWarper(RotationWarper):
@@ -1244,10 +1251,9 @@ def leaveBiggestComponentConf(confidence, conf_threshold):
 WAVE_CORRECT_HORIZ, WAVE_CORRECT_VERT = 0, 1
 
 
-def refine_cameras(ctx, features, pairwise_matches, indices, cameras, cfg):
-    """The reference's sequence after the pruning (image_stitching.cpp:671-726) on the kept subset: bundle adjustment
-    of the subset's cameras (features / matches re-indexed as leaveBiggestComponent does), then wave correction.
-    cameras: dicts with K (3x3), R; returns new dicts for the kept frames, in the order of `indices`."""
+def _subset_matches(ctx, pairwise_matches, indices):
+    """The table of the kept subset, re-indexed as leaveBiggestComponent does (image_stitching.cpp:746-748): a view whose entries
+    borrow the full table's match arrays.  The caller sets view._mis = None when done (borrowed entries: nothing to free)."""
     n, k = pairwise_matches.n, len(indices)
     sub = (capi.MisMatchesInfo * (k * k))()
     for a, i in enumerate(indices):
@@ -1257,6 +1263,30 @@ def refine_cameras(ctx, features, pairwise_matches, indices, cameras, cfg):
     view = PairwiseMatches.__new__(PairwiseMatches)
     view._ctx, view._mis, view.n, view._cache = ctx, sub, k, {}
     view._owner = pairwise_matches              # the match arrays belong to the full table
+    return view
+
+
+def estimate_and_refine(ctx, features, pairwise_matches, indices, conf_thresh, estimator, adjuster):
+    """The reference's sequence after the pruning for a job without supplied cameras (cv::Stitcher::estimateCameraParams): the
+    estimator on the kept subset's table, its rotations handed on as float32, then the bundle adjuster on the subset's features.
+    estimator(pairwise_matches) -> cameras; adjuster(ctx, features, pairwise_matches, cameras, conf_thresh) -> cameras or None for
+    no adjustment.  -> camera dicts with K (3x3 float64) and R (3x3 float32) for the kept frames, in the order of `indices`."""
+    view = _subset_matches(ctx, pairwise_matches, indices)
+    try:
+        cams = estimator(view)
+        if adjuster is not None:
+            cams = adjuster(ctx, [features[i] for i in indices], view, cams, conf_thresh)
+    finally:
+        view._mis = None
+    return [dict(K=np.array([[c["focal"], 0, c["ppx"]], [0, c["focal"] * c["aspect"], c["ppy"]], [0, 0, 1]], np.float64),
+                 R=np.asarray(c["R"], np.float32), f=c["focal"], params=c) for c in cams]
+
+
+def refine_cameras(ctx, features, pairwise_matches, indices, cameras, cfg):
+    """The reference's sequence after the pruning (image_stitching.cpp:671-726) on the kept subset: bundle adjustment
+    of the subset's cameras (features / matches re-indexed as leaveBiggestComponent does), then wave correction.
+    cameras: dicts with K (3x3), R; returns new dicts for the kept frames, in the order of `indices`."""
+    view = _subset_matches(ctx, pairwise_matches, indices)
     start = [dict(focal=float(cameras[i]["K"][0, 0]), aspect=float(cameras[i]["K"][1, 1] / cameras[i]["K"][0, 0]), ppx=float(cameras[i]["K"][0, 2]),
                   ppy=float(cameras[i]["K"][1, 2]), R=cameras[i]["R"]) for i in indices]
     cost_func = check_ba_config(cfg)
@@ -1327,6 +1357,36 @@ def bundle_adjust_ray(ctx, features, pairwise_matches, cameras, conf_thresh=0.95
         C.memmove(C.byref(arr[k]), C.byref(f.raw), C.sizeof(capi.MisFeatures))
     cams = _camera_array(cameras, n)
     ctx.check(ctx.lib.mis_bundle_adjust_ray(ctx.h, arr, pairwise_matches._mis, n, float(conf_thresh), cams))
+    return _camera_dicts(cams, n)
+
+
+def bundle_adjust_affine_partial(ctx, features, pairwise_matches, cameras, conf_thresh=0.95):
+    """(*makePtr<detail::BundleAdjusterAffinePartial>())(features, pairwise_matches, cameras) with setConfThresh
+    (image_stitching.cpp:685-686; what Stitcher::create(SCANS) installs): the similarity (a, b, tx, ty) in every camera's R
+    refined on the inlier matches, evaluated on the device; focal, aspect, ppx, ppy and t come back as given.  cameras and the
+    result as in bundle_adjust_reproj, R the 3x3 homogeneous similarity."""
+    n = len(features)
+    if not isinstance(pairwise_matches, PairwiseMatches):
+        raise TypeError("pairwise_matches must be the PairwiseMatches object a matcher call returned")
+    arr = (capi.MisFeatures * n)()
+    for k, f in enumerate(features):
+        C.memmove(C.byref(arr[k]), C.byref(f.raw), C.sizeof(capi.MisFeatures))
+    cams = _camera_array(cameras, n)
+    ctx.check(ctx.lib.mis_bundle_adjust_affine_partial(ctx.h, arr, pairwise_matches._mis, n, float(conf_thresh), cams))
+    return _camera_dicts(cams, n)
+
+
+def estimate_affine_cameras(pairwise_matches):
+    """(*makePtr<detail::AffineBasedEstimator>())(features, pairwise_matches, cameras): default cameras (focal 1, aspect 1,
+    ppx = ppy = 0, t = 0) whose R is the product of the pairwise similarities along the maximum spanning tree from its centre, as
+    float32 values.  Host logic; it never fails.  -> list of dicts as bundle_adjust_reproj takes them."""
+    if not isinstance(pairwise_matches, PairwiseMatches):
+        raise TypeError("pairwise_matches must be the PairwiseMatches object a matcher call returned")
+    n = pairwise_matches.n
+    cams = (capi.MisCameraParams * n)()
+    rc = capi.load().mis_estimate_affine_cameras(pairwise_matches._mis, n, cams)
+    if rc != capi.MIS_OK:
+        raise MisError(rc, "mis_estimate_affine_cameras")
     return _camera_dicts(cams, n)
 
 
@@ -1414,13 +1474,15 @@ def check_seam_config(cfg):
         raise ValueError("expos_comp_nr_feeds %r: an integer >= 1 (image_stitching.cpp:74)" % (nf,))
 
 
-def seam_scale_warp(ctx, cfg, frame_size, frame, camera, warped_image_scale, work_scale=1.0):
+def seam_scale_warp(ctx, cfg, frame_size, frame, camera, warped_image_scale, work_scale=1.0, kind=None):
     """One frame of the seam-scale loop of main() (image_stitching.cpp:604-622 resize to seam_megapix, :973-990 warp of image and
     mask with K scaled by seam_work_aspect) -> (corner, image_warped 8UC3, mask_warped 8U) on the device."""
     w, h = frame_size
     seam_scale = min(1.0, float(np.sqrt(cfg.seam_megapix * 1e6 / (w * h))))
     swa = np.float32(seam_scale / work_scale)
-    warper = make_warper(ctx, np.float32(np.float32(warped_image_scale) * swa), cfg.warp_type)
+    # kind: the warper kind set in place of the configured warp_type (Stitcher.set_warper)
+    sscale = np.float32(np.float32(warped_image_scale) * swa)
+    warper = make_warper(ctx, sscale, cfg.warp_type) if kind is None else RotationWarper(ctx, sscale, kind)
     img = resize(ctx, frame, fx=seam_scale, fy=seam_scale) if seam_scale < 1.0 else frame
     K = np.array(camera["K"], np.float32).copy()
     K[0, 0] *= swa; K[0, 2] *= swa; K[1, 1] *= swa; K[1, 2] *= swa
@@ -1564,6 +1626,46 @@ class Stitcher:
         self.finder = OrbFeatureFinder(ctx, self.work_size)
         self.matcher = make_matcher(ctx, self.cfg)
         self.seam_finder = None       # set_seam_finder
+        self.estimator = None         # set_estimator: None = the caller supplies the cameras
+        self.bundle_adjuster = None   # set_bundle_adjuster (read with an estimator only)
+
+    @classmethod
+    def create_scans(cls, ctx, frame_size, **config_overrides):
+        """cv::Stitcher::create(Stitcher::SCANS): flat material under similarities -- the affine matcher, AffineBasedEstimator,
+        BundleAdjusterAffinePartial, AffineWarper, no wave correction, no exposure compensation; the seam finder and the blender
+        are the configured ones (StitchConfig.hot_path's unless overridden).  stitch(frames) needs no cameras."""
+        kw = dict(matcher_type="affine", wave_correct="no", expos_comp_type="no")
+        kw.update(config_overrides)
+        st = cls(ctx, frame_size, StitchConfig.hot_path(**kw))
+        st.set_estimator(estimate_affine_cameras)
+        st.set_bundle_adjuster(bundle_adjust_affine_partial)
+        st.set_warper(AffineWarper)
+        return st
+
+    def set_estimator(self, estimator):
+        """cv::Stitcher::setEstimator: estimator(pairwise_matches) -> cameras (estimate_affine_cameras), run by stitch() on the kept
+        subset in place of cameras from the caller; None goes back to supplied cameras."""
+        if estimator is not None and not callable(estimator):
+            raise TypeError("set_estimator: %r is not callable" % (estimator,))
+        self.estimator = estimator
+
+    def set_bundle_adjuster(self, adjuster):
+        """cv::Stitcher::setBundleAdjuster: adjuster(ctx, features, pairwise_matches, cameras, conf_thresh) -> cameras
+        (bundle_adjust_affine_partial), run on the estimator's cameras; None: the estimate is used as it is."""
+        if adjuster is not None and not callable(adjuster):
+            raise TypeError("set_bundle_adjuster: %r is not callable" % (adjuster,))
+        self.bundle_adjuster = adjuster
+
+    def set_warper(self, warper_cls):
+        """cv::Stitcher::setWarper: a RotationWarper class with a kind of its own (AffineWarper) replaces the configured warp_type in
+        the seam-scale and the compose-scale warps; None goes back to warp_type."""
+        if warper_cls is None:
+            self.kind = check_warp_config(self.cfg)
+            return
+        kind = getattr(warper_cls, "kind", None)
+        if not (isinstance(warper_cls, type) and issubclass(warper_cls, RotationWarper)) or kind not in BUILT_WARP_KINDS:
+            raise TypeError("set_warper: %r is not a RotationWarper class with a built kind" % (warper_cls,))
+        self.kind = kind
 
     def set_seam_finder(self, finder):
         """cv::Stitcher::setSeamFinder: the seam step runs this finder object (e.g. GraphCutSeamFinder(ctx)) whatever
@@ -1643,12 +1745,28 @@ class Stitcher:
         if self.cfg.expos_comp_type == "no" and self.cfg.seam_find_type == "no" and self.seam_finder is None:
             return None
         work_scale = self.work_scale if work_scale is None else work_scale
-        items = [seam_scale_warp(self.ctx, self.cfg, self.frame_size, frames[i], cameras[i], warped_image_scale, work_scale) for i in indices]
+        items = [seam_scale_warp(self.ctx, self.cfg, self.frame_size, frames[i], cameras[i], warped_image_scale, work_scale,
+                                 self.kind if self.kind != check_warp_config(self.cfg) else None) for i in indices]
         return seam_solve(self.ctx, self.cfg, [it[0] for it in items], [it[1] for it in items], [it[2] for it in items], self.seam_finder)
 
-    def stitch(self, frames, cameras):
+    def estimate_cameras(self, feats, pm, idx):
+        """With an estimator set: the cameras of the kept frames from the matches alone (estimate_and_refine), in work units
+        -> {frame index: camera}; also kept as self.cameras."""
+        cams = estimate_and_refine(self.ctx, feats, pm, [int(i) for i in idx], self.cfg.conf_thresh, self.estimator, self.bundle_adjuster)
+        self.cameras = {int(i): c for i, c in zip(idx, cams)}
+        return self.cameras
+
+    def stitch(self, frames, cameras=None):
         feats = self.features(frames)
         pm = self.match(feats)
         idx = leaveBiggestComponent(pm, len(frames), self.cfg.conf_thresh)
-        result, mask = self.compose(frames, self.work_cameras(cameras), list(idx))
+        if self.estimator is not None:
+            if cameras is not None:
+                raise ValueError("stitch: an estimator is set, the cameras come from the matches")
+            work = self.estimate_cameras(feats, pm, idx)
+        elif cameras is None:
+            raise ValueError("stitch: cameras are needed (no estimator is set)")
+        else:
+            work = self.work_cameras(cameras)
+        result, mask = self.compose(frames, work, list(idx))
         return result, mask, feats, pm, idx

@@ -47,12 +47,16 @@ enum { MIS_BORDER_CONSTANT = 0, MIS_BORDER_REFLECT = 2 };       /* cv::BORDER_CO
  * transcendental per pixel); the fisheye and stereographic maps are polar and are evaluated per output pixel.
  * Kinds 8 .. 11: the compressed-rectilinear (:945-948) and Panini (:953-956) warpers, one kind per (A, B) setting the reference offers
  * (the entries have no slot for the two parameters).  Their backward map is half separable: the horizontal angle depends on the
- * column only, the vertical one on the pixel.  Kinds 6 and 7 are not assigned. */
+ * column only, the vertical one on the pixel.  Kinds 6, 7 and 12 are not assigned.
+ * Kind 13: cv::detail::AffineWarper (:935-936), the plane warper with a translation.  Its `R` argument is the 3x3 homogeneous affine
+ * H of AffineWarper::warp(src, K, H, ...): getRTfromHomogeneous splits it into the plane projector's R (H without its translation
+ * column, transposed) and T = -(R T0).  Same separable tables as the plane, the two subtractions of T folded into them. */
 enum { MIS_WARP_SPHERICAL = 0, MIS_WARP_CYLINDRICAL = 1, MIS_WARP_PLANE = 2, MIS_WARP_MERCATOR = 3, MIS_WARP_FISHEYE = 4, MIS_WARP_STEREOGRAPHIC = 5,
-       MIS_WARP_COMPRESSED_PLANE_A2B1 = 8, MIS_WARP_COMPRESSED_PLANE_A15B1 = 9, MIS_WARP_PANINI_A2B1 = 10, MIS_WARP_PANINI_A15B1 = 11 };
+       MIS_WARP_COMPRESSED_PLANE_A2B1 = 8, MIS_WARP_COMPRESSED_PLANE_A15B1 = 9, MIS_WARP_PANINI_A2B1 = 10, MIS_WARP_PANINI_A15B1 = 11,
+       MIS_WARP_AFFINE = 13 };
 /* the kinds the library builds: every entry that takes a kind answers MIS_E_UNSUPPORTED ("unknown warp kind") for any other value */
 #define MIS_WARP_KIND_IS_KNOWN(kind) (((kind) >= MIS_WARP_SPHERICAL && (kind) <= MIS_WARP_STEREOGRAPHIC) || \
-                                      ((kind) >= MIS_WARP_COMPRESSED_PLANE_A2B1 && (kind) <= MIS_WARP_PANINI_A15B1))
+                                      ((kind) >= MIS_WARP_COMPRESSED_PLANE_A2B1 && (kind) <= MIS_WARP_PANINI_A15B1) || (kind) == MIS_WARP_AFFINE)
 /* the kinds whose warper has no detectResultRoi of its own: RotationWarperBase::detectResultRoi projects EVERY source pixel forward.
  * For these mis_warper_roi is O(width * height) on the host and mis_warper_roi_batch a grid-wide reduction on the device. */
 #define MIS_WARP_ROI_IS_FULL_SCAN(kind) (((kind) >= MIS_WARP_MERCATOR && (kind) <= MIS_WARP_STEREOGRAPHIC) || \
@@ -277,6 +281,20 @@ int mis_bundle_adjust_reproj(MisContext* ctx, const MisFeatures* features, const
  * match indices are validated on the host first.  The rotations are normalised to the centre of the maximum spanning tree. */
 int mis_bundle_adjust_ray(MisContext* ctx, const MisFeatures* features, const MisMatchesInfo* pairwise, int n, float conf_thresh,
                           MisCameraParams* cameras);
+/* (*adjuster)(features, pairwise_matches, cameras) with makePtr<detail::BundleAdjusterAffinePartial>(), setConfThresh -- replaces
+ * image_stitching.cpp:685-686 (ba_cost_func = "affine"; reached through the scans mode, not through that name).  Levenberg-Marquardt
+ * over 4 parameters per camera, (a, b, tx, ty) = (R[0,0], R[1,0], R[0,2], R[1,2]) of the float32 R, H = [a -b tx; b a ty; 0 0 1]: 2
+ * errors per inlier correspondence of the pairs above conf_thresh, p2 - (H_i^-1 H_j) p1 (invertAffineTransform in double).  On return
+ * R = the float32 H of the refined four values, normalised to the centre of the maximum spanning tree; focal, aspect, ppx, ppy and t
+ * come back as given.  The solver is host logic; the errors, the central-difference Jacobian (step 1e-4) and the per-pair sums of
+ * the normal equations are evaluated by kernels on the context's stream, reading the keypoints in the features' device arrays.
+ * The match indices are validated on the host first. */
+int mis_bundle_adjust_affine_partial(MisContext* ctx, const MisFeatures* features, const MisMatchesInfo* pairwise, int n, float conf_thresh,
+                                     MisCameraParams* cameras);
+/* estimator = makePtr<detail::AffineBasedEstimator>(); (*estimator)(features, pairwise_matches, cameras): every camera a default
+ * CameraParams (focal 1, aspect 1, ppx = ppy = 0, t = 0), R chained along the maximum spanning tree on num_inliers, breadth-first
+ * from its centre: R_to = R_from * H(from, to) in double, handed on as float32 values.  Host logic; it never fails. */
+int mis_estimate_affine_cameras(const MisMatchesInfo* pairwise, int n, MisCameraParams* cameras);
 /* waveCorrect(rmats, wave_correct) -- replaces image_stitching.cpp:718-726; rmats: n x 9 doubles in place; kind 0 = HORIZ, 1 = VERT */
 int mis_wave_correct(double* rmats, int n, int kind);
 

@@ -35,7 +35,7 @@ from image_stitching_amd import _capi as capi          # noqa: E402
 from image_stitching_amd import stitching as st        # noqa: E402
 from image_stitching_amd.distributed import StitchJob  # noqa: E402
 
-KERNELS = ("ba_ray_eval_kernel", "ba_ray_normal_kernel")
+KERNELS = ("ba_eval_kernel", "ba_normal_kernel")      # ba_eval_device.h; the child runs the ray adjuster only, so these are its instantiations
 CONF = 0.95
 
 
@@ -133,7 +133,7 @@ def kernel_stats(a):
         for path in glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True):
             with open(path) as fh:
                 for row in csv.DictReader(fh):
-                    m = re.search(r"(\w+)\s*$", row.get("Name", "").replace("(anonymous namespace)::", "").split("(")[0])
+                    m = re.search(r"(\w+)(<.*>)?\s*$", row.get("Name", "").replace("(anonymous namespace)::", "").split("(")[0])
                     k = m.group(1) if m else ""
                     if k in KERNELS:
                         e = out.setdefault(k, {"calls": 0, "total_us": 0.0})
