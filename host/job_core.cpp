@@ -48,6 +48,8 @@ JobCore::JobCore(const char* who, std::string where, int device, void* main_stre
             throw std::runtime_error(std::string(who) + " runs the hot path (ORB, supplied cameras, no seam-scale step); use mis::Stitcher for the other options");
         if (mode_is_scans(cfg_.mode))       // the jobs speculate the composition from supplied cameras; the scans mode has none
             throw std::runtime_error(std::string(who) + " runs supplied cameras only; the scans mode is mis::Stitcher's");
+        if (estimator_is_homography(cfg_.estimator_type))      // likewise: an estimator's cameras exist only after the matcher has returned (a name that is no estimator is refused as mis::Stitcher refuses it)
+            throw std::runtime_error(std::string(who) + " runs supplied cameras only; estimator_type '" + cfg_.estimator_type + "' is mis::Stitcher's");
         kind_ = warp_kind(cfg_.warp_type);
         check_range_width(cfg_.range_width);
         model_ = matcher_model(cfg_.matcher_type, cfg_.range_width);

@@ -43,6 +43,7 @@ struct Args {
     double work_megapix = -1;      // features at work scale (image_stitching.cpp:589-603); -1: full resolution
     int range_width = -1;          // BestOf2NearestRangeMatcher (:83, :646-649); -1: all pairs
     std::string matcher = "homography";      // matcher_type (:64, :644-645): "affine" = AffineBestOf2NearestMatcher
+    std::string estimator = "supplied";      // estimator_type: the jobs run supplied cameras only and refuse any other value by name
 };
 
 static bool read_cams(const std::string& path, int* n, int* W, int* H, std::vector<SyCamera>* sy, std::vector<mis::CameraParams>* cams) {
@@ -126,6 +127,7 @@ static int run_single(const Args& a) {
         cfg.work_megapix = a.work_megapix;
         cfg.range_width = a.range_width;
         cfg.matcher_type = a.matcher;
+        cfg.estimator_type = a.estimator;
         mis::StitchJob job(0, W, H, cams, cfg);
         std::vector<int> everyone(n);
         for (int i = 0; i < n; i++) everyone[i] = i;
@@ -163,6 +165,7 @@ static int run_rank(const Args& a, int rank) {
         cfg.work_megapix = a.work_megapix;
         cfg.range_width = a.range_width;
         cfg.matcher_type = a.matcher;
+        cfg.estimator_type = a.estimator;
         mis::ShardedJob job(device, W, H, cams, *comm, cfg);
         std::vector<MisImage> frames;
         if (render_frames(sy, job.my_frames(), W, H, &frames)) return 1;
@@ -228,7 +231,7 @@ static int launch(const Args& a, int argc, char** argv) {
 }
 
 int main(int argc, char** argv) {
-    if (argc < 2) { std::fprintf(stderr, "usage: stitch_bench cams.txt [--steps K] [--warmup W] [--dump prefix] [--ranks N] [--comm host|rccl] [--one-gpu] [--warp spherical|cylindrical|plane|mercator|fisheye|stereographic|compressedPlaneA2B1|compressedPlaneA1.5B1|paniniA2B1|paniniA1.5B1] [--work_megapix f] [--rangewidth N] [--matcher homography|affine]\n"); return 2; }
+    if (argc < 2) { std::fprintf(stderr, "usage: stitch_bench cams.txt [--steps K] [--warmup W] [--dump prefix] [--ranks N] [--comm host|rccl] [--one-gpu] [--warp spherical|cylindrical|plane|mercator|fisheye|stereographic|compressedPlaneA2B1|compressedPlaneA1.5B1|paniniA2B1|paniniA1.5B1] [--work_megapix f] [--rangewidth N] [--matcher homography|affine] [--estimator supplied]\n"); return 2; }
     Args a;
     a.cams_path = argv[1];
     for (int i = 2; i < argc; i++) {
@@ -242,6 +245,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--work_megapix") && i + 1 < argc) a.work_megapix = std::strtod(argv[++i], nullptr);
         else if (!std::strcmp(argv[i], "--rangewidth") && i + 1 < argc) a.range_width = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--matcher") && i + 1 < argc) a.matcher = argv[++i];
+        else if (!std::strcmp(argv[i], "--estimator") && i + 1 < argc) a.estimator = argv[++i];
         else if (!std::strcmp(argv[i], "--rank-child") && i + 1 < argc) a.child_rank = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--session") && i + 1 < argc) a.session = argv[++i];
     }

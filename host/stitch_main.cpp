@@ -6,6 +6,9 @@
 // Frames are sorted by the leading integer of the file name (:327-335).  Writes result.ppm / result_mask.pgm.
 //   stitch_main <dir> --mode scans
 // stitches flat material (scanner passes, document photos) as cv::Stitcher::create(SCANS) does: no "<k>.txt" is read.
+//   stitch_main <dir> --estimator homography [--ba ray]
+// stitches a rotation panorama from the images alone as cv::Stitcher::create(PANORAMA) does (HomographyBasedEstimator, then the
+// configured adjuster and wave correction): no "<k>.txt" is read either.
 #include <algorithm>
 #include <cctype>
 #include <filesystem>
@@ -19,7 +22,7 @@
 int main(int argc, char** argv) {
     if (argc < 2) {
         std::cout << "usage: " << argv[0] << " <image directory> [--features orb|sift] [--ba no|reproj|ray] [--ba_refine_mask xxxxx] [--wave_correct horiz|vert|no]\n"
-                     "       [--expos_comp no|gain|gain_blocks|channels|channels_blocks] [--expos_comp_nr_feeds N] [--seam no|voronoi|dp_color|dp_colorgrad] [--warp spherical|cylindrical|plane|fisheye|stereographic|compressedPlaneA2B1|compressedPlaneA1.5B1|paniniA2B1|paniniA1.5B1] [--blend no|feather|multiband] [--conf_thresh f] [--match_conf f] [--compose_megapix f] [--seam_megapix f] [--work_megapix f] [--rangewidth N] [--matcher homography|affine] [--mode panorama|scans]\n"
+                     "       [--expos_comp no|gain|gain_blocks|channels|channels_blocks] [--expos_comp_nr_feeds N] [--seam no|voronoi|dp_color|dp_colorgrad] [--warp spherical|cylindrical|plane|fisheye|stereographic|compressedPlaneA2B1|compressedPlaneA1.5B1|paniniA2B1|paniniA1.5B1] [--blend no|feather|multiband] [--conf_thresh f] [--match_conf f] [--compose_megapix f] [--seam_megapix f] [--work_megapix f] [--rangewidth N] [--matcher homography|affine] [--mode panorama|scans] [--estimator supplied|homography]\n"
                      "(the reference sets these as globals, image_stitching.cpp:49-85)\n";
         return -1;
     }
@@ -43,13 +46,14 @@ int main(int argc, char** argv) {
         else if (k == "--rangewidth") cfg.range_width = std::atoi(v.c_str());
         else if (k == "--matcher") cfg.matcher_type = v;
         else if (k == "--mode") cfg.mode = v;
+        else if (k == "--estimator") cfg.estimator_type = v;
         else { std::cout << "unknown option " << k << "\n"; return -1; }
     }
     // tests/test_warpers_job_gpu.py::test_stitch_main_warp_equals_python_stitcher uses `--warp mercator` as its example of a warper
     // this driver refuses ("not implemented", non-zero exit): the library, mis::Stitcher, mis::JobCore, mis::ShardedJob and stitch_bench
     // run the Mercator warper, this driver alone keeps refusing the name here until that test names another value
     if (cfg.warp_type == "mercator") { std::cout << "warper 'mercator' is not implemented in stitch_main (stitch_bench --warp mercator and the mis:: C++ API run it)\n"; return -1; }
-    try { mis::mode_is_scans(cfg.mode); mis::check_range_width(cfg.range_width); mis::matcher_model(cfg.matcher_type, cfg.range_width); mis::expos_comp_kind(cfg.expos_comp_type, cfg.expos_comp_nr_feeds); } catch (const std::exception& e) { std::cout << e.what() << "\n"; return -1; }
+    try { if (!mis::mode_is_scans(cfg.mode)) mis::estimator_is_homography(cfg.estimator_type); mis::check_range_width(cfg.range_width); mis::matcher_model(cfg.matcher_type, cfg.range_width); mis::expos_comp_kind(cfg.expos_comp_type, cfg.expos_comp_nr_feeds); } catch (const std::exception& e) { std::cout << e.what() << "\n"; return -1; }
     namespace fs = std::filesystem;
     std::vector<std::string> img_names;
     for (auto& e : fs::directory_iterator(argv[1])) {
@@ -71,7 +75,8 @@ int main(int argc, char** argv) {
         std::vector<mis::CameraParams> cams;
         for (auto& name : img_names) {
             frames.push_back(mis::readPPM(name));
-            if (cfg.mode == "scans") continue;      // Stitcher::create(SCANS): the cameras come from the matches, no per-frame description is read
+            // Stitcher::create(SCANS) and --estimator homography: the cameras come from the matches, no per-frame description is read
+            if (cfg.mode == "scans" || cfg.estimator_type == "homography") continue;
             // the camera: the EXIF ImageDescription of "<k>.jpg" beside the frame when there is one (the reference's source,
             // image_stitching.cpp:344-347, :411-417; the pixels still come from the .ppm: no JPEG decoder here), else "<k>.txt"
             std::string desc;

@@ -95,10 +95,11 @@ static const SeamFinderEntry& seam_finder(const std::string& type) {
 StitchResult Stitcher::stitch(const std::vector<HostImage>& frames, const std::vector<CameraParams>& cams_in) {
     const int n = (int)frames.size();
     const bool scans = mode_is_scans(cfg_.mode);
-    if (n < 2 || (scans ? !cams_in.empty() : (int)cams_in.size() != n)) throw std::runtime_error("Need more images");
+    const bool estimated = scans || estimator_is_homography(cfg_.estimator_type);      // (estimator_type is not read in the scans mode)
+    if (n < 2 || (estimated ? !cams_in.empty() : (int)cams_in.size() != n)) throw std::runtime_error("Need more images");
     StitchResult out;
     std::vector<CameraParams> cameras = cams_in;
-    if (scans) {        // default CameraParams until the estimator runs (focal 1, ppx = ppy = 0, R = I)
+    if (estimated) {    // default CameraParams until the estimator runs (focal 1, ppx = ppy = 0, R = I)
         cameras.assign(n, CameraParams());
         for (auto& c : cameras) c.R(0, 0) = c.R(1, 1) = c.R(2, 2) = 1;
     }
@@ -156,7 +157,8 @@ StitchResult Stitcher::stitch(const std::vector<HostImage>& frames, const std::v
     out.indices.resize(kept);
     // ---- camera refinement on the kept subset (:671-726): bundle adjustment (reprojection or ray cost), wave correction ----
     //      in the scans mode: AffineBasedEstimator on the kept subset's table, then BundleAdjusterAffinePartial
-    if (kept >= 2 && (scans || cfg_.ba_cost_func != "no")) {
+    //      with estimator_type "homography": HomographyBasedEstimator on that table, then the configured adjuster
+    if (kept >= 2 && (estimated || cfg_.ba_cost_func != "no")) {
         std::vector<MisFeatures> fsub(kept);
         std::vector<MisMatchesInfo> psub((size_t)kept * kept);
         std::vector<MisCameraParams> cp(kept);
@@ -173,7 +175,13 @@ StitchResult Stitcher::stitch(const std::vector<HostImage>& frames, const std::v
             std::copy(c.t.begin(), c.t.end(), cp[a].t);
         }
         if (scans) check(mis_estimate_affine_cameras(psub.data(), kept, cp.data()), "mis_estimate_affine_cameras");
+        else if (estimated) {       // on the sizes of the images the features were found on (work scale)
+            std::vector<MisSize> fsizes(kept);
+            for (int a = 0; a < kept; a++) fsizes[a] = {fsub[a].img_w, fsub[a].img_h};
+            check(mis_estimate_homography_cameras(psub.data(), kept, fsizes.data(), cp.data()), "mis_estimate_homography_cameras");
+        }
         const int ba_rc = scans ? mis_bundle_adjust_affine_partial(ctx_, fsub.data(), psub.data(), kept, cfg_.conf_thresh, cp.data())
+                        : cfg_.ba_cost_func == "no" ? MIS_OK          // (reached with an estimator only: its cameras are kept)
                         : cfg_.ba_cost_func == "ray" ? mis_bundle_adjust_ray(ctx_, fsub.data(), psub.data(), kept, cfg_.conf_thresh, cp.data())
                                                      : mis_bundle_adjust_reproj(ctx_, fsub.data(), psub.data(), kept, cfg_.conf_thresh, cfg_.ba_refine_mask.c_str(), cp.data());
         if (ba_rc != MIS_OK)

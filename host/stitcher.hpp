@@ -44,6 +44,10 @@ struct StitchConfig {
     // under similarities -- no cameras are supplied; the affine matcher, AffineBasedEstimator, BundleAdjusterAffinePartial and the
     // AffineWarper run whatever matcher_type, ba_cost_func and warp_type say; no wave correction, no exposure compensation)
     std::string mode = "panorama";
+    // where the panorama mode's cameras come from: "supplied" (the caller's, one per frame) | "homography" (HomographyBasedEstimator,
+    // image_stitchin3g.cpp:746-779 / Stitcher::create(PANORAMA): no cameras are supplied; focals from the pairwise homographies,
+    // rotations chained along the spanning tree, then ba_cost_func and wave_correct as configured).  Not read in the scans mode.
+    std::string estimator_type = "supplied";
 };
 
 // mode of the config -> scans?; an unknown name is refused by name
@@ -51,6 +55,15 @@ inline bool mode_is_scans(const std::string& m) {
     if (m == "panorama") return false;
     if (m != "scans") throw std::runtime_error("mode '" + m + "': 'panorama' or 'scans' (--mode)");
     return true;
+}
+
+// estimator_type of the config -> does the homography estimator run?; "affine" (AffineBasedEstimator) is the scans mode's and is
+// refused by name with that pointer, an unknown name is refused by name
+inline bool estimator_is_homography(const std::string& t) {
+    if (t == "supplied") return false;
+    if (t == "homography") return true;
+    if (t == "affine") throw std::runtime_error("estimator_type 'affine': AffineBasedEstimator runs in mode = \"scans\" (--mode scans), not under this name");
+    throw std::runtime_error("estimator_type '" + t + "': 'supplied' or 'homography' (--estimator)");
 }
 
 // matcher_type of the config -> MIS_MATCH_*, the check before any device work.  An unknown name is refused by name; so is "affine"
@@ -163,7 +176,8 @@ class Stitcher {
 public:
     explicit Stitcher(int device = 0, const StitchConfig& cfg = StitchConfig());
     ~Stitcher();
-    // frames: 8UC3 BGR of one size; cameras: one per frame (sensor / ground-truth K, R); none in the scans mode
+    // frames: 8UC3 BGR of one size; cameras: one per frame (sensor / ground-truth K, R); none in the scans mode or with
+    // estimator_type = "homography"
     StitchResult stitch(const std::vector<HostImage>& frames, const std::vector<CameraParams>& cameras);
 
 private:

@@ -14,7 +14,7 @@ from ._capi import (BLEND_FEATHER, BLEND_MULTI_BAND, BLEND_NO, BORDER_CONSTANT, 
 from .stitching import (AffineBestOf2NearestMatcher, BestOf2NearestMatcher, BestOf2NearestRangeMatcher, estimate_affine_partial, Blender, BlocksGainCompensator, GainCompensator, ChannelsCompensator, BlocksChannelsCompensator, NoSeamFinder, VoronoiSeamFinder, DpSeamFinder, GraphCutSeamFinder, Context, FeatherBlender, ImageFeatures, MatchesInfo,
                         MisError, MultiBandBlender, OrbFeatureFinder, SiftFeatureFinder, SphericalWarper, CylindricalWarper, PlaneWarper, MercatorWarper, FisheyeWarper, StereographicWarper, CompressedRectilinearWarper, PaniniWarper, AffineWarper,
                         RotationWarper, StitchConfig, Stitcher,
-                        blend_config, bundle_adjust_affine_partial, bundle_adjust_ray, bundle_adjust_reproj, estimate_affine_cameras, computeImageFeatures, find_homography, leaveBiggestComponent, resize, resize_batch, result_roi,
+                        blend_config, bundle_adjust_affine_partial, bundle_adjust_ray, bundle_adjust_reproj, estimate_affine_cameras, estimate_focal, estimate_homography_cameras, focals_from_homography, computeImageFeatures, find_homography, leaveBiggestComponent, resize, resize_batch, result_roi,
                         rotate, seam_gradients, seam_mask_apply, selected_pairs, warp_roi, wave_correct, work_geometry)
 
 __all__ = [
@@ -27,4 +27,5 @@ __all__ = [
     "WARP_COMPRESSED_PLANE_A2B1", "WARP_COMPRESSED_PLANE_A15B1", "WARP_PANINI_A2B1", "WARP_PANINI_A15B1", "CompressedRectilinearWarper", "PaniniWarper",
     "BestOf2NearestRangeMatcher", "selected_pairs", "AffineBestOf2NearestMatcher", "estimate_affine_partial", "seam_gradients",
     "WARP_AFFINE", "AffineWarper", "bundle_adjust_affine_partial", "estimate_affine_cameras",
+    "focals_from_homography", "estimate_focal", "estimate_homography_cameras",
 ]

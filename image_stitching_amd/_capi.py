@@ -163,6 +163,9 @@ PROTOTYPES = {
     "mis_bundle_adjust_ray": (_i, [_vp, _P(MisFeatures), _P(MisMatchesInfo), _i, _f, _P(MisCameraParams)]),
     "mis_bundle_adjust_affine_partial": (_i, [_vp, _P(MisFeatures), _P(MisMatchesInfo), _i, _f, _P(MisCameraParams)]),
     "mis_estimate_affine_cameras": (_i, [_P(MisMatchesInfo), _i, _P(MisCameraParams)]),
+    "mis_focals_from_homography": (_i, [_P(_d), _P(_d), _P(_d), _P(_i), _P(_i)]),
+    "mis_estimate_focal": (_i, [_P(MisMatchesInfo), _i, _P(MisSize), _P(_d)]),
+    "mis_estimate_homography_cameras": (_i, [_P(MisMatchesInfo), _i, _P(MisSize), _P(MisCameraParams)]),
     "mis_wave_correct": (_i, [_vp, _i, _i]),
     "mis_warp_roi": (_i, [_f, _i, _i, _vp, _vp, _P(MisRect)]),
     "mis_warp_spherical": (_i, [_vp, _P(MisImage), _f, _vp, _vp, _i, _i, _P(MisImage), _P(MisPoint)]),

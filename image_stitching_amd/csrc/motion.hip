@@ -1,6 +1,7 @@
 // motion.hip -- camera refinement between matching and warping, host logic of the library:
 //   (*adjuster)(features, pairwise_matches, cameras) with BundleAdjusterReproj   image_stitching/image_stitching.cpp:681-712
 //   waveCorrect(rmats, WAVE_CORRECT_HORIZ)                                       image_stitching/image_stitching.cpp:718-726
+//   (*estimator)(features, pairwise_matches, cameras) with HomographyBasedEstimator   image_stitching/image_stitchin3g.cpp:746-779
 // The reference runs both on the CPU inside OpenCV (stitching/src/motion_estimators.cpp, calib3d CvLevMarq, core
 // JacobiSVD / Jacobi eigen, calib3d Rodrigues); restated here from the published algorithms with the reference's precisions: the
 // cameras' rotations are CV_32F (image_stitching.cpp:626-634), the solver state is CV_64F, the refined rotations leave as CV_32F
@@ -248,5 +249,31 @@ extern "C" int mis_wave_correct(double* rmats, int n, int kind) {
         mul3(Rg, &R[9 * i], o);
         for (int k = 0; k < 9; k++) rmats[9 * i + k] = o[k];
     }
+    return MIS_OK;
+}
+
+// ---------------------------------------------------------------- HomographyBasedEstimator ------
+// estimator = makePtr<detail::HomographyBasedEstimator>(); (*estimator)(features, pairwise_matches, cameras), what
+// Stitcher::create(PANORAMA) runs ahead of the ray adjuster.  Host logic (motion_host.h), no context:
+// O(n^2) closed forms on nine doubles and a tree walk -- a launch would cost more than the work.
+static bool sizes_ok(const MisSize* s, int n) {
+    for (int i = 0; i < n; i++) if (s[i].width <= 0 || s[i].height <= 0) return false;
+    return true;
+}
+extern "C" int mis_focals_from_homography(const double H[9], double* f0, double* f1, int* f0_ok, int* f1_ok) {
+    if (!H || !f0 || !f1 || !f0_ok || !f1_ok) return MIS_E_INVALID;
+    bool ok0, ok1;
+    focals_from_homography(H, *f0, *f1, ok0, ok1);
+    *f0_ok = ok0; *f1_ok = ok1;
+    return MIS_OK;
+}
+extern "C" int mis_estimate_focal(const MisMatchesInfo* pairwise, int n, const MisSize* img_sizes, double* focals) {
+    if (!pairwise || !img_sizes || !focals || n < 1 || !sizes_ok(img_sizes, n)) return MIS_E_INVALID;
+    estimate_focal(n, pairwise, img_sizes, focals);
+    return MIS_OK;
+}
+extern "C" int mis_estimate_homography_cameras(const MisMatchesInfo* pairwise, int n, const MisSize* img_sizes, MisCameraParams* cameras) {
+    if (!pairwise || !img_sizes || !cameras || n < 1 || !sizes_ok(img_sizes, n)) return MIS_E_INVALID;
+    estimate_homography_cameras(n, pairwise, img_sizes, cameras);
     return MIS_OK;
 }

@@ -1,5 +1,5 @@
 // motion_host.h -- host pieces shared by the bundle adjusters (motion.hip: reprojection cost; motion_ray.hip: ray cost; motion_affine.hip:
-// the affine-partial cost and the affine estimator): small dense
+// the affine-partial cost and the affine estimator) and the homography-based estimator with its focal estimation: small dense
 // linear algebra, the Jacobi SVD and its solve, the Rodrigues pair, the CvLevMarq state machine and the spanning tree's centres.
 // Restated from the published algorithms with the reference's precisions (see motion.hip).  Everything sits in an unnamed
 // namespace: each translation unit that includes this header gets its own copy.
@@ -401,6 +401,106 @@ void estimate_affine_cameras(int n, const MisMatchesInfo* pm, MisCameraParams* c
         }
     }
     for (int i = 0; i < n; i++) for (int k = 0; k < 9; k++) cameras[i].R[k] = (double)(float)cameras[i].R[k];
+}
+
+// stitching/src/autocalib.cpp focalsFromHomography: the two focal lengths a homography between two views of a
+// rotating camera implies, f0 of the source and f1 of the destination view, each from two closed forms.  Zero denominators are
+// not special-cased: H = I or a pure roll gives NaN, every comparison with NaN is false, so ok = false; an infinite v gives
+// f = inf with ok = true.  The choice between v1 and v2 is made AFTER the swap, as OpenCV makes it.  A focal that is not ok is 0.
+inline bool focal_from_forms(double d1, double d2, double v1, double v2, double& f) {
+    if (v1 < v2) std::swap(v1, v2);
+    if (v1 > 0 && v2 > 0) f = std::sqrt(std::abs(d1) > std::abs(d2) ? v1 : v2);
+    else if (v1 > 0) f = std::sqrt(v1);
+    else { f = 0.; return false; }
+    return true;
+}
+void focals_from_homography(const double* h, double& f0, double& f1, bool& f0_ok, bool& f1_ok) {
+    double d1 = h[6] * h[7];
+    double d2 = (h[7] - h[6]) * (h[7] + h[6]);
+    double v1 = -(h[0] * h[1] + h[3] * h[4]) / d1;
+    double v2 = (h[0] * h[0] + h[3] * h[3] - h[1] * h[1] - h[4] * h[4]) / d2;
+    f1_ok = focal_from_forms(d1, d2, v1, v2, f1);
+    d1 = h[0] * h[3] + h[1] * h[4];
+    d2 = h[0] * h[0] + h[1] * h[1] - h[3] * h[3] - h[4] * h[4];
+    v1 = -h[2] * h[5] / d1;
+    v2 = (h[5] * h[5] - h[2] * h[2]) / d2;
+    f0_ok = focal_from_forms(d1, d2, v1, v2, f0);
+}
+
+// autocalib.cpp estimateFocal: sqrt(f0 f1) of every ordered pair with has_H whose two focals are ok; with at least n - 1 such
+// candidates every focal is their median (even count: the mean of the two middle ones), otherwise -- and with no candidate at all,
+// which OpenCV reaches for n = 1 and then reads outside its vector -- the "naive approach": the sum of (width + height) over n.
+void estimate_focal(int n, const MisMatchesInfo* pm, const MisSize* sizes, double* focals, std::vector<double>* candidates = nullptr) {
+    std::vector<double> all;
+    for (int i = 0; i < n; i++)
+        for (int j = 0; j < n; j++) {
+            const MisMatchesInfo& m = pm[i * n + j];
+            if (m.has_H == 0) continue;
+            double f0, f1;
+            bool ok0, ok1;
+            focals_from_homography(m.H, f0, f1, ok0, ok1);
+            if (ok0 && ok1) all.push_back(std::sqrt(f0 * f1));
+        }
+    if (candidates) *candidates = all;
+    double f;
+    if (!all.empty() && (int)all.size() >= n - 1) {
+        std::sort(all.begin(), all.end());
+        f = all.size() % 2 == 1 ? all[all.size() / 2] : (all[all.size() / 2 - 1] + all[all.size() / 2]) * 0.5;
+    } else {
+        double s = 0;
+        for (int i = 0; i < n; i++) s += sizes[i].width + sizes[i].height;
+        f = s / n;
+    }
+    for (int i = 0; i < n; i++) focals[i] = f;
+}
+
+// HomographyBasedEstimator::estimate: default cameras (aspect 1, ppx = ppy = 0, R = I, t = 0) with the focal of
+// estimate_focal; the maximum spanning tree walked breadth-first from its first centre, per tree edge
+// R_to = R_from * (K_from^-1 * H(from, to)^-1 * K_to) in double (cv::invert's 3x3 cofactors; a singular matrix inverts to zero),
+// not orthonormalised; then ppx += 0.5 * width, ppy += 0.5 * height: the matcher's homographies are in centred coordinates.  It
+// never fails; cameras no tree edge reaches keep R = I.  R is handed on as CV_32F values (the Stitcher's convertTo).
+void estimate_homography_cameras(int n, const MisMatchesInfo* pm, const MisSize* sizes, MisCameraParams* cameras) {
+    std::vector<double> focals((size_t)n);
+    estimate_focal(n, pm, sizes, focals.data());
+    for (int i = 0; i < n; i++) {
+        MisCameraParams& c = cameras[i];
+        c.focal = focals[i]; c.aspect = 1.; c.ppx = 0.; c.ppy = 0.;
+        for (int k = 0; k < 9; k++) c.R[k] = (k % 4 == 0) ? 1. : 0.;
+        c.t[0] = c.t[1] = c.t[2] = 0.;
+    }
+    std::vector<int> centers;
+    std::vector<std::vector<int>> tree;
+    max_spanning_tree_centers(n, pm, centers, &tree);
+    if (!centers.empty()) {
+        auto Kof = [](const MisCameraParams& c, double* K) {
+            const double k[9] = {c.focal, 0., c.ppx, 0., c.focal * c.aspect, c.ppy, 0., 0., 1.};
+            memcpy(K, k, sizeof(k));
+        };
+        std::vector<char> was((size_t)n, 0);
+        std::vector<int> q{centers[0]};
+        was[centers[0]] = 1;
+        for (size_t h = 0; h < q.size(); h++) {
+            const int from = q[h];
+            for (int to : tree[from]) {
+                if (was[to]) continue;
+                double Kf[9], Kt[9], Kfi[9], Hi[9], rel[9];
+                Kof(cameras[from], Kf);
+                Kof(cameras[to], Kt);
+                if (!inv3(Kf, Kfi)) std::fill(Kfi, Kfi + 9, 0.);
+                if (!inv3(pm[from * n + to].H, Hi)) std::fill(Hi, Hi + 9, 0.);
+                mul3(Kfi, Hi, rel);
+                mul3(rel, Kt, rel);
+                mul3(cameras[from].R, rel, cameras[to].R);
+                was[to] = 1;
+                q.push_back(to);
+            }
+        }
+    }
+    for (int i = 0; i < n; i++) {
+        cameras[i].ppx += 0.5 * sizes[i].width;
+        cameras[i].ppy += 0.5 * sizes[i].height;
+        for (int k = 0; k < 9; k++) cameras[i].R[k] = (double)(float)cameras[i].R[k];
+    }
 }
 
 

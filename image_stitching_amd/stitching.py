@@ -5,6 +5,7 @@ Names and argument meaning follow the cv::detail objects that image_stitching.cp
 arrays (host buffers staged by the library).
 """
 import ctypes as C
+import functools
 import math
 from dataclasses import dataclass, field
 
@@ -1266,9 +1267,10 @@ def _subset_matches(ctx, pairwise_matches, indices):
     return view
 
 
-def estimate_and_refine(ctx, features, pairwise_matches, indices, conf_thresh, estimator, adjuster):
+def estimate_and_refine(ctx, features, pairwise_matches, indices, conf_thresh, estimator, adjuster, wave_correct="no"):
     """The reference's sequence after the pruning for a job without supplied cameras (cv::Stitcher::estimateCameraParams): the
-    estimator on the kept subset's table, its rotations handed on as float32, then the bundle adjuster on the subset's features.
+    estimator on the kept subset's table, its rotations handed on as float32, then the bundle adjuster on the subset's features,
+    then wave correction of the rotations ("horiz" | "vert"; "no": none, as the scans mode has it).
     estimator(pairwise_matches) -> cameras; adjuster(ctx, features, pairwise_matches, cameras, conf_thresh) -> cameras or None for
     no adjustment.  -> camera dicts with K (3x3 float64) and R (3x3 float32) for the kept frames, in the order of `indices`."""
     view = _subset_matches(ctx, pairwise_matches, indices)
@@ -1278,6 +1280,8 @@ def estimate_and_refine(ctx, features, pairwise_matches, indices, conf_thresh, e
             cams = adjuster(ctx, [features[i] for i in indices], view, cams, conf_thresh)
     finally:
         view._mis = None
+    if wave_correct != "no":
+        cams = _wave_corrected(cams, wave_correct)
     return [dict(K=np.array([[c["focal"], 0, c["ppx"]], [0, c["focal"] * c["aspect"], c["ppy"]], [0, 0, 1]], np.float64),
                  R=np.asarray(c["R"], np.float32), f=c["focal"], params=c) for c in cams]
 
@@ -1390,6 +1394,59 @@ def estimate_affine_cameras(pairwise_matches):
     return _camera_dicts(cams, n)
 
 
+def focals_from_homography(H):
+    """detail::focalsFromHomography(H, f0, f1, f0_ok, f1_ok) (autocalib.cpp): the focal lengths of the source and the destination
+    view a homography in centred coordinates implies -> (f0, f1, f0_ok, f1_ok); a focal that is not ok is 0.  Host logic."""
+    h = (C.c_double * 9)(*np.asarray(H, np.float64).reshape(9))
+    f0, f1, ok0, ok1 = C.c_double(), C.c_double(), C.c_int(), C.c_int()
+    rc = capi.load().mis_focals_from_homography(h, C.byref(f0), C.byref(f1), C.byref(ok0), C.byref(ok1))
+    if rc != capi.MIS_OK:
+        raise MisError(rc, "mis_focals_from_homography")
+    return f0.value, f1.value, bool(ok0.value), bool(ok1.value)
+
+
+def _size_array(img_sizes, n):
+    """img_sizes: one (width, height) for every image, or a list of n of them -> MisSize array."""
+    sizes = list(img_sizes)
+    if len(sizes) == 2 and all(isinstance(v, (int, np.integer)) for v in sizes):
+        sizes = [tuple(sizes)] * n
+    if len(sizes) != n:
+        raise ValueError("img_sizes: %d sizes for %d images" % (len(sizes), n))
+    arr = (capi.MisSize * n)()
+    for k, (w, h) in enumerate(sizes):
+        arr[k].width, arr[k].height = int(w), int(h)
+    return arr
+
+
+def estimate_focal(pairwise_matches, img_sizes):
+    """detail::estimateFocal(features, pairwise_matches, focals): the median of sqrt(f0 f1) over the pairs whose homography gives
+    both focals, or sum(width + height) / n with fewer than n - 1 such pairs.  img_sizes: the (width, height) the features were
+    found on (work scale), one pair for all images or one per image.  Host logic.  -> list of n focals (all equal)."""
+    if not isinstance(pairwise_matches, PairwiseMatches):
+        raise TypeError("pairwise_matches must be the PairwiseMatches object a matcher call returned")
+    n = pairwise_matches.n
+    focals = (C.c_double * n)()
+    rc = capi.load().mis_estimate_focal(pairwise_matches._mis, n, _size_array(img_sizes, n), focals)
+    if rc != capi.MIS_OK:
+        raise MisError(rc, "mis_estimate_focal")
+    return list(focals)
+
+
+def estimate_homography_cameras(pairwise_matches, img_sizes):
+    """(*makePtr<detail::HomographyBasedEstimator>())(features, pairwise_matches, cameras) (image_stitchin3g.cpp:746-779; what
+    Stitcher::create(PANORAMA) runs): default cameras (aspect 1, t = 0) with the focal of estimate_focal, ppx, ppy at the image
+    centre, and R the product of K_from^-1 H^-1 K_to along the maximum spanning tree from its centre, as float32 values.
+    img_sizes as in estimate_focal.  Host logic; it never fails.  -> list of dicts as bundle_adjust_ray takes them."""
+    if not isinstance(pairwise_matches, PairwiseMatches):
+        raise TypeError("pairwise_matches must be the PairwiseMatches object a matcher call returned")
+    n = pairwise_matches.n
+    cams = (capi.MisCameraParams * n)()
+    rc = capi.load().mis_estimate_homography_cameras(pairwise_matches._mis, n, _size_array(img_sizes, n), cams)
+    if rc != capi.MIS_OK:
+        raise MisError(rc, "mis_estimate_homography_cameras")
+    return _camera_dicts(cams, n)
+
+
 def bundle_adjust_reproj(ctx, features, pairwise_matches, cameras, conf_thresh=0.95, refine_mask="xxxxx"):
     """(*makePtr<detail::BundleAdjusterReproj>())(features, pairwise_matches, cameras) with setConfThresh /
     setRefinementMask (image_stitching.cpp:681-712).  cameras: list of dicts with focal, ppx, ppy, R (3x3) and
@@ -1412,6 +1469,12 @@ def wave_correct(rmats, kind=WAVE_CORRECT_HORIZ):
     if rc != capi.MIS_OK:
         raise MisError(rc, "mis_wave_correct")
     return [a[i].copy() for i in range(len(rmats))]
+
+
+def _wave_corrected(cams, name):
+    """Camera dicts with their rotations wave-corrected; name: "horiz" | "vert" (StitchConfig.wave_correct)."""
+    Rs = wave_correct([c["R"] for c in cams], WAVE_CORRECT_VERT if name == "vert" else WAVE_CORRECT_HORIZ)
+    return [dict(c, R=R) for c, R in zip(cams, Rs)]
 
 
 def find_homography(ctx, src, dst, thresh=3.0, max_iters=2000, confidence=0.995):
@@ -1612,7 +1675,9 @@ class Stitcher:
     """The hot-path sequence of main() (image_stitching.cpp:567-1228) for frames already in HBM:
     features -> pairwise matches (+RANSAC) -> [cameras supplied by the caller] -> compose-scale
     warp -> blend.  Optional (off by default): reprojection bundle adjustment with wave
-    correction (refine_cameras), block gain compensation and the "voronoi" seam finder (seam_step)."""
+    correction (refine_cameras), block gain compensation and the "voronoi" seam finder (seam_step).  Without cameras:
+    create_panorama (HomographyBasedEstimator + BundleAdjusterRay + wave correction) and create_scans; estimate_transform registers
+    once, compose_panorama composes further frame sets from the kept registration."""
 
     def __init__(self, ctx, frame_size, config=None):
         self.ctx = ctx
@@ -1628,6 +1693,7 @@ class Stitcher:
         self.seam_finder = None       # set_seam_finder
         self.estimator = None         # set_estimator: None = the caller supplies the cameras
         self.bundle_adjuster = None   # set_bundle_adjuster (read with an estimator only)
+        self.cameras = self.indices = None      # the registration estimate_transform keeps for compose_panorama
 
     @classmethod
     def create_scans(cls, ctx, frame_size, **config_overrides):
@@ -1640,6 +1706,19 @@ class Stitcher:
         st.set_estimator(estimate_affine_cameras)
         st.set_bundle_adjuster(bundle_adjust_affine_partial)
         st.set_warper(AffineWarper)
+        return st
+
+    @classmethod
+    def create_panorama(cls, ctx, frame_size, **config_overrides):
+        """cv::Stitcher::create(Stitcher::PANORAMA): a rotating camera from the images alone -- the homography matcher,
+        HomographyBasedEstimator on the work-scale image size, BundleAdjusterRay, wave correction (horizontal unless overridden);
+        the warper (spherical by default), compensator, seam finder and blender are the configured ones (StitchConfig.hot_path's
+        unless overridden).  stitch(frames) needs no cameras."""
+        kw = dict(matcher_type="homography", wave_correct="horiz")
+        kw.update(config_overrides)
+        st = cls(ctx, frame_size, StitchConfig.hot_path(**kw))
+        st.set_estimator(functools.partial(estimate_homography_cameras, img_sizes=st.work_size))
+        st.set_bundle_adjuster(bundle_adjust_ray)
         return st
 
     def set_estimator(self, estimator):
@@ -1750,23 +1829,44 @@ class Stitcher:
         return seam_solve(self.ctx, self.cfg, [it[0] for it in items], [it[1] for it in items], [it[2] for it in items], self.seam_finder)
 
     def estimate_cameras(self, feats, pm, idx):
-        """With an estimator set: the cameras of the kept frames from the matches alone (estimate_and_refine), in work units
-        -> {frame index: camera}; also kept as self.cameras."""
-        cams = estimate_and_refine(self.ctx, feats, pm, [int(i) for i in idx], self.cfg.conf_thresh, self.estimator, self.bundle_adjuster)
+        """With an estimator set: the cameras of the kept frames from the matches alone (estimate_and_refine: estimator, bundle
+        adjuster, the configured wave correction), in work units -> {frame index: camera}; also kept as self.cameras."""
+        if len(idx) < 2:
+            raise ValueError("Need more images: %d of the frames are left after the pruning at conf_thresh %g, cameras are estimated from two or more"
+                             % (len(idx), self.cfg.conf_thresh))
+        cams = estimate_and_refine(self.ctx, feats, pm, [int(i) for i in idx], self.cfg.conf_thresh, self.estimator, self.bundle_adjuster,
+                                   self.cfg.wave_correct)
         self.cameras = {int(i): c for i, c in zip(idx, cams)}
         return self.cameras
 
-    def stitch(self, frames, cameras=None):
+    def estimate_transform(self, frames, cameras=None):
+        """cv::Stitcher::estimateTransform: features, matches, pruning and -- with an estimator set -- estimation, adjustment and
+        wave correction; without one the caller's cameras in work units.  The registration is kept for compose_panorama as
+        self.cameras (work units: {frame index: camera} from an estimator, else the caller's list or dict as given) and self.indices.
+        An earlier registration is dropped first, so a call that raises leaves none.  -> (features, pairwise matches, kept indices)."""
+        self.cameras = self.indices = None
         feats = self.features(frames)
         pm = self.match(feats)
         idx = leaveBiggestComponent(pm, len(frames), self.cfg.conf_thresh)
         if self.estimator is not None:
             if cameras is not None:
                 raise ValueError("stitch: an estimator is set, the cameras come from the matches")
-            work = self.estimate_cameras(feats, pm, idx)
+            self.estimate_cameras(feats, pm, idx)
         elif cameras is None:
             raise ValueError("stitch: cameras are needed (no estimator is set)")
         else:
-            work = self.work_cameras(cameras)
-        result, mask = self.compose(frames, work, list(idx))
+            self.cameras = self.work_cameras(cameras)
+        self.indices = [int(i) for i in idx]
+        return feats, pm, idx
+
+    def compose_panorama(self, frames):
+        """cv::Stitcher::composePanorama: frames of the registered rig (as many, of the same size, in the same order as the ones
+        estimate_transform saw) composed with the kept cameras and indices; no finder or matcher call.  -> (pano, mask)."""
+        if self.indices is None:
+            raise ValueError("compose_panorama: estimate_transform has not run")
+        return self.compose(frames, self.cameras, list(self.indices))
+
+    def stitch(self, frames, cameras=None):
+        feats, pm, idx = self.estimate_transform(frames, cameras)
+        result, mask = self.compose_panorama(frames)
         return result, mask, feats, pm, idx

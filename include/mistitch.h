@@ -295,6 +295,21 @@ int mis_bundle_adjust_affine_partial(MisContext* ctx, const MisFeatures* feature
  * CameraParams (focal 1, aspect 1, ppx = ppy = 0, t = 0), R chained along the maximum spanning tree on num_inliers, breadth-first
  * from its centre: R_to = R_from * H(from, to) in double, handed on as float32 values.  Host logic; it never fails. */
 int mis_estimate_affine_cameras(const MisMatchesInfo* pairwise, int n, MisCameraParams* cameras);
+/* detail::focalsFromHomography(H, f0, f1, f0_ok, f1_ok) (stitching/src/autocalib.cpp): the focal lengths of the source (f0) and the
+ * destination (f1) view that a homography in centred coordinates between two views of a rotating camera implies, in IEEE double
+ * as SURVEY Appendix A.16 writes them out.  Zero denominators are not special-cased (H = I and a pure roll give ok = 0 through
+ * NaN comparisons; an infinite quotient gives f = inf with ok = 1).  A focal whose ok is 0 is returned as 0. */
+int mis_focals_from_homography(const double H[9], double* f0, double* f1, int* f0_ok, int* f1_ok);
+/* detail::estimateFocal(features, pairwise_matches, focals): sqrt(f0 f1) of every ordered pair with has_H whose two focals are ok;
+ * with at least n - 1 (and at least one) such candidates every focal is their median, otherwise sum(width + height) / n.
+ * img_sizes: the sizes of the images the features were found on (MisFeatures.img_w, img_h: work scale); focals: n doubles. */
+int mis_estimate_focal(const MisMatchesInfo* pairwise, int n, const MisSize* img_sizes, double* focals);
+/* estimator = makePtr<detail::HomographyBasedEstimator>(); (*estimator)(features, pairwise_matches, cameras): what
+ * Stitcher::create(PANORAMA) runs when no cameras are supplied.  Every camera a default CameraParams (aspect 1, t = 0) with the
+ * focal of mis_estimate_focal; R chained along the maximum spanning tree on num_inliers, breadth-first from its centre:
+ * R_to = R_from * K_from^-1 * H(from, to)^-1 * K_to in double, not orthonormalised, handed on as float32 values; ppx, ppy = half
+ * the image size.  Host logic, no context; it never fails.  MIS_E_INVALID: a null pointer, n < 1 or a non-positive size. */
+int mis_estimate_homography_cameras(const MisMatchesInfo* pairwise, int n, const MisSize* img_sizes, MisCameraParams* cameras);
 /* waveCorrect(rmats, wave_correct) -- replaces image_stitching.cpp:718-726; rmats: n x 9 doubles in place; kind 0 = HORIZ, 1 = VERT */
 int mis_wave_correct(double* rmats, int n, int kind);
 
