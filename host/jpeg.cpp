@@ -1,0 +1,35 @@
+// jpeg.cpp -- imread of "<k>.jpg" for the host tools (declared in stitcher.hpp): the files' bytes through mis_jpeg_decode_batch, one
+// call for all frames (host entropy decode, device IDCT / upsampling / colour), the pixels back as 8UC3 BGR host images
+#include <fstream>
+#include <iterator>
+#include <stdexcept>
+#include "stitcher.hpp"
+
+namespace mis {
+
+std::vector<HostImage> decodeJPEGBatch(MisContext* ctx, const std::vector<std::string>& paths) {
+    const int n = (int)paths.size();
+    std::vector<std::vector<char>> bytes(n);
+    std::vector<const void*> datas(n);
+    std::vector<size_t> sizes(n);
+    std::vector<HostImage> out(n);
+    std::vector<MisImage> dsts(n);
+    for (int i = 0; i < n; i++) {
+        std::ifstream f(paths[i], std::ios::binary);
+        if (!f) throw std::runtime_error("Can't open image " + paths[i]);
+        bytes[i].assign(std::istreambuf_iterator<char>(f), std::istreambuf_iterator<char>());
+        datas[i] = bytes[i].data(); sizes[i] = bytes[i].size();
+        MisJpegInfo info;
+        if (mis_jpeg_info(datas[i], sizes[i], &info) != MIS_OK) throw std::runtime_error(paths[i] + ": " + mis_jpeg_last_error());
+        out[i].width = info.width; out[i].height = info.height; out[i].channels = 3;
+        out[i].data.resize((size_t)info.width * info.height * 3);
+        dsts[i] = MisImage{out[i].data.data(), info.width, info.height, 3, (size_t)info.width * 3, MIS_U8, MIS_MEM_HOST};
+    }
+    if (n > 0 && mis_jpeg_decode_batch(ctx, datas.data(), sizes.data(), n, dsts.data()) != MIS_OK)
+        throw std::runtime_error(std::string("mis_jpeg_decode_batch: ") + mis_last_error(ctx));
+    return out;
+}
+
+HostImage decodeJPEG(MisContext* ctx, const std::string& path) { return std::move(decodeJPEGBatch(ctx, {path})[0]); }
+
+}  // namespace mis

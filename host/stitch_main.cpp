@@ -1,7 +1,8 @@
 // stitch_main.cpp -- command-line driver mirroring the reference's main() (image_stitching.cpp:281):
 //   stitch_main <dir>
-// <dir> holds frames "<k>.ppm" (binary PPM; libjpeg / libexif are not available in this environment)
-// and, per frame, "<k>.txt" with the phone app's EXIF ImageDescription string
+// <dir> holds frames "<k>.jpg" (baseline JPEG, decoded by the library: mis_jpeg_decode_batch, one call for all frames) or "<k>.ppm"
+// (binary PPM); where a directory holds numbered .ppm files they are the frames, as before, and a "<k>.jpg" beside one is only its
+// EXIF source.  Per frame the camera is the EXIF ImageDescription of "<k>.jpg", else "<k>.txt" with the phone app's string
 // "isPortrait;compass;[proj 4x4];[view 4x4];[cameraTransform 4x4];[K 3x3]" (image_stitching.cpp:413-445).
 // Frames are sorted by the leading integer of the file name (:327-335).  Writes result.ppm / result_mask.pgm.
 //   stitch_main <dir> --mode scans
@@ -55,14 +56,18 @@ int main(int argc, char** argv) {
     if (cfg.warp_type == "mercator") { std::cout << "warper 'mercator' is not implemented in stitch_main (stitch_bench --warp mercator and the mis:: C++ API run it)\n"; return -1; }
     try { if (!mis::mode_is_scans(cfg.mode)) mis::estimator_is_homography(cfg.estimator_type); mis::check_range_width(cfg.range_width); mis::matcher_model(cfg.matcher_type, cfg.range_width); mis::expos_comp_kind(cfg.expos_comp_type, cfg.expos_comp_nr_feeds); } catch (const std::exception& e) { std::cout << e.what() << "\n"; return -1; }
     namespace fs = std::filesystem;
-    std::vector<std::string> img_names;
+    std::vector<std::string> img_names, jpg_names;
     for (auto& e : fs::directory_iterator(argv[1])) {
         std::string ext = e.path().extension().string();
         std::transform(ext.begin(), ext.end(), ext.begin(), ::tolower);
         const std::string stem = e.path().stem().string();
         const bool numbered = !stem.empty() && std::all_of(stem.begin(), stem.end(), [](unsigned char ch) { return std::isdigit(ch) != 0; });
         if (ext == ".ppm" && numbered) img_names.push_back(e.path().string());   // 1.ppm, 2.ppm, ...: not an earlier run's result.ppm
+        if (ext == ".jpg" && numbered) jpg_names.push_back(e.path().string());
     }
+    // the frames are the numbered .ppm files where there are any; a directory of numbered .jpg files alone is decoded (image_stitching.cpp:569)
+    const bool from_jpeg = img_names.empty() && !jpg_names.empty();
+    if (from_jpeg) img_names = jpg_names;
     std::sort(img_names.begin(), img_names.end(), [](const std::string& a, const std::string& b) {
         return std::strtol(fs::path(a).filename().string().c_str(), nullptr, 10) < std::strtol(fs::path(b).filename().string().c_str(), nullptr, 10);
     });
@@ -73,12 +78,18 @@ int main(int argc, char** argv) {
     try {
         std::vector<mis::HostImage> frames;
         std::vector<mis::CameraParams> cams;
+        if (from_jpeg) {
+            MisContext* dctx = nullptr;
+            if (mis_context_create(0, nullptr, &dctx) != MIS_OK) throw std::runtime_error("mis_context_create failed: no HIP device (there is no CPU fallback)");
+            try { frames = mis::decodeJPEGBatch(dctx, img_names); } catch (...) { mis_context_destroy(dctx); throw; }
+            mis_context_destroy(dctx);
+        }
         for (auto& name : img_names) {
-            frames.push_back(mis::readPPM(name));
+            if (!from_jpeg) frames.push_back(mis::readPPM(name));
             // Stitcher::create(SCANS) and --estimator homography: the cameras come from the matches, no per-frame description is read
             if (cfg.mode == "scans" || cfg.estimator_type == "homography") continue;
-            // the camera: the EXIF ImageDescription of "<k>.jpg" beside the frame when there is one (the reference's source,
-            // image_stitching.cpp:344-347, :411-417; the pixels still come from the .ppm: no JPEG decoder here), else "<k>.txt"
+            // the camera: the EXIF ImageDescription of "<k>.jpg" -- the frame itself or the file beside a .ppm frame -- when there is
+            // one (the reference's source, image_stitching.cpp:344-347, :411-417), else "<k>.txt"
             std::string desc;
             if (!mis::exifImageDescriptionFile(fs::path(name).replace_extension(".jpg").string(), &desc)) {
                 std::ifstream f(fs::path(name).replace_extension(".txt"));

@@ -161,6 +161,9 @@ std::vector<double> parseMatrixStr(std::string_view sv, int* side);
 CameraParams cameraFromImageDescription(const std::string& desc, bool* isPortrait);
 HostImage readPPM(const std::string& path);
 void writePPM(const std::string& path, const HostImage& img);
+// imread of baseline JPEG files (jpeg.cpp: mis_jpeg_decode_batch, one call for all frames) -> 8UC3 BGR; a refused file throws its cause
+std::vector<HostImage> decodeJPEGBatch(MisContext* ctx, const std::vector<std::string>& paths);
+HostImage decodeJPEG(MisContext* ctx, const std::string& path);
 
 struct StitchResult {
     HostImage pano;      // 8UC3 (saturate_cast<uchar> of the 16SC3 result, as imwrite does)

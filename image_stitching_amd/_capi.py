@@ -14,6 +14,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mistitch.h")
 
 MIS_OK = 0
 MIS_FENCE_TIMEOUT = 1
+MIS_E_INVALID, MIS_E_UNSUPPORTED = -1, -6
 MEM_HOST, MEM_DEVICE = 0, 1
 U8, S16, F32 = 0, 1, 2
 INTER_NEAREST, INTER_LINEAR = 0, 1
@@ -98,6 +99,11 @@ class MisMatchParams(C.Structure):
 class MisCompensatorParams(C.Structure):
     _fields_ = [("type", C.c_int), ("nr_feeds", C.c_int), ("block_width", C.c_int), ("block_height", C.c_int),
                 ("nr_gain_filtering_iterations", C.c_int)]
+
+
+class MisJpegInfo(C.Structure):
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("components", C.c_int), ("h", C.c_int * 4), ("v", C.c_int * 4),
+                ("restart_interval", C.c_int)]
 
 
 class MisDMatch(C.Structure):
@@ -227,6 +233,12 @@ PROTOTYPES = {
     "mis_copy_2d": (_i, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_size_t, C.c_size_t]),
     "mis_blender_feed_rect": (_i, [_vp, _i, _i, MisPoint, _P(MisRect)]),
     "mis_blender_level_info": (_i, [_vp, _i, _P(_i), _P(_i), _P(_vp), _P(_vp)]),
+    "mis_jpeg_info": (_i, [_vp, C.c_size_t, _P(MisJpegInfo)]),
+    "mis_jpeg_last_error": (C.c_char_p, []),
+    "mis_jpeg_decode": (_i, [_vp, _vp, C.c_size_t, _P(MisImage)]),
+    "mis_jpeg_decode_batch": (_i, [_vp, _P(_vp), _P(C.c_size_t), _i, _P(MisImage)]),
+    "mis_jpeg_decode_batch_timed": (_i, [_vp, _P(_vp), _P(C.c_size_t), _i, _P(MisImage), _P(C.c_float)]),
+    "mis_jpeg_debug_coefficients": (_i, [_vp, C.c_size_t, _i, _vp, C.c_size_t, _vp]),
 }
 
 

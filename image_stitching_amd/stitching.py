@@ -420,6 +420,52 @@ def resize_batch(ctx, frames, fx, fy, out=None):
     return out
 
 
+def _jpeg_bytes(path_or_bytes):
+    if isinstance(path_or_bytes, (bytes, bytearray, memoryview)):
+        return bytes(path_or_bytes)
+    with open(path_or_bytes, "rb") as fh:
+        return fh.read()
+
+
+def jpeg_info(data):
+    """The frame header of a JPEG stream (mis_jpeg_info; host logic, no device): dict(width, height, components, h, v,
+    restart_interval).  A stream the decoder refuses raises MisError with the cause."""
+    data = _jpeg_bytes(data)
+    lib = capi.load()
+    info = capi.MisJpegInfo()
+    rc = lib.mis_jpeg_info(data, len(data), C.byref(info))
+    if rc != capi.MIS_OK:
+        raise MisError(rc, lib.mis_jpeg_last_error().decode())
+    nc = info.components
+    return dict(width=info.width, height=info.height, components=nc, h=list(info.h)[:nc], v=list(info.v)[:nc], restart_interval=info.restart_interval)
+
+
+def imread_batch(ctx, sources):
+    """cv::imread (IMREAD_COLOR) of n baseline JPEG files or byte strings of any sizes in one pass (mis_jpeg_decode_batch; the
+    imread of image_stitching.cpp:569) -> list of H x W x 3 uint8 BGR device images.  One refused stream refuses the call; the
+    error names the frame."""
+    datas = [_jpeg_bytes(s) for s in sources]
+    n = len(datas)
+    if n == 0:
+        return []
+    out = []
+    for i, d in enumerate(datas):
+        try:
+            info = jpeg_info(d)
+        except MisError as e:
+            raise MisError(e.code, "frame %d: %s" % (i, str(e).split(": ", 1)[1])) from None
+        out.append(_empty_image(ctx, info["height"], info["width"], 3, torch.uint8))
+    ptrs = _c_array(C.c_void_p, (C.cast(C.c_char_p(d), C.c_void_p) for d in datas))
+    sizes = _c_array(C.c_size_t, (len(d) for d in datas))
+    ctx.check(ctx.lib.mis_jpeg_decode_batch(ctx.h, ptrs, sizes, n, _images(out)))
+    return out
+
+
+def imread(ctx, path_or_bytes):
+    """cv::imread(path) of one baseline JPEG (file name or bytes) -> H x W x 3 uint8 BGR device image."""
+    return imread_batch(ctx, [path_or_bytes])[0]
+
+
 def rotate(ctx, src, code):
     """cv::rotate(src, dst, code) on the device (8UC1 / 8UC3)."""
     simg = as_image(src)

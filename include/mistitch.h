@@ -594,6 +594,42 @@ int mis_blender_feed_rect(const MisBlender* b, int width, int height, MisPoint t
 /* accumulated pyramid level before blend() (host copies, parity tests / multi-GPU reduction hooks) */
 int mis_blender_level_info(const MisBlender* b, int level, int* width, int* height, void** lap_dev, void** weight_dev);
 
+/* ---------------------------------------------------------------- JPEG ingest ---------------- */
+/* imread("<k>.jpg") -- replaces image_stitching.cpp:569 (cv::imread with IMREAD_COLOR: 8UC3 BGR, a grey file gives B = G = R).
+ * Baseline (SOF0, Huffman, 8-bit) streams of 1 or 3 components in one interleaved scan, luma sampled 1x1, 2x1 or 2x2 with 1x1
+ * chroma; restart markers, custom Huffman tables and fill bytes are handled.  The result is bit for bit libjpeg-turbo's default
+ * decode (JDCT_ISLOW, fancy upsampling), which is cv::imread's.  The entropy decode runs on host threads (frames and restart
+ * intervals side by side), dequantisation + inverse DCT, upsampling and colour conversion on the device.
+ * MIS_E_UNSUPPORTED, by name: progressive (SOF2), extended / lossless / hierarchical SOFs, arithmetic coding, 12-bit precision,
+ * 16-bit quantisation tables, 4 components, multi-scan or non-interleaved files, any other sampling layout (4:4:0, 4:1:1, 4:4:4
+ * written as all-2x2, ...), and a block whose coefficients are beyond the bound of the 32-bit inverse DCT (jpeg_core.h: no
+ * encoder makes one).  MIS_E_INVALID: a truncated stream (libjpeg pads a truncated scan with zeros; this decoder refuses it), a
+ * missing table, a zero run past coefficient 63, a Huffman code that is not in the table, a wrong restart index or count, a zero
+ * dimension, width * height >= 2^31.  A refused stream writes nothing.  No EXIF-orientation rotation (the reference rotates by
+ * isPortrait itself, :570-577). */
+typedef struct {
+    int width, height, components;
+    int h[4], v[4];             /* the sampling factors of each component as the frame header writes them */
+    int restart_interval;       /* MCUs between restart markers, 0: none */
+} MisJpegInfo;
+/* the frame header of a stream: host logic, no context and no device.  The text of a refusal: mis_jpeg_last_error(), of the
+ * calling thread's last context-free JPEG call. */
+int mis_jpeg_info(const void* data, size_t bytes, MisJpegInfo* out);
+const char* mis_jpeg_last_error(void);
+/* One frame / n frames of any sizes and layouts in one pass: one upload, one set of two launches for all n.  Outputs follow the
+ * library's convention (data == NULL: allocated in HBM; otherwise exactly width x height, 8UC3, host or device, any stride >= 3 *
+ * width).  A refused stream anywhere in a batch refuses the whole call before anything is launched or allocated; the error text
+ * names the frame ("frame <i>: ..."). */
+int mis_jpeg_decode(MisContext* ctx, const void* data, size_t bytes, MisImage* dst_bgr);
+int mis_jpeg_decode_batch(MisContext* ctx, const void* const* datas, const size_t* bytes, int n, MisImage* dsts_bgr);
+/* the same call with its parts timed (tools/jpeg_decode_bench.py): ms[0] the header pass and ms[1] the entropy decode on the host
+ * clock, ms[2] the upload, ms[3] the IDCT launch and ms[4] the upsampling + colour launch between events on the stream */
+int mis_jpeg_decode_batch_timed(MisContext* ctx, const void* const* datas, const size_t* bytes, int n, MisImage* dsts_bgr, float ms[5]);
+/* the host layer alone: the quantised coefficient blocks of one component as the entropy decoder hands them to the device (int16,
+ * natural order, 64 per block, the plane of (MCUs_y * V) x (MCUs_x * H) blocks row by row) and its quantisation table in natural
+ * order.  No context and no device.  capacity (in coefficients) smaller than the plane: MIS_E_INVALID. */
+int mis_jpeg_debug_coefficients(const void* data, size_t bytes, int component, int16_t* out, size_t capacity, uint16_t qtable[64]);
+
 #ifdef __cplusplus
 }
 #endif
