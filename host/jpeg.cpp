@@ -1,5 +1,6 @@
 // jpeg.cpp -- imread of "<k>.jpg" for the host tools (declared in stitcher.hpp): the files' bytes through mis_jpeg_decode_batch, one
-// call for all frames (host entropy decode, device IDCT / upsampling / colour), the pixels back as 8UC3 BGR host images
+// call for all frames (host entropy decode, device IDCT / upsampling / colour), the pixels back as 8UC3 BGR host images; and imwrite
+// of a .jpg (image_stitching.cpp:1228) through mis_jpeg_encode (device colour / DCT / quantisation, host Huffman coding)
 #include <fstream>
 #include <iterator>
 #include <stdexcept>
@@ -31,5 +32,30 @@ std::vector<HostImage> decodeJPEGBatch(MisContext* ctx, const std::vector<std::s
 }
 
 HostImage decodeJPEG(MisContext* ctx, const std::string& path) { return std::move(decodeJPEGBatch(ctx, {path})[0]); }
+
+std::vector<uint8_t> encodeJPEG(MisContext* ctx, const MisImage& bgr, const MisJpegEncodeParams& params) {
+    MisJpegStream s{nullptr, 0};
+    if (mis_jpeg_encode(ctx, &bgr, &params, &s) != MIS_OK) throw std::runtime_error(std::string("mis_jpeg_encode: ") + mis_last_error(ctx));
+    std::vector<uint8_t> out(s.data, s.data + s.bytes);
+    mis_jpeg_stream_free(&s);
+    return out;
+}
+
+std::vector<uint8_t> encodeJPEG(MisContext* ctx, const HostImage& bgr, const MisJpegEncodeParams& params) {
+    const MisImage img{const_cast<uint8_t*>(bgr.data.data()), bgr.width, bgr.height, bgr.channels, (size_t)bgr.width * bgr.channels, MIS_U8, MIS_MEM_HOST};
+    return encodeJPEG(ctx, img, params);
+}
+
+void writeJPEG(const std::string& path, MisContext* ctx, const MisImage& bgr, const MisJpegEncodeParams& params) {
+    const std::vector<uint8_t> bytes = encodeJPEG(ctx, bgr, params);
+    std::ofstream f(path, std::ios::binary);
+    f.write((const char*)bytes.data(), (std::streamsize)bytes.size());
+    if (!f) throw std::runtime_error("Can't write " + path);
+}
+
+void writeJPEG(const std::string& path, MisContext* ctx, const HostImage& bgr, const MisJpegEncodeParams& params) {
+    const MisImage img{const_cast<uint8_t*>(bgr.data.data()), bgr.width, bgr.height, bgr.channels, (size_t)bgr.width * bgr.channels, MIS_U8, MIS_MEM_HOST};
+    writeJPEG(path, ctx, img, params);
+}
 
 }  // namespace mis

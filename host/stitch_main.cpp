@@ -10,6 +10,9 @@
 //   stitch_main <dir> --estimator homography [--ba ray]
 // stitches a rotation panorama from the images alone as cv::Stitcher::create(PANORAMA) does (HomographyBasedEstimator, then the
 // configured adjuster and wave correction): no "<k>.txt" is read either.
+//   stitch_main <dir> --jpeg [quality]
+// writes result.jpg as well (image_stitching.cpp:1228: imwrite's JPEG, quality 95 unless given, 4:2:0), in every mode; the flag
+// stands last on the command line.
 #include <algorithm>
 #include <cctype>
 #include <filesystem>
@@ -23,10 +26,20 @@
 int main(int argc, char** argv) {
     if (argc < 2) {
         std::cout << "usage: " << argv[0] << " <image directory> [--features orb|sift] [--ba no|reproj|ray] [--ba_refine_mask xxxxx] [--wave_correct horiz|vert|no]\n"
-                     "       [--expos_comp no|gain|gain_blocks|channels|channels_blocks] [--expos_comp_nr_feeds N] [--seam no|voronoi|dp_color|dp_colorgrad] [--warp spherical|cylindrical|plane|fisheye|stereographic|compressedPlaneA2B1|compressedPlaneA1.5B1|paniniA2B1|paniniA1.5B1] [--blend no|feather|multiband] [--conf_thresh f] [--match_conf f] [--compose_megapix f] [--seam_megapix f] [--work_megapix f] [--rangewidth N] [--matcher homography|affine] [--mode panorama|scans] [--estimator supplied|homography]\n"
+                     "       [--expos_comp no|gain|gain_blocks|channels|channels_blocks] [--expos_comp_nr_feeds N] [--seam no|voronoi|dp_color|dp_colorgrad] [--warp spherical|cylindrical|plane|fisheye|stereographic|compressedPlaneA2B1|compressedPlaneA1.5B1|paniniA2B1|paniniA1.5B1] [--blend no|feather|multiband] [--conf_thresh f] [--match_conf f] [--compose_megapix f] [--seam_megapix f] [--work_megapix f] [--rangewidth N] [--matcher homography|affine] [--mode panorama|scans] [--estimator supplied|homography] [--jpeg [quality]]\n"
                      "(the reference sets these as globals, image_stitching.cpp:49-85)\n";
         return -1;
     }
+    // --jpeg [quality] closes the command line: the options before it come in pairs
+    bool write_jpeg = false;
+    int jpeg_quality = 0;       // 0: the library's default, cv::imwrite's 95
+    for (int i = 2; i < argc; i++)
+        if (std::string(argv[i]) == "--jpeg") {
+            if (i + 2 < argc || (i + 1 < argc && (jpeg_quality = std::atoi(argv[i + 1])) < 1)) { std::cout << "--jpeg [quality 1..100] is the last option\n"; return -1; }
+            if (jpeg_quality > 100) { std::cout << "--jpeg quality " << jpeg_quality << ": 1..100\n"; return -1; }
+            write_jpeg = true;
+            argc = i;
+        }
     mis::StitchConfig cfg;
     for (int i = 2; i + 1 < argc; i += 2) {
         const std::string k = argv[i], v = argv[i + 1];
@@ -109,6 +122,12 @@ int main(int argc, char** argv) {
         mis::serializeIndices(r.indices, (fs::path(argv[1]) / "indices.data").string());
         mis::writePPM((fs::path(argv[1]) / "result.ppm").string(), r.pano);
         mis::writePPM((fs::path(argv[1]) / "result_mask.pgm").string(), r.mask);
+        if (write_jpeg) {
+            MisContext* ectx = nullptr;
+            if (mis_context_create(0, nullptr, &ectx) != MIS_OK) throw std::runtime_error("mis_context_create failed: no HIP device (there is no CPU fallback)");
+            try { mis::writeJPEG((fs::path(argv[1]) / "result.jpg").string(), ectx, r.pano, MisJpegEncodeParams{jpeg_quality, MIS_JPEG_420, 0}); } catch (...) { mis_context_destroy(ectx); throw; }
+            mis_context_destroy(ectx);
+        }
         std::cout << "result " << r.pano.width << "x" << r.pano.height << ", kept " << r.indices.size() << " of " << frames.size() << " images\n";
     } catch (const std::exception& e) {
         std::cout << e.what() << "\n";

@@ -164,6 +164,12 @@ void writePPM(const std::string& path, const HostImage& img);
 // imread of baseline JPEG files (jpeg.cpp: mis_jpeg_decode_batch, one call for all frames) -> 8UC3 BGR; a refused file throws its cause
 std::vector<HostImage> decodeJPEGBatch(MisContext* ctx, const std::vector<std::string>& paths);
 HostImage decodeJPEG(MisContext* ctx, const std::string& path);
+// imwrite of a JPEG file (jpeg.cpp: mis_jpeg_encode; image_stitching.cpp:1228) from an 8UC3 BGR image in host memory or, as a MisImage,
+// wherever it lies: the file's bytes, cv::imwrite's with the defaults (quality 95, 4:2:0); a refused image throws its cause
+std::vector<uint8_t> encodeJPEG(MisContext* ctx, const MisImage& bgr, const MisJpegEncodeParams& params = MisJpegEncodeParams{0, MIS_JPEG_420, 0});
+std::vector<uint8_t> encodeJPEG(MisContext* ctx, const HostImage& bgr, const MisJpegEncodeParams& params = MisJpegEncodeParams{0, MIS_JPEG_420, 0});
+void writeJPEG(const std::string& path, MisContext* ctx, const MisImage& bgr, const MisJpegEncodeParams& params = MisJpegEncodeParams{0, MIS_JPEG_420, 0});
+void writeJPEG(const std::string& path, MisContext* ctx, const HostImage& bgr, const MisJpegEncodeParams& params = MisJpegEncodeParams{0, MIS_JPEG_420, 0});
 
 struct StitchResult {
     HostImage pano;      // 8UC3 (saturate_cast<uchar> of the 16SC3 result, as imwrite does)

@@ -15,6 +15,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mistitch.h")
 MIS_OK = 0
 MIS_FENCE_TIMEOUT = 1
 MIS_E_INVALID, MIS_E_UNSUPPORTED = -1, -6
+JPEG_420, JPEG_422, JPEG_444, JPEG_440, JPEG_411 = 0, 1, 2, 3, 4
 MEM_HOST, MEM_DEVICE = 0, 1
 U8, S16, F32 = 0, 1, 2
 INTER_NEAREST, INTER_LINEAR = 0, 1
@@ -99,6 +100,14 @@ class MisMatchParams(C.Structure):
 class MisCompensatorParams(C.Structure):
     _fields_ = [("type", C.c_int), ("nr_feeds", C.c_int), ("block_width", C.c_int), ("block_height", C.c_int),
                 ("nr_gain_filtering_iterations", C.c_int)]
+
+
+class MisJpegEncodeParams(C.Structure):
+    _fields_ = [("quality", C.c_int), ("sampling", C.c_int), ("restart_interval", C.c_int)]
+
+
+class MisJpegStream(C.Structure):
+    _fields_ = [("data", C.c_void_p), ("bytes", C.c_size_t)]
 
 
 class MisJpegInfo(C.Structure):
@@ -239,6 +248,12 @@ PROTOTYPES = {
     "mis_jpeg_decode_batch": (_i, [_vp, _P(_vp), _P(C.c_size_t), _i, _P(MisImage)]),
     "mis_jpeg_decode_batch_timed": (_i, [_vp, _P(_vp), _P(C.c_size_t), _i, _P(MisImage), _P(C.c_float)]),
     "mis_jpeg_debug_coefficients": (_i, [_vp, C.c_size_t, _i, _vp, C.c_size_t, _vp]),
+    "mis_jpeg_encode": (_i, [_vp, _P(MisImage), _P(MisJpegEncodeParams), _P(MisJpegStream)]),
+    "mis_jpeg_encode_batch": (_i, [_vp, _P(MisImage), _i, _P(MisJpegEncodeParams), _P(MisJpegStream)]),
+    "mis_jpeg_encode_batch_timed": (_i, [_vp, _P(MisImage), _i, _P(MisJpegEncodeParams), _P(MisJpegStream), _P(C.c_float)]),
+    "mis_jpeg_stream_free": (_i, [_P(MisJpegStream)]),
+    "mis_jpeg_debug_entropy_encode": (_i, [_P(_vp), _i, _i, _P(MisJpegEncodeParams), _i, _P(MisJpegStream)]),
+    "mis_jpeg_debug_encode_coefficients": (_i, [_vp, _P(MisImage), _P(MisJpegEncodeParams), _i, _vp, C.c_size_t, _vp]),
 }
 
 

@@ -75,6 +75,9 @@ void mis_knn_ahead_drop(MisContext* ctx, const void* owner);
 struct MisSeamGradJob { const uint8_t* src; size_t ss; float* gx; size_t gxs; float* gy; size_t gys; int w, h; };
 int mis_seam_grad_enqueue(MisContext* ctx, const MisSeamGradJob* jobs, int n);
 
+// the text mis_jpeg_last_error() returns to the calling thread (jpeg.hip): set by the context-free JPEG entries
+void mis_jpeg_set_last_error(const char* text);
+
 #define MIS_HIP(ctx, call)                                                                           \
     do {                                                                                               \
         hipError_t e_ = (call);                                                                        \

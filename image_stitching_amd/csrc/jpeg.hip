@@ -8,10 +8,9 @@
 // holds only geometry that jpeg_parse has validated.
 #include <algorithm>
 #include <array>
-#include <atomic>
 #include <chrono>
-#include <thread>
 #include "common.h"
+#include "host_threads.h"
 #include "jpeg_core.h"
 #include "jpeg_host.h"
 
@@ -117,18 +116,6 @@ thread_local std::string g_jpeg_error;      // of the context-free entries
 
 int free_error(const JpegError& e) { g_jpeg_error = e.text; return e.code; }
 
-// items 0 .. n - 1 handed out in order to at most min(16, hardware threads) host threads, the caller's among them
-template <class F>
-void run_on_host_threads(size_t n, F f) {
-    std::atomic<size_t> next{0};
-    auto worker = [&]() { for (size_t t = next++; t < n; t = next++) f(t); };
-    const size_t hw = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-    std::vector<std::thread> th;
-    for (size_t t = 1; t < std::min(hw, n); t++) th.emplace_back(worker);
-    worker();
-    for (auto& t : th) t.join();
-}
-
 // the restart intervals of all frames on host threads: a frame's intervals in up to 16 runs, the runs handed out in order
 struct EntropyTask { int frame; size_t first, count; };
 
@@ -158,6 +145,8 @@ int decode_batch(MisContext* ctx, const void* const* datas, const size_t* bytes,
 }  // namespace
 
 extern "C" const char* mis_jpeg_last_error(void) { return g_jpeg_error.c_str(); }
+
+void mis_jpeg_set_last_error(const char* text) { g_jpeg_error = text; }
 
 extern "C" int mis_jpeg_info(const void* data, size_t bytes, MisJpegInfo* out) {
     JpegError e;

@@ -466,6 +466,56 @@ def imread(ctx, path_or_bytes):
     return imread_batch(ctx, [path_or_bytes])[0]
 
 
+JPEG_SAMPLING = {"420": capi.JPEG_420, "422": capi.JPEG_422, "444": capi.JPEG_444, "440": capi.JPEG_440, "411": capi.JPEG_411}
+
+
+def jpeg_encode_params(quality=95, sampling="420", restart_interval=0, optimize=False, progressive=False):
+    """MisJpegEncodeParams of the keyword arguments imencode / imwrite take.  The library writes standard Huffman tables in one
+    sequential scan: optimize and progressive are refused by name."""
+    if optimize:
+        raise MisError(capi.MIS_E_UNSUPPORTED, "jpeg: optimised Huffman tables")
+    if progressive:
+        raise MisError(capi.MIS_E_UNSUPPORTED, "jpeg: progressive output")
+    key = str(sampling).replace(":", "")
+    if key not in JPEG_SAMPLING:
+        raise MisError(capi.MIS_E_UNSUPPORTED, "jpeg: sampling %r (4:2:0, 4:2:2 and 4:4:4 only)" % (sampling,))
+    return capi.MisJpegEncodeParams(int(quality), JPEG_SAMPLING[key], int(restart_interval))
+
+
+def _take_stream(lib, stream):
+    try:
+        return C.string_at(stream.data, stream.bytes) if stream.data else b""
+    finally:
+        lib.mis_jpeg_stream_free(C.byref(stream))
+
+
+def imencode_batch(ctx, images, **params):
+    """cv::imwrite's JPEG bytes (image_stitching.cpp:1228) of n 8UC3 BGR images of any sizes -- device tensors or host arrays -- in
+    one pass (mis_jpeg_encode_batch) -> list of bytes.  Keywords: quality=95, sampling="420" | "422" | "444", restart_interval=0.
+    One refused image refuses the call; the error names the frame."""
+    images = list(images)
+    n = len(images)
+    if n == 0:
+        return []
+    p = jpeg_encode_params(**params)
+    outs = (capi.MisJpegStream * n)()
+    ctx.check(ctx.lib.mis_jpeg_encode_batch(ctx.h, _images(images), n, C.byref(p), outs))
+    return [_take_stream(ctx.lib, s) for s in outs]
+
+
+def imencode(ctx, image, quality=95, sampling="420", restart_interval=0, **more):
+    """cv::imencode(".jpg", image) with cv::imwrite's defaults: one 8UC3 BGR image -> the file's bytes."""
+    return imencode_batch(ctx, [image], quality=quality, sampling=sampling, restart_interval=restart_interval, **more)[0]
+
+
+def imwrite(ctx, path, image, **params):
+    """cv::imwrite(path, image) of image_stitching.cpp:1228 for a .jpg path; returns the number of bytes written."""
+    data = imencode(ctx, image, **params)
+    with open(path, "wb") as fh:
+        fh.write(data)
+    return len(data)
+
+
 def rotate(ctx, src, code):
     """cv::rotate(src, dst, code) on the device (8UC1 / 8UC3)."""
     simg = as_image(src)

@@ -630,6 +630,46 @@ int mis_jpeg_decode_batch_timed(MisContext* ctx, const void* const* datas, const
  * order.  No context and no device.  capacity (in coefficients) smaller than the plane: MIS_E_INVALID. */
 int mis_jpeg_debug_coefficients(const void* data, size_t bytes, int component, int16_t* out, size_t capacity, uint16_t qtable[64]);
 
+/* ---------------------------------------------------------------- JPEG output ---------------- */
+/* imwrite("result.jpg", result) -- replaces image_stitching.cpp:1228 (cv::imwrite with its defaults: quality 95, 4:2:0, standard
+ * Huffman tables, a JFIF 1.01 header).  The whole file is byte for byte what libjpeg-turbo writes from the same pixels (JDCT_ISLOW).
+ * Colour conversion, chroma downsampling, forward DCT and quantisation run on the device (edges are replicated by clamped reads,
+ * dummy blocks of a partial MCU are filled there too); one copy brings the quantised coefficients to the host, whose threads
+ * Huffman-code chunks of whole MCU rows (whole restart intervals when there is an interval) side by side; the chunks are joined at
+ * bit granularity and FF bytes stuffed after the join, so the stream does not depend on the number of threads.
+ * MIS_E_UNSUPPORTED, by name: a 1- or 4-channel source, any other sampling (MIS_JPEG_440, MIS_JPEG_411, ...).  Optimised Huffman
+ * tables and progressive streams are not written: the parameters have no field for them.  MIS_E_INVALID: a zero or negative size, a
+ * dimension above 65535, a quality outside 0 .. 100, a restart interval outside 0 .. 65535. */
+enum { MIS_JPEG_420 = 0, MIS_JPEG_422 = 1, MIS_JPEG_444 = 2, MIS_JPEG_440 = 3, MIS_JPEG_411 = 4 };
+typedef struct {
+    int quality;          /* 1 .. 100, 0: the default 95 (cv::imwrite's) */
+    int sampling;         /* MIS_JPEG_420 (the default), MIS_JPEG_422, MIS_JPEG_444 */
+    int restart_interval; /* MCUs between restart markers, 0: none */
+} MisJpegEncodeParams;
+typedef struct { uint8_t* data; size_t bytes; } MisJpegStream;   /* host memory the library owns: mis_jpeg_stream_free */
+/* One image / n images of any sizes in one pass (image_stitching.cpp:1228): one upload of the argument table, one set of two
+ * launches and one download for all n.  Sources are 8UC3 BGR in host or device memory with any stride >= 3 * width; params == NULL
+ * means all defaults.  A refused image anywhere in a batch refuses the whole call before anything is launched or allocated; the
+ * error text names the frame ("frame <i>: ...").  On success every outs[i] holds a whole file. */
+int mis_jpeg_encode(MisContext* ctx, const MisImage* src_bgr, const MisJpegEncodeParams* params, MisJpegStream* out);
+int mis_jpeg_encode_batch(MisContext* ctx, const MisImage* srcs_bgr, int n, const MisJpegEncodeParams* params, MisJpegStream* outs);
+/* the same call with its parts timed (tools/jpeg_encode_bench.py; image_stitching.cpp:1228): ms[0] the upload of the argument table
+ * and the two launches, ms[1] the download of the coefficients, both between events on the stream; ms[2] the entropy coding of the
+ * chunks, ms[3] the join with byte stuffing, ms[4] the headers, on the host clock */
+int mis_jpeg_encode_batch_timed(MisContext* ctx, const MisImage* srcs_bgr, int n, const MisJpegEncodeParams* params, MisJpegStream* outs, float ms[5]);
+/* frees a stream of the entries above and of mis_jpeg_debug_entropy_encode and clears it (image_stitching.cpp:1228); NULL or an empty
+ * stream is fine */
+int mis_jpeg_stream_free(MisJpegStream* s);
+/* the host layer alone (the entropy coder of image_stitching.cpp:1228's imwrite), no context and no device: the coefficient planes
+ * of a w x h image in the layout of mis_jpeg_debug_coefficients (dummy blocks filled) -> the whole file, coded in `chunks` chunks
+ * (clamped to 1 .. the number of MCU rows or restart intervals).  The text of a refusal: mis_jpeg_last_error(). */
+int mis_jpeg_debug_entropy_encode(const int16_t* const coef[3], int w, int h, const MisJpegEncodeParams* params, int chunks, MisJpegStream* out);
+/* the device layer alone (the transform of image_stitching.cpp:1228's imwrite): the coefficient plane of one component as the kernels
+ * wrote it (int16, natural order, 64 per block, (MCUs_y * V) x (MCUs_x * H) blocks row by row) and its quantisation table in natural
+ * order.  capacity (in coefficients) smaller than the plane: MIS_E_INVALID. */
+int mis_jpeg_debug_encode_coefficients(MisContext* ctx, const MisImage* src_bgr, const MisJpegEncodeParams* params, int component,
+                                       int16_t* out, size_t capacity, uint16_t qtable[64]);
+
 #ifdef __cplusplus
 }
 #endif
