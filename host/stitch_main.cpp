@@ -10,11 +10,17 @@
 //   stitch_main <dir> --estimator homography [--ba ray]
 // stitches a rotation panorama from the images alone as cv::Stitcher::create(PANORAMA) does (HomographyBasedEstimator, then the
 // configured adjuster and wave correction): no "<k>.txt" is read either.
+//   stitch_main <dir> --view yaw,pitch,hfov,width,height
+// writes view.ppm as well: the pinhole view of that size out of the finished panorama (mis::renderView), looking yaw (about y) and
+// pitch (about x) degrees off the panorama's axis with a horizontal field of view of hfov degrees.  K and R are computed in double and
+// handed on as float32: f = (width / 2) / tan(hfov / 2), the principal point at the centre, R = Ry(yaw) Rx(pitch).
 //   stitch_main <dir> --jpeg [quality]
 // writes result.jpg as well (image_stitching.cpp:1228: imwrite's JPEG, quality 95 unless given, 4:2:0), in every mode; the flag
 // stands last on the command line.
 #include <algorithm>
 #include <cctype>
+#include <cmath>
+#include <cstdio>
 #include <filesystem>
 #include <fstream>
 #include <iostream>
@@ -26,7 +32,7 @@
 int main(int argc, char** argv) {
     if (argc < 2) {
         std::cout << "usage: " << argv[0] << " <image directory> [--features orb|sift] [--ba no|reproj|ray] [--ba_refine_mask xxxxx] [--wave_correct horiz|vert|no]\n"
-                     "       [--expos_comp no|gain|gain_blocks|channels|channels_blocks] [--expos_comp_nr_feeds N] [--seam no|voronoi|dp_color|dp_colorgrad] [--warp spherical|cylindrical|plane|fisheye|stereographic|compressedPlaneA2B1|compressedPlaneA1.5B1|paniniA2B1|paniniA1.5B1] [--blend no|feather|multiband] [--conf_thresh f] [--match_conf f] [--compose_megapix f] [--seam_megapix f] [--work_megapix f] [--rangewidth N] [--matcher homography|affine] [--mode panorama|scans] [--estimator supplied|homography] [--jpeg [quality]]\n"
+                     "       [--expos_comp no|gain|gain_blocks|channels|channels_blocks] [--expos_comp_nr_feeds N] [--seam no|voronoi|dp_color|dp_colorgrad] [--warp spherical|cylindrical|plane|fisheye|stereographic|compressedPlaneA2B1|compressedPlaneA1.5B1|paniniA2B1|paniniA1.5B1] [--blend no|feather|multiband] [--conf_thresh f] [--match_conf f] [--compose_megapix f] [--seam_megapix f] [--work_megapix f] [--rangewidth N] [--matcher homography|affine] [--mode panorama|scans] [--estimator supplied|homography] [--view yaw,pitch,hfov,width,height] [--jpeg [quality]]\n"
                      "(the reference sets these as globals, image_stitching.cpp:49-85)\n";
         return -1;
     }
@@ -41,6 +47,9 @@ int main(int argc, char** argv) {
             argc = i;
         }
     mis::StitchConfig cfg;
+    bool write_view = false;
+    double view_yaw = 0, view_pitch = 0, view_hfov = 0;
+    int view_w = 0, view_h = 0;
     for (int i = 2; i + 1 < argc; i += 2) {
         const std::string k = argv[i], v = argv[i + 1];
         if (k == "--features") cfg.features_type = v;
@@ -61,6 +70,12 @@ int main(int argc, char** argv) {
         else if (k == "--matcher") cfg.matcher_type = v;
         else if (k == "--mode") cfg.mode = v;
         else if (k == "--estimator") cfg.estimator_type = v;
+        else if (k == "--view") {
+            char tail = 0;
+            if (std::sscanf(v.c_str(), "%lf,%lf,%lf,%d,%d%c", &view_yaw, &view_pitch, &view_hfov, &view_w, &view_h, &tail) != 5 || view_w < 1 || view_h < 1 ||
+                !(view_hfov > 0 && view_hfov < 180)) { std::cout << "--view yaw,pitch,hfov,width,height: angles in degrees, 0 < hfov < 180, a positive size\n"; return -1; }
+            write_view = true;
+        }
         else { std::cout << "unknown option " << k << "\n"; return -1; }
     }
     // tests/test_warpers_job_gpu.py::test_stitch_main_warp_equals_python_stitcher uses `--warp mercator` as its example of a warper
@@ -122,6 +137,19 @@ int main(int argc, char** argv) {
         mis::serializeIndices(r.indices, (fs::path(argv[1]) / "indices.data").string());
         mis::writePPM((fs::path(argv[1]) / "result.ppm").string(), r.pano);
         mis::writePPM((fs::path(argv[1]) / "result_mask.pgm").string(), r.mask);
+        if (write_view) {
+            const double rad = M_PI / 180.0;
+            const double f = (view_w / 2.0) / std::tan(view_hfov * rad / 2.0);
+            const double cy = std::cos(view_yaw * rad), sy = std::sin(view_yaw * rad), cx = std::cos(view_pitch * rad), sx = std::sin(view_pitch * rad);
+            const double Kd[9] = {f, 0, view_w * 0.5, 0, f, view_h * 0.5, 0, 0, 1};
+            const double Rd[9] = {cy, sy * sx, sy * cx, 0, cx, -sx, -sy, cy * sx, cy * cx};      // Ry(yaw) Rx(pitch)
+            float K[9], R[9];
+            for (int i = 0; i < 9; i++) { K[i] = (float)Kd[i]; R[i] = (float)Rd[i]; }
+            MisContext* vctx = nullptr;
+            if (mis_context_create(0, nullptr, &vctx) != MIS_OK) throw std::runtime_error("mis_context_create failed: no HIP device (there is no CPU fallback)");
+            try { mis::writePPM((fs::path(argv[1]) / "view.ppm").string(), mis::renderView(vctx, r, K, R, view_w, view_h)); } catch (...) { mis_context_destroy(vctx); throw; }
+            mis_context_destroy(vctx);
+        }
         if (write_jpeg) {
             MisContext* ectx = nullptr;
             if (mis_context_create(0, nullptr, &ectx) != MIS_OK) throw std::runtime_error("mis_context_create failed: no HIP device (there is no CPU fallback)");

@@ -246,6 +246,7 @@ StitchResult Stitcher::stitch(const std::vector<HostImage>& frames, const std::v
     }
     MisRect pano;
     mis_result_roi(corners.data(), sizes.data(), kept, &pano);
+    out.pano_tl = {pano.x, pano.y}; out.warp_scale = compose_warp_scale; out.warp_kind = kind;
     int btype = 0, bands = 0;
     float sharp = 0;
     mis_blend_config(cfg_.blend_type, cfg_.blend_strength, pano.width, pano.height, &btype, &bands, &sharp);
@@ -322,6 +323,18 @@ StitchResult Stitcher::stitch(const std::vector<HostImage>& frames, const std::v
     out.pano.data.resize(res16.size());
     for (size_t i = 0; i < res16.size(); i++) out.pano.data[i] = (uint8_t)std::clamp<int>(res16[i], 0, 255);
     return out;
+}
+
+HostImage renderView(MisContext* ctx, const StitchResult& result, const float K[9], const float R[9], int width, int height) {
+    if (width <= 0 || height <= 0) throw std::runtime_error("renderView: the view size must be positive");
+    HostImage view;
+    view.width = width; view.height = height; view.channels = 3;
+    view.data.resize((size_t)width * height * 3);
+    const MisImage src{const_cast<uint8_t*>(result.pano.data.data()), result.pano.width, result.pano.height, 3, (size_t)result.pano.width * 3, MIS_U8, MIS_MEM_HOST};
+    MisImage dst{view.data.data(), width, height, 3, (size_t)width * 3, MIS_U8, MIS_MEM_HOST};
+    if (mis_warper_warp_backward(ctx, result.warp_kind, &src, result.pano_tl, result.warp_scale, K, R, MIS_INTER_LINEAR, MIS_BORDER_CONSTANT, width, height, &dst, nullptr) != MIS_OK)
+        throw std::runtime_error(std::string("mis_warper_warp_backward failed: ") + mis_last_error(ctx));
+    return view;
 }
 
 }  // namespace mis

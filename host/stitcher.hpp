@@ -179,7 +179,16 @@ struct StitchResult {
     std::vector<int> num_features;
     std::vector<double> confidence;    // n x n
     double t_features = 0, t_matching = 0, t_compositing = 0;
+    // where the panorama lies in the warper's plane: what renderView needs to go back from it
+    MisPoint pano_tl{0, 0};            // result_roi's corner
+    float warp_scale = 0.f;            // the compositing loop's warper scale
+    int warp_kind = MIS_WARP_SPHERICAL;
 };
+
+// A pinhole view (K, R: 3x3 row-major float32; width x height) rendered out of a finished panorama: mis_warper_warp_backward of
+// result.pano with its corner, scale and kind, (LINEAR, CONSTANT 0) -- a viewer's frame, a cube face, a re-projection into a source
+// camera -> 8UC3.  A refused view (a panorama wider than 32767, a scans-mode result: AffineWarper has no warpBackward) throws its cause.
+HostImage renderView(MisContext* ctx, const StitchResult& result, const float K[9], const float R[9], int width, int height);
 
 class Stitcher {
 public:

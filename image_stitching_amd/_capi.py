@@ -20,6 +20,7 @@ MEM_HOST, MEM_DEVICE = 0, 1
 U8, S16, F32 = 0, 1, 2
 INTER_NEAREST, INTER_LINEAR = 0, 1
 BORDER_CONSTANT, BORDER_REFLECT = 0, 2
+MAP_FORWARD, MAP_BACKWARD = 0, 1     # mis_warper_warp_points
 BLEND_NO, BLEND_FEATHER, BLEND_MULTI_BAND = 0, 1, 2
 WARP_SPHERICAL, WARP_CYLINDRICAL, WARP_PLANE, WARP_MERCATOR, WARP_FISHEYE, WARP_STEREOGRAPHIC = 0, 1, 2, 3, 4, 5
 # one kind per (A, B) setting the reference offers (the entries have no slot for the two parameters); 6 and 7 are not assigned
@@ -200,6 +201,10 @@ PROTOTYPES = {
     "mis_warper_warp_fused_roi": (_i, [_vp, _i, _P(MisImage), _f, _vp, _vp, _P(MisRect), _P(MisImage), _P(MisImage), _P(MisPoint)]),
     "mis_warper_warp_fused_batch": (_i, [_vp, _i, _P(MisImage), _i, C.c_float, _P(C.c_float), _P(C.c_float), _P(MisRect), _P(MisImage), _P(MisImage), _P(MisPoint)]),
     "mis_warp_spherical_fused": (_i, [_vp, _P(MisImage), _f, _vp, _vp, _P(MisImage), _P(MisImage), _P(MisPoint)]),
+    "mis_warper_warp_points": (_i, [_vp, _i, _f, _vp, _vp, _i, _vp, _vp, _i]),
+    "mis_warper_build_maps": (_i, [_vp, _i, _f, _i, _i, _vp, _vp, _P(MisRect), _P(MisImage), _P(MisImage), _P(MisRect)]),
+    "mis_warper_warp_backward": (_i, [_vp, _i, _P(MisImage), MisPoint, _f, _vp, _vp, _i, _i, _i, _i, _P(MisImage), _P(MisImage)]),
+    "mis_warper_warp_backward_batch": (_i, [_vp, _i, _P(MisImage), MisPoint, _f, _i, _vp, _vp, _P(MisSize), _i, _i, _P(MisImage), _P(MisImage)]),
     "mis_resize_linear_exact": (_i, [_vp, _P(MisImage), _i, _i, C.c_double, C.c_double, _P(MisImage)]),
     "mis_resize_linear_exact_batch": (_i, [_vp, _P(MisImage), _i, _i, _i, C.c_double, C.c_double, _P(MisImage)]),
     "mis_rotate": (_i, [_vp, _P(MisImage), _i, _P(MisImage)]),

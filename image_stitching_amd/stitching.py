@@ -316,6 +316,103 @@ class RotationWarper:
         tl = self.warp_fused_into(src_bgr, K, R, roi, dst, msk)
         return tl, dst, msk
 
+    # ---- warpPoint / warpPointBackward / buildMaps / warpBackward ----
+    def warp_points(self, pts, K, R, backward=False):
+        """mis_warper_warp_points: mapForward (or, backward=True, mapBackward at float coordinates) of an (n, 2) array of points
+        -> (n, 2) float32.  A warper without a context (ctx None) runs the library's host loop, which the kernel equals in every bit."""
+        xy = np.ascontiguousarray(np.asarray(pts, np.float32).reshape(-1, 2))
+        out = np.empty_like(xy)
+        _, kp = _mat9(K)
+        _, rp = _mat9(R)
+        lib = capi.load()
+        rc = lib.mis_warper_warp_points(self.ctx.h if self.ctx is not None else None, self.kind, self.scale, kp, rp,
+                                        capi.MAP_BACKWARD if backward else capi.MAP_FORWARD, xy.ctypes.data_as(C.c_void_p),
+                                        out.ctypes.data_as(C.c_void_p), len(xy))
+        if rc != capi.MIS_OK:
+            raise MisError(rc, self.ctx.lib.mis_last_error(self.ctx.h).decode() if self.ctx is not None else "mis_warper_warp_points: invalid arguments")
+        return out
+
+    def warpPoint(self, pt, K, R):
+        """Point2f warpPoint(pt, K, R) -> (u, v)."""
+        u, v = self.warp_points([pt], K, R)[0]
+        return float(u), float(v)
+
+    def warpPointBackward(self, pt, K, R):
+        """Point2f warpPointBackward(pt, K, R) -> (x, y); (-1, -1) behind the camera for the kinds that test z > 0."""
+        x, y = self.warp_points([pt], K, R, backward=True)[0]
+        return float(x), float(y)
+
+    def build_maps(self, src_size, K, R, roi=None, xmap=None, ymap=None):
+        """mis_warper_build_maps -> (roi, xmap, ymap): the backward map of every roi pixel as two float32 device tensors (given ones
+        are written in place, at their pitch).  roi: the one warp_roi gave for these parameters, or None (computed)."""
+        if roi is None:
+            roi = self.warp_roi(src_size, K, R)
+        x, y, w, h = (int(v) for v in roi)
+        xmap = _empty_image(self.ctx, h, w, 1, torch.float32) if xmap is None else xmap
+        ymap = _empty_image(self.ctx, h, w, 1, torch.float32) if ymap is None else ymap
+        ximg, yimg = as_image(xmap), as_image(ymap)
+        _, kp = _mat9(K)
+        _, rp = _mat9(R)
+        rin, rout = capi.MisRect(x, y, w, h), capi.MisRect()
+        self.ctx.check(self.ctx.lib.mis_warper_build_maps(self.ctx.h, self.kind, self.scale, int(src_size[0]), int(src_size[1]), kp, rp, C.byref(rin),
+                                                          C.byref(ximg), C.byref(yimg), C.byref(rout)))
+        return (rout.x, rout.y, rout.width, rout.height), xmap, ymap
+
+    def buildMaps(self, src_size, K, R):
+        """Rect buildMaps(src_size, K, R, xmap, ymap) -> (roi, xmap, ymap).  roi is (x, y, width, height) with the maps' size; OpenCV
+        returns Rect(tl, br), one less in both directions."""
+        return self.build_maps(src_size, K, R)
+
+    def _back_view(self, dst_size, cn, with_mask, dst=None, mask=None):
+        w, h = int(dst_size[0]), int(dst_size[1])
+        if w <= 0 or h <= 0:
+            raise ValueError("dst_size %r must be positive" % (dst_size,))
+        dst = _empty_image(self.ctx, h, w, cn, torch.uint8) if dst is None else dst
+        mask = (_empty_image(self.ctx, h, w, 1, torch.uint8) if mask is None else mask) if with_mask else None
+        return dst, mask
+
+    def warp_backward(self, src, src_tl, K, R, dst_size, interp=capi.INTER_LINEAR, border=capi.BORDER_CONSTANT, with_mask=False, dst=None, mask=None):
+        """mis_warper_warp_backward: the pinhole view (K, R) of size dst_size = (w, h) out of `src`, an 8UC1 / 8UC3 image whose
+        top-left pixel lies at src_tl in this warper's plane (a warped frame with its corner, a panorama with result_roi's corner)
+        -> dst, or (dst, mask) with with_mask (255 where the nearest source pixel lies inside src)."""
+        simg = as_image(src)
+        dst, mask = self._back_view(dst_size, simg.channels, with_mask, dst, mask)
+        dimg = as_image(dst)
+        mimg = as_image(mask) if mask is not None else None
+        _, kp = _mat9(K)
+        _, rp = _mat9(R)
+        self.ctx.check(self.ctx.lib.mis_warper_warp_backward(self.ctx.h, self.kind, C.byref(simg), capi.MisPoint(int(src_tl[0]), int(src_tl[1])), self.scale, kp, rp,
+                                                             int(interp), int(border), dimg.width, dimg.height, C.byref(dimg),
+                                                             C.byref(mimg) if mimg is not None else None))
+        return (dst, mask) if with_mask else dst
+
+    def warp_backward_batch(self, src, src_tl, cameras, dst_sizes, interp=capi.INTER_LINEAR, border=capi.BORDER_CONSTANT, with_mask=False):
+        """mis_warper_warp_backward_batch: the views of `cameras` ({"K", "R"} each) of sizes dst_sizes out of one source, up to 16
+        views per grid -> [dst] or [(dst, mask)], the results of warp_backward per view."""
+        n = len(cameras)
+        if n == 0:
+            return []
+        simg = as_image(src)
+        outs = [self._back_view(s, simg.channels, with_mask) for s in dst_sizes]
+        ds = _images([o[0] for o in outs])
+        ms = _images([o[1] for o in outs]) if with_mask else None
+        Ks = np.ascontiguousarray(np.stack([np.asarray(c["K"], np.float32).reshape(9) for c in cameras]))
+        Rs = np.ascontiguousarray(np.stack([np.asarray(c["R"], np.float32).reshape(9) for c in cameras]))
+        sz = _c_array(capi.MisSize, (capi.MisSize(int(s[0]), int(s[1])) for s in dst_sizes))
+        self.ctx.check(self.ctx.lib.mis_warper_warp_backward_batch(self.ctx.h, self.kind, C.byref(simg), capi.MisPoint(int(src_tl[0]), int(src_tl[1])), self.scale, n,
+                                                                   Ks.ctypes.data_as(C.c_void_p), Rs.ctypes.data_as(C.c_void_p), sz, int(interp), int(border), ds, ms))
+        return [(o[0], o[1]) if with_mask else o[0] for o in outs]
+
+    def warpBackward(self, src, K, R, interp, border, dst_size):
+        """void warpBackward(src, K, R, interp, border, dst_size, dst) -> dst.  src must have exactly the size of warpRoi(dst_size, K, R),
+        as OpenCV asserts (ValueError otherwise); its top-left is that roi's."""
+        simg = as_image(src)
+        x, y, w, h = self.warp_roi(dst_size, K, R)
+        if (simg.width, simg.height) != (w, h):
+            raise ValueError("warpBackward: src is %dx%d, the roi of dst_size %r is %dx%d (OpenCV: CV_Assert(src_size == src.size()))"
+                             % (simg.width, simg.height, tuple(dst_size), w, h))
+        return self.warp_backward(src, (x, y), K, R, dst_size, interp, border)
+
 
 class SphericalWarper(RotationWarper):
     """SphericalWarper::create(scale) (image_stitching.cpp:927, :939)."""
@@ -1893,8 +1990,10 @@ class Stitcher:
         rois = warp_rois(self.ctx, scale, (w, h), [cameras[i] for i in indices], self.kind)
         corners = [(r[0], r[1]) for r in rois]
         sizes = [(r[2], r[3]) for r in rois]
+        x, y, pw, ph = result_roi(corners, sizes)
+        # where the panorama lies in the warper's plane: what render_view needs to go back from it
+        self.composition = {"pano_tl": (x, y), "warp_scale": scale, "kind": self.kind}
         if blender is None:
-            x, y, pw, ph = result_roi(corners, sizes)
             btype, bands, sharp = blend_config(self.cfg.blend_type, self.cfg.blend_strength, (pw, ph))
             if btype == capi.BLEND_MULTI_BAND:
                 blender = MultiBandBlender(self.ctx, bands)
@@ -1912,6 +2011,15 @@ class Stitcher:
                 seam_mask_apply(self.ctx, seam_masks[k], mask)           # :1169-1171
             blender.feed(img_s, mask, tl)
         return blender.blend()
+
+    def render_view(self, pano_u8, K, R, size, interp=capi.INTER_LINEAR, border=capi.BORDER_CONSTANT, with_mask=False):
+        """A pinhole view (K, R; size = (w, h)) rendered out of the last composition's panorama, given as 8UC3 (the caller converts
+        the blender's 16SC3 result, as for imwrite): RotationWarper.warp_backward with the panorama's corner, the compose scale and
+        the warper kind that compose() recorded."""
+        c = getattr(self, "composition", None)
+        if c is None:
+            raise RuntimeError("render_view: compose() has not run on this stitcher")
+        return RotationWarper(self.ctx, c["warp_scale"], c["kind"]).warp_backward(pano_u8, c["pano_tl"], K, R, size, interp, border, with_mask)
 
     def seam_step(self, frames, cameras, indices, warped_image_scale, work_scale=None):
         """The seam-scale pass of main() (image_stitching.cpp:604-622 resize, :973-990 warp, :1002-1023 exposure

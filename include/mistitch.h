@@ -382,6 +382,44 @@ int mis_warper_warp_fused_roi(MisContext* ctx, int kind, const MisImage* src_bgr
 /* the fused warps of n frames (the loop :1086-1220) in one grid per 16 frames: the results of n mis_warper_warp_fused_roi calls */
 int mis_warper_warp_fused_batch(MisContext* ctx, int kind, const MisImage* srcs_u8x3, int n, float scale, const float* Ks, const float* Rs,
                                 const MisRect* rois, MisImage* dsts_s16x3, MisImage* dmasks_u8, MisPoint* tls);
+/* ---- the warper's point, map and backward methods ----
+ * warper->warpPoint(pt, K, R) (direction MIS_MAP_FORWARD: setCameraParams, then mapForward(pt.x, pt.y)) and
+ * warper->warpPointBackward(pt, K, R) (MIS_MAP_BACKWARD: mapBackward at float coordinates; the kinds that test z > 0 give (-1, -1),
+ * the plane and affine kinds divide whatever the sign) for n points.  xy_in / xy_out: host arrays of n (x, y) pairs
+ * (they may be the same array).  ctx NULL: a host loop over the library's mapForward and over the operation sequences its warp
+ * kernels evaluate for mapBackward; with a context: one point per lane of a kernel on the context's stream.  The two agree in every
+ * bit (NaN payloads aside).  The affine kind takes H for R.  n == 0: MIS_OK, nothing read or written.  MIS_E_UNSUPPORTED: an unknown
+ * kind; MIS_E_INVALID: a null pointer, scale <= 0, n < 0, another direction, with a context more than 2^27 points in one call. */
+enum { MIS_MAP_FORWARD = 0, MIS_MAP_BACKWARD = 1 };
+int mis_warper_warp_points(MisContext* ctx_or_null, int kind, float scale, const float K[9], const float R[9], int direction,
+                           const float* xy_in, float* xy_out, int n);
+/* warper->buildMaps(src_size, K, R, xmap, ymap): mapBackward(u, v) for every integer (u, v) of the warp roi into two
+ * 1-channel MIS_F32 device images of the roi's size (any row pitch that is a multiple of 4; data == NULL: the library allocates) --
+ * the maps the warp kernels evaluate in registers, bit for bit.  roi_or_null: the roi mis_warper_roi / mis_warper_roi_batch gave for
+ * these parameters (nothing is scanned again), or NULL (computed here).  roi_out (may be NULL): that roi, (x, y, width, height) with
+ * the maps' size; OpenCV returns Rect(tl, br), one less in both directions (A.17).  Refused before anything is launched or
+ * allocated: an unknown kind (MIS_E_UNSUPPORTED); null pointers, sizes <= 0, scale <= 0, maps of another geometry, a refused roi
+ * (MIS_E_INVALID). */
+int mis_warper_build_maps(MisContext* ctx, int kind, float scale, int src_width, int src_height, const float K[9], const float R[9],
+                          const MisRect* roi_or_null, MisImage* xmap_f32, MisImage* ymap_f32, MisRect* roi_out);
+/* warper->warpBackward(src, K, R, interp, border, dst_size, dst), generalised: src (8UC1 or 8UC3, 2 .. 32767 on a side)
+ * is any image whose top-left pixel lies at src_tl in the warper's plane -- a warped frame with its roi's corner (OpenCV's call, which
+ * also asserts src's size to be the roi's), or a panorama with result_roi's corner.  For every pixel (x, y) of the dst_width x
+ * dst_height view: (u, v) = mapForward(x, y), xmap = u - src_tl.x, ymap = v - src_tl.y (float32), dst = remap(src, xmap, ymap).
+ * (interp, border): (LINEAR, REFLECT), (NEAREST, CONSTANT 0) or (LINEAR, CONSTANT 0: remap's INTER_BITS = 5 quantisation and Q15
+ * weights, a tap outside src contributing 0); anything else is MIS_E_UNSUPPORTED.  dst_mask_or_null: 255 where the nearest source
+ * pixel of the map coordinate lies inside src (warpBackward of an all-255 mask with (NEAREST, CONSTANT)).  dst / mask: 8U buffers of
+ * the view's size at any pitch, or data == NULL (the library allocates).  Taps past src are border: nothing wraps at the +-180 degree
+ * seam.  A 16SC3 blend result is converted to 8U by the caller, as for imwrite.  Refused before anything is launched or allocated:
+ * an unknown kind or MIS_WARP_AFFINE, whose warper does not override warpBackward (MIS_E_UNSUPPORTED); null pointers, sizes <= 0,
+ * scale <= 0 (MIS_E_INVALID). */
+int mis_warper_warp_backward(MisContext* ctx, int kind, const MisImage* src, MisPoint src_tl, float scale, const float K[9], const float R[9],
+                             int interp, int border, int dst_width, int dst_height, MisImage* dst, MisImage* dst_mask_or_null);
+/* n views (Ks, Rs: n x 9 floats; dst_sizes[i]: view i's size) out of one source: the results of n
+ * mis_warper_warp_backward calls, the tiles of up to 16 views in one one-dimensional grid.  masks_or_null: n masks or NULL.  n == 0:
+ * MIS_OK; n < 0: MIS_E_INVALID.  Every view is checked before the first output is touched; the error text names a refused view. */
+int mis_warper_warp_backward_batch(MisContext* ctx, int kind, const MisImage* src, MisPoint src_tl, float scale, int n, const float* Ks,
+                                   const float* Rs, const MisSize* dst_sizes, int interp, int border, MisImage* dsts, MisImage* masks_or_null);
 /* test aid: out[i] = f(in[i]) for one of the library's float32 functions (dev_math.h), evaluated on the host (ctx NULL) or in a
  * one-thread-per-element kernel on the context's stream (in / out are host arrays either way).  fn: MIS_MATH_*. */
 enum { MIS_MATH_LOG = 0, MIS_MATH_TAN = 1, MIS_MATH_SINH = 2, MIS_MATH_ASIN = 3, MIS_MATH_ATAN = 4, MIS_MATH_EXP = 5 };
