@@ -165,7 +165,7 @@ class HipEngine:
         # finder per features_type (image_stitching.cpp:543-563): ORB, or SIFT (float descriptors -> the L2 matcher)
         self.finder = st.SiftFeatureFinder(ctx, self.work_size) if self.cfg.features_type == "sift" else st.OrbFeatureFinder(ctx, self.work_size)
         self.matcher = st.make_matcher(ctx, self.cfg)
-        self.blender = None
+        self.blender = self._blend = None      # begin_compose
         self._keep = []
         # warp + blend run in a context of their own (second stream): StitchJob composes speculatively while the
         # latency-bound RANSAC chains of the matcher leave most of the device idle
@@ -205,10 +205,7 @@ class HipEngine:
         kps = torch.empty((m, cap * 24), dtype=torch.uint8, device=dev)
         desc = torch.empty((m, cap * rb), dtype=torch.uint8, device=dev)
         if m:
-            arr = (capi.MisFeatures * m)()
-            for k, f in enumerate(feats):
-                C.memmove(C.byref(arr[k]), C.byref(f.raw), C.sizeof(capi.MisFeatures))
-            self.ctx.check(self.ctx.lib.mis_features_pack(self.ctx.h, arr, m, int(cap), int(rb), C.c_void_p(kps.data_ptr()), C.c_void_p(desc.data_ptr())))
+            self.ctx.check(self.ctx.lib.mis_features_pack(self.ctx.h, st.features_array(feats), m, int(cap), int(rb), C.c_void_p(kps.data_ptr()), C.c_void_p(desc.data_ptr())))
         return kps, desc
 
     def _row_bytes(self, feats=None):
@@ -286,20 +283,14 @@ class HipEngine:
         if not frames:       # every frame of this rank was pruned: nothing to warp or feed (the collectives around still run)
             return
         warped = self.warper.warp_fused_batch(frames, cams, rois)
-        compensator, seam_masks = self._seam
         for (tl, img_s, mask), k in zip(warped, ks):
-            if compensator is not None:
-                compensator.apply(k, tl, img_s, mask)
-            st.seam_mask_apply(self.cctx, seam_masks[k], mask)
+            st.apply_seam(self.cctx, self._seam, k, tl, img_s, mask)
         self.blender.feed_batch([w[1] for w in warped], [w[2] for w in warped], [w[0] for w in warped])
 
     def warp_feed_seam(self, frame, cam, roi, k):
         """warp -> gains of image k -> seam mask of image k -> feed (image_stitching.cpp:1154-1171, :1218)."""
         tl, img_s, mask = self.warper.warp_fused(frame, cam["K"], cam["R"], roi)
-        compensator, seam_masks = self._seam
-        if compensator is not None:
-            compensator.apply(k, tl, img_s, mask)
-        st.seam_mask_apply(self.cctx, seam_masks[k], mask)
+        st.apply_seam(self.cctx, self._seam, k, tl, img_s, mask)
         self.blender.feed(img_s, mask, tl)
 
     # ---- compose ----
@@ -318,12 +309,9 @@ class HipEngine:
 
     def begin_compose(self, scale, corners, sizes):
         x, y, pw, ph = st.result_roi(corners, sizes)
-        btype, bands, sharp = st.blend_config(self.cfg.blend_type, self.cfg.blend_strength, (pw, ph))
-        key = (btype, bands, sharp)
-        if self.blender is None or getattr(self, "_blender_key", None) != key:   # band count / sharpness are creation parameters
-            self._blender_key = key
-            self.blender = {capi.BLEND_MULTI_BAND: lambda: st.MultiBandBlender(self.cctx, bands),
-                            capi.BLEND_FEATHER: lambda: st.FeatherBlender(self.cctx, sharp), capi.BLEND_NO: lambda: st.Blender(self.cctx)}[btype]()
+        # the blender of the last job is used again while band count / sharpness, its creation parameters, stay the same
+        self._blend = st.make_blender(self.cctx, self.cfg.blend_type, self.cfg.blend_strength, (pw, ph), reuse=self._blend)
+        self.blender, btype, bands, _ = self._blend
         self.blender.prepare(corners, sizes)
         self.warper = st.RotationWarper(self.cctx, scale, self.kind)
         self.pano_size = (pw, ph)
