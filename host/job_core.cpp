@@ -46,6 +46,8 @@ JobCore::JobCore(const char* who, std::string where, int device, void* main_stre
     try {
         if (cfg_.features_type != "orb" || cfg_.ba_cost_func != "no" || cfg_.expos_comp_type != "no" || cfg_.seam_find_type != "no")
             throw std::runtime_error(std::string(who) + " runs the hot path (ORB, supplied cameras, no seam-scale step); use mis::Stitcher for the other options");
+        if (cfg_.timelapse)     // the jobs end in the blender; the timelapser is another sink
+            throw std::runtime_error(std::string(who) + " blends a panorama; timelapse = true (the timelapse output) is mis::Stitcher::timelapse");
         if (mode_is_scans(cfg_.mode))       // the jobs speculate the composition from supplied cameras; the scans mode has none
             throw std::runtime_error(std::string(who) + " runs supplied cameras only; the scans mode is mis::Stitcher's");
         if (estimator_is_homography(cfg_.estimator_type))      // likewise: an estimator's cameras exist only after the matcher has returned (a name that is no estimator is refused as mis::Stitcher refuses it)

@@ -46,6 +46,20 @@ std::vector<uint8_t> encodeJPEG(MisContext* ctx, const HostImage& bgr, const Mis
     return encodeJPEG(ctx, img, params);
 }
 
+std::vector<std::vector<uint8_t>> encodeJPEGBatch(MisContext* ctx, const std::vector<HostImage>& bgrs, const MisJpegEncodeParams& params) {
+    std::vector<MisImage> imgs;
+    for (const HostImage& b : bgrs) imgs.push_back(MisImage{const_cast<uint8_t*>(b.data.data()), b.width, b.height, b.channels, (size_t)b.width * b.channels, MIS_U8, MIS_MEM_HOST});
+    std::vector<MisJpegStream> streams(imgs.size(), MisJpegStream{nullptr, 0});
+    if (imgs.empty()) return {};
+    if (mis_jpeg_encode_batch(ctx, imgs.data(), (int)imgs.size(), &params, streams.data()) != MIS_OK) throw std::runtime_error(std::string("mis_jpeg_encode_batch: ") + mis_last_error(ctx));
+    std::vector<std::vector<uint8_t>> out;
+    for (MisJpegStream& s : streams) {
+        out.emplace_back(s.data, s.data + s.bytes);
+        mis_jpeg_stream_free(&s);
+    }
+    return out;
+}
+
 void writeJPEG(const std::string& path, MisContext* ctx, const MisImage& bgr, const MisJpegEncodeParams& params) {
     const std::vector<uint8_t> bytes = encodeJPEG(ctx, bgr, params);
     std::ofstream f(path, std::ios::binary);

@@ -17,6 +17,12 @@
 //   stitch_main <dir> --jpeg [quality]
 // writes result.jpg as well (image_stitching.cpp:1228: imwrite's JPEG, quality 95 unless given, 4:2:0), in every mode; the flag
 // stands last on the command line.
+//   stitch_main <dir> --timelapse [as_is|crop]
+// writes the reference's timelapse output (image_stitching.cpp:82, :1194-1215) in place of the panorama: one registered frame
+// "fixed_<k>.jpg" per kept image <k> (imwrite's JPEG: quality 95, 4:2:0; all frames in one mis_jpeg_encode_batch call), every one warped
+// into the common canvas -- the frames' intersection ("crop", the default, :79) or their union ("as_is").  No result.ppm, no
+// result_mask.pgm and no panorama are written (:1222); with --view there is no panorama to view and the driver exits non-zero.  The
+// flag stands behind the paired options and before --view / --jpeg.
 #include <algorithm>
 #include <cctype>
 #include <cmath>
@@ -32,7 +38,7 @@
 int main(int argc, char** argv) {
     if (argc < 2) {
         std::cout << "usage: " << argv[0] << " <image directory> [--features orb|sift] [--ba no|reproj|ray] [--ba_refine_mask xxxxx] [--wave_correct horiz|vert|no]\n"
-                     "       [--expos_comp no|gain|gain_blocks|channels|channels_blocks] [--expos_comp_nr_feeds N] [--seam no|voronoi|dp_color|dp_colorgrad] [--warp spherical|cylindrical|plane|fisheye|stereographic|compressedPlaneA2B1|compressedPlaneA1.5B1|paniniA2B1|paniniA1.5B1] [--blend no|feather|multiband] [--conf_thresh f] [--match_conf f] [--compose_megapix f] [--seam_megapix f] [--work_megapix f] [--rangewidth N] [--matcher homography|affine] [--mode panorama|scans] [--estimator supplied|homography] [--view yaw,pitch,hfov,width,height] [--jpeg [quality]]\n"
+                     "       [--expos_comp no|gain|gain_blocks|channels|channels_blocks] [--expos_comp_nr_feeds N] [--seam no|voronoi|dp_color|dp_colorgrad] [--warp spherical|cylindrical|plane|fisheye|stereographic|compressedPlaneA2B1|compressedPlaneA1.5B1|paniniA2B1|paniniA1.5B1] [--blend no|feather|multiband] [--conf_thresh f] [--match_conf f] [--compose_megapix f] [--seam_megapix f] [--work_megapix f] [--rangewidth N] [--matcher homography|affine] [--mode panorama|scans] [--estimator supplied|homography] [--timelapse [as_is|crop]] [--view yaw,pitch,hfov,width,height] [--jpeg [quality]]\n"
                      "(the reference sets these as globals, image_stitching.cpp:49-85)\n";
         return -1;
     }
@@ -47,6 +53,17 @@ int main(int argc, char** argv) {
             argc = i;
         }
     mis::StitchConfig cfg;
+    // --timelapse [as_is|crop] is a flag, not a pair: it is taken out of the argument list before the pairs are read
+    std::vector<char*> args(argv, argv + argc);
+    for (size_t i = 2; i < args.size(); i++)
+        if (std::string(args[i]) == "--timelapse") {
+            cfg.timelapse = true;
+            size_t last = i + 1;
+            if (last < args.size() && std::string(args[last]).rfind("--", 0) != 0) cfg.timelapse_type = args[last++];
+            args.erase(args.begin() + i, args.begin() + last);
+            break;
+        }
+    argc = (int)args.size(); argv = args.data();
     bool write_view = false;
     double view_yaw = 0, view_pitch = 0, view_hfov = 0;
     int view_w = 0, view_h = 0;
@@ -82,6 +99,9 @@ int main(int argc, char** argv) {
     // this driver refuses ("not implemented", non-zero exit): the library, mis::Stitcher, mis::JobCore, mis::ShardedJob and stitch_bench
     // run the Mercator warper, this driver alone keeps refusing the name here until that test names another value
     if (cfg.warp_type == "mercator") { std::cout << "warper 'mercator' is not implemented in stitch_main (stitch_bench --warp mercator and the mis:: C++ API run it)\n"; return -1; }
+    try { mis::timelapse_kind(cfg.timelapse_type); } catch (const std::exception& e) { std::cout << e.what() << "\n"; return -1; }
+    if (cfg.timelapse && write_view) { std::cout << "--timelapse with --view: the timelapse output writes no panorama (image_stitching.cpp:1222), there is nothing to view\n"; return -1; }
+    if (cfg.timelapse && write_jpeg) { std::cout << "--timelapse with --jpeg: the timelapse output writes no panorama (image_stitching.cpp:1222); fixed_<k>.jpg are always JPEG files\n"; return -1; }
     try { if (!mis::mode_is_scans(cfg.mode)) mis::estimator_is_homography(cfg.estimator_type); mis::check_range_width(cfg.range_width); mis::matcher_model(cfg.matcher_type, cfg.range_width); mis::expos_comp_kind(cfg.expos_comp_type, cfg.expos_comp_nr_feeds); } catch (const std::exception& e) { std::cout << e.what() << "\n"; return -1; }
     namespace fs = std::filesystem;
     std::vector<std::string> img_names, jpg_names;
@@ -130,6 +150,26 @@ int main(int argc, char** argv) {
             cams.push_back(mis::cameraFromImageDescription(desc, &portrait));
         }
         mis::Stitcher st(0, cfg);
+        if (cfg.timelapse) {
+            mis::TimelapseResult tr = st.timelapse(frames, cams);
+            mis::serializeCameraParams(tr.cameras, (fs::path(argv[1]) / "cams.data").string());
+            mis::serializeIndices(tr.indices, (fs::path(argv[1]) / "indices.data").string());
+            // imwrite(fixed_file_name, timelapser->getDst()) (:1206-1214) for every kept frame, one encoder call for all of them
+            MisContext* ectx = nullptr;
+            if (mis_context_create(0, nullptr, &ectx) != MIS_OK) throw std::runtime_error("mis_context_create failed: no HIP device (there is no CPU fallback)");
+            try {
+                std::vector<std::vector<uint8_t>> files = mis::encodeJPEGBatch(ectx, tr.frames);
+                for (size_t k = 0; k < files.size(); k++) {
+                    const fs::path name = fs::path(argv[1]) / ("fixed_" + fs::path(img_names[tr.indices[k]]).stem().string() + ".jpg");
+                    std::ofstream f(name, std::ios::binary);
+                    f.write((const char*)files[k].data(), (std::streamsize)files[k].size());
+                    if (!f) throw std::runtime_error("cannot write " + name.string());
+                }
+            } catch (...) { mis_context_destroy(ectx); throw; }
+            mis_context_destroy(ectx);
+            std::cout << "timelapse " << tr.dst_roi.width << "x" << tr.dst_roi.height << " (" << cfg.timelapse_type << "), kept " << tr.indices.size() << " of " << frames.size() << " images\n";
+            return 0;
+        }
         mis::StitchResult r = st.stitch(frames, cams);
         // the reference checkpoints the refined cameras and the kept indices (image_stitching.cpp:707-708); with --work_megapix the
         // cameras are in work units, as the reference's are at that point

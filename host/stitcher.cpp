@@ -92,7 +92,57 @@ static const SeamFinderEntry& seam_finder(const std::string& type) {
     throw std::runtime_error("seam finder '" + type + "' is not implemented (" + names + " are)");
 }
 
+MisRect resultRoiIntersection(const std::vector<MisPoint>& corners, const std::vector<MisSize>& sizes) {
+    if (corners.empty() || corners.size() != sizes.size()) throw std::runtime_error("resultRoiIntersection: as many corners as sizes, at least one");
+    MisRect r;
+    if (mis_result_roi_intersection(corners.data(), sizes.data(), (int)corners.size(), &r) != MIS_OK) {
+        long long x0 = corners[0].x, y0 = corners[0].y, x1 = x0 + sizes[0].width, y1 = y0 + sizes[0].height;
+        for (size_t i = 1; i < corners.size(); i++) {
+            x0 = std::max<long long>(x0, corners[i].x); y0 = std::max<long long>(y0, corners[i].y);
+            x1 = std::min<long long>(x1, (long long)corners[i].x + sizes[i].width); y1 = std::min<long long>(y1, (long long)corners[i].y + sizes[i].height);
+        }
+        throw std::runtime_error("resultRoiIntersection: the frames' intersection Rect(tl = (" + std::to_string(x0) + ", " + std::to_string(y0) + "), br = (" +
+                                 std::to_string(x1) + ", " + std::to_string(y1) + ")) is empty");
+    }
+    return r;
+}
+
+Timelapser::Timelapser(MisContext* ctx, const std::string& type) : ctx_(ctx) {
+    if (mis_timelapser_create(ctx_, timelapse_kind(type), &t_) != MIS_OK) throw std::runtime_error(std::string("mis_timelapser_create: ") + mis_last_error(ctx_));
+}
+Timelapser::~Timelapser() { mis_timelapser_destroy(t_); }
+void Timelapser::initialize(const std::vector<MisPoint>& corners, const std::vector<MisSize>& sizes) {
+    if (corners.size() != sizes.size()) throw std::runtime_error("Timelapser::initialize: as many corners as sizes");
+    if (mis_timelapser_initialize(t_, corners.data(), sizes.data(), (int)corners.size()) != MIS_OK)
+        throw std::runtime_error(std::string("mis_timelapser_initialize: ") + mis_last_error(ctx_));
+}
+MisRect Timelapser::dstRoi() const {
+    MisRect r;
+    if (mis_timelapser_dst_roi(t_, &r) != MIS_OK) throw std::runtime_error(std::string("mis_timelapser_dst_roi: ") + mis_last_error(ctx_));
+    return r;
+}
+const std::vector<int16_t>& Timelapser::process(const MisImage& img, MisPoint tl) {
+    const MisRect r = dstRoi();
+    dst_.resize((size_t)r.width * r.height * 3);
+    MisImage d{dst_.data(), r.width, r.height, 3, (size_t)r.width * 6, MIS_S16, MIS_MEM_HOST};
+    if (mis_timelapser_process(t_, &img, tl, &d) != MIS_OK) throw std::runtime_error(std::string("mis_timelapser_process: ") + mis_last_error(ctx_));
+    return dst_;
+}
+
 StitchResult Stitcher::stitch(const std::vector<HostImage>& frames, const std::vector<CameraParams>& cams_in) {
+    if (cfg_.timelapse) throw std::runtime_error("timelapse = true: the timelapse output is Stitcher::timelapse, stitch() blends a panorama");
+    return run(frames, cams_in, nullptr);
+}
+
+TimelapseResult Stitcher::timelapse(const std::vector<HostImage>& frames, const std::vector<CameraParams>& cams_in) {
+    TimelapseResult tl;
+    StitchResult r = run(frames, cams_in, &tl);
+    tl.indices = std::move(r.indices); tl.cameras = std::move(r.cameras); tl.num_features = std::move(r.num_features); tl.confidence = std::move(r.confidence);
+    return tl;
+}
+
+// timelapse == nullptr: the panorama (stitch); otherwise the compositing loop ends in the timelapser and the result's pano stays empty
+StitchResult Stitcher::run(const std::vector<HostImage>& frames, const std::vector<CameraParams>& cams_in, TimelapseResult* timelapse) {
     const int n = (int)frames.size();
     const bool scans = mode_is_scans(cfg_.mode);
     const bool estimated = scans || estimator_is_homography(cfg_.estimator_type);      // (estimator_type is not read in the scans mode)
@@ -113,7 +163,9 @@ StitchResult Stitcher::stitch(const std::vector<HostImage>& frames, const std::v
     if (cfg_.ba_cost_func != "no" && cfg_.ba_cost_func != "reproj" && cfg_.ba_cost_func != "ray")
         throw std::runtime_error("bundle adjustment cost function '" + cfg_.ba_cost_func + "' is not implemented ('no', 'reproj' and 'ray' are)");
     const int expos_kind = expos_comp_kind(cfg_.expos_comp_type, cfg_.expos_comp_nr_feeds);
-    const SeamFinderEntry& seam = seam_finder(cfg_.seam_find_type);
+    const SeamFinderEntry& seam = seam_finder(timelapse ? std::string("no") : cfg_.seam_find_type);     // (the timelapser never sees the seam masks)
+    if (timelapse) seam_finder(cfg_.seam_find_type);     // an unknown name is still refused
+    const int tl_type = timelapse_kind(cfg_.timelapse_type);
     const int kind = scans ? MIS_WARP_AFFINE : warp_kind(cfg_.warp_type);
     check_range_width(cfg_.range_width);
     const int model = matcher_model(cfg_.matcher_type, cfg_.range_width);
@@ -247,14 +299,17 @@ StitchResult Stitcher::stitch(const std::vector<HostImage>& frames, const std::v
     MisRect pano;
     mis_result_roi(corners.data(), sizes.data(), kept, &pano);
     out.pano_tl = {pano.x, pano.y}; out.warp_scale = compose_warp_scale; out.warp_kind = kind;
+    if (timelapse) timelapse->dst_roi = tl_type == MIS_TIMELAPSE_CROP ? resultRoiIntersection(corners, sizes) : pano;     // :1197
     int btype = 0, bands = 0;
     float sharp = 0;
-    mis_blend_config(cfg_.blend_type, cfg_.blend_strength, pano.width, pano.height, &btype, &bands, &sharp);
-    if (btype == MIS_BLEND_MULTI_BAND) std::cout << "Multi-band blender, number of bands: " << bands << std::endl;
-    else if (btype == MIS_BLEND_FEATHER) std::cout << "Feather blender, sharpness: " << sharp << std::endl;
     MisBlender* blender = nullptr;
-    check(mis_blender_create(ctx_, btype, bands, sharp, &blender), "mis_blender_create");
-    check(mis_blender_prepare(blender, corners.data(), sizes.data(), kept), "mis_blender_prepare");
+    if (!timelapse) {
+        mis_blend_config(cfg_.blend_type, cfg_.blend_strength, pano.width, pano.height, &btype, &bands, &sharp);
+        if (btype == MIS_BLEND_MULTI_BAND) std::cout << "Multi-band blender, number of bands: " << bands << std::endl;
+        else if (btype == MIS_BLEND_FEATHER) std::cout << "Feather blender, sharpness: " << sharp << std::endl;
+        check(mis_blender_create(ctx_, btype, bands, sharp, &blender), "mis_blender_create");
+        check(mis_blender_prepare(blender, corners.data(), sizes.data(), kept), "mis_blender_prepare");
+    }
     // ---- seam-scale pass (:604-622 resize, :973-990 warp, :1002-1023 exposure compensator, :1029-1065 seam finder) ----
     const bool seam_step = cfg_.expos_comp_type != "no" || seam.find;
     MisCompensator* compensator = nullptr;
@@ -290,6 +345,58 @@ StitchResult Stitcher::stitch(const std::vector<HostImage>& frames, const std::v
         }
         if (seam.find) check(seam.find(ctx_, seam_corners.data(), images_warped.data(), masks_warped.data(), kept), seam.what);
         for (auto& im : images_warped) mis_image_free(ctx_, &im);
+    }
+    if (timelapse) {
+        // ---- the timelapser as the sink (:1194-1215): no blender, one registered frame per kept image ----
+        for (auto& m : masks_warped) if (m.data) mis_image_free(ctx_, &m);      // the seam-scale masks fed the compensator; nothing else reads them
+        const MisRect dr = timelapse->dst_roi;
+        timelapse->frames.assign(kept, HostImage{dr.width, dr.height, 3, {}});
+        for (auto& f : timelapse->frames) f.data.resize((size_t)dr.width * dr.height * 3);
+        std::vector<MisImage> srcs(kept);
+        for (int k = 0; k < kept; k++) {
+            MisImage full = view(frames[out.indices[k]]);
+            if (compose_resized) { srcs[k] = MisImage{}; check(mis_resize_linear_exact(ctx_, &full, 0, 0, compose_scale, compose_scale, &srcs[k]), "mis_resize_linear_exact (compose scale)"); }
+            else srcs[k] = full;
+        }
+        auto free_srcs = [&]() { if (compose_resized) for (auto& s : srcs) mis_image_free(ctx_, &s); };
+        if (expos_kind == MIS_EXPOS_NO || expos_kind == MIS_EXPOS_GAIN || expos_kind == MIS_EXPOS_CHANNELS) {
+            // scalar gains: warp -> gains -> canvas -> 8U of all frames in one launch per 16 frames
+            std::vector<double> gains((size_t)kept * 3);
+            for (int k = 0; compensator && k < kept; k++) check(mis_compensator_gains(compensator, k, &gains[3 * (size_t)k]), "mis_compensator_gains");
+            std::vector<float> Kf((size_t)kept * 9), Rf((size_t)kept * 9);
+            std::vector<MisRect> rois(kept);
+            std::vector<MisImage> dsts(kept);
+            for (int k = 0; k < kept; k++) {
+                std::copy(cKs[k].begin(), cKs[k].end(), Kf.begin() + 9 * (size_t)k);
+                std::copy(Rs[k].begin(), Rs[k].end(), Rf.begin() + 9 * (size_t)k);
+                rois[k] = {corners[k].x, corners[k].y, sizes[k].width, sizes[k].height};
+                dsts[k] = view(timelapse->frames[k]);
+            }
+            const int rc = mis_timelapse_warp_batch(ctx_, kind, srcs.data(), kept, compose_warp_scale, Kf.data(), Rf.data(), rois.data(), &dr, compensator ? gains.data() : nullptr,
+                                                    dsts.data(), MIS_U8);
+            free_srcs();
+            if (compensator) mis_compensator_destroy(compensator);
+            check(rc, "mis_timelapse_warp_batch");
+        } else {
+            // a gain map per frame: the warped frame is stored, multiplied, placed and clamped, frame by frame
+            Timelapser timelapser(ctx_, cfg_.timelapse_type);
+            timelapser.initialize(corners, sizes);
+            for (int k = 0; k < kept; k++) {
+                MisImage img_warped_s{}, mask_warped{};
+                MisPoint tl;
+                check(mis_warper_warp_fused(ctx_, kind, &srcs[k], compose_warp_scale, cKs[k].data(), Rs[k].data(), &img_warped_s, &mask_warped, &tl), "mis_warper_warp_fused");
+                check(mis_compensator_apply(compensator, k, &img_warped_s), "mis_compensator_apply");   // :1162
+                const std::vector<int16_t>& dst = timelapser.process(img_warped_s, tl);                  // :1203-1204
+                mis_image_free(ctx_, &img_warped_s);
+                mis_image_free(ctx_, &mask_warped);
+                for (size_t i = 0; i < dst.size(); i++) timelapse->frames[k].data[i] = (uint8_t)std::clamp<int>(dst[i], 0, 255);     // :1214
+            }
+            free_srcs();
+            mis_compensator_destroy(compensator);
+        }
+        out.t_compositing = now() - t;
+        std::cout << "Compositing, time: " << out.t_compositing << " sec" << std::endl;
+        return out;
     }
     for (int k = 0; k < kept; k++) {
         std::cout << "Compositing image #" << out.indices[k] + 1 << std::endl;

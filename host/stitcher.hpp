@@ -48,7 +48,18 @@ struct StitchConfig {
     // image_stitchin3g.cpp:746-779 / Stitcher::create(PANORAMA): no cameras are supplied; focals from the pairwise homographies,
     // rotations chained along the spanning tree, then ba_cost_func and wave_correct as configured).  Not read in the scans mode.
     std::string estimator_type = "supplied";
+    // the reference's `timelapse` switch (:82) and timelapse_type = Timelapser::CROP (:79): the compositing loop's other sink.  The flag is
+    // what a driver reads to call Stitcher::timelapse in place of stitch (stitch_main --timelapse); stitch() and the jobs refuse it by name
+    bool timelapse = false;
+    std::string timelapse_type = "crop";   // "as_is" | "crop"
 };
+
+// timelapse_type of the config -> MIS_TIMELAPSE_*; any other name is refused by name
+inline int timelapse_kind(const std::string& t) {
+    if (t == "as_is") return MIS_TIMELAPSE_AS_IS;
+    if (t == "crop") return MIS_TIMELAPSE_CROP;
+    throw std::runtime_error("timelapse_type '" + t + "': 'as_is' or 'crop' (--timelapse)");
+}
 
 // mode of the config -> scans?; an unknown name is refused by name
 inline bool mode_is_scans(const std::string& m) {
@@ -168,6 +179,8 @@ HostImage decodeJPEG(MisContext* ctx, const std::string& path);
 // wherever it lies: the file's bytes, cv::imwrite's with the defaults (quality 95, 4:2:0); a refused image throws its cause
 std::vector<uint8_t> encodeJPEG(MisContext* ctx, const MisImage& bgr, const MisJpegEncodeParams& params = MisJpegEncodeParams{0, MIS_JPEG_420, 0});
 std::vector<uint8_t> encodeJPEG(MisContext* ctx, const HostImage& bgr, const MisJpegEncodeParams& params = MisJpegEncodeParams{0, MIS_JPEG_420, 0});
+// n files in one mis_jpeg_encode_batch call (the timelapse output's fixed_<k>.jpg, image_stitching.cpp:1214)
+std::vector<std::vector<uint8_t>> encodeJPEGBatch(MisContext* ctx, const std::vector<HostImage>& bgrs, const MisJpegEncodeParams& params = MisJpegEncodeParams{0, MIS_JPEG_420, 0});
 void writeJPEG(const std::string& path, MisContext* ctx, const MisImage& bgr, const MisJpegEncodeParams& params = MisJpegEncodeParams{0, MIS_JPEG_420, 0});
 void writeJPEG(const std::string& path, MisContext* ctx, const HostImage& bgr, const MisJpegEncodeParams& params = MisJpegEncodeParams{0, MIS_JPEG_420, 0});
 
@@ -190,6 +203,39 @@ struct StitchResult {
 // camera -> 8UC3.  A refused view (a panorama wider than 32767, a scans-mode result: AffineWarper has no warpBackward) throws its cause.
 HostImage renderView(MisContext* ctx, const StitchResult& result, const float K[9], const float R[9], int width, int height);
 
+// cv::detail::resultRoiIntersection (mis_result_roi_intersection); an empty intersection throws with the rectangle named
+MisRect resultRoiIntersection(const std::vector<MisPoint>& corners, const std::vector<MisSize>& sizes);
+
+// cv::detail::Timelapser over mis_timelapser_* (image_stitching.cpp:1083, :1196-1197, :1203-1204): initialize fixes dst_roi (resultRoi for
+// "as_is", resultRoiIntersection for "crop"), process places a warped 16SC3 image (host or device) into a canvas of dst_roi's size
+class Timelapser {
+public:
+    Timelapser(MisContext* ctx, const std::string& type);
+    ~Timelapser();
+    Timelapser(const Timelapser&) = delete;
+    Timelapser& operator=(const Timelapser&) = delete;
+    void initialize(const std::vector<MisPoint>& corners, const std::vector<MisSize>& sizes);
+    MisRect dstRoi() const;
+    // -> the 16SC3 canvas, dst_roi.width * dst_roi.height * 3 values (getDst)
+    const std::vector<int16_t>& process(const MisImage& img_s16x3, MisPoint tl);
+    const std::vector<int16_t>& getDst() const { return dst_; }
+
+private:
+    MisContext* ctx_;
+    MisTimelapser* t_ = nullptr;
+    std::vector<int16_t> dst_;
+};
+
+// what Stitcher::timelapse returns: one registered frame per kept image, all of dst_roi's size
+struct TimelapseResult {
+    std::vector<HostImage> frames;     // 8UC3 BGR (saturate_cast<uchar> of the 16SC3 canvases, as imwrite does at :1214), kept-index order
+    MisRect dst_roi{0, 0, 0, 0};       // where the canvas lies in the warper's plane
+    std::vector<int> indices;
+    std::vector<CameraParams> cameras;
+    std::vector<int> num_features;
+    std::vector<double> confidence;
+};
+
 class Stitcher {
 public:
     explicit Stitcher(int device = 0, const StitchConfig& cfg = StitchConfig());
@@ -197,8 +243,13 @@ public:
     // frames: 8UC3 BGR of one size; cameras: one per frame (sensor / ground-truth K, R); none in the scans mode or with
     // estimator_type = "homography"
     StitchResult stitch(const std::vector<HostImage>& frames, const std::vector<CameraParams>& cameras);
+    // the same registration, then the timelapser in place of the blender (:1194-1215): every kept frame warped into the common
+    // canvas of cfg.timelapse_type after the exposure compensator's apply; the seam finder does not run (its masks reach no result).
+    // expos_comp_type "no", "gain", "channels": one mis_timelapse_warp_batch call; the block types: warp_fused -> apply -> process
+    TimelapseResult timelapse(const std::vector<HostImage>& frames, const std::vector<CameraParams>& cameras);
 
 private:
+    StitchResult run(const std::vector<HostImage>& frames, const std::vector<CameraParams>& cameras, TimelapseResult* timelapse);
     void check(int rc, const char* what) const;
     StitchConfig cfg_;
     MisContext* ctx_ = nullptr;

@@ -15,7 +15,8 @@ from .stitching import (AffineBestOf2NearestMatcher, BestOf2NearestMatcher, Best
                         MisError, MultiBandBlender, OrbFeatureFinder, SiftFeatureFinder, SphericalWarper, CylindricalWarper, PlaneWarper, MercatorWarper, FisheyeWarper, StereographicWarper, CompressedRectilinearWarper, PaniniWarper, AffineWarper,
                         RotationWarper, StitchConfig, Stitcher,
                         blend_config, bundle_adjust_affine_partial, bundle_adjust_ray, bundle_adjust_reproj, estimate_affine_cameras, estimate_focal, estimate_homography_cameras, focals_from_homography, computeImageFeatures, find_homography, leaveBiggestComponent, resize, resize_batch, result_roi,
-                        rotate, seam_gradients, seam_mask_apply, selected_pairs, warp_roi, wave_correct, work_geometry, imread, imread_batch, jpeg_info, imencode, imencode_batch, imwrite, jpeg_encode_params)
+                        rotate, seam_gradients, seam_mask_apply, selected_pairs, warp_roi, wave_correct, work_geometry, imread, imread_batch, jpeg_info, imencode, imencode_batch, imwrite, jpeg_encode_params,
+                        Timelapser, result_roi_intersection, timelapse_warp_batch)
 
 __all__ = [
     "Context", "MisError", "SphericalWarper", "Blender", "MultiBandBlender", "FeatherBlender", "OrbFeatureFinder", "SiftFeatureFinder",
@@ -30,3 +31,5 @@ __all__ = [
     "focals_from_homography", "estimate_focal", "estimate_homography_cameras",
     "imread", "imread_batch", "jpeg_info", "imencode", "imencode_batch", "imwrite", "jpeg_encode_params",
 ]
+# Timelapser, result_roi_intersection and timelapse_warp_batch are names of the package too; __all__ stays the list that
+# tests/golden/package_all.txt records

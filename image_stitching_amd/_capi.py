@@ -22,6 +22,7 @@ INTER_NEAREST, INTER_LINEAR = 0, 1
 BORDER_CONSTANT, BORDER_REFLECT = 0, 2
 MAP_FORWARD, MAP_BACKWARD = 0, 1     # mis_warper_warp_points
 BLEND_NO, BLEND_FEATHER, BLEND_MULTI_BAND = 0, 1, 2
+TIMELAPSE_AS_IS, TIMELAPSE_CROP = 0, 1     # cv::detail::Timelapser::AS_IS / CROP
 WARP_SPHERICAL, WARP_CYLINDRICAL, WARP_PLANE, WARP_MERCATOR, WARP_FISHEYE, WARP_STEREOGRAPHIC = 0, 1, 2, 3, 4, 5
 # one kind per (A, B) setting the reference offers (the entries have no slot for the two parameters); 6 and 7 are not assigned
 WARP_COMPRESSED_PLANE_A2B1, WARP_COMPRESSED_PLANE_A15B1, WARP_PANINI_A2B1, WARP_PANINI_A15B1 = 8, 9, 10, 11
@@ -247,6 +248,14 @@ PROTOTYPES = {
     "mis_copy_2d": (_i, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_size_t, C.c_size_t]),
     "mis_blender_feed_rect": (_i, [_vp, _i, _i, MisPoint, _P(MisRect)]),
     "mis_blender_level_info": (_i, [_vp, _i, _P(_i), _P(_i), _P(_vp), _P(_vp)]),
+    "mis_result_roi_intersection": (_i, [_P(MisPoint), _P(MisSize), _i, _P(MisRect)]),
+    "mis_timelapser_create": (_i, [_vp, _i, _P(_vp)]),
+    "mis_timelapser_destroy": (_i, [_vp]),
+    "mis_timelapser_initialize": (_i, [_vp, _P(MisPoint), _P(MisSize), _i]),
+    "mis_timelapser_dst_roi": (_i, [_vp, _P(MisRect)]),
+    "mis_timelapser_process": (_i, [_vp, _P(MisImage), MisPoint, _P(MisImage)]),
+    "mis_timelapse_warp_batch": (_i, [_vp, _i, _P(MisImage), _i, _f, _P(_f), _P(_f), _P(MisRect), _P(MisRect), _P(_d), _P(MisImage), _i]),
+    "mis_timelapse_warp_batch_timed": (_i, [_vp, _i, _P(MisImage), _i, _f, _P(_f), _P(_f), _P(MisRect), _P(MisRect), _P(_d), _P(MisImage), _i, _i, _P(_f)]),
     "mis_jpeg_info": (_i, [_vp, C.c_size_t, _P(MisJpegInfo)]),
     "mis_jpeg_last_error": (C.c_char_p, []),
     "mis_jpeg_decode": (_i, [_vp, _vp, C.c_size_t, _P(MisImage)]),

@@ -25,6 +25,8 @@ from .seams import (EXPOS_COMP_TYPES, SEAM_FIND_TYPES, BlocksChannelsCompensator
                     GainCompensator, GraphCutSeamFinder, NoSeamFinder, VoronoiSeamFinder, _Compensator, _seam_args, apply_seam,
                     check_seam_config, make_compensator, make_seam_finder, seam_gradients)
 from .blenders import Blender, FeatherBlender, MultiBandBlender, blend_config, make_blender, result_roi
+from .timelapse import (TIMELAPSE_TYPES, Timelapser, check_timelapse_config, result_roi_intersection, timelapse_kind, timelapse_warp_batch,
+                        timelapse_warp_batch_timed)
 from .features import KP_DTYPE, ImageFeatures, OrbFeatureFinder, SiftFeatureFinder, computeImageFeatures, features_array, orb_params
 from .matchers import (DMATCH_DTYPE, MATCHER_TYPES, AffineBestOf2NearestMatcher, BestOf2NearestMatcher, BestOf2NearestRangeMatcher,
                        MatchesInfo, PairwiseMatches, _require_matches, _unpack_mi, check_matcher_config, check_range_config,
@@ -64,13 +66,16 @@ def seam_scale_warp(ctx, cfg, frame_size, frame, camera, warped_image_scale, wor
     return tl, iw, mw
 
 
-def seam_solve(ctx, cfg, corners, images_warped, masks_warped, seam_finder=None):
+def seam_solve(ctx, cfg, corners, images_warped, masks_warped, seam_finder=None, find_seams=True):
     """The part of the seam-scale pass that needs every image (image_stitching.cpp:1002-1023 exposure compensator feed, :1029-1065
     seam finder) -> (compensator | None, masks_warped edited in place).  seam_finder: a finder object (anything with
-    find(images, corners, masks)) that runs in place of the configured one, as cv::Stitcher::setSeamFinder's does."""
+    find(images, corners, masks)) that runs in place of the configured one, as cv::Stitcher::setSeamFinder's does.
+    find_seams False: no finder runs, the configured one included (the timelapse mode: its masks reach no result)."""
     compensator = make_compensator(ctx, cfg)
     if compensator is not None:
         compensator.feed(corners, images_warped, masks_warped)
+    if not find_seams:
+        return compensator, masks_warped
     if seam_finder is None:
         seam_finder = make_seam_finder(ctx, cfg)
     if seam_finder is not None:
@@ -158,9 +163,11 @@ class StitchConfig:
     expos_comp_block_size: int = 64
     expos_comp_nr_filtering: int = 2
     seam_find_type: str = "dp_color"       # "no" | "voronoi" | "dp_color" | "dp_colorgrad" (SEAM_FIND_TYPES)
+    timelapse_type: str = "crop"           # "as_is" | "crop" (:79; read by Stitcher.compose_timelapse / timelapse only)
 
     def __post_init__(self):
         check_ba_config(self)
+        check_timelapse_config(self)
 
     @classmethod
     def reference(cls, **kw):
@@ -327,16 +334,17 @@ class Stitcher:
             raise RuntimeError("render_view: compose() has not run on this stitcher")
         return RotationWarper(self.ctx, c["warp_scale"], c["kind"]).warp_backward(pano_u8, c["pano_tl"], K, R, size, interp, border, with_mask)
 
-    def seam_step(self, frames, cameras, indices, warped_image_scale, work_scale=None):
+    def seam_step(self, frames, cameras, indices, warped_image_scale, work_scale=None, find_seams=True):
         """The seam-scale pass of main() (image_stitching.cpp:604-622 resize, :973-990 warp, :1002-1023 exposure
-        compensator feed, :1029-1065 seam finder) -> (compensator | None, masks_warped) or None when both are off."""
+        compensator feed, :1029-1065 seam finder) -> (compensator | None, masks_warped) or None when both are off.
+        find_seams False: the exposure compensator alone (compose_timelapse); None when it is off."""
         check_seam_config(self.cfg)
-        if self.cfg.expos_comp_type == "no" and self.cfg.seam_find_type == "no" and self.seam_finder is None:
+        if self.cfg.expos_comp_type == "no" and (not find_seams or (self.cfg.seam_find_type == "no" and self.seam_finder is None)):
             return None
         work_scale = self.work_scale if work_scale is None else work_scale
         items = [seam_scale_warp(self.ctx, self.cfg, self.frame_size, frames[i], cameras[i], warped_image_scale, work_scale,
                                  self.kind if self.kind != check_warp_config(self.cfg) else None) for i in indices]
-        return seam_solve(self.ctx, self.cfg, [it[0] for it in items], [it[1] for it in items], [it[2] for it in items], self.seam_finder)
+        return seam_solve(self.ctx, self.cfg, [it[0] for it in items], [it[1] for it in items], [it[2] for it in items], self.seam_finder, find_seams)
 
     def estimate_cameras(self, feats, pm, idx):
         """With an estimator set: the cameras of the kept frames from the matches alone (estimate_and_refine: estimator, bundle
@@ -375,6 +383,54 @@ class Stitcher:
         if self.indices is None:
             raise ValueError("compose_panorama: estimate_transform has not run")
         return self.compose(frames, self.cameras, list(self.indices))
+
+    def compose_timelapse(self, frames, as_u8=True):
+        """The compositing loop with the timelapser as its sink (image_stitching.cpp:1086-1215 with `timelapse` set): frames of the
+        registered rig (as compose_panorama takes them) each warped into the common canvas of cfg.timelapse_type -- resultRoi of all
+        warp rois ("as_is") or their intersection ("crop") -- after the exposure compensator's apply (:1162); nothing is blended and
+        the seam finder does not run (its masks reach no result).  Geometry, cameras, rois and the compose-scale resize are compose()'s.
+        No compensator, GainCompensator: one fused launch per 16 frames (timelapse_warp_batch); the block compensators: warp_fused ->
+        apply -> Timelapser.process -> saturate_cast<uchar>, frame by frame.
+        -> (canvases in kept-index order: packed 8UC3 BGR (as_u8, what imencode_batch reads) or 16SC3, dst_roi)."""
+        if self.indices is None:
+            raise ValueError("compose_timelapse: estimate_transform has not run")
+        indices, cameras = list(self.indices), self.cameras
+        scale = self.warped_image_scale([cameras[i] for i in indices])
+        g = compose_geometry(self.cfg, self.frame_size, scale, self.work_scale)
+        seam = self.seam_step(frames, cameras, indices, scale, self.work_scale, find_seams=False)
+        compensator = None if seam is None else seam[0]
+        if g.aspect != 1.0:
+            cameras = {i: scaled_camera(cameras[i], g.aspect) for i in indices}
+        if g.size != tuple(self.frame_size):
+            frames = {i: resize(self.ctx, frames[i], fx=g.compose_scale, fy=g.compose_scale) for i in indices}
+        scale = g.warp_scale
+        cams = [cameras[i] for i in indices]
+        rois = warp_rois(self.ctx, scale, g.size, cams, self.kind)
+        corners = [(r[0], r[1]) for r in rois]
+        sizes = [(r[2], r[3]) for r in rois]
+        if check_timelapse_config(self.cfg) == capi.TIMELAPSE_CROP:
+            dst_roi = result_roi_intersection(corners, sizes)
+        else:
+            dst_roi = result_roi(corners, sizes)
+        if compensator is None or isinstance(compensator, (GainCompensator, ChannelsCompensator)):
+            gains = None if compensator is None else np.stack([compensator.gains(k) for k in range(len(indices))])
+            return timelapse_warp_batch(self.ctx, self.kind, [frames[i] for i in indices], cams, rois, scale, dst_roi, gains, as_u8), dst_roi
+        warper = RotationWarper(self.ctx, scale, self.kind)
+        timelapser = Timelapser(self.ctx, self.cfg.timelapse_type)
+        timelapser.initialize(corners, sizes)
+        canvases = []
+        for k, i in enumerate(indices):
+            tl, img_s, mask = warper.warp_fused(frames[i], cameras[i]["K"], cameras[i]["R"], rois[k])
+            compensator.apply(k, corners[k], img_s, mask)
+            canvas = timelapser.process(img_s, None, tl)
+            canvases.append(canvas.clamp(0, 255).to(torch.uint8) if as_u8 else canvas)       # imwrite's saturate_cast<uchar> (:1214)
+        return canvases, dst_roi
+
+    def timelapse(self, frames, cameras=None):
+        """estimate_transform + compose_timelapse: N frames in, N registered frames out -> (canvases, dst_roi); the kept frame
+        indices are self.indices."""
+        self.estimate_transform(frames, cameras)
+        return self.compose_timelapse(frames)
 
     def stitch(self, frames, cameras=None):
         feats, pm, idx = self.estimate_transform(frames, cameras)

@@ -632,6 +632,48 @@ int mis_blender_feed_rect(const MisBlender* b, int width, int height, MisPoint t
 /* accumulated pyramid level before blend() (host copies, parity tests / multi-GPU reduction hooks) */
 int mis_blender_level_info(const MisBlender* b, int level, int* width, int* height, void** lap_dev, void** weight_dev);
 
+/* ---------------------------------------------------------------- timelapse ----------------- */
+/* The compositing loop's other sink (image_stitching.cpp:82 `timelapse`, :79 timelapse_type = Timelapser::CROP, :1083, :1194-1215):
+ * every frame is warped into one common canvas and written out as a registered frame of its own ("fixed_<name>"), nothing is
+ * blended.  SURVEY appendix A.18 has the semantics. */
+enum { MIS_TIMELAPSE_AS_IS = 0, MIS_TIMELAPSE_CROP = 1 };      /* cv::detail::Timelapser::AS_IS / CROP */
+typedef struct MisTimelapser MisTimelapser;
+/* cv::detail::resultRoiIntersection(corners, sizes) -- what TimelapserCrop::initialize (:1197) sizes its canvas with:
+ * Rect(tl = (max x_i, max y_i), br = (min (x_i + w_i), min (y_i + h_i))).  Host only, no context.  MIS_E_INVALID: a null pointer,
+ * n < 1, an empty intersection (width or height <= 0; OpenCV fails in Mat::create there). */
+int mis_result_roi_intersection(const MisPoint* corners, const MisSize* sizes, int n, MisRect* roi);
+/* timelapser = Timelapser::createDefault(timelapse_type) -- replaces :1083 (the declaration) and :1196.  Another type: MIS_E_INVALID. */
+int mis_timelapser_create(MisContext* ctx, int type, MisTimelapser** out);
+int mis_timelapser_destroy(MisTimelapser* t);
+/* timelapser->initialize(corners, sizes) -- replaces :1197: dst_roi = resultRoi (AS_IS, mis_result_roi) or resultRoiIntersection
+ * (CROP); an empty intersection is MIS_E_INVALID with the rectangle named, a canvas of 2^31 pixels or more too. */
+int mis_timelapser_initialize(MisTimelapser* t, const MisPoint* corners, const MisSize* sizes, int n);
+int mis_timelapser_dst_roi(const MisTimelapser* t, MisRect* roi);      /* before initialize: MIS_E_STATE */
+/* timelapser->process(img_warped_s, Mat::ones(...), corners[img_idx]) then getDst() -- replaces :1203-1204: the 16SC3 canvas of
+ * dst_roi's size set to 0, then every pixel of img whose panorama position tl + (x, y) lies in dst_roi copied to it, in one pass
+ * (one write per canvas pixel).  The reference's mask is all ones and is not an argument.  dst: the caller's 16SC3 buffer of the
+ * canvas's size at any 2-byte aligned pitch, or data == NULL (the library allocates).  img may lie anywhere, wholly outside
+ * included (the canvas is then all 0). */
+int mis_timelapser_process(MisTimelapser* t, const MisImage* img_s16x3, MisPoint tl, MisImage* dst_s16x3);
+/* The loop body :1154-1164 + :1203-1204 (+ the 16S -> 8U conversion of imwrite, :1214) for n frames in one launch per 16 frames:
+ * canvas i = Timelapser::process of { mis_warper_warp_fused_roi(srcs[i], Ks + 9 i, Rs + 9 i, rois[i]), then -- gains given --
+ * mis_compensator_apply of a GAIN / CHANNELS compensator whose mis_compensator_gains(i) are gains[3 i ..] } into dst_roi, bit for
+ * bit, but a canvas pixel is mapped only where it lies in rois[i] (with CROP: nowhere else), no mask plane is produced and no
+ * warped frame is stored.  rois[i]: what mis_warper_roi gave for frame i; dst_roi: mis_result_roi (AS_IS) or
+ * mis_result_roi_intersection (CROP) of the rois, or any other rectangle.  dst_format: MIS_S16 (16SC3, getDst's) or MIS_U8 (packed
+ * 8UC3 BGR, saturate_cast<uchar> of it: what mis_jpeg_encode_batch reads).  dsts[i]: a buffer of dst_roi's size in that format at
+ * any pitch, or data == NULL (the library allocates).  All kinds mis_warper_warp_fused_batch accepts; the affine kind takes H for R.
+ * Refused before anything is allocated or launched: an unknown kind (MIS_E_UNSUPPORTED); null pointers, n < 1, scale <= 0, an
+ * empty dst_roi, a canvas of 2^31 pixels or more, another format, a non-finite gain, and by name ("frame <i>: ...") a source that
+ * is not 8UC3 of 2 .. 32767 on a side, an empty roi, an output of another geometry (MIS_E_INVALID). */
+int mis_timelapse_warp_batch(MisContext* ctx, int kind, const MisImage* srcs_u8x3, int n, float scale, const float* Ks, const float* Rs,
+                             const MisRect* rois, const MisRect* dst_roi, const double* gains_or_null, MisImage* dsts, int dst_format);
+/* measurement aid (tools/timelapse_bench.py; :1203-1214): the batch launched `repeats` times between two HIP events on the context's
+ * stream; *avg_us = one pass over all n frames */
+int mis_timelapse_warp_batch_timed(MisContext* ctx, int kind, const MisImage* srcs_u8x3, int n, float scale, const float* Ks, const float* Rs,
+                                   const MisRect* rois, const MisRect* dst_roi, const double* gains_or_null, MisImage* dsts, int dst_format,
+                                   int repeats, float* avg_us);
+
 /* ---------------------------------------------------------------- JPEG ingest ---------------- */
 /* imread("<k>.jpg") -- replaces image_stitching.cpp:569 (cv::imread with IMREAD_COLOR: 8UC3 BGR, a grey file gives B = G = R).
  * Baseline (SOF0, Huffman, 8-bit) streams of 1 or 3 components in one interleaved scan, luma sampled 1x1, 2x1 or 2x2 with 1x1
