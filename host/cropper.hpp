@@ -22,6 +22,13 @@ bool compareX(Point a, Point b);   // cropper.cpp:114-117
 bool compareY(Point a, Point b);   // cropper.cpp:119-122
 // cropper.cpp:124-209 -- source: 8UC3 (or 8UC1); replaced by its crop.  Returns the rectangle used.
 Rect crop(HostImage& source);
+// the same rectangle from the library's kernels (mis_crop_rect / mis_crop, csrc/crop.hip; cropper_device.cpp), cropper.cpp:124-209.
+// src: 8UC3 BGR or 8UC1 in device memory at any stride; the two failures of crop() throw with the same texts
+Rect cropRectDevice(MisContext* ctx, const MisImage& src);
+// ... and the dense copy of the rectangle (:202-207) to dst: a device buffer with the source's rows, whose width and height become the rectangle's
+Rect cropDevice(MisContext* ctx, const MisImage& src, MisImage* dst);
+// a host image staged through the device (one upload, the rectangle's download): replaced by its crop like crop()
+Rect cropDevice(MisContext* ctx, HostImage& source);
 
 // the restated OpenCV pieces, exposed for the tests
 std::vector<std::vector<Point>> findExternalContours(const HostImage& mask /* 8UC1, non-zero = foreground */);

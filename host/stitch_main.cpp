@@ -23,6 +23,11 @@
 // into the common canvas -- the frames' intersection ("crop", the default, :79) or their union ("as_is").  No result.ppm, no
 // result_mask.pgm and no panorama are written (:1222); with --view there is no panorama to view and the driver exits non-zero.  The
 // flag stands behind the paired options and before --view / --jpeg.
+//   stitch_main <dir> --crop
+// writes the panorama without its ragged border (the reference's cropper, cropper.cpp:124-209): result.ppm, result_mask.pgm and -- with
+// --jpeg -- result.jpg are cut to the rectangle mis::cropDevice finds on the result mask with the library's kernels, and the rectangle
+// is printed ("crop x y w h").  A flag like --timelapse, anywhere among the options before --view / --jpeg; --view still looks at the
+// whole panorama; with --timelapse there is no panorama to crop and the driver exits non-zero.
 #include <algorithm>
 #include <cctype>
 #include <cmath>
@@ -34,11 +39,12 @@
 #include "stitcher.hpp"
 #include "exif.hpp"
 #include "serializer.hpp"
+#include "cropper.hpp"
 
 int main(int argc, char** argv) {
     if (argc < 2) {
         std::cout << "usage: " << argv[0] << " <image directory> [--features orb|sift] [--ba no|reproj|ray] [--ba_refine_mask xxxxx] [--wave_correct horiz|vert|no]\n"
-                     "       [--expos_comp no|gain|gain_blocks|channels|channels_blocks] [--expos_comp_nr_feeds N] [--seam no|voronoi|dp_color|dp_colorgrad] [--warp spherical|cylindrical|plane|fisheye|stereographic|compressedPlaneA2B1|compressedPlaneA1.5B1|paniniA2B1|paniniA1.5B1] [--blend no|feather|multiband] [--conf_thresh f] [--match_conf f] [--compose_megapix f] [--seam_megapix f] [--work_megapix f] [--rangewidth N] [--matcher homography|affine] [--mode panorama|scans] [--estimator supplied|homography] [--timelapse [as_is|crop]] [--view yaw,pitch,hfov,width,height] [--jpeg [quality]]\n"
+                     "       [--expos_comp no|gain|gain_blocks|channels|channels_blocks] [--expos_comp_nr_feeds N] [--seam no|voronoi|dp_color|dp_colorgrad] [--warp spherical|cylindrical|plane|fisheye|stereographic|compressedPlaneA2B1|compressedPlaneA1.5B1|paniniA2B1|paniniA1.5B1] [--blend no|feather|multiband] [--conf_thresh f] [--match_conf f] [--compose_megapix f] [--seam_megapix f] [--work_megapix f] [--rangewidth N] [--matcher homography|affine] [--mode panorama|scans] [--estimator supplied|homography] [--timelapse [as_is|crop]] [--crop] [--view yaw,pitch,hfov,width,height] [--jpeg [quality]]\n"
                      "(the reference sets these as globals, image_stitching.cpp:49-85)\n";
         return -1;
     }
@@ -63,6 +69,10 @@ int main(int argc, char** argv) {
             args.erase(args.begin() + i, args.begin() + last);
             break;
         }
+    // --crop is a flag too
+    bool crop_result = false;
+    for (size_t i = 2; i < args.size(); i++)
+        if (std::string(args[i]) == "--crop") { crop_result = true; args.erase(args.begin() + i); break; }
     argc = (int)args.size(); argv = args.data();
     bool write_view = false;
     double view_yaw = 0, view_pitch = 0, view_hfov = 0;
@@ -102,6 +112,7 @@ int main(int argc, char** argv) {
     try { mis::timelapse_kind(cfg.timelapse_type); } catch (const std::exception& e) { std::cout << e.what() << "\n"; return -1; }
     if (cfg.timelapse && write_view) { std::cout << "--timelapse with --view: the timelapse output writes no panorama (image_stitching.cpp:1222), there is nothing to view\n"; return -1; }
     if (cfg.timelapse && write_jpeg) { std::cout << "--timelapse with --jpeg: the timelapse output writes no panorama (image_stitching.cpp:1222); fixed_<k>.jpg are always JPEG files\n"; return -1; }
+    if (cfg.timelapse && crop_result) { std::cout << "--timelapse with --crop: the timelapse output writes no panorama (image_stitching.cpp:1222), there is nothing to crop; --timelapse crop cuts the frames to their intersection\n"; return -1; }
     try { if (!mis::mode_is_scans(cfg.mode)) mis::estimator_is_homography(cfg.estimator_type); mis::check_range_width(cfg.range_width); mis::matcher_model(cfg.matcher_type, cfg.range_width); mis::expos_comp_kind(cfg.expos_comp_type, cfg.expos_comp_nr_feeds); } catch (const std::exception& e) { std::cout << e.what() << "\n"; return -1; }
     namespace fs = std::filesystem;
     std::vector<std::string> img_names, jpg_names;
@@ -175,8 +186,24 @@ int main(int argc, char** argv) {
         // cameras are in work units, as the reference's are at that point
         mis::serializeCameraParams(r.cameras, (fs::path(argv[1]) / "cams.data").string());
         mis::serializeIndices(r.indices, (fs::path(argv[1]) / "indices.data").string());
-        mis::writePPM((fs::path(argv[1]) / "result.ppm").string(), r.pano);
-        mis::writePPM((fs::path(argv[1]) / "result_mask.pgm").string(), r.mask);
+        // --crop: what is written is the rectangle of the result mask; the view below still looks at the whole panorama
+        mis::HostImage cropped_pano, cropped_mask;
+        if (crop_result) {
+            MisContext* cctx = nullptr;
+            if (mis_context_create(0, nullptr, &cctx) != MIS_OK) throw std::runtime_error("mis_context_create failed: no HIP device (there is no CPU fallback)");
+            mis::Rect cr;
+            cropped_mask = r.mask;
+            try { cr = mis::cropDevice(cctx, cropped_mask); } catch (...) { mis_context_destroy(cctx); throw; }
+            mis_context_destroy(cctx);
+            cropped_pano.width = cr.width; cropped_pano.height = cr.height; cropped_pano.channels = 3;
+            cropped_pano.data.resize((size_t)cr.width * cr.height * 3);
+            for (int y = 0; y < cr.height; y++)
+                std::copy_n(&r.pano.data[((size_t)(cr.y + y) * r.pano.width + cr.x) * 3], (size_t)cr.width * 3, &cropped_pano.data[(size_t)y * cr.width * 3]);
+            std::cout << "crop " << cr.x << " " << cr.y << " " << cr.width << " " << cr.height << "\n";
+        }
+        const mis::HostImage& out_pano = crop_result ? cropped_pano : r.pano;
+        mis::writePPM((fs::path(argv[1]) / "result.ppm").string(), out_pano);
+        mis::writePPM((fs::path(argv[1]) / "result_mask.pgm").string(), crop_result ? cropped_mask : r.mask);
         if (write_view) {
             const double rad = M_PI / 180.0;
             const double f = (view_w / 2.0) / std::tan(view_hfov * rad / 2.0);
@@ -193,7 +220,7 @@ int main(int argc, char** argv) {
         if (write_jpeg) {
             MisContext* ectx = nullptr;
             if (mis_context_create(0, nullptr, &ectx) != MIS_OK) throw std::runtime_error("mis_context_create failed: no HIP device (there is no CPU fallback)");
-            try { mis::writeJPEG((fs::path(argv[1]) / "result.jpg").string(), ectx, r.pano, MisJpegEncodeParams{jpeg_quality, MIS_JPEG_420, 0}); } catch (...) { mis_context_destroy(ectx); throw; }
+            try { mis::writeJPEG((fs::path(argv[1]) / "result.jpg").string(), ectx, out_pano, MisJpegEncodeParams{jpeg_quality, MIS_JPEG_420, 0}); } catch (...) { mis_context_destroy(ectx); throw; }
             mis_context_destroy(ectx);
         }
         std::cout << "result " << r.pano.width << "x" << r.pano.height << ", kept " << r.indices.size() << " of " << frames.size() << " images\n";

@@ -16,7 +16,7 @@ from .stitching import (AffineBestOf2NearestMatcher, BestOf2NearestMatcher, Best
                         RotationWarper, StitchConfig, Stitcher,
                         blend_config, bundle_adjust_affine_partial, bundle_adjust_ray, bundle_adjust_reproj, estimate_affine_cameras, estimate_focal, estimate_homography_cameras, focals_from_homography, computeImageFeatures, find_homography, leaveBiggestComponent, resize, resize_batch, result_roi,
                         rotate, seam_gradients, seam_mask_apply, selected_pairs, warp_roi, wave_correct, work_geometry, imread, imread_batch, jpeg_info, imencode, imencode_batch, imwrite, jpeg_encode_params,
-                        Timelapser, result_roi_intersection, timelapse_warp_batch)
+                        Timelapser, result_roi_intersection, timelapse_warp_batch, crop_device, crop_rect_device)
 
 __all__ = [
     "Context", "MisError", "SphericalWarper", "Blender", "MultiBandBlender", "FeatherBlender", "OrbFeatureFinder", "SiftFeatureFinder",
@@ -31,5 +31,5 @@ __all__ = [
     "focals_from_homography", "estimate_focal", "estimate_homography_cameras",
     "imread", "imread_batch", "jpeg_info", "imencode", "imencode_batch", "imwrite", "jpeg_encode_params",
 ]
-# Timelapser, result_roi_intersection and timelapse_warp_batch are names of the package too; __all__ stays the list that
+# Timelapser, result_roi_intersection, timelapse_warp_batch, crop_device and crop_rect_device are names of the package too; __all__ stays the list that
 # tests/golden/package_all.txt records

@@ -268,6 +268,11 @@ PROTOTYPES = {
     "mis_jpeg_stream_free": (_i, [_P(MisJpegStream)]),
     "mis_jpeg_debug_entropy_encode": (_i, [_P(_vp), _i, _i, _P(MisJpegEncodeParams), _i, _P(MisJpegStream)]),
     "mis_jpeg_debug_encode_coefficients": (_i, [_vp, _P(MisImage), _P(MisJpegEncodeParams), _i, _vp, C.c_size_t, _vp]),
+    "mis_crop_rect": (_i, [_vp, _vp, _i, _i, _i, C.c_size_t, _P(_i), _P(_i)]),
+    "mis_crop_rect_timed": (_i, [_vp, _vp, _i, _i, _i, C.c_size_t, _P(_i), _P(_i), _P(_f)]),
+    "mis_crop": (_i, [_vp, _vp, _i, _i, _i, C.c_size_t, _vp, C.c_size_t, _P(_i), _P(_i)]),
+    "mis_crop_debug_contour": (_i, [_vp, _vp, _i, _i, _i, C.c_size_t, _P(_i), _P(_i), _vp, _vp, _vp]),
+    "mis_crop_stats": (_i, [_vp, _P(_i), _i, _P(_i)]),
 }
 
 

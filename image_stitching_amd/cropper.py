@@ -156,3 +156,70 @@ def crop(source):
         raise ValueError("crop: no interior rectangle found")
     x, y, w, h = rect
     return source[y:y + h, x:x + w].copy(), rect
+
+
+# ---- the device form (include/mistitch.h: mis_crop_rect, csrc/crop.hip): the same rectangle, the image stays on the device ----
+_STATUS_TEXT = {1: "crop: the image is empty", 2: "crop: no interior rectangle found"}
+
+
+def _device_source(source):
+    if not (hasattr(source, "data_ptr") and source.is_cuda and str(source.dtype) == "torch.uint8"):
+        raise TypeError("crop_device: a uint8 tensor on the device expected")
+    if source.dim() == 3 and source.shape[2] == 3 and source.stride(2) == 1 and source.stride(1) == 3:
+        return source, 3
+    if source.dim() == 2 and source.stride(1) == 1:
+        return source, 1
+    if source.dim() in (2, 3) and (source.dim() == 2 or source.shape[2] == 3):
+        return source.contiguous(), 1 if source.dim() == 2 else 3       # pixels that are not packed along a row: one device copy
+    raise ValueError("crop_device: an H x W x 3 or H x W image expected, not %s" % (tuple(source.shape),))
+
+
+def crop_rect_device(ctx, source):
+    """crop()'s rectangle (x, y, w, h) of a device image -- H x W x 3 BGR or H x W uint8, rows at any stride (a slice of a larger
+    tensor works) -- computed by the library's kernels; four integers and a status come back to the host.  Raises crop()'s two
+    ValueErrors."""
+    import ctypes as C
+    src, cn = _device_source(source)
+    rect, status = (C.c_int * 4)(), C.c_int()
+    ctx.check(ctx.lib.mis_crop_rect(ctx.h, C.c_void_p(src.data_ptr()), src.shape[1], src.shape[0], cn, src.stride(0), rect, C.byref(status)))
+    if status.value:
+        raise ValueError(_STATUS_TEXT[status.value])
+    return tuple(rect)
+
+
+def crop_device(ctx, source):
+    """crop(source) on the device -> (view, (x, y, w, h)): the view is source[y:y + h, x:x + w], no copy."""
+    x, y, w, h = crop_rect_device(ctx, source)
+    return source[y:y + h, x:x + w], (x, y, w, h)
+
+
+def crop_debug_device(ctx, source):
+    """Test hook over mis_crop_debug_contour / mis_crop_stats -> dict(count, first, xhist, yhist, cmask, launches, rounds,
+    border_pixels): the chosen contour's stages and the last call's counts."""
+    import ctypes as C
+    src, cn = _device_source(source)
+    h, w = src.shape[:2]
+    count, first = C.c_int(), C.c_int()
+    xh, yh, cm = np.zeros(w, np.int32), np.zeros(h, np.int32), np.zeros((h, w), np.uint8)
+    ctx.check(ctx.lib.mis_crop_debug_contour(ctx.h, C.c_void_p(src.data_ptr()), w, h, cn, src.stride(0), C.byref(count), C.byref(first),
+                                             xh.ctypes.data_as(C.c_void_p), yh.ctypes.data_as(C.c_void_p), cm.ctypes.data_as(C.c_void_p)))
+    st, n = (C.c_int * 4)(), C.c_int()
+    ctx.check(ctx.lib.mis_crop_stats(ctx.h, st, 4, C.byref(n)))
+    return dict(count=count.value, first=first.value, xhist=xh, yhist=yh, cmask=cm, launches=st[0], rounds=st[1], border_pixels=st[2])
+
+
+def crop_copy_device(ctx, source):
+    """crop(source) with the dense copy made on the device (mis_crop) -> (a new contiguous tensor, (x, y, w, h)), for callers that
+    cannot use crop_device's strided view."""
+    import ctypes as C
+    import torch
+    src, cn = _device_source(source)
+    h, w = src.shape[:2]
+    dst = torch.empty((h, w * cn), dtype=torch.uint8, device=src.device)
+    rect, status = (C.c_int * 4)(), C.c_int()
+    ctx.check(ctx.lib.mis_crop(ctx.h, C.c_void_p(src.data_ptr()), w, h, cn, src.stride(0), C.c_void_p(dst.data_ptr()), dst.stride(0), rect, C.byref(status)))
+    if status.value:
+        raise ValueError(_STATUS_TEXT[status.value])
+    x, y, rw, rh = rect
+    out = dst[:rh, :rw * cn]
+    return (out.reshape(rh, rw, 3) if cn == 3 else out).contiguous(), (x, y, rw, rh)

@@ -40,6 +40,8 @@ struct MisContext {
     // the last mis_seam_graphcut call's counts (seam_gc.hip): pairs, levels, grid nodes, the round-set cap, global relabels, relabel
     // sweeps, then the round sets of every level
     std::vector<int> gc_stats;
+    // the last device crop's counts (crop.hip): kernel launches, doubling rounds, border pixels, the chosen contour's points
+    std::vector<int> crop_stats;
 };
 
 int mis_set_error(MisContext* ctx, int code, const char* fmt, ...);

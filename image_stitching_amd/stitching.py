@@ -27,6 +27,7 @@ from .seams import (EXPOS_COMP_TYPES, SEAM_FIND_TYPES, BlocksChannelsCompensator
 from .blenders import Blender, FeatherBlender, MultiBandBlender, blend_config, make_blender, result_roi
 from .timelapse import (TIMELAPSE_TYPES, Timelapser, check_timelapse_config, result_roi_intersection, timelapse_kind, timelapse_warp_batch,
                         timelapse_warp_batch_timed)
+from .cropper import crop_device, crop_rect_device
 from .features import KP_DTYPE, ImageFeatures, OrbFeatureFinder, SiftFeatureFinder, computeImageFeatures, features_array, orb_params
 from .matchers import (DMATCH_DTYPE, MATCHER_TYPES, AffineBestOf2NearestMatcher, BestOf2NearestMatcher, BestOf2NearestRangeMatcher,
                        MatchesInfo, PairwiseMatches, _require_matches, _unpack_mi, check_matcher_config, check_range_config,
@@ -324,6 +325,12 @@ class Stitcher:
                 apply_seam(self.ctx, seam, k, corners[k], img_s, mask)
             blender.feed(img_s, mask, tl)
         return blender.blend()
+
+    def crop_panorama(self, pano, mask):
+        """The reference's cropper (cropper.cpp:124-209) on the blender's result: the rectangle crop() finds on the result mask,
+        computed on the device -> (pano[y:y + h, x:x + w], mask[y:y + h, x:x + w], (x, y, w, h)), views without a copy."""
+        x, y, w, h = crop_rect_device(self.ctx, mask)
+        return pano[y:y + h, x:x + w], mask[y:y + h, x:x + w], (x, y, w, h)
 
     def render_view(self, pano_u8, K, R, size, interp=capi.INTER_LINEAR, border=capi.BORDER_CONSTANT, with_mask=False):
         """A pinhole view (K, R; size = (w, h)) rendered out of the last composition's panorama, given as 8UC3 (the caller converts

@@ -750,6 +750,43 @@ int mis_jpeg_debug_entropy_encode(const int16_t* const coef[3], int w, int h, co
 int mis_jpeg_debug_encode_coefficients(MisContext* ctx, const MisImage* src_bgr, const MisJpegEncodeParams* params, int component,
                                        int16_t* out, size_t capacity, uint16_t qtable[64]);
 
+/* ---------------------------------------------------------------- cropper -------------------- */
+/* crop(cv::Mat& source) -- replaces image_stitching/cropper.cpp:124-209 (API in cropper.h) on the device: the rectangle the host
+ * cropper (host/cropper.cpp, image_stitching_amd/cropper.py) finds, bit for bit, without the image leaving the device.  The steps
+ * of :128-158 (grey > 0 with the integer grey formula, findContours RETR_EXTERNAL + CHAIN_APPROX_NONE, the first contour of maximal
+ * point count, drawContours FILLED, the contour's coordinates sorted by x and by y) and the shrink loop of :160-200 with
+ * checkInteriorExterior (:6-112) all run as kernels; one count and the result block cross to the host.
+ * src: 8UC1 or 8UC3 (BGR) in DEVICE memory, `row_stride` bytes a row (any value >= width * channels: a view into a larger image
+ * works).  rect_out = (x, y, width, height); *status_out = 0 ok, 1 "the image is empty" (no foreground: cropper.cpp would fail on
+ * contours[0]), 2 "no interior rectangle found" (the lists crossed on an empty rectangle); with 1 and 2 the rectangle is all zero
+ * or empty and the call itself succeeds.  MIS_E_INVALID: a null pointer, a size <= 0, channels not 1 or 3, a stride below a row,
+ * (width + 2) * (height + 2) >= 2^28 (the cropper's 32-bit state indices).  Other approximation modes than CHAIN_APPROX_NONE and
+ * contour hierarchies are not built. */
+int mis_crop_rect(MisContext* ctx, const void* src, int width, int height, int channels, size_t row_stride, int rect_out[4], int* status_out);
+/* measurement aid (tools/crop_device_bench.py; cropper.cpp:124-209): the same call with events between its stages on the context's
+ * stream.  ms[0] the mask, ms[1] the foreground labelling, ms[2] the background labelling, ms[3] the border slots and the read of
+ * their count, ms[4] successor table and start states, ms[5] the doubling rounds, ms[6] counts, winner and walls, ms[7] the fill's
+ * labelling, ms[8] the two prefix counts, ms[9] the shrink loop. */
+enum { MIS_CROP_STAGES = 10 };
+int mis_crop_rect_timed(MisContext* ctx, const void* src, int width, int height, int channels, size_t row_stride, int rect_out[4], int* status_out,
+                        float ms[MIS_CROP_STAGES]);
+/* the same (cropper.cpp:124-209) and source(croppingMask).copyTo(dst) (:202-207): the rectangle's pixels packed from dst's first
+ * byte on, `dst_stride` bytes a row.  dst: DEVICE memory of the source's size (height rows of dst_stride >= width * channels bytes:
+ * the rectangle is known on the device only when the copy is enqueued).  Nothing is copied unless the status is 0.  A caller that
+ * can use a strided view of src needs no copy: mis_crop_rect. */
+int mis_crop(MisContext* ctx, const void* src, int width, int height, int channels, size_t row_stride, void* dst, size_t dst_stride, int rect_out[4],
+             int* status_out);
+/* test hook for the stages of cropper.cpp:132-158: the chosen contour's point count and first pixel in raster order (y * width + x;
+ * 0 and -1 without a contour), the histograms of its points' x (width entries) and y (height entries) with multiplicity -- the
+ * sorted lists of :150-158 in counted form -- and the filled contour mask of :146-148 (width * height bytes, 0 / 255), all to HOST
+ * memory. */
+int mis_crop_debug_contour(MisContext* ctx, const void* src, int width, int height, int channels, size_t row_stride, int* count_out, int* first_out,
+                           int32_t* xhist, int32_t* yhist, uint8_t* cmask_out);
+/* the last crop call's counts (cropper.cpp:124-209 takes one pass; this takes launches): kernel launches, pointer-doubling rounds
+ * (ceil(log2(8 * border pixels))), border pixels, the chosen contour's points.  *count = how many there are; at most `capacity`
+ * are written. */
+int mis_crop_stats(const MisContext* ctx, int* out, int capacity, int* count);
+
 #ifdef __cplusplus
 }
 #endif
