@@ -43,7 +43,7 @@
 
 int main(int argc, char** argv) {
     if (argc < 2) {
-        std::cout << "usage: " << argv[0] << " <image directory> [--features orb|sift] [--ba no|reproj|ray] [--ba_refine_mask xxxxx] [--wave_correct horiz|vert|no]\n"
+        std::cout << "usage: " << argv[0] << " <image directory> [--features orb|akaze|sift] [--ba no|reproj|ray] [--ba_refine_mask xxxxx] [--wave_correct horiz|vert|no]\n"
                      "       [--expos_comp no|gain|gain_blocks|channels|channels_blocks] [--expos_comp_nr_feeds N] [--seam no|voronoi|dp_color|dp_colorgrad] [--warp spherical|cylindrical|plane|fisheye|stereographic|compressedPlaneA2B1|compressedPlaneA1.5B1|paniniA2B1|paniniA1.5B1] [--blend no|feather|multiband] [--conf_thresh f] [--match_conf f] [--compose_megapix f] [--seam_megapix f] [--work_megapix f] [--rangewidth N] [--matcher homography|affine] [--mode panorama|scans] [--estimator supplied|homography] [--timelapse [as_is|crop]] [--crop] [--view yaw,pitch,hfov,width,height] [--jpeg [quality]]\n"
                      "(the reference sets these as globals, image_stitching.cpp:49-85)\n";
         return -1;
@@ -113,7 +113,7 @@ int main(int argc, char** argv) {
     if (cfg.timelapse && write_view) { std::cout << "--timelapse with --view: the timelapse output writes no panorama (image_stitching.cpp:1222), there is nothing to view\n"; return -1; }
     if (cfg.timelapse && write_jpeg) { std::cout << "--timelapse with --jpeg: the timelapse output writes no panorama (image_stitching.cpp:1222); fixed_<k>.jpg are always JPEG files\n"; return -1; }
     if (cfg.timelapse && crop_result) { std::cout << "--timelapse with --crop: the timelapse output writes no panorama (image_stitching.cpp:1222), there is nothing to crop; --timelapse crop cuts the frames to their intersection\n"; return -1; }
-    try { if (!mis::mode_is_scans(cfg.mode)) mis::estimator_is_homography(cfg.estimator_type); mis::check_range_width(cfg.range_width); mis::matcher_model(cfg.matcher_type, cfg.range_width); mis::expos_comp_kind(cfg.expos_comp_type, cfg.expos_comp_nr_feeds); } catch (const std::exception& e) { std::cout << e.what() << "\n"; return -1; }
+    try { mis::check_features_type(cfg.features_type); if (!mis::mode_is_scans(cfg.mode)) mis::estimator_is_homography(cfg.estimator_type); mis::check_range_width(cfg.range_width); mis::matcher_model(cfg.matcher_type, cfg.range_width); mis::expos_comp_kind(cfg.expos_comp_type, cfg.expos_comp_nr_feeds); } catch (const std::exception& e) { std::cout << e.what() << "\n"; return -1; }
     namespace fs = std::filesystem;
     std::vector<std::string> img_names, jpg_names;
     for (auto& e : fs::directory_iterator(argv[1])) {

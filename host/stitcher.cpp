@@ -159,7 +159,7 @@ StitchResult Stitcher::run(const std::vector<HostImage>& frames, const std::vect
     const WorkGeometry wg = work_geometry(cfg_, W, H);
     const double work_scale = wg.scale;
     double t = now();
-    if (cfg_.features_type != "orb" && cfg_.features_type != "sift") throw std::runtime_error("Unknown 2D features type: '" + cfg_.features_type + "'.");
+    check_features_type(cfg_.features_type);
     if (cfg_.ba_cost_func != "no" && cfg_.ba_cost_func != "reproj" && cfg_.ba_cost_func != "ray")
         throw std::runtime_error("bundle adjustment cost function '" + cfg_.ba_cost_func + "' is not implemented ('no', 'reproj' and 'ray' are)");
     const int expos_kind = expos_comp_kind(cfg_.expos_comp_type, cfg_.expos_comp_nr_feeds);
@@ -171,6 +171,7 @@ StitchResult Stitcher::run(const std::vector<HostImage>& frames, const std::vect
     const int model = matcher_model(cfg_.matcher_type, cfg_.range_width);
     MisOrb* orb = nullptr;
     MisSift* sift = nullptr;
+    MisAkaze* akaze = nullptr;
     std::vector<MisFeatures> features(n);
     std::vector<MisImage> views(n);
     for (int i = 0; i < n; i++) views[i] = view(frames[i]);
@@ -180,6 +181,9 @@ StitchResult Stitcher::run(const std::vector<HostImage>& frames, const std::vect
     if (cfg_.features_type == "sift") {
         check(mis_sift_create(ctx_, nullptr, wg.width, wg.height, &sift), "mis_sift_create");
         check(mis_sift_detect_batch(sift, imgs, n, features.data()), "mis_sift_detect_batch");
+    } else if (cfg_.features_type == "akaze") {      // AKAZE::create() (:547-550): 61-byte descriptors, the wide Hamming 2-NN
+        check(mis_akaze_create(ctx_, nullptr, wg.width, wg.height, &akaze), "mis_akaze_create");
+        check(mis_akaze_detect_batch(akaze, imgs, n, features.data()), "mis_akaze_detect_batch");
     } else {
         MisOrbParams op;
         mis_orb_default_params(&op);
@@ -255,6 +259,7 @@ StitchResult Stitcher::run(const std::vector<HostImage>& frames, const std::vect
     for (auto& f : features) mis_features_free(ctx_, &f);
     if (orb) mis_orb_destroy(orb);
     if (sift) mis_sift_destroy(sift);
+    if (akaze) mis_akaze_destroy(akaze);
     out.t_matching = now() - t;
     if (kept < 2) throw std::runtime_error("Need more images");
     out.cameras.clear();

@@ -22,7 +22,7 @@ struct StitchConfig {
     float match_conf = 0.32f;
     int blend_type = MIS_BLEND_MULTI_BAND;
     float blend_strength = 5;
-    std::string features_type = "orb";     // "orb" | "sift" (:543-563)
+    std::string features_type = "orb";     // "orb" | "akaze" | "sift" (:543-563)
     // camera refinement (:681-726).  The reference's default is "reproj"; "no" keeps the supplied (sensor) cameras.
     std::string ba_cost_func = "no";       // "no" | "reproj" | "ray"
     std::string ba_refine_mask = "_____";  // the reference's default: rotations only
@@ -104,6 +104,11 @@ inline MisMatchParams match_params(int model, float match_conf) {
     return mp;
 }
 
+// features_type of the config (image_stitching.cpp:543-565): the finders this library builds, refused in the reference's words otherwise
+inline const std::string& check_features_type(const std::string& t) {
+    if (t != "orb" && t != "sift" && t != "akaze") throw std::runtime_error("Unknown 2D features type: '" + t + "'.");
+    return t;
+}
 // range_width of the config: -1 or >= 1 (mis_match_pairs_select refuses the rest too; this is the check before any device work)
 inline int check_range_width(int w) {
     if (w != -1 && w < 1) throw std::runtime_error("range_width " + std::to_string(w) + ": -1 (match all pairs) or a width >= 1");

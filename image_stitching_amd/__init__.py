@@ -12,7 +12,7 @@ from ._capi import (BLEND_FEATHER, BLEND_MULTI_BAND, BLEND_NO, BORDER_CONSTANT, 
                     INTER_NEAREST, WARP_CYLINDRICAL, WARP_FISHEYE, WARP_MERCATOR, WARP_PLANE, WARP_SPHERICAL, WARP_STEREOGRAPHIC,
                     WARP_COMPRESSED_PLANE_A2B1, WARP_COMPRESSED_PLANE_A15B1, WARP_PANINI_A2B1, WARP_PANINI_A15B1, WARP_AFFINE)
 from .stitching import (AffineBestOf2NearestMatcher, BestOf2NearestMatcher, BestOf2NearestRangeMatcher, estimate_affine_partial, Blender, BlocksGainCompensator, GainCompensator, ChannelsCompensator, BlocksChannelsCompensator, NoSeamFinder, VoronoiSeamFinder, DpSeamFinder, GraphCutSeamFinder, Context, FeatherBlender, ImageFeatures, MatchesInfo,
-                        MisError, MultiBandBlender, OrbFeatureFinder, SiftFeatureFinder, SphericalWarper, CylindricalWarper, PlaneWarper, MercatorWarper, FisheyeWarper, StereographicWarper, CompressedRectilinearWarper, PaniniWarper, AffineWarper,
+                        MisError, MultiBandBlender, OrbFeatureFinder, SiftFeatureFinder, AkazeFeatureFinder, SphericalWarper, CylindricalWarper, PlaneWarper, MercatorWarper, FisheyeWarper, StereographicWarper, CompressedRectilinearWarper, PaniniWarper, AffineWarper,
                         RotationWarper, StitchConfig, Stitcher,
                         blend_config, bundle_adjust_affine_partial, bundle_adjust_ray, bundle_adjust_reproj, estimate_affine_cameras, estimate_focal, estimate_homography_cameras, focals_from_homography, computeImageFeatures, find_homography, leaveBiggestComponent, resize, resize_batch, result_roi,
                         rotate, seam_gradients, seam_mask_apply, selected_pairs, warp_roi, wave_correct, work_geometry, imread, imread_batch, jpeg_info, imencode, imencode_batch, imwrite, jpeg_encode_params,
@@ -31,5 +31,5 @@ __all__ = [
     "focals_from_homography", "estimate_focal", "estimate_homography_cameras",
     "imread", "imread_batch", "jpeg_info", "imencode", "imencode_batch", "imwrite", "jpeg_encode_params",
 ]
-# Timelapser, result_roi_intersection, timelapse_warp_batch, crop_device and crop_rect_device are names of the package too; __all__ stays the list that
+# AkazeFeatureFinder, Timelapser, result_roi_intersection, timelapse_warp_batch, crop_device and crop_rect_device are names of the package too; __all__ stays the list that
 # tests/golden/package_all.txt records

@@ -83,6 +83,11 @@ class MisSiftParams(C.Structure):
                 ("edge_threshold", C.c_double), ("sigma", C.c_double)]
 
 
+class MisAkazeParams(C.Structure):
+    _fields_ = [("threshold", C.c_float), ("n_octaves", C.c_int), ("n_octave_layers", C.c_int), ("max_points", C.c_int),
+                ("descriptor_type", C.c_int), ("descriptor_size", C.c_int), ("descriptor_channels", C.c_int), ("diffusivity", C.c_int)]
+
+
 class MisCameraParams(C.Structure):
     _fields_ = [("focal", C.c_double), ("aspect", C.c_double), ("ppx", C.c_double), ("ppy", C.c_double), ("R", C.c_double * 9),
                 ("t", C.c_double * 3)]
@@ -161,6 +166,15 @@ PROTOTYPES = {
     "mis_sift_detect_batch": (_i, [_vp, _P(MisImage), _i, _P(MisFeatures)]),
     "mis_sift_debug_level": (_i, [_vp, _P(MisImage), _i, _i, _i, _vp, _P(_i), _P(_i)]),
     "mis_sift_debug_counts": (_i, [_vp, _P(C.c_uint)]),
+    "mis_akaze_default_params": (None, [_P(MisAkazeParams)]),
+    "mis_akaze_create": (_i, [_vp, _P(MisAkazeParams), _i, _i, _P(_vp)]),
+    "mis_akaze_destroy": (_i, [_vp]),
+    "mis_akaze_detect": (_i, [_vp, _P(MisImage), _P(MisFeatures)]),
+    "mis_akaze_detect_batch": (_i, [_vp, _P(MisImage), _i, _P(MisFeatures)]),
+    "mis_akaze_debug_level": (_i, [_vp, _i, _i, _vp, _P(_i), _P(_i)]),
+    "mis_akaze_debug_counts": (_i, [_vp, _P(C.c_uint)]),
+    "mis_akaze_debug_class_ids": (_i, [_vp, _P(_i), _i]),
+    "mis_akaze_debug_fed": (_i, [_vp, _i, _P(C.c_float), _P(_i)]),
     "mis_match_default_params": (None, [_P(MisMatchParams)]),
     "mis_match_all_pairs": (_i, [_vp, _P(MisFeatures), _i, _P(MisMatchParams), _P(MisMatchesInfo)]),
     "mis_match_pairs_sharded": (_i, [_vp, _P(MisFeatures), _i, _P(MisMatchParams), _i, _i, _P(MisMatchesInfo)]),

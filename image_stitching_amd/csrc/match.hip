@@ -85,6 +85,62 @@ __global__ __launch_bounds__(256) void knn2_hamming_kernel(const FeatDev* feats,
     }
 }
 
+// ---------------------------------------------------------------- K7 for 61-byte rows (AKAZE's MLDB, 486 bits) --
+// The same search over rows of HMW_BYTES bytes: a row is read as 16 dwords whose last three bytes are zero-filled while it is
+// assembled -- byte loads, none past the row's 61 bytes (rows are not dword aligned: 61 is odd) -- the query into registers, a tile
+// of trains into LDS.  Distances are at most 486 < 2^9, so the key (distance << 22 | train index) keeps its form and its
+// (distance, index) order.  An MFMA form over 512 padded bits is not built.
+constexpr int HMW_BYTES = 61, HMW_DWORDS = 16, HMW_TILE = 128;
+__device__ __forceinline__ unsigned hmw_dword(const uint8_t* row, int d) {
+    unsigned v = 0;
+#pragma unroll
+    for (int b = 0; b < 4; b++)
+        if (4 * d + b < HMW_BYTES) v |= (unsigned)row[4 * d + b] << (8 * b);
+    return v;
+}
+__global__ __launch_bounds__(256) void knn2_hamming_wide_kernel(const FeatDev* feats, const PairDesc* pairs, int* idx2, float* dist2) {
+    __shared__ uint4 tr[HMW_TILE * 4];
+    const PairDesc pd = pairs[blockIdx.y >> 1];
+    const bool fwd = (blockIdx.y & 1) == 0;
+    const FeatDev Q = feats[fwd ? pd.i : pd.j], T = feats[fwd ? pd.j : pd.i];
+    const size_t off = fwd ? pd.knn_off12 : pd.knn_off21;
+    const int q0 = blockIdx.x * 256;
+    if (q0 >= Q.n) return;
+    const int q = q0 + threadIdx.x;
+    const bool active = q < Q.n;
+    unsigned a[HMW_DWORDS];
+#pragma unroll
+    for (int d = 0; d < HMW_DWORDS; d++) a[d] = active ? hmw_dword(Q.desc + (size_t)q * HMW_BYTES, d) : 0u;
+    int k0 = 0x7fffffff, k1 = 0x7fffffff;
+    unsigned* trw = reinterpret_cast<unsigned*>(tr);
+    for (int t0 = 0; t0 < T.n; t0 += HMW_TILE) {
+        const int nt = min(HMW_TILE, T.n - t0);
+        __syncthreads();
+        for (int k = threadIdx.x; k < nt * HMW_DWORDS; k += 256)
+            trw[k] = hmw_dword(T.desc + (size_t)(t0 + (k >> 4)) * HMW_BYTES, k & 15);
+        __syncthreads();
+        if (active) {
+            for (int j = 0; j < nt; j++) {
+                unsigned d = 0;
+#pragma unroll
+                for (int v = 0; v < 4; v++) {
+                    const uint4 b = tr[4 * j + v];
+                    d += __popc(a[4 * v] ^ b.x) + __popc(a[4 * v + 1] ^ b.y) + __popc(a[4 * v + 2] ^ b.z) + __popc(a[4 * v + 3] ^ b.w);
+                }
+                const int key = (int)((d << 22) | (unsigned)(t0 + j));
+                // k0 <= k1 always: the new second best is the median of (k0, k1, key), the new best the minimum
+                k1 = max(min(k0, k1), min(max(k0, k1), key));
+                k0 = min(k0, key);
+            }
+        }
+    }
+    if (active) {
+        const int d0 = k0 == 0x7fffffff ? 1 << 30 : k0 >> 22, d1 = k1 == 0x7fffffff ? 1 << 30 : k1 >> 22;
+        idx2[(off + q) * 2] = k0 == 0x7fffffff ? -1 : (k0 & 0x3fffff); idx2[(off + q) * 2 + 1] = k1 == 0x7fffffff ? -1 : (k1 & 0x3fffff);
+        dist2[(off + q) * 2] = (float)d0; dist2[(off + q) * 2 + 1] = (float)d1;
+    }
+}
+
 // ---------------------------------------------------------------- K7 on the matrix cores --------
 // Hamming-256 as an exact dense product on the matrix cores (north star: "MFMA only if descriptor distance is cast as a dense
 // GEMM").  Every descriptor bit becomes a signed element -- +v where a train bit is set, -v where it is clear, the opposite signs
@@ -832,7 +888,7 @@ int l2_knn2_pairs(MisContext* ctx, Arena& arena, const MisFeatures* f, int nsets
     return MIS_OK;
 }
 
-enum DescKind { DESC_NONE, DESC_BINARY, DESC_L2 };
+enum DescKind { DESC_NONE, DESC_BINARY, DESC_L2, DESC_WIDE };   // DESC_WIDE: 61-byte binary rows (knn2_hamming_wide_kernel)
 // What a matcher call does, decided on the host before anything is enqueued.  FeaturesMatcher::operator(): all i < j with
 // non-empty keypoint lists that the mask (strict upper triangle, NULL: all) and BestOf2NearestRangeMatcher's range_width
 // (-1: all, else j < i + range_width) select, dealt round-robin over ranks.
@@ -847,14 +903,15 @@ struct MatchPlan {
 int plan_match(MisContext* ctx, const MisFeatures* feats, int n, const uint8_t* mask, int range_width, int rank, int world, MatchPlan* pl) {
     std::vector<PairDesc>& pairs = pl->pairs;
     pl->fd.resize(n);
-    bool use_l2 = false, use_bin = false;
+    bool use_l2 = false, use_bin = false, use_wide = false;
     for (int i = 0; i < n; i++) {
+        const bool wide_i = feats[i].desc_dtype == MIS_U8 && feats[i].desc_cols == HMW_BYTES;
         const bool bin_i = feats[i].desc_dtype == MIS_U8 && feats[i].desc_cols == 32;
         const bool l2_i = feats[i].desc_dtype == MIS_F32 && feats[i].desc_cols >= 1 && feats[i].desc_cols <= 128;
-        MIS_CHECK(ctx, feats[i].n == 0 || bin_i || l2_i, MIS_E_UNSUPPORTED,
-                  "all-pairs matching supports 32-byte binary descriptors (Hamming) or f32 descriptors of <= 128 columns (L2)");
+        MIS_CHECK(ctx, feats[i].n == 0 || bin_i || l2_i || wide_i, MIS_E_UNSUPPORTED,
+                  "all-pairs matching supports 32-byte or 61-byte binary descriptors (Hamming) or f32 descriptors of <= 128 columns (L2)");
         MIS_CHECK(ctx, feats[i].n < (1 << 22), MIS_E_UNSUPPORTED, "more than 4 M keypoints in one image");   // index bits of the 2-NN keys
-        if (feats[i].n > 0) { if (l2_i) use_l2 = true; else use_bin = true; }
+        if (feats[i].n > 0) { if (l2_i) use_l2 = true; else if (wide_i) use_wide = true; else use_bin = true; }
         pl->fd[i] = FeatDev{(const uint8_t*)feats[i].descriptors, feats[i].keypoints, feats[i].n, feats[i].img_w, feats[i].img_h};
     }
     int pair_index = 0;
@@ -868,7 +925,8 @@ int plan_match(MisContext* ctx, const MisFeatures* feats, int n, const uint8_t* 
             pairs.push_back(PairDesc{i, j, pl->knn_total, pl->knn_total + feats[i].n, pl->m_total, cap});
             pl->knn_total += cap; pl->m_total += cap;
         }
-    MIS_CHECK(ctx, !(use_l2 && use_bin), MIS_E_INVALID, "binary and float descriptors cannot be mixed in one matcher call");
+    MIS_CHECK(ctx, !(use_l2 && (use_bin || use_wide)), MIS_E_INVALID, "binary and float descriptors cannot be mixed in one matcher call");
+    MIS_CHECK(ctx, !(use_bin && use_wide), MIS_E_INVALID, "binary descriptors of 32 and of 61 bytes in one matcher call");
     // l2_prep_kernel zero-pads every frame to 128 columns: frames of different widths would be compared silently
     // (cv::BFMatcher asserts on it, and mis_knn2 refuses it)
     for (int i = 0, cols = 0; use_l2 && i < n; i++)
@@ -876,7 +934,7 @@ int plan_match(MisContext* ctx, const MisFeatures* feats, int n, const uint8_t* 
             MIS_CHECK(ctx, cols == 0 || feats[i].desc_cols == cols, MIS_E_INVALID, "float descriptors of different widths in one matcher call");
             cols = feats[i].desc_cols;
         }
-    pl->kind = use_l2 ? DESC_L2 : (use_bin ? DESC_BINARY : DESC_NONE);
+    pl->kind = use_l2 ? DESC_L2 : (use_wide ? DESC_WIDE : (use_bin ? DESC_BINARY : DESC_NONE));
     const int np = (int)pairs.size();
     if (np == 0) return MIS_OK;
     // workgroup table of the Hamming pass on the matrix cores (HmJob): eight lists by train frame mod 8, interleaved
@@ -933,6 +991,10 @@ int enqueue_knn(MisContext* ctx, MatchWorkspace* ws, const MatchPlan& pl, const 
     hipStream_t st = ctx->stream;
     const int n = (int)pl.fd.size(), np = (int)pl.pairs.size();
     if (pl.kind == DESC_L2) return l2_knn2_pairs(ctx, ws->l2, feats, n, pl.pairs.data(), np, true, d.idx, d.dist, (int*)h.l2_bad);
+    if (pl.kind == DESC_WIDE) {
+        hipLaunchKernelGGL(knn2_hamming_wide_kernel, dim3((pl.maxq + 255) / 256, 2 * np), dim3(256), 0, st, (const FeatDev*)d.feats, (const PairDesc*)d.pairs, d.idx, d.dist);
+        return MIS_OK;
+    }
     if (pl.maxq > HM_MAX_TRAINS) {
         hipLaunchKernelGGL(knn2_hamming_kernel, dim3((pl.maxq + 255) / 256, 2 * np), dim3(256), 0, st, (const FeatDev*)d.feats, (const PairDesc*)d.pairs, d.idx, d.dist);
         return MIS_OK;
@@ -1463,7 +1525,11 @@ extern "C" int mis_knn2(MisContext* ctx, const MisFeatures* q, const MisFeatures
     MIS_CHECK(ctx, q && t && idx2 && dist2, MIS_E_INVALID, "null argument");
     const bool binary = q->desc_dtype == MIS_U8 && q->desc_cols == 32 && t->desc_dtype == MIS_U8 && t->desc_cols == 32;
     const bool l2 = q->desc_dtype == MIS_F32 && t->desc_dtype == MIS_F32 && q->desc_cols == t->desc_cols && q->desc_cols >= 1 && q->desc_cols <= 128;
-    MIS_CHECK(ctx, binary || l2, MIS_E_UNSUPPORTED, "mis_knn2 supports 32-byte binary descriptors (Hamming) and f32 descriptors of <= 128 columns (L2)");
+    const bool u8_both = q->desc_dtype == MIS_U8 && t->desc_dtype == MIS_U8;
+    const bool wide = u8_both && q->desc_cols == HMW_BYTES && t->desc_cols == HMW_BYTES;
+    MIS_CHECK(ctx, !(u8_both && q->desc_cols != t->desc_cols && (q->desc_cols == 32 || q->desc_cols == HMW_BYTES) && (t->desc_cols == 32 || t->desc_cols == HMW_BYTES)),
+              MIS_E_INVALID, "binary descriptors of 32 and of 61 bytes in one call");
+    MIS_CHECK(ctx, binary || l2 || wide, MIS_E_UNSUPPORTED, "mis_knn2 supports 32-byte and 61-byte binary descriptors (Hamming) and f32 descriptors of <= 128 columns (L2)");
     if (q->n <= 0) return MIS_OK;
     MIS_HIP(ctx, hipSetDevice(ctx->device));
     MatchWorkspace* ws = workspace(ctx);
@@ -1476,14 +1542,18 @@ extern "C" int mis_knn2(MisContext* ctx, const MisFeatures* q, const MisFeatures
     uint8_t* D = (uint8_t*)ws->dev.p;
     const PairDesc pd{0, 1, 0, nq, 0, q->n + t->n};
     int bad = 0;
-    if (binary) {
+    if (binary || wide) {
         FeatDev fd[2] = {{(const uint8_t*)q->descriptors, q->keypoints, q->n, q->img_w, q->img_h},
                          {(const uint8_t*)t->descriptors, t->keypoints, t->n, t->img_w, t->img_h}};
         MIS_HIP(ctx, hipMemcpyAsync(D + o_feats, fd, sizeof(fd), hipMemcpyHostToDevice, st));
         MIS_HIP(ctx, hipMemcpyAsync(D + o_pairs, &pd, sizeof(pd), hipMemcpyHostToDevice, st));
         MIS_HIP(ctx, hipStreamSynchronize(st));  // fd / pd live on this stack frame
-        hipLaunchKernelGGL(knn2_hamming_kernel, dim3((q->n + 255) / 256, 1), dim3(256), 0, st, (const FeatDev*)(D + o_feats), (const PairDesc*)(D + o_pairs),
-                           (int*)(D + o_idx), (float*)(D + o_dist));
+        if (wide)
+            hipLaunchKernelGGL(knn2_hamming_wide_kernel, dim3((q->n + 255) / 256, 1), dim3(256), 0, st, (const FeatDev*)(D + o_feats), (const PairDesc*)(D + o_pairs),
+                               (int*)(D + o_idx), (float*)(D + o_dist));
+        else
+            hipLaunchKernelGGL(knn2_hamming_kernel, dim3((q->n + 255) / 256, 1), dim3(256), 0, st, (const FeatDev*)(D + o_feats), (const PairDesc*)(D + o_pairs),
+                               (int*)(D + o_idx), (float*)(D + o_dist));
     } else {
         const MisFeatures qt[2] = {*q, *t};
         if (int rc = l2_knn2_pairs(ctx, ws->l2, qt, 2, &pd, 1, false, (int*)(D + o_idx), (float*)(D + o_dist), &bad); rc != MIS_OK) return rc;

@@ -163,7 +163,10 @@ class HipEngine:
         self.work_scale, self.work_size = st.work_geometry(self.cfg, frame_size)
         self._work_frames = []
         # finder per features_type (image_stitching.cpp:543-563): ORB, or SIFT (float descriptors -> the L2 matcher)
-        self.finder = st.SiftFeatureFinder(ctx, self.work_size) if self.cfg.features_type == "sift" else st.OrbFeatureFinder(ctx, self.work_size)
+        if self.cfg.features_type == "akaze":      # (:547-550; 61-byte binary descriptors -> the wide Hamming 2-NN)
+            self.finder = st.AkazeFeatureFinder(ctx, self.work_size)
+        else:
+            self.finder = st.SiftFeatureFinder(ctx, self.work_size) if self.cfg.features_type == "sift" else st.OrbFeatureFinder(ctx, self.work_size)
         self.matcher = st.make_matcher(ctx, self.cfg)
         self.blender = self._blend = None      # begin_compose
         self._keep = []
@@ -209,7 +212,7 @@ class HipEngine:
         return kps, desc
 
     def _row_bytes(self, feats=None):
-        return 512 if self.cfg.features_type == "sift" else 32
+        return {"sift": 512, "akaze": 61}.get(self.cfg.features_type, 32)
 
     def unpack_features(self, kps_all, desc_all, counts_all):
         """Gathered tensors [n, ...] -> ImageFeatures views (no copies; tensors kept alive)."""
@@ -223,7 +226,7 @@ class HipEngine:
             raw.img_idx, raw.img_w, raw.img_h, raw.n = i, w, h, int(n)
             raw.keypoints = kps_all[i].data_ptr()
             raw.descriptors = desc_all[i].data_ptr()
-            raw.desc_cols, raw.desc_dtype, raw.owner_ = (128, capi.F32, None) if sift else (32, capi.U8, None)
+            raw.desc_cols, raw.desc_dtype, raw.owner_ = (128, capi.F32, None) if sift else (61 if self.cfg.features_type == "akaze" else 32, capi.U8, None)
             out.append(st.ImageFeatures(self.ctx, raw))
         return out
 
@@ -483,6 +486,8 @@ class StitchJob:
         self.work_cams0 = cameras if self.work_scale == 1.0 else [st.scaled_camera(c, self.work_scale) for c in cameras]
         self.cams = self.work_cams0   # work units; holds the refined cameras after a run with bundle adjustment
         self.n = len(cameras)
+        if self.cfg.features_type == "akaze" and world_size > 1:
+            raise NotImplementedError("features_type 'akaze' with world_size %d: the AKAZE job is built for a single rank" % world_size)
         self.rank, self.world = rank, world_size
         self.comm = Comm(rank, world_size, group, always_collective)
         self.my_frames = frame_block(self.n, rank, world_size)

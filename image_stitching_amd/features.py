@@ -1,4 +1,4 @@
-"""features: ORB::create / SIFT::create + computeImageFeatures (image_stitching.cpp:545, :559, :613)."""
+"""features: ORB::create / AKAZE::create / SIFT::create + computeImageFeatures (image_stitching.cpp:545, :547-550, :559, :613)."""
 import ctypes as C
 
 import numpy as np
@@ -198,6 +198,74 @@ class SiftFeatureFinder(Handle):
         c = (C.c_uint * 4)()
         self.ctx.check(self.ctx.lib.mis_sift_debug_counts(self.h, c))
         return dict(candidates=int(c[0]), raw=int(c[1]), keypoints=int(c[2]), refined=int(c[3]))
+
+
+class AkazeFeatureFinder(Handle):
+    """AKAZE::create() (image_stitching.cpp:547-550, features_type == "akaze"): same detect() interface as the other finders;
+    descriptors are n x 61 u8 (MLDB, 486 bits; the wide Hamming 2-NN consumes them), keypoints in (level, y, x) order.  params: a
+    dict of MisAkazeParams fields (threshold, n_octaves, n_octave_layers, max_points, ...)."""
+    DESTROY = "mis_akaze_destroy"
+    PLANES = dict(Lt=0, Lsmooth=1, flow=2, Lx=3, Ly=4, Ldet=5)
+
+    def __init__(self, ctx, max_size, params=None):
+        self.ctx = ctx
+        p = capi.MisAkazeParams()
+        ctx.lib.mis_akaze_default_params(C.byref(p))
+        for k, v in (params or {}).items():
+            setattr(p, k, v)
+        self.params = p
+        h = C.c_void_p()
+        ctx.check(ctx.lib.mis_akaze_create(ctx.h, C.byref(p), int(max_size[0]), int(max_size[1]), C.byref(h)))
+        self.h = h
+
+    def detect(self, img):
+        raw = capi.MisFeatures()
+        i = as_image(img)
+        self.ctx.check(self.ctx.lib.mis_akaze_detect(self.h, C.byref(i), C.byref(raw)))
+        return ImageFeatures(self.ctx, raw)
+
+    def detect_batch(self, imgs):
+        n = len(imgs)
+        if n == 0:
+            return []
+        arr = _images(imgs)
+        raws = (capi.MisFeatures * n)()
+        self.ctx.check(self.ctx.lib.mis_akaze_detect_batch(self.h, arr, n, raws))
+        out = []
+        for k in range(n):
+            raw = capi.MisFeatures()
+            C.memmove(C.byref(raw), C.byref(raws[k]), C.sizeof(capi.MisFeatures))
+            out.append(ImageFeatures(self.ctx, raw))
+        return out
+
+    def debug_level(self, level, which):
+        """Plane `which` ("Lt", "Lsmooth", "flow", "Lx", "Ly", "Ldet") of a level of the last detect, (h, w) f32."""
+        k = self.PLANES[which] if isinstance(which, str) else int(which)
+        w, h = C.c_int(), C.c_int()
+        self.ctx.check(self.ctx.lib.mis_akaze_debug_level(self.h, int(level), k, None, C.byref(w), C.byref(h)))
+        out = np.zeros((h.value, w.value), np.float32)
+        self.ctx.check(self.ctx.lib.mis_akaze_debug_level(self.h, int(level), k, out.ctypes.data_as(C.c_void_p), C.byref(w), C.byref(h)))
+        return out
+
+    def debug_counts(self):
+        """Counters of the last detect(): dict(candidates, suppressed, refined, kcontrast)."""
+        c = (C.c_uint * 4)()
+        self.ctx.check(self.ctx.lib.mis_akaze_debug_counts(self.h, c))
+        return dict(candidates=int(c[0]), suppressed=int(c[1]), refined=int(c[2]), kcontrast=float(np.array([c[3]], np.uint32).view(np.float32)[0]))
+
+    def debug_class_ids(self, n):
+        """The levels (cv::KeyPoint::class_id) of the last detect's n keypoints."""
+        out = np.zeros(max(int(n), 1), np.int32)
+        self.ctx.check(self.ctx.lib.mis_akaze_debug_class_ids(self.h, out.ctypes.data_as(C.POINTER(C.c_int)), len(out)))
+        return out[:n]
+
+    def debug_fed(self, level):
+        """The reordered FED steps into a level (empty for level 0), f32."""
+        n = C.c_int()
+        self.ctx.check(self.ctx.lib.mis_akaze_debug_fed(self.h, int(level), None, C.byref(n)))
+        out = np.zeros(max(n.value, 1), np.float32)
+        self.ctx.check(self.ctx.lib.mis_akaze_debug_fed(self.h, int(level), out.ctypes.data_as(C.POINTER(C.c_float)), C.byref(n)))
+        return out[:n.value]
 
 
 def computeImageFeatures(finder, img, img_idx=0):

@@ -28,7 +28,7 @@ from .blenders import Blender, FeatherBlender, MultiBandBlender, blend_config, m
 from .timelapse import (TIMELAPSE_TYPES, Timelapser, check_timelapse_config, result_roi_intersection, timelapse_kind, timelapse_warp_batch,
                         timelapse_warp_batch_timed)
 from .cropper import crop_device, crop_rect_device
-from .features import KP_DTYPE, ImageFeatures, OrbFeatureFinder, SiftFeatureFinder, computeImageFeatures, features_array, orb_params
+from .features import KP_DTYPE, AkazeFeatureFinder, ImageFeatures, OrbFeatureFinder, SiftFeatureFinder, computeImageFeatures, features_array, orb_params
 from .matchers import (DMATCH_DTYPE, MATCHER_TYPES, AffineBestOf2NearestMatcher, BestOf2NearestMatcher, BestOf2NearestRangeMatcher,
                        MatchesInfo, PairwiseMatches, _require_matches, _unpack_mi, check_matcher_config, check_range_config,
                        estimate_affine_partial, find_homography, leaveBiggestComponent, leaveBiggestComponentConf, match_params,
@@ -140,7 +140,9 @@ def scaled_camera(cam, aspect):
 class StitchConfig:
     """The reference's globals-as-config (image_stitching.cpp:49-85), same defaults; compose_megapix
     <= 0 keeps frames at full resolution through warp + blend (the throughput configuration).  work_megapix >= 0: features,
-    matching and bundle adjustment at work scale (:589-603); the cameras a caller passes are always in full-resolution pixels."""
+    matching and bundle adjustment at work scale (:589-603); the cameras a caller passes are always in full-resolution pixels.
+    match_conf is the caller's: 0.32 is this package's default (ORB), and 0.65 is the reference's value for every non-ORB
+    features_type (:59) -- pass it with features_type "akaze"."""
     work_megapix: float = -1
     seam_megapix: float = 0.1
     compose_megapix: float = 0.4
@@ -204,7 +206,8 @@ class Stitcher:
         self.frame_size = frame_size
         # features come from the work image (image_stitching.cpp:602, :613): the finder is sized for it
         self.work_scale, self.work_size = work_geometry(self.cfg, frame_size)
-        self.finder = OrbFeatureFinder(ctx, self.work_size)
+        # (:547-550: AKAZE, 61-byte descriptors -> the wide Hamming 2-NN; every other value: the ORB finder)
+        self.finder = AkazeFeatureFinder(ctx, self.work_size) if self.cfg.features_type == "akaze" else OrbFeatureFinder(ctx, self.work_size)
         self.matcher = make_matcher(ctx, self.cfg)
         self.seam_finder = None       # set_seam_finder
         self.estimator = None         # set_estimator: None = the caller supplies the cameras

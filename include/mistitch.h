@@ -244,7 +244,10 @@ long long mis_debug_knn_ahead_adopted(MisContext* ctx);
  * null pointer, a count below 0 or above its capacity; where the finder would enqueue nothing, so does this, and returns MIS_OK. */
 int mis_debug_knn_ahead(MisContext* ctx, MisFeatures* feats, int n, const int* counts, const uint8_t* mask, int range_width, int rank,
                         int world);
-/* exact 2-NN (distance, trainIdx) for one direction; results in host memory (stage test hook) */
+/* exact 2-NN (distance, trainIdx) for one direction; results in host memory (stage test hook).  Binary sets are 32 bytes wide
+ * (ORB) or 61 (AKAZE's 486-bit MLDB, the last byte's top two bits clear): the matcher entries above and this one take either, and
+ * every set of a call must have one width (MIS_E_INVALID otherwise).  61-byte sets run a vector-pipe kernel of their own; the
+ * 32-byte kernels and their selection do not see them. */
 int mis_knn2(MisContext* ctx, const MisFeatures* query, const MisFeatures* train, int* idx2_host, float* dist2_host);
 /* cv::findHomography(src, dst, mask, RANSAC, thresh, max_iters, confidence) on host point lists */
 int mis_find_homography(MisContext* ctx, const float* src_xy, const float* dst_xy, int n, double thresh, int max_iters,
@@ -468,6 +471,38 @@ int mis_sift_detect_batch(MisSift* sift, const MisImage* bgr, int n_images, MisF
 int mis_sift_debug_level(MisSift* sift, const MisImage* bgr, int octave, int layer, int dog, float* host_out, int* width, int* height);
 /* counters of this finder's last mis_sift_detect: extrema candidates, raw keypoints, keypoints after duplicate removal, refined candidates */
 int mis_sift_debug_counts(MisSift* sift, unsigned* counts4);
+
+/* ---------------------------------------------------------------- AKAZE --------------------- */
+/* AKAZE::create() -- replaces image_stitching/image_stitching.cpp:547-550 (features_type == "akaze").  The definition is SURVEY
+ * Appendix A.19.  Defaults: threshold 0.001, 4 octaves, 4 layers an octave, max_points -1 (all; > 0: the max_points keypoints of
+ * highest response), the rotation-invariant MLDB descriptor at full size (486 bits in 61 bytes) over 3 channels, PM-G2
+ * diffusivity.  Every other descriptor kind, size, channel count or diffusivity: MIS_E_UNSUPPORTED.  1 .. 6 octaves, 1 .. 8 layers,
+ * at most 32 levels. */
+enum { MIS_AKAZE_DESCRIPTOR_KAZE_UPRIGHT = 2, MIS_AKAZE_DESCRIPTOR_KAZE = 3, MIS_AKAZE_DESCRIPTOR_MLDB_UPRIGHT = 4, MIS_AKAZE_DESCRIPTOR_MLDB = 5 };
+enum { MIS_AKAZE_DIFF_PM_G1 = 0, MIS_AKAZE_DIFF_PM_G2 = 1, MIS_AKAZE_DIFF_WEICKERT = 2, MIS_AKAZE_DIFF_CHARBONNIER = 3 };
+typedef struct {
+    float threshold;
+    int n_octaves, n_octave_layers, max_points;
+    int descriptor_type, descriptor_size, descriptor_channels, diffusivity;
+} MisAkazeParams;
+typedef struct MisAkaze MisAkaze;
+void mis_akaze_default_params(MisAkazeParams* p);       /* image_stitching.cpp:547-550 */
+int mis_akaze_create(MisContext* ctx, const MisAkazeParams* params /* NULL = defaults */, int max_width, int max_height, MisAkaze** out);   /* :547-550 */
+int mis_akaze_destroy(MisAkaze* akaze);                 /* :547-550 (the finder's lifetime) */
+/* computeImageFeatures(finder, img, features) -- :613 for the finder of :547-550: keypoints in (level, y, x) order, descriptors
+ * n x 61 MIS_U8 (the top two bits of byte 60 are 0).  A frame with more candidates than the finder's capacity (one per 32 pixels,
+ * at least 16384) is refused with MIS_E_OVERFLOW and the count, never truncated. */
+int mis_akaze_detect(MisAkaze* akaze, const MisImage* bgr, MisFeatures* out);
+/* n frames, one after the other (:547-550, :613-614): out[i].img_idx = i */
+int mis_akaze_detect_batch(MisAkaze* akaze, const MisImage* bgr, int n_images, MisFeatures* out);
+/* test aids of the finder of :547-550, all about its LAST detect.  debug_level: plane `which` (0 Lt, 1 Lsmooth, 2 flow, 3 Lx, 4 Ly,
+ * 5 Ldet) of a level, copied to host_out (may be NULL: only the size).  debug_counts: candidates, after suppression, after
+ * refinement, the k-contrast's float bits.  debug_class_ids: the keypoints' levels (cv::KeyPoint::class_id, which MisKeyPoint does
+ * not carry).  debug_fed: the reordered FED steps into a level (taus may be NULL; level 0 has none). */
+int mis_akaze_debug_level(MisAkaze* akaze, int level, int which, float* host_out, int* width, int* height);
+int mis_akaze_debug_counts(MisAkaze* akaze, unsigned* counts4);
+int mis_akaze_debug_class_ids(MisAkaze* akaze, int* host_out, int capacity);
+int mis_akaze_debug_fed(MisAkaze* akaze, int level, float* taus, int* n);
 
 /* ---------------------------------------------------------------- image operators ----------- */
 /* cv::resize(src, dst, dsize, fx, fy, INTER_LINEAR_EXACT) -- replaces image_stitching.cpp:580 (work scale), :619 (seam
